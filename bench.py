@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the ssa-gym hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--objects M] [--propagator fg|elements]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--objects M] [--propagator fg|elements] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one call of the reference's SSA_Tasker_Env.step() (ssa_tasker_simple_2.py:243-367)
@@ -15,6 +15,8 @@ Farnocchia; the "J2 on" of that config has no counterpart in the reference -- SU
 N>1: BASELINE config 4 -- one env of N x 20 000 objects sharded 20k per GPU, with one RCCL
 all-gather per step reassembling the global (az, el, range, trace P) observation vector and the
 reward statistics (parallel.py).  `value` = 20 000-object env-steps per second summed over GPUs.
+
+`value` and `ms_per_step` time exactly the K steps after the warm-up, between two fences.
 
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (the fused step kernel)
 against HBM; `cpu_baseline` times the single-threaded C oracle (a port of the reference's
@@ -138,6 +140,40 @@ def episode_groups(steps_per_block, episode=479):
 def spread(K, scale, med, lo, hi, reps):
     """fields every leg reports next to its rate: repeats and the min / max rate over them"""
     return {"repeats": reps, "value_spread": [round(K / hi * scale, 2), round(K / lo * scale, 2)]}
+
+
+DUMP_BYTES_MAX = 64 * 10 ** 6     # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, eng, slot):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the history slot that step wrote (one env),
+    with the objects numbered as the caller numbers them -- as float64 DIR/<name>.npy:
+        x_true, x_filter [m][6], P_filter [m][6][6], obs [m][12], delta_pos, delta_vel, status [m] (the metrics rows the
+                   statistics read; sigma_pos / sigma_vel, sqrt of P_filter's diagonal-block sums, are NaN -- as in the reference --
+                   once a diverging filter's covariance turns indefinite, and add nothing to P_filter),
+        stats [4]: max delta_pos, count(delta_pos < 1e4), count(delta_pos < 1e7), failed filters -- the statistics this path
+                   computes (its launches leave the arg-max / max of sigma_pos out: -1 / NaN placeholders, include/ssa_hip.h),
+        upd [57]: the update record up to SSA_UPD_ACTION (the words after it are padding).
+    When the per-object arrays would exceed DUMP_BYTES_MAX, a fixed sample of the objects (seed 0) is written instead, and
+    sample_rows.npy holds the caller's indices of the rows kept."""
+    import torch
+    from ssa_gym_amd import _lib
+    rows = {"x_true": eng.x_true[slot], "x_filter": eng.x_filter[slot], "P_filter": eng.P_filter[slot], "obs": eng.obs[slot],
+            "delta_pos": eng.metrics[slot, 0, 0], "delta_vel": eng.metrics[slot, 0, 1], "status": eng.status}
+    rows = {k: eng.caller_rows(v) for k, v in rows.items()}
+    stat_idx = [_lib.STAT_MAX_DPOS, _lib.STAT_CNT_LT_1E4, _lib.STAT_CNT_LT_1E7, _lib.STAT_N_FAILED]
+    whole = {"stats": eng.stats[slot, 0, stat_idx], "upd": eng.upd[slot, 0, :_lib.UPD_ACTION + 1]}
+    m = eng.m
+    row_bytes = sum(8 * v[0].numel() for v in rows.values())
+    room = DUMP_BYTES_MAX - sum(8 * v.numel() for v in whole.values()) - 128 * (len(rows) + len(whole) + 1)   # (.npy headers)
+    if m * row_bytes > room:
+        keep = np.sort(np.random.RandomState(0).choice(m, room // (row_bytes + 8), replace=False))
+        sel = torch.as_tensor(keep, device=eng.dev)
+        rows = {k: v.index_select(0, sel) for k, v in rows.items()}
+        whole["sample_rows"] = torch.as_tensor(keep.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in list(rows.items()) + list(whole.items()):
+        np.save(os.path.join(out_dir, name + ".npy"), v.to(torch.float64).contiguous().cpu().numpy())
 
 
 def cpu_baseline(m, budget_s=15.0, all_cores=False):
@@ -583,7 +619,11 @@ def main():
     ap.add_argument("--eager-sharded", action="store_true",
                     help="sharded runs: enqueue every step from the host (default: hipGraph replay of whole units of steps)")
     ap.add_argument("--no-legs", action="store_true", help="skip the additional N=1 legs (j2, elements, resample, gym_api, closed_loop)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or "RANK" in os.environ):
+        ap.error("--dump-outputs: single-process runs only (--gpus 1, no torch.distributed launcher)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -696,6 +736,11 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
+    # (as in timed_repeats: no full collection of the set-up's objects inside the timed region.  Collected BEFORE the warm-up: the
+    # ~50 ms collection right before the timed region left the card idle, and a 20-step region then read 22 us per step instead of 16)
+    gc.collect()
+    gc.freeze()
+
     # Where the all-gather runs is chosen during the warm-up, by measurement, identically on every rank: in the
     # compute stream (the global observation of step k is complete before step k+1 starts: what a closed-loop
     # agent needs), or on a communication stream so that RCCL moves step k's payload over xGMI while step k+1
@@ -805,9 +850,8 @@ def main():
         local.reset_episode(snap, ep_len)
         state["i"] = 0
         fence()
-    # The timed block: EXACTLY K steps between two fences (barrier + synchronize), MAX over ranks.  The driver's K = 20 makes
-    # that block 0.3 ms, so it is repeated (same K, same fences) until the blocks add up to 50 ms and `value` is the MEDIAN
-    # block; min / max go into `value_spread`.
+    # The timed region: EXACTLY K steps between two fences (barrier + synchronize), MAX over ranks, timed once; an episode that ends
+    # inside it is reset there, as in a caller's run.  `ms_per_step` = its time / K (callers size K for later measurements by it).
     def max_over_ranks(v):
         if not use_dist:
             return v
@@ -827,8 +871,13 @@ def main():
             return
         for k in range(W, W + K):
             one_step(k)
-    elapsed, el_min, el_max, repeats = timed_repeats(timed_block_graph if graphed is not None else timed_block, fence, agree=max_over_ranks,
-                                                         group=episode_groups(K))
+    fence()
+    t0 = time.perf_counter()
+    (timed_block_graph if graphed is not None else timed_block)()
+    fence()
+    elapsed = max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, local.tick % eng.H)
 
     # sanity: nothing diverged during the run
     n_failed = int((eng.status != 0).sum().item())
@@ -983,8 +1032,8 @@ def main():
             "metric": "env_steps_per_sec_at_20k_objects", "value": round(value, 2),
             "unit": "env-steps/s (20 000-object UKF+propagate steps, summed over GPUs)",
             "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(1e3 * elapsed / K, 5),
-            "repeats": repeats, "value_spread": [round(K / el_max * world * (m / 20000.0), 2), round(K / el_min * world * (m / 20000.0), 2)],
-            "timing": "`repeats` timed blocks of exactly `steps` steps, each between two fences (repeated until >= 50 ms in total and at least three whole episodes); value = the median over episode-long groups of consecutive blocks of the mean block inside each group",
+            "timing": "one timed region of exactly `steps` steps between two fences (episodes of 479 steps, reset inside the region); "
+                      "value = steps / its time",
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": "ssa_tasker_simple-v2 hot path: %d objects/GPU x %d GPU, %s + "
                                    "UKF predict (13 sigma points) + 1 az-el-range update/step%s" %
