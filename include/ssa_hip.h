@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SSA_ABI_VERSION 22
+#define SSA_ABI_VERSION 23
 #define SSA_INLINE_ENVS 8
 
 /* error codes */
@@ -470,6 +470,36 @@ typedef struct ssa_closed_loop_params {
                                      give-up path (tests/test_env_gpu.py): the grid must drain, `error` must be set, later launches must work */
 int ssa_env_closed_loop_f64(const ssa_consts *c_host, const ssa_step_params *first, const ssa_closed_loop_params *r, void *stream);
 int64_t ssa_closed_loop_workspace_bytes(int64_t n_obj, int32_t n_env);
+
+/* ---------------------------------------------------------------- one-step tasking lookahead
+ * From the state a step would start from (ssa_step_params inputs: slot i), for EVERY object j of every env what the step at i + 1
+ * would produce for j if the env's action were j -- the prior, the covariance after the hypothetical update and the gains of the
+ * classic sensor-tasking baselines -- in one launch of the step kernel's own predict / update code (nothing committed).  The UKF
+ * update's covariance P+ = P- - K S K^T does not depend on the measured value, so no measurement noise is involved: z_noise is never
+ * read, and nothing returned depends on it (no x+, no innovation).  Bit-identical to the step: x_prior / P_prior to what
+ * ssa_env_step_f64 leaves for any object it does not update, P_post to P_out[j] of a step whose action is j, status / visible to that
+ * step's status word and SSA_UPD_VISIBLE -- for every propagator, observation type, SSA_FLAG_RESAMPLE and SSA_FLAG_REFERENCE_COV.
+ * Cost: every wavefront runs four updates where a step runs at most one per env. */
+#define SSA_LOOK_NSCORE 3
+#define SSA_LOOK_TRACE_GAIN 0     /* tr P- - tr P+ (agent_visible_greedy's trace, agents.py:36) */
+#define SSA_LOOK_POS_TRACE_GAIN 1 /* the same over the 3x3 position block */
+#define SSA_LOOK_INFO_GAIN 2      /* expected information gain 1/2 (ln det P- - ln det P+), both log-dets through the Cholesky factor */
+typedef struct ssa_lookahead_out {
+    double *score;     /* [E*m][SSA_LOOK_NSCORE], required.  NaN unless status == SSA_ST_OK and visible */
+    int32_t *status;   /* [E*m], required: the SSA_ST_* code object j would carry after the step that updates it -- an earlier failure,
+                          SSA_ST_PREDICT_NAN / SSA_ST_PREDICT_LINALG of this predict, SSA_ST_UPDATE_LINALG (singular S).  SSA_ST_UPDATE_NAN
+                          is NOT foreseen: it comes from x+, which depends on the drawn measurement noise */
+    uint8_t *visible;  /* [E*m], required: the update's visibility test (elevation of the true state at i + 1, ssa_tasker_simple_2.py:418-425);
+                          0 where the update would not be attempted (a failed filter, a step the update_interval skips) */
+    double *x_prior;   /* [E*m][6] or NULL */
+    double *P_prior;   /* [E*m][36] or NULL */
+    double *P_post;    /* [E*m][36] or NULL: P- where the update would not run, the failure sentinel where S is singular */
+} ssa_lookahead_out;
+/* Reads only the INPUT fields of ssa_step_params: n_obj, n_env, time_offset, x_true_in, x_in, P_in, status, trans, env_time, n_time,
+ * obj_ids and -- the only launch_mask bit honoured -- SSA_LAUNCH_INLINE_ENVS with inline_time.  None of its output pointers is touched,
+ * nor actions / z_noise: no history slot, status word, failure record, update record or statistics word is written.  Output row of an
+ * object = e * n_obj + its index as the caller numbers it (obj_ids, as obs_mirror / aer_out): a storage layout never shows. */
+int ssa_lookahead_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_lookahead_out *out, void *stream);
 
 /* ------------------------------------------------ all-gather by direct peer stores (SURVEY 8e "Collective")
  * The reference runs one env per process and has no exchange step; the sharded env of this library (one env's objects spread over the

@@ -59,9 +59,15 @@ class ssa_closed_loop_params(C.Structure):
     ]
 
 
+class ssa_lookahead_out(C.Structure):
+    _fields_ = [
+        ("score", c_dp), ("status", c_dp), ("visible", c_dp), ("x_prior", c_dp), ("P_prior", c_dp), ("P_post", c_dp),
+    ]
+
+
 # constants of include/ssa_hip.h
 E_INVALID, E_LAUNCH, E_UNSUPPORTED = -1, -2, -3
-ABI_VERSION = 22
+ABI_VERSION = 23
 ST_OK, ST_PREDICT_NAN, ST_PREDICT_LINALG, ST_UPDATE_NAN, ST_UPDATE_LINALG = range(5)
 OBS_AER, OBS_XYZ = 0, 1
 PROP_ELEMENTS, PROP_FG, PROP_J2_RK4, PROP_HYBRID = 0, 1, 2, 3
@@ -80,6 +86,7 @@ INLINE_ENVS = 8
 LOOP_ARGMAX_SPOS, LOOP_DEBUG_WITHHOLD = 1, 2
 FAIL_STRIDE, FAIL_ENV, FAIL_OBJ, FAIL_STATUS, FAIL_TIME, FAIL_ERR = 8, 0, 1, 2, 3, 4
 AGENT_NAIVE_GREEDY, AGENT_VISIBLE_GREEDY, AGENT_SHANNON, AGENT_POS_ERROR, AGENT_VEL_ERROR = range(5)
+LOOK_NSCORE, LOOK_TRACE_GAIN, LOOK_POS_TRACE_GAIN, LOOK_INFO_GAIN = 3, 0, 1, 2
 STAT_STRIDE, STAT_MAX_DPOS, STAT_CNT_LT_1E4, STAT_CNT_LT_1E7, STAT_ARGMAX_SPOS, STAT_N_FAILED, STAT_MAX_SPOS = 8, 0, 1, 2, 3, 4, 5
 
 # every symbol the header declares, with its ctypes signature
@@ -94,6 +101,7 @@ SIGNATURES = {
     "ssa_ladder_probe_f64": (C.c_int, [c_dp, C.c_double, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_env_rollout_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_rollout_params), c_dp]),
     "ssa_env_closed_loop_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_closed_loop_params), c_dp]),
+    "ssa_lookahead_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_lookahead_out), c_dp]),
     "ssa_closed_loop_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
     "ssa_env_step_work_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
     "ssa_reward_stats_f64": (C.c_int, [c_dp, c_dp, c_dp, c_dp, C.c_int64, C.c_int32, c_dp]),

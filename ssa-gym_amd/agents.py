@@ -9,6 +9,8 @@ Deviation: objects whose score is NaN (non positive definite covariance in the S
 skipped by the arg-max; numpy's argmax would return the first NaN's index."""
 import numpy as np
 
+from . import _lib
+
 
 def _scores(env):
     """(scores[4, m], mask[m]) on the device for the env's current step."""
@@ -61,3 +63,32 @@ def agent_pos_error_greedy(obs, env):           # agents.py:66
 
 def agent_vel_error_greedy(obs, env):           # agents.py:75
     return _pick(env, 3)
+
+
+# ---- one-step lookahead agents (no reference counterpart): the standard SSA tasking baseline -- task the object whose observation
+# would shrink its uncertainty most -- from env.lookahead(): every object's hypothetical update in one launch, then ONE masked arg-max
+# over the score column (NaN = not visible / failed, skipped), 16 bytes to the host.  run_agent has no persistent form of these.
+def _column_mask(env, k, n):
+    """uint8 mask over the [m][3] score rows that selects column k (built once per env)"""
+    import torch
+    cache = env.__dict__.setdefault("_look_cols", {})
+    if (k, n) not in cache:
+        msk = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        msk[k::3] = 1
+        cache[(k, n)] = msk
+    return cache[(k, n)]
+
+
+def _pick_lookahead(env, k):
+    from . import device
+    flat = env.lookahead()["score"].t().reshape(-1)      # (the engine's [m][3] rows: a view, no copy)
+    j = device.masked_argmax(flat, _column_mask(env, k, flat.shape[0]))
+    return j // _lib.LOOK_NSCORE if j >= 0 else env.action_space.sample()
+
+
+def agent_info_gain(obs, env):                  # argmax 1/2 ln(det P- / det P+) over the objects an update would reach
+    return _pick_lookahead(env, _lib.LOOK_INFO_GAIN)
+
+
+def agent_trace_gain(obs, env):                 # argmax tr P- - tr P+ over the objects an update would reach
+    return _pick_lookahead(env, _lib.LOOK_TRACE_GAIN)

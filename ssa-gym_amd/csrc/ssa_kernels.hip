@@ -1105,6 +1105,69 @@ struct ActLate {
         return (int)lo;
     }
 };
+// ActAll (lookahead_kernel, ssa_lookahead_f64): EVERY row is "selected" -- the update's covariance of every object as if the action
+// had chosen it (P+ = P- - K S K^T does not depend on the measured value), nothing committed.  The update block then runs Phase 1 in
+// all four rows at once and Phase 2 in four turns; the outputs go to `o` at the caller's rows, the measurement noise is never read,
+// and no history slot, status word, failure record, update record or statistics word is written.
+struct ActAll {
+    static constexpr bool late = false;
+    const ssa_lookahead_out* o;
+    SSA_DEV int get() { return -1; }
+    SSA_DEV void before_wait(Tiles&, int, int) {}
+    SSA_DEV void mid_step(Tiles&, int) {}
+};
+template <class ACT> struct ActIsAll { static constexpr bool v = false; };
+template <> struct ActIsAll<ActAll> { static constexpr bool v = true; };
+SSA_DEV double logdet_chol(const double (&A)[21]);   // (defined with the agents' scores)
+// the lookahead's outputs of row g (lane l of it) at the caller's row `orow`.  P- / x- are the tile after the predict and the
+// failure sentinels (what a step leaves for an object it does not update); P+ (row g's turn of Phase 2, left at t.UA[g * 117]) where
+// the update ran, the sentinel where S was singular, P- otherwise.  The scores: one lane per object, log-dets by logdet_chol.
+SSA_DEV void lookahead_store(const Tiles& t, const ssa_lookahead_out& o, int g, int l, int64_t orow, int st, bool vis, bool taken)
+{
+    const double* Pm = &t.P[g * 36];
+    const double* Pp = &t.UA[g * 117];
+    const bool lin = st == SSA_ST_UPDATE_LINALG;
+    for (int idx = l; idx < 36; idx += 16) {
+        const int a = idx / 6, b = idx - 6 * a;
+        const double pm = Pm[idx];
+        const double pp = taken ? Pp[idx] : (lin ? ((a == b) ? (a < 3 ? X_FAILED_POS : X_FAILED_VEL) : 0.0) : pm);
+        if (o.P_prior) o.P_prior[orow * 36 + idx] = pm;
+        if (o.P_post) o.P_post[orow * 36 + idx] = pp;
+    }
+    if (o.x_prior && l < 6) o.x_prior[orow * 6 + l] = t.X[g * 6 + l];
+    // the two log-dets in two lanes of the row (lane 0: P-, lane 1: P+): one factorisation's registers at a time
+    double ld = 0.0;
+    if (taken && l < 2) {   // (status OK and visible: exactly the rows whose update ran)
+        const double* src = (l == 0) ? Pm : Pp;
+        double A[21];
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = r; c < 6; ++c) A[tri(r, c)] = src[r * 6 + c];
+        ld = logdet_chol(A);
+    }
+    const double ld_post = __shfl_down(ld, 1, 64);
+    if (l == 0) {
+        const double nan = __builtin_nan("");
+        double sc[SSA_LOOK_NSCORE] = {nan, nan, nan};
+        if (taken) {
+            double trm = 0.0, trp = 0.0, pos_m = 0.0, pos_p = 0.0;
+#pragma unroll
+            for (int r = 0; r < 6; ++r) {
+                trm += Pm[7 * r];
+                trp += Pp[7 * r];
+                if (r == 2) { pos_m = trm; pos_p = trp; }
+            }
+            sc[SSA_LOOK_TRACE_GAIN] = trm - trp;
+            sc[SSA_LOOK_POS_TRACE_GAIN] = pos_m - pos_p;
+            sc[SSA_LOOK_INFO_GAIN] = 0.5 * (ld - ld_post);
+        }
+#pragma unroll
+        for (int k = 0; k < SSA_LOOK_NSCORE; ++k) o.score[orow * SSA_LOOK_NSCORE + k] = sc[k];
+        o.status[orow] = st;
+        o.visible[orow] = vis ? 1 : 0;
+    }
+}
 
 template <int PROP, int TILE, class ACT>
 SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& p, int lane, int64_t obj_in, bool valid,
@@ -1119,13 +1182,14 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // a grid-stride launch end together, and the 128 shard-complete increments per env land on ONE word one after the other -- the vector
     // env's step 123.9 -> 130.4 us although its host side got 4 us shorter.)
     constexpr bool FOLD_OK = (TILE == 0);
+    constexpr bool ALL = ActIsAll<ACT>::v;   // the lookahead: every row updated hypothetically, nothing committed (ActAll)
     int g = lane >> 4, l = lane & 15;
     int64_t obj = obj_in;
     // (TILE 0: the kernel issued the tile's loads from its preloaded pointer arguments before anything else.)  First thing here,
     // so that these scalar loads complete with the action / time words' below -- placed behind the wait for the tile they
     // put one more scalar-memory round trip between the tile's arrival and its commit to LDS
 #ifndef SSA_NO_EARLY_ARGS
-    if (TILE == 0) {
+    if (TILE == 0 && !ALL) {
         // the epilogue's output pointers are fetched NOW: their scalar loads (kernarg segment) overlap the tile's HBM round
         // trip instead of each adding a scalar-memory round trip to the store path of a latency-bound wavefront
         asm volatile("" ::"s"(p.P_out), "s"(p.x_out), "s"(p.x_true_out), "s"(p.obs), "s"(p.metrics), "s"(p.stat_shards), "s"(p.upd),
@@ -1142,6 +1206,9 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     if (ACT::late) {   // (one env; the action arrives behind the predict)
         act = -1;
         tix = valid ? p.env_time[0] + p.time_offset : 0;
+    } else if (ALL) {   // (no action: every row is selected)
+        act = -1;
+        tix = valid ? env_time_of<INL>(p, e) + p.time_offset : 0;
     } else if (p.n_env > 1) {
         act = valid ? env_action<INL>(p, e) : -1;
         tix = valid ? env_time_of<INL>(p, e) + p.time_offset : 0;
@@ -1165,15 +1232,15 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         jid = valid ? (int64_t)mine : 0;
         if (l == 0) t.Oid[g] = mine;
     }
-    bool my_update = !ACT::late && valid && act >= 0 && (int64_t)act == jid && interval_ok;
+    bool my_update = ALL ? (valid && interval_ok) : (!ACT::late && valid && act >= 0 && (int64_t)act == jid && interval_ok);
     // (ActLate: every row prefetches for its own object)
     const bool may_update = ACT::late ? (valid && interval_ok) : my_update;
     // ... and it issues ahead of its SIMD's other wavefronts from here on: at equal priority its predict runs at a fifth of the
     // SIMD and the update then starts when everybody else is finishing (the kernel's tail)
-    if (!ACT::late && __any(my_update)) __builtin_amdgcn_s_setprio(3);
+    if (!ACT::late && !ALL && __any(my_update)) __builtin_amdgcn_s_setprio(3);
     int tmod = 0;                                           // row of `trans` / `z_noise` (episodes wrap)
     double upd_in = 0.0;
-    if (may_update && l < 12) {
+    if (may_update && l < (ALL ? 9 : 12)) {   // (ActAll: the matrix only -- the noise slots stay zero, z_noise is never read)
         tmod = time_row(tix, p.n_time);
         const int64_t aobj = ACT::late ? jid : (int64_t)act;   // (the measurement noise is indexed as the caller numbers the objects)
         const double* src = (l < 9) ? p.trans + (int64_t)tmod * 9 + l
@@ -1379,6 +1446,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         wave_lds_sync();
         if (active && st_new == SSA_ST_OK && rg == 16) st_new = SSA_ST_PREDICT_LINALG;
     }
+    const int st_pred = st_new;   // (ActAll: the tile keeps the predict's outcome; a singular S shows in the outputs only)
 
     // ---- U5: the one update of this env (ssa_tasker_simple_2.py:292-315) for the selected object.
     // Phase 1 (row-local, lanes of the selected object's row): measurement of the sigma points, predicted measurement,
@@ -1391,6 +1459,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         my_update = valid && act >= 0 && (int64_t)act == (p.obj_ids ? (int64_t)t.Oid[g] : obj) && interval_ok;   // (one env: the object index IS the index in the env)
         if (__any(my_update)) __builtin_amdgcn_s_setprio(3);
     }
+    bool look_vis = false, look_taken = false;   // (ActAll: the row's visibility and whether its update ran, for the outputs)
     if (__any(my_update)) {   // whole-wave branch: a wavefront without a selected object skips the block, its variables included
     bool upd_go = false, taken = false, visible = false, attempted = false;
     double z[3] = {0.0, 0.0, 0.0}, y_row[3] = {0.0, 0.0, 0.0};   // (y_row: lane 13 of the row keeps the innovation)
@@ -1402,7 +1471,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     static_assert(offsetof(Tiles, D) == offsetof(Tiles, UA) + sizeof(double) * OBJ_PER_WAVE * 36, "UA and D contiguous");
     static_assert(4 * 117 <= OBJ_PER_WAVE * 36 + 330 && 330 + 57 <= 408, "update staging fits");
     if (my_update) {
-        rec = p.upd ? p.upd + (int64_t)e * SSA_UPD_STRIDE : nullptr;
+        rec = (!ALL && p.upd) ? p.upd + (int64_t)e * SSA_UPD_STRIDE : nullptr;
         // a filter that has failed (earlier, or in this step's predict) is skipped entirely (:293): no z_true, no record
         attempted = (st_new == SSA_ST_OK);
         if (attempted) {
@@ -1554,6 +1623,18 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                 }
                 wave_lds_sync();
                 SSA_TR(13);
+                if constexpr (ALL) {   // P+ = P- - K S K^T into the row's consumed staging matrix; x and the tile's P stay as they are
+                    if (lane < 36) {
+                        const int a = lane / 6, b = lane - 6 * a;
+                        double corr = 0.0;
+#pragma unroll
+                        for (int u = 0; u < 3; ++u) {
+                            const double sk = W[u * 3] * W[36 + b * 3] + W[u * 3 + 1] * W[36 + b * 3 + 1] + W[u * 3 + 2] * W[36 + b * 3 + 2];  // (S K^T)[u][b]
+                            corr = fma(W[36 + a * 3 + u], sk, corr);
+                        }
+                        t.UA[gu * 117 + lane] = t.P[gu * 36 + lane] - corr;
+                    }
+                } else {
                 // x += K y  (lanes 0..5); P -= K S K^T (36 entries, one per lane)
                 double xn = 0.0;
                 if (lane < 6) xn = t.X[gu * 6 + lane] + (W[36 + lane * 3] * W[54] + W[36 + lane * 3 + 1] * W[55] + W[36 + lane * 3 + 2] * W[56]);
@@ -1569,6 +1650,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                     t.P[gu * 36 + lane] = t.P[gu * 36 + lane] - corr;
                 }
                 if (lane < 6) t.X[gu * 6 + lane] = xn;
+                }
                 SSA_TR(14);
             }
             if (g == gu) {
@@ -1594,6 +1676,10 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         rec[SSA_UPD_VISIBLE] = visible ? 1.0 : 0.0;
         rec[SSA_UPD_ACTION] = attempted ? (double)(ACT::late ? act : env_action<INL>(p, e)) : -1.0;   // (my_update: the env's action IS this object)
     }
+    if constexpr (ALL) {
+        look_vis = visible;
+        look_taken = taken;
+    }
     // The update is the register-pressure peak behind the propagator and only ONE wavefront of a launch runs it: whatever is
     // live across it would be spilled by EVERY wavefront.  So the values that are cheap to get again are got again behind
     // it: the lane coordinates, the object / env, and the next tile's loads (issued a second time).
@@ -1605,7 +1691,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     if (TILE == 1) tile_issue(pf, p, lane, next_base, next_cnt);
     }   // wavefronts holding a selected object
     // envs whose action selects nobody still get a cleared record (written by object 0's row)
-    if (valid && p.upd && obj == (int64_t)e * p.n_obj && l == 0) {   // (object 0 of an env: one lane per env)
+    if (!ALL && valid && p.upd && obj == (int64_t)e * p.n_obj && l == 0) {   // (object 0 of an env: one lane per env)
       const int a_env = ACT::late ? act : env_action<INL>(p, e);
       if (!(a_env >= 0 && interval_ok && (int64_t)a_env < p.n_obj)) {
         double* rec = p.upd + (int64_t)e * SSA_UPD_STRIDE;
@@ -1618,13 +1704,13 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // ---- F1: failed filters carry the sentinels (ssa_tasker_simple_2.py:157-158, 369-382)
     wave_lds_sync();
     SSA_TR(6);
-    if (valid && st_new != SSA_ST_OK && st_in == SSA_ST_OK) {
+    if (valid && (ALL ? st_pred : st_new) != SSA_ST_OK && st_in == SSA_ST_OK) {   // (ActAll: the predict's failures only)
         for (int idx = l; idx < 36; idx += 16) {
             int a = idx / 6, b = idx - a * 6;
             t.P[g * 36 + idx] = (a == b) ? (a < 3 ? X_FAILED_POS : X_FAILED_VEL) : 0.0;
         }
         if (l < 6) t.X[g * 6 + l] = (l < 3) ? X_FAILED_POS : X_FAILED_VEL;
-        if (p.fail_log && l == 0) {
+        if (!ALL && p.fail_log && l == 0) {
             // filter_error()'s record (:369-382): who, why, when, and error_failed() of the state the filter failed FROM (:376-378) -- the
             // step's inputs, still in HBM (a rare, row-divergent branch: three loads per failing filter)
             if (ACT::late) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the closed loop stores the previous step's tile inside this one)
@@ -1654,6 +1740,11 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     }
     if (l == 0) t.St[g] = st_new;
     wave_lds_sync();
+    if constexpr (ALL) {   // the lookahead's outputs; nothing of the step's epilogue (observation, metrics, statistics, tile store)
+        if (valid) lookahead_store(t, *asrc.o, g, l, (int64_t)e * p.n_obj + (p.obj_ids ? (int64_t)t.Oid[g] : obj - (int64_t)e * p.n_obj),
+                                   st_new, look_vis, look_taken);
+        return;
+    }
 #if !(defined(SSA_ABLATE) && (SSA_ABLATE & 16))
     observe_rows(t, g, l, cnt != OBJ_PER_WAVE);
 #endif
@@ -1910,6 +2001,59 @@ __global__ void __launch_bounds__(64, SSA_STEP_WAVES) step_fast_kernel(int ntile
         ActEarly early;
         process_wave<PROP, 1>(t, k.c, k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, nbase, ncnt, tile, early);
         wave_lds_sync();   // the tile's LDS reads (store) precede the next tile's commit
+    }
+}
+
+// The lookahead (ssa_lookahead_f64): the step kernel's launch forms with ActAll.  Same tiles, same predict and update code; the
+// outputs are the lookahead's, at the caller's rows.
+struct LookK {
+    StepK k;
+    ssa_lookahead_out o;
+};
+struct LookaheadArgs {   // the kernarg segment of lookahead_kernel (see StepFastArgs)
+    int ntiles, nwork;
+    const double *pre_P_in, *pre_x_in, *pre_x_true_in;
+    const int32_t* pre_status;
+    LookK k;
+};
+typedef const __attribute__((address_space(4))) LookK* LookKernargPtr;
+template <int PROP, bool MULTI>
+__global__ void __launch_bounds__(64, SSA_STEP_WAVES) lookahead_kernel(int ntiles, int nwork, const double* pre_P_in,
+                                                                       const double* pre_x_in, const double* pre_x_true_in,
+                                                                       const int32_t* pre_status, const LookK k_arg)
+{
+    __shared__ Tiles t;
+    int lane = threadIdx.x;
+    const int unit = (int)blockIdx.x;
+    const int64_t total = (int64_t)k_arg.k.p.n_env * k_arg.k.p.n_obj;
+    TileRegs pf;
+    int tile = xcd_tile(unit, nwork);
+    if (!MULTI) {
+        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
+        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
+        tile_dma_issue(t, pf, pre_P_in, pre_x_in, pre_x_true_in, pre_status, lane, base, cnt);
+        ActAll all{&k_arg.o};
+        process_wave<PROP, 0>(t, k_arg.k.c, k_arg.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, all);
+        return;
+    }
+    {
+        const int64_t b0 = (int64_t)tile * OBJ_PER_WAVE;
+        tile_issue(pf, k_arg.k.p, lane, b0, tile < ntiles ? (int)((total - b0) < OBJ_PER_WAVE ? (total - b0) : OBJ_PER_WAVE) : 0);
+    }
+    LookKernargPtr kp = (LookKernargPtr)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(LookaheadArgs, k));
+    for (; tile < ntiles; tile += nwork) {
+        // (as step_fast_kernel: the argument block and the lane id re-derived per tile)
+        asm volatile("" : "+s"(kp));
+        asm volatile("" : "+v"(lane));
+        const LookK& k = *(const LookK*)kp;
+        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
+        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
+        const int nt = tile + nwork;
+        const int64_t nbase = (int64_t)nt * OBJ_PER_WAVE;
+        const int ncnt = nt < ntiles ? (int)((total - nbase) < OBJ_PER_WAVE ? (total - nbase) : OBJ_PER_WAVE) : 0;
+        ActAll all{&k.o};
+        process_wave<PROP, 1>(t, k.k.c, k.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, nbase, ncnt, tile, all);
+        wave_lds_sync();   // the tile's LDS reads precede the next tile's commit
     }
 }
 
@@ -3461,6 +3605,51 @@ int ssa_env_step_profile_ms(int32_t slot, float* kernel_ms)
     if (hipEventSynchronize(g_prof_ev[slot][1]) != hipSuccess ||
         hipEventElapsedTime(kernel_ms, g_prof_ev[slot][0], g_prof_ev[slot][1]) != hipSuccess) return SSA_E_LAUNCH;
     return SSA_OK;
+}
+int ssa_lookahead_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_lookahead_out* o, void* stream)
+{
+    if (!c || !p || !o || p->n_obj <= 0 || p->n_env <= 0) return SSA_E_INVALID;
+    if (!p->x_true_in || !p->x_in || !p->P_in || !p->status || !p->trans || !p->env_time) return SSA_E_INVALID;
+    if (!o->score || !o->status || !o->visible) return SSA_E_INVALID;
+    if ((p->launch_mask & SSA_LAUNCH_INLINE_ENVS) && p->n_env > SSA_INLINE_ENVS) return SSA_E_INVALID;
+    if (p->obj_ids && p->n_env != 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // (whole tiles per env, as the step)
+    if (c->obs_type != SSA_OBS_AER && c->obs_type != SSA_OBS_XYZ) return SSA_E_INVALID;
+    if (c->propagator != SSA_PROP_FG && c->propagator != SSA_PROP_ELEMENTS && c->propagator != SSA_PROP_J2_RK4 && c->propagator != SSA_PROP_HYBRID) return SSA_E_INVALID;
+    if (c->propagator == SSA_PROP_J2_RK4 && (c->rk4_substeps < 1 || c->rk4_substeps > 4096)) return SSA_E_INVALID;
+    const int64_t total = (int64_t)p->n_env * p->n_obj;
+    if (total >= ((int64_t)1 << 31)) return SSA_E_INVALID;
+    LookK k;
+    k.k.c = *c;
+    k.k.p = *p;
+    k.o = *o;
+    // the inputs only: every output of the step -- and the action / measurement noise -- is withheld from the kernel
+    ssa_step_params& q = k.k.p;
+    q.x_true_out = nullptr; q.x_out = nullptr; q.P_out = nullptr; q.obs = nullptr; q.metrics = nullptr; q.upd = nullptr;
+    q.actions = nullptr; q.z_noise = nullptr; q.stats = nullptr; q.work = nullptr; q.stat_ws = nullptr;
+    q.stat_shards = nullptr; q.stat_shards_prev = nullptr; q.stats_prev = nullptr; q.aer_out = nullptr; q.stat_shards_clear = nullptr;
+    q.obs_mirror = nullptr; q.spos_tiles = nullptr; q.spos_tiles_prev = nullptr; q.fail_log = nullptr; q.fail_count = nullptr;
+    q.fail_cap = 0;
+    q.launch_mask = p->launch_mask & SSA_LAUNCH_INLINE_ENVS;
+    const int64_t ntiles = (total + OBJ_PER_WAVE - 1) / OBJ_PER_WAVE;
+    const int64_t slots = (int64_t)device_cu_count() * 4 * SSA_STEP_WAVES;
+    const int64_t per_wave = (ntiles + slots - 1) / slots;
+    const int nwork = (int)((ntiles + per_wave - 1) / per_wave);
+    const int nt = (int)ntiles;
+    const int prop = c->propagator;
+    dim3 grid((unsigned)nwork), block(64);
+    hipStream_t s = (hipStream_t)stream;
+    if (per_wave == 1) {
+        if (prop == SSA_PROP_FG) hipLaunchKernelGGL((lookahead_kernel<1, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        else if (prop == SSA_PROP_ELEMENTS) hipLaunchKernelGGL((lookahead_kernel<0, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        else if (prop == SSA_PROP_HYBRID) hipLaunchKernelGGL((lookahead_kernel<3, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        else hipLaunchKernelGGL((lookahead_kernel<2, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+    } else {
+        if (prop == SSA_PROP_FG) hipLaunchKernelGGL((lookahead_kernel<1, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        else if (prop == SSA_PROP_ELEMENTS) hipLaunchKernelGGL((lookahead_kernel<0, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        else if (prop == SSA_PROP_HYBRID) hipLaunchKernelGGL((lookahead_kernel<3, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        else hipLaunchKernelGGL((lookahead_kernel<2, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+    }
+    return launch_status();
 }
 int ssa_env_rollout_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, void* stream)
 {

@@ -356,6 +356,49 @@ class HotPathEngine:
             self._fold_pending = (self._shard_cur, stats_ptr, argmax)
             self._shard_cur ^= 1
 
+    LOOKAHEAD_PARTS = ("x_prior", "P_prior", "P_post")
+
+    def launch_lookahead(self, slot_in, time_offset, out=(), stream=None, env_times=None):
+        """enqueue the one-step tasking lookahead (include/ssa_hip.h: ssa_lookahead_f64) from history slot `slot_in` for the step whose
+        time index is env_time + time_offset (env_times: the envs' time words by value, n_env <= 8; else the engine's env_time0 words, as a
+        step reads them).  Nothing of the engine's state is written.  `out`: which of LOOKAHEAD_PARTS to produce besides the scores, status
+        and visibility.  Returns a dict of this engine's output tensors, rows at the caller's indices of every env: score [E*m, 3],
+        status [E*m] int32, visible [E*m] uint8 and the parts asked for (x_prior [E*m, 6], P_prior / P_post [E*m, 6, 6]) -- the buffers
+        are allocated on first use and reused by the next call.  Asynchronous, no host sync."""
+        N = self.m * self.E
+        want = tuple(out)
+        bad = [k for k in want if k not in self.LOOKAHEAD_PARTS]
+        if bad:
+            raise ValueError("launch_lookahead: unknown output(s) %s (choose from %s)" % (bad, self.LOOKAHEAD_PARTS))
+        if getattr(self, "_look", None) is None:
+            self._look = {"score": torch.empty((N, _lib.LOOK_NSCORE), dtype=f64, device=self.dev),
+                          "status": torch.empty(N, dtype=torch.int32, device=self.dev),
+                          "visible": torch.empty(N, dtype=torch.uint8, device=self.dev)}
+        shapes = {"x_prior": (N, 6), "P_prior": (N, 6, 6), "P_post": (N, 6, 6)}
+        for k in want:
+            if k not in self._look:
+                self._look[k] = torch.empty(shapes[k], dtype=f64, device=self.dev)
+        o = _lib.ssa_lookahead_out()
+        o.score, o.status, o.visible = self._look["score"].data_ptr(), self._look["status"].data_ptr(), self._look["visible"].data_ptr()
+        for k in self.LOOKAHEAD_PARTS:
+            setattr(o, k, self._look[k].data_ptr() if k in want else 0)
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        p = _lib.ssa_step_params()
+        C.memmove(C.byref(p), C.byref(self._p), C.sizeof(p))
+        sl = int(slot_in) % self.H
+        p.x_true_in, p.x_in, p.P_in = self._bx_t + sl * self._sx, self._bx + sl * self._sx, self._bP + sl * self._sP
+        p.time_offset, p.launch_mask = int(time_offset), 0
+        if env_times is not None:
+            if self.E > _lib.INLINE_ENVS:
+                raise _lib.SsaHipError("env_times: at most %d envs travel in the parameter block" % _lib.INLINE_ENVS)
+            p.inline_time[:self.E] = [int(v) for v in env_times]
+            p.launch_mask = _lib.LAUNCH_INLINE_ENVS
+        rc = self._lib.ssa_lookahead_f64(self._cref, C.byref(p), C.byref(o), s)
+        if rc:
+            raise _lib.SsaHipError("ssa_lookahead_f64 failed with code %d" % rc)
+        res = {k: self._look[k] for k in ("score", "status", "visible") + want}
+        return res
+
     def launch_rollout(self, slot_in, time_offset, actions, stream=None, argmax_spos=False):
         """K = actions.shape[0] consecutive steps in one launch (include/ssa_hip.h: ssa_env_rollout_f64): step k reads
         history slot (slot_in + k) % H, writes (slot_in + k + 1) % H and has time index time_offset + k.  `actions`

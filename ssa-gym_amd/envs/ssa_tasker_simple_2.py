@@ -1091,6 +1091,29 @@ class SSA_Tasker_Env(Env):
         P_prev = e.P_filter[prev] if self.i >= 1 else None
         return device.agent_scores(e.x_true[cur], e.x_filter[cur], e.P_filter[cur], P_prev, M, self._consts)
 
+    def lookahead(self, covariances=False):
+        """One-step tasking lookahead (no reference counterpart; include/ssa_hip.h: ssa_lookahead_f64): for EVERY object j, what step(j)
+        would produce for j at the next step, from the current state and in ONE launch -- nothing of the env changes, and nothing
+        returned depends on the measurement noise still to be drawn.  A dict of CUDA tensors, objects in the env's own order:
+            score   [3, m]  float64: rows _lib.LOOK_TRACE_GAIN (tr P- - tr P+), LOOK_POS_TRACE_GAIN (position block), LOOK_INFO_GAIN
+                            (1/2 ln(det P- / det P+)); NaN unless status == OK and visible
+            visible [m]     uint8: the update's visibility test at the next step (0 where the update would not be attempted)
+            status  [m]     int32: the SSA_ST_* code step(j) would leave on j (a NaN update, which depends on the noise, is not foreseen)
+        and with covariances=True also x_prior [m, 6], P_prior [m, 6, 6] (the prediction every object gets) and P_post [m, 6, 6] (P_filter
+        of the next step after step(j)).  The tensors are the env's lookahead buffers: the next call overwrites them."""
+        from .. import engine as _engine
+        if self._engine is None:
+            raise _lib.SsaHipError("no device state: the lookahead runs on the GPU only (no CPU fallback)")
+        if self.i + 1 >= self.n:
+            raise ValueError("lookahead: the episode has no next step (i = %d, steps = %d)" % (self.i, self.n))
+        e = self._engine
+        want = _engine.HotPathEngine.LOOKAHEAD_PARTS if covariances else ()
+        r = e.launch_lookahead(self.i % e.H, self.i + 1, out=want, stream=self._stream.cuda_stream)
+        res = {"score": r["score"].t(), "visible": r["visible"], "status": r["status"]}
+        for k in want:
+            res[k] = r[k]
+        return res
+
     def aer_obs(self, obs):
         """:834-840 -- [az, el, range, trace(P)] per object, NaN/inf -> 0.001."""
         from .. import device

@@ -249,6 +249,30 @@ class SSA_Tasker_VecEnv:
         # finite by construction -- counts of comparisons, constants -- so there is nothing for it to replace)
         return obs, rewards, dones, infos
 
+    def lookahead(self, covariances=False):
+        """SSA_Tasker_Env.lookahead() of every env from ONE launch: the same dict with a leading [n_env] axis -- score [E, 3, m],
+        visible / status [E, m], and with covariances=True x_prior [E, m, 6], P_prior / P_post [E, m, 6, 6]; objects in each env's own
+        order.  Nothing of the envs changes; the next call overwrites the tensors."""
+        import torch
+        from .. import engine as _engine
+        if np.any(self.i + 1 >= self.n):
+            raise ValueError("lookahead: an env has no next step")
+        e = self._eng
+        want = _engine.HotPathEngine.LOOKAHEAD_PARTS if covariances else ()
+        times = [int(v) + 1 for v in self.i]
+        if self._inline:
+            r = e.launch_lookahead(self.tick % 2, 0, out=want, stream=self._stream.cuda_stream, env_times=times)
+        else:     # (the time words in device memory, as a step reads them; a synchronous copy: the pinned staging is the step's)
+            e.env_time0.copy_(torch.as_tensor(times, dtype=torch.int32))
+            r = e.launch_lookahead(self.tick % 2, 0, out=want)
+        E, m = self.E, self.m
+        res = {"score": r["score"].view(E, m, _lib.LOOK_NSCORE).permute(0, 2, 1), "visible": r["visible"].view(E, m),
+               "status": r["status"].view(E, m)}
+        shapes = {"x_prior": (E, m, 6), "P_prior": (E, m, 6, 6), "P_post": (E, m, 6, 6)}
+        for k in want:
+            res[k] = r[k].view(shapes[k])
+        return res
+
     # inspection helpers (per env)
     def P_filter(self, e):
         return self._eng.env_caller_rows(e, self._eng.P_filter[self.tick % 2, e * self.m:(e + 1) * self.m]).cpu().numpy()

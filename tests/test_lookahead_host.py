@@ -1,0 +1,99 @@
+"""CPU-only checks of the one-step tasking lookahead (include/ssa_hip.h: ssa_lookahead_f64): the export, the output struct's layout
+and constants against the header, the kernel's resource budget in the shipped code object, and no CPU fallback."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import ssa_gym_amd
+    from ssa_gym_amd import _lib
+    ssa_gym_amd.build()
+    return _lib.load()
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "ssa_hip.h")).read()
+
+
+def test_lookahead_is_exported_and_declared(lib):
+    from ssa_gym_amd import _lib
+    assert re.search(r"\bssa_lookahead_f64\s*\(", _header())
+    assert "ssa_lookahead_f64" in _lib.SIGNATURES
+    assert hasattr(lib, "ssa_lookahead_f64")
+    assert lib.ssa_abi_version() == _lib.ABI_VERSION == 23
+
+
+def test_lookahead_out_layout_and_constants_match_the_header(lib, tmp_path):
+    from ssa_gym_amd import _lib
+    st = _lib.ssa_lookahead_out
+    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "ssa_hip.h"', 'int main(void){',
+           'printf("%zu\\n", sizeof(ssa_lookahead_out));']
+    want = [C.sizeof(st)]
+    for f, _ in st._fields_:
+        src.append('printf("%%zu\\n", offsetof(ssa_lookahead_out, %s));' % f)
+        want.append(getattr(st, f).offset)
+    src.append('return 0;}')
+    c = tmp_path / "look.c"
+    c.write_text("\n".join(src))
+    exe = tmp_path / "look"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(c)])
+    assert [int(v) for v in subprocess.check_output([str(exe)]).decode().split()] == want
+    hdr = _header()
+    for name in ("LOOK_NSCORE", "LOOK_TRACE_GAIN", "LOOK_POS_TRACE_GAIN", "LOOK_INFO_GAIN"):
+        m = re.search(r"#define SSA_%s\s+(\d+)" % name, hdr)
+        assert m and int(m.group(1)) == getattr(_lib, name), name
+
+
+def test_lookahead_refuses_bad_arguments_before_any_launch(lib):
+    """argument checks come first: NULL blocks / required outputs are refused with SSA_E_INVALID, no device is touched"""
+    from ssa_gym_amd import _lib
+    assert lib.ssa_lookahead_f64(None, None, None, None) == _lib.E_INVALID
+    c, p, o = _lib.ssa_consts(), _lib.ssa_step_params(), _lib.ssa_lookahead_out()
+    p.n_obj, p.n_env = 4, 1
+    p.x_true_in = p.x_in = p.P_in = p.status = p.trans = p.env_time = 16      # (never dereferenced: o.score is missing)
+    assert lib.ssa_lookahead_f64(C.byref(c), C.byref(p), C.byref(o), None) == _lib.E_INVALID
+
+
+def test_env_lookahead_has_no_cpu_fallback(lib):
+    from ssa_gym_amd import _lib
+    from ssa_gym_amd.envs.ssa_tasker_simple_2 import SSA_Tasker_Env
+    env = SSA_Tasker_Env.__new__(SSA_Tasker_Env)     # (an env without device state: what a machine without a GPU has)
+    env._engine, env.i, env.n = None, 0, 480
+    with pytest.raises(_lib.SsaHipError):
+        env.lookahead()
+
+
+def test_lookahead_kernels_keep_the_step_kernels_budget(tmp_path):
+    """the lookahead instances fit the step kernel's register budget and LDS, and touch scratch only where the step kernel does:
+    the save / restore around the out-of-line calls of SSA_PROP_ELEMENTS / SSA_PROP_HYBRID -- none on the common path"""
+    from test_abi_and_host import _code_object
+    notes, dis = _code_object(tmp_path)
+    kern = {}
+    for blk in notes.split("- .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        kern[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1)) for k in
+                      ("vgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")}
+    look = [k for k in kern if "lookahead_kernel" in k]
+    assert len(look) == 8, look                    # 4 propagators x {one tile, multi tile}
+    bodies = re.split(r"\n[0-9a-f]+ <([^>]+)>:\n", dis)
+    checked = 0
+    for name, body in zip(bodies[1::2], bodies[2::2]):
+        if "lookahead_kernel" not in name:
+            continue
+        k = kern[name]
+        assert k["vgpr_count"] <= 96 and k["group_segment_fixed_size"] <= 160 * 1024 // 20, (name, k)
+        ins = [ln.split()[0] for ln in body.splitlines() if ln.strip() and not ln.strip().startswith(("//", ";"))]
+        calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
+        stray = [i for i, op in enumerate(ins) if op.startswith("scratch_") and not (calls and min(abs(i - c) for c in calls) <= 96)]
+        assert not stray, (name, stray[:8])
+        if "ILi0E" not in name and "ILi3E" not in name:     # FG / J2: no call, no scratch at all
+            assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)
+        checked += 1
+    assert checked == 8
