@@ -21,7 +21,7 @@ def needs_build():
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in DEPS)
 
 
-def build_library(force=False, verbose=False, extra_flags=()):
+def build_library(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 -shared -fPIC -> ssa-gym_amd/libssa_hip.so"""
     if not force and not needs_build():
         return LIB
@@ -35,7 +35,7 @@ def build_library(force=False, verbose=False, extra_flags=()):
     # arguments arrive in SGPRs at wavefront launch (no scalar-memory round trip before the tile loads)
     cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=" + ARCH, "-fPIC", "-shared",
            "-ffp-contract=fast", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-kernarg-preload-count=8",
-           *extra_flags, "-o", LIB + ".tmp", SRC]
+           "-o", LIB + ".tmp", SRC]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

@@ -239,14 +239,6 @@ __device__ static void kepler_general_impl(const double* x, double tof, double* 
 // cosh in the hyperbolic Newton loop) instead of libm -- the complete restatement costs ~3 000 vector instructions per
 // call, four times the whole SSA_PROP_FG step, and late in an episode most wavefronts hold a diverged sigma point.
 // Episode-level failure statistics: as SSA_PROP_ELEMENTS / the oracle (tests/test_episode_failures.py).
-#ifdef SSA_TRACE   // (diagnostic build: which branch of the out-of-line propagation a workgroup's lanes took, and their longest Newton run)
-__device__ unsigned g_kep_dbg[16384 * 2];
-#define SSA_KEP_DBG_BRANCH(b) atomicOr(&g_kep_dbg[(blockIdx.x & 16383) * 2], (unsigned)(b))
-#define SSA_KEP_DBG_ITERS(n) atomicMax(&g_kep_dbg[(blockIdx.x & 16383) * 2 + 1], (unsigned)(n))
-#else
-#define SSA_KEP_DBG_BRANCH(b) do { } while (0)
-#define SSA_KEP_DBG_ITERS(n) do { } while (0)
-#endif
 namespace genf {
 // log x for finite x > 0 (the arguments of this path: ratios and sums of positive magnitudes; anything else takes libm):
 // x = m 2^k with m in [sqrt(1/2), sqrt 2), log m = 2 atanh(s), s = (m - 1)/(m + 1), by the fdlibm kernel polynomial; < 1 ulp,
@@ -301,8 +293,7 @@ __device__ static double newton_hyp(double x0, double M, double ecc)
         if (!done && fabs(d) < NEWTON_TOL) { res = p; done = true; }
         p0 = p;
         if (!(fabs(p0) <= 1.79769313486231570e308)) done = true;      // (inf / NaN iterate: it will never converge)
-        if (__ballot(!done) == 0ull) { SSA_KEP_DBG_ITERS(i + 1); break; }
-        if (i == 99) SSA_KEP_DBG_ITERS(100);
+        if (__ballot(!done) == 0ull) break;
         // sinh / cosh of the new iterate: by the addition formulas where the lane's step is small (all steps after the first or
         // second: the exponential of a fresh evaluation is four times as long), afresh otherwise.  The choice is the LANE's own
         // (round 3 took a wavefront-wide vote: a lane's rounding then depended on who shared its wavefront); the fresh
@@ -480,26 +471,16 @@ SSA_DEV double nu_from_delta_t_band(double delta_t, double ecc, double q)
 }  // namespace genf
 SSA_DEV double kepler_band_nu_inl(double nu, double ecc, double q, double tof)
 {
-#ifdef SSA_BAND_LIBM   // diagnostic: the libm-level restatement (what round 3 shipped)
-    const double dt0 = gen::delta_t_from_nu(nu, ecc, MU, q);
-    return gen::nu_from_delta_t(dt0 + tof, ecc, MU, q);
-#else
     const double dt0 = genf::delta_t_from_nu_band(nu, ecc, q);
     return genf::nu_from_delta_t_band(dt0 + tof, ecc, q);
-#endif
 }
 // (as a call of their own for the complete restatement's special-orientation branches: inlined there the bands pushed the whole
 // function past the step kernels' 96 registers)
 template <int TAG>
 __device__ __noinline__ double kepler_band_nu(double nu, double ecc, double q, double tof)
 {
-#ifdef SSA_BAND_LIBM   // diagnostic: the libm-level restatement (what round 3 shipped)
-    const double dt0 = gen::delta_t_from_nu(nu, ecc, MU, q);
-    return gen::nu_from_delta_t(dt0 + tof, ecc, MU, q);
-#else
     const double dt0 = genf::delta_t_from_nu_band(nu, ecc, q);
     return genf::nu_from_delta_t_band(dt0 + tof, ecc, q);
-#endif
 }
 // ---- the conic branches INLINE, for the general orientation (SSA_PROP_HYBRID's second tier; the fallback of SSA_PROP_ELEMENTS too).
 // A filter that has diverged late in a predict-mostly episode lives in the strong-hyperbolic branch (ecc > 1 + 1e-2:
@@ -537,7 +518,6 @@ SSA_DEV bool kepler_conic_lean(const double* x, double tof, double* out)
     const bool lean = (HYPER_ONLY ? (ecc > 1.0 + 1e-2) : (ecc >= 1e-8)) && (h[2] * h[2] < hh * (1.0 - 4e-15)) && (hh <= 1.79769313486231570e308) &&
                       (ecc <= 1.79769313486231570e308) && (rn > 0.0);
     if (!lean) return false;                 // (lane-divergent from here on: only the lanes that take this tier run its loops)
-#ifndef SSA_HYBRID_REFERENCE_BANDS
     // TAG 1 = SSA_PROP_HYBRID: the BANDS -- near-parabolic |ecc - 1| <= 1e-2, parabolic, elliptic beyond the series solver's domain -- go
     // through the universal-variable solver (kepler_uv_general: SSA_PROP_FG's, 1e-15 on every conic) instead of the reference's
     // near-parabolic machinery (farnocchia.py:876-908, 975-1000).  What makes the hybrid behaviour-faithful is the strong-hyperbolic
@@ -546,16 +526,14 @@ SSA_DEV bool kepler_conic_lean(const double* x, double tof, double* out)
     // ~1e-12, and the gate (tests/test_episode_failures.py) does not tell them apart.  But 2.7 % of the late-episode wavefronts hold such a
     // sigma point next to hyperbolic ones, ran this tier's hyperbolic branch AND ~1 500 dependent instructions of band arithmetic one after
     // the other, and ended every late launch 3 us behind the 99th percentile (profiles/r04_wave_timeline_hybrid_step330_layout.txt).
-    // SSA_PROP_ELEMENTS (TAG 2) and the operator kernels (TAG 0) keep the reference's bands; -DSSA_HYBRID_REFERENCE_BANDS: the hybrid too.
+    // SSA_PROP_ELEMENTS (TAG 2) and the operator kernels (TAG 0) keep the reference's bands.
     if (TAG == 1 && !HYPER_ONLY && !(ecc > 1.0 + 1e-2)) {
-        SSA_KEP_DBG_BRANCH(ecc >= 1.0 - 1e-2 ? 2 : 4);
         if (!kepler_uv_general(x, tof, out)) {       // (no convergence in 16 iterations: NaN, as the reference's newton() gives up -- farnocchia.py:353)
 #pragma unroll
             for (int c = 0; c < 6; ++c) out[c] = __builtin_nan("");
         }
         return true;
     }
-#endif
     const double a = div_fast(p, 1.0 - ecc * ecc);
     const double ka = MU * a;
     const double e_c = rn * vv * inv_mu - 1.0;                                                   // e cos E | e cosh F
@@ -575,7 +553,6 @@ SSA_DEV bool kepler_conic_lean(const double* x, double tof, double* out)
     sincos_small(nu, sn, cn);                     // (nu is wrapped)
     double nu1;
     const bool hyper = HYPER_ONLY || ecc > 1.0 + 1e-2;
-    SSA_KEP_DBG_BRANCH(hyper ? 1 : (ecc >= 1.0 - 1e-2 ? 2 : 4));   // hyperbolic | near-parabolic band | elliptic the series declined
     if (hyper) {              // the strong-hyperbolic branch (farnocchia.py:909-912, :1001-1004)
         const bool beyond = 1.0 + ecc * cn < 0.0;                                                // (:885-888: beyond the asymptote -> NaN)
         // delta_t_from_nu (:909-912): F from nu again, M = e sinh F - F
@@ -674,7 +651,6 @@ SSA_DEV Vec6 kepler_general_fast_impl(Vec6 xin, double tof)
     nu = wrap_pi(nu);
     double q = div_fast(p, 1.0 + ecc);
     double nu1;
-    SSA_KEP_DBG_BRANCH(ecc > 1.0 + 1e-2 ? 1 : (ecc >= 1.0 - 1e-2 ? 2 : 4));   // hyperbolic | near-parabolic band | elliptic the series declined
     if (ecc > 1.0 + 1e-2) {   // the strong-hyperbolic branch (farnocchia.py:909-912, :1001-1004): where a diverged filter lives
         double sn, cn;
         sincos_fast(nu, sn, cn);

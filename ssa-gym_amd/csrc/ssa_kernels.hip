@@ -200,16 +200,8 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 template <bool NT>
 SSA_DEV void store16(double* dst, const double* src)
 {
-#ifdef SSA_PLAIN_STORES   // diagnostic: never stream
-    *reinterpret_cast<v2d*>(dst) = *reinterpret_cast<const v2d*>(src);
-#else
-#ifdef SSA_NT_ALWAYS   // diagnostic: always stream
-    __builtin_nontemporal_store(*reinterpret_cast<const v2d*>(src), reinterpret_cast<v2d*>(dst));
-#else
     if (NT) __builtin_nontemporal_store(*reinterpret_cast<const v2d*>(src), reinterpret_cast<v2d*>(dst));
     else *reinterpret_cast<v2d*>(dst) = *reinterpret_cast<const v2d*>(src);
-#endif
-#endif
 }
 // first row of the env a tile belongs to (a storage layout with several envs: whole tiles per env, so the tile has ONE env)
 SSA_DEV int64_t env_row0(const ssa_step_params& p, int64_t base)
@@ -219,11 +211,7 @@ SSA_DEV int64_t env_row0(const ssa_step_params& p, int64_t base)
 template <bool NT>
 SSA_DEV void store_tile(const Tiles& t, const ssa_step_params& p, int lane, int64_t base, int cnt)
 {
-#ifdef SSA_SKIP_STORES   // diagnostic builds (write-traffic attribution): bit 1 = P, 2 = obs, 4 = x / x_true, 8 = metrics, 16 = status
-#define SSA_SKIP(b) ((SSA_SKIP_STORES) & (b))
-#else
-#define SSA_SKIP(b) 0
-#endif
+#define SSA_SKIP(b) 0   // (no store is skipped; without the ragged tile's `skip` below the multi-tile step kernel allocates its registers differently)
     if (cnt == OBJ_PER_WAVE) {
         // A whole tile (wave-uniform; every tile of a launch but a ragged last one).  Every group of lanes stores from
         // (uniform pointer) + lane x 16 bytes on both sides -- the global address in scalar-base + lane-offset form, the LDS address
@@ -333,7 +321,7 @@ SSA_DEV void observe_rows(Tiles& t, int g, int l, bool stage_obs)
 //   A^(g) = D^T D :  A[a][b] = sum_i d_i[a] d_i[b]  (a, b < 6)   and   A[a][6] = sum_i d_i[a]
 // -- 21 row reductions over the 16 lanes plus 6 more for the mean if done with DPP butterflies.  v_mfma_f64_4x4x4_4b_f64
 // multiplies four independent 4x4x4 blocks per instruction; its block index is lane bits 3:2, its k (operands) / i
-// (result) index lane bits 5:4, its i / j index lane bits 1:0 (measured, build_ablate/probe): block b = object b, three
+// (result) index lane bits 5:4, its i / j index lane bits 1:0 (measured: profiles/r02_mfma_probe.txt): block b = object b, three
 // k-chunks of four sigma points, 4x4 tiles (0,0), (0,1), (1,1) of the symmetric 8x8 result = 9 instructions of 16 cycles
 // on the otherwise idle matrix pipe, operands by six conflict-free ds_read_b64.  Lane (hi, mid, lo) ends up with
 // A^(mid)[hi][lo], A^(mid)[hi][4 + lo], A^(mid)[4 + hi][4 + lo] and KEEPS them in registers: covariance_finish() below turns
@@ -454,16 +442,12 @@ SSA_DEV StatAcc stat_wave_reduce(StatAcc a)
 // workgroup barrier.)
 SSA_DEV void wave_lds_sync()
 {
-#ifdef SSA_LDS_WAIT   // the former form: additionally drains the DS queue (not needed, see above)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
     // wavefront-scope fence: no instruction on gfx9 (the DS unit executes one wavefront's operations in
     // issue order, so a lane's read issued after another lane's write observes it); it only pins the
     // compiler's ordering of the LDS accesses around this point
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
-#endif
 }
 
 // U3, covariance in the REFERENCE's own arithmetic (SSA_FLAG_REFERENCE_COV): filterpy's unscented_transform evaluates
@@ -478,7 +462,7 @@ SSA_DEV void wave_lds_sync()
 // three 4x4 tiles of sum_i y_i (Wc_i y_i)^T, i = 0 .. 11, in three k-chunks and three vector fmas add point 12; the weight enters
 // with the right operand, as in the reference.  (What the form costs -- every wavefront of a SIMD runs this stage at the same time, so
 // its instructions add up: a vector instruction ~8 ns of a 20 000-object step, a 4x4x4 matrix instruction ~33 ns; 13.0 us per healthy
-// step against 11.9 with covariance_finish: build_ablate/healthy_phase_ab.py.)
+// step against 11.9 with covariance_finish.)
 SSA_DEV int ybase(int g) { return g * 104 + (g & 1) * 28 + (g >> 1) * 32; }   // 0, 132, 240, 372: bank slots as dbase()
 // (xb_l: lanes 0 .. 5 of a row hold component l of the row's prior mean -- the value they have just written to t.X.  The other lanes take
 // it from there by DPP row broadcasts: the detour through t.X was three dependent LDS round trips in front of the y rows' own)
@@ -489,13 +473,8 @@ SSA_DEV void covariance_reference(Tiles& t, const ssa_consts& C, int lane, const
     double* const Y = t.UA;
     {
         const int g = lane >> 4, l = lane & 15;
-#ifdef SSA_COV_MEAN_FROM_LDS   // (diagnostic: the former form)
-        const double* xb = &t.X[g * 6];
-        const double x0 = xb[0], x1 = xb[1], x2 = xb[2], x3 = xb[3], x4 = xb[4], x5 = xb[5];
-#else
         const double x0 = row_bcast<0>(xb_l), x1 = row_bcast<1>(xb_l), x2 = row_bcast<2>(xb_l), x3 = row_bcast<3>(xb_l),
                      x4 = row_bcast<4>(xb_l), x5 = row_bcast<5>(xb_l);
-#endif
         if (l <= 12) {
             v2d_t* dst = reinterpret_cast<v2d_t*>(&Y[ybase(g) + l * 8]);
             dst[0] = v2d_t{o[0] - x0, o[1] - x1};
@@ -508,11 +487,7 @@ SSA_DEV void covariance_reference(Tiles& t, const ssa_consts& C, int lane, const
     const int hi = lane >> 4, mid = (lane >> 2) & 3, lo = lane & 3;
     const double* src = &Y[ybase(mid) + hi * 8 + lo];
     Moments mo = {0.0, 0.0, 0.0};
-#ifndef SSA_COV_FOUR_CHUNKS
     constexpr int NKC = 3;
-#else
-    constexpr int NKC = 4;
-#endif
 #pragma unroll
     for (int kc = 0; kc < NKC; ++kc) {
         double a0 = src[kc * 32], a1 = src[kc * 32 + 4];
@@ -523,10 +498,9 @@ SSA_DEV void covariance_reference(Tiles& t, const ssa_consts& C, int lane, const
         mo.c01 = __builtin_amdgcn_mfma_f64_4x4x4f64(a0, b1, mo.c01, 0, 0, 0);
         mo.c11 = __builtin_amdgcn_mfma_f64_4x4x4f64(a1, b1, mo.c11, 0, 0, 0);
     }
-#ifndef SSA_COV_FOUR_CHUNKS
     {   // point 12, the last term of the sum, by three vector fmas: the fourth k-chunk held it alone (three matrix instructions that
         // multiplied three rows of zeros) -- entry (i, j) += y12[i] (Wi y12[j]), the product rounded as the matrix unit's operand was;
-        // whole 20 000-object episodes bit-identical to the four-chunk form (build_ablate/r04_run52.sh), 0.2 us per step less with
+        // whole 20 000-object episodes bit-identical to the four-chunk form, 0.2 us per step less with
         // the broadcasts above
         const double* y12 = &Y[ybase(mid) + 12 * 8];
         const double ai = y12[hi], ai4 = y12[4 + hi], bj = C.Wi * y12[lo], bj4 = C.Wi * y12[4 + lo];
@@ -534,7 +508,6 @@ SSA_DEV void covariance_reference(Tiles& t, const ssa_consts& C, int lane, const
         mo.c01 = fma(ai, bj4, mo.c01);
         mo.c11 = fma(ai4, bj4, mo.c11);
     }
-#endif
     const int hi1 = hi & 1, lo1 = lo & 1;
     double* P = &t.P[mid * 36];
     const double p00 = mo.c00 + t.Q[hi * 6 + lo];
@@ -625,11 +598,8 @@ SSA_DEV void chol_store_rows(double* Ug, const double (&uc)[6], int l)
 
 // robust_cholesky (dynamics.py:402-417) for the four objects of the wavefront: plain attempt, then a + 10^i I for
 // i = -6..9 (first success wins); returns the calling row's -1, 0..15, or 16 (LinAlgError).
-// The plain attempt runs row-parallel (each row its own object).  Rows that fail are then served ONE AT A TIME BY THE
-// WHOLE WAVEFRONT: the four rows try four consecutive rungs of that object's ladder at once and the lowest successful
-// one wins -- the same answer as the reference's sequential ladder in a quarter of the factorisations (a diverged
-// filter late in an episode needs rung 10-15: without this its wavefront ran 11-16 factorisations back to back and held
-// the end of the launch, build_ablate/wave_timeline.py).
+// The plain attempt runs row-parallel (each row its own object); the rows that fail then try all sixteen rungs at once, one
+// lane per rung (robust_chol_row_lds below).
 __constant__ double JITTER[16] = {1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1, 1.0, 10.0, 100.0, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9};
 // Does scale * P + jit * I factorise?  ONE lane decides, alone, in its own registers: the ladder's unit of work when every lane
 // of a row tries its own rung (robust_chol_row_lds below).  Operation by operation the arithmetic of chol_row_regs<false> --
@@ -664,95 +634,43 @@ SSA_DEV int robust_chol_row_lds(Tiles& t, double scale, int g, int l)
 {
     double uc[6];
     int rung = 16;
-    {
-        const bool ok = chol_row_regs<true>(&t.P[g * 36], scale, 0.0, g, l, uc);
-        if (ok) {
+    const bool ok = chol_row_regs<true>(&t.P[g * 36], scale, 0.0, g, l, uc);
+    if (ok) {
+        chol_store_rows(&t.UA[g * 36], uc, l);
+        rung = -1;
+    }
+    const unsigned long long bad = __ballot(!ok);
+    wave_lds_sync();
+    if (bad == 0ull) return rung;                  // the common case, wave-uniform
+    __builtin_amdgcn_s_setprio(3);                 // a straggler in the making: issue priority for the rest of its life
+    // The ladder in ONE pass, every failed row at once: lane l of a row decides, whole and alone (chol_lane_ok), whether its
+    // row's matrix factorises with rung l's jitter, so the sixteen rungs of up to four objects are tried side by side; the
+    // FIRST rung that succeeds -- the reference's sequential answer, dynamics.py:406-414, also where success is not monotone
+    // in the jitter: every rung is actually tried -- is the lowest set bit of the row's ballot, and the row forms that rung's
+    // factor.  Two factorisations' latency whatever the rung and however many of the four objects need the ladder (before:
+    // the rows took turns, four rungs per pass: a wavefront with four diverged objects at rungs 12-15 ran sixteen passes back
+    // to back and held the end of a late-episode launch, profiles/r03_wave_timeline_hybrid_step400.txt).
+    const bool mine = ((bad >> (g * 16)) & 1ull) != 0ull;   // row-uniform
+    if (mine) {
+        const double* Pg = &t.P[g * 36];
+        const double jit = JITTER[l];
+        bool finite = true;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int idx = l + 16 * r;
+            if (idx < 36) finite = finite && (fabs(Pg[idx]) <= 1.79769313486231570e308);
+        }
+        finite = ((__ballot(!finite) >> (g * 16)) & 0xFFFFull) == 0ull;      // scipy's check_finite: the whole matrix
+        const bool okr = chol_lane_ok(Pg, scale, jit) && finite;
+        const unsigned won = (unsigned)((__ballot(okr) >> (g * 16)) & 0xFFFFull);
+        if (won != 0u) {
+            rung = __ffs((int)won) - 1;
+            const double jw = __shfl(jit, g * 16 + rung, 64);            // the winning rung's jitter, from the lane that tried it
+            chol_row_regs<false>(Pg, scale, jw, g, l, uc);               // (succeeds: the same arithmetic said so)
             chol_store_rows(&t.UA[g * 36], uc, l);
-            rung = -1;
-        }
-        const unsigned long long bad = __ballot(!ok);
-        wave_lds_sync();
-        if (bad == 0ull) return rung;                  // the common case, wave-uniform
-        __builtin_amdgcn_s_setprio(3);                 // a straggler in the making: issue priority for the rest of its life
-#ifndef SSA_LADDER_BY_PASSES
-        // The ladder in ONE pass, every failed row at once: lane l of a row decides, whole and alone (chol_lane_ok), whether its
-        // row's matrix factorises with rung l's jitter, so the sixteen rungs of up to four objects are tried side by side; the
-        // FIRST rung that succeeds -- the reference's sequential answer, dynamics.py:406-414, also where success is not monotone
-        // in the jitter: every rung is actually tried -- is the lowest set bit of the row's ballot, and the row forms that rung's
-        // factor.  Two factorisations' latency whatever the rung and however many of the four objects need the ladder (before:
-        // the rows took turns, four rungs per pass: a wavefront with four diverged objects at rungs 12-15 ran sixteen passes back
-        // to back and held the end of a late-episode launch, build_ablate/wave_timeline.py).
-        {
-            const bool mine = ((bad >> (g * 16)) & 1ull) != 0ull;   // row-uniform
-            if (mine) {
-                const double* Pg = &t.P[g * 36];
-                const double jit = JITTER[l];
-                bool finite = true;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const int idx = l + 16 * r;
-                    if (idx < 36) finite = finite && (fabs(Pg[idx]) <= 1.79769313486231570e308);
-                }
-                finite = ((__ballot(!finite) >> (g * 16)) & 0xFFFFull) == 0ull;      // scipy's check_finite: the whole matrix
-                const bool okr = chol_lane_ok(Pg, scale, jit) && finite;
-                const unsigned won = (unsigned)((__ballot(okr) >> (g * 16)) & 0xFFFFull);
-                if (won != 0u) {
-                    rung = __ffs((int)won) - 1;
-                    const double jw = __shfl(jit, g * 16 + rung, 64);            // the winning rung's jitter, from the lane that tried it
-                    chol_row_regs<false>(Pg, scale, jw, g, l, uc);               // (succeeds: the same arithmetic said so)
-                    chol_store_rows(&t.UA[g * 36], uc, l);
-                }
-            }
-            wave_lds_sync();
-            return rung;
-        }
-#endif
-        for (int gf = 0; gf < OBJ_PER_WAVE; ++gf) {    // wave-uniform loop over the rows that failed (the former form: -DSSA_LADDER_BY_PASSES)
-            if (((bad >> (gf * 16)) & 1ull) == 0ull) continue;
-            const double* Pg = &t.P[gf * 36];
-            bool finite = true;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const int idx = l + 16 * r;
-                if (idx < 36) finite = finite && (fabs(Pg[idx]) <= 1.79769313486231570e308);
-            }
-            int found = 16;
-            if (__ballot(!finite) == 0ull) {
-                // (Group by group from the bottom: the reference's answer is the FIRST rung that factorises.  Round 3 believed success was not
-                // monotone in the jitter for a diverged filter's (n + lambda) P ~ 1e14 and blamed a two-pass search for three lost filters per
-                // episode; measured in round 4 (ssa_ladder_probe_f64, tests/test_hip_step.py::test_ladder_on_the_ill_conditioned_tile) it IS
-                // monotone on that tile and 4 096 perturbations of it -- the two builds differed in ONE rounding of the diagonal entry,
-                // scaled_entry above.)
-#ifdef SSA_LADDER_TWO_PASS   // diagnostic ONLY (build_ablate/ladder_probe_tile.py, profiles/r04_ladder_case.txt): the search round 3 tried and
-                // reverted -- last rung of each group of four, then the group.  It assumes success is monotone in the jitter (it is, on every case seen).
-                const bool ok1 = chol_row_regs<false>(Pg, scale, JITTER[4 * g + 3], g, l, uc);
-                const unsigned long long won1 = __ballot(ok1);
-                if (won1 != 0ull) {
-                    const int grp = (won1 & 0xFFFFull) ? 0 : ((won1 >> 16) & 0xFFFFull) ? 1 : ((won1 >> 32) & 0xFFFFull) ? 2 : 3;
-                    const bool okr = chol_row_regs<false>(Pg, scale, JITTER[grp * 4 + g], g, l, uc);
-                    const unsigned long long won = __ballot(okr);
-                    const int win = (won & 0xFFFFull) ? 0 : ((won >> 16) & 0xFFFFull) ? 1 : ((won >> 32) & 0xFFFFull) ? 2 : 3;
-                    found = grp * 4 + win;
-                    if (g == win) chol_store_rows(&t.UA[gf * 36], uc, l);
-                }
-                for (int pass = 4; pass < 4; ++pass) {
-#else
-                for (int pass = 0; pass < 4; ++pass) {
-#endif
-                    const bool okr = chol_row_regs<false>(Pg, scale, JITTER[pass * 4 + g], g, l, uc);   // row g tries rung 4 pass + g
-                    const unsigned long long won = __ballot(okr);
-                    if (won != 0ull) {
-                        const int win = (won & 0xFFFFull) ? 0 : ((won >> 16) & 0xFFFFull) ? 1 : ((won >> 32) & 0xFFFFull) ? 2 : 3;
-                        found = pass * 4 + win;
-                        if (g == win) chol_store_rows(&t.UA[gf * 36], uc, l);
-                        break;
-                    }
-                }
-            }
-            if (g == gf) rung = found;
-            wave_lds_sync();
         }
     }
+    wave_lds_sync();
     return rung;
 }
 
@@ -849,19 +767,6 @@ SSA_DEV void aer_obs_tile(const Tiles& t, const ssa_step_params& p, const ssa_co
     else aer_obs_tile_at(t, p, C, g, l, obj, env_time_of<INL>(p, 0) + p.time_offset);
 }
 
-#ifdef SSA_CL_TRACE   // diagnostic build only (build_ablate/closed_loop_timeline.py): closed_loop_kernel, steps SSA_CL_TRACE and + 1
-__device__ unsigned long long g_cl_trace[8192 * 16];
-#endif
-#ifdef SSA_TRACE   // diagnostic build only (build_ablate/wave_timeline.py): per-wave phase timestamps, 100 MHz wall clock
-__device__ unsigned long long g_trace[16384 * 16];
-// (the FIRST ACTIVE lane stamps: markers 10-14 sit inside the update's row-divergent code, where lane 0 is active only when the
-// selected object is the tile's first)
-#define SSA_TR(k) do { if (lane == __builtin_amdgcn_readfirstlane(lane) && tile < 16384) g_trace[tile * 16 + (k)] = wall_clock64(); } while (0)
-#elif defined(SSA_TRUNC)   // diagnostic build only (build_ablate/trunc_counters.sh): the wave ends at marker SSA_TRUNC, so that the
-#define SSA_TR(k) do { if ((k) == SSA_TRUNC) return; } while (0)   // PMC instruction counts of successive builds difference into stages
-#else
-#define SSA_TR(k) do { } while (0)
-#endif
 
 // SSA_LAUNCH_FOLD_INSIDE: the statistics of the step are folded by the LAST wavefront of the launch to finish its atomics instead
 // of by a fold kernel behind it (a caller that needs them on the host right after the step -- the gym env -- saves a dependent
@@ -1038,9 +943,6 @@ struct ActLate {
     int first;                       // action of the launch's first step (decided by the caller)
     int last;                        // the action get() returned most recently
     bool aborted;
-#ifdef SSA_CL_TRACE
-    unsigned long long t_wait, t_seen;
-#endif
     int agent;                       // SSA_AGENT_*
     const ssa_consts* C;             // (kernarg copy)
     const double* M;                 // GCRS -> ITRS matrix of the current step
@@ -1050,7 +952,7 @@ struct ActLate {
     SSA_DEV void before_wait(Tiles& t, int lane, int cnt) { closed_loop_prescore(*this, t, lane, cnt); }
     // The outputs of step k leave for HBM inside step k + 1, behind its Cholesky stage (the tile is intact until then): right
     // after the decision every wavefront is released at once, and 18 MB of tile stores issued at that moment delayed the
-    // acknowledgements of the parts the NEXT decision waits for (late announcers: +3 us, build_ablate/closed_loop_timeline.py);
+    // acknowledgements of the parts the NEXT decision waits for (late announcers: +3 us);
     // here they overlap the Kepler stage instead.
     const LoopK* lk;                 // the kernel's argument block
     int pend;                        // step whose tile is still to be stored (-1: none)
@@ -1074,13 +976,7 @@ struct ActLate {
     SSA_DEV int get()
     {
         if (want == 0u) { last = first; return first; }
-#ifdef SSA_CL_NOWAIT   // diagnostic (build_ablate/closed_loop_variants.py): no wait for the decision -- what the exchange's latency costs
-        return first;
-#endif
         const unsigned long long t0 = wall_clock64();
-#ifdef SSA_CL_TRACE
-        t_wait = t0;
-#endif
         unsigned lo, hi;
         for (;;) {
             const unsigned long long v = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1098,9 +994,6 @@ struct ActLate {
             aborted = true;
             return -2;
         }
-#ifdef SSA_CL_TRACE
-        t_seen = wall_clock64();
-#endif
         last = (int)lo;
         return (int)lo;
     }
@@ -1178,7 +1071,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // and for a returning atomic -- once, at the end of a one-tile wavefront's life, but ~1.5 us per tile in the grid-stride
     // instance (8 x 20 000 objects: 100.7 us per step instead of 89.0); the launcher sends those launches a fold kernel instead.
     // (Round 4 tried counting once per WAVEFRONT, at the end of its life -- lane i counts the walk's i-th tile, one round trip:
-    // build_ablate/grid_stride_fold_inside_experiment.patch.  Correct, and slower than the 4.3 us fold kernel it replaces: the wavefronts of
+    // profiles/r04_vec_env_breakdown.txt.  Correct, and slower than the 4.3 us fold kernel it replaces: the wavefronts of
     // a grid-stride launch end together, and the 128 shard-complete increments per env land on ONE word one after the other -- the vector
     // env's step 123.9 -> 130.4 us although its host side got 4 us shorter.)
     constexpr bool FOLD_OK = (TILE == 0);
@@ -1188,14 +1081,12 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // (TILE 0: the kernel issued the tile's loads from its preloaded pointer arguments before anything else.)  First thing here,
     // so that these scalar loads complete with the action / time words' below -- placed behind the wait for the tile they
     // put one more scalar-memory round trip between the tile's arrival and its commit to LDS
-#ifndef SSA_NO_EARLY_ARGS
     if (TILE == 0 && !ALL) {
         // the epilogue's output pointers are fetched NOW: their scalar loads (kernarg segment) overlap the tile's HBM round
         // trip instead of each adding a scalar-memory round trip to the store path of a latency-bound wavefront
         asm volatile("" ::"s"(p.P_out), "s"(p.x_out), "s"(p.x_true_out), "s"(p.obs), "s"(p.metrics), "s"(p.stat_shards), "s"(p.upd),
                      "s"(p.aer_out), "s"(p.n_obj));
     }
-#endif
 
     // env of the object: no division for the single-env case, a 32-bit one otherwise (n_env * n_obj < 2^31)
     int e = (valid && p.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
@@ -1247,38 +1138,21 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                                     : p.z_noise + (int64_t)e * p.zn_stride_env + (int64_t)tmod * p.zn_stride_time + aobj * p.zn_stride_obj + (l - 9);
         upd_in = *src;
     }
-    SSA_TR(0);
-#ifdef SSA_TRACE
-    if (lane == 0 && tile < 16384) {
-        unsigned hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_trace[tile * 16 + 15] = ((unsigned long long)xcc << 32) | hw;
-        g_kep_dbg[(blockIdx.x & 16383) * 2] = 0u;
-        g_kep_dbg[(blockIdx.x & 16383) * 2 + 1] = 0u;
-    }
-#endif
 
     if (TILE == 0 && pf.dma) tile_dma_wait(t, pf, lane);   // (the one-tile kernels: the tile came by LDS-DMA)
     else if (TILE != 2) tile_commit(t, pf, lane);        // TILE 1: requested one tile ago (or by the kernel prologue)
     if (lane < 8) t.Z[lane] = 0.0;
     if (TILE != 2 && lane < 36) t.Q[lane] = C.Q[lane];   // (a rollout's later steps find it in place)
     wave_lds_sync();
-    SSA_TR(1);
 
     const int st_in = t.St[g];
     const bool active = valid && st_in == SSA_ST_OK;
 
     // ---- U1/U2: sigma points
-#if defined(SSA_ABLATE) && (SSA_ABLATE & 2)
-    const int rung = -1;
-    if (l < 6) for (int c = 0; c < 6; ++c) t.UA[g * 36 + l * 6 + c] = 1e-3 * t.P[g * 36 + l * 6 + c];
-#else
     const int rung = robust_chol_row_lds(t, C.scale, g, l);
-#endif
     asrc.mid_step(t, lane);   // (closed loop: the PREVIOUS step's tile leaves for HBM now, its last reader of t.Obs)
     if (may_update && l < 12) t.Obs[g * 12 + l] = upd_in;
     wave_lds_sync();
-    SSA_TR(2);
     const bool chol_fail = (rung == 16);
     const bool is_sigma = (l <= 12);
     const bool is_pm = (l >= 1 && l <= 12);
@@ -1298,20 +1172,14 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // branch through the out-of-line complete restatement
     double o[6];
     {
-#if defined(SSA_ABLATE) && (SSA_ABLATE & 1)
-        for (int c = 0; c < 6; ++c) o[c] = s[c] + 1e-3 * C.dt * s[(c + 3) % 6];
-        const bool kep_ok = true;
-#else
         bool kep_ok;
         if (PROP == 2) {
             const J2Params jq = {C.j2, C.r_eq, C.rk4_substeps};
             kep_ok = propagate_j2_rk4(s, C.dt, jq, o);
         } else {
             if (PROP == 3) kep_ok = kepler_hybrid_fast(s, C.dt, o);
-            else
-            kep_ok = kepler_step_fast<PROP == 2 ? 1 : PROP, 1>(s, C.dt, o);
+            else kep_ok = kepler_step_fast<PROP == 2 ? 1 : PROP, 1>(s, C.dt, o);
         }
-#endif
         if (PROP == 3) {
             if (__any(!kep_ok)) {   // sigma points outside the strong-elliptic regime: the reference's branches (whole-wave branch)
                 // (no issue priority for the inline tier: late in an episode three wavefronts in four take it, and boosting the many
@@ -1378,7 +1246,6 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // again where the rare paths below need it (a scalar load here would sit in front of every LDS wait that follows)
     obj = base + g;
     e = (valid && p.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
-    SSA_TR(3);
     // the next tile's inputs: in flight during the transform / covariance / observation / store of this one
     if (TILE == 1) tile_issue(pf, p, lane, next_base, next_cnt);
 
@@ -1405,15 +1272,9 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     }
     wave_lds_sync();
     Moments mo = {0.0, 0.0, 0.0};
-#if !(defined(SSA_ABLATE) && (SSA_ABLATE & 8))
-#ifndef SSA_COV_FOUR_CHUNKS   // (diagnostic: round 4's first form of the reference covariance -- nine + twelve matrix instructions)
     if (C.flags & SSA_FLAG_REFERENCE_COV) mo = moment_sums_mfma<true>(t, lane);   // (wave-uniform branch: the sums alone, six matrix instructions)
-    else
-#endif
-    mo = moment_sums_mfma(t, lane);
-#endif
+    else mo = moment_sums_mfma(t, lane);
     wave_lds_sync();
-    SSA_TR(4);
     double xb_l = 0.0;   // lanes 0..5: component l of the prior mean
     if (l < 6) {
         const double s0 = t.X[g * 6 + l];
@@ -1426,12 +1287,9 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     }
     const bool nan_x = ((__ballot(l < 6 && xb_l != xb_l) >> (g * 16)) & 0xFFFFull) != 0;
     wave_lds_sync();
-#if !(defined(SSA_ABLATE) && (SSA_ABLATE & 4))
     if (C.flags & SSA_FLAG_REFERENCE_COV) covariance_reference(t, C, lane, o, xb_l);   // (wave-uniform branch)
     else covariance_finish(t, C, lane, mo);
-#endif
     wave_lds_sync();
-    SSA_TR(5);
 
     int st_new = st_in;
     if (active) {
@@ -1509,7 +1367,6 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                 if (C.obs_type == SSA_OBS_AER) { z[0] = aer[0]; z[1] = aer[1]; z[2] = aer[2]; }
                 else { z[0] = sf[0]; z[1] = sf[1]; z[2] = sf[2]; }
             }
-            SSA_TR(10);
             visible = row_bcast<13>(el_mine) >= C.obs_limit;  // object_visible(): elevation of the TRUE state (:418-425)
             if (rec && l == 13) {
 #pragma unroll
@@ -1536,7 +1393,6 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                         zp[c] = u0 + (C.sum_wm_m1 * u0 + C.Wi * row_allsum(du));
                     }
                 }
-                SSA_TR(11);
                 // H4: residuals; lane 13 forms the innovation of the noisy measurement
                 double rz[3];
                 {
@@ -1605,7 +1461,6 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                 }
             }
             wave_lds_sync();
-            SSA_TR(12);
             bool inv_ok;
             double SI[9];
             {
@@ -1622,7 +1477,6 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                     W[36 + lane] = W[9 + a * 3] * SI[b] + W[9 + a * 3 + 1] * SI[3 + b] + W[9 + a * 3 + 2] * SI[6 + b];
                 }
                 wave_lds_sync();
-                SSA_TR(13);
                 if constexpr (ALL) {   // P+ = P- - K S K^T into the row's consumed staging matrix; x and the tile's P stay as they are
                     if (lane < 36) {
                         const int a = lane / 6, b = lane - 6 * a;
@@ -1651,7 +1505,6 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                 }
                 if (lane < 6) t.X[gu * 6 + lane] = xn;
                 }
-                SSA_TR(14);
             }
             if (g == gu) {
                 if (!inv_ok) st_new = SSA_ST_UPDATE_LINALG;
@@ -1703,7 +1556,6 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
 
     // ---- F1: failed filters carry the sentinels (ssa_tasker_simple_2.py:157-158, 369-382)
     wave_lds_sync();
-    SSA_TR(6);
     if (valid && (ALL ? st_pred : st_new) != SSA_ST_OK && st_in == SSA_ST_OK) {   // (ActAll: the predict's failures only)
         for (int idx = l; idx < 36; idx += 16) {
             int a = idx / 6, b = idx - a * 6;
@@ -1745,9 +1597,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                                    st_new, look_vis, look_taken);
         return;
     }
-#if !(defined(SSA_ABLATE) && (SSA_ABLATE & 16))
     observe_rows(t, g, l, cnt != OBJ_PER_WAVE);
-#endif
     // O4 in the epilogue (atomics-statistics path): the (az, el, range, trace P) block of the NEW state -- the 'aer'
     // observation mode and the multi-GPU all-gather payload -- from the tiles, so that no second pass over x / P (the
     // former post kernel: 6.7 MB re-read per 20 000 objects plus a launch) is needed
@@ -1755,9 +1605,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         if (l < 4 && valid) aer_obs_tile<INL>(t, p, C, g, l, e, p.obj_ids ? (int64_t)e * p.n_obj + t.Oid[g] : obj);
     }
     wave_lds_sync();
-    SSA_TR(7);
     if (!ACT::late) {   // (closed_loop_kernel stores the tile itself, AFTER it has announced its part of the decision)
-#if !(defined(SSA_ABLATE) && (SSA_ABLATE & 32))
         if (p.spos_tiles && p.stat_shards && lane == 0) {   // the tile's first maximum of sigma_pos (np.argmax for the 'shaped' reward): one slot, no atomics
             unsigned long long key, idx;
             spos_tile_best(t, cnt, obj - (int64_t)e * p.n_obj, key, idx, p.obj_ids != nullptr);
@@ -1766,7 +1614,6 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
             __hip_atomic_store(slot + 1, idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         store_tile<TILE != 1>(t, p, lane, base, cnt);
-        SSA_TR(8);
         // O3 by sharded atomics: max delta_pos (as ordered bits: non-negative doubles and NaN order like unsigned
         // integers, so NaN wins exactly as in np.max), trinary counts (packed in one word), failures
         const bool one_env = p.n_env == 1 || ((uint32_t)base / (uint32_t)p.n_obj == (uint32_t)(base + cnt - 1) / (uint32_t)p.n_obj);
@@ -1795,11 +1642,9 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
             if (lane == 63) {
                 const int64_t e_tile = (p.n_env > 1) ? (int64_t)((uint32_t)base / (uint32_t)p.n_obj) : 0;
                 unsigned long long* sh = (unsigned long long*)p.stat_shards + ((e_tile * SSA_STAT_SHARDS) + (tile & (SSA_STAT_SHARDS - 1))) * SSA_STAT_SHARD_WORDS;
-#ifndef SSA_NO_ATOMICS   // (diagnostic builds only)
                 atomicMax(sh, mx);
                 atomicAdd(sh + 1, (unsigned long long)c4 | ((unsigned long long)c7 << 32));
                 if (nfl) atomicAdd(sh + 2, (unsigned long long)nfl);
-#endif
                 if (FOLD_OK && (p.launch_mask & SSA_LAUNCH_FOLD_INSIDE)) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // this tile's sums are in before it is counted
                     i_fold = stat_tile_counted(p, e_tile, tile);
@@ -1856,14 +1701,6 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                                               p.stats + (e_first + i) * SSA_STAT_STRIDE, lane);      // (straddling tiles: no spos_tiles, see step_launch)
           }
         }
-        SSA_TR(9);
-#ifdef SSA_TRACE
-        if (lane == 0 && tile < 16384 && !__any(my_update)) {   // (the update's wavefront uses words 10-14 for its own phases)
-            g_trace[tile * 16 + 13] = __hip_atomic_load(&g_kep_dbg[(blockIdx.x & 16383) * 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            g_trace[tile * 16 + 14] = __hip_atomic_load(&g_kep_dbg[(blockIdx.x & 16383) * 2 + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#endif
-#endif
         // raw-shard consumers (stat_shards_clear): the first tile's wavefront zeroes the shard set the NEXT step accumulates
         // into -- at the very end, so that no wavefront waits for this pointer's kernarg line before its tile loads
         if (tile == 0) {
@@ -2095,7 +1932,6 @@ __global__ void __launch_bounds__(64, SSA_STEP_WAVES) rollout_kernel(const RollK
         unsigned wave_slot;   // the wavefront's slot on its SIMD (HW_ID bits 3:0)
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(wave_slot));
         for (int kk = 0; kk < K; ++kk) {
-#ifndef SSA_ROLL_NOPRIO
             // The SIMD arbiter serves the oldest wavefront first: left alone, the 5 co-resident wavefronts finish
             // their K steps one after the other and the SIMD runs the tail of the launch with 4, 3, 2, 1 of them
             // (latency-bound).  Rotating the issue priority per step keeps them level, so all stay resident and
@@ -2106,7 +1942,6 @@ __global__ void __launch_bounds__(64, SSA_STEP_WAVES) rollout_kernel(const RollK
                 case 2: __builtin_amdgcn_s_setprio(2); break;
                 default: __builtin_amdgcn_s_setprio(3); break;
             }
-#endif
             asm volatile("" : "+s"(kp));      // per step, as per tile in step_fast_kernel: nothing carried around the loop
             asm volatile("" : "+v"(lane));
             const StepK& k = ((const RollK*)kp)->k;
@@ -2725,7 +2560,7 @@ __global__ void __launch_bounds__(64) agent_final_kernel(const AgentPart* __rest
 // (First version: the last wavefront to arrive did the folding.  The wavefront that runs the update arrives last, lost three
 // more microseconds folding while the others were already in their next predict, so it was the last to arrive at the NEXT
 // step too -- every step waited for one wavefront's predict + update + folds in series: 14.4 us per step against 10.2 without
-// the wait, build_ablate/closed_loop_timeline.py.  Folders without objects cannot fall behind.)
+// the wait, profiles/r03_closed_loop_timeline.txt.  Folders without objects cannot fall behind.)
 // No compute wavefront can be two steps ahead (the update of step k + 1 needs every part of step k), hence two sets of parts,
 // indexed by the step's parity, suffice; the counters only ever grow.  All words that cross wavefronts are agent-scope atomics
 // (coherent across the XCDs' L2s); a store is ordered before the atomic that announces it by waiting for its
@@ -3039,16 +2874,12 @@ __global__ void __launch_bounds__(64, SSA_STEP_WAVES) closed_loop_kernel(const L
         // microseconds the others spent on the next predict, and if it stays behind it is the last to announce its part of
         // the NEXT step too, with every wavefront waiting for it.  It catches up at top priority.
         if (boost) __builtin_amdgcn_s_setprio(3);
-#ifdef SSA_CL_NOROT   // diagnostic: no rotation of the issue priority
-        else __builtin_amdgcn_s_setprio(1);
-#else
         else switch ((wave_slot + (unsigned)kk) & 3u) {
             case 0: __builtin_amdgcn_s_setprio(0); break;
             case 1: __builtin_amdgcn_s_setprio(1); break;
             case 2: __builtin_amdgcn_s_setprio(2); break;
             default: __builtin_amdgcn_s_setprio(3); break;
         }
-#endif
         asm volatile("" : "+s"(kp));
         asm volatile("" : "+v"(lane));
         const StepK& k = ((const LoopK*)kp)->k;
@@ -3067,16 +2898,6 @@ __global__ void __launch_bounds__(64, SSA_STEP_WAVES) closed_loop_kernel(const L
         pk.stats = nullptr;
         pk.aer_out = nullptr;
         pk.stat_shards_clear = nullptr;
-#ifdef SSA_CL_TRACE
-        const bool trc = (kk == SSA_CL_TRACE || kk == SSA_CL_TRACE + 1) && w < 8192 && lane == 0;
-        unsigned long long* const trp = g_cl_trace + (int64_t)w * 16 + (kk - SSA_CL_TRACE) * 8;
-        if (trc) { trp[0] = wall_clock64(); trp[7] = 0ull; }
-#define SSA_CLT(i) do { if (trc) trp[i] = wall_clock64(); } while (0)
-#define SSA_CLF(b) do { if (trc) trp[7] |= (b); } while (0)
-#else
-#define SSA_CLT(i) do { } while (0)
-#define SSA_CLF(b) do { } while (0)
-#endif
         asrc.want = (unsigned)kk;
         asrc.C = &k.c;
         asrc.lk = (const LoopK*)kp;
@@ -3085,15 +2906,7 @@ __global__ void __launch_bounds__(64, SSA_STEP_WAVES) closed_loop_kernel(const L
         wave_lds_sync();
         if (asrc.aborted) return;
         boost = tile == closer_tile(asrc.last, total, r.slot_of);           // the update ran here (or would have)
-#ifdef SSA_CL_TRACE
-        if (trc) { trp[1] = asrc.t_wait; trp[2] = asrc.t_seen; }
-        if (boost) SSA_CLF(1ull);
-#endif
-        SSA_CLT(3);
         // ---- this wavefront's part: the agent's score of its objects (lane 0 of each row) and the step's statistics
-#ifdef SSA_CL_NOTREE   // diagnostic: no exchange at all (1: scores still computed, 2: not even those)
-        if (SSA_CL_NOTREE == 2) { asrc.pend = kk; continue; }
-#endif
         {
             const int g = lane >> 4, l = lane & 15;
             if (l == 0) {
@@ -3133,11 +2946,6 @@ __global__ void __launch_bounds__(64, SSA_STEP_WAVES) closed_loop_kernel(const L
             }
         }
         wave_lds_sync();
-#ifdef SSA_CL_NOTREE
-        if (lane == 0 && rowpart[0].arg == -12345) a.c.stats_out[0] = rowpart[1].best;   // (keeps the scores alive)
-        asrc.pend = kk;
-        continue;
-#endif
         if (lane == 0) {
             ClPart me = rowpart[0];
             cl_merge(me, rowpart[1]);
@@ -3148,7 +2956,6 @@ __global__ void __launch_bounds__(64, SSA_STEP_WAVES) closed_loop_kernel(const L
             cl_stores_done();
             __hip_atomic_fetch_add(closer ? ws + L.fcount : ws + L.gcount + (int64_t)G * 16, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (nobody waits for it here)
         }
-        SSA_CLT(4);
         asrc.pend = kk;      // the step's outputs leave inside the next step (ActLate::mid_step)
     }
     if (asrc.pend >= 0) closed_loop_store((const LoopK*)kp, t, lane, asrc.pend, base, cnt);
@@ -3474,12 +3281,6 @@ using namespace ssa;
 extern "C" {
 
 int ssa_abi_version(void) { return SSA_ABI_VERSION; }
-#ifdef SSA_CL_TRACE
-int ssa_debug_cl_trace_copy(void* host, int64_t nbytes) { return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_cl_trace), (size_t)nbytes) == hipSuccess ? 0 : -1; }
-#endif
-#ifdef SSA_TRACE
-int ssa_debug_trace_copy(void* host, int64_t nbytes) { return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace), (size_t)nbytes) == hipSuccess ? 0 : -1; }
-#endif
 const char* ssa_build_info(void) { return "libssa_hip gfx950 fp64 (" __DATE__ " " __TIME__ ")"; }
 
 static int device_cu_count()
@@ -3530,11 +3331,7 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     if (total >= ((int64_t)1 << 31)) return SSA_E_INVALID;
     // tiles per wavefront T = ceil(tiles / resident wavefront slots); G = ceil(tiles / T) wavefronts
     const int64_t ntiles = (total + OBJ_PER_WAVE - 1) / OBJ_PER_WAVE;
-#ifdef SSA_SLOTS_DIV   // (diagnostic: fewer, longer wavefronts)
-    const int64_t slots = (int64_t)device_cu_count() * 4 * SSA_STEP_WAVES / SSA_SLOTS_DIV;
-#else
     const int64_t slots = (int64_t)device_cu_count() * 4 * SSA_STEP_WAVES;
-#endif
     const int64_t per_wave = (ntiles + slots - 1) / slots;
     const int nwork = (int)((ntiles + per_wave - 1) / per_wave);
     const bool fast_stats = p->stat_shards != nullptr;   // statistics by the common-path kernel's atomics
@@ -3741,15 +3538,7 @@ int ssa_env_closed_loop_f64(const ssa_consts* c, const ssa_step_params* p, const
     const dim3 grid((unsigned)(nwork + L.ng + 1));
     // A COOPERATIVE launch: the decision is a grid-wide exchange, so every wavefront must be resident at once -- with a cooperative
     // launch that is the runtime's guarantee (it refuses a grid the device cannot hold next to what else is running), not only this
-    // function's occupancy estimate above.  SSA_LOOP_PLAIN_LAUNCH=1 in the environment: the plain launch of round 3 (diagnostic).
-    static const bool plain = []() { const char* e = getenv("SSA_LOOP_PLAIN_LAUNCH"); return e && e[0] == '1'; }();
-    if (plain) {
-        if (c->propagator == SSA_PROP_FG) hipLaunchKernelGGL(closed_loop_kernel<1>, grid, dim3(64), 0, s, lk, nwork, nwork);
-        else if (c->propagator == SSA_PROP_ELEMENTS) hipLaunchKernelGGL(closed_loop_kernel<0>, grid, dim3(64), 0, s, lk, nwork, nwork);
-        else if (c->propagator == SSA_PROP_HYBRID) hipLaunchKernelGGL(closed_loop_kernel<3>, grid, dim3(64), 0, s, lk, nwork, nwork);
-        else hipLaunchKernelGGL(closed_loop_kernel<2>, grid, dim3(64), 0, s, lk, nwork, nwork);
-        return launch_status();
-    }
+    // function's occupancy estimate above.
     void* args[3] = {(void*)&lk, (void*)&nwork, (void*)&nwork};
     const void* fn = (c->propagator == SSA_PROP_FG) ? (const void*)closed_loop_kernel<1>
                      : (c->propagator == SSA_PROP_ELEMENTS) ? (const void*)closed_loop_kernel<0>

@@ -147,7 +147,7 @@ def _never_destroy(graph):
     state it registered with, and in this torch build (2.10 + ROCm 7) its destructor then fails a TORCH_CHECK ("The graph should be registered
     to the state") -- an exception out of a C++ destructor: the process aborts, whenever the object happens to be freed (at the return of the
     capturing function, or later by the garbage collector).  One leaked reference keeps the few hundred bytes alive for the life of the
-    process (build_ablate/r04_run20.sh isolated it: tests/test_env_gpu.py::test_run_policy_replayed_from_a_graph_equals_the_eager_loop)."""
+    process (tests/test_env_gpu.py::test_run_policy_replayed_from_a_graph_equals_the_eager_loop)."""
     import ctypes
     ctypes.pythonapi.Py_IncRef(ctypes.py_object(graph))
 

@@ -13,8 +13,9 @@ one rounding in a diagonal entry, amplified 1e8-fold by the conditioning.  The k
 roundings (scaled_entry in csrc/ssa_kernels.hip: the product (n + lambda) P rounded, then + jitter: dynamics.py:410), contraction off,
 and tests/test_hip_step.py::test_ladder_on_the_ill_conditioned_tile pins exactly that.
 
-This file was produced ON THE GPU BOX (build_ablate/ladder_ab.py: first object / step at which the two builds' filter states part over a
-20 000-object episode of the bench workload -- object 19 669, step 277, i.e. tile 4 917, row 1):
+This file was produced ON THE GPU BOX at commit aaefe5b: the recipe below needs that commit's -DSSA_LADDER_* builds and build_ablate/
+scripts, both retired after it.  build_ablate/ladder_ab.py finds the first object / step at which the two builds' filter states part over a
+20 000-object episode of the bench workload -- object 19 669, step 277, i.e. tile 4 917, row 1:
 
     hipcc ... -DSSA_LADDER_BY_PASSES -DSSA_LADDER_TWO_PASS -o build_ablate/libs/twopass.so ssa-gym_amd/csrc/ssa_kernels.hip
     LIB=build_ablate/libs/twopass.so OUT=/tmp/ladder_twopass.npz python build_ablate/ladder_ab.py          # record the two-pass build
