@@ -388,7 +388,7 @@ class SSA_Tasker_Env(Env):
         self.i = 0
         self._fetch_small(0)
         self.runtime['reset'] += time.time() - s
-        return self._obs_out(reset=True)
+        return self._obs_out()
 
     def _fetch_small(self, i):
         e = self._engine
@@ -405,15 +405,22 @@ class SSA_Tasker_Env(Env):
         """an observation that reached the host through a device-to-host copy, in the dtype step() hands out (config['obs_dtype'])"""
         return arr.astype(np.float32) if getattr(self, "_mirror_f32", False) else arr
 
-    def _obs_out(self, reset=False):
+    def _obs_out(self, refresh_aer_dev=False):
         """the observation of the current step through the slow path (reset(), rollout(), run_agent()): a device-to-host copy (gathered into
-        the env's object order while a storage layout is set: a reset does not cost the layout)"""
+        the env's object order while a storage layout is set: a reset does not cost the layout).  'aer' refreshes self.observation in
+        place; with refresh_aer_dev (the multi-step drivers) it goes through self._aer_dev, the (4 m,) block an obs_device consumer may
+        hold, which reset() leaves alone"""
         e, slot = self._engine, self.i % self._engine.H
-        if self.obs_returned == 'flatten':
-            return self._host_obs(e.caller_rows(e.obs[slot]).cpu().numpy().reshape(-1))
-        elif self.obs_returned == 'aer':
-            return self.aer_obs(self.observation)
-        return self._host_obs(e.caller_rows(e.obs[slot]).cpu().numpy())
+        if self.obs_returned == 'aer':
+            if not refresh_aer_dev:
+                return self.aer_obs(self.observation)
+            from .. import device
+            M = e.trans[self.i % e.n_time].reshape(3, 3)
+            device.aer_obs(e.x_filter[slot], e.P_filter[slot], M, self._consts, out=self._aer_dev.view(self.m, 4))
+            self.observation[:] = e.caller_rows(self._aer_dev.view(self.m, 4)).cpu().numpy().reshape(-1)
+            return self.observation
+        obs = e.caller_rows(e.obs[slot]).cpu().numpy()
+        return self._host_obs(obs.reshape(-1) if self.obs_returned == 'flatten' else obs)
 
     def step(self, a):
         step_s = time.time()
@@ -472,10 +479,7 @@ class SSA_Tasker_Env(Env):
         e_t = time.time()
         self.runtime['Observations and Reward'] += e_t - t_dev
         self.runtime['step'] += e_t - step_s
-        if self.obs_returned == 'flatten':
-            return obs, self.rewards[i], done, {}
-        r = self.rewards[i]   # np.nan_to_num(..., nan=0.5, posinf=0.5, neginf=0.5) of a scalar (:365-367)
-        return obs, (r if np.isfinite(r) else np.float64(0.5)), done, {}
+        return obs, self._returned_reward(self.rewards[i]), done, {}
 
     # ------------------------------------------------------------------ per-step host bookkeeping
     def _book_update(self, i, a, rec):
@@ -517,6 +521,45 @@ class SSA_Tasker_Env(Env):
                 self.rewards[i] = -1 / self.n
         return done
 
+    def _returned_reward(self, r):
+        """the reward as step() hands it out: np.nan_to_num(r, nan=0.5, posinf=0.5, neginf=0.5) of a scalar (:365-367), except in the
+        'flatten' mode, which returns it as it is"""
+        return r if (self.obs_returned == 'flatten' or np.isfinite(r)) else np.float64(0.5)
+
+    def _ring_chunk(self, i0, kk):
+        """(statistics, update records) of steps i0 + 1 .. i0 + kk from the engine's history rings; synchronises the stream"""
+        e = self._engine
+        slots = [(i0 + 1 + k) % e.H for k in range(kk)]
+        return e.stats[slots, 0].cpu().numpy(), e.upd[slots, 0].cpu().numpy()
+
+    def _book_steps(self, acts, stats, upd, ring_head, out, check_actions=False):
+        """the bookkeeping of consecutive step() calls for steps self.i + 1, ... of a multi-step launch (rollout, run_agent, run_policy):
+        actions, update records, failures, rewards, dones, arg-max of sigma_pos, in step order, up to the first `done`.  `ring_head`: the
+        newest step the history rings hold; check_actions: a ValueError for an action outside 0 .. m-1 before its step is booked
+        (run_policy).  Appends the booked steps to the caller's lists out = (actions, rewards, dones), rewards as step() hands them
+        out; returns the `done` of the last booked step."""
+        self._ring_head = ring_head
+        self._fail_chunk_total = int(stats[-1][_lib.STAT_N_FAILED])      # (the chunk's last LAUNCHED step, even when booking stops early)
+        actions, rewards, dones = out
+        for k in range(len(acts)):
+            self.i += 1
+            i, a = self.i, int(acts[k])
+            if check_actions and not (0 <= a < self.m):
+                raise ValueError("run_policy: the policy chose action %d at step %d (valid: 0 .. %d)" % (a, i, self.m - 1))
+            self.actions[i] = a
+            self._book_update(i, a, upd[k])
+            self._stats = stats[k]
+            if int(stats[k][_lib.STAT_N_FAILED]) != self._n_failed:
+                self._record_failures(at_step=i)
+            done = self._reward_done(i, a, stats[k], self._argmax_sigma) or (i + 1 >= self.n)
+            self._argmax_sigma = int(stats[k][_lib.STAT_ARGMAX_SPOS])      # (-1 unless 'shaped' asked for it)
+            actions.append(a)
+            rewards.append(self._returned_reward(self.rewards[i]))
+            dones.append(done)
+            if done:
+                break
+        return done
+
     def rollout(self, actions):
         """Open-loop extension (no reference counterpart as ONE call): apply `actions` as consecutive step()
         calls would -- the loop of the reference's agent_naive_random / round-robin drivers (agents.py,
@@ -539,39 +582,10 @@ class SSA_Tasker_Env(Env):
             i0 = self.i
             act = torch.as_tensor(actions[pos:pos + kk].astype(np.int32)).view(kk, 1).to(e.dev)
             e.launch_rollout(i0 % e.H, i0 + 1, act, argmax_spos=shaped)
-            self._ring_head = i0 + kk
-            slots = [(i0 + 1 + k) % e.H for k in range(kk)]
-            stats = e.stats[slots, 0].cpu().numpy()          # synchronises the stream
-            upd = e.upd[slots, 0].cpu().numpy()
-            self._fail_chunk_total = int(stats[-1][_lib.STAT_N_FAILED])
-            for k in range(kk):
-                self.i += 1
-                i, a = self.i, int(actions[pos + k])
-                self.actions[i] = a
-                self._book_update(i, a, upd[k])
-                self._stats = stats[k]
-                if int(stats[k][_lib.STAT_N_FAILED]) != self._n_failed:
-                    self._record_failures(at_step=i)
-                done = self._reward_done(i, a, stats[k], self._argmax_sigma) or (i + 1 >= self.n)
-                self._argmax_sigma = int(stats[k][_lib.STAT_ARGMAX_SPOS])      # (-1 unless 'shaped' asked for it)
-                r = self.rewards[i]
-                rewards.append(r if (self.obs_returned == 'flatten' or np.isfinite(r)) else np.float64(0.5))
-                dones.append(done)
-                if done:
-                    break
+            stats, upd = self._ring_chunk(i0, kk)
+            done = self._book_steps(actions[pos:pos + kk], stats, upd, i0 + kk, ([], rewards, dones))
             pos += kk
-        slot = self.i % e.H
-        if self.obs_returned == 'aer':
-            from .. import device
-            M = e.trans[self.i % e.n_time].reshape(3, 3)
-            device.aer_obs(e.x_filter[slot], e.P_filter[slot], M, self._consts, out=self._aer_dev.view(self.m, 4))
-            self.observation[:] = self._aer_dev.cpu().numpy()
-            obs = self.observation
-        elif self.obs_returned == 'flatten':
-            obs = self._host_obs(e.obs[slot].cpu().numpy().reshape(-1))
-        else:
-            obs = self._host_obs(e.obs[slot].cpu().numpy())
-        return obs, np.asarray(rewards), np.asarray(dones, dtype=bool), {}
+        return self._obs_out(refresh_aer_dev=True), np.asarray(rewards), np.asarray(dones, dtype=bool), {}
 
     AGENT_KINDS = {'agent_naive_greedy': _lib.AGENT_NAIVE_GREEDY, 'agent_visible_greedy': _lib.AGENT_VISIBLE_GREEDY,
                    'agent_visible_greedy_aer': _lib.AGENT_VISIBLE_GREEDY, 'agent_shannon': _lib.AGENT_SHANNON,
@@ -650,41 +664,10 @@ class SSA_Tasker_Env(Env):
                     if pos + k + 1 < K:     # (the decision for the step after this one)
                         e.launch_agent_select(i, i, kind, log.data_ptr() + 4 * (pos + k + 1), fallback_ptr=fb.data_ptr() + 4 * (pos + k + 1))
                 e.flush_stats()
-                slots = [(i0 + 1 + k) % e.H for k in range(kk)]
-                stats = e.stats[slots, 0].cpu().numpy()          # synchronises the stream
-                upd = e.upd[slots, 0].cpu().numpy()
-            acts = log[pos:pos + kk].cpu().numpy()
-            self._ring_head = i0 + kk
-            self._fail_chunk_total = int(stats[-1][_lib.STAT_N_FAILED])
-            for k in range(kk):
-                self.i += 1
-                i, a = self.i, int(acts[k])
-                self.actions[i] = a
-                self._book_update(i, a, upd[k])
-                self._stats = stats[k]
-                if int(stats[k][_lib.STAT_N_FAILED]) != self._n_failed:
-                    self._record_failures(at_step=i)
-                done = self._reward_done(i, a, stats[k], self._argmax_sigma) or (i + 1 >= self.n)
-                self._argmax_sigma = int(stats[k][_lib.STAT_ARGMAX_SPOS])
-                r = self.rewards[i]
-                actions.append(a)
-                rewards.append(r if (self.obs_returned == 'flatten' or np.isfinite(r)) else np.float64(0.5))
-                dones.append(done)
-                if done:
-                    break
+                stats, upd = self._ring_chunk(i0, kk)
+            done = self._book_steps(log[pos:pos + kk].cpu().numpy(), stats, upd, i0 + kk, (actions, rewards, dones))
             pos += kk
-        slot = self.i % e.H
-        if self.obs_returned == 'aer':
-            from .. import device
-            M = e.trans[self.i % e.n_time].reshape(3, 3)
-            device.aer_obs(e.x_filter[slot], e.P_filter[slot], M, self._consts, out=self._aer_dev.view(self.m, 4))
-            self.observation[:] = e.caller_rows(self._aer_dev.view(self.m, 4)).cpu().numpy().reshape(-1)     # (a storage layout is kept here)
-            obs = self.observation
-        elif self.obs_returned == 'flatten':
-            obs = self._host_obs(e.caller_rows(e.obs[slot]).cpu().numpy().reshape(-1))
-        else:
-            obs = self._host_obs(e.caller_rows(e.obs[slot]).cpu().numpy())
-        return obs, np.asarray(actions, dtype=int), np.asarray(rewards), np.asarray(dones, dtype=bool)
+        return self._obs_out(refresh_aer_dev=True), np.asarray(actions, dtype=int), np.asarray(rewards), np.asarray(dones, dtype=bool)
 
     # ------------------------------------------------------------------ closed loop with ANY policy that lives on the GPU
     class PolicyView:
@@ -842,32 +825,16 @@ class SSA_Tasker_Env(Env):
         # GPU runs chunk c + 1.  (Round 4 measurement, profiles/r04_run_policy_timeline.txt: inside a replay the GPU idles < 1 us between
         # kernels, but synchronise - copy - book - replay left it idle for 16 us per step at chunk boundaries.)  An invalid action is
         # therefore reported one chunk late: the steps enqueued behind it have run (with no update: the kernel ignores an action out of range).
-        pend = None            # (i0, host arrays, event) of the replay whose bookkeeping is outstanding
-        state = {"done": False}
+        pend = None            # (host arrays, event) of the replay whose bookkeeping is outstanding
 
-        def book(i0, host, ev):
+        def book(host, ev):
+            nonlocal done
             ev.synchronize()
-            stats, upd, acts = host
-            self._ring_head = i_start + launched
-            self._fail_chunk_total = int(stats[-1][_lib.STAT_N_FAILED])
-            for k in range(G):
-                self.i += 1
-                i, a = self.i, int(acts[k])
-                if not (0 <= a < self.m):
-                    raise ValueError("run_policy: the policy chose action %d at step %d (valid: 0 .. %d)" % (a, i, self.m - 1))
-                self.actions[i] = a
-                self._book_update(i, a, upd[k])
-                self._stats = stats[k]
-                if int(stats[k][_lib.STAT_N_FAILED]) != self._n_failed:
-                    self._record_failures(at_step=i)
-                state["done"] = self._reward_done(i, a, stats[k], self._argmax_sigma) or (i + 1 >= self.n)
-                self._argmax_sigma = int(stats[k][_lib.STAT_ARGMAX_SPOS])
-                actions.append(a)
-                rewards.append(self.rewards[i] if (self.obs_returned == 'flatten' or np.isfinite(self.rewards[i])) else np.float64(0.5))
-                dones.append(state["done"])
+            stats, upd, acts = host       # (ring head: the replays run ahead of the booking)
+            done = self._book_steps(acts, stats, upd, i_start + launched, (actions, rewards, dones), check_actions=True)
         launched, i_start, gstream = 0, self.i, None      # steps enqueued by replays (self.i follows as the chunks are booked)
         try:
-            while use_graph and K - launched >= G and not state["done"]:
+            while use_graph and K - launched >= G and not done:
                 i0 = i_start + launched
                 ent = self._policy_graph(policy, G, i0)
                 if ent is None:
@@ -892,14 +859,14 @@ class SSA_Tasker_Env(Env):
                 launched += G
                 if pend is not None:
                     book(*pend)                    # chunk c - 1, while the GPU runs chunk c
-                pend = (i0, tuple(h.numpy() for h in hosts[slot]), copied)
+                pend = (tuple(h.numpy() for h in hosts[slot]), copied)
             if pend is not None:
                 book(*pend)
         finally:
             if gstream is not None:
                 torch.cuda.current_stream().wait_stream(gstream)
                 e.env_time0.zero_()
-        pos, done = launched, state["done"]
+        pos = launched
         while pos < K and not done:
             kk = (K - pos) if self.reward_type == 'trinary' else min(K - pos, e.H - 1)
             i0 = self.i
@@ -918,26 +885,7 @@ class SSA_Tasker_Env(Env):
             upd = upd_d.cpu().numpy()
             acts = torch.cat([a.reshape(1) for a in acts_d]).cpu().numpy()
             self.i = i0
-            self._ring_head = i0 + kk
-            self._fail_chunk_total = int(stats[-1][_lib.STAT_N_FAILED])
-            for k in range(kk):
-                self.i += 1
-                i, a = self.i, int(acts[k])
-                if not (0 <= a < self.m):
-                    raise ValueError("run_policy: the policy chose action %d at step %d (valid: 0 .. %d)" % (a, i, self.m - 1))
-                self.actions[i] = a
-                self._book_update(i, a, upd[k])
-                self._stats = stats[k]
-                if int(stats[k][_lib.STAT_N_FAILED]) != self._n_failed:
-                    self._record_failures(at_step=i)
-                done = self._reward_done(i, a, stats[k], self._argmax_sigma) or (i + 1 >= self.n)
-                self._argmax_sigma = int(stats[k][_lib.STAT_ARGMAX_SPOS])
-                r = self.rewards[i]
-                actions.append(a)
-                rewards.append(r if (self.obs_returned == 'flatten' or np.isfinite(r)) else np.float64(0.5))
-                dones.append(done)
-                if done:
-                    break
+            done = self._book_steps(acts, stats, upd, i0 + kk, (actions, rewards, dones), check_actions=True)
             pos += kk
         return np.asarray(actions, dtype=int), np.asarray(rewards), np.asarray(dones, dtype=bool)
 
