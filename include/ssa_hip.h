@@ -347,11 +347,16 @@ int ssa_aer_obs_f64(const double *x, const double *P, const double *M, const ssa
 /* ------------------------------------------------ device-side agent primitives
  * Per-object scores the reference's heuristic agents compute in Python loops (agents.py:7-81):
  *   scores[0][j] = trace(P_cur[j])                        agent_naive_greedy / agent_visible_greedy
- *   scores[1][j] = log(det P_cur[j] / det P_prev[j])      agent_shannon        (NaN if either det <= 0)
+ *   scores[1][j] = log(det P_cur[j] / det P_prev[j])      agent_shannon        (NaN if either Cholesky fails, below)
  *   scores[2][j] = |x_cur[j][:3] - x_true[j][:3]|         agent_pos_error_greedy
  *   scores[3][j] = |x_cur[j][3:] - x_true[j][3:]|         agent_vel_error_greedy
  *   mask[j]      = elevation(x_true[j]) >= obs_limit      visible_objects()    (:410-425)
- * P_prev may be NULL (scores[1] = NaN). */
+ * P_prev may be NULL (scores[1] = NaN).  scores[1] is 2 log(prod diag U) of the plain Cholesky factor U of each matrix's upper
+ * triangle, and NaN whenever either factorisation fails -- not only when a determinant is <= 0: a matrix with two negative
+ * eigenvalues has det > 0 and a finite reference score, and late in an episode the filter leaves covariances whose smallest
+ * eigenvalue is negative at rounding level (at most 3e-16 of the largest, diagonal entries 1e18 .. 1e21; 1-3 objects per step of
+ * tests/episode_workload.py's seed-7 episode from step 300 on).  The reference's score on those is set by rounding, not by the
+ * filter, and the arg-max skips them (tests/test_agent_ops.py). */
 int ssa_agent_scores_f64(const double *x_true, const double *x_cur, const double *P_cur, const double *P_prev,
                          const double *M, const ssa_consts *c_host, double *scores, uint8_t *mask, int64_t n,
                          void *stream);

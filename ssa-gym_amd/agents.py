@@ -5,8 +5,13 @@ as much as the env step itself; here one kernel produces the 
 the per-object scores from the HBM-resident state and a second one does the masked arg-max, so an
 agent call moves 16 bytes to the host.
 
-Deviation: objects whose score is NaN (non positive definite covariance in the Shannon ratio) are
-skipped by the arg-max; numpy's argmax would return the first NaN's index."""
+Deviations: objects whose score is NaN are skipped by the arg-max; numpy's argmax would return the first NaN's index.  The
+Shannon score log(det P / det P_prev) comes from plain Cholesky factors (ssa_hip.h, ssa_agent_scores_f64) and is NaN whenever
+either factorisation fails, not only where the ratio of determinants is <= 0.  A matrix with two negative eigenvalues (det > 0)
+therefore gets no score here but a finite one in the reference; in a filter's own covariances this happens late in an episode
+(1-3 objects per step of the seed-7 test episode from step 300 on), on matrices whose negative eigenvalue is at rounding level
+(at most 3e-16 of the largest, diagonal entries 1e18 .. 1e21), where the reference's score is set by rounding, not by the
+filter.  On those steps the two agents may pick different objects."""
 import numpy as np
 
 from . import _lib

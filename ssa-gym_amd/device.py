@@ -221,6 +221,35 @@ def visible_mask_at(x_true, trans, env_time, time_offset, consts):
     return mask
 
 
+def agent_select_workspace(n_obj, n_env, device):
+    """device scratch of ssa_agent_select_f64 for n_env envs of n_obj objects (one call at a time)"""
+    nbytes = int(_lib.load().ssa_agent_select_workspace_bytes(int(n_obj), int(n_env)))
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
+def agent_select(consts, kind, x_true, x_cur, P_cur, P_prev, trans, env_time, time_offset, fallback=None, workspace=None, obj_ids=None):
+    """ssa_agent_select_f64 (ssa_agent_select_ids_f64 with obj_ids, one env): for every env e -- objects e*n_obj .. +n_obj of the
+    [n_env * n_obj] state, n_env = env_time.shape[0] -- the first maximum of agent `kind`'s score (_lib.AGENT_*) over the objects it
+    considers, NaN skipped, or fallback[e] when none qualifies (-1 without fallback).  Returns (action int32 [n_env], pick int64
+    [n_env, 2]: the arg-max, -1 = none, and the winning score's bit pattern)."""
+    lib = _lib.load()
+    n_env = env_time.shape[0]
+    n_obj = x_cur.shape[0] // n_env
+    dev = x_cur.device
+    ws = agent_select_workspace(n_obj, n_env, dev) if workspace is None else workspace
+    action = torch.empty(n_env, dtype=torch.int32, device=dev)
+    pick = torch.empty((n_env, 2), dtype=torch.int64, device=dev)
+    args = (C.byref(consts), int(kind), _chk(x_true, "x_true"), _chk(x_cur, "x_cur"), _chk(P_cur, "P_cur"),
+            _chk(P_prev, "P_prev") if P_prev is not None else None, _chk(trans, "trans"), _chk(env_time, "env_time", torch.int32),
+            int(time_offset), int(trans.shape[0]), _chk(fallback, "fallback", torch.int32) if fallback is not None else None,
+            _chk(ws, "workspace", torch.uint8), _chk(action, "action", torch.int32), _chk(pick, "pick", torch.int64), n_obj, n_env)
+    if obj_ids is None:
+        _lib.check(lib.ssa_agent_select_f64(*args, _stream()), "ssa_agent_select_f64")
+    else:
+        _lib.check(lib.ssa_agent_select_ids_f64(*args, _chk(obj_ids, "obj_ids", torch.int32), _stream()), "ssa_agent_select_ids_f64")
+    return action, pick
+
+
 def masked_argmax(score, mask=None):
     """index of the first maximum of score[mask != 0] (NaN skipped), -1 if nothing is selected."""
     lib = _lib.load()
