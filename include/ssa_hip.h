@@ -506,6 +506,33 @@ typedef struct ssa_lookahead_out {
  * object = e * n_obj + its index as the caller numbers it (obj_ids, as obs_mirror / aer_out): a storage layout never shows. */
 int ssa_lookahead_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_lookahead_out *out, void *stream);
 
+/* ---------------------------------------------------------------- sensor networks: several ground sensors in one step
+ * EXTENSION without reference counterpart (the reference has one observer).  One env step in which each of n_sensor ground sites
+ * observes one object: sensor s updates object action[s] exactly as ssa_env_step_f64 updates the env's action, with ITS site's
+ * geometry (enu, obs_itrs), elevation mask and measurement noise covariance R -- the visibility test of the true state as seen from
+ * site s, z_true, the innovation, S, K and the failure handling.  Everything else -- the predict of every object, observations,
+ * metrics, reward statistics, failure records (per object), obs_mirror / aer_out, obj_ids, spos_tiles, every launch_mask bit but
+ * SSA_LAUNCH_INLINE_ACTION -- comes from ssa_step_params with unchanged meaning; its `actions` / action0 and `upd` are not read (set
+ * the update records' destination here).  aer_out is hx of ssa_consts' observer (the primary sensor: the caller passes sensor 0's).
+ *   action[s] < 0 or >= n_obj: sensor s is idle.  Two sensors on one object: the lowest-numbered one updates it; the others are idle.
+ *   An idle sensor, every sensor of a step the update_interval skips, and a sensor whose object has failed get a record with
+ *   SSA_UPD_ACTION = -1 (OBS_TAKEN = VISIBLE = 0 unless the update was attempted).
+ *   Measurement noise of sensor s: z_noise + s*zn_stride_sensor + i*zn_stride_time + action[s]*zn_stride_obj (ssa_step_params strides).
+ * n_env == 1 only (SSA_E_UNSUPPORTED otherwise); 1 <= n_sensor <= SSA_MAX_SENSORS. */
+#define SSA_MAX_SENSORS 8
+typedef struct ssa_sensor_params {
+    int32_t n_sensor;                      /* S */
+    int32_t reserved;
+    int32_t action[SSA_MAX_SENSORS];       /* object sensor s observes, BY VALUE (< 0: idle) */
+    double enu[SSA_MAX_SENSORS][9];        /* ecef2aer's trans_uvw_ecef matrix of site s (as ssa_consts.enu) */
+    double obs_itrs[SSA_MAX_SENSORS][3];   /* lla2ecef(site s) */
+    double obs_limit[SSA_MAX_SENSORS];     /* elevation mask of site s [rad] */
+    double R[SSA_MAX_SENSORS][9];          /* measurement noise covariance of sensor s */
+    int64_t zn_stride_sensor;              /* doubles between the noise tables of consecutive sensors */
+    double *upd;                           /* [S][SSA_UPD_STRIDE] update record per sensor, or NULL */
+} ssa_sensor_params;
+int ssa_env_step_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_sensor_params *s_host, void *stream);
+
 /* ------------------------------------------------ all-gather by direct peer stores (SURVEY 8e "Collective")
  * The reference runs one env per process and has no exchange step; the sharded env of this library (one env's objects spread over the
  * GPUs of a node) reassembles every step's observation block + statistics words on every rank.  These two entry points do that without a

@@ -65,6 +65,14 @@ class ssa_lookahead_out(C.Structure):
     ]
 
 
+class ssa_sensor_params(C.Structure):
+    _fields_ = [
+        ("n_sensor", C.c_int32), ("reserved", C.c_int32), ("action", C.c_int32 * 8),
+        ("enu", (C.c_double * 9) * 8), ("obs_itrs", (C.c_double * 3) * 8), ("obs_limit", C.c_double * 8), ("R", (C.c_double * 9) * 8),
+        ("zn_stride_sensor", C.c_int64), ("upd", c_dp),
+    ]
+
+
 # constants of include/ssa_hip.h
 E_INVALID, E_LAUNCH, E_UNSUPPORTED = -1, -2, -3
 ABI_VERSION = 23
@@ -86,6 +94,7 @@ INLINE_ENVS = 8
 LOOP_ARGMAX_SPOS, LOOP_DEBUG_WITHHOLD = 1, 2
 FAIL_STRIDE, FAIL_ENV, FAIL_OBJ, FAIL_STATUS, FAIL_TIME, FAIL_ERR = 8, 0, 1, 2, 3, 4
 AGENT_NAIVE_GREEDY, AGENT_VISIBLE_GREEDY, AGENT_SHANNON, AGENT_POS_ERROR, AGENT_VEL_ERROR = range(5)
+MAX_SENSORS = 8
 LOOK_NSCORE, LOOK_TRACE_GAIN, LOOK_POS_TRACE_GAIN, LOOK_INFO_GAIN = 3, 0, 1, 2
 STAT_STRIDE, STAT_MAX_DPOS, STAT_CNT_LT_1E4, STAT_CNT_LT_1E7, STAT_ARGMAX_SPOS, STAT_N_FAILED, STAT_MAX_SPOS = 8, 0, 1, 2, 3, 4, 5
 
@@ -102,6 +111,7 @@ SIGNATURES = {
     "ssa_env_rollout_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_rollout_params), c_dp]),
     "ssa_env_closed_loop_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_closed_loop_params), c_dp]),
     "ssa_lookahead_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_lookahead_out), c_dp]),
+    "ssa_env_step_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params), c_dp]),
     "ssa_closed_loop_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
     "ssa_env_step_work_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
     "ssa_reward_stats_f64": (C.c_int, [c_dp, c_dp, c_dp, c_dp, C.c_int64, C.c_int32, c_dp]),

@@ -1011,6 +1011,30 @@ struct ActAll {
 };
 template <class ACT> struct ActIsAll { static constexpr bool v = false; };
 template <> struct ActIsAll<ActAll> { static constexpr bool v = true; };
+// ActSensors (step_sensors_kernel, ssa_env_step_sensors_f64; one env): up to SSA_MAX_SENSORS sites each select one object.  A row is
+// selected if any sensor's action is its caller index; it then carries the lowest such sensor's index, and the update block reads that
+// sensor's site, elevation mask, R, noise table and record slot instead of ssa_consts' / ssa_step_params'.  `s` points at the kernel's
+// argument block: the actions and the geometry are wave-uniform (scalar) loads.
+struct ActSensors {
+    static constexpr bool late = false;
+    const ssa_sensor_params* s;
+    SSA_DEV int get() { return -1; }
+    SSA_DEV void before_wait(Tiles&, int, int) {}
+    SSA_DEV void mid_step(Tiles&, int) {}
+};
+// the sensor that updates the object the caller calls `jid`: the lowest-numbered one whose action it is, -1 for none
+SSA_DEV int sensor_index(const ssa_sensor_params* s, int64_t jid)
+{
+    int sid = -1;
+#pragma unroll
+    for (int k = SSA_MAX_SENSORS - 1; k >= 0; --k)
+        if (k < s->n_sensor && s->action[k] >= 0 && (int64_t)s->action[k] == jid) sid = k;
+    return sid;
+}
+template <class ACT> struct ActIsSensors { static constexpr bool v = false; };
+template <> struct ActIsSensors<ActSensors> { static constexpr bool v = true; };
+template <class ACT> SSA_DEV const ssa_sensor_params* sensors_of(const ACT&) { return nullptr; }
+template <> SSA_DEV const ssa_sensor_params* sensors_of<ActSensors>(const ActSensors& a) { return a.s; }
 SSA_DEV double logdet_chol(const double (&A)[21]);   // (defined with the agents' scores)
 // the lookahead's outputs of row g (lane l of it) at the caller's row `orow`.  P- / x- are the tile after the predict and the
 // failure sentinels (what a step leaves for an object it does not update); P+ (row g's turn of Phase 2, left at t.UA[g * 117]) where
@@ -1076,6 +1100,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // env's step 123.9 -> 130.4 us although its host side got 4 us shorter.)
     constexpr bool FOLD_OK = (TILE == 0);
     constexpr bool ALL = ActIsAll<ACT>::v;   // the lookahead: every row updated hypothetically, nothing committed (ActAll)
+    constexpr bool SENS = ActIsSensors<ACT>::v;   // a sensor network: one update per sensor, each with its own site (ActSensors)
     int g = lane >> 4, l = lane & 15;
     int64_t obj = obj_in;
     // (TILE 0: the kernel issued the tile's loads from its preloaded pointer arguments before anything else.)  First thing here,
@@ -1100,6 +1125,9 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     } else if (ALL) {   // (no action: every row is selected)
         act = -1;
         tix = valid ? env_time_of<INL>(p, e) + p.time_offset : 0;
+    } else if (SENS) {   // (one env; the sensors' actions are matched below, against the row's caller index)
+        act = -1;
+        tix = valid ? env_time_of<INL>(p, 0) + p.time_offset : 0;
     } else if (p.n_env > 1) {
         act = valid ? env_action<INL>(p, e) : -1;
         tix = valid ? env_time_of<INL>(p, e) + p.time_offset : 0;
@@ -1123,7 +1151,13 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         jid = valid ? (int64_t)mine : 0;
         if (l == 0) t.Oid[g] = mine;
     }
-    bool my_update = ALL ? (valid && interval_ok) : (!ACT::late && valid && act >= 0 && (int64_t)act == jid && interval_ok);
+    int sid = -1;   // (ActSensors: the sensor that updates this row's object, -1 for none)
+    if constexpr (SENS) {
+        sid = valid ? sensor_index(sensors_of(asrc), jid) : -1;
+        act = (sid >= 0) ? (int)jid : -1;
+    }
+    bool my_update = ALL ? (valid && interval_ok) : SENS ? (sid >= 0 && interval_ok)
+                                                         : (!ACT::late && valid && act >= 0 && (int64_t)act == jid && interval_ok);
     // (ActLate: every row prefetches for its own object)
     const bool may_update = ACT::late ? (valid && interval_ok) : my_update;
     // ... and it issues ahead of its SIMD's other wavefronts from here on: at equal priority its predict runs at a fifth of the
@@ -1136,6 +1170,9 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         const int64_t aobj = ACT::late ? jid : (int64_t)act;   // (the measurement noise is indexed as the caller numbers the objects)
         const double* src = (l < 9) ? p.trans + (int64_t)tmod * 9 + l
                                     : p.z_noise + (int64_t)e * p.zn_stride_env + (int64_t)tmod * p.zn_stride_time + aobj * p.zn_stride_obj + (l - 9);
+        if constexpr (SENS) {
+            if (l >= 9) src += (int64_t)sid * sensors_of(asrc)->zn_stride_sensor;   // (the sensor's own noise table)
+        }
         upd_in = *src;
     }
 
@@ -1318,6 +1355,9 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         if (__any(my_update)) __builtin_amdgcn_s_setprio(3);
     }
     bool look_vis = false, look_taken = false;   // (ActAll: the row's visibility and whether its update ran, for the outputs)
+    // (ActSensors: the row's sensor matched again here rather than carried across the propagator)
+    const ssa_sensor_params* SP = sensors_of(asrc);
+    if constexpr (SENS) sid = valid ? sensor_index(SP, p.obj_ids ? (int64_t)t.Oid[g] : obj) : -1;
     if (__any(my_update)) {   // whole-wave branch: a wavefront without a selected object skips the block, its variables included
     bool upd_go = false, taken = false, visible = false, attempted = false;
     double z[3] = {0.0, 0.0, 0.0}, y_row[3] = {0.0, 0.0, 0.0};   // (y_row: lane 13 of the row keeps the innovation)
@@ -1329,7 +1369,8 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     static_assert(offsetof(Tiles, D) == offsetof(Tiles, UA) + sizeof(double) * OBJ_PER_WAVE * 36, "UA and D contiguous");
     static_assert(4 * 117 <= OBJ_PER_WAVE * 36 + 330 && 330 + 57 <= 408, "update staging fits");
     if (my_update) {
-        rec = (!ALL && p.upd) ? p.upd + (int64_t)e * SSA_UPD_STRIDE : nullptr;
+        if constexpr (SENS) rec = SP->upd ? SP->upd + (int64_t)sid * SSA_UPD_STRIDE : nullptr;
+        else rec = (!ALL && p.upd) ? p.upd + (int64_t)e * SSA_UPD_STRIDE : nullptr;
         // a filter that has failed (earlier, or in this step's predict) is skipped entirely (:293): no z_true, no record
         attempted = (st_new == SSA_ST_OK);
         if (attempted) {
@@ -1358,16 +1399,28 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
             // H1/H2: measurement of every sigma point (lanes 0-12) and of the true state (lane 13)
             double enu_vec[3];
             double el_mine;
+            double lim = 0.0;   // (ActSensors: the elevation mask of the row's sensor)
             {
                 double Mm[9], aer[3];
 #pragma unroll
                 for (int i = 0; i < 9; ++i) Mm[i] = M[i];
-                hx_aer_enu(sf, Mm, C.enu, C.obs_itrs, aer, enu_vec);
+                if constexpr (SENS) {
+                    // the rows of one sensor at a time (a waterfall over the sensors present), its site in scalar registers
+                    for (;;) {
+                        const int su = __builtin_amdgcn_readfirstlane(sid);
+                        if (sid == su) {
+                            hx_aer_enu(sf, Mm, SP->enu[su], SP->obs_itrs[su], aer, enu_vec);
+                            lim = SP->obs_limit[su];
+                            break;
+                        }
+                    }
+                } else hx_aer_enu(sf, Mm, C.enu, C.obs_itrs, aer, enu_vec);
                 el_mine = aer[1];
                 if (C.obs_type == SSA_OBS_AER) { z[0] = aer[0]; z[1] = aer[1]; z[2] = aer[2]; }
                 else { z[0] = sf[0]; z[1] = sf[1]; z[2] = sf[2]; }
             }
-            visible = row_bcast<13>(el_mine) >= C.obs_limit;  // object_visible(): elevation of the TRUE state (:418-425)
+            if constexpr (SENS) visible = row_bcast<13>(el_mine) >= lim;   // (as seen from the row's sensor)
+            else visible = row_bcast<13>(el_mine) >= C.obs_limit;  // object_visible(): elevation of the TRUE state (:418-425)
             if (rec && l == 13) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) rec[SSA_UPD_Z_TRUE + c] = z[c];
@@ -1429,6 +1482,8 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         while (pend) {   // (several selected objects in one wavefront -- vectorised envs of fewer than four objects -- take turns)
             const int gu = (__ffsll((long long)pend) - 1) >> 4;
             pend &= ~(0xFFFFull << (gu * 16));
+            const double* Rm = C.R;   // (ActSensors: R of row gu's sensor, a wave-uniform index)
+            if constexpr (SENS) Rm = SP->R[__builtin_amdgcn_readlane(sid, gu * 16)];
             if (g == gu && l == 13) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) W[54 + c] = y_row[c];
@@ -1456,8 +1511,8 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                 if (ij < 3 && ri < 6) W[9 + ri * 3 + ij] = acc;
                 if (ij < 3 && ri >= 6 && ri < 9 && ri - 6 <= ij) {   // S symmetric by construction: the upper triangle, mirrored
                     const int a = ri - 6;
-                    W[a * 3 + ij] = acc + C.R[a * 3 + ij];
-                    W[ij * 3 + a] = acc + C.R[ij * 3 + a];
+                    W[a * 3 + ij] = acc + Rm[a * 3 + ij];
+                    W[ij * 3 + a] = acc + Rm[ij * 3 + a];
                 }
             }
             wave_lds_sync();
@@ -1527,7 +1582,8 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     if (my_update && rec && l == 0) {
         rec[SSA_UPD_OBS_TAKEN] = taken ? 1.0 : 0.0;
         rec[SSA_UPD_VISIBLE] = visible ? 1.0 : 0.0;
-        rec[SSA_UPD_ACTION] = attempted ? (double)(ACT::late ? act : env_action<INL>(p, e)) : -1.0;   // (my_update: the env's action IS this object)
+        if constexpr (SENS) rec[SSA_UPD_ACTION] = attempted ? (double)(p.obj_ids ? (int64_t)t.Oid[g] : obj) : -1.0;   // (the sensor's action IS this object)
+        else rec[SSA_UPD_ACTION] = attempted ? (double)(ACT::late ? act : env_action<INL>(p, e)) : -1.0;   // (my_update: the env's action IS this object)
     }
     if constexpr (ALL) {
         look_vis = visible;
@@ -1552,6 +1608,22 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         rec[SSA_UPD_VISIBLE] = 0.0;
         rec[SSA_UPD_ACTION] = -1.0;
       }
+    }
+    if constexpr (SENS) {   // sensors that update nobody -- idle, out of range, a lower sensor's object, a step the interval skips: a cleared record
+        if (SP->upd && valid && obj == 0 && l == 0) {
+            for (int k = 0; k < SP->n_sensor; ++k) {
+                const int a = SP->action[k];
+                bool owns = a >= 0 && (int64_t)a < p.n_obj && interval_ok;
+                for (int q = 0; q < k; ++q)
+                    if (SP->action[q] == a) owns = false;
+                if (!owns) {
+                    double* rec = SP->upd + (int64_t)k * SSA_UPD_STRIDE;
+                    rec[SSA_UPD_OBS_TAKEN] = 0.0;
+                    rec[SSA_UPD_VISIBLE] = 0.0;
+                    rec[SSA_UPD_ACTION] = -1.0;
+                }
+            }
+        }
     }
 
     // ---- F1: failed filters carry the sentinels (ssa_tasker_simple_2.py:157-158, 369-382)
@@ -1891,6 +1963,71 @@ __global__ void __launch_bounds__(64, SSA_STEP_WAVES) lookahead_kernel(int ntile
         ActAll all{&k.o};
         process_wave<PROP, 1>(t, k.k.c, k.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, nbase, ncnt, tile, all);
         wave_lds_sync();   // the tile's LDS reads precede the next tile's commit
+    }
+}
+
+// A sensor network's step (ssa_env_step_sensors_f64): step_fast_kernel's launch forms with ActSensors -- the deferred fold's extra
+// wavefronts and the issue-priority rotation included; the sensors' block travels behind the step's in the argument segment.
+struct SensK {
+    StepK k;
+    ssa_sensor_params s;
+};
+struct StepSensorsArgs {   // the kernarg segment of step_sensors_kernel (see StepFastArgs)
+    int ntiles, nwork;
+    const double *pre_P_in, *pre_x_in, *pre_x_true_in;
+    const int32_t* pre_status;
+    SensK k;
+};
+typedef const __attribute__((address_space(4))) SensK* SensKernargPtr;
+template <int PROP, bool MULTI>
+__global__ void __launch_bounds__(64, SSA_STEP_WAVES) step_sensors_kernel(int ntiles, int nwork, const double* pre_P_in,
+                                                                          const double* pre_x_in, const double* pre_x_true_in,
+                                                                          const int32_t* pre_status, const SensK k_arg)
+{
+    __shared__ Tiles t;
+    int lane = threadIdx.x;
+    const int unit = (int)blockIdx.x;
+    if (unit >= nwork) {   // deferred fold of the previous step's statistics (one env: one extra wavefront)
+        fold_stat_shards((unsigned long long*)k_arg.k.p.stat_shards_prev, k_arg.k.p.stats_prev, unit - nwork, lane,
+                         (const unsigned long long*)k_arg.k.p.spos_tiles_prev, k_arg.k.p.n_obj);
+        return;
+    }
+    const int64_t total = k_arg.k.p.n_obj;
+    TileRegs pf;
+    int tile = xcd_tile(unit, nwork);
+    if (!MULTI) {
+        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
+        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
+        tile_dma_issue(t, pf, pre_P_in, pre_x_in, pre_x_true_in, pre_status, lane, base, cnt);
+        ActSensors sens{&k_arg.s};
+        process_wave<PROP, 0>(t, k_arg.k.c, k_arg.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, sens);
+        return;
+    }
+    {
+        const int64_t b0 = (int64_t)tile * OBJ_PER_WAVE;
+        tile_issue(pf, k_arg.k.p, lane, b0, tile < ntiles ? (int)((total - b0) < OBJ_PER_WAVE ? (total - b0) : OBJ_PER_WAVE) : 0);
+    }
+    SensKernargPtr kp = (SensKernargPtr)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(StepSensorsArgs, k));
+    unsigned wave_slot, turn = 0;   // issue priority rotated per tile, as step_fast_kernel
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(wave_slot));
+    for (; tile < ntiles; tile += nwork) {
+        switch ((wave_slot + turn++) & 3u) {
+            case 0: __builtin_amdgcn_s_setprio(0); break;
+            case 1: __builtin_amdgcn_s_setprio(1); break;
+            case 2: __builtin_amdgcn_s_setprio(2); break;
+            default: __builtin_amdgcn_s_setprio(3); break;
+        }
+        asm volatile("" : "+s"(kp));
+        asm volatile("" : "+v"(lane));
+        const SensK& k = *(const SensK*)kp;
+        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
+        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
+        const int nt = tile + nwork;
+        const int64_t nbase = (int64_t)nt * OBJ_PER_WAVE;
+        const int ncnt = nt < ntiles ? (int)((total - nbase) < OBJ_PER_WAVE ? (total - nbase) : OBJ_PER_WAVE) : 0;
+        ActSensors sens{&k.s};
+        process_wave<PROP, 1>(t, k.k.c, k.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, nbase, ncnt, tile, sens);
+        wave_lds_sync();   // the tile's LDS reads (store) precede the next tile's commit
     }
 }
 
@@ -3302,13 +3439,16 @@ static int post_parts(int64_t n_obj, int32_t n_env)
     return (int)want;
 }
 
-static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stream, hipEvent_t ev0, hipEvent_t ev1)
+// sens: a sensor network's step (ssa_env_step_sensors_f64; checked by the caller) -- step_sensors_kernel instead of step_fast_kernel
+static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stream, hipEvent_t ev0, hipEvent_t ev1,
+                       const ssa_sensor_params* sens = nullptr)
 {
     if (!c || !p || p->n_obj <= 0 || p->n_env <= 0) return SSA_E_INVALID;
     if (!p->x_true_in || !p->x_true_out || !p->x_in || !p->x_out || !p->P_in || !p->P_out || !p->status ||
         !p->obs || !p->metrics || !p->trans || !p->env_time || !p->z_noise || !p->stat_ws)
         return SSA_E_INVALID;
-    if (p->launch_mask & SSA_LAUNCH_INLINE_ENVS) {
+    if (sens) {   // (the actions are the sensors'; the env's action word and record are not read)
+    } else if (p->launch_mask & SSA_LAUNCH_INLINE_ENVS) {
         if (p->n_env > SSA_INLINE_ENVS || (p->launch_mask & SSA_LAUNCH_INLINE_ACTION)) return SSA_E_INVALID;
     } else if (p->launch_mask & SSA_LAUNCH_INLINE_ACTION) {
         if (p->n_env != 1) return SSA_E_INVALID;
@@ -3346,7 +3486,26 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     if (c->propagator != SSA_PROP_FG && c->propagator != SSA_PROP_ELEMENTS && c->propagator != SSA_PROP_J2_RK4 && c->propagator != SSA_PROP_HYBRID) return SSA_E_INVALID;
     if (c->propagator == SSA_PROP_J2_RK4 && (c->rk4_substeps < 1 || c->rk4_substeps > 4096)) return SSA_E_INVALID;
     const int prop = c->propagator;
-    if (mask & 1u) {   // (ev0, ev1: dispatch timestamps of this kernel for ssa_env_step_profiled_f64, else null)
+    if ((mask & 1u) && sens) {
+        SensK ks;
+        ks.k = k;
+        ks.k.p.upd = nullptr;
+        ks.k.p.actions = nullptr;
+        ks.k.p.launch_mask &= ~SSA_LAUNCH_INLINE_ACTION;
+        ks.s = *sens;
+        const int nt = (int)ntiles;
+        if (per_wave == 1) {
+            if (prop == SSA_PROP_FG) hipExtLaunchKernelGGL((step_sensors_kernel<1, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
+            else if (prop == SSA_PROP_ELEMENTS) hipExtLaunchKernelGGL((step_sensors_kernel<0, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
+            else if (prop == SSA_PROP_HYBRID) hipExtLaunchKernelGGL((step_sensors_kernel<3, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
+            else hipExtLaunchKernelGGL((step_sensors_kernel<2, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
+        } else {
+            if (prop == SSA_PROP_FG) hipExtLaunchKernelGGL((step_sensors_kernel<1, true>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
+            else if (prop == SSA_PROP_ELEMENTS) hipExtLaunchKernelGGL((step_sensors_kernel<0, true>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
+            else if (prop == SSA_PROP_HYBRID) hipExtLaunchKernelGGL((step_sensors_kernel<3, true>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
+            else hipExtLaunchKernelGGL((step_sensors_kernel<2, true>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
+        }
+    } else if (mask & 1u) {   // (ev0, ev1: dispatch timestamps of this kernel for ssa_env_step_profiled_f64, else null)
         const int nt = (int)ntiles;
         if (per_wave == 1) {
             if (prop == SSA_PROP_FG) hipExtLaunchKernelGGL((step_fast_kernel<1, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
@@ -3382,6 +3541,16 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
 int ssa_env_step_f64(const ssa_consts* c, const ssa_step_params* p, void* stream)
 {
     return step_launch(c, p, stream, nullptr, nullptr);
+}
+int ssa_env_step_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, void* stream)
+{
+    if (!c || !p || !sp) return SSA_E_INVALID;
+    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
+    if (p->n_env != 1) return SSA_E_UNSUPPORTED;
+    if (sp->zn_stride_sensor < 0 || (sp->n_sensor > 1 && sp->zn_stride_sensor == 0)) return SSA_E_INVALID;
+    for (int k = 0; k < sp->n_sensor; ++k)
+        if (!(sp->obs_limit[k] == sp->obs_limit[k])) return SSA_E_INVALID;
+    return step_launch(c, p, stream, nullptr, nullptr, sp);
 }
 // dispatch-timestamp event pairs, created on first use (a ring, so that back-to-back launches can be timed
 // without draining the queue after each of them)

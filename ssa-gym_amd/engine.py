@@ -305,7 +305,7 @@ class HotPathEngine:
 
     def launch_step(self, slot_in, slot_out, time_offset, actions_ptr=None, stream=None, aer_out=0, stats_out=0, upd_out=0,
                     fast_stats=False, defer_fold=False, profile_slot=None, shards_out=0, shards_clear=0, aer_cols=4, action=None,
-                    obs_mirror=0, fold_inside=False, env_words=None, argmax_spos=False, mirror_f32=False):
+                    obs_mirror=0, fold_inside=False, env_words=None, argmax_spos=False, mirror_f32=False, sensors=None):
         """enqueue the step; asynchronous, no host sync.  fast_stats: statistics by the step kernel's atomics (two
         launches, no arg-max of sigma_pos).  defer_fold (with fast_stats): ONE launch -- this step's
         statistics are folded by extra wavefronts of the NEXT deferred step, or by flush_stats().  action (one env): the
@@ -313,7 +313,9 @@ class HotPathEngine:
         destination of the observation rows (host-mapped pinned memory: the observation reaches the host from inside the kernel).
         env_words = (time indices, actions) of all envs (n_env <= 8) by value in the parameter block (SSA_LAUNCH_INLINE_ENVS).
         argmax_spos (with fast_stats): np.argmax / np.max of sigma_pos in the step's statistics on the one-launch paths as well
-        (ssa_step_params.spos_tiles; the 'shaped' reward) -- needs self.supports_argmax."""
+        (ssa_step_params.spos_tiles; the 'shaped' reward) -- needs self.supports_argmax.
+        sensors: an ssa_sensor_params block (host.make_sensor_params, actions and record destination set): the step of a sensor network
+        (ssa_env_step_sensors_f64; see launch_step_sensors) -- `action` / actions_ptr / upd_out are then not used."""
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
         if shards_out:
             fast_stats, defer_fold = True, False
@@ -346,15 +348,38 @@ class HotPathEngine:
         else:
             p.launch_mask = (_lib.LAUNCH_DEFER_FOLD if defer else 0) | inline
             p.stat_shards_prev, p.stats_prev, p.spos_tiles_prev = 0, 0, 0
-        if profile_slot is None:
+        if sensors is not None:
+            if profile_slot is not None:
+                raise _lib.SsaHipError("profile_slot: the step of a sensor network is not profiled by event pairs")
+            rc = self._lib.ssa_env_step_sensors_f64(self._cref, pref, C.byref(sensors), s)
+        elif profile_slot is None:
             rc = self._lib.ssa_env_step_f64(self._cref, pref, s)
         else:   # the dominant launch bracketed by event pair `profile_slot` (read back with profile_ms)
             rc = self._lib.ssa_env_step_profiled_f64(self._cref, pref, s, int(profile_slot))
         if rc:
-            raise _lib.SsaHipError("ssa_env_step_f64 failed with code %d" % rc)
+            raise _lib.SsaHipError("%s failed with code %d" % ("ssa_env_step_sensors_f64" if sensors is not None else "ssa_env_step_f64", rc))
         if defer:
             self._fold_pending = (self._shard_cur, stats_ptr, argmax)
             self._shard_cur ^= 1
+
+    def launch_step_sensors(self, slot_in, slot_out, time_offset, sensors, actions, upd_out, stream=None, **kw):
+        """enqueue the step of a sensor network (include/ssa_hip.h: ssa_env_step_sensors_f64; one env): sensor s observes object
+        actions[s] (< 0: idle; two sensors on one object: the lower one updates it) with its own site, elevation mask, R and noise table
+        z_noise[s * sensors.zn_stride_sensor ...]; the per-sensor update records go to `upd_out` (a pointer to [S][UPD_STRIDE] doubles, may
+        be 0).  `sensors`: host.make_sensor_params(); its action words and record pointer are set here.  Every other keyword as
+        launch_step (fast_stats, fold_inside, argmax_spos, obs_mirror, aer_out, stats_out, ...).  Asynchronous, no host sync."""
+        if self.E != 1:
+            raise _lib.SsaHipError("a sensor network's step covers one env (n_env == 1)")
+        S = int(sensors.n_sensor)
+        if len(actions) != S:
+            raise _lib.SsaHipError("launch_step_sensors: %d actions for %d sensors" % (len(actions), S))
+        need = (S - 1) * int(sensors.zn_stride_sensor) + (self.n_time - 1) * self.zn_stride_time + (self.m - 1) * int(self._p.zn_stride_obj) + 3
+        if self.z_noise.numel() < need:
+            raise _lib.SsaHipError("z_noise: %d values needed for %d sensors, got %d" % (need, S, self.z_noise.numel()))
+        for k in range(S):
+            sensors.action[k] = int(actions[k])
+        sensors.upd = int(upd_out)
+        self.launch_step(slot_in, slot_out, time_offset, stream=stream, sensors=sensors, **kw)
 
     LOOKAHEAD_PARTS = ("x_prior", "P_prior", "P_post")
 

@@ -1,6 +1,8 @@
 """Resolution of the operator plug points of an env_config dict (envs/__init__.py:23-28 of the reference) into
 the fused-kernel variant, shared by SSA_Tasker_Env and SSA_Tasker_VecEnv so that both accept -- and refuse --
 exactly the same configurations."""
+import numpy as np
+
 from . import dynamics
 
 _MODELS = {(("hx", "aer"), ("mean_z", "uvw"), ("residual_z", "aer")): 'aer',
@@ -57,3 +59,38 @@ def kernel_consts(config, Q, R, dt, obs_limit_rad, obs_lla):
                               propagator=propagator, resample=bool(config.get('resample_sigmas', False)),
                               update_interval=config['update_interval'], covariance=config.get('covariance_form'), **kw)
     return consts, model
+
+
+MAX_SENSORS = 8
+
+
+def resolve_sensors(config):
+    """the sensor network of a config dict (EXTENSION, no reference counterpart), or None without config['observers']:
+    {'sites': [(lat, lon, h)] * S (degrees, degrees, metres), 'obs_limit': [S] degrees or None, 'z_sigma': [S] or None}.
+    config['observers'] lists 1 <= S <= 8 sites; the optional config['sensor_obs_limit'] / config['sensor_z_sigma'] give per-sensor
+    values (S of them; default: the scalar obs_limit / z_sigma / R).  Anything else raises ValueError."""
+    sites = config.get('observers')
+    lim, zs = config.get('sensor_obs_limit'), config.get('sensor_z_sigma')
+    if sites is None:
+        if lim is not None or zs is not None:
+            raise ValueError("config['sensor_obs_limit'] / config['sensor_z_sigma'] need config['observers']")
+        return None
+    try:
+        arr = np.asarray(sites, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("config['observers'] must be a list of (lat, lon, h) sites") from None
+    if arr.ndim != 2 or arr.shape[1] != 3 or not 1 <= arr.shape[0] <= MAX_SENSORS or not np.all(np.isfinite(arr)):
+        raise ValueError("config['observers'] must list 1 .. %d sites (lat, lon, h), got %r" % (MAX_SENSORS, sites))
+    S = arr.shape[0]
+    if lim is not None:
+        lim = np.asarray(lim, dtype=np.float64)
+        if lim.shape != (S,) or not np.all(np.isfinite(lim)):
+            raise ValueError("config['sensor_obs_limit'] must give one elevation mask (degrees) per sensor: %d" % S)
+        lim = [float(v) for v in lim]
+    if zs is not None:
+        if len(zs) != S:
+            raise ValueError("config['sensor_z_sigma'] must give one z_sigma per sensor: %d" % S)
+        zs = [np.asarray(z, dtype=np.float64) for z in zs]
+        if any(z.shape != (3,) or not np.all(np.isfinite(z)) or np.any(z < 0) for z in zs):
+            raise ValueError("config['sensor_z_sigma']: every entry is a z_sigma of three non-negative values")
+    return {'sites': [tuple(float(v) for v in row) for row in arr], 'obs_limit': lim, 'z_sigma': zs}

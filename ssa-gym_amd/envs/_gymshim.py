@@ -78,9 +78,25 @@ except Exception:  # noqa: BLE001
             def __repr__(self):
                 return "Box%s" % (self.shape,)
 
+        class MultiDiscrete(_Space):
+            def __init__(self, nvec):
+                self.nvec = np.asarray(nvec, dtype=np.int64)
+                super().__init__(self.nvec.shape, np.int64)
+
+            def sample(self):
+                return (self._rng.random_sample(self.nvec.shape) * self.nvec).astype(np.int64)
+
+            def contains(self, x):
+                x = np.asarray(x)
+                return x.shape == self.shape and x.dtype.kind in "iu" and bool(np.all(x >= 0) and np.all(x < self.nvec))
+
+            def __repr__(self):
+                return "MultiDiscrete(%s)" % (self.nvec,)
+
         class spaces:  # noqa: N801 - mirrors the module name
             Discrete = Discrete
             Box = Box
+            MultiDiscrete = MultiDiscrete
 
 
 # ---- old-gym seeding (gym <= 0.21 gym.utils.seeding.np_random): SHA-512 hash_seed ->

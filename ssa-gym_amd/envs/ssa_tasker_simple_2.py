@@ -14,7 +14,7 @@ import numpy as np
 
 from .. import _lib, host
 from . import transformations
-from ._config import kernel_consts, resolve_kernel_variant
+from ._config import kernel_consts, resolve_kernel_variant, resolve_sensors
 from ._gymshim import Env, np_random, spaces
 from .results import error_failed
 
@@ -155,6 +155,7 @@ def _never_destroy(graph):
 class SSA_Tasker_Env(Env):
     metadata = {'render.modes': ['live', 'none']}
     visualization = None
+    n_sensor = 1      # sensors of the network (config['observers']); one observer without
 
     def __init__(self, config=None):
         s = time.time()
@@ -204,6 +205,24 @@ class SSA_Tasker_Env(Env):
             self.R = np.diag(self.z_sigma ** 2)
         else:
             self.R = np.copy(config['R'])
+        # ---- sensor network (EXTENSION, config['observers']: DESIGN.md section 8c).  Sensor 0 is the PRIMARY sensor: it is the env's
+        # observer (obs_lla, obs_limit, z_sigma, R), and the 'aer' observation, the visibility helpers and the agents' scores use its site
+        net = resolve_sensors(config)
+        self.n_sensor = 1 if net is None else len(net['sites'])
+        if net is not None:
+            S = self.n_sensor
+            self.sensor_lla = np.array(net['sites']) * [host.deg2rad, host.deg2rad, 1]
+            self.sensor_obs_limit = np.radians(net['obs_limit']) if net['obs_limit'] is not None else np.full(S, self.obs_limit)
+            if net['z_sigma'] is not None:
+                unit = np.array([host.arcsec2rad, host.arcsec2rad, 1]) if self.obs_type == 'aer' else 1.0
+                self.sensor_z_sigma = np.array([z * unit for z in net['z_sigma']])
+                self.sensor_R = np.array([np.diag(z ** 2) for z in self.sensor_z_sigma])
+            else:
+                self.sensor_z_sigma = np.tile(self.z_sigma, (S, 1))
+                self.sensor_R = np.tile(self.R, (S, 1, 1))
+            self.obs_lla, self.obs_limit = self.sensor_lla[0], self.sensor_obs_limit[0]
+            self.obs_itrs = host.lla2ecef(self.obs_lla)
+            self.z_sigma, self.R = self.sensor_z_sigma[0], np.copy(self.sensor_R[0])
         self.time = [self.t_0 + (timedelta(seconds=self.dt) * i) for i in range(self.n)]
         if config.get('trans_matrix') is not None:
             self.trans_matrix = np.asarray(config['trans_matrix'], dtype=np.float64).reshape(-1, 3, 3)
@@ -214,15 +233,17 @@ class SSA_Tasker_Env(Env):
         self.rewards = np.empty(self.n)
         self.failed_filters_id = []
         self.failed_filters_msg = _FailureMessages(self.m)
-        self.actions = np.empty(self.n, dtype=int)
-        self.obs_taken = np.empty(self.n, dtype=bool)
+        # (a sensor network: one column per sensor -- actions (n, S), obs_taken (n, S), sigmas_h (n, S, 13, 3), S (n, S, m, 3, 3))
+        sens = (self.n_sensor,) if self.n_sensor > 1 else ()
+        self.actions = np.empty((self.n,) + sens, dtype=int)
+        self.obs_taken = np.empty((self.n,) + sens, dtype=bool)
         self.x_failed = np.copy(host.X_FAILED)
         self.P_failed = np.copy(host.P_FAILED)
         self.visibility = []
-        self.sigmas_h = np.empty((self.n, 13, 3))
-        self.S = np.empty((self.n, self.m, 3, 3)) if self.n * self.m <= (1 << 22) else None
+        self.sigmas_h = np.empty((self.n,) + sens + (13, 3))
+        self.S = np.empty((self.n,) + sens + (self.m, 3, 3)) if self.n * self.m * self.n_sensor <= (1 << 22) else None
         # ---- spaces (:163-177)
-        self.action_space = spaces.Discrete(self.m)
+        self.action_space = spaces.MultiDiscrete([self.m] * self.n_sensor) if self.n_sensor > 1 else spaces.Discrete(self.m)
         if self.obs_returned == 'flatten':
             shp = (self.m * 12,)
         elif self.obs_returned == 'aer':
@@ -244,6 +265,9 @@ class SSA_Tasker_Env(Env):
             hist = 'full' if self.n * bytes_per_step <= 64 * 2 ** 30 else 2
         self._H = self.n if hist == 'full' else max(2, int(hist))
         self._consts, _ = kernel_consts(config, self.Q, self.R, self.dt, self.obs_limit, self.obs_lla)
+        # the other sensors' sites as kernel constants (their visibility helpers)
+        self._sensor_consts = [self._consts] + [kernel_consts(config, self.Q, self.sensor_R[k], self.dt, self.sensor_obs_limit[k],
+                                                              self.sensor_lla[k])[0] for k in range(1, self.n_sensor)]
         self._engine = None
         self._device_rng = bool(config.get('device_rng', False))
         # config['storage_layout'] = None (default) | 'regime': how the engine STORES the objects (reset()); invisible but for speed
@@ -287,6 +311,10 @@ class SSA_Tasker_Env(Env):
         # from / write statistics and the update record to host memory directly, so a step needs one
         # stream synchronisation and one observation copy instead of four blocking transfers
         self._stats_host = torch.zeros(_lib.STAT_STRIDE, dtype=torch.float64).pin_memory()
+        if self.n_sensor > 1:     # the network's sites and one update record per sensor (host-mapped, as the single record)
+            self._sensors = host.make_sensor_params(self.sensor_lla, self.sensor_obs_limit, self.sensor_R, self.n * self.m * 3)
+            self._upd_s_host = torch.zeros((self.n_sensor, _lib.UPD_STRIDE), dtype=torch.float64).pin_memory()
+            self._upd_s_np, self._upd_s_ptr = self._upd_s_host.numpy(), self._upd_s_host.data_ptr()
         self._upd_host = torch.zeros(_lib.UPD_STRIDE, dtype=torch.float64).pin_memory()
         # The observation reaches the host FROM INSIDE the step kernel: its epilogue writes the (az, el, range, trace P) block
         # ('aer') or a second copy of the observation rows (other modes) straight into host-mapped pinned memory, overlapped
@@ -340,10 +368,14 @@ class SSA_Tasker_Env(Env):
         if self._device_rng:
             gen = torch.Generator(device="cuda").manual_seed(int(self.np_random.randint(0, 2 ** 31 - 1)))
             zs = torch.as_tensor(self.z_sigma, dtype=torch.float64, device="cuda")
-            self._z_noise_dev = torch.randn((1, n, m, 3), dtype=torch.float64, device="cuda", generator=gen) * zs
+            if self.n_sensor > 1:     # (a leading sensor axis: sensor s draws z_noise[s][i][j])
+                zs = torch.as_tensor(self.sensor_z_sigma, dtype=torch.float64, device="cuda").view(self.n_sensor, 1, 1, 3)
+                self._z_noise_dev = torch.randn((self.n_sensor, n, m, 3), dtype=torch.float64, device="cuda", generator=gen) * zs
+            else:
+                self._z_noise_dev = torch.randn((1, n, m, 3), dtype=torch.float64, device="cuda", generator=gen) * zs
             self.z_noise = None
         else:
-            self.z_noise = self.np_random.normal(size=(n, m, 3)) * self.z_sigma
+            self.z_noise = self._draw_z_noise()
             self._z_noise_dev = torch.as_tensor(self.z_noise, dtype=torch.float64).to("cuda")
         if self._engine is None:
             self._build_engine()
@@ -374,12 +406,16 @@ class SSA_Tasker_Env(Env):
         self.sigmas_h[:] = 0
         if self.S is not None:
             self.S[:] = np.nan
-        self._y = np.full((n, 3), np.nan)
-        self._z_true = np.full((n, 3), np.nan)
-        self._S_sel = np.full((n, 3, 3), np.nan)
-        self._upd_action = np.full(n, -1, dtype=int)
-        self.y = _Sparse(self, self._y, (3,))
-        self.z_true = _Sparse(self, self._z_true, (3,))
+        sens = (self.n_sensor,) if self.n_sensor > 1 else ()
+        self._y = np.full((n,) + sens + (3,), np.nan)
+        self._z_true = np.full((n,) + sens + (3,), np.nan)
+        self._S_sel = np.full((n,) + sens + (3, 3), np.nan)
+        self._upd_action = np.full((n,) + sens, -1, dtype=int)
+        if sens:      # (a sensor network: per-sensor records (n, S, 3), NaN where the sensor updated nothing)
+            self.y, self.z_true = self._y, self._z_true
+        else:
+            self.y = _Sparse(self, self._y, (3,))
+            self.z_true = _Sparse(self, self._z_true, (3,))
         self._n_failed = 0
         self._fail_read, self._fail_pending, self._fail_chunk_total = 0, {}, 0      # records of the kernel's failure log consumed so far
         self._engine.fail_log[:] = 0.0             # (time index 0 = "not written": steps count from 1)
@@ -389,6 +425,14 @@ class SSA_Tasker_Env(Env):
         self._fetch_small(0)
         self.runtime['reset'] += time.time() - s
         return self._obs_out()
+
+    def _draw_z_noise(self):
+        """the measurement noise of the episode from np_random (:219-221): (n, m, 3); a sensor network (S, n, m, 3) -- sensor 0's draws are
+        the reference's stream, sensors 1 .. S-1 draw after it, in order"""
+        z = self.np_random.normal(size=(self.n, self.m, 3)) * self.z_sigma
+        if self.n_sensor > 1:
+            z = np.stack([z] + [self.np_random.normal(size=(self.n, self.m, 3)) * self.sensor_z_sigma[k] for k in range(1, self.n_sensor)])
+        return z
 
     def _fetch_small(self, i):
         e = self._engine
@@ -423,6 +467,8 @@ class SSA_Tasker_Env(Env):
         return self._host_obs(obs.reshape(-1) if self.obs_returned == 'flatten' else obs)
 
     def step(self, a):
+        if self.n_sensor > 1:
+            return self._step_sensors(a)
         step_s = time.time()
         assert self.action_space.contains(a), "%r (%s) invalid" % (a, type(a))
         self._argmax_sigma_prev = self._argmax_sigma
@@ -481,6 +527,77 @@ class SSA_Tasker_Env(Env):
         self.runtime['step'] += e_t - step_s
         return obs, self._returned_reward(self.rewards[i]), done, {}
 
+    def _step_sensors(self, a):
+        """step() of a sensor network (config['observers'] with S > 1 sites): `a` holds one object per sensor, all different; sensor s
+        updates object a[s] with its own site, elevation mask, R and noise (ssa_env_step_sensors_f64), in the same single launch as step()"""
+        step_s = time.time()
+        if self._engine is None:
+            raise _lib.SsaHipError("no device state: a sensor network's step runs on the GPU only (no CPU fallback)")
+        if not self.action_space.contains(a):
+            raise AssertionError("%r (%s) invalid: one object in 0 .. %d per sensor (%d sensors)" % (a, type(a), self.m - 1, self.n_sensor))
+        a = np.asarray(a, dtype=np.int64)
+        if len(np.unique(a)) != len(a):
+            raise ValueError("step: two sensors tasked to the same object (%s)" % (a,))
+        self._argmax_sigma_prev = self._argmax_sigma
+        self._ring_head = None
+        self.i += 1
+        i = self.i
+        self.actions[i] = a
+        e = self._engine
+        cur = self._stream
+        aer = self.obs_returned == 'aer'
+        k = 0 if aer else i % len(self._obs_ring)
+        shaped = self.reward_type == 'shaped'
+        kp = None
+        if self._obs_device:
+            e.launch_step_sensors((i - 1) % e.H, i % e.H, i, self._sensors, a, self._upd_s_ptr, aer_out=self._aer_dev.data_ptr() if aer else 0,
+                                  stats_out=self._stats_ptr, stream=cur.cuda_stream, fast_stats=True, fold_inside=True, argmax_spos=shaped)
+            obs_np = self._aer_dev if aer else (e.obs[i % e.H].reshape(-1) if self.obs_returned == 'flatten' else e.obs[i % e.H])
+        else:
+            pool = self._obs_pool
+            kp = pool.acquire() if pool is not None else None
+            e.launch_step_sensors((i - 1) % e.H, i % e.H, i, self._sensors, a, self._upd_s_ptr, aer_out=self._obs_ring_ptr[0] if aer else 0,
+                                  obs_mirror=0 if aer else (pool.ptrs[kp] if kp is not None else self._obs_ring_ptr[k]),
+                                  stats_out=self._stats_ptr, stream=cur.cuda_stream, fast_stats=True, fold_inside=True, argmax_spos=shaped,
+                                  mirror_f32=self._mirror_f32)
+            obs_np = self._obs_ring_np[k]
+        cur.synchronize()
+        self._stats = self._stats_np.copy()
+        self._argmax_sigma = int(self._stats[_lib.STAT_ARGMAX_SPOS])
+        for s in range(self.n_sensor):
+            self._book_sensor_update(i, s, int(a[s]), self._upd_s_np[s])
+        if int(self._stats[_lib.STAT_N_FAILED]) != self._n_failed:
+            self._record_failures()
+        done = self._reward_done(i, a, self._stats, self._argmax_sigma_prev)
+        if i + 1 >= self.n:
+            done = True
+        if aer or self._obs_device or self._obs_zero_copy:
+            obs = obs_np
+        elif kp is not None:
+            obs = self._obs_pool.hand_out(kp)
+        else:
+            obs = obs_np.copy()
+        self.runtime['step'] += time.time() - step_s
+        return obs, self._returned_reward(self.rewards[i]), done, {}
+
+    def _book_sensor_update(self, i, s, a, rec):
+        """update record of sensor s at step i into the per-sensor histories"""
+        if rec[_lib.UPD_ACTION] >= 0:
+            self._upd_action[i, s] = a
+            self._z_true[i, s] = rec[_lib.UPD_Z_TRUE:_lib.UPD_Z_TRUE + 3]
+            if rec[_lib.UPD_OBS_TAKEN] == 1.0:
+                self._y[i, s] = rec[_lib.UPD_Y:_lib.UPD_Y + 3]
+                self._S_sel[i, s] = rec[_lib.UPD_S:_lib.UPD_S + 9].reshape(3, 3)
+                if self.S is not None:
+                    self.S[i, s, a] = self._S_sel[i, s]
+                self.sigmas_h[i, s] = rec[_lib.UPD_SIGMAS_H:_lib.UPD_SIGMAS_H + 39].reshape(13, 3)
+                self.obs_taken[i, s] = True
+
+    def _single_sensor(self, what):
+        if self.n_sensor > 1:
+            raise NotImplementedError("%s: not implemented for a sensor network (config['observers'] with %d sensors); "
+                                      "use step()" % (what, self.n_sensor))
+
     # ------------------------------------------------------------------ per-step host bookkeeping
     def _book_update(self, i, a, rec):
         """update record of step i (:292-315) into the env's sparse histories"""
@@ -496,7 +613,8 @@ class SSA_Tasker_Env(Env):
                 self.obs_taken[i] = True
 
     def _reward_done(self, i, a, st, argmax_sigma_prev):
-        """reward / done of step i from its statistics (:324-354); fills self.rewards[i]"""
+        """reward / done of step i from its statistics (:324-354); fills self.rewards[i].  The statistics are taken over all objects
+        whatever the number of sensors; with a sensor network 'shaped' pays its +1/n if ANY sensor tasked np.argmax(sigma_pos[i - 1])"""
         max_dpos = st[_lib.STAT_MAX_DPOS]
         done = False
         if self.reward_type == 'jones':
@@ -515,7 +633,7 @@ class SSA_Tasker_Env(Env):
                 done, self.rewards[i] = True, 0
             elif max_dpos < 3e4:
                 done, self.rewards[i] = True, 1 - np.sum(self.rewards[:i])
-            elif a == argmax_sigma_prev:
+            elif (a == argmax_sigma_prev) if self.n_sensor == 1 else bool(np.any(np.asarray(a) == argmax_sigma_prev)):
                 self.rewards[i] = 1 / self.n
             else:
                 self.rewards[i] = -1 / self.n
@@ -567,6 +685,7 @@ class SSA_Tasker_Env(Env):
         chip across the steps, results bit-identical to step()).  Stops at the first `done`.  Returns
         (observation after the last executed step, rewards[k], dones[k], info).  Every reward type ('shaped': the arg-max of
         sigma_pos of every step comes from the rollout's arg-max slots, ssa_rollout_params.spos_tiles)."""
+        self._single_sensor('rollout')
         self._caller_order()
         import torch
         shaped = self.reward_type == 'shaped'     # (np.argmax(sigma_pos) of every step from the arg-max slots of the rollout)
@@ -602,6 +721,7 @@ class SSA_Tasker_Env(Env):
         Every reward type.  If the persistent launch gives up (a wavefront waited longer than config['closed_loop_wait_ticks'] for a
         decision: something else holds the GPU's wavefront slots) the env restores the state the chunk started from, takes the
         per-step launches for this and every later call, and warns once."""
+        self._single_sensor('run_agent')
         import torch
         name = agent if isinstance(agent, str) else getattr(agent, "__name__", None)
         if name not in self.AGENT_KINDS:
@@ -805,6 +925,7 @@ class SSA_Tasker_Env(Env):
         greedy ones (those: run_agent, one persistent launch).  Every reward type; a data-dependent `done` ('jones', 'shaped') is
         honoured at the bookkeeping -- the steps launched behind it are discarded (chunks of history - 1 steps, as run_agent).
         Returns (actions[k], rewards[k], dones[k])."""
+        self._single_sensor('run_policy')
         self._caller_order()          # (the policy's views are the env's own object order)
         import torch
         shaped = self.reward_type == 'shaped'
@@ -938,12 +1059,13 @@ class SSA_Tasker_Env(Env):
         return float(np.mean(self.nees[lo:self.i + 1]))
 
     def nis(self):
-        """normalised innovation squared of every update taken so far (fitness_test(), :750-754); NaN where no update ran"""
+        """normalised innovation squared of every update taken so far (fitness_test(), :750-754); NaN where no update ran.  A sensor
+        network: (n, S), one value per (step, sensor) update"""
         import torch
         from .. import device
-        out = np.full(self.n, np.nan)
-        k = np.where(self.obs_taken[:self.i + 1])[0]
-        if len(k):
+        out = np.full(self.obs_taken.shape, np.nan)     # ((n, S) for a sensor network: every (step, sensor) update)
+        k = np.nonzero(self.obs_taken[:self.i + 1])
+        if len(k[0]):
             out[k] = device.nis(torch.as_tensor(self._y[k]).to("cuda"), torch.as_tensor(self._S_sel[k]).to("cuda")).cpu().numpy()
         return out
 
@@ -972,9 +1094,9 @@ class SSA_Tasker_Env(Env):
         from .. import device
         e = self._engine
         out = {}
-        k = np.where(self.obs_taken[:self.i + 1])[0]
+        k = np.nonzero(self.obs_taken[:self.i + 1])      # (a sensor network: every (step, sensor) update, pooled)
         lo, hi = self._chi2_points(alpha, 3)
-        if len(k):
+        if len(k[0]):
             nis = device.nis(torch.as_tensor(self._y[k]).to("cuda"), torch.as_tensor(self._S_sel[k]).to("cuda"))
             inside, valid = device.chi2_contained(nis, lo, hi)
         else:
@@ -1004,28 +1126,31 @@ class SSA_Tasker_Env(Env):
                 print(self.failed_filters_msg[rso_id])
 
     # ------------------------------------------------------------------ visibility (:410-434)
-    def _mask(self):
+    def _mask(self, sensor=0):
         from .. import device
+        if not 0 <= int(sensor) < self.n_sensor:
+            raise ValueError("sensor %r: the env has %d sensor(s)" % (sensor, self.n_sensor))
         self._caller_order()
         e = self._engine
         M = e.trans[self.i % e.n_time].reshape(3, 3)
-        return device.visible_mask(e.x_true[self.i % e.H], M, self._consts).cpu().numpy().astype(bool)
+        return device.visible_mask(e.x_true[self.i % e.H], M, self._sensor_consts[int(sensor)]).cpu().numpy().astype(bool)
 
-    def visible_objects(self):
+    # (sensor=: a sensor network's site s; default the primary sensor, the only one without config['observers'])
+    def visible_objects(self, sensor=0):
         s = time.time()
-        viz = np.where(self._mask())[0]
+        viz = np.where(self._mask(sensor))[0]
         self.runtime['visible_objects'] += time.time() - s
         return viz
 
-    def object_visible(self, RSO_ID=[]):
+    def object_visible(self, RSO_ID=[], sensor=0):
         if len(RSO_ID) == 0:
             print('RSO ID expected, but not supplied')
             return RSO_ID
-        return self._mask()[np.asarray(RSO_ID)]
+        return self._mask(sensor)[np.asarray(RSO_ID)]
 
-    def object_visibility(self):
+    def object_visibility(self, sensor=0):
         s = time.time()
-        viz = self._mask()
+        viz = self._mask(sensor)
         self.runtime['object_visibility'] += time.time() - s
         return viz
 
@@ -1049,6 +1174,7 @@ class SSA_Tasker_Env(Env):
             status  [m]     int32: the SSA_ST_* code step(j) would leave on j (a NaN update, which depends on the noise, is not foreseen)
         and with covariances=True also x_prior [m, 6], P_prior [m, 6, 6] (the prediction every object gets) and P_post [m, 6, 6] (P_filter
         of the next step after step(j)).  The tensors are the env's lookahead buffers: the next call overwrites them."""
+        self._single_sensor('lookahead')
         from .. import engine as _engine
         if self._engine is None:
             raise _lib.SsaHipError("no device state: the lookahead runs on the GPU only (no CPU fallback)")

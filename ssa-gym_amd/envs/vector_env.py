@@ -21,6 +21,11 @@ class SSA_Tasker_VecEnv:
     def __init__(self, config, num_envs, seed=0):
         import torch
         from .. import engine
+        from ._config import resolve_sensors
+        net = resolve_sensors(config)
+        if net is not None and len(net['sites']) > 1:
+            raise NotImplementedError("SSA_Tasker_VecEnv: not implemented for a sensor network (config['observers'] with %d sensors); "
+                                      "use SSA_Tasker_Env" % len(net['sites']))
         self.E, self.m, self.n, self.dt = int(num_envs), config['rso_count'], config['steps'], config['time_step']
         self._bulk_draws = bool(config.get('device_rng', False))
         self.obs_returned, self.reward_type = config['obs_returned'], config['reward_type']
@@ -31,9 +36,13 @@ class SSA_Tasker_VecEnv:
                         else np.asarray(config['z_sigma'], dtype=np.float64))
         self.P_0 = np.diag(self.x_sigma ** 2) if config['P_0'] is None else np.copy(config['P_0'])
         R = np.diag(self.z_sigma ** 2) if config['R'] is None else np.copy(config['R'])
+        if net is not None and net['z_sigma'] is not None:     # (config['observers'] with one site: that sensor's values)
+            self.z_sigma = net['z_sigma'][0] * (np.array([host.arcsec2rad, host.arcsec2rad, 1]) if self.obs_type == 'aer' else 1.0)
+            R = np.diag(self.z_sigma ** 2)
         Q = host.Q_discrete_white_noise(dim=2, dt=self.dt, var=config['q_sigma'] ** 2, block_size=3, order_by_dim=False)
-        obs_lla = np.array(config['observer']) * [host.deg2rad, host.deg2rad, 1]
-        self._consts, model = kernel_consts(config, Q, R, self.dt, np.radians(config['obs_limit']), obs_lla)   # as SSA_Tasker_Env
+        obs_lla = np.array(config['observer'] if net is None else net['sites'][0]) * [host.deg2rad, host.deg2rad, 1]
+        obs_limit = config['obs_limit'] if net is None or net['obs_limit'] is None else net['obs_limit'][0]
+        self._consts, model = kernel_consts(config, Q, R, self.dt, np.radians(obs_limit), obs_lla)   # as SSA_Tasker_Env
         trans = (np.asarray(config['trans_matrix']) if config.get('trans_matrix') is not None
                  else transformations.trans_matrix_table(config['t_0'], self.dt, self.n))
         self._gen = torch.Generator(device="cuda").manual_seed(int(seed))

@@ -107,3 +107,26 @@ def make_consts(Q, R, alpha, beta, kappa, dt, obs_limit_rad, obs_lla, obs_type='
     c.flags = (_lib.FLAG_RESAMPLE if resample else 0) | (_lib.FLAG_REFERENCE_COV if covariance == 'reference' else 0)
     c.update_interval = int(update_interval)
     return c
+
+
+def make_sensor_params(sites_lla, obs_limits_rad, Rs, zn_stride_sensor):
+    """pack a sensor network (include/ssa_hip.h: ssa_sensor_params): site s at sites_lla[s] = (lat [rad], lon [rad], h [m]) with elevation
+    mask obs_limits_rad[s] and measurement noise covariance Rs[s] (3 x 3); sensor s's noise table starts zn_stride_sensor doubles after
+    sensor s - 1's.  Every sensor idle (action -1) and no record destination: the caller sets `action` and `upd` per step."""
+    S = len(sites_lla)
+    if not 1 <= S <= _lib.MAX_SENSORS or len(obs_limits_rad) != S or len(Rs) != S:
+        raise ValueError("a sensor network has 1 .. %d sites, each with one elevation mask and one R" % _lib.MAX_SENSORS)
+    sp = _lib.ssa_sensor_params()
+    sp.n_sensor = S
+    for k in range(_lib.MAX_SENSORS):
+        sp.action[k] = -1
+    for k in range(S):
+        lla = np.asarray(sites_lla[k], dtype=np.float64)
+        sp.enu[k][:] = enu_matrix(lla).reshape(9)
+        sp.obs_itrs[k][:] = lla2ecef(lla)
+        sp.obs_limit[k] = float(obs_limits_rad[k])
+        sp.R[k][:] = np.asarray(Rs[k], dtype=np.float64).reshape(9)
+    sp.zn_stride_sensor = int(zn_stride_sensor)
+    sp.upd = 0
+    return sp
+

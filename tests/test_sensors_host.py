@@ -1,0 +1,174 @@
+"""CPU-only checks of the sensor network (include/ssa_hip.h: ssa_env_step_sensors_f64; config['observers']): the export, the parameter
+block's layout against the header, refusal of bad arguments before any launch, the config parser, the noise stream, no CPU fallback,
+and the new kernels' resource budget in the shipped code object."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import ssa_gym_amd
+    from ssa_gym_amd import _lib
+    ssa_gym_amd.build()
+    return _lib.load()
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "ssa_hip.h")).read()
+
+
+def test_sensor_step_is_exported_and_declared(lib):
+    from ssa_gym_amd import _lib
+    assert re.search(r"\bssa_env_step_sensors_f64\s*\(", _header())
+    assert "ssa_env_step_sensors_f64" in _lib.SIGNATURES
+    assert hasattr(lib, "ssa_env_step_sensors_f64")
+    m = re.search(r"#define SSA_MAX_SENSORS\s+(\d+)", _header())
+    assert m and int(m.group(1)) == _lib.MAX_SENSORS == 8
+
+
+def test_sensor_params_layout_matches_the_header(lib, tmp_path):
+    from ssa_gym_amd import _lib
+    st = _lib.ssa_sensor_params
+    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "ssa_hip.h"', 'int main(void){',
+           'printf("%zu\\n", sizeof(ssa_sensor_params));']
+    want = [C.sizeof(st)]
+    for f, _ in st._fields_:
+        src.append('printf("%%zu\\n", offsetof(ssa_sensor_params, %s));' % f)
+        want.append(getattr(st, f).offset)
+    src.append('return 0;}')
+    c = tmp_path / "sens.c"
+    c.write_text("\n".join(src))
+    exe = tmp_path / "sens"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(c)])
+    assert [int(v) for v in subprocess.check_output([str(exe)]).decode().split()] == want
+
+
+def test_sensor_step_refuses_bad_arguments_before_any_launch(lib):
+    """NULL blocks, 0 or more than 8 sensors -> SSA_E_INVALID; several envs -> SSA_E_UNSUPPORTED; missing step pointers -> SSA_E_INVALID.
+    Nothing is launched (no device is touched: this runs without a GPU)."""
+    from ssa_gym_amd import _lib
+    f = lib.ssa_env_step_sensors_f64
+    c, p, sp = _lib.ssa_consts(), _lib.ssa_step_params(), _lib.ssa_sensor_params()
+    p.n_obj, p.n_env = 8, 1
+    sp.n_sensor = 2
+    sp.zn_stride_sensor = 8 * 3
+    assert f(None, C.byref(p), C.byref(sp), None) == _lib.E_INVALID
+    assert f(C.byref(c), None, C.byref(sp), None) == _lib.E_INVALID
+    assert f(C.byref(c), C.byref(p), None, None) == _lib.E_INVALID
+    for bad in (0, -1, 9):
+        sp.n_sensor = bad
+        assert f(C.byref(c), C.byref(p), C.byref(sp), None) == _lib.E_INVALID, bad
+    sp.n_sensor = 2
+    p.n_env = 2
+    assert f(C.byref(c), C.byref(p), C.byref(sp), None) == _lib.E_UNSUPPORTED
+    p.n_env = 1
+    assert f(C.byref(c), C.byref(p), C.byref(sp), None) == _lib.E_INVALID      # (x_true_in & co. are NULL)
+    sp.zn_stride_sensor = 0                                                     # two sensors cannot share one noise table
+    assert f(C.byref(c), C.byref(p), C.byref(sp), None) == _lib.E_INVALID
+
+
+def test_config_parser_accepts_and_refuses():
+    from ssa_gym_amd.envs._config import resolve_sensors
+    assert resolve_sensors({}) is None
+    net = resolve_sensors({'observers': [(38.8, -104.5, 1800), (28.4, -80.6, 3)], 'sensor_obs_limit': [15, 20],
+                           'sensor_z_sigma': [(1, 1, 1e3), (2, 2, 2e3)]})
+    assert net['sites'] == [(38.8, -104.5, 1800.0), (28.4, -80.6, 3.0)] and net['obs_limit'] == [15.0, 20.0]
+    assert np.array_equal(net['z_sigma'][1], [2, 2, 2e3])
+    one = resolve_sensors({'observers': [(38.8, -104.5, 1800)]})
+    assert len(one['sites']) == 1 and one['obs_limit'] is None and one['z_sigma'] is None
+    site = (0.0, 0.0, 0.0)
+    for bad in ({'observers': []}, {'observers': [site] * 9}, {'observers': [(1.0, 2.0)]}, {'observers': [(np.nan, 0, 0)]},
+                {'observers': 'nowhere'}, {'observers': [site, site], 'sensor_obs_limit': [10]},
+                {'observers': [site], 'sensor_z_sigma': [(1, 1)]}, {'observers': [site], 'sensor_z_sigma': [(1, 1, -1)]},
+                {'sensor_obs_limit': [10]}, {'sensor_z_sigma': [(1, 1, 1)]}):
+        with pytest.raises(ValueError):
+            resolve_sensors(bad)
+
+
+def _bare_env(S, m=10, n=6, seed=5):
+    """an env object without device state (what a machine without a GPU has), with just what the host-side paths read"""
+    from ssa_gym_amd import host
+    from ssa_gym_amd.envs._gymshim import np_random, spaces
+    from ssa_gym_amd.envs.ssa_tasker_simple_2 import SSA_Tasker_Env
+    env = SSA_Tasker_Env.__new__(SSA_Tasker_Env)
+    env._engine, env.i, env.n, env.m, env.n_sensor = None, 0, n, m, S
+    env.z_sigma = np.array([1.0, 1.0, 1e3]) * [host.arcsec2rad, host.arcsec2rad, 1]
+    env.sensor_z_sigma = np.stack([env.z_sigma * (k + 1) for k in range(S)])
+    env.np_random, _ = np_random(seed)
+    env.action_space = spaces.MultiDiscrete([m] * S) if S > 1 else spaces.Discrete(m)
+    return env
+
+
+def test_noise_stream_of_one_sensor_is_todays_and_the_others_follow_it():
+    from ssa_gym_amd.envs._gymshim import np_random
+    one = _bare_env(1)._draw_z_noise()
+    ref, _ = np_random(5)
+    want = ref.normal(size=(6, 10, 3)) * _bare_env(1).z_sigma          # the reference's draw (:219-221)
+    assert one.shape == (6, 10, 3) and np.array_equal(one, want)
+    env3 = _bare_env(3)
+    three = env3._draw_z_noise()
+    assert three.shape == (3, 6, 10, 3) and np.array_equal(three[0], want)
+    for k in (1, 2):
+        assert np.array_equal(three[k], ref.normal(size=(6, 10, 3)) * env3.sensor_z_sigma[k])
+
+
+def test_step_refuses_two_sensors_on_one_object_and_has_no_cpu_fallback():
+    from ssa_gym_amd import _lib
+    env = _bare_env(3)
+    with pytest.raises(_lib.SsaHipError):
+        env.step([1, 2, 3])                 # no device state: no CPU fallback
+    env._engine = object()                  # (the checks below come before anything touches the engine)
+    with pytest.raises(ValueError):
+        env.step([1, 2, 1])
+    with pytest.raises(AssertionError):
+        env.step([1, 2])
+    with pytest.raises(AssertionError):
+        env.step([1, 2, 10])
+
+
+def test_multi_step_drivers_refuse_a_sensor_network():
+    env = _bare_env(3)
+    for call in (lambda: env.rollout([0, 1]), lambda: env.run_agent('agent_naive_greedy', 2), lambda: env.run_policy(None, 2),
+                 lambda: env.lookahead()):
+        with pytest.raises(NotImplementedError, match="sensor network"):
+            call()
+
+
+def test_sensor_kernels_keep_the_step_kernels_budget(tmp_path):
+    """the eight sensor-network kernels (4 propagators x {one tile, multi tile}) fit the step kernel's register budget and LDS, use no
+    more scratch than the step kernel of the same propagator and launch form, and touch it only around the out-of-line calls
+    (SSA_PROP_ELEMENTS / SSA_PROP_HYBRID) -- FG and J2 none at all"""
+    from test_abi_and_host import _code_object
+    notes, dis = _code_object(tmp_path)
+    kern = {}
+    for blk in notes.split("- .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        kern[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1)) for k in
+                      ("vgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")}
+    sens = [k for k in kern if "step_sensors_kernel" in k]
+    assert len(sens) == 8, sens
+    bodies = re.split(r"\n[0-9a-f]+ <([^>]+)>:\n", dis)
+    checked = 0
+    for name, body in zip(bodies[1::2], bodies[2::2]):
+        if "step_sensors_kernel" not in name:
+            continue
+        k = kern[name]
+        step = kern[name.replace("19step_sensors_kernel", "16step_fast_kernel").replace("NS_5SensKE", "NS_5StepKE")]
+        assert k["vgpr_count"] <= 96 and k["group_segment_fixed_size"] == step["group_segment_fixed_size"], (name, k)
+        assert k["private_segment_fixed_size"] <= step["private_segment_fixed_size"], (name, k, step)
+        assert k["vgpr_spill_count"] <= step["vgpr_spill_count"], (name, k, step)
+        ins = [ln.split()[0] for ln in body.splitlines() if ln.strip() and not ln.strip().startswith(("//", ";"))]
+        calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
+        stray = [i for i, op in enumerate(ins) if op.startswith("scratch_") and not (calls and min(abs(i - c) for c in calls) <= 96)]
+        assert not stray, (name, stray[:8])
+        if "ILi0E" not in name and "ILi3E" not in name:
+            assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)
+        checked += 1
+    assert checked == 8
