@@ -533,6 +533,20 @@ typedef struct ssa_sensor_params {
 } ssa_sensor_params;
 int ssa_env_step_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_sensor_params *s_host, void *stream);
 
+/* ---------------------------------------------------------------- the lookahead of a sensor network
+ * ssa_lookahead_f64 for every sensor of ssa_sensor_params, in one launch (one env).  For sensor s and object j the outputs are what
+ * ssa_env_step_sensors_f64 would leave for j with action[s] = j and every other sensor idle -- by the sensor step's definition, what
+ * ssa_lookahead_f64 reports for j with ssa_consts' site, elevation mask and R replaced by sensor s's -- bit for bit.  The predict runs
+ * once; the hypothetical update runs once per sensor.  Output rows, with m = n_obj and the caller's object numbering:
+ *   score [S*m][SSA_LOOK_NSCORE], status [S*m], visible [S*m], P_post [S*m][36] (or NULL): row s * m + j;
+ *   x_prior [m][6], P_prior [m][36] (or NULL): row j -- the prediction does not depend on the site.
+ * Reads the same ssa_step_params fields as ssa_lookahead_f64 and, of ssa_sensor_params, n_sensor, enu, obs_itrs, obs_limit and R
+ * (its action, zn_stride_sensor and upd are not read).  Nothing is written but `out`.
+ * Refused before any launch: NULL blocks or required outputs, n_sensor outside 1 .. SSA_MAX_SENSORS, a NaN elevation mask
+ * (SSA_E_INVALID); n_env != 1 (SSA_E_UNSUPPORTED); and every refusal of ssa_lookahead_f64. */
+int ssa_lookahead_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_sensor_params *s_host,
+                              const ssa_lookahead_out *out, void *stream);
+
 /* ------------------------------------------------ all-gather by direct peer stores (SURVEY 8e "Collective")
  * The reference runs one env per process and has no exchange step; the sharded env of this library (one env's objects spread over the
  * GPUs of a node) reassembles every step's observation block + statistics words on every rank.  These two entry points do that without a

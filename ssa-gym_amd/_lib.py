@@ -112,6 +112,8 @@ SIGNATURES = {
     "ssa_env_closed_loop_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_closed_loop_params), c_dp]),
     "ssa_lookahead_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_lookahead_out), c_dp]),
     "ssa_env_step_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params), c_dp]),
+    "ssa_lookahead_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
+                                            C.POINTER(ssa_lookahead_out), c_dp]),
     "ssa_closed_loop_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
     "ssa_env_step_work_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
     "ssa_reward_stats_f64": (C.c_int, [c_dp, c_dp, c_dp, c_dp, C.c_int64, C.c_int32, c_dp]),

@@ -97,3 +97,48 @@ def agent_info_gain(obs, env):                  # argmax 1/2 ln(det P- / det P+)
 
 def agent_trace_gain(obs, env):                 # argmax tr P- - tr P+ over the objects an update would reach
     return _pick_lookahead(env, _lib.LOOK_TRACE_GAIN)
+
+
+# ---- the same baselines for a sensor network (config['observers']): every sensor's lookahead in one launch
+# (env.lookahead_sensors), then a global greedy assignment over the [S, m] score column -- the largest finite score (ties: the lowest
+# s * m + j, the masked arg-max's first maximum) assigns its object to its sensor, that sensor's row and that object's column leave,
+# and so on: one masked arg-max launch per sensor.  A sensor left without a finite score gets an object nobody has, drawn from the action
+# space's generator as _pick's fallback (env.np_random, the env's noise stream, is not touched).
+def _draw_unassigned(env, taken):
+    if len(taken) >= env.m:
+        raise ValueError("%d sensors but %d objects: no object left to assign" % (len(taken) + 1, env.m))
+    while True:
+        for j in np.atleast_1d(env.action_space.sample()):
+            if int(j) not in taken:
+                return int(j)
+
+
+def _assign_lookahead_sensors(env, k):
+    from . import device
+    score = env.lookahead_sensors()["score"]               # [S, 3, m]: a view of the engine's [S][m][3] rows
+    S, m = score.shape[0], score.shape[2]
+    flat = score.permute(0, 2, 1).reshape(-1)               # (no copy)
+    mask = _column_mask(env, k, flat.shape[0]).clone()
+    rows = mask.view(S, m, _lib.LOOK_NSCORE)
+    act = np.full(S, -1, dtype=np.int64)
+    for _ in range(S):
+        f = device.masked_argmax(flat, mask)
+        if f < 0:
+            break
+        s, j = divmod(f // _lib.LOOK_NSCORE, m)
+        act[s] = j
+        rows[s] = 0
+        rows[:, j] = 0
+    taken = set(act[act >= 0].tolist())
+    for s in np.flatnonzero(act < 0):
+        act[s] = _draw_unassigned(env, taken)
+        taken.add(int(act[s]))
+    return act if env.n_sensor > 1 else int(act[0])        # (one sensor: a Discrete action, as agent_info_gain's)
+
+
+def agent_info_gain_sensors(obs, env):          # one object per sensor, greedy over 1/2 ln(det P- / det P+) from every site
+    return _assign_lookahead_sensors(env, _lib.LOOK_INFO_GAIN)
+
+
+def agent_trace_gain_sensors(obs, env):         # one object per sensor, greedy over tr P- - tr P+ from every site
+    return _assign_lookahead_sensors(env, _lib.LOOK_TRACE_GAIN)

@@ -1033,12 +1033,42 @@ SSA_DEV int sensor_index(const ssa_sensor_params* s, int64_t jid)
 }
 template <class ACT> struct ActIsSensors { static constexpr bool v = false; };
 template <> struct ActIsSensors<ActSensors> { static constexpr bool v = true; };
+// ActLookSensors (lookahead_sensors_kernel, ssa_lookahead_sensors_f64; one env): ActAll for every sensor of a network.  The predict
+// runs once; the update block and the outputs then run once per sensor (a pass), from that sensor's site with its elevation mask and R
+// -- wave-uniform: scalar loads of the argument block, no waterfall.  Sensor s's outputs go to row s * n_obj + the caller's index; the
+// prior (x_prior / P_prior) is written by the first pass only.
+struct ActLookSensors {
+    static constexpr bool late = false;
+    const ssa_lookahead_out* o;
+    const ssa_sensor_params* s;
+    SSA_DEV int get() { return -1; }
+    SSA_DEV void before_wait(Tiles&, int, int) {}
+    SSA_DEV void mid_step(Tiles&, int) {}
+};
+template <class ACT> struct ActIsLookSensors { static constexpr bool v = false; };
+template <> struct ActIsLookSensors<ActLookSensors> { static constexpr bool v = true; };
+template <> struct ActIsAll<ActLookSensors> { static constexpr bool v = true; };
 template <class ACT> SSA_DEV const ssa_sensor_params* sensors_of(const ACT&) { return nullptr; }
 template <> SSA_DEV const ssa_sensor_params* sensors_of<ActSensors>(const ActSensors& a) { return a.s; }
+template <> SSA_DEV const ssa_sensor_params* sensors_of<ActLookSensors>(const ActLookSensors& a) { return a.s; }
+// a pointer into the argument segment that the optimiser cannot see through: the (scalar) loads from it stay inside ActLookSensors'
+// passes instead of being hoisted in front of them, where their results would hold scalar registers across every pass
+template <class T> SSA_DEV const T* kernarg_opaque(const T* q)
+{
+    typedef const __attribute__((address_space(4))) T* KP;
+    KP k = (KP)q;
+    asm volatile("" : "+s"(k));
+    return (const T*)k;
+}
 SSA_DEV double logdet_chol(const double (&A)[21]);   // (defined with the agents' scores)
+// where entry idx of P+ lies in a row's staging matrix ([13][9]): PPL 0 (ActAll) -- the first 36 slots; PPL 1 (ActLookSensors) -- the
+// right halves (the residual columns) of its first 12 rows, so that the left halves survive the pass
+template <int PPL> SSA_DEV int pp_at(int idx) { return PPL == 0 ? idx : (idx / 3) * 9 + 6 + idx % 3; }
 // the lookahead's outputs of row g (lane l of it) at the caller's row `orow`.  P- / x- are the tile after the predict and the
-// failure sentinels (what a step leaves for an object it does not update); P+ (row g's turn of Phase 2, left at t.UA[g * 117]) where
-// the update ran, the sentinel where S was singular, P- otherwise.  The scores: one lane per object, log-dets by logdet_chol.
+// failure sentinels (what a step leaves for an object it does not update); P+ (row g's turn of Phase 2, left in t.UA[g * 117 ...] as
+// pp_at<PPL> places it) where the update ran, the sentinel where S was singular, P- otherwise.  The scores: one lane per object, log-dets
+// by logdet_chol.
+template <int PPL = 0>
 SSA_DEV void lookahead_store(const Tiles& t, const ssa_lookahead_out& o, int g, int l, int64_t orow, int st, bool vis, bool taken)
 {
     const double* Pm = &t.P[g * 36];
@@ -1047,7 +1077,7 @@ SSA_DEV void lookahead_store(const Tiles& t, const ssa_lookahead_out& o, int g, 
     for (int idx = l; idx < 36; idx += 16) {
         const int a = idx / 6, b = idx - 6 * a;
         const double pm = Pm[idx];
-        const double pp = taken ? Pp[idx] : (lin ? ((a == b) ? (a < 3 ? X_FAILED_POS : X_FAILED_VEL) : 0.0) : pm);
+        const double pp = taken ? Pp[pp_at<PPL>(idx)] : (lin ? ((a == b) ? (a < 3 ? X_FAILED_POS : X_FAILED_VEL) : 0.0) : pm);
         if (o.P_prior) o.P_prior[orow * 36 + idx] = pm;
         if (o.P_post) o.P_post[orow * 36 + idx] = pp;
     }
@@ -1060,7 +1090,7 @@ SSA_DEV void lookahead_store(const Tiles& t, const ssa_lookahead_out& o, int g, 
 #pragma unroll
         for (int r = 0; r < 6; ++r)
 #pragma unroll
-            for (int c = r; c < 6; ++c) A[tri(r, c)] = src[r * 6 + c];
+            for (int c = r; c < 6; ++c) A[tri(r, c)] = (PPL == 0 || l == 0) ? src[r * 6 + c] : src[pp_at<PPL>(r * 6 + c)];
         ld = logdet_chol(A);
     }
     const double ld_post = __shfl_down(ld, 1, 64);
@@ -1072,7 +1102,7 @@ SSA_DEV void lookahead_store(const Tiles& t, const ssa_lookahead_out& o, int g, 
 #pragma unroll
             for (int r = 0; r < 6; ++r) {
                 trm += Pm[7 * r];
-                trp += Pp[7 * r];
+                trp += Pp[pp_at<PPL>(7 * r)];
                 if (r == 2) { pos_m = trm; pos_p = trp; }
             }
             sc[SSA_LOOK_TRACE_GAIN] = trm - trp;
@@ -1101,6 +1131,14 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     constexpr bool FOLD_OK = (TILE == 0);
     constexpr bool ALL = ActIsAll<ACT>::v;   // the lookahead: every row updated hypothetically, nothing committed (ActAll)
     constexpr bool SENS = ActIsSensors<ACT>::v;   // a sensor network: one update per sensor, each with its own site (ActSensors)
+    constexpr bool LSENS = ActIsLookSensors<ACT>::v;   // the lookahead of a sensor network: ALL, one pass per sensor (ActLookSensors)
+    // (ActLookSensors, multi-tile instance: the next tile's loads leave once, behind the last pass -- except with SSA_PROP_ELEMENTS, whose
+    // out-of-line call then spills 8 more VGPRs: there they are issued as in every other kernel, after the propagator and again at the end
+    // of each pass's update)
+    constexpr bool ISSUE_LAST = LSENS && PROP != 0;
+    // (ActLookSensors: the sites' and the outputs' pointers through kernarg_opaque in every pass -- but in that same SSA_PROP_ELEMENTS
+    // instance, which re-derives its argument block per tile anyway and spills across the tile loop with it)
+    constexpr bool PASS_ARGS = LSENS && !(TILE == 1 && PROP == 0);
     int g = lane >> 4, l = lane & 15;
     int64_t obj = obj_in;
     // (TILE 0: the kernel issued the tile's loads from its preloaded pointer arguments before anything else.)  First thing here,
@@ -1284,7 +1322,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     obj = base + g;
     e = (valid && p.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
     // the next tile's inputs: in flight during the transform / covariance / observation / store of this one
-    if (TILE == 1) tile_issue(pf, p, lane, next_base, next_cnt);
+    if (TILE == 1 && !ISSUE_LAST) tile_issue(pf, p, lane, next_base, next_cnt);
 
     // ---- U3: unscented transform, centred form of x = dot(Wm, sigmas_f):
     //   x = sigma_0' + m',   m' = (sum(Wm) - 1) sigma_0' + Wi sum_{i>=1} (sigma_i' - sigma_0')
@@ -1354,9 +1392,16 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         my_update = valid && act >= 0 && (int64_t)act == (p.obj_ids ? (int64_t)t.Oid[g] : obj) && interval_ok;   // (one env: the object index IS the index in the env)
         if (__any(my_update)) __builtin_amdgcn_s_setprio(3);
     }
+    // ActLookSensors: the passes start here, one per sensor.  What the predict left stays in place for every pass: the tile's x- / P-
+    // (t.X / t.P), the truth (t.T), the step's matrix (t.Obs) and, from the first pass on, the sigma points handed to update() (the
+    // left halves of the staging matrices).  Each pass rewrites the residual columns, P+ among them, and starts again from the
+    // predict's status.
+    int look_s = 0;
+look_pass:
+    if constexpr (LSENS) st_new = st_pred;
     bool look_vis = false, look_taken = false;   // (ActAll: the row's visibility and whether its update ran, for the outputs)
     // (ActSensors: the row's sensor matched again here rather than carried across the propagator)
-    const ssa_sensor_params* SP = sensors_of(asrc);
+    const ssa_sensor_params* SP = PASS_ARGS ? kernarg_opaque(sensors_of(asrc)) : sensors_of(asrc);
     if constexpr (SENS) sid = valid ? sensor_index(SP, p.obj_ids ? (int64_t)t.Oid[g] : obj) : -1;
     if (__any(my_update)) {   // whole-wave branch: a wavefront without a selected object skips the block, its variables included
     bool upd_go = false, taken = false, visible = false, attempted = false;
@@ -1383,7 +1428,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                 sf[c] = o[c];
                 xb[c] = t.X[g * 6 + c];   // the prior mean
             }
-            if (C.flags & SSA_FLAG_RESAMPLE) {
+            if ((C.flags & SSA_FLAG_RESAMPLE) && (!LSENS || look_s == 0)) {
                 const int krow = is_pm ? (l - 1) % 6 : 0;
                 const double sgn = (l >= 1 && l <= 6) ? 1.0 : ((l >= 7 && l <= 12) ? -1.0 : 0.0);
 #pragma unroll
@@ -1392,7 +1437,19 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
             }
             // (the left half of the staging row leaves now -- harmless if the object turns out not to be visible -- so that the
             // prior mean does not have to live across the measurement function)
-            if (l <= 12) {
+            if constexpr (LSENS) {
+                // ActLookSensors: the left half holds the sigma point itself (Phase 2 subtracts the prior mean as it reads it), and
+                // keeps it for the later passes, which take their points from there -- and the truth from t.T -- instead of registers
+                if (look_s == 0) {
+                    if (l <= 12) {
+#pragma unroll
+                        for (int c = 0; c < 6; ++c) STG[l * 9 + c] = sf[c];
+                    }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) sf[c] = (l <= 12) ? STG[l * 9 + c] : t.T[g * 6 + c];
+                }
+            } else if (l <= 12) {
 #pragma unroll
                 for (int c = 0; c < 6; ++c) STG[l * 9 + c] = sf[c] - xb[c];
             }
@@ -1414,12 +1471,15 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                             break;
                         }
                     }
+                } else if constexpr (LSENS) {   // (the pass's sensor: one site for the whole wavefront)
+                    hx_aer_enu(sf, Mm, SP->enu[look_s], SP->obs_itrs[look_s], aer, enu_vec);
+                    lim = SP->obs_limit[look_s];
                 } else hx_aer_enu(sf, Mm, C.enu, C.obs_itrs, aer, enu_vec);
                 el_mine = aer[1];
                 if (C.obs_type == SSA_OBS_AER) { z[0] = aer[0]; z[1] = aer[1]; z[2] = aer[2]; }
                 else { z[0] = sf[0]; z[1] = sf[1]; z[2] = sf[2]; }
             }
-            if constexpr (SENS) visible = row_bcast<13>(el_mine) >= lim;   // (as seen from the row's sensor)
+            if constexpr (SENS || LSENS) visible = row_bcast<13>(el_mine) >= lim;   // (as seen from the row's sensor)
             else visible = row_bcast<13>(el_mine) >= C.obs_limit;  // object_visible(): elevation of the TRUE state (:418-425)
             if (rec && l == 13) {
 #pragma unroll
@@ -1484,6 +1544,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
             pend &= ~(0xFFFFull << (gu * 16));
             const double* Rm = C.R;   // (ActSensors: R of row gu's sensor, a wave-uniform index)
             if constexpr (SENS) Rm = SP->R[__builtin_amdgcn_readlane(sid, gu * 16)];
+            if constexpr (LSENS) Rm = SP->R[look_s];
             if (g == gu && l == 13) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) W[54 + c] = y_row[c];
@@ -1502,6 +1563,9 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                     const int k = (cch < 3) ? 4 * cch + kk : 12;   // sigma point; the last chunk holds point 12 and three empty slots
                     const double* row = &SG[k * 9];
                     double av = row[acol];
+                    if constexpr (LSENS) {   // (sigma - x: the left half holds the sigma point)
+                        if (acol < 6) av = av - t.X[gu * 6 + acol];
+                    }
                     double bv = row[6 + (ij < 3 ? ij : 2)] * ((cch == 0 && kk == 0) ? C.Wc0 : C.Wi);
                     if (cch == 3 && kk != 0) { av = 0.0; bv = 0.0; }
                     acc = __builtin_amdgcn_mfma_f64_4x4x4f64(av, bv, acc, 0, 0, 0);
@@ -1541,7 +1605,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                             const double sk = W[u * 3] * W[36 + b * 3] + W[u * 3 + 1] * W[36 + b * 3 + 1] + W[u * 3 + 2] * W[36 + b * 3 + 2];  // (S K^T)[u][b]
                             corr = fma(W[36 + a * 3 + u], sk, corr);
                         }
-                        t.UA[gu * 117 + lane] = t.P[gu * 36 + lane] - corr;
+                        t.UA[gu * 117 + (LSENS ? pp_at<1>(lane) : lane)] = t.P[gu * 36 + lane] - corr;
                     }
                 } else {
                 // x += K y  (lanes 0..5); P -= K S K^T (36 entries, one per lane)
@@ -1597,7 +1661,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     l = lane & 15;
     obj = base + g;
     e = (valid && p.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
-    if (TILE == 1) tile_issue(pf, p, lane, next_base, next_cnt);
+    if (TILE == 1 && !ISSUE_LAST) tile_issue(pf, p, lane, next_base, next_cnt);
     }   // wavefronts holding a selected object
     // envs whose action selects nobody still get a cleared record (written by object 0's row)
     if (!ALL && valid && p.upd && obj == (int64_t)e * p.n_obj && l == 0) {   // (object 0 of an env: one lane per env)
@@ -1664,7 +1728,19 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     }
     if (l == 0) t.St[g] = st_new;
     wave_lds_sync();
-    if constexpr (ALL) {   // the lookahead's outputs; nothing of the step's epilogue (observation, metrics, statistics, tile store)
+    if constexpr (LSENS) {   // sensor look_s's outputs (one env), then the next sensor's pass
+        const bool last = look_s + 1 >= SP->n_sensor;
+        if (TILE == 1 && ISSUE_LAST && last) tile_issue(pf, p, lane, next_base, next_cnt);
+        ssa_lookahead_out os = PASS_ARGS ? *kernarg_opaque(asrc.o) : *asrc.o;
+        if (look_s > 0) os.x_prior = os.P_prior = nullptr;   // (no sensor axis: the first pass wrote them)
+        if (valid) lookahead_store<1>(t, os, g, l, (int64_t)look_s * p.n_obj + (p.obj_ids ? (int64_t)t.Oid[g] : obj), st_new, look_vis, look_taken);
+        if (!last) {
+            ++look_s;
+            wave_lds_sync();   // (this pass's reads of P+ precede the next pass's staging)
+            goto look_pass;
+        }
+        return;
+    } else if constexpr (ALL) {   // the lookahead's outputs; nothing of the step's epilogue (observation, metrics, statistics, tile store)
         if (valid) lookahead_store(t, *asrc.o, g, l, (int64_t)e * p.n_obj + (p.obj_ids ? (int64_t)t.Oid[g] : obj - (int64_t)e * p.n_obj),
                                    st_new, look_vis, look_taken);
         return;
@@ -1962,6 +2038,62 @@ __global__ void __launch_bounds__(64, SSA_STEP_WAVES) lookahead_kernel(int ntile
         const int ncnt = nt < ntiles ? (int)((total - nbase) < OBJ_PER_WAVE ? (total - nbase) : OBJ_PER_WAVE) : 0;
         ActAll all{&k.o};
         process_wave<PROP, 1>(t, k.k.c, k.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, nbase, ncnt, tile, all);
+        wave_lds_sync();   // the tile's LDS reads precede the next tile's commit
+    }
+}
+
+// The lookahead of a sensor network (ssa_lookahead_sensors_f64): lookahead_kernel's launch forms with ActLookSensors; the sensors'
+// block travels behind the lookahead's in the argument segment.
+struct LookSensK {
+    LookK k;
+    ssa_sensor_params s;
+};
+struct LookaheadSensorsArgs {   // the kernarg segment of lookahead_sensors_kernel (see StepFastArgs)
+    int ntiles, nwork;
+    const double *pre_P_in, *pre_x_in, *pre_x_true_in;
+    const int32_t* pre_status;
+    LookSensK k;
+};
+typedef const __attribute__((address_space(4))) LookSensK* LookSensKernargPtr;
+template <int PROP, bool MULTI>
+__global__ void __launch_bounds__(64, SSA_STEP_WAVES) lookahead_sensors_kernel(int ntiles, int nwork, const double* pre_P_in,
+                                                                               const double* pre_x_in, const double* pre_x_true_in,
+                                                                               const int32_t* pre_status, const LookSensK k_arg)
+{
+    __shared__ Tiles t;
+    int lane = threadIdx.x;
+    const int unit = (int)blockIdx.x;
+    const int64_t total = k_arg.k.k.p.n_obj;   // (one env)
+    TileRegs pf;
+    int tile = xcd_tile(unit, nwork);
+    if (!MULTI) {
+        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
+        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
+        tile_dma_issue(t, pf, pre_P_in, pre_x_in, pre_x_true_in, pre_status, lane, base, cnt);
+        // (the outputs' and the sites' block by the argument segment's address, not the argument's: kernarg_opaque takes them)
+        const LookSensK& ka = *(const LookSensK*)(LookSensKernargPtr)((const char*)__builtin_amdgcn_kernarg_segment_ptr() +
+                                                                      offsetof(LookaheadSensorsArgs, k));
+        ActLookSensors look{&ka.k.o, &ka.s};
+        process_wave<PROP, 0>(t, k_arg.k.k.c, k_arg.k.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, look);
+        return;
+    }
+    {
+        const int64_t b0 = (int64_t)tile * OBJ_PER_WAVE;
+        tile_issue(pf, k_arg.k.k.p, lane, b0, tile < ntiles ? (int)((total - b0) < OBJ_PER_WAVE ? (total - b0) : OBJ_PER_WAVE) : 0);
+    }
+    LookSensKernargPtr kp = (LookSensKernargPtr)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(LookaheadSensorsArgs, k));
+    for (; tile < ntiles; tile += nwork) {
+        // (as step_fast_kernel: the argument block and the lane id re-derived per tile)
+        asm volatile("" : "+s"(kp));
+        asm volatile("" : "+v"(lane));
+        const LookSensK& k = *(const LookSensK*)kp;
+        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
+        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
+        const int nt = tile + nwork;
+        const int64_t nbase = (int64_t)nt * OBJ_PER_WAVE;
+        const int ncnt = nt < ntiles ? (int)((total - nbase) < OBJ_PER_WAVE ? (total - nbase) : OBJ_PER_WAVE) : 0;
+        ActLookSensors look{&k.k.o, &k.s};
+        process_wave<PROP, 1>(t, k.k.k.c, k.k.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, nbase, ncnt, tile, look);
         wave_lds_sync();   // the tile's LDS reads precede the next tile's commit
     }
 }
@@ -3572,7 +3704,8 @@ int ssa_env_step_profile_ms(int32_t slot, float* kernel_ms)
         hipEventElapsedTime(kernel_ms, g_prof_ev[slot][0], g_prof_ev[slot][1]) != hipSuccess) return SSA_E_LAUNCH;
     return SSA_OK;
 }
-int ssa_lookahead_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_lookahead_out* o, void* stream)
+// the checks and the argument block shared by ssa_lookahead_f64 and ssa_lookahead_sensors_f64; SSA_OK or the refusal
+static int lookahead_args(const ssa_consts* c, const ssa_step_params* p, const ssa_lookahead_out* o, LookK& k)
 {
     if (!c || !p || !o || p->n_obj <= 0 || p->n_env <= 0) return SSA_E_INVALID;
     if (!p->x_true_in || !p->x_in || !p->P_in || !p->status || !p->trans || !p->env_time) return SSA_E_INVALID;
@@ -3584,7 +3717,6 @@ int ssa_lookahead_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_l
     if (c->propagator == SSA_PROP_J2_RK4 && (c->rk4_substeps < 1 || c->rk4_substeps > 4096)) return SSA_E_INVALID;
     const int64_t total = (int64_t)p->n_env * p->n_obj;
     if (total >= ((int64_t)1 << 31)) return SSA_E_INVALID;
-    LookK k;
     k.k.c = *c;
     k.k.p = *p;
     k.o = *o;
@@ -3596,15 +3728,30 @@ int ssa_lookahead_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_l
     q.obs_mirror = nullptr; q.spos_tiles = nullptr; q.spos_tiles_prev = nullptr; q.fail_log = nullptr; q.fail_count = nullptr;
     q.fail_cap = 0;
     q.launch_mask = p->launch_mask & SSA_LAUNCH_INLINE_ENVS;
+    return SSA_OK;
+}
+// the lookahead's grid: one tile per wavefront up to the resident wavefronts, a grid-stride walk beyond (as the step)
+static void lookahead_grid(int64_t total, int& nt, int& nwork, bool& multi)
+{
     const int64_t ntiles = (total + OBJ_PER_WAVE - 1) / OBJ_PER_WAVE;
     const int64_t slots = (int64_t)device_cu_count() * 4 * SSA_STEP_WAVES;
     const int64_t per_wave = (ntiles + slots - 1) / slots;
-    const int nwork = (int)((ntiles + per_wave - 1) / per_wave);
-    const int nt = (int)ntiles;
+    nwork = (int)((ntiles + per_wave - 1) / per_wave);
+    nt = (int)ntiles;
+    multi = per_wave != 1;
+}
+int ssa_lookahead_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_lookahead_out* o, void* stream)
+{
+    LookK k;
+    const int rc = lookahead_args(c, p, o, k);
+    if (rc != SSA_OK) return rc;
+    int nt, nwork;
+    bool multi;
+    lookahead_grid((int64_t)p->n_env * p->n_obj, nt, nwork, multi);
     const int prop = c->propagator;
     dim3 grid((unsigned)nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
-    if (per_wave == 1) {
+    if (!multi) {
         if (prop == SSA_PROP_FG) hipLaunchKernelGGL((lookahead_kernel<1, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
         else if (prop == SSA_PROP_ELEMENTS) hipLaunchKernelGGL((lookahead_kernel<0, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
         else if (prop == SSA_PROP_HYBRID) hipLaunchKernelGGL((lookahead_kernel<3, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
@@ -3614,6 +3761,40 @@ int ssa_lookahead_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_l
         else if (prop == SSA_PROP_ELEMENTS) hipLaunchKernelGGL((lookahead_kernel<0, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
         else if (prop == SSA_PROP_HYBRID) hipLaunchKernelGGL((lookahead_kernel<3, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
         else hipLaunchKernelGGL((lookahead_kernel<2, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+    }
+    return launch_status();
+}
+int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_lookahead_out* o,
+                              void* stream)
+{
+    if (!c || !p || !sp || !o) return SSA_E_INVALID;
+    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
+    if (p->n_env != 1) return SSA_E_UNSUPPORTED;
+    for (int k = 0; k < sp->n_sensor; ++k)
+        if (!(sp->obs_limit[k] == sp->obs_limit[k])) return SSA_E_INVALID;
+    LookSensK k;
+    const int rc = lookahead_args(c, p, o, k.k);
+    if (rc != SSA_OK) return rc;
+    if ((int64_t)sp->n_sensor * p->n_obj >= ((int64_t)1 << 31)) return SSA_E_INVALID;
+    k.s = *sp;
+    k.s.upd = nullptr;   // (its action words and record destination are not read)
+    for (int q = 0; q < SSA_MAX_SENSORS; ++q) k.s.action[q] = -1;
+    int nt, nwork;
+    bool multi;
+    lookahead_grid(p->n_obj, nt, nwork, multi);
+    const int prop = c->propagator;
+    dim3 grid((unsigned)nwork), block(64);
+    hipStream_t s = (hipStream_t)stream;
+    if (!multi) {
+        if (prop == SSA_PROP_FG) hipLaunchKernelGGL((lookahead_sensors_kernel<1, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        else if (prop == SSA_PROP_ELEMENTS) hipLaunchKernelGGL((lookahead_sensors_kernel<0, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        else if (prop == SSA_PROP_HYBRID) hipLaunchKernelGGL((lookahead_sensors_kernel<3, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        else hipLaunchKernelGGL((lookahead_sensors_kernel<2, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+    } else {
+        if (prop == SSA_PROP_FG) hipLaunchKernelGGL((lookahead_sensors_kernel<1, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        else if (prop == SSA_PROP_ELEMENTS) hipLaunchKernelGGL((lookahead_sensors_kernel<0, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        else if (prop == SSA_PROP_HYBRID) hipLaunchKernelGGL((lookahead_sensors_kernel<3, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        else hipLaunchKernelGGL((lookahead_sensors_kernel<2, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
     }
     return launch_status();
 }

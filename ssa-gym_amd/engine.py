@@ -424,6 +424,44 @@ class HotPathEngine:
         res = {k: self._look[k] for k in ("score", "status", "visible") + want}
         return res
 
+    def launch_lookahead_sensors(self, slot_in, time_offset, sensors, out=(), stream=None):
+        """enqueue the lookahead of a sensor network (include/ssa_hip.h: ssa_lookahead_sensors_f64; one env): launch_lookahead for every
+        sensor of `sensors` (host.make_sensor_params; its action words and record pointer are not read) in one launch -- the predict once,
+        the hypothetical update once per sensor, from its site with its elevation mask and R.  Nothing of the engine's state is written.
+        Returns a dict of this engine's output tensors, objects at the caller's indices: score [S, m, 3], status [S, m] int32,
+        visible [S, m] uint8 and the parts of LOOKAHEAD_PARTS asked for in `out` (x_prior [m, 6], P_prior [m, 6, 6] -- the prediction, the
+        same for every sensor -- and P_post [S, m, 6, 6]).  The buffers are allocated on first use (again when S changes) and reused by
+        the next call.  Asynchronous, no host sync."""
+        if self.E != 1:
+            raise _lib.SsaHipError("the lookahead of a sensor network covers one env (n_env == 1)")
+        S, m = int(sensors.n_sensor), self.m
+        want = tuple(out)
+        bad = [k for k in want if k not in self.LOOKAHEAD_PARTS]
+        if bad:
+            raise ValueError("launch_lookahead_sensors: unknown output(s) %s (choose from %s)" % (bad, self.LOOKAHEAD_PARTS))
+        if getattr(self, "_look_s", None) is None or self._look_s["score"].shape[0] != S:
+            self._look_s = {"score": torch.empty((S, m, _lib.LOOK_NSCORE), dtype=f64, device=self.dev),
+                            "status": torch.empty((S, m), dtype=torch.int32, device=self.dev),
+                            "visible": torch.empty((S, m), dtype=torch.uint8, device=self.dev)}
+        shapes = {"x_prior": (m, 6), "P_prior": (m, 6, 6), "P_post": (S, m, 6, 6)}
+        for k in want:
+            if k not in self._look_s:
+                self._look_s[k] = torch.empty(shapes[k], dtype=f64, device=self.dev)
+        o = _lib.ssa_lookahead_out()
+        o.score, o.status, o.visible = (self._look_s[k].data_ptr() for k in ("score", "status", "visible"))
+        for k in self.LOOKAHEAD_PARTS:
+            setattr(o, k, self._look_s[k].data_ptr() if k in want else 0)
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        p = _lib.ssa_step_params()
+        C.memmove(C.byref(p), C.byref(self._p), C.sizeof(p))
+        sl = int(slot_in) % self.H
+        p.x_true_in, p.x_in, p.P_in = self._bx_t + sl * self._sx, self._bx + sl * self._sx, self._bP + sl * self._sP
+        p.time_offset, p.launch_mask = int(time_offset), 0
+        rc = self._lib.ssa_lookahead_sensors_f64(self._cref, C.byref(p), C.byref(sensors), C.byref(o), s)
+        if rc:
+            raise _lib.SsaHipError("ssa_lookahead_sensors_f64 failed with code %d" % rc)
+        return {k: self._look_s[k] for k in ("score", "status", "visible") + want}
+
     def launch_rollout(self, slot_in, time_offset, actions, stream=None, argmax_spos=False):
         """K = actions.shape[0] consecutive steps in one launch (include/ssa_hip.h: ssa_env_rollout_f64): step k reads
         history slot (slot_in + k) % H, writes (slot_in + k + 1) % H and has time index time_offset + k.  `actions`

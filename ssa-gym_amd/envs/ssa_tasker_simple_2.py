@@ -1188,6 +1188,32 @@ class SSA_Tasker_Env(Env):
             res[k] = r[k]
         return res
 
+    def lookahead_sensors(self, covariances=False):
+        """The lookahead of every sensor of the network (no reference counterpart; include/ssa_hip.h: ssa_lookahead_sensors_f64; DESIGN.md
+        section 8d): for every sensor s and object j, what step() would produce for j at the next step if s were tasked to j and no other
+        sensor were -- lookahead() from sensor s's site, with its elevation mask and R -- in ONE launch that predicts every object once.
+        Nothing of the env changes.  A dict of CUDA tensors, objects in the env's own order, S = n_sensor (1 without config['observers']:
+        the env's own observer):
+            score   [S, 3, m]  float64: rows as lookahead()'s score (_lib.LOOK_*); NaN unless status == OK and visible from s
+            visible [S, m]     uint8: the update's visibility test from site s at the next step
+            status  [S, m]     int32: the SSA_ST_* code the step would leave on j (a singular S is per sensor)
+        and with covariances=True also x_prior [m, 6], P_prior [m, 6, 6] (the prediction, the same for every sensor) and P_post
+        [S, m, 6, 6].  The tensors are the env's buffers: the next call overwrites them."""
+        from .. import engine as _engine
+        if self._engine is None:
+            raise _lib.SsaHipError("no device state: the lookahead runs on the GPU only (no CPU fallback)")
+        if self.i + 1 >= self.n:
+            raise ValueError("lookahead_sensors: the episode has no next step (i = %d, steps = %d)" % (self.i, self.n))
+        if getattr(self, "_look_sites", None) is None:   # (the network's sites; without observers the env's one observer)
+            self._look_sites = self._sensors if self.n_sensor > 1 else host.make_sensor_params([self.obs_lla], [self.obs_limit], [self.R], 0)
+        e = self._engine
+        want = _engine.HotPathEngine.LOOKAHEAD_PARTS if covariances else ()
+        r = e.launch_lookahead_sensors(self.i % e.H, self.i + 1, self._look_sites, out=want, stream=self._stream.cuda_stream)
+        res = {"score": r["score"].permute(0, 2, 1), "visible": r["visible"], "status": r["status"]}
+        for k in want:
+            res[k] = r[k]
+        return res
+
     def aer_obs(self, obs):
         """:834-840 -- [az, el, range, trace(P)] per object, NaN/inf -> 0.001."""
         from .. import device
