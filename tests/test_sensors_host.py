@@ -172,3 +172,61 @@ def test_sensor_kernels_keep_the_step_kernels_budget(tmp_path):
             assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)
         checked += 1
     assert checked == 8
+
+
+# ---- the network's geometry at eight sites against the oracle's own (oracle/ssa_oracle.c: lla2ecef, ecef2aer), not the host's formulas.
+# (lat [deg], lon [deg], h [m]): the default observer, south-east, high altitude, the antimeridian, far north, far south, a pole, (0, 0)
+SITES8 = [(38.828198, -77.305352, 20.0), (-31.9, 115.9, 20.0), (19.8, -155.5, 4200.0), (-17.7, 179.95, 5.0),
+          (78.2, 15.6, 500.0), (-77.8, 166.7, 200.0), (89.9995, 45.0, 10.0), (0.0, 0.0, 0.0)]
+
+
+def sites_rad(sites=SITES8):
+    return [np.array([np.radians(la), np.radians(lo), h]) for la, lo, h in sites]
+
+
+def _net8():
+    from ssa_gym_amd import host
+    lla = sites_rad()
+    lim = np.radians([15.0, -90.0, 30.0, 0.0, 5.0, -10.0, 20.0, 90.0])
+    Rs = [np.diag([(1.0 + k) ** 2, (0.5 + 2.0 * k) ** 2, (1e3 / (1 + k)) ** 2]) * [host.arcsec2rad ** 2, host.arcsec2rad ** 2, 1]
+          for k in range(8)]
+    return lla, lim, Rs, host.make_sensor_params(lla, lim, Rs, 480 * 10 * 3)
+
+
+def test_sensor_sites_against_the_oracle(lib, oracle):
+    """each site's observer position within a few ulp of the oracle's lla2ecef, and enu^T d the oracle's ecef2aer (az, el, range) for
+    directions all over the sky -- north and south of the horizon, through the zenith and the nadir"""
+    lla, _, _, sp = _net8()
+    rs = np.random.RandomState(0)
+    dirs = rs.normal(size=(64, 3))
+    dirs /= np.linalg.norm(dirs, axis=1)[:, None]
+    for s, site in enumerate(lla):
+        o = oracle.lla2ecef(site)
+        got = np.array(sp.obs_itrs[s][:])
+        assert np.all(np.abs(got - o) <= 4 * np.spacing(np.linalg.norm(o))), (s, got - o)
+        enu = np.array(sp.enu[s][:]).reshape(3, 3)
+        for k, u in enumerate(dirs):
+            d = u * (1e6 + 4e7 * k / len(dirs))
+            ref = oracle.ecef2aer(site, o + d, o)
+            R = enu.T @ d
+            r = np.linalg.norm(d)
+            assert abs(np.linalg.norm(R) - ref[2]) <= 1e-14 * ref[2], (s, k)
+            el = np.arctan2(R[2], np.hypot(R[0], R[1]))
+            assert abs(el - ref[1]) <= 1e-13 + 1e-15 / max(np.cos(ref[1]), 1e-12), (s, k, el, ref[1])   # (asin near +-90 deg)
+            if np.hypot(R[0], R[1]) > 1e-3 * r:
+                daz = (np.arctan2(R[1], R[0]) - ref[0] + np.pi) % (2 * np.pi) - np.pi
+                assert abs(daz) <= 1e-13, (s, k, daz)
+
+
+def test_sensor_params_slices_are_the_kernel_consts_of_each_site(lib):
+    """site s's slice of make_sensor_params is, bit for bit, what kernel_consts gives an env observing from that site alone"""
+    from ssa_gym_amd.envs import env_config
+    from ssa_gym_amd.envs._config import kernel_consts
+    lla, lim, Rs, sp = _net8()
+    cfg = dict(env_config)
+    Q = np.eye(6)
+    for s in range(8):
+        c, _ = kernel_consts(cfg, Q, Rs[s], 20.0, lim[s], lla[s])
+        for name, got, want in (("enu", sp.enu[s][:], c.enu[:]), ("obs_itrs", sp.obs_itrs[s][:], c.obs_itrs[:]),
+                                ("R", sp.R[s][:], c.R[:]), ("obs_limit", [sp.obs_limit[s]], [c.obs_limit])):
+            assert np.array_equal(np.array(got).view(np.int64), np.array(want).view(np.int64)), (s, name)

@@ -1,0 +1,615 @@
+"""Sensor networks against the CPU oracle at eight sites (include/ssa_hip.h: ssa_env_step_sensors_f64, ssa_lookahead_sensors_f64;
+config['observers']).
+
+tests/test_sensors_gpu.py and tests/test_lookahead_sensors_gpu.py hold the network kernels to the project's own single-sensor kernels,
+whose constants come from the same host code (host.enu_matrix, host.lla2ecef) and which run the same device geometry.  Here the ground
+truth is oracle/ssa_oracle.c, which builds its own observer position (lla2ecef) and local frame (ecef2aer) from the site: every site is
+handed to it as (lat, lon, h) in radians with oracle.lla2ecef(site) as its position, never through the host.  The sites
+(tests/test_sensors_host.py: SITES8) are south of the equator, east of Greenwich, high, at the antimeridian, near both poles and at
+(0, 0); the states are built where the geometry is delicate: near the zenith, across north, within 1e-9 rad of an elevation mask.
+
+Three values as in tests/test_hip_step.py: the kernel, the oracle in fp64 (the reference's arithmetic) and in 80-bit (the exact value).
+A state is built in the ITRS at the step's time, rotated into the GCRS with M^T and -- where a step or a lookahead propagates it --
+propagated 20 s back with the 80-bit oracle, so that the step's own prediction brings it to the intended place."""
+import numpy as np
+import pytest
+
+import oracle as orc
+from test_hip_step import c2t, errs, make_batch
+from test_sensors_host import SITES8, sites_rad
+
+pytestmark = pytest.mark.gpu
+
+MASKS_DEG = [15.0, -90.0, 30.0, 0.0, 5.0, -10.0, 20.0, 90.0]   # (sensor 7 sees nothing)
+ALPHA, TIX, DT = 1e-3, 5, 20.0
+EPS = np.finfo(np.float64).eps
+BAND = 3e-13          # elevations this close to a mask are not judged (tests/test_agent_ops.py)
+NEAR_ZENITH = np.radians(89.9)
+MU = 3.986004418e14
+ARCSEC = np.pi / 648000.0
+
+
+@pytest.fixture(scope="module")
+def hip():
+    import torch
+    import ssa_gym_amd
+    from ssa_gym_amd import _lib
+    ssa_gym_amd.build()
+    _lib.load()
+    assert torch.cuda.is_available()
+    return torch
+
+
+def _wrap(a):
+    return (np.asarray(a) + np.pi) % (2 * np.pi) - np.pi
+
+
+def _sigmas(obs_type):
+    """per-sensor measurement sigmas, different per sensor and per axis: 'aer' (az [arcsec], el [arcsec], range [m]) in radians, 'xyz' [m]"""
+    if obs_type == 'aer':
+        return np.array([[(1.0 + k) * ARCSEC, (0.5 + 2.0 * k) * ARCSEC, 1e3 / (1 + k)] for k in range(8)])
+    return np.array([[300.0 + 50 * k, 500.0 - 40 * k, 800.0 + 100 * k] for k in range(8)])
+
+
+class Net:
+    """the eight sensors as the oracle sees them, and the same network packed for the kernels"""
+
+    def __init__(self, oracle, obs_type='aer'):
+        self.lla = sites_rad()
+        self.itrs = [oracle.lla2ecef(s) for s in self.lla]
+        self.lim = np.radians(MASKS_DEG)
+        self.sig = _sigmas(obs_type)
+        self.R = [np.diag(s ** 2) for s in self.sig]
+        self.obs_type = obs_type
+        self.ot = 0 if obs_type == 'aer' else 1
+        self.S = len(self.lla)
+
+    def params(self, zn_stride_sensor):
+        from ssa_gym_amd import host
+        return host.make_sensor_params(self.lla, self.lim, self.R, zn_stride_sensor)
+
+
+def _frame(site):
+    lat, lon = site[0], site[1]
+    e = np.array([-np.sin(lon), np.cos(lon), 0.0])
+    n = np.array([-np.sin(lat) * np.cos(lon), -np.sin(lat) * np.sin(lon), np.cos(lat)])
+    u = np.array([np.cos(lat) * np.cos(lon), np.cos(lat) * np.sin(lon), np.sin(lat)])
+    return e, n, u
+
+
+def place(site, itrs, M, az, el, rng, rs):
+    """a GCRS state whose ITRS position is seen from `site` at (az, el, range) under M; velocity: circular, in a random plane"""
+    e, n, u = _frame(site)
+    p = np.asarray(M).reshape(3, 3).T @ (itrs + rng * (np.cos(el) * np.cos(az) * n + np.cos(el) * np.sin(az) * e + np.sin(el) * u))
+    w = np.cross(p, rs.normal(size=3))
+    v = np.sqrt(MU / np.linalg.norm(p)) * w / np.linalg.norm(w)
+    return np.concatenate([p, v])
+
+
+def _aer(o, x, site, itrs, M):
+    return o.hx_aer(np.atleast_2d(x), M, site, itrs)
+
+
+def _aer_witness(x, site, itrs, M):
+    """(az, el, range) in 80-bit arithmetic with the elevation as atan2(u, hypot(e, n)): the witness near the zenith and the nadir, where
+    asin(u / r) -- the oracle's, in either precision -- loses digits, or returns NaN once u / r has rounded past +-1.  The local frame
+    is the oracle's (ecef2aer), the observer position oracle.lla2ecef(site)"""
+    L = np.longdouble
+    lat, lon = L(site[0]), L(site[1])
+    sl, cl, so, co = np.sin(lat), np.cos(lat), np.sin(lon), np.cos(lon)
+    d = np.atleast_2d(x)[:, :3].astype(L) @ np.asarray(M, dtype=np.float64).reshape(3, 3).astype(L).T - np.asarray(itrs).astype(L)
+    n = -sl * co * d[:, 0] - sl * so * d[:, 1] + cl * d[:, 2]
+    e = -so * d[:, 0] + co * d[:, 1]
+    u = cl * co * d[:, 0] + cl * so * d[:, 1] + sl * d[:, 2]
+    az = np.arctan2(e, n)
+    az = np.where(az < 0, az + 2 * np.pi, az)
+    return np.stack([az, np.arctan2(u, np.hypot(e, n)), np.sqrt((d * d).sum(axis=1))], axis=1).astype(np.float64)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1. geometry per site
+def _geometry_states(s, net, M, rs):
+    """(states, kind): make_batch states, near the zenith (and the nadir), within +-1e-3 rad of north, within 1e-9 rad of the mask"""
+    site, itrs, lim = net.lla[s], net.itrs[s], net.lim[s]
+    xs, kind = [], []
+    xt, _, _, _ = make_batch(128, seed=40 + s)
+    xs += list(xt)
+    kind += ["batch"] * len(xt)
+    for k, d in enumerate([1.5e-3, 3e-4, 5e-5, 4e-6, 1e-6, 7e-7, 1e-7, 3e-8, 1e-9]):
+        for sgn in (1, -1):
+            xs.append(place(site, itrs, M, rs.uniform(0, 2 * np.pi), sgn * (np.pi / 2 - d), rs.uniform(1.5e6, 3.6e7), rs))
+            kind.append("zenith")
+    for d in (1e-3, 2e-4, 1e-6, 1e-9, 1e-12, 1e-15, 0.0):
+        for sgn in (1, -1):
+            for el in (np.radians(40.0), rs.uniform(-1.2, 1.2)):
+                xs.append(place(site, itrs, M, sgn * d, el, rs.uniform(1.5e6, 3.6e7), rs))
+                kind.append("north")
+    for d in (1e-9, 6e-10, 2e-10, 5e-11, 7e-12, 1e-12):
+        for sgn in (1, -1):
+            el = lim + sgn * d
+            if abs(el) >= np.pi / 2:
+                continue
+            rng = 2.2e7 if el < -0.5 else rs.uniform(2e6, 3.6e7)
+            xs.append(place(site, itrs, M, rs.uniform(0, 2 * np.pi), el, rng, rs))
+            kind.append("mask")
+    return np.array(xs), np.array(kind)
+
+
+def test_geometry_at_eight_sites(hip, oracle, oracle_ld):
+    """device hx_aer and visible_mask against oracle.hx_aer (fp64 and 80-bit) at every site, with the site's consts from make_consts"""
+    import torch
+    from ssa_gym_amd import device, host
+    net = Net(oracle)
+    M = c2t()[TIX]
+    Md = torch.as_tensor(np.ascontiguousarray(M.reshape(3, 3)), dtype=torch.float64).cuda()
+    g = make_batch(1, seed=0)[3]
+    rs = np.random.RandomState(17)
+    for s in range(net.S):
+        site, itrs, lim = net.lla[s], net.itrs[s], net.lim[s]
+        consts = host.make_consts(g["Q"], net.R[s], ALPHA, 2.0, -3, DT, lim, site)
+        x, kind = _geometry_states(s, net, M, rs)
+        xd = torch.as_tensor(x).cuda()
+        zd = device.hx_aer(xd, Md, consts).cpu().numpy()
+        vis = device.visible_mask(xd, Md, consts).cpu().numpy().astype(bool)
+        zf, zl = _aer(oracle, x, site, itrs, M), _aer(oracle_ld, x, site, itrs, M)
+        zen = np.abs(_aer_witness(x, site, itrs, M)[:, 1]) > NEAR_ZENITH
+        zl[zen] = _aer_witness(x[zen], site, itrs, M)
+        # elevation, azimuth (modulo 2 pi) within 1e-13 rad of the reference away from the zenith
+        far = ~zen
+        # (the azimuth is defined only to the rounding of the ITRS position over the horizontal distance h: that term where it matters)
+        h = zl[:, 2] * np.cos(zl[:, 1])
+        cond_az = 4 * EPS * np.linalg.norm(x[:, :3], axis=1) / np.maximum(h, 1e-300)
+        e_el = np.abs(zd[:, 1] - zf[:, 1])
+        e_az = np.abs(_wrap(zd[:, 0] - zf[:, 0]))
+        assert e_el[far].max() <= 1e-13 and np.all(e_az[far] <= 1e-13 + cond_az[far]), (s, e_el[far].max(), e_az[far].max())
+        assert np.all((zd[:, 0] >= 0) & (zd[:, 0] <= 2 * np.pi)), s
+        # near the zenith (and the nadir) the reference's asin(u / r) loses digits: the kernel no further from the exact value than 3x
+        # the reference arithmetic is (the azimuth: or the conditioning bound above, when that is larger)
+        ref_el, ref_az = np.abs(zf[:, 1] - zl[:, 1]), np.abs(_wrap(zf[:, 0] - zl[:, 0]))
+        ref_el[np.isnan(ref_el)] = np.inf        # (the reference's asin(u / r) past +-1)
+        dev_el, dev_az = np.abs(zd[:, 1] - zl[:, 1]), np.abs(_wrap(zd[:, 0] - zl[:, 0]))
+        assert np.all(dev_el[zen] <= 3 * ref_el[zen] + 1e-15), (s, dev_el[zen], ref_el[zen])
+        assert np.all(dev_az[zen] <= np.maximum(3 * ref_az[zen], cond_az[zen]) + 1e-15), (s, dev_az[zen], ref_az[zen], cond_az[zen])
+        # range: 1e-15 relative (plus the rounding of the ITRS position it is formed from: LEO objects are seen from a few hundred km)
+        e_r = np.abs(zd[:, 2] - zl[:, 2])
+        assert np.all(e_r <= 1e-15 * zl[:, 2] + 4 * EPS * np.linalg.norm(x[:, :3], axis=1)), (s, (e_r / zl[:, 2]).max())
+        # the mask: identical to the reference's elevation test outside the band (the 80-bit elevation where fp64 asin loses digits)
+        el_ref = np.where(zen, zl[:, 1], zf[:, 1])
+        judged = np.abs(el_ref - lim) > BAND
+        assert np.array_equal(vis[judged], (el_ref >= lim)[judged]), (s, np.where(vis[judged] != (el_ref >= lim)[judged])[0])
+        near_mask = judged & (np.abs(zl[:, 1] - lim) < 1e-9)
+        within_1e6 = zen & (np.pi / 2 - np.abs(zl[:, 1]) < 1e-6)
+        north = (kind == "north") & (np.abs(_wrap(zl[:, 0])) <= 1e-3)
+        counts = dict(batch=int((kind == "batch").sum()), zenith=int(zen.sum()), zenith_1e6=int(within_1e6.sum()),
+                      north_east=int((north & (_wrap(zl[:, 0]) > 0)).sum()), north_west=int((north & (_wrap(zl[:, 0]) < 0)).sum()),
+                      near_mask=int(near_mask.sum()), visible=int(vis.sum()))
+        print("[geometry] site %d %s mask %g deg: %s; max |el| err %.1e |az| err %.1e (away from the zenith)"
+              % (s, SITES8[s], MASKS_DEG[s], counts, e_el[far].max(), e_az[far].max()))
+        assert all(v > 0 for k, v in counts.items() if k != "visible"), (s, counts)
+        if MASKS_DEG[s] == 90.0:
+            assert not vis.any()
+        if MASKS_DEG[s] == -90.0:
+            assert vis.all()
+
+
+# ------------------------------------------------------------------------------------------------- 2. the sensor step against the oracle
+class Scene:
+    """a batch of m objects at time index TIX - 1 with, per sensor s, three constructed objects (near its zenith, its sigma points across
+    its north, within 1e-9 rad of its mask), and the fp64 / 80-bit truth the step's prediction leads to"""
+
+    def __init__(self, oracle, oracle_ld, net, m, seed):
+        rs = np.random.RandomState(seed)
+        xt, x, P, g = make_batch(m, seed=seed)
+        self.g, self.m = g, m
+        M = c2t()[TIX]
+        self.M = M
+        fixed = [m - 1, m - 2] + ([20479, 20480, 20481, m - 3] if m > 20480 else [])     # (the last tile; the second instance's edge)
+        rows = np.r_[fixed, rs.choice(np.setdiff1d(np.arange(m), fixed), 3 * net.S - len(fixed), replace=False)]
+        self.zen, self.north, self.mask = rows[:net.S], rows[net.S:2 * net.S], rows[2 * net.S:]
+        back = lambda v: oracle_ld.propagate(v, -DT)[0]
+        for s in range(net.S):
+            site, itrs, lim = net.lla[s], net.itrs[s], net.lim[s]
+            # near the zenith: truth and filter mean there (1.5e-3 .. 2e-6 rad below it), the filter 30 m off the truth
+            d = [1.5e-3, 4e-4, 1e-4, 2e-5, 6e-6, 2e-6, 1e-4, 3e-5][s]
+            t = place(site, itrs, M, rs.uniform(0, 2 * np.pi), np.pi / 2 - d, rs.uniform(2e6, 8e6), rs)
+            xt[self.zen[s]] = back(t)
+            x[self.zen[s]] = back(t + np.r_[rs.normal(size=3) * 30.0, rs.normal(size=3) * 0.03])
+            # across north: the filter's predicted mean 1e-7 rad east or west of north, the truth on the other side, above the mask
+            el = np.clip(lim, -0.2, 1.2) + 0.15
+            rng = rs.uniform(3e6, 1.2e7)
+            sgn = 1 if s % 2 else -1
+            f = place(site, itrs, M, sgn * 1e-7, el, rng, rs)
+            t = place(site, itrs, M, -sgn * 3e-6, el + 1e-5, rng, rs)
+            x[self.north[s]], xt[self.north[s]] = back(f), back(np.r_[t[:3], f[3:]])
+            # within 1e-9 rad of the mask (90 deg: 2e-7 rad below the zenith -- closer, the reference's asin(u / r) can turn NaN, which
+            # its visibility test reads as 'not visible'; -90 deg: 0.3 rad above the nadir, through the Earth.  test_geometry_at_eight_sites
+            # goes closer)
+            dm = [8e-10, 0.3, 7e-10, 3e-10, 9e-10, 6e-10, 4e-10, 2e-7][s]
+            el = lim + (1 if s % 2 else -1) * dm
+            el = np.clip(el, -np.pi / 2 + dm, np.pi / 2 - dm)
+            t = place(site, itrs, M, rs.uniform(0, 2 * np.pi), el, 2.2e7 if el < -0.5 else rs.uniform(3e6, 2e7), rs)
+            xt[self.mask[s]] = back(t)
+            x[self.mask[s]] = back(t + np.r_[rs.normal(size=3) * 100.0, rs.normal(size=3) * 0.1])
+        self.xt, self.x, self.P = xt, x, P
+        # the truth at the step (fp64, as the oracle's step propagates it) and its elevation from every site; 80-bit near the zenith
+        xt1 = oracle.propagate(xt, DT)
+        self.el = np.empty((net.S, m))
+        for s in range(net.S):
+            zf = _aer(oracle, xt1, net.lla[s], net.itrs[s], M)[:, 1]
+            zen = ~(np.abs(zf) <= NEAR_ZENITH)
+            if zen.any():
+                zf[zen] = _aer_witness(xt1[zen], net.lla[s], net.itrs[s], M)[:, 1]
+            self.el[s] = zf
+        self.vis = self.el >= net.lim[:, None]
+        self.clear = np.abs(self.el - net.lim[:, None]) > 1e-7      # (comfortably on one side of the mask)
+        # seen by a sensor that does not see everything or nothing (sensors 1 and 7: masks -90 and 90 deg)
+        self.seen = self.vis & self.clear & (np.abs(net.lim) < 1.5)[:, None]
+
+
+def _engine(hip, net, sc, propagator):
+    from ssa_gym_amd import engine, host
+    import torch
+    m, S = sc.m, net.S
+    consts = host.make_consts(sc.g["Q"], net.R[0], ALPHA, 2.0, -3, DT, net.lim[0], net.lla[0], obs_type=net.obs_type,
+                              propagator=propagator)
+    # the env's noise table (ssa_tasker_simple_2.py: reset, _build_engine): (S, n, m, 3), sensor s's sigmas, stride n m 3 between sensors
+    gen = torch.Generator(device="cuda").manual_seed(1234 + m)
+    zn = torch.randn((S, 480, m, 3), dtype=torch.float64, device="cuda", generator=gen) * \
+        torch.as_tensor(net.sig, dtype=torch.float64, device="cuda").view(S, 1, 1, 3)
+    eng = engine.HotPathEngine(consts, m, 1, c2t(), zn, history=2)
+    eng.load_state(0, sc.xt, sc.x, sc.P)
+    return eng, zn, net.params(480 * m * 3)
+
+
+def _launch(hip, eng, sp, acts, failed=()):
+    import torch
+    from ssa_gym_amd import _lib
+    eng.status.zero_()
+    eng.fail_count.zero_()
+    keep = [(int(j), eng.x_filter[0, int(j)].clone(), eng.P_filter[0, int(j)].clone()) for j in failed]
+    for j in failed:       # (as the env leaves a failed filter: its status word and the sentinel state)
+        eng.status[int(j)] = _lib.ST_PREDICT_NAN
+        eng.x_filter[0, int(j)] = torch.as_tensor(orc.X_FAILED)
+        eng.P_filter[0, int(j)] = torch.diag(torch.as_tensor(orc.X_FAILED))
+    upd = torch.zeros((len(acts), _lib.UPD_STRIDE), dtype=torch.float64, device="cuda")
+    eng.launch_step_sensors(0, 1, TIX, sp, [int(a) for a in acts], upd.data_ptr())
+    torch.cuda.synchronize()
+    for j, xj, Pj in keep:
+        eng.x_filter[0, j], eng.P_filter[0, j] = xj, Pj
+    return dict(x=eng.x_filter[1].cpu().numpy(), P=eng.P_filter[1].cpu().numpy(), xt=eng.x_true[1].cpu().numpy(),
+                st=eng.status.cpu().numpy(), upd=upd.cpu().numpy())
+
+
+def _scenarios(net, sc, rs):
+    """launches of S actions each (and the filters that have failed before it), with the category of every (sensor, action)"""
+    S, m = net.S, sc.m
+    special = set(np.r_[sc.zen, sc.north, sc.mask].tolist())
+    ok = np.array([j not in special for j in range(m)])
+    out = [(list(sc.zen), (), ["zenith"] * S), (list(sc.north), (), ["north"] * S), (list(sc.mask), (), ["mask"] * S)]
+    # visible objects, one per sensor (sensor 7 sees nothing: an object another sensor sees)
+    used, acts = set(), []
+    for s in range(S):
+        cand = np.where(ok & sc.vis[s] & sc.clear[s])[0] if s != 7 else np.where(ok & sc.seen.any(axis=0))[0]
+        j = int(rs.choice([c for c in cand if c not in used]))
+        used.add(j)
+        acts.append(j)
+    out.append((acts, (), ["visible"] * 7 + ["hidden"]))
+    # hidden from its sensor but visible to another; a failed filter; two sensors on one object; an idle sensor
+    acts, used = [-1] * S, set()
+    for s in (0, 2, 3, 4, 7):
+        cand = np.where(ok & ~sc.vis[s] & sc.clear[s] & sc.seen.any(axis=0))[0]
+        j = int(rs.choice([c for c in cand if c not in used]))
+        used.add(j)
+        acts[s] = j
+    bad = int(rs.choice([c for c in np.where(ok)[0] if c not in used]))
+    acts[1] = bad
+    both = int(rs.choice([c for c in np.where(ok & sc.vis[5] & sc.clear[5])[0] if c not in used and c != bad]))
+    acts[5], acts[6] = both, both
+    cats = ["hidden"] * S
+    cats[1], cats[5], cats[6] = "failed", "shared", "shared_loser"
+    out.append((acts, (bad,), cats))
+    acts = list(acts)
+    acts[4] = -1
+    cats = list(cats)
+    cats[4] = "idle"
+    out.append((acts, (bad,), cats))
+    return out
+
+
+def _oracle_one(o, net, sc, j, s, zn3, centred, status=0):
+    Wm, Wc, scale = orc.merwe_weights(ALPHA, 2.0, -3)
+    st = np.array([status], dtype=np.int32)
+    r = o.env_step(sc.xt[j:j + 1], sc.x[j:j + 1], sc.P[j:j + 1], st, DT, sc.g["Q"], net.R[s], Wm, Wc, scale, 0, sc.M, net.lla[s],
+                   net.itrs[s], net.lim[s], zn3, obs_type=net.ot, centred=centred)
+    r["status"] = st
+    return r
+
+
+def _az_of(o, net, s, pos, M):
+    return _aer(o, np.c_[pos, np.zeros_like(pos)], net.lla[s], net.itrs[s], M)[:, 0]
+
+
+def check_update(net, sc, rec, dev, j, s, f, ld, oracle, tag):
+    """one object's update record and state against the oracle's step on that object alone (criteria of
+    tests/test_hip_step.py: test_update_parity_every_object); returns (gpu, reference) distances from the exact value"""
+    from ssa_gym_amd import _lib
+    assert rec[_lib.UPD_ACTION] == j, (tag, s, j, rec[:8])
+    assert rec[_lib.UPD_OBS_TAKEN] == float(f["obs_taken"]), (tag, s, j)
+    el = _aer(oracle, f["x_true"], net.lla[s], net.itrs[s], sc.M)[0, 1]
+    if abs(el) > NEAR_ZENITH:
+        el = sc.el[s, j]
+    assert rec[_lib.UPD_VISIBLE] == float(el >= net.lim[s]), (tag, s, j, el, net.lim[s])
+    # z_true: 1e-12 relative per component (az modulo 2 pi; its conditioning h = horizontal distance where the truth is near the zenith)
+    zt, zf = rec[_lib.UPD_Z_TRUE:_lib.UPD_Z_TRUE + 3], f["z_true"]
+    if net.obs_type == 'aer':
+        dx = np.linalg.norm(dev["xt"][j, :3] - f["x_true"][0, :3]) + 4 * EPS * np.linalg.norm(f["x_true"][0, :3])
+        h = zf[2] * np.cos(zf[1])
+        assert abs(_wrap(zt[0] - zf[0])) <= 1e-12 * 2 * np.pi + 2 * dx / h, (tag, s, j, zt, zf)
+        # (near the zenith the reference's asin(u / r) carries eps / (pi / 2 - el))
+        zen_tol = 0.0 if abs(zf[1]) < NEAR_ZENITH else 2 * dx / zf[2] + 8 * EPS / max(np.pi / 2 - abs(sc.el[s, j]), 1e-12)
+        assert abs(zt[1] - zf[1]) <= 1e-12 + zen_tol, (tag, s, j, zt, zf)
+        assert abs(zt[2] - zf[2]) <= 1e-12 * zf[2], (tag, s, j, zt, zf)
+    else:
+        assert np.linalg.norm(zt - zf) <= 1e-12 * np.linalg.norm(zf), (tag, s, j, zt, zf)
+    if f["obs_taken"]:
+        Sd = np.sqrt(np.diag(ld["S"]))
+        e_y = np.max(np.abs(rec[_lib.UPD_Y:_lib.UPD_Y + 3] - ld["y"]) / Sd)
+        e_S = np.max(np.abs(rec[_lib.UPD_S:_lib.UPD_S + 9].reshape(3, 3) - ld["S"]) / np.outer(Sd, Sd))
+        assert e_y < 1e-3 and e_S < 1e-2, (tag, s, j, e_y, e_S)
+        sh = rec[_lib.UPD_SIGMAS_H:_lib.UPD_SIGMAS_H + 39].reshape(13, 3)
+        if net.obs_type == 'aer':
+            assert np.all(np.abs(_wrap(sh[:, 0] - f["sigmas_h"][:, 0])) <= 1e-7 + 1e-12 * 2 * np.pi), (tag, s, j)
+            np.testing.assert_allclose(sh[:, 1:], f["sigmas_h"][:, 1:], rtol=1e-12, atol=1e-7)
+        else:              # (positions: 1e-12 relative to the vector, a GEO object's small component included)
+            d = np.linalg.norm(sh - f["sigmas_h"], axis=1)
+            assert np.all(d <= 1e-12 * np.linalg.norm(f["sigmas_h"], axis=1) + 1e-7), (tag, s, j, d)
+    one = lambda r: {"x": r["x"][-1:], "P": r["P"][-1:]}
+    g = errs({"x": dev["x"][j:j + 1], "P": dev["P"][j:j + 1]}, one(ld))
+    r = errs(one(f), one(ld))
+    assert g[0][0] < 1e-5 and g[1][0] < 1e-5, (tag, s, j, g)      # (sanity bound; the statistical criterion is the caller's)
+    return np.array(g)[:, 0], np.array(r)[:, 0]
+
+
+def run_network_step(hip, oracle, oracle_ld, net, sc, propagator, pred_ld, tag):
+    from ssa_gym_amd import _lib
+    eng, zn, sp = _engine(hip, net, sc, propagator)
+    rs = np.random.RandomState(sc.m)
+    seen = {k: 0 for k in ("visible", "north", "zenith", "mask", "hidden_seen_by_another", "shared", "idle", "failed")}
+    G, Rf = [], []
+    for acts, failed, cats in _scenarios(net, sc, rs):
+        dev = _launch(hip, eng, sp, acts, failed)
+        winners = {}
+        for s, a in enumerate(acts):
+            if a >= 0 and a not in winners.values():
+                winners[s] = a
+        for s in range(net.S):
+            rec = dev["upd"][s]
+            if s not in winners:       # idle, or a higher sensor on an object a lower one has: no record
+                assert rec[_lib.UPD_ACTION] == -1 and rec[_lib.UPD_OBS_TAKEN] == 0 and rec[_lib.UPD_VISIBLE] == 0, (tag, s, rec[:8])
+                seen["idle" if acts[s] < 0 else "shared"] += 1
+                continue
+            j = winners[s]
+            zn3 = zn[s, TIX, j].cpu().numpy()
+            if j in failed:            # an already failed filter is skipped: no record, the sentinel state as the oracle's
+                f = _oracle_one(oracle, net, sc, j, s, zn3, False, status=_lib.ST_PREDICT_NAN)
+                assert rec[_lib.UPD_ACTION] == -1 and rec[_lib.UPD_OBS_TAKEN] == 0 and rec[_lib.UPD_VISIBLE] == 0, (tag, s, rec[:8])
+                assert dev["st"][j] == _lib.ST_PREDICT_NAN and not f["obs_taken"]
+                assert np.array_equal(dev["x"][j], f["x"][0]) and np.array_equal(dev["P"][j], f["P"][0]), (tag, s, j)
+                seen["failed"] += 1
+                continue
+            f = _oracle_one(oracle, net, sc, j, s, zn3, False)
+            ld = _oracle_one(oracle_ld, net, sc, j, s, zn3, True)
+            assert dev["st"][j] == f["status"][0] == 0, (tag, s, j, dev["st"][j], f["status"])
+            g, r = check_update(net, sc, rec, dev, j, s, f, ld, oracle, tag)
+            G.append(g)
+            Rf.append(r)
+            c = cats[s]
+            if c == "north" and f["obs_taken"]:
+                az = f["sigmas_h"][:, 0] if net.obs_type == 'aer' else _az_of(oracle, net, s, f["sigmas_h"], sc.M)
+                c = "north" if (az < 0.5).any() and (az > 2 * np.pi - 0.5).any() else "visible"
+            elif c == "zenith":
+                c = "zenith" if sc.el[s, j] > NEAR_ZENITH else "visible"
+            elif c == "mask":
+                c = "mask" if BAND < abs(sc.el[s, j] - net.lim[s]) < 1e-9 else None
+            elif c == "hidden":
+                c = "hidden_seen_by_another" if not f["obs_taken"] and sc.seen[:, j].any() else None
+            elif c == "shared":
+                c = "visible" if f["obs_taken"] else None
+            if c == "visible" and not f["obs_taken"]:
+                c = None
+            if c:
+                seen[c] += 1
+        # every object no sensor updated: the prediction, within 1e-6 of the exact value
+        others = np.ones(sc.m, dtype=bool)
+        others[list(winners.values())] = False
+        others[list(failed)] = False
+        ep = np.linalg.norm((dev["x"] - pred_ld["x"])[others, :3], axis=1) / np.linalg.norm(pred_ld["x"][others, :3], axis=1)
+        ev = np.linalg.norm((dev["x"] - pred_ld["x"])[others, 3:], axis=1) / np.linalg.norm(pred_ld["x"][others, 3:], axis=1)
+        assert ep.max() < 1e-6 and ev.max() < 1e-6, (tag, ep.max(), ev.max())
+        assert np.all(dev["st"][others] == 0)
+    # the updated objects' x and P: as close to the exact value as the reference arithmetic is (factor 3, median and maximum)
+    G, Rf = np.array(G), np.array(Rf)
+    print("[sensor step vs oracle] %s: %s; vs exact (pos, vel, cov) gpu median %s max %s, reference median %s max %s"
+          % (tag, seen, np.median(G, 0), G.max(0), np.median(Rf, 0), Rf.max(0)))
+    assert all(v > 0 for v in seen.values()), (tag, seen)
+    for k, slack in ((0, 1e-12), (1, 1e-12), (2, 1e-9)):
+        assert np.median(G[:, k]) <= 3 * np.median(Rf[:, k]) + slack, (tag, k)
+        assert G[:, k].max() <= 3 * Rf[:, k].max() + slack, (tag, k)
+
+
+_PRED = {}
+
+
+def _predict_ld(oracle_ld, sc):
+    """the 80-bit oracle's predict-only step of the whole batch (one per batch)"""
+    if sc.m not in _PRED:
+        Wm, Wc, scale = orc.merwe_weights(ALPHA, 2.0, -3)
+        st = np.zeros(sc.m, dtype=np.int32)
+        _PRED[sc.m] = oracle_ld.env_step(sc.xt, sc.x, sc.P, st, DT, sc.g["Q"], sc.g["R"], Wm, Wc, scale, -1, sc.M, sc.g["obs_lla"],
+                                         sc.g["obs_itrs"], -np.pi / 2, np.zeros(3), centred=True)
+        assert np.all(st == 0)
+    return _PRED[sc.m]
+
+
+_SCENES = {}
+
+
+def _scene(oracle, oracle_ld, m):
+    if m not in _SCENES:
+        _SCENES[m] = Scene(oracle, oracle_ld, Net(oracle), m, seed=m % 1000 + 7)
+    return _SCENES[m]
+
+
+@pytest.mark.parametrize("m", [2000, 24003])
+@pytest.mark.parametrize("obs_type", ["aer", "xyz"])
+@pytest.mark.parametrize("propagator", ["fg", "hybrid"])
+def test_sensor_step_against_the_oracle(hip, oracle, oracle_ld, propagator, obs_type, m):
+    net = Net(oracle, obs_type)
+    sc = _scene(oracle, oracle_ld, m)
+    run_network_step(hip, oracle, oracle_ld, net, sc, propagator, _predict_ld(oracle_ld, sc), "%s %s m=%d" % (propagator, obs_type, m))
+
+
+# ------------------------------------------------------------------------------------------------ 3. the network lookahead against the oracle
+@pytest.mark.parametrize("m", [2000, 24003])
+def test_network_lookahead_against_the_oracle(hip, oracle, oracle_ld, m):
+    """x_prior and every sensor's P_post against ukf_predict + ukf_update from its site with its R (criteria of
+    tests/test_lookahead_gpu.py: test_against_the_oracle) on a sample of objects -- the constructed ones, the last tiles, the tiles
+    around 20 480 and random ones; visible[s] against the elevation of the propagated truth; the trace gains"""
+    import torch
+    from ssa_gym_amd import _lib, engine
+    net = Net(oracle)
+    sc = _scene(oracle, oracle_ld, m)
+    eng, _, sp = _engine(hip, net, sc, 'fg')
+    eng.status.zero_()
+    r = eng.launch_lookahead_sensors(0, TIX, sp, out=engine.HotPathEngine.LOOKAHEAD_PARTS)
+    torch.cuda.synchronize()
+    look = {k: v.cpu().numpy() for k, v in r.items()}
+    S = net.S
+    assert np.all(look["status"] == 0)
+    # visibility of every object from every site, identical to the reference's outside the band
+    for s in range(S):
+        judged = np.abs(sc.el[s] - net.lim[s]) > BAND
+        got = look["visible"][s].astype(bool)
+        assert np.array_equal(got[judged], sc.vis[s][judged]), (s, np.where(got[judged] != sc.vis[s][judged])[0][:8])
+    assert not look["visible"][7].any() and look["visible"][1].all()
+    rs = np.random.RandomState(m)
+    pick = np.r_[sc.zen, sc.north, sc.mask, np.arange(m - 8, m), rs.choice(m, 300, replace=False)]
+    if m > 20480:
+        pick = np.r_[pick, np.arange(20472, 20488)]
+    pick = np.unique(pick)
+    Wm, Wc, scale = orc.merwe_weights(ALPHA, 2.0, -3)
+    ref = {}
+    for name, o, centred in (("f64", oracle, False), ("ld", oracle_ld, True)):
+        xs, Pm, Pu = np.empty((len(pick), 6)), np.empty((len(pick), 6, 6)), np.empty((S, len(pick), 6, 6))
+        for k, j in enumerate(pick):
+            rc, xp, Pp, sf = o.ukf_predict(sc.x[j], sc.P[j], sc.g["Q"], DT, Wm, Wc, scale, centred=centred)
+            assert rc == 0
+            xs[k], Pm[k] = xp, Pp
+            for s in range(S):
+                if not look["visible"][s, j]:
+                    Pu[s, k] = Pp
+                    continue
+                rc2, _, P2, _, _, _ = o.ukf_update(xp, Pp, sf, np.zeros(3), net.R[s], Wm, Wc, scale, sc.M, net.lla[s], net.itrs[s],
+                                                   obs_type=0, centred=centred)
+                assert rc2 == 0
+                Pu[s, k] = P2
+        ref[name] = dict(x=xs, Pm=Pm, Pu=Pu)
+    f, ld = ref["f64"], ref["ld"]
+    xg = look["x_prior"][pick]
+    ep, ev, _ = errs({"x": xg, "P": f["Pm"]}, {"x": f["x"], "P": f["Pm"]})
+    rp, rv, _ = errs({"x": f["x"], "P": f["Pm"]}, {"x": ld["x"], "P": ld["Pm"]})
+    well = (rp < 0.5e-6) & (rv < 0.5e-6)
+    assert well.mean() >= 0.99 and (ep[well] < 1e-6).all() and (ev[well] < 1e-6).all()
+    n_upd = 0
+    for s in range(S):
+        gp, gv, gP = errs({"x": xg, "P": look["P_post"][s][pick]}, {"x": ld["x"], "P": ld["Pu"][s]})
+        rp, rv, rP = errs({"x": f["x"], "P": f["Pu"][s]}, {"x": ld["x"], "P": ld["Pu"][s]})
+        for g_, r_ in ((gp, rp), (gv, rv), (gP, rP)):
+            assert np.median(g_) <= 3 * np.median(r_) + 1e-13, s
+            assert g_.max() <= 3 * r_.max() + 1e-12, s
+        # trace and position-trace gains against the 80-bit covariances, where the update runs
+        upd = look["visible"][s][pick].astype(bool)
+        n_upd += int(upd.sum())
+        sc_s = look["score"][s][pick]
+        trm = np.trace(ld["Pm"], axis1=1, axis2=2)
+        tr = trm - np.trace(ld["Pu"][s], axis1=1, axis2=2)
+        trp = np.trace(ld["Pm"][:, :3, :3], axis1=1, axis2=2) - np.trace(ld["Pu"][s][:, :3, :3], axis1=1, axis2=2)
+        # (1e-9 tr(P-), or 3x the reference arithmetic's own distance where its P+ is not defined that well: near the zenith)
+        ftr = np.trace(f["Pm"], axis1=1, axis2=2) - np.trace(f["Pu"][s], axis1=1, axis2=2)
+        ftrp = np.trace(f["Pm"][:, :3, :3], axis1=1, axis2=2) - np.trace(f["Pu"][s][:, :3, :3], axis1=1, axis2=2)
+        for col, want, ref_ in ((_lib.LOOK_TRACE_GAIN, tr, ftr), (_lib.LOOK_POS_TRACE_GAIN, trp, ftrp)):
+            e_dev, e_ref = np.abs(sc_s[upd, col] - want[upd]), np.abs(ref_[upd] - want[upd])
+            bad = e_dev > 1e-9 * trm[upd] + 3 * e_ref
+            assert not bad.any(), (s, col, pick[upd][bad], e_dev[bad], e_ref[bad], trm[upd][bad])
+        assert np.isnan(sc_s[~upd]).all(), s
+    print("[network lookahead vs oracle] m=%d: %d objects, %d (sensor, object) updates, visible per sensor %s"
+          % (m, len(pick), n_upd, look["visible"].sum(axis=1).tolist()))
+    assert n_upd > 0
+
+
+# ------------------------------------------------------------------------------------------------------------------- 4. the env end to end
+ENV_SITES = [0, 1, 4, 3]                                    # default observer, south-east, far north, antimeridian
+ENV_MASKS = [15.0, 5.0, 10.0, 20.0]                         # [deg]
+ENV_SIGMAS = [(1.0, 2.0, 1e3), (3.0, 1.5, 500.0), (0.8, 4.0, 2e3), (2.0, 2.5, 800.0)]   # ([arcsec], [arcsec], [m])
+
+
+def test_env_steps_against_the_oracle(hip, oracle, oracle_ld):
+    """an env with four sensors, its config in degrees and arcseconds: 20 steps, every sensor's update against the oracle's step of that
+    object from history slot i - 1 with the env's own noise draw z_noise[s, i, a[s]] -- the radians, masks and R computed here"""
+    from ssa_gym_amd import envs as E
+    cfg = dict(E.env_config)
+    cfg.update(rso_count=2000, steps=480, reward_type='trinary', obs_returned='flatten', seed=11, alpha=ALPHA,
+               observers=[SITES8[k] for k in ENV_SITES], sensor_obs_limit=ENV_MASKS, sensor_z_sigma=ENV_SIGMAS)
+    env = E.make('ssa_tasker_simple-v2', config=cfg)
+    lla = [np.array([np.radians(SITES8[k][0]), np.radians(SITES8[k][1]), SITES8[k][2]]) for k in ENV_SITES]
+    itrs = [oracle.lla2ecef(s) for s in lla]
+    lim = np.radians(ENV_MASKS)
+    R = [np.diag((np.array(z) * [ARCSEC, ARCSEC, 1.0]) ** 2) for z in ENV_SIGMAS]
+    Wm, Wc, scale = orc.merwe_weights(ALPHA, cfg['beta'], cfg['kappa'])
+    rs = np.random.RandomState(5)
+    S, m = len(lla), env.m
+    G, Rf, taken = [], [], 0
+    for i in range(1, 21):
+        xt0, x0, P0 = env.x_true[i - 1], env.x_filter[i - 1], env.P_filter[i - 1]
+        M = env.trans_matrix[i]
+        xt1 = oracle.propagate(xt0, env.dt)
+        acts, used = [], set()
+        for s in range(S):
+            vis = np.where(_aer(oracle, xt1, lla[s], itrs[s], M)[:, 1] > lim[s] + 1e-6)[0]
+            vis = [j for j in vis if j not in used and j not in env.failed_filters_id]
+            j = int(rs.choice(vis)) if vis else int(rs.choice([j for j in range(m) if j not in used]))
+            used.add(j)
+            acts.append(j)
+        env.step(np.array(acts))
+        xf, Pf = env.x_filter[i], env.P_filter[i]
+        for s, a in enumerate(acts):
+            one = dict(x_true=xt0[a:a + 1], x=x0[a:a + 1], P=P0[a:a + 1])
+            zn3 = env.z_noise[s, i, a]
+            res = {}
+            for name, o, centred in (("f64", oracle, False), ("ld", oracle_ld, True)):
+                st = np.zeros(1, dtype=np.int32)
+                res[name] = o.env_step(one["x_true"], one["x"], one["P"], st, env.dt, env.Q, R[s], Wm, Wc, scale, 0, M, lla[s], itrs[s],
+                                       lim[s], zn3, obs_type=0, centred=centred)
+            f, ld = res["f64"], res["ld"]
+            assert bool(env.obs_taken[i, s]) == f["obs_taken"], (i, s, a)
+            zt, zf = env.z_true[i, s], f["z_true"]
+            dx = np.linalg.norm(env.x_true[i][a, :3] - f["x_true"][0, :3]) + 4 * EPS * np.linalg.norm(f["x_true"][0, :3])
+            assert abs(_wrap(zt[0] - zf[0])) <= 1e-12 + 2 * dx / (zf[2] * np.cos(zf[1])) and abs(zt[1] - zf[1]) <= 1e-12 and abs(zt[2] - zf[2]) <= 1e-12 * zf[2], (i, s, zt, zf)
+            if f["obs_taken"]:
+                taken += 1
+                Sd = np.sqrt(np.diag(ld["S"]))
+                assert np.max(np.abs(env.y[i, s] - ld["y"]) / Sd) < 1e-3, (i, s, a, env.y[i, s], ld["y"])
+                assert np.max(np.abs(env.S[i, s, a] - ld["S"]) / np.outer(Sd, Sd)) < 1e-2, (i, s, a)
+                np.testing.assert_allclose(env.sigmas_h[i, s][:, 1:], f["sigmas_h"][:, 1:], rtol=1e-12, atol=1e-7)
+                assert np.all(np.abs(_wrap(env.sigmas_h[i, s][:, 0] - f["sigmas_h"][:, 0])) <= 1e-7)
+            g = errs({"x": xf[a:a + 1], "P": Pf[a:a + 1]}, ld)
+            r = errs(f, ld)
+            assert g[0][0] < 1e-5 and g[1][0] < 1e-5, (i, s, a, g)
+            G.append(np.array(g)[:, 0])
+            Rf.append(np.array(r)[:, 0])
+    G, Rf = np.array(G), np.array(Rf)
+    print("[env vs oracle] 20 steps x %d sensors, %d updates; vs exact (pos, vel, cov) gpu median %s max %s, reference median %s max %s"
+          % (S, taken, np.median(G, 0), G.max(0), np.median(Rf, 0), Rf.max(0)))
+    assert taken >= 20 * S // 2
+    for k, slack in ((0, 1e-12), (1, 1e-12), (2, 1e-9)):
+        assert np.median(G[:, k]) <= 3 * np.median(Rf[:, k]) + slack, k
+        assert G[:, k].max() <= 3 * Rf[:, k].max() + slack, k
