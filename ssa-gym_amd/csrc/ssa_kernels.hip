@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/ssa_hip.h"
 #include "ssa_math.hpp"
@@ -1915,253 +1916,134 @@ SSA_DEV int xcd_tile(int b, int n)
     return x * q + (x < r ? x : r) + i;
 }
 
-// Grid-stride over tiles: wavefront w advances tiles w, w + G, w + 2G, ... (G = gridDim.x, chosen by the
-// launcher so that every wavefront is resident at once and all get the same number of tiles) with the
-// next tile's loads issued while the current one is being worked on.
+// The tile walk of the four tile kernels: step_fast_kernel (ActEarly), step_sensors_kernel (ActSensors), lookahead_kernel (ActAll)
+// and lookahead_sensors_kernel (ActLookSensors).  MULTI = false is the one-tile-per-wavefront instance (every launch up to
+// 20 480 objects): no loop, no staging registers.  MULTI = true is the grid-stride walk: wavefront w advances tiles w, w + G,
+// w + 2G, ... (G = nwork, chosen by the launcher so that every wavefront is resident at once and all get the same number of
+// tiles) with the next tile's loads issued while the current one is being worked on.
 //
-// MULTI = false is the one-tile-per-wavefront instance (every launch up to 20 480 objects): no loop, no staging
-// registers.
-typedef const __attribute__((address_space(4))) StepK* KernargPtr;
-// The kernarg segment of step_fast_kernel as a struct: kernel arguments are laid out in declaration order at their natural
-// alignment, exactly as the members of this mirror are (tests/test_abi_and_host.py parses the shipped code object's metadata
-// and checks the offset of the by-value block against it).
-struct StepFastArgs {
+// Each kernel carries one argument block K behind six scalar arguments.  TileArgs<K> is its kernarg segment as a struct: kernel
+// arguments are laid out in declaration order at their natural alignment, exactly as the members of this mirror are
+// (tests/test_abi_and_host.py parses the shipped code object's metadata and checks the offset of the by-value block against it).
+// The leading arguments -- the two tile counts and the pointers k.p.{P_in, x_in, x_true_in, status} repeated -- are plain
+// scalars: they are PRELOADED into SGPRs at wavefront launch (-amdgpu-kernarg-preload-count, _build.py), so the tile's loads --
+// the first link of every wavefront's dependency chain -- leave without waiting for a scalar-memory round trip to the segment.
+template <class K> struct TileArgs {
     int ntiles, nwork;
     const double *pre_P_in, *pre_x_in, *pre_x_true_in;
     const int32_t* pre_status;
-    StepK k;
+    K k;
 };
-// The leading arguments -- the two tile counts and the pointers k_arg.p.{P_in, x_in, x_true_in, status} repeated -- are plain
-// scalars: they are PRELOADED into SGPRs at wavefront launch (-amdgpu-kernarg-preload-count, _build.py), so the tile's loads -- the first link
-// of every wavefront's dependency chain -- leave without waiting for a scalar-memory round trip to the kernarg segment.
-template <int PROP, bool MULTI>
-__global__ void __launch_bounds__(64, SSA_STEP_WAVES) step_fast_kernel(int ntiles, int nwork, const double* pre_P_in,
-                                                                       const double* pre_x_in, const double* pre_x_true_in,
-                                                                       const int32_t* pre_status, const StepK k_arg)
-{
-    __shared__ Tiles t;
-    int lane = threadIdx.x;
-    const int unit = (int)blockIdx.x;
-    if (unit >= nwork) {   // deferred fold of the previous step's statistics: one extra wavefront per env
-        fold_stat_shards((unsigned long long*)k_arg.p.stat_shards_prev, k_arg.p.stats_prev, unit - nwork, lane,
-                         (const unsigned long long*)k_arg.p.spos_tiles_prev, k_arg.p.n_obj);
-        return;
-    }
-    const int64_t total = (int64_t)k_arg.p.n_env * k_arg.p.n_obj;
-    TileRegs pf;
-    int tile = xcd_tile(unit, nwork);
-    if (!MULTI) {
-        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
-        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
-        tile_dma_issue(t, pf, pre_P_in, pre_x_in, pre_x_true_in, pre_status, lane, base, cnt);
-        ActEarly early;
-        process_wave<PROP, 0>(t, k_arg.c, k_arg.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, early);
-        return;
-    }
-    {
-        const int64_t b0 = (int64_t)tile * OBJ_PER_WAVE;
-        tile_issue(pf, k_arg.p, lane, b0, tile < ntiles ? (int)((total - b0) < OBJ_PER_WAVE ? (total - b0) : OBJ_PER_WAVE) : 0);
-    }
-    KernargPtr kp = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    unsigned wave_slot, turn = 0;   // issue priority rotated per tile: see rollout_kernel
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(wave_slot));
-    for (; tile < ntiles; tile += nwork) {
-        switch ((wave_slot + turn++) & 3u) {
-            case 0: __builtin_amdgcn_s_setprio(0); break;
-            case 1: __builtin_amdgcn_s_setprio(1); break;
-            case 2: __builtin_amdgcn_s_setprio(2); break;
-            default: __builtin_amdgcn_s_setprio(3); break;
-        }
-        // the body must compile like a one-tile kernel: re-derive the argument block and the lane id per
-        // tile, so that the ~100 argument scalars and the lane-derived LDS addresses are produced on demand
-        // instead of being carried around the loop in registers
-        asm volatile("" : "+s"(kp));
-        asm volatile("" : "+v"(lane));
-        const StepK& k = *(const StepK*)((const char*)kp + offsetof(StepFastArgs, k));   // behind the preloaded scalar arguments
-        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
-        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
-        const int nt = tile + nwork;
-        const int64_t nbase = (int64_t)nt * OBJ_PER_WAVE;
-        const int ncnt = nt < ntiles ? (int)((total - nbase) < OBJ_PER_WAVE ? (total - nbase) : OBJ_PER_WAVE) : 0;
-        ActEarly early;
-        process_wave<PROP, 1>(t, k.c, k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, nbase, ncnt, tile, early);
-        wave_lds_sync();   // the tile's LDS reads (store) precede the next tile's commit
-    }
-}
-
-// The lookahead (ssa_lookahead_f64): the step kernel's launch forms with ActAll.  Same tiles, same predict and update code; the
-// outputs are the lookahead's, at the caller's rows.
+template <class K> using KernargPtr = const __attribute__((address_space(4))) K*;
+// The argument blocks: the step's own (StepK); the lookahead's outputs, at the caller's rows, behind it (LookK); a sensor
+// network's sites behind the step's (SensK) or the lookahead's (LookSensK) block.
 struct LookK {
     StepK k;
     ssa_lookahead_out o;
 };
-struct LookaheadArgs {   // the kernarg segment of lookahead_kernel (see StepFastArgs)
-    int ntiles, nwork;
-    const double *pre_P_in, *pre_x_in, *pre_x_true_in;
-    const int32_t* pre_status;
-    LookK k;
-};
-typedef const __attribute__((address_space(4))) LookK* LookKernargPtr;
-template <int PROP, bool MULTI>
-__global__ void __launch_bounds__(64, SSA_STEP_WAVES) lookahead_kernel(int ntiles, int nwork, const double* pre_P_in,
-                                                                       const double* pre_x_in, const double* pre_x_true_in,
-                                                                       const int32_t* pre_status, const LookK k_arg)
-{
-    __shared__ Tiles t;
-    int lane = threadIdx.x;
-    const int unit = (int)blockIdx.x;
-    const int64_t total = (int64_t)k_arg.k.p.n_env * k_arg.k.p.n_obj;
-    TileRegs pf;
-    int tile = xcd_tile(unit, nwork);
-    if (!MULTI) {
-        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
-        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
-        tile_dma_issue(t, pf, pre_P_in, pre_x_in, pre_x_true_in, pre_status, lane, base, cnt);
-        ActAll all{&k_arg.o};
-        process_wave<PROP, 0>(t, k_arg.k.c, k_arg.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, all);
-        return;
-    }
-    {
-        const int64_t b0 = (int64_t)tile * OBJ_PER_WAVE;
-        tile_issue(pf, k_arg.k.p, lane, b0, tile < ntiles ? (int)((total - b0) < OBJ_PER_WAVE ? (total - b0) : OBJ_PER_WAVE) : 0);
-    }
-    LookKernargPtr kp = (LookKernargPtr)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(LookaheadArgs, k));
-    for (; tile < ntiles; tile += nwork) {
-        // (as step_fast_kernel: the argument block and the lane id re-derived per tile)
-        asm volatile("" : "+s"(kp));
-        asm volatile("" : "+v"(lane));
-        const LookK& k = *(const LookK*)kp;
-        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
-        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
-        const int nt = tile + nwork;
-        const int64_t nbase = (int64_t)nt * OBJ_PER_WAVE;
-        const int ncnt = nt < ntiles ? (int)((total - nbase) < OBJ_PER_WAVE ? (total - nbase) : OBJ_PER_WAVE) : 0;
-        ActAll all{&k.o};
-        process_wave<PROP, 1>(t, k.k.c, k.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, nbase, ncnt, tile, all);
-        wave_lds_sync();   // the tile's LDS reads precede the next tile's commit
-    }
-}
-
-// The lookahead of a sensor network (ssa_lookahead_sensors_f64): lookahead_kernel's launch forms with ActLookSensors; the sensors'
-// block travels behind the lookahead's in the argument segment.
-struct LookSensK {
-    LookK k;
-    ssa_sensor_params s;
-};
-struct LookaheadSensorsArgs {   // the kernarg segment of lookahead_sensors_kernel (see StepFastArgs)
-    int ntiles, nwork;
-    const double *pre_P_in, *pre_x_in, *pre_x_true_in;
-    const int32_t* pre_status;
-    LookSensK k;
-};
-typedef const __attribute__((address_space(4))) LookSensK* LookSensKernargPtr;
-template <int PROP, bool MULTI>
-__global__ void __launch_bounds__(64, SSA_STEP_WAVES) lookahead_sensors_kernel(int ntiles, int nwork, const double* pre_P_in,
-                                                                               const double* pre_x_in, const double* pre_x_true_in,
-                                                                               const int32_t* pre_status, const LookSensK k_arg)
-{
-    __shared__ Tiles t;
-    int lane = threadIdx.x;
-    const int unit = (int)blockIdx.x;
-    const int64_t total = k_arg.k.k.p.n_obj;   // (one env)
-    TileRegs pf;
-    int tile = xcd_tile(unit, nwork);
-    if (!MULTI) {
-        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
-        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
-        tile_dma_issue(t, pf, pre_P_in, pre_x_in, pre_x_true_in, pre_status, lane, base, cnt);
-        // (the outputs' and the sites' block by the argument segment's address, not the argument's: kernarg_opaque takes them)
-        const LookSensK& ka = *(const LookSensK*)(LookSensKernargPtr)((const char*)__builtin_amdgcn_kernarg_segment_ptr() +
-                                                                      offsetof(LookaheadSensorsArgs, k));
-        ActLookSensors look{&ka.k.o, &ka.s};
-        process_wave<PROP, 0>(t, k_arg.k.k.c, k_arg.k.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, look);
-        return;
-    }
-    {
-        const int64_t b0 = (int64_t)tile * OBJ_PER_WAVE;
-        tile_issue(pf, k_arg.k.k.p, lane, b0, tile < ntiles ? (int)((total - b0) < OBJ_PER_WAVE ? (total - b0) : OBJ_PER_WAVE) : 0);
-    }
-    LookSensKernargPtr kp = (LookSensKernargPtr)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(LookaheadSensorsArgs, k));
-    for (; tile < ntiles; tile += nwork) {
-        // (as step_fast_kernel: the argument block and the lane id re-derived per tile)
-        asm volatile("" : "+s"(kp));
-        asm volatile("" : "+v"(lane));
-        const LookSensK& k = *(const LookSensK*)kp;
-        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
-        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
-        const int nt = tile + nwork;
-        const int64_t nbase = (int64_t)nt * OBJ_PER_WAVE;
-        const int ncnt = nt < ntiles ? (int)((total - nbase) < OBJ_PER_WAVE ? (total - nbase) : OBJ_PER_WAVE) : 0;
-        ActLookSensors look{&k.k.o, &k.s};
-        process_wave<PROP, 1>(t, k.k.k.c, k.k.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, nbase, ncnt, tile, look);
-        wave_lds_sync();   // the tile's LDS reads precede the next tile's commit
-    }
-}
-
-// A sensor network's step (ssa_env_step_sensors_f64): step_fast_kernel's launch forms with ActSensors -- the deferred fold's extra
-// wavefronts and the issue-priority rotation included; the sensors' block travels behind the step's in the argument segment.
 struct SensK {
     StepK k;
     ssa_sensor_params s;
 };
-struct StepSensorsArgs {   // the kernarg segment of step_sensors_kernel (see StepFastArgs)
-    int ntiles, nwork;
-    const double *pre_P_in, *pre_x_in, *pre_x_true_in;
-    const int32_t* pre_status;
-    SensK k;
+struct LookSensK {
+    LookK k;
+    ssa_sensor_params s;
 };
-typedef const __attribute__((address_space(4))) SensK* SensKernargPtr;
-template <int PROP, bool MULTI>
-__global__ void __launch_bounds__(64, SSA_STEP_WAVES) step_sensors_kernel(int ntiles, int nwork, const double* pre_P_in,
-                                                                          const double* pre_x_in, const double* pre_x_true_in,
-                                                                          const int32_t* pre_status, const SensK k_arg)
-{
-    __shared__ Tiles t;
-    int lane = threadIdx.x;
-    const int unit = (int)blockIdx.x;
-    if (unit >= nwork) {   // deferred fold of the previous step's statistics (one env: one extra wavefront)
-        fold_stat_shards((unsigned long long*)k_arg.k.p.stat_shards_prev, k_arg.k.p.stats_prev, unit - nwork, lane,
-                         (const unsigned long long*)k_arg.k.p.spos_tiles_prev, k_arg.k.p.n_obj);
-        return;
+// what a block hands process_wave: the step's constants and parameters, and the ACT policy (its pointers into the block)
+SSA_DEV const StepK& step_of(const StepK& k) { return k; }
+SSA_DEV const StepK& step_of(const LookK& k) { return k.k; }
+SSA_DEV const StepK& step_of(const SensK& k) { return k.k; }
+SSA_DEV const StepK& step_of(const LookSensK& k) { return k.k.k; }
+SSA_DEV ActEarly act_of(const StepK&) { return ActEarly(); }
+SSA_DEV ActAll act_of(const LookK& k) { return ActAll{&k.o}; }
+SSA_DEV ActSensors act_of(const SensK& k) { return ActSensors{&k.s}; }
+SSA_DEV ActLookSensors act_of(const LookSensK& k) { return ActLookSensors{&k.k.o, &k.s}; }
+// WALK: what sets the four kernels apart
+enum : unsigned {
+    WALK_STEP = 1,          // a step: the deferred fold of the previous step's statistics in the extra wavefronts (unit >= nwork, one
+                            // per env) and the issue priority rotated per tile (see rollout_kernel)
+    WALK_ONE_ENV = 2,       // a sensor network: one env, n_obj objects
+    WALK_ACT_SEGMENT = 4,   // the one-tile instance takes the ACT's pointers by the argument segment's address, not the argument's:
+                            // kernarg_opaque (process_wave) needs a pointer into the segment
+    WALK_BASE_PER_TILE = 8  // the grid-stride loop carries the segment's base and adds the block's offset per tile (step_fast_kernel),
+                            // not the block's address formed once in front of the loop
+};
+// One tile kernel: NAME<PROP, MULTI>(ntiles, nwork, pre_P_in, pre_x_in, pre_x_true_in, pre_status, const K k_arg).
+// The walk is written out once, here, but expands into the body of each kernel rather than living in a device function they call:
+// process_wave has to be inlined straight into the kernel.  Behind a device function its body is optimised once more, on its own
+// and without the kernel's launch bounds, before it reaches the kernel -- which reorders the step kernel's instructions (and
+// promotes one of its private arrays that the kernel itself leaves to the code generator).
+// In the grid-stride loop the body must compile like a one-tile kernel: the argument block and the lane id are re-derived per
+// tile (the empty asm statements), so that the ~100 argument scalars and the lane-derived LDS addresses are produced on demand
+// instead of being carried around the loop in registers.  The block lies behind the preloaded scalar arguments (TileArgs).
+// wave_lds_sync() between tiles: the tile's LDS reads (its stores) precede the next tile's commit.
+#define SSA_TILE_KERNEL(NAME, K, WALK)                                                                                                        \
+    template <int PROP, bool MULTI>                                                                                                           \
+    __global__ void __launch_bounds__(64, SSA_STEP_WAVES) NAME(int ntiles, int nwork, const double* pre_P_in, const double* pre_x_in,         \
+                                                               const double* pre_x_true_in, const int32_t* pre_status, const K k_arg)         \
+    {                                                                                                                                         \
+        __shared__ Tiles t;                                                                                                                   \
+        int lane = threadIdx.x;                                                                                                               \
+        const int unit = (int)blockIdx.x;                                                                                                     \
+        if (((WALK) & WALK_STEP) && unit >= nwork) {                                                                                          \
+            const ssa_step_params& p = step_of(k_arg).p;                                                                                      \
+            fold_stat_shards((unsigned long long*)p.stat_shards_prev, p.stats_prev, unit - nwork, lane,                                       \
+                             (const unsigned long long*)p.spos_tiles_prev, p.n_obj);                                                          \
+            return;                                                                                                                           \
+        }                                                                                                                                     \
+        const int64_t total = ((WALK) & WALK_ONE_ENV) ? step_of(k_arg).p.n_obj : (int64_t)step_of(k_arg).p.n_env * step_of(k_arg).p.n_obj;    \
+        TileRegs pf;                                                                                                                          \
+        int tile = xcd_tile(unit, nwork);                                                                                                     \
+        if (!MULTI) {                                                                                                                         \
+            const int64_t base = (int64_t)tile * OBJ_PER_WAVE;                                                                                \
+            const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);                                             \
+            tile_dma_issue(t, pf, pre_P_in, pre_x_in, pre_x_true_in, pre_status, lane, base, cnt);                                            \
+            const K& ka = ((WALK) & WALK_ACT_SEGMENT)                                                                                         \
+                              ? *(const K*)(KernargPtr<K>)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(TileArgs<K>, k))    \
+                              : k_arg;                                                                                                        \
+            auto act = act_of(ka);                                                                                                            \
+            process_wave<PROP, 0>(t, step_of(k_arg).c, step_of(k_arg).p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0,    \
+                                  tile, act);                                                                                                 \
+            return;                                                                                                                           \
+        }                                                                                                                                     \
+        {                                                                                                                                     \
+            const int64_t b0 = (int64_t)tile * OBJ_PER_WAVE;                                                                                  \
+            tile_issue(pf, step_of(k_arg).p, lane, b0, tile < ntiles ? (int)((total - b0) < OBJ_PER_WAVE ? (total - b0) : OBJ_PER_WAVE) : 0); \
+        }                                                                                                                                     \
+        constexpr size_t pre_off = ((WALK) & WALK_BASE_PER_TILE) ? 0 : offsetof(TileArgs<K>, k);                                              \
+        KernargPtr<K> kp = (KernargPtr<K>)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + pre_off);                                    \
+        unsigned wave_slot, turn = 0;                                                                                                         \
+        if ((WALK) & WALK_STEP) asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(wave_slot));                                 \
+        for (; tile < ntiles; tile += nwork) {                                                                                                \
+            if ((WALK) & WALK_STEP) {                                                                                                         \
+                switch ((wave_slot + turn++) & 3u) {                                                                                          \
+                    case 0: __builtin_amdgcn_s_setprio(0); break;                                                                             \
+                    case 1: __builtin_amdgcn_s_setprio(1); break;                                                                             \
+                    case 2: __builtin_amdgcn_s_setprio(2); break;                                                                             \
+                    default: __builtin_amdgcn_s_setprio(3); break;                                                                            \
+                }                                                                                                                             \
+            }                                                                                                                                 \
+            asm volatile("" : "+s"(kp));                                                                                                      \
+            asm volatile("" : "+v"(lane));                                                                                                    \
+            const K& k = *(const K*)((const char*)kp + (offsetof(TileArgs<K>, k) - pre_off));                                                 \
+            const int64_t base = (int64_t)tile * OBJ_PER_WAVE;                                                                                \
+            const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);                                             \
+            const int nt = tile + nwork;                                                                                                      \
+            const int64_t nbase = (int64_t)nt * OBJ_PER_WAVE;                                                                                 \
+            const int ncnt = nt < ntiles ? (int)((total - nbase) < OBJ_PER_WAVE ? (total - nbase) : OBJ_PER_WAVE) : 0;                        \
+            auto act = act_of(k);                                                                                                             \
+            process_wave<PROP, 1>(t, step_of(k).c, step_of(k).p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, nbase, ncnt,     \
+                                  tile, act);                                                                                                 \
+            wave_lds_sync();                                                                                                                  \
+        }                                                                                                                                     \
     }
-    const int64_t total = k_arg.k.p.n_obj;
-    TileRegs pf;
-    int tile = xcd_tile(unit, nwork);
-    if (!MULTI) {
-        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
-        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
-        tile_dma_issue(t, pf, pre_P_in, pre_x_in, pre_x_true_in, pre_status, lane, base, cnt);
-        ActSensors sens{&k_arg.s};
-        process_wave<PROP, 0>(t, k_arg.k.c, k_arg.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, sens);
-        return;
-    }
-    {
-        const int64_t b0 = (int64_t)tile * OBJ_PER_WAVE;
-        tile_issue(pf, k_arg.k.p, lane, b0, tile < ntiles ? (int)((total - b0) < OBJ_PER_WAVE ? (total - b0) : OBJ_PER_WAVE) : 0);
-    }
-    SensKernargPtr kp = (SensKernargPtr)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(StepSensorsArgs, k));
-    unsigned wave_slot, turn = 0;   // issue priority rotated per tile, as step_fast_kernel
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(wave_slot));
-    for (; tile < ntiles; tile += nwork) {
-        switch ((wave_slot + turn++) & 3u) {
-            case 0: __builtin_amdgcn_s_setprio(0); break;
-            case 1: __builtin_amdgcn_s_setprio(1); break;
-            case 2: __builtin_amdgcn_s_setprio(2); break;
-            default: __builtin_amdgcn_s_setprio(3); break;
-        }
-        asm volatile("" : "+s"(kp));
-        asm volatile("" : "+v"(lane));
-        const SensK& k = *(const SensK*)kp;
-        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
-        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
-        const int nt = tile + nwork;
-        const int64_t nbase = (int64_t)nt * OBJ_PER_WAVE;
-        const int ncnt = nt < ntiles ? (int)((total - nbase) < OBJ_PER_WAVE ? (total - nbase) : OBJ_PER_WAVE) : 0;
-        ActSensors sens{&k.s};
-        process_wave<PROP, 1>(t, k.k.c, k.k.p, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, nbase, ncnt, tile, sens);
-        wave_lds_sync();   // the tile's LDS reads (store) precede the next tile's commit
-    }
-}
+
+// The kernels' names are what the profiles, the host tests and bench.py's roofline find them by.
+SSA_TILE_KERNEL(step_fast_kernel, StepK, WALK_STEP | WALK_BASE_PER_TILE)                   // a step (ssa_env_step_f64)
+SSA_TILE_KERNEL(lookahead_kernel, LookK, 0)                                                // the lookahead (ssa_lookahead_f64)
+SSA_TILE_KERNEL(lookahead_sensors_kernel, LookSensK, WALK_ONE_ENV | WALK_ACT_SEGMENT)      // a sensor network's lookahead
+SSA_TILE_KERNEL(step_sensors_kernel, SensK, WALK_STEP | WALK_ONE_ENV)                      // a sensor network's step
+#undef SSA_TILE_KERNEL
 
 // Rollout: K consecutive env steps of the same objects in ONE launch.  An object's trajectory depends on no other
 // object (the single update per step touches only the selected one; the statistics are reductions), so a wavefront
@@ -2211,7 +2093,7 @@ __global__ void __launch_bounds__(64, SSA_STEP_WAVES) rollout_kernel(const RollK
                 case 2: __builtin_amdgcn_s_setprio(2); break;
                 default: __builtin_amdgcn_s_setprio(3); break;
             }
-            asm volatile("" : "+s"(kp));      // per step, as per tile in step_fast_kernel: nothing carried around the loop
+            asm volatile("" : "+s"(kp));      // per step, as per tile in the tile kernels: nothing carried around the loop
             asm volatile("" : "+v"(lane));
             const StepK& k = ((const RollK*)kp)->k;
             const ssa_rollout_params& r = ((const RollK*)kp)->r;
@@ -3547,6 +3429,23 @@ __global__ void __launch_bounds__(64) peer_wait_kernel(const unsigned long long*
 // ============================================================================= C ABI
 using namespace ssa;
 
+// f(std::integral_constant<int, P>()) for the propagator `prop` (checked by consts_ok): the kernels' PROP template argument
+template <class F> static void with_prop(int prop, F&& f)
+{
+    if (prop == SSA_PROP_FG) f(std::integral_constant<int, SSA_PROP_FG>());
+    else if (prop == SSA_PROP_ELEMENTS) f(std::integral_constant<int, SSA_PROP_ELEMENTS>());
+    else if (prop == SSA_PROP_HYBRID) f(std::integral_constant<int, SSA_PROP_HYBRID>());
+    else f(std::integral_constant<int, SSA_PROP_J2_RK4>());
+}
+// ... and the tile kernels' MULTI: f(P, std::bool_constant<multi>())
+template <class F> static void with_prop(int prop, bool multi, F&& f)
+{
+    with_prop(prop, [&](auto P) {
+        if (multi) f(P, std::true_type());
+        else f(P, std::false_type());
+    });
+}
+
 extern "C" {
 
 int ssa_abi_version(void) { return SSA_ABI_VERSION; }
@@ -3569,6 +3468,31 @@ static int post_parts(int64_t n_obj, int32_t n_env)
     if (want < 1) want = 1;
     if (want > 256) want = 256;
     return (int)want;
+}
+// the checks of ssa_consts every fused launch shares: observation model, propagator, RK4 substeps
+static bool consts_ok(const ssa_consts* c)
+{
+    if (c->obs_type != SSA_OBS_AER && c->obs_type != SSA_OBS_XYZ) return false;
+    if (c->propagator != SSA_PROP_FG && c->propagator != SSA_PROP_ELEMENTS && c->propagator != SSA_PROP_J2_RK4 && c->propagator != SSA_PROP_HYBRID) return false;
+    return c->propagator != SSA_PROP_J2_RK4 || (c->rk4_substeps >= 1 && c->rk4_substeps <= 4096);
+}
+// the tile kernels' grid: tiles per wavefront T = ceil(tiles / resident wavefront slots); G = ceil(tiles / T) wavefronts.  T = 1:
+// the one-tile instance, else the grid-stride walk.
+static void tile_grid(int64_t total, int64_t& ntiles, int& nwork, int64_t& per_wave)
+{
+    ntiles = (total + OBJ_PER_WAVE - 1) / OBJ_PER_WAVE;
+    const int64_t slots = (int64_t)device_cu_count() * 4 * SSA_STEP_WAVES;
+    per_wave = (ntiles + slots - 1) / slots;
+    nwork = (int)((ntiles + per_wave - 1) / per_wave);
+}
+// the checks of a sensor network's sites that its step and its lookahead share; SSA_OK or the refusal
+static int sensors_ok(const ssa_sensor_params* sp, const ssa_step_params* p)
+{
+    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
+    if (p->n_env != 1) return SSA_E_UNSUPPORTED;
+    for (int k = 0; k < sp->n_sensor; ++k)
+        if (!(sp->obs_limit[k] == sp->obs_limit[k])) return SSA_E_INVALID;
+    return SSA_OK;
 }
 
 // sens: a sensor network's step (ssa_env_step_sensors_f64; checked by the caller) -- step_sensors_kernel instead of step_fast_kernel
@@ -3594,18 +3518,16 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     // indices within the env, whole tiles per env)
     if (p->obj_ids && (!p->stat_shards || (p->n_env != 1 && (p->n_obj % OBJ_PER_WAVE) != 0))) return SSA_E_UNSUPPORTED;
     if ((p->spos_tiles || p->spos_tiles_prev) && p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // whole tiles per env
-    if (c->obs_type != SSA_OBS_AER && c->obs_type != SSA_OBS_XYZ) return SSA_E_INVALID;
+    if (!consts_ok(c)) return SSA_E_INVALID;
     if (p->aer_cols != 0 && p->aer_cols != 1 && p->aer_cols != 4) return SSA_E_INVALID;
     StepK k;
     k.c = *c;
     k.p = *p;
     const int64_t total = (int64_t)p->n_env * p->n_obj;
     if (total >= ((int64_t)1 << 31)) return SSA_E_INVALID;
-    // tiles per wavefront T = ceil(tiles / resident wavefront slots); G = ceil(tiles / T) wavefronts
-    const int64_t ntiles = (total + OBJ_PER_WAVE - 1) / OBJ_PER_WAVE;
-    const int64_t slots = (int64_t)device_cu_count() * 4 * SSA_STEP_WAVES;
-    const int64_t per_wave = (ntiles + slots - 1) / slots;
-    const int nwork = (int)((ntiles + per_wave - 1) / per_wave);
+    int64_t ntiles, per_wave;
+    int nwork;
+    tile_grid(total, ntiles, nwork, per_wave);
     const bool fast_stats = p->stat_shards != nullptr;   // statistics by the common-path kernel's atomics
     const bool defer = fast_stats && (p->launch_mask & SSA_LAUNCH_DEFER_FOLD);
     if (defer && p->stat_shards_prev && (!p->stats_prev || p->stat_shards_prev == p->stat_shards)) return SSA_E_INVALID;
@@ -3615,9 +3537,8 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     StatAcc* parts = (StatAcc*)p->stat_ws;
     hipStream_t s = (hipStream_t)stream;
     const unsigned mask = (p->launch_mask & 7u) ? (p->launch_mask & 7u) : 7u;   // diagnostic: time one launch alone
-    if (c->propagator != SSA_PROP_FG && c->propagator != SSA_PROP_ELEMENTS && c->propagator != SSA_PROP_J2_RK4 && c->propagator != SSA_PROP_HYBRID) return SSA_E_INVALID;
-    if (c->propagator == SSA_PROP_J2_RK4 && (c->rk4_substeps < 1 || c->rk4_substeps > 4096)) return SSA_E_INVALID;
     const int prop = c->propagator;
+    const int nt = (int)ntiles;
     if ((mask & 1u) && sens) {
         SensK ks;
         ks.k = k;
@@ -3625,31 +3546,13 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
         ks.k.p.actions = nullptr;
         ks.k.p.launch_mask &= ~SSA_LAUNCH_INLINE_ACTION;
         ks.s = *sens;
-        const int nt = (int)ntiles;
-        if (per_wave == 1) {
-            if (prop == SSA_PROP_FG) hipExtLaunchKernelGGL((step_sensors_kernel<1, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
-            else if (prop == SSA_PROP_ELEMENTS) hipExtLaunchKernelGGL((step_sensors_kernel<0, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
-            else if (prop == SSA_PROP_HYBRID) hipExtLaunchKernelGGL((step_sensors_kernel<3, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
-            else hipExtLaunchKernelGGL((step_sensors_kernel<2, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
-        } else {
-            if (prop == SSA_PROP_FG) hipExtLaunchKernelGGL((step_sensors_kernel<1, true>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
-            else if (prop == SSA_PROP_ELEMENTS) hipExtLaunchKernelGGL((step_sensors_kernel<0, true>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
-            else if (prop == SSA_PROP_HYBRID) hipExtLaunchKernelGGL((step_sensors_kernel<3, true>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
-            else hipExtLaunchKernelGGL((step_sensors_kernel<2, true>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
-        }
+        with_prop(prop, per_wave != 1, [&](auto P, auto M) {
+            hipExtLaunchKernelGGL((step_sensors_kernel<P, M>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
+        });
     } else if (mask & 1u) {   // (ev0, ev1: dispatch timestamps of this kernel for ssa_env_step_profiled_f64, else null)
-        const int nt = (int)ntiles;
-        if (per_wave == 1) {
-            if (prop == SSA_PROP_FG) hipExtLaunchKernelGGL((step_fast_kernel<1, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-            else if (prop == SSA_PROP_ELEMENTS) hipExtLaunchKernelGGL((step_fast_kernel<0, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-            else if (prop == SSA_PROP_HYBRID) hipExtLaunchKernelGGL((step_fast_kernel<3, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-            else hipExtLaunchKernelGGL((step_fast_kernel<2, false>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        } else {
-            if (prop == SSA_PROP_FG) hipExtLaunchKernelGGL((step_fast_kernel<1, true>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-            else if (prop == SSA_PROP_ELEMENTS) hipExtLaunchKernelGGL((step_fast_kernel<0, true>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-            else if (prop == SSA_PROP_HYBRID) hipExtLaunchKernelGGL((step_fast_kernel<3, true>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-            else hipExtLaunchKernelGGL((step_fast_kernel<2, true>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        }
+        with_prop(prop, per_wave != 1, [&](auto P, auto M) {
+            hipExtLaunchKernelGGL((step_fast_kernel<P, M>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        });
     }
     if (fast_stats) {   // (the aer_out payload, if any, was the step kernel's epilogue) a one-wave fold finishes the step
                         // (2 launches), unless deferred (1 launch)
@@ -3659,12 +3562,8 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
                                (const unsigned long long*)p->spos_tiles, p->n_obj);
         return launch_status();
     }
-    if (mask & 2u) {
-        if (prop == SSA_PROP_FG) hipLaunchKernelGGL(step_post_kernel<1>, dim3(nparts, p->n_env), dim3(POST_T), 0, s, k, parts, nparts);
-        else if (prop == SSA_PROP_ELEMENTS) hipLaunchKernelGGL(step_post_kernel<0>, dim3(nparts, p->n_env), dim3(POST_T), 0, s, k, parts, nparts);
-        else if (prop == SSA_PROP_HYBRID) hipLaunchKernelGGL(step_post_kernel<3>, dim3(nparts, p->n_env), dim3(POST_T), 0, s, k, parts, nparts);
-        else hipLaunchKernelGGL(step_post_kernel<2>, dim3(nparts, p->n_env), dim3(POST_T), 0, s, k, parts, nparts);
-    }
+    if (mask & 2u)
+        with_prop(prop, [&](auto P) { hipLaunchKernelGGL(step_post_kernel<P>, dim3(nparts, p->n_env), dim3(POST_T), 0, s, k, parts, nparts); });
     // folds the per-block statistics
     if ((mask & 4u) && p->stats)
         hipLaunchKernelGGL(reward_final_kernel, dim3(p->n_env), dim3(64), 0, s, (const StatAcc*)parts, p->stats, nparts);
@@ -3677,11 +3576,9 @@ int ssa_env_step_f64(const ssa_consts* c, const ssa_step_params* p, void* stream
 int ssa_env_step_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, void* stream)
 {
     if (!c || !p || !sp) return SSA_E_INVALID;
-    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
-    if (p->n_env != 1) return SSA_E_UNSUPPORTED;
+    const int rc = sensors_ok(sp, p);
+    if (rc != SSA_OK) return rc;
     if (sp->zn_stride_sensor < 0 || (sp->n_sensor > 1 && sp->zn_stride_sensor == 0)) return SSA_E_INVALID;
-    for (int k = 0; k < sp->n_sensor; ++k)
-        if (!(sp->obs_limit[k] == sp->obs_limit[k])) return SSA_E_INVALID;
     return step_launch(c, p, stream, nullptr, nullptr, sp);
 }
 // dispatch-timestamp event pairs, created on first use (a ring, so that back-to-back launches can be timed
@@ -3712,9 +3609,7 @@ static int lookahead_args(const ssa_consts* c, const ssa_step_params* p, const s
     if (!o->score || !o->status || !o->visible) return SSA_E_INVALID;
     if ((p->launch_mask & SSA_LAUNCH_INLINE_ENVS) && p->n_env > SSA_INLINE_ENVS) return SSA_E_INVALID;
     if (p->obj_ids && p->n_env != 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // (whole tiles per env, as the step)
-    if (c->obs_type != SSA_OBS_AER && c->obs_type != SSA_OBS_XYZ) return SSA_E_INVALID;
-    if (c->propagator != SSA_PROP_FG && c->propagator != SSA_PROP_ELEMENTS && c->propagator != SSA_PROP_J2_RK4 && c->propagator != SSA_PROP_HYBRID) return SSA_E_INVALID;
-    if (c->propagator == SSA_PROP_J2_RK4 && (c->rk4_substeps < 1 || c->rk4_substeps > 4096)) return SSA_E_INVALID;
+    if (!consts_ok(c)) return SSA_E_INVALID;
     const int64_t total = (int64_t)p->n_env * p->n_obj;
     if (total >= ((int64_t)1 << 31)) return SSA_E_INVALID;
     k.k.c = *c;
@@ -3730,72 +3625,44 @@ static int lookahead_args(const ssa_consts* c, const ssa_step_params* p, const s
     q.launch_mask = p->launch_mask & SSA_LAUNCH_INLINE_ENVS;
     return SSA_OK;
 }
-// the lookahead's grid: one tile per wavefront up to the resident wavefronts, a grid-stride walk beyond (as the step)
-static void lookahead_grid(int64_t total, int& nt, int& nwork, bool& multi)
-{
-    const int64_t ntiles = (total + OBJ_PER_WAVE - 1) / OBJ_PER_WAVE;
-    const int64_t slots = (int64_t)device_cu_count() * 4 * SSA_STEP_WAVES;
-    const int64_t per_wave = (ntiles + slots - 1) / slots;
-    nwork = (int)((ntiles + per_wave - 1) / per_wave);
-    nt = (int)ntiles;
-    multi = per_wave != 1;
-}
 int ssa_lookahead_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_lookahead_out* o, void* stream)
 {
     LookK k;
     const int rc = lookahead_args(c, p, o, k);
     if (rc != SSA_OK) return rc;
-    int nt, nwork;
-    bool multi;
-    lookahead_grid((int64_t)p->n_env * p->n_obj, nt, nwork, multi);
-    const int prop = c->propagator;
+    int64_t ntiles, per_wave;
+    int nwork;
+    tile_grid((int64_t)p->n_env * p->n_obj, ntiles, nwork, per_wave);
+    const int nt = (int)ntiles;
     dim3 grid((unsigned)nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
-    if (!multi) {
-        if (prop == SSA_PROP_FG) hipLaunchKernelGGL((lookahead_kernel<1, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        else if (prop == SSA_PROP_ELEMENTS) hipLaunchKernelGGL((lookahead_kernel<0, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        else if (prop == SSA_PROP_HYBRID) hipLaunchKernelGGL((lookahead_kernel<3, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        else hipLaunchKernelGGL((lookahead_kernel<2, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-    } else {
-        if (prop == SSA_PROP_FG) hipLaunchKernelGGL((lookahead_kernel<1, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        else if (prop == SSA_PROP_ELEMENTS) hipLaunchKernelGGL((lookahead_kernel<0, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        else if (prop == SSA_PROP_HYBRID) hipLaunchKernelGGL((lookahead_kernel<3, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        else hipLaunchKernelGGL((lookahead_kernel<2, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-    }
+    with_prop(c->propagator, per_wave != 1, [&](auto P, auto M) {
+        hipLaunchKernelGGL((lookahead_kernel<P, M>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+    });
     return launch_status();
 }
 int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_lookahead_out* o,
                               void* stream)
 {
     if (!c || !p || !sp || !o) return SSA_E_INVALID;
-    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
-    if (p->n_env != 1) return SSA_E_UNSUPPORTED;
-    for (int k = 0; k < sp->n_sensor; ++k)
-        if (!(sp->obs_limit[k] == sp->obs_limit[k])) return SSA_E_INVALID;
+    int rc = sensors_ok(sp, p);
+    if (rc != SSA_OK) return rc;
     LookSensK k;
-    const int rc = lookahead_args(c, p, o, k.k);
+    rc = lookahead_args(c, p, o, k.k);
     if (rc != SSA_OK) return rc;
     if ((int64_t)sp->n_sensor * p->n_obj >= ((int64_t)1 << 31)) return SSA_E_INVALID;
     k.s = *sp;
     k.s.upd = nullptr;   // (its action words and record destination are not read)
     for (int q = 0; q < SSA_MAX_SENSORS; ++q) k.s.action[q] = -1;
-    int nt, nwork;
-    bool multi;
-    lookahead_grid(p->n_obj, nt, nwork, multi);
-    const int prop = c->propagator;
+    int64_t ntiles, per_wave;
+    int nwork;
+    tile_grid(p->n_obj, ntiles, nwork, per_wave);
+    const int nt = (int)ntiles;
     dim3 grid((unsigned)nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
-    if (!multi) {
-        if (prop == SSA_PROP_FG) hipLaunchKernelGGL((lookahead_sensors_kernel<1, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        else if (prop == SSA_PROP_ELEMENTS) hipLaunchKernelGGL((lookahead_sensors_kernel<0, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        else if (prop == SSA_PROP_HYBRID) hipLaunchKernelGGL((lookahead_sensors_kernel<3, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        else hipLaunchKernelGGL((lookahead_sensors_kernel<2, false>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-    } else {
-        if (prop == SSA_PROP_FG) hipLaunchKernelGGL((lookahead_sensors_kernel<1, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        else if (prop == SSA_PROP_ELEMENTS) hipLaunchKernelGGL((lookahead_sensors_kernel<0, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        else if (prop == SSA_PROP_HYBRID) hipLaunchKernelGGL((lookahead_sensors_kernel<3, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-        else hipLaunchKernelGGL((lookahead_sensors_kernel<2, true>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
-    }
+    with_prop(c->propagator, per_wave != 1, [&](auto P, auto M) {
+        hipLaunchKernelGGL((lookahead_sensors_kernel<P, M>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+    });
     return launch_status();
 }
 int ssa_env_rollout_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, void* stream)
@@ -3805,9 +3672,7 @@ int ssa_env_rollout_f64(const ssa_consts* c, const ssa_step_params* p, const ssa
     if (!r->x_true_ring || !r->x_ring || !r->P_ring || !r->obs_ring || !r->metrics_ring || !r->stats_ring || !r->actions || !r->stat_shards)
         return SSA_E_INVALID;
     if (!p->status || !p->trans || !p->env_time || !p->z_noise) return SSA_E_INVALID;
-    if (c->obs_type != SSA_OBS_AER && c->obs_type != SSA_OBS_XYZ) return SSA_E_INVALID;
-    if (c->propagator != SSA_PROP_FG && c->propagator != SSA_PROP_ELEMENTS && c->propagator != SSA_PROP_J2_RK4 && c->propagator != SSA_PROP_HYBRID) return SSA_E_INVALID;
-    if (c->propagator == SSA_PROP_J2_RK4 && (c->rk4_substeps < 1 || c->rk4_substeps > 4096)) return SSA_E_INVALID;
+    if (!consts_ok(c)) return SSA_E_INVALID;
     const int64_t total = (int64_t)p->n_env * p->n_obj;
     if (total >= ((int64_t)1 << 31)) return SSA_E_INVALID;
     if (r->spos_tiles && p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;
@@ -3819,15 +3684,11 @@ int ssa_env_rollout_f64(const ssa_consts* c, const ssa_step_params* p, const ssa
     rk.k.p.spos_tiles_prev = nullptr;
     if (p->obj_ids && p->n_env != 1) return SSA_E_UNSUPPORTED;
     rk.r = *r;
-    const int64_t ntiles = (total + OBJ_PER_WAVE - 1) / OBJ_PER_WAVE;
-    const int64_t slots = (int64_t)device_cu_count() * 4 * SSA_STEP_WAVES;
-    const int64_t per_wave = (ntiles + slots - 1) / slots;
-    const int nwork = (int)((ntiles + per_wave - 1) / per_wave);
+    int64_t ntiles, per_wave;
+    int nwork;
+    tile_grid(total, ntiles, nwork, per_wave);
     hipStream_t s = (hipStream_t)stream;
-    if (c->propagator == SSA_PROP_FG) hipLaunchKernelGGL(rollout_kernel<1>, dim3(nwork), dim3(64), 0, s, rk, (int)ntiles, nwork);
-    else if (c->propagator == SSA_PROP_ELEMENTS) hipLaunchKernelGGL(rollout_kernel<0>, dim3(nwork), dim3(64), 0, s, rk, (int)ntiles, nwork);
-    else if (c->propagator == SSA_PROP_HYBRID) hipLaunchKernelGGL(rollout_kernel<3>, dim3(nwork), dim3(64), 0, s, rk, (int)ntiles, nwork);
-    else hipLaunchKernelGGL(rollout_kernel<2>, dim3(nwork), dim3(64), 0, s, rk, (int)ntiles, nwork);
+    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(rollout_kernel<P>, dim3(nwork), dim3(64), 0, s, rk, (int)ntiles, nwork); });
     hipLaunchKernelGGL(rollout_fold_kernel, dim3(r->n_steps, p->n_env), dim3(64), 0, s, (unsigned long long*)r->stat_shards, r->stats_ring,
                        p->n_env, r->n_steps, r->slot_out, r->history, (const unsigned long long*)r->spos_tiles, p->n_obj, ntiles);
     return launch_status();
@@ -3846,10 +3707,7 @@ static int64_t closed_loop_capacity(int prop)
     if (cached[prop] <= 0) {
         int per_cu = 0;
         hipError_t e;
-        if (prop == SSA_PROP_FG) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, closed_loop_kernel<1>, 64, 0);
-        else if (prop == SSA_PROP_ELEMENTS) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, closed_loop_kernel<0>, 64, 0);
-        else if (prop == SSA_PROP_HYBRID) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, closed_loop_kernel<3>, 64, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, closed_loop_kernel<2>, 64, 0);
+        with_prop(prop, [&](auto P) { e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, closed_loop_kernel<P>, 64, 0); });
         if (e != hipSuccess || per_cu <= 0) return 0;
         cached[prop] = (int64_t)per_cu * device_cu_count();
     }
@@ -3863,9 +3721,7 @@ int ssa_env_closed_loop_f64(const ssa_consts* c, const ssa_step_params* p, const
         return SSA_E_INVALID;
     if (!p->status || !p->trans || !p->env_time || !p->z_noise) return SSA_E_INVALID;
     if (r->agent < SSA_AGENT_NAIVE_GREEDY || r->agent > SSA_AGENT_VEL_ERROR) return SSA_E_INVALID;
-    if (c->obs_type != SSA_OBS_AER && c->obs_type != SSA_OBS_XYZ) return SSA_E_INVALID;
-    if (c->propagator != SSA_PROP_FG && c->propagator != SSA_PROP_ELEMENTS && c->propagator != SSA_PROP_J2_RK4 && c->propagator != SSA_PROP_HYBRID) return SSA_E_INVALID;
-    if (c->propagator == SSA_PROP_J2_RK4 && (c->rk4_substeps < 1 || c->rk4_substeps > 4096)) return SSA_E_INVALID;
+    if (!consts_ok(c)) return SSA_E_INVALID;
     if (p->n_env != 1) return SSA_E_UNSUPPORTED;
     if ((p->obj_ids != nullptr) != (r->slot_of != nullptr)) return SSA_E_INVALID;     // (a storage layout comes with its inverse table)
     const int64_t ntiles = (p->n_obj + OBJ_PER_WAVE - 1) / OBJ_PER_WAVE;
@@ -3890,9 +3746,8 @@ int ssa_env_closed_loop_f64(const ssa_consts* c, const ssa_step_params* p, const
     // launch that is the runtime's guarantee (it refuses a grid the device cannot hold next to what else is running), not only this
     // function's occupancy estimate above.
     void* args[3] = {(void*)&lk, (void*)&nwork, (void*)&nwork};
-    const void* fn = (c->propagator == SSA_PROP_FG) ? (const void*)closed_loop_kernel<1>
-                     : (c->propagator == SSA_PROP_ELEMENTS) ? (const void*)closed_loop_kernel<0>
-                     : (c->propagator == SSA_PROP_HYBRID) ? (const void*)closed_loop_kernel<3> : (const void*)closed_loop_kernel<2>;
+    const void* fn = nullptr;
+    with_prop(c->propagator, [&](auto P) { fn = (const void*)closed_loop_kernel<P>; });
     const hipError_t ce = hipLaunchCooperativeKernel(fn, grid, dim3(64), args, 0, s);
     if (ce == hipErrorCooperativeLaunchTooLarge) {
         (void)hipGetLastError();

@@ -171,25 +171,42 @@ def _code_object(tmp_path):
     return notes, dis
 
 
+def _kernels(tmp_path):
+    """the built code object (_code_object) per kernel: {name: metadata} -- register counts, scratch, LDS, the arguments' value
+    kinds and the offsets of the by-value ones -- and {name: instruction list} (the opcodes of its disassembly, in order)"""
+    import re
+    notes, dis = _code_object(tmp_path)
+    meta = {}
+    for blk in notes.split("- .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        meta[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1)) for k in
+                      ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")}
+        meta[name]["arg_kinds"] = re.findall(r"\.value_kind:\s+(\w+)", blk)
+        meta[name]["by_value_offsets"] = [int(v) for v in re.findall(r"\.offset:\s+(\d+)\s+\.size:\s+\d+\s+\.value_kind:\s+by_value", blk)]
+    bodies = re.split(r"\n[0-9a-f]+ <([^>]+)>:\n", dis)
+    ins = {name: [ln.split()[0] for ln in body.splitlines() if ln.strip() and not ln.strip().startswith(("//", ";"))]
+           for name, body in zip(bodies[1::2], bodies[2::2])}
+    return meta, ins
+
+
+def stray_scratch(ops):
+    """(the indices of) the scratch accesses of an instruction list that lie away from every out-of-line call (s_swappc_b64)"""
+    calls = [i for i, op in enumerate(ops) if op == "s_swappc_b64"]
+    return [i for i, op in enumerate(ops) if op.startswith("scratch_") and not (calls and min(abs(i - c) for c in calls) <= 96)]
+
+
 def test_step_kernels_keep_their_register_budget(tmp_path):
     """The step / rollout kernels must fit 96 VGPRs (5 wavefronts per SIMD = the whole 20 000-object step resident in
     one round) and must not spill on the common path: the build relies on a whole-TU compiler switch
     (-disable-machine-licm, _build.py), so a toolchain change that brings the spills back (41.7 MB of scratch traffic
     per launch when it happened) has to fail HERE, not show up as a slower bench.  Scratch accesses are allowed only
     as the save / restore around the rare out-of-line calls of SSA_PROP_ELEMENTS (the complete farnocchia())."""
-    import re
-    notes, dis = _code_object(tmp_path)
-    kern = {}
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        kern[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1)) for k in
-                      ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")}
+    kern, ins_of = _kernels(tmp_path)
     # the grid-stride instance re-derives its argument block from the kernarg segment pointer: the by-value StepK must sit
     # right behind the six preloaded scalar arguments (offset 40) (a wrong offset there is a wild-pointer GPU fault, not a wrong number)
-    for blk in notes.split("- .agpr_count:")[1:]:
-        if "step_fast_kernel" in re.search(r"\.name:\s+(\S+)", blk).group(1):
-            offs = [int(v) for v in re.findall(r"\.offset:\s+(\d+)\s+\.size:\s+\d+\s+\.value_kind:\s+by_value", blk)]
-            kinds = re.findall(r"\.value_kind:\s+(\w+)", blk)
+    for name, k in kern.items():
+        if "step_fast_kernel" in name:
+            offs, kinds = k["by_value_offsets"], k["arg_kinds"]
             assert kinds[:6] == ["by_value"] * 2 + ["global_buffer"] * 4 and 40 in offs, (kinds[:7], offs)
     hot = [k for k in kern if "step_fast_kernel" in k or "rollout_kernel" in k or "closed_loop_kernel" in k]
     assert len(hot) == 16, hot                     # 4 propagators x {one tile, multi tile, rollout, closed loop}
@@ -198,14 +215,11 @@ def test_step_kernels_keep_their_register_budget(tmp_path):
         assert kern[k]["private_segment_fixed_size"] <= 320, (k, kern[k])     # the callees' frames only (two levels: lean form, complete restatement)
         assert kern[k]["group_segment_fixed_size"] <= 160 * 1024 // 20, (k, kern[k])   # 20 wavefronts' tiles per CU
     # disassembly: every scratch access of a hot kernel lies next to an out-of-line call (s_swappc_b64)
-    bodies = re.split(r"\n[0-9a-f]+ <([^>]+)>:\n", dis)
     checked = 0
-    for name, body in zip(bodies[1::2], bodies[2::2]):
+    for name, ins in ins_of.items():
         if not ("step_fast_kernel" in name or "rollout_kernel" in name or "closed_loop_kernel" in name):
             continue
-        ins = [ln.split()[0] for ln in body.splitlines() if ln.strip() and not ln.strip().startswith(("//", ";"))]
-        calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
-        stray = [i for i, op in enumerate(ins) if op.startswith("scratch_") and not (calls and min(abs(i - c) for c in calls) <= 96)]
+        stray = stray_scratch(ins)
         # none in any instance -- the grid-stride one once spilled the object / env / action words across the propagator in
         # EVERY wavefront (24 bytes per lane and tile: 61 MB of scratch writes per 160 000-object step, found as write
         # traffic 1.58x the algorithmic bytes)

@@ -73,25 +73,18 @@ def test_env_lookahead_has_no_cpu_fallback(lib):
 def test_lookahead_kernels_keep_the_step_kernels_budget(tmp_path):
     """the lookahead instances fit the step kernel's register budget and LDS, and touch scratch only where the step kernel does:
     the save / restore around the out-of-line calls of SSA_PROP_ELEMENTS / SSA_PROP_HYBRID -- none on the common path"""
-    from test_abi_and_host import _code_object
-    notes, dis = _code_object(tmp_path)
-    kern = {}
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        kern[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1)) for k in
-                      ("vgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")}
+    from test_abi_and_host import _kernels, stray_scratch
+    kern, ins_of = _kernels(tmp_path)
     look = [k for k in kern if "lookahead_kernel" in k]
     assert len(look) == 8, look                    # 4 propagators x {one tile, multi tile}
-    bodies = re.split(r"\n[0-9a-f]+ <([^>]+)>:\n", dis)
     checked = 0
-    for name, body in zip(bodies[1::2], bodies[2::2]):
+    for name, ins in ins_of.items():
         if "lookahead_kernel" not in name:
             continue
         k = kern[name]
         assert k["vgpr_count"] <= 96 and k["group_segment_fixed_size"] <= 160 * 1024 // 20, (name, k)
-        ins = [ln.split()[0] for ln in body.splitlines() if ln.strip() and not ln.strip().startswith(("//", ";"))]
         calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
-        stray = [i for i, op in enumerate(ins) if op.startswith("scratch_") and not (calls and min(abs(i - c) for c in calls) <= 96)]
+        stray = stray_scratch(ins)
         assert not stray, (name, stray[:8])
         if "ILi0E" not in name and "ILi3E" not in name:     # FG / J2: no call, no scratch at all
             assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)

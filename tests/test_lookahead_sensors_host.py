@@ -89,27 +89,16 @@ def test_env_lookahead_sensors_has_no_cpu_fallback(lib):
         env.lookahead_sensors(covariances=True)
 
 
-def _resources(notes):
-    kern = {}
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        kern[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1)) for k in
-                      ("vgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")}
-    return kern
-
-
 def test_lookahead_sensors_kernels_keep_the_lookahead_kernels_budget(tmp_path):
     """each of the eight instances (4 propagators x {one tile, multi tile}) within lookahead_kernel of the same propagator and launch
     form: at most 96 VGPRs, the same LDS, no more scratch and no more VGPR spills; scratch touched only around the out-of-line calls of
     SSA_PROP_ELEMENTS / SSA_PROP_HYBRID; FG and J2 without calls or scratch"""
-    from test_abi_and_host import _code_object
-    notes, dis = _code_object(tmp_path)
-    kern = _resources(notes)
+    from test_abi_and_host import _kernels, stray_scratch
+    kern, ins_of = _kernels(tmp_path)
     new = sorted(k for k in kern if "lookahead_sensors_kernel" in k)
     assert len(new) == 8, new
-    bodies = re.split(r"\n[0-9a-f]+ <([^>]+)>:\n", dis)
     checked = 0
-    for name, body in zip(bodies[1::2], bodies[2::2]):
+    for name, ins in ins_of.items():
         if "lookahead_sensors_kernel" not in name:
             continue
         form = re.search(r"ILi(\d)ELb(\d)E", name).group(0)
@@ -120,9 +109,8 @@ def test_lookahead_sensors_kernels_keep_the_lookahead_kernels_budget(tmp_path):
         assert k["group_segment_fixed_size"] == b["group_segment_fixed_size"], (name, k, b)
         assert k["private_segment_fixed_size"] <= b["private_segment_fixed_size"], (name, k, b)
         assert k["vgpr_spill_count"] <= b["vgpr_spill_count"], (name, k, b)
-        ins = [ln.split()[0] for ln in body.splitlines() if ln.strip() and not ln.strip().startswith(("//", ";"))]
         calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
-        stray = [i for i, op in enumerate(ins) if op.startswith("scratch_") and not (calls and min(abs(i - c) for c in calls) <= 96)]
+        stray = stray_scratch(ins)
         assert not stray, (name, stray[:8])
         if form.startswith(("ILi1", "ILi2")):     # FG / J2: no call, no scratch at all
             assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)

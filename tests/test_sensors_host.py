@@ -145,18 +145,12 @@ def test_sensor_kernels_keep_the_step_kernels_budget(tmp_path):
     """the eight sensor-network kernels (4 propagators x {one tile, multi tile}) fit the step kernel's register budget and LDS, use no
     more scratch than the step kernel of the same propagator and launch form, and touch it only around the out-of-line calls
     (SSA_PROP_ELEMENTS / SSA_PROP_HYBRID) -- FG and J2 none at all"""
-    from test_abi_and_host import _code_object
-    notes, dis = _code_object(tmp_path)
-    kern = {}
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        kern[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1)) for k in
-                      ("vgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")}
+    from test_abi_and_host import _kernels, stray_scratch
+    kern, ins_of = _kernels(tmp_path)
     sens = [k for k in kern if "step_sensors_kernel" in k]
     assert len(sens) == 8, sens
-    bodies = re.split(r"\n[0-9a-f]+ <([^>]+)>:\n", dis)
     checked = 0
-    for name, body in zip(bodies[1::2], bodies[2::2]):
+    for name, ins in ins_of.items():
         if "step_sensors_kernel" not in name:
             continue
         k = kern[name]
@@ -164,9 +158,8 @@ def test_sensor_kernels_keep_the_step_kernels_budget(tmp_path):
         assert k["vgpr_count"] <= 96 and k["group_segment_fixed_size"] == step["group_segment_fixed_size"], (name, k)
         assert k["private_segment_fixed_size"] <= step["private_segment_fixed_size"], (name, k, step)
         assert k["vgpr_spill_count"] <= step["vgpr_spill_count"], (name, k, step)
-        ins = [ln.split()[0] for ln in body.splitlines() if ln.strip() and not ln.strip().startswith(("//", ";"))]
         calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
-        stray = [i for i, op in enumerate(ins) if op.startswith("scratch_") and not (calls and min(abs(i - c) for c in calls) <= 96)]
+        stray = stray_scratch(ins)
         assert not stray, (name, stray[:8])
         if "ILi0E" not in name and "ILi3E" not in name:
             assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)
