@@ -383,6 +383,39 @@ class HotPathEngine:
 
     LOOKAHEAD_PARTS = ("x_prior", "P_prior", "P_post")
 
+    def _lookahead_out(self, name, attr, lead, prior_lead, out):
+        """(ssa_lookahead_out, result dict) of a lookahead launch: the output buffers `attr` of this engine -- score lead + [3], status /
+        visible [lead], the parts of LOOKAHEAD_PARTS asked for in `out` (x_prior prior_lead + [6], P_prior prior_lead + [6, 6], P_post
+        lead + [6, 6]) -- allocated on first use (again when `lead` changes) and reused by the next call"""
+        want = tuple(out)
+        bad = [k for k in want if k not in self.LOOKAHEAD_PARTS]
+        if bad:
+            raise ValueError("%s: unknown output(s) %s (choose from %s)" % (name, bad, self.LOOKAHEAD_PARTS))
+        look = getattr(self, attr, None)
+        if look is None or tuple(look["status"].shape) != lead:
+            look = {"score": torch.empty(lead + (_lib.LOOK_NSCORE,), dtype=f64, device=self.dev),
+                    "status": torch.empty(lead, dtype=torch.int32, device=self.dev),
+                    "visible": torch.empty(lead, dtype=torch.uint8, device=self.dev)}
+            setattr(self, attr, look)
+        shapes = {"x_prior": prior_lead + (6,), "P_prior": prior_lead + (6, 6), "P_post": lead + (6, 6)}
+        for k in want:
+            if k not in look:
+                look[k] = torch.empty(shapes[k], dtype=f64, device=self.dev)
+        o = _lib.ssa_lookahead_out()
+        o.score, o.status, o.visible = (look[k].data_ptr() for k in ("score", "status", "visible"))
+        for k in self.LOOKAHEAD_PARTS:
+            setattr(o, k, look[k].data_ptr() if k in want else 0)
+        return o, {k: look[k] for k in ("score", "status", "visible") + want}
+
+    def _lookahead_params(self, slot_in, time_offset):
+        """the input-only parameter block of a lookahead from history slot `slot_in` (nothing of the engine's state is written)"""
+        p = _lib.ssa_step_params()
+        C.memmove(C.byref(p), C.byref(self._p), C.sizeof(p))
+        sl = int(slot_in) % self.H
+        p.x_true_in, p.x_in, p.P_in = self._bx_t + sl * self._sx, self._bx + sl * self._sx, self._bP + sl * self._sP
+        p.time_offset, p.launch_mask = int(time_offset), 0
+        return p
+
     def launch_lookahead(self, slot_in, time_offset, out=(), stream=None, env_times=None):
         """enqueue the one-step tasking lookahead (include/ssa_hip.h: ssa_lookahead_f64) from history slot `slot_in` for the step whose
         time index is env_time + time_offset (env_times: the envs' time words by value, n_env <= 8; else the engine's env_time0 words, as a
@@ -391,28 +424,9 @@ class HotPathEngine:
         status [E*m] int32, visible [E*m] uint8 and the parts asked for (x_prior [E*m, 6], P_prior / P_post [E*m, 6, 6]) -- the buffers
         are allocated on first use and reused by the next call.  Asynchronous, no host sync."""
         N = self.m * self.E
-        want = tuple(out)
-        bad = [k for k in want if k not in self.LOOKAHEAD_PARTS]
-        if bad:
-            raise ValueError("launch_lookahead: unknown output(s) %s (choose from %s)" % (bad, self.LOOKAHEAD_PARTS))
-        if getattr(self, "_look", None) is None:
-            self._look = {"score": torch.empty((N, _lib.LOOK_NSCORE), dtype=f64, device=self.dev),
-                          "status": torch.empty(N, dtype=torch.int32, device=self.dev),
-                          "visible": torch.empty(N, dtype=torch.uint8, device=self.dev)}
-        shapes = {"x_prior": (N, 6), "P_prior": (N, 6, 6), "P_post": (N, 6, 6)}
-        for k in want:
-            if k not in self._look:
-                self._look[k] = torch.empty(shapes[k], dtype=f64, device=self.dev)
-        o = _lib.ssa_lookahead_out()
-        o.score, o.status, o.visible = self._look["score"].data_ptr(), self._look["status"].data_ptr(), self._look["visible"].data_ptr()
-        for k in self.LOOKAHEAD_PARTS:
-            setattr(o, k, self._look[k].data_ptr() if k in want else 0)
+        o, res = self._lookahead_out("launch_lookahead", "_look", (N,), (N,), out)
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        p = _lib.ssa_step_params()
-        C.memmove(C.byref(p), C.byref(self._p), C.sizeof(p))
-        sl = int(slot_in) % self.H
-        p.x_true_in, p.x_in, p.P_in = self._bx_t + sl * self._sx, self._bx + sl * self._sx, self._bP + sl * self._sP
-        p.time_offset, p.launch_mask = int(time_offset), 0
+        p = self._lookahead_params(slot_in, time_offset)
         if env_times is not None:
             if self.E > _lib.INLINE_ENVS:
                 raise _lib.SsaHipError("env_times: at most %d envs travel in the parameter block" % _lib.INLINE_ENVS)
@@ -421,7 +435,6 @@ class HotPathEngine:
         rc = self._lib.ssa_lookahead_f64(self._cref, C.byref(p), C.byref(o), s)
         if rc:
             raise _lib.SsaHipError("ssa_lookahead_f64 failed with code %d" % rc)
-        res = {k: self._look[k] for k in ("score", "status", "visible") + want}
         return res
 
     def launch_lookahead_sensors(self, slot_in, time_offset, sensors, out=(), stream=None):
@@ -434,33 +447,13 @@ class HotPathEngine:
         the next call.  Asynchronous, no host sync."""
         if self.E != 1:
             raise _lib.SsaHipError("the lookahead of a sensor network covers one env (n_env == 1)")
-        S, m = int(sensors.n_sensor), self.m
-        want = tuple(out)
-        bad = [k for k in want if k not in self.LOOKAHEAD_PARTS]
-        if bad:
-            raise ValueError("launch_lookahead_sensors: unknown output(s) %s (choose from %s)" % (bad, self.LOOKAHEAD_PARTS))
-        if getattr(self, "_look_s", None) is None or self._look_s["score"].shape[0] != S:
-            self._look_s = {"score": torch.empty((S, m, _lib.LOOK_NSCORE), dtype=f64, device=self.dev),
-                            "status": torch.empty((S, m), dtype=torch.int32, device=self.dev),
-                            "visible": torch.empty((S, m), dtype=torch.uint8, device=self.dev)}
-        shapes = {"x_prior": (m, 6), "P_prior": (m, 6, 6), "P_post": (S, m, 6, 6)}
-        for k in want:
-            if k not in self._look_s:
-                self._look_s[k] = torch.empty(shapes[k], dtype=f64, device=self.dev)
-        o = _lib.ssa_lookahead_out()
-        o.score, o.status, o.visible = (self._look_s[k].data_ptr() for k in ("score", "status", "visible"))
-        for k in self.LOOKAHEAD_PARTS:
-            setattr(o, k, self._look_s[k].data_ptr() if k in want else 0)
+        o, res = self._lookahead_out("launch_lookahead_sensors", "_look_s", (int(sensors.n_sensor), self.m), (self.m,), out)
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        p = _lib.ssa_step_params()
-        C.memmove(C.byref(p), C.byref(self._p), C.sizeof(p))
-        sl = int(slot_in) % self.H
-        p.x_true_in, p.x_in, p.P_in = self._bx_t + sl * self._sx, self._bx + sl * self._sx, self._bP + sl * self._sP
-        p.time_offset, p.launch_mask = int(time_offset), 0
+        p = self._lookahead_params(slot_in, time_offset)
         rc = self._lib.ssa_lookahead_sensors_f64(self._cref, C.byref(p), C.byref(sensors), C.byref(o), s)
         if rc:
             raise _lib.SsaHipError("ssa_lookahead_sensors_f64 failed with code %d" % rc)
-        return {k: self._look_s[k] for k in ("score", "status", "visible") + want}
+        return res
 
     def launch_rollout(self, slot_in, time_offset, actions, stream=None, argmax_spos=False):
         """K = actions.shape[0] consecutive steps in one launch (include/ssa_hip.h: ssa_env_rollout_f64): step k reads

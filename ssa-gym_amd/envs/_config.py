@@ -1,9 +1,14 @@
-"""Resolution of the operator plug points of an env_config dict (envs/__init__.py:23-28 of the reference) into
-the fused-kernel variant, shared by SSA_Tasker_Env and SSA_Tasker_VecEnv so that both accept -- and refuse --
-exactly the same configurations."""
+"""What SSA_Tasker_Env and SSA_Tasker_VecEnv derive from an env_config dict, in one place so that both accept -- and refuse --
+exactly the same configurations and resolve them to the same values: the operator plug points (envs/__init__.py:23-28 of the
+reference) as the fused-kernel variant, the sensor network, the filter and site values, the kernel constants and the observation
+options (resolve_config); and the two rules both envs apply per episode and per step: the initial-state draw and the reward."""
+from types import SimpleNamespace
+
 import numpy as np
 
-from . import dynamics
+from .. import _lib, host
+from . import dynamics, transformations
+from ._gymshim import spaces
 
 _MODELS = {(("hx", "aer"), ("mean_z", "uvw"), ("residual_z", "aer")): 'aer',
            (("hx", "xyz"), ("mean_z", "xyz"), ("residual_z", "xyz")): 'xyz'}
@@ -47,7 +52,6 @@ def kernel_consts(config, Q, R, dt, obs_limit_rad, obs_lla):
     operator tokens and the optional keys `propagator`, `resample_sigmas`, `covariance_form` ('reference' | 'centred';
     default: 'reference' with the 'hybrid' and 'elements' propagators -- the behaviour-faithful variants -- else 'centred'),
     `ad` / `ad_kwargs` into kernel constants."""
-    from .. import host
     model, propagator = resolve_kernel_variant(config)
     kw = {}
     pert = resolve_perturbation(config)
@@ -94,3 +98,120 @@ def resolve_sensors(config):
         if any(z.shape != (3,) or not np.all(np.isfinite(z)) or np.any(z < 0) for z in zs):
             raise ValueError("config['sensor_z_sigma']: every entry is a z_sigma of three non-negative values")
     return {'sites': [tuple(float(v) for v in row) for row in arr], 'obs_limit': lim, 'z_sigma': zs}
+
+
+def resolve_config(config):
+    """everything SSA_Tasker_Env and SSA_Tasker_VecEnv derive from a config dict, in one place (no GPU needed): the filter and site
+    values (z_sigma, R, P_0, x_sigma, Q, obs_lla / obs_itrs / obs_limit of the primary sensor), the sensor network (`net`: None
+    without config['observers']; else per-sensor lla, obs_limit, z_sigma, R and ssa_consts), the primary ssa_consts, the
+    measurement model, the trans table and the validated observation options.  Sensor 0 of a network is the PRIMARY sensor: its
+    site, elevation mask, z_sigma and R are the env's observer."""
+    c = SimpleNamespace(obs_type=config['obs_type'], dt=config['time_step'], n=config['steps'], m=config['rso_count'])
+    unit = np.array([host.arcsec2rad, host.arcsec2rad, 1])
+    if c.obs_type == 'aer':
+        c.z_sigma = config['z_sigma'] * unit
+    elif c.obs_type == 'xyz':
+        c.z_sigma = np.asarray(config['z_sigma'], dtype=np.float64)
+    else:
+        print('Invalid Observation Type: ' + str(config['obs_type']))
+        raise SystemExit
+    c.x_sigma = np.array(config['x_sigma'])
+    c.Q = host.Q_discrete_white_noise(dim=2, dt=c.dt, var=config['q_sigma'] ** 2, block_size=3, order_by_dim=False)
+    c.model, _ = resolve_kernel_variant(config)      # (operator plug points -> fused kernel variant; no CPU fallback)
+    c.P_0 = np.copy(np.diag(c.x_sigma ** 2)) if config['P_0'] is None else np.copy(config['P_0'])
+    c.R = np.diag(c.z_sigma ** 2) if config['R'] is None else np.copy(config['R'])
+    c.obs_lla = np.array(config['observer']) * [host.deg2rad, host.deg2rad, 1]
+    c.obs_limit = np.radians(config['obs_limit'])
+    net = resolve_sensors(config)
+    c.n_sensor = 1 if net is None else len(net['sites'])
+    c.net = None
+    if net is not None:
+        S = c.n_sensor
+        lla = np.array(net['sites']) * [host.deg2rad, host.deg2rad, 1]
+        lim = np.radians(net['obs_limit']) if net['obs_limit'] is not None else np.full(S, c.obs_limit)
+        if net['z_sigma'] is not None:
+            zs = np.array([z * (unit if c.obs_type == 'aer' else 1.0) for z in net['z_sigma']])
+            R = np.array([np.diag(z ** 2) for z in zs])
+        else:
+            zs, R = np.tile(c.z_sigma, (S, 1)), np.tile(c.R, (S, 1, 1))
+        c.net = SimpleNamespace(lla=lla, obs_limit=lim, z_sigma=zs, R=R)
+        c.obs_lla, c.obs_limit = lla[0], lim[0]
+        c.z_sigma, c.R = zs[0], np.copy(R[0])
+    c.obs_itrs = host.lla2ecef(c.obs_lla)
+    # config['obs_dtype'] = 'float64' (default, the reference's) | 'float32' (EXTENSION): the observation handed to the host in single
+    # precision -- the step kernel writes its host-facing copy that way (SSA_LAUNCH_MIRROR_F32).  The device state stays float64
+    dt = np.dtype(config.get('obs_dtype', np.float64))
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("config['obs_dtype'] must be float64 or float32")
+    c.obs_f32 = dt == np.float32
+    # config['obs_device'] = True (opt-in, for policies that live on the GPU): step() returns CUDA tensors the kernel wrote, nothing but
+    # the statistics crosses PCIe.  config['obs_zero_copy'] = True (opt-in): a view of the host-mapped ring the kernel writes instead of
+    # a fresh array per step
+    c.obs_device = bool(config.get('obs_device', False))
+    c.obs_zero_copy = bool(config.get('obs_zero_copy', False))
+    shape = {'flatten': (c.m * 12,), 'aer': (c.m * 4,)}.get(config['obs_returned'], (c.m, 12))
+    c.obs_space = spaces.Box(low=np.full(shape, -np.inf), high=np.full(shape, np.inf), dtype=np.float32 if c.obs_f32 else np.float64)
+    # config['storage_layout'] = None (default) | 'regime': how the engine STORES the objects; invisible but for speed
+    c.storage_layout = config.get('storage_layout', None)
+    if c.storage_layout not in (None, 'regime'):
+        raise ValueError("config['storage_layout'] must be None or 'regime', not %r" % (c.storage_layout,))
+    c.consts, _ = kernel_consts(config, c.Q, c.R, c.dt, c.obs_limit, c.obs_lla)
+    # (every sensor's site as kernel constants: their visibility helpers)
+    c.sensor_consts = [c.consts] + [kernel_consts(config, c.Q, c.net.R[k], c.dt, c.net.obs_limit[k], c.net.lla[k])[0]
+                                    for k in range(1, c.n_sensor)]
+    if config.get('trans_matrix') is not None:
+        c.trans = np.asarray(config['trans_matrix'], dtype=np.float64).reshape(-1, 3, 3)
+    else:
+        c.trans = transformations.trans_matrix_table(config['t_0'], c.dt, c.n)
+    return c
+
+
+def reward_done(reward_type, st, hit, paid, last, m, n):
+    """(rewards, dones) of a step from its statistics rows st [E, STAT_STRIDE], for SSA_Tasker_Env and SSA_Tasker_VecEnv alike
+    (ssa_tasker_simple_2.py:324-354 of the reference): 'jones' pays 1 and ends the episode when every filter is within 30 km
+    (max_dpos < 3e4), ends it unpaid when one is 5000 km off; 'trinary' pays the mean of the two threshold counts (results.py:432);
+    'shaped' ends as 'jones' but pays 1 - `paid` (what the episode has paid so far) on the win, else +1/n on a `hit` (the action was
+    np.argmax(sigma_pos[i - 1])) and -1/n otherwise; any other reward type pays 0.  `last`: the step is the episode's last, which ends
+    it whatever the reward type.  A NaN max_dpos neither wins nor loses.
+    One row st [STAT_STRIDE] (a single env's step): scalars in, scalars out with the same bits, at a scalar's cost -- `last` is returned as
+    given, and `paid` may be a function, called on a win only (the env sums its reward history for it)."""
+    if st.ndim == 1:
+        if reward_type == 'trinary':          # (Python floats: the same IEEE double arithmetic, without numpy's scalar overhead)
+            return (st.item(_lib.STAT_CNT_LT_1E4) + st.item(_lib.STAT_CNT_LT_1E7)) / m / 2, last
+        mx = st.item(_lib.STAT_MAX_DPOS)
+        if reward_type == 'jones':
+            return (0.0, True) if mx > 5e6 else (1.0, True) if mx < 3e4 else (0.0, last)
+        if reward_type == 'shaped':
+            if mx > 5e6:
+                return 0.0, True
+            if mx < 3e4:
+                return 1.0 - (paid() if callable(paid) else paid), True
+            return (1.0 / n if hit else -1.0 / n), last
+        return 0.0, last
+    if reward_type == 'trinary':
+        return (st[:, _lib.STAT_CNT_LT_1E4] + st[:, _lib.STAT_CNT_LT_1E7]) / m / 2, last
+    mx = st[:, _lib.STAT_MAX_DPOS]
+    if reward_type not in ('jones', 'shaped'):
+        return np.zeros_like(mx), last
+    lost, won = mx > 5e6, mx < 3e4
+    done = lost | won | last
+    if reward_type == 'jones':
+        return np.where(won, 1.0, 0.0), done
+    return np.where(lost, 0.0, np.where(won, 1.0 - paid, np.where(hit, 1.0 / n, -1.0 / n))), done
+
+
+def draw_initial_state(rs, orbits, m, x_sigma, bulk, x_noise=None):
+    """(x_true, x_filter) of a reset from RandomState `rs`: per object a catalogue row, then six normals scaled by x_sigma -- the
+    reference's draw order (ssa_tasker_simple_2.py:206-209) -- or with `bulk` (config['device_rng']) all rows, then all normals: 1 ms
+    instead of 40 at m = 20 000.  The noise goes into `x_noise` when given."""
+    N = orbits.shape[0]
+    x_true = np.empty((m, 6))
+    noise = np.empty((m, 6)) if x_noise is None else x_noise
+    if bulk:
+        x_true[:] = orbits[rs.randint(low=0, high=N, size=m)]
+        noise[:] = rs.normal(size=(m, 6)) * x_sigma
+    else:
+        for j in range(m):
+            x_true[j] = orbits[rs.randint(low=0, high=N), :]
+            noise[j] = rs.normal(size=6) * x_sigma
+    return x_true, x_true + noise

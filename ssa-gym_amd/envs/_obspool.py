@@ -48,3 +48,46 @@ class ObsPool:
 
     def __len__(self):
         return len(self._bufs)
+
+
+class HostObs:
+    """the host side of a step's observation, for SSA_Tasker_Env and SSA_Tasker_VecEnv: the step kernel writes the observation straight
+    into host-mapped pinned memory (its epilogue's 'aer' block, or a second copy of the observation rows), `dest(k)` names that memory
+    for step k's launch and `hand_out()` returns what step() gives the caller.  With a pool (`pool_cap`): a buffer nobody holds, handed
+    out as a fresh array (ObsPool), or a copy of ring buffer k % depth when `pool_cap` buffers are out.  Without (pool_cap None): ring
+    buffer k % depth itself -- config['obs_zero_copy'] (intact until `depth` further steps), or a depth-1 ring: the ONE persistent array
+    of the reference's 'aer' observation (ssa_tasker_simple_2.py:362-363), refreshed in place.  f32: float32 buffers
+    (config['obs_dtype']: the kernel writes the host copy in single precision)."""
+
+    def __init__(self, n, shape, f32, depth, pool_cap):
+        import torch
+        self.f32 = bool(f32)
+        self.dtype = np.dtype(np.float32 if self.f32 else np.float64)
+        ring = [torch.zeros(n, dtype=torch.float32 if self.f32 else torch.float64).pin_memory() for _ in range(depth)]
+        self._ring = ring
+        self.ring_np = [b.numpy().reshape(shape) for b in ring]
+        self._ring_ptr = [b.data_ptr() for b in ring]
+        self._depth = depth
+        self.pool = None if pool_cap is None else ObsPool(n, shape, cap=int(pool_cap), dtype=self.dtype)
+        self._k, self._kp = 0, None
+
+    def dest(self, k):
+        """the host-mapped destination of step k's observation (call once per launch, before hand_out)"""
+        pool = self.pool
+        kp = self._kp = pool.acquire() if pool is not None else None
+        if kp is not None:
+            return pool.ptrs[kp]
+        k = self._k = k % self._depth
+        return self._ring_ptr[k]
+
+    def hand_out(self):
+        """the observation the last dest() named, once the launch has completed"""
+        if self._kp is not None:
+            return self.pool.hand_out(self._kp)     # fresh array, no copy: the buffer comes back when the consumer drops it
+        if self.pool is not None:
+            return self.ring_np[self._k].copy()     # (more than `pool_cap` observations alive at once)
+        return self.ring_np[self._k]
+
+    def cast(self, a):
+        """an observation that reached the host through a device-to-host copy, in the dtype step() hands out"""
+        return a.astype(np.float32) if self.f32 else a

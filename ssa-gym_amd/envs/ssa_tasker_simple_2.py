@@ -13,8 +13,7 @@ from datetime import timedelta
 import numpy as np
 
 from .. import _lib, host
-from . import transformations
-from ._config import kernel_consts, resolve_kernel_variant, resolve_sensors
+from ._config import draw_initial_state, resolve_config, reward_done
 from ._gymshim import Env, np_random, spaces
 from .results import error_failed
 
@@ -166,68 +165,32 @@ class SSA_Tasker_Env(Env):
                         'filter_error': 0, 'visible_objects': 0, 'object_visibility': 0, 'anees': 0,
                         'failed_filters': 0, 'plot_sigma_delta': 0, 'plot_rewards': 0, 'plot_anees': 0,
                         'plot_actions': 0, 'all_true_obs': 0, 'plot_visibility': 0, 'predict method': 0}
-        # ---- simulation configuration (:81-96)
+        # ---- simulation and filter configuration (:81-118), the sensor network, the kernel constants and the observation options:
+        # envs/_config.py resolves them for this env and SSA_Tasker_VecEnv alike
+        c = resolve_config(config)
         self.t_0 = config['t_0']
-        self.dt = config['time_step']
-        self.n = config['steps']
-        self.m = config['rso_count']
-        self.obs_limit = np.radians(config['obs_limit'])
+        self.dt, self.n, self.m = c.dt, c.n, c.m
         self.obs_returned = config['obs_returned']
         self.reward_type = config['reward_type']
         self.orbits = config['orbits']
-        self.obs_lla = np.array(config['observer']) * [host.deg2rad, host.deg2rad, 1]
-        self.obs_itrs = host.lla2ecef(self.obs_lla)
         self.update_interval = config['update_interval']
         self.i = 0
-        # ---- filter configuration (:97-118)
-        self.obs_type = config['obs_type']
-        if self.obs_type == 'aer':
-            self.z_sigma = config['z_sigma'] * np.array([host.arcsec2rad, host.arcsec2rad, 1])
-        elif self.obs_type == 'xyz':
-            self.z_sigma = np.asarray(config['z_sigma'], dtype=np.float64)
-        else:
-            print('Invalid Observation Type: ' + str(config['obs_type']))
-            raise SystemExit
-        self.x_sigma = np.array(config['x_sigma'])
-        self.Q = host.Q_discrete_white_noise(dim=2, dt=self.dt, var=config['q_sigma'] ** 2, block_size=3,
-                                             order_by_dim=False)
+        self.obs_type = c.obs_type
         self.fx, self.hx = config['fx'], config['hx']
         self.mean_z, self.residual_z, self.msqrt = config['mean_z'], config['residual_z'], config['msqrt']
         self.alpha, self.beta, self.kappa = config['alpha'], config['beta'], config['kappa']
-        # operator plug points -> fused kernel variant (no CPU fallback for foreign callables)
-        self._model, propagator = resolve_kernel_variant(config)
-        # ---- arrays (:120-161)
-        if config['P_0'] is None:
-            self.P_0 = np.copy(np.diag(self.x_sigma ** 2))
-        else:
-            self.P_0 = np.copy(config['P_0'])
-        if config['R'] is None:
-            self.R = np.diag(self.z_sigma ** 2)
-        else:
-            self.R = np.copy(config['R'])
-        # ---- sensor network (EXTENSION, config['observers']: DESIGN.md section 8c).  Sensor 0 is the PRIMARY sensor: it is the env's
-        # observer (obs_lla, obs_limit, z_sigma, R), and the 'aer' observation, the visibility helpers and the agents' scores use its site
-        net = resolve_sensors(config)
-        self.n_sensor = 1 if net is None else len(net['sites'])
-        if net is not None:
-            S = self.n_sensor
-            self.sensor_lla = np.array(net['sites']) * [host.deg2rad, host.deg2rad, 1]
-            self.sensor_obs_limit = np.radians(net['obs_limit']) if net['obs_limit'] is not None else np.full(S, self.obs_limit)
-            if net['z_sigma'] is not None:
-                unit = np.array([host.arcsec2rad, host.arcsec2rad, 1]) if self.obs_type == 'aer' else 1.0
-                self.sensor_z_sigma = np.array([z * unit for z in net['z_sigma']])
-                self.sensor_R = np.array([np.diag(z ** 2) for z in self.sensor_z_sigma])
-            else:
-                self.sensor_z_sigma = np.tile(self.z_sigma, (S, 1))
-                self.sensor_R = np.tile(self.R, (S, 1, 1))
-            self.obs_lla, self.obs_limit = self.sensor_lla[0], self.sensor_obs_limit[0]
-            self.obs_itrs = host.lla2ecef(self.obs_lla)
-            self.z_sigma, self.R = self.sensor_z_sigma[0], np.copy(self.sensor_R[0])
+        self._model = c.model
+        self.x_sigma, self.Q, self.P_0 = c.x_sigma, c.Q, c.P_0
+        # (a sensor network, config['observers'] -- DESIGN.md section 8c: sensor 0 is the PRIMARY sensor, the env's observer (obs_lla,
+        # obs_limit, z_sigma, R); the 'aer' observation, the visibility helpers and the agents' scores use its site)
+        self.z_sigma, self.R = c.z_sigma, c.R
+        self.obs_lla, self.obs_itrs, self.obs_limit = c.obs_lla, c.obs_itrs, c.obs_limit
+        self.n_sensor = c.n_sensor
+        if c.net is not None:
+            self.sensor_lla, self.sensor_obs_limit = c.net.lla, c.net.obs_limit
+            self.sensor_z_sigma, self.sensor_R = c.net.z_sigma, c.net.R
         self.time = [self.t_0 + (timedelta(seconds=self.dt) * i) for i in range(self.n)]
-        if config.get('trans_matrix') is not None:
-            self.trans_matrix = np.asarray(config['trans_matrix'], dtype=np.float64).reshape(-1, 3, 3)
-        else:
-            self.trans_matrix = transformations.trans_matrix_table(self.t_0, self.dt, self.n)
+        self.trans_matrix = c.trans
         self.x_noise = np.empty(shape=(self.m, 6))
         self.filters = []   # the reference keeps one filterpy object per RSO; state lives in HBM here
         self.rewards = np.empty(self.n)
@@ -244,49 +207,35 @@ class SSA_Tasker_Env(Env):
         self.S = np.empty((self.n,) + sens + (self.m, 3, 3)) if self.n * self.m * self.n_sensor <= (1 << 22) else None
         # ---- spaces (:163-177)
         self.action_space = spaces.MultiDiscrete([self.m] * self.n_sensor) if self.n_sensor > 1 else spaces.Discrete(self.m)
-        if self.obs_returned == 'flatten':
-            shp = (self.m * 12,)
-        elif self.obs_returned == 'aer':
-            shp = (self.m * 4,)
+        if self.obs_returned == 'aer':
             self.observation = np.zeros(self.m * 4)
-        else:
-            shp = (self.m, 12)
-        # config['obs_dtype'] = 'float64' (default, the reference's) | 'float32' (EXTENSION): the observation handed to the host in single
-        # precision -- the step kernel writes its host-facing copy that way (SSA_LAUNCH_MIRROR_F32): half the bytes over PCIe, for consumers
-        # that cast to float32 anyway (every RL framework does).  The device-resident history and everything computed stay float64.
-        self._obs_f32 = np.dtype(config.get('obs_dtype', np.float64)) == np.float32
-        if np.dtype(config.get('obs_dtype', np.float64)) not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise ValueError("config['obs_dtype'] must be float64 or float32")
-        self.observation_space = spaces.Box(low=np.full(shp, -np.inf), high=np.full(shp, np.inf), dtype=np.float32 if self._obs_f32 else np.float64)
+        # (config['obs_dtype'] = 'float32': the observation reaches the host in single precision; the device-resident history and
+        # everything computed stay float64)
+        self._obs_f32 = c.obs_f32
+        self.observation_space = c.obs_space
         # ---- device engine
         hist = config.get('history', 'auto')
         bytes_per_step = self.m * (6 + 6 + 36 + 12 + 4) * 8
         if hist == 'auto':
             hist = 'full' if self.n * bytes_per_step <= 64 * 2 ** 30 else 2
         self._H = self.n if hist == 'full' else max(2, int(hist))
-        self._consts, _ = kernel_consts(config, self.Q, self.R, self.dt, self.obs_limit, self.obs_lla)
-        # the other sensors' sites as kernel constants (their visibility helpers)
-        self._sensor_consts = [self._consts] + [kernel_consts(config, self.Q, self.sensor_R[k], self.dt, self.sensor_obs_limit[k],
-                                                              self.sensor_lla[k])[0] for k in range(1, self.n_sensor)]
+        self._consts, self._sensor_consts = c.consts, c.sensor_consts
         self._engine = None
         self._device_rng = bool(config.get('device_rng', False))
-        # config['storage_layout'] = None (default) | 'regime': how the engine STORES the objects (reset()); invisible but for speed
-        self._storage_layout = config.get('storage_layout', None)
-        if self._storage_layout not in (None, 'regime'):
-            raise ValueError("config['storage_layout'] must be None or 'regime', not %r" % (self._storage_layout,))
+        self._storage_layout = c.storage_layout      # (how the engine STORES the objects: reset())
         self._obs_buffers = config.get('obs_buffers', 2)
         # step() hands out a FRESH array per call for the 'flatten' and (m, 12) observations, as the reference does (:360-366: `.flatten()` /
         # a row of the history that no later step overwrites) -- a consumer may keep it as long as it likes (replay buffers, sample
         # collectors, GAE targets).  config['obs_zero_copy'] = True (opt-in): a VIEW of the host-mapped ring the kernel writes, valid until
         # `obs_buffers` (default 2) further steps have been taken -- no 1.9 MB host copy per step at 20 000 objects
-        self._obs_zero_copy = bool(config.get('obs_zero_copy', False))
+        self._obs_zero_copy = c.obs_zero_copy
         self._obs_pool_cap = config.get('obs_pool', 64)      # (pinned buffers that may be out with the consumer at once; beyond: copies)
         # the persistent closed loop's bound on any wait inside the launch (100 MHz ticks; 0 = the library's 2 s)
         self._loop_wait_ticks = int(config.get('closed_loop_wait_ticks', 0))
         self._loop_debug_withhold = False
-        # config['obs_device'] = True (opt-in, for policies that live on the GPU): step() returns the observation as a CUDA tensor
-        # -- a view of the device-resident history slot ('aer': of the persistent (4 m,) block) -- and nothing crosses PCIe
-        self._obs_device = bool(config.get('obs_device', False))
+        # config['obs_device'] = True: step() returns the observation as a CUDA tensor -- a view of the device-resident history slot
+        # ('aer': of the persistent (4 m,) block) -- and nothing crosses PCIe
+        self._obs_device = c.obs_device
         # run_agent(): the persistent closed-loop kernel (one launch per chunk) unless config['closed_loop'] == 'per_step'
         self._closed_loop_persistent = config.get('closed_loop', 'persistent') != 'per_step'
         self.np_random = None
@@ -319,29 +268,21 @@ class SSA_Tasker_Env(Env):
         # The observation reaches the host FROM INSIDE the step kernel: its epilogue writes the (az, el, range, trace P) block
         # ('aer') or a second copy of the observation rows (other modes) straight into host-mapped pinned memory, overlapped
         # with the other wavefronts' arithmetic -- no copy-engine pass behind the kernel (1.92 MB 'flatten' vector: 44 us).
-        # 'aer' hands out ONE persistent array refreshed in place, as the reference does (:362-363); the other modes alternate
-        # between TWO pinned arrays the kernel writes, and step() returns a COPY of the current one (the reference returns a fresh
-        # array per step) unless config['obs_zero_copy'] asks for the view itself, which stays intact until step i + 2 is taken
-        # (config['obs_buffers'] = k >= 2 deepens that ring).
+        # 'aer' hands out ONE persistent array refreshed in place, as the reference does (:362-363); the other modes a buffer nobody
+        # holds, returned as a fresh array (the reference returns a fresh array per step) unless config['obs_zero_copy'] asks for a
+        # view of the ring the kernel writes, which stays intact until step i + `obs_buffers` (default 2) is taken (envs/_obspool.py)
+        from ._obspool import HostObs
         aer = self.obs_returned == 'aer'
-        nobs = self.m * (4 if aer else 12)
-        nbuf = 1 if aer else max(2, int(self._obs_buffers))
-        f32 = self._obs_f32 and not self._obs_device        # (obs_device hands out the float64 device tensors themselves)
-        self._mirror_f32 = f32
-        self._obs_ring = [torch.zeros(nobs, dtype=torch.float32 if f32 else torch.float64).pin_memory() for _ in range(nbuf)]
-        shape = (nobs,) if self.obs_returned in ('aer', 'flatten') else (self.m, 12)
-        self._obs_ring_np = [b.numpy().reshape(shape) for b in self._obs_ring]
-        self._obs_ring_ptr = [b.data_ptr() for b in self._obs_ring]
+        self._mirror_f32 = self._obs_f32 and not self._obs_device      # (obs_device hands out the float64 device tensors themselves)
+        self._obs_host = HostObs(self.m * (4 if aer else 12), self.observation_space.shape, self._mirror_f32,
+                                 1 if aer else max(2, int(self._obs_buffers)),
+                                 None if (aer or self._obs_zero_copy or self._obs_device) else self._obs_pool_cap)
+        self._obs_pool = self._obs_host.pool
         # (numpy views and raw pointers of the mailboxes, taken once: each .numpy() / .data_ptr() costs the step a microsecond)
         self._upd_np, self._stats_np = self._upd_host.numpy(), self._stats_host.numpy()
         self._upd_ptr, self._stats_ptr = self._upd_host.data_ptr(), self._stats_host.data_ptr()
         if aer:
-            self.observation = self._obs_ring_np[0]
-        # default hand-out of the 'flatten' / (m, 12) observation: a buffer nobody holds, written by the kernel, returned as a fresh array,
-        # taken back when the consumer lets go of it (envs/_obspool.py) -- the reference's semantics without the copy
-        from ._obspool import ObsPool
-        self._obs_pool = None if (aer or self._obs_zero_copy or self._obs_device) else ObsPool(nobs, shape, cap=int(self._obs_pool_cap),
-                                                                                               dtype=np.float32 if f32 else np.float64)
+            self.observation = self._obs_host.ring_np[0]
         self.x_true = _History(self, e.x_true, self.m, (6,))
         self.x_filter = _History(self, e.x_filter, self.m, (6,))
         self.P_filter = _History(self, e.P_filter, self.m, (6, 6))
@@ -353,16 +294,7 @@ class SSA_Tasker_Env(Env):
         s = time.time()
         import torch
         m, n = self.m, self.n
-        x_true0 = np.empty((m, 6))
-        N = self.orbits.shape[0]
-        if self._device_rng:   # bulk draws (this mode is not seed-compatible with the reference anyway): 1 ms instead of 40 at m = 20 000
-            x_true0[:] = self.orbits[self.np_random.randint(low=0, high=N, size=m)]
-            self.x_noise[:] = self.np_random.normal(size=(m, 6)) * self.x_sigma
-        else:
-            for j in range(m):   # draw order of :206-209: (row, 6 normals) per object ...
-                x_true0[j] = self.orbits[self.np_random.randint(low=0, high=N), :]
-                self.x_noise[j] = self.np_random.normal(size=6) * self.x_sigma
-        x_filter0 = x_true0 + self.x_noise
+        x_true0, x_filter0 = draw_initial_state(self.np_random, self.orbits, m, self.x_sigma, self._device_rng, self.x_noise)
         # ... then n*m*3 normals (:219-221); RandomState.normal keeps its Box-Muller cache across
         # calls, so one bulk draw consumes the stream exactly like the reference's n*m size-3 draws
         if self._device_rng:
@@ -445,10 +377,6 @@ class SSA_Tasker_Env(Env):
         if self._engine is not None:
             self._engine.to_caller_order()
 
-    def _host_obs(self, arr):
-        """an observation that reached the host through a device-to-host copy, in the dtype step() hands out (config['obs_dtype'])"""
-        return arr.astype(np.float32) if getattr(self, "_mirror_f32", False) else arr
-
     def _obs_out(self, refresh_aer_dev=False):
         """the observation of the current step through the slow path (reset(), rollout(), run_agent()): a device-to-host copy (gathered into
         the env's object order while a storage layout is set: a reset does not cost the layout).  'aer' refreshes self.observation in
@@ -464,134 +392,76 @@ class SSA_Tasker_Env(Env):
             self.observation[:] = e.caller_rows(self._aer_dev.view(self.m, 4)).cpu().numpy().reshape(-1)
             return self.observation
         obs = e.caller_rows(e.obs[slot]).cpu().numpy()
-        return self._host_obs(obs.reshape(-1) if self.obs_returned == 'flatten' else obs)
+        return self._obs_host.cast(obs.reshape(-1) if self.obs_returned == 'flatten' else obs)
 
     def step(self, a):
-        if self.n_sensor > 1:
-            return self._step_sensors(a)
+        """step() of the reference (:265-367); with a sensor network (config['observers'] with S > 1 sites) `a` holds one object per
+        sensor, all different, and sensor s updates object a[s] with its own site, elevation mask, R and noise (ssa_env_step_sensors_f64)
+        in the same single launch"""
         step_s = time.time()
-        assert self.action_space.contains(a), "%r (%s) invalid" % (a, type(a))
-        self._argmax_sigma_prev = self._argmax_sigma
-        self._ring_head = None
-        self.i += 1
-        i = self.i
-        self.actions[i] = np.copy(a)
-        e = self._engine
-        s = time.time()
-        self.runtime['step prep'] += s - step_s
-        # propagate + predict + update + observations/metrics + statistics: ONE launch (:265-322; the step kernel's last wavefront folds
-        # the statistics, SSA_LAUNCH_FOLD_INSIDE).  The action travels by value in the parameter block; statistics, update record
-        # and the observation are written by the kernel straight into host-mapped pinned memory: ONE stream synchronisation, no copy
-        cur = self._stream                    # (the stream the engine was built in; torch.cuda.current_stream() costs 3 us per call,
-        #                                        and every step ends with a synchronisation, so later work in any stream sees its results)
-        aer = self.obs_returned == 'aer'
-        k = 0 if aer else i % len(self._obs_ring)
-        shaped = self.reward_type == 'shaped'      # needs np.argmax(sigma_pos[i - 1]) (:346): the arg-max slots of the one-launch path
-        if self._obs_device:
-            e.launch_step((i - 1) % e.H, i % e.H, i, action=int(a), aer_out=self._aer_dev.data_ptr() if aer else 0,
-                          stats_out=self._stats_ptr, upd_out=self._upd_ptr, stream=cur.cuda_stream,
-                          fast_stats=True, fold_inside=True, argmax_spos=shaped)
-            obs_np = self._aer_dev if aer else (e.obs[i % e.H].reshape(-1) if self.obs_returned == 'flatten' else e.obs[i % e.H])
+        S = self.n_sensor
+        if S == 1:
+            assert self.action_space.contains(a), "%r (%s) invalid" % (a, type(a))
         else:
-            pool = self._obs_pool
-            kp = pool.acquire() if pool is not None else None
-            e.launch_step((i - 1) % e.H, i % e.H, i, action=int(a),
-                          aer_out=self._obs_ring_ptr[0] if aer else 0,
-                          obs_mirror=0 if aer else (pool.ptrs[kp] if kp is not None else self._obs_ring_ptr[k]),
-                          stats_out=self._stats_ptr, upd_out=self._upd_ptr, stream=cur.cuda_stream,
-                          fast_stats=True, fold_inside=True, argmax_spos=shaped, mirror_f32=self._mirror_f32)
-            obs_np = self._obs_ring_np[k]
-        cur.synchronize()
-        rec = self._upd_np
-        self._stats = self._stats_np.copy()
-        self._argmax_sigma = int(self._stats[_lib.STAT_ARGMAX_SPOS])
-        t_dev = time.time()
-        self.runtime['perform predictions'] += t_dev - s
-        self._book_update(i, a, rec)
-        n_failed = int(self._stats[_lib.STAT_N_FAILED])
-        if n_failed != self._n_failed:
-            self._record_failures()
-        done = self._reward_done(i, a, self._stats, self._argmax_sigma_prev)
-        if i + 1 >= self.n:
-            done = True
-        # 'aer' hands out its ONE persistent array refreshed in place, as the reference does (:362-363: self.observation); the other
-        # modes a fresh copy unless config['obs_zero_copy']
-        if aer or self._obs_device or self._obs_zero_copy:
-            obs = obs_np
-        elif kp is not None:
-            obs = self._obs_pool.hand_out(kp)       # fresh array, no copy: the buffer comes back when the consumer drops it
-        else:
-            obs = obs_np.copy()                     # (more than `obs_pool` observations alive at once)
-        e_t = time.time()
-        self.runtime['Observations and Reward'] += e_t - t_dev
-        self.runtime['step'] += e_t - step_s
-        return obs, self._returned_reward(self.rewards[i]), done, {}
-
-    def _step_sensors(self, a):
-        """step() of a sensor network (config['observers'] with S > 1 sites): `a` holds one object per sensor, all different; sensor s
-        updates object a[s] with its own site, elevation mask, R and noise (ssa_env_step_sensors_f64), in the same single launch as step()"""
-        step_s = time.time()
-        if self._engine is None:
-            raise _lib.SsaHipError("no device state: a sensor network's step runs on the GPU only (no CPU fallback)")
-        if not self.action_space.contains(a):
-            raise AssertionError("%r (%s) invalid: one object in 0 .. %d per sensor (%d sensors)" % (a, type(a), self.m - 1, self.n_sensor))
-        a = np.asarray(a, dtype=np.int64)
-        if len(np.unique(a)) != len(a):
-            raise ValueError("step: two sensors tasked to the same object (%s)" % (a,))
+            if self._engine is None:
+                raise _lib.SsaHipError("no device state: a sensor network's step runs on the GPU only (no CPU fallback)")
+            if not self.action_space.contains(a):
+                raise AssertionError("%r (%s) invalid: one object in 0 .. %d per sensor (%d sensors)" % (a, type(a), self.m - 1, S))
+            a = np.asarray(a, dtype=np.int64)
+            if len(np.unique(a)) != len(a):
+                raise ValueError("step: two sensors tasked to the same object (%s)" % (a,))
         self._argmax_sigma_prev = self._argmax_sigma
         self._ring_head = None
         self.i += 1
         i = self.i
         self.actions[i] = a
         e = self._engine
-        cur = self._stream
+        s = time.time()
+        self.runtime['step prep'] += s - step_s
+        # propagate + predict + update + observations/metrics + statistics: ONE launch (:265-322; the step kernel's last wavefront folds
+        # the statistics, SSA_LAUNCH_FOLD_INSIDE).  The action travels by value in the parameter block (a network's actions in its sensor
+        # block); statistics, update records and the observation are written by the kernel straight into host-mapped pinned memory: ONE
+        # stream synchronisation, no copy
+        cur = self._stream                    # (the stream the engine was built in; torch.cuda.current_stream() costs 3 us per call,
+        #                                        and every step ends with a synchronisation, so later work in any stream sees its results)
         aer = self.obs_returned == 'aer'
-        k = 0 if aer else i % len(self._obs_ring)
-        shaped = self.reward_type == 'shaped'
-        kp = None
+        shaped = self.reward_type == 'shaped'      # needs np.argmax(sigma_pos[i - 1]) (:346): the arg-max slots of the one-launch path
         if self._obs_device:
-            e.launch_step_sensors((i - 1) % e.H, i % e.H, i, self._sensors, a, self._upd_s_ptr, aer_out=self._aer_dev.data_ptr() if aer else 0,
-                                  stats_out=self._stats_ptr, stream=cur.cuda_stream, fast_stats=True, fold_inside=True, argmax_spos=shaped)
-            obs_np = self._aer_dev if aer else (e.obs[i % e.H].reshape(-1) if self.obs_returned == 'flatten' else e.obs[i % e.H])
+            aer_out, mirror = (self._aer_dev.data_ptr() if aer else 0), 0
         else:
-            pool = self._obs_pool
-            kp = pool.acquire() if pool is not None else None
-            e.launch_step_sensors((i - 1) % e.H, i % e.H, i, self._sensors, a, self._upd_s_ptr, aer_out=self._obs_ring_ptr[0] if aer else 0,
-                                  obs_mirror=0 if aer else (pool.ptrs[kp] if kp is not None else self._obs_ring_ptr[k]),
+            dst = self._obs_host.dest(i)
+            aer_out, mirror = (dst, 0) if aer else (0, dst)
+        if S == 1:
+            e.launch_step((i - 1) % e.H, i % e.H, i, action=int(a), aer_out=aer_out, obs_mirror=mirror, stats_out=self._stats_ptr,
+                          upd_out=self._upd_ptr, stream=cur.cuda_stream, fast_stats=True, fold_inside=True, argmax_spos=shaped,
+                          mirror_f32=self._mirror_f32)
+        else:
+            e.launch_step_sensors((i - 1) % e.H, i % e.H, i, self._sensors, a, self._upd_s_ptr, aer_out=aer_out, obs_mirror=mirror,
                                   stats_out=self._stats_ptr, stream=cur.cuda_stream, fast_stats=True, fold_inside=True, argmax_spos=shaped,
                                   mirror_f32=self._mirror_f32)
-            obs_np = self._obs_ring_np[k]
         cur.synchronize()
         self._stats = self._stats_np.copy()
         self._argmax_sigma = int(self._stats[_lib.STAT_ARGMAX_SPOS])
-        for s in range(self.n_sensor):
-            self._book_sensor_update(i, s, int(a[s]), self._upd_s_np[s])
+        t_dev = time.time()
+        self.runtime['perform predictions'] += t_dev - s
+        if S == 1:
+            self._book_update(i, a, self._upd_np)
+        else:
+            for k in range(S):
+                self._book_update(i, a[k], self._upd_s_np[k], sensor=k)
         if int(self._stats[_lib.STAT_N_FAILED]) != self._n_failed:
             self._record_failures()
         done = self._reward_done(i, a, self._stats, self._argmax_sigma_prev)
-        if i + 1 >= self.n:
-            done = True
-        if aer or self._obs_device or self._obs_zero_copy:
-            obs = obs_np
-        elif kp is not None:
-            obs = self._obs_pool.hand_out(kp)
+        # 'aer' hands out its ONE persistent array refreshed in place, as the reference does (:362-363: self.observation); the other
+        # modes a fresh array unless config['obs_zero_copy']
+        if self._obs_device:
+            obs = self._aer_dev if aer else (e.obs[i % e.H].reshape(-1) if self.obs_returned == 'flatten' else e.obs[i % e.H])
         else:
-            obs = obs_np.copy()
-        self.runtime['step'] += time.time() - step_s
+            obs = self._obs_host.hand_out()
+        e_t = time.time()
+        self.runtime['Observations and Reward'] += e_t - t_dev
+        self.runtime['step'] += e_t - step_s
         return obs, self._returned_reward(self.rewards[i]), done, {}
-
-    def _book_sensor_update(self, i, s, a, rec):
-        """update record of sensor s at step i into the per-sensor histories"""
-        if rec[_lib.UPD_ACTION] >= 0:
-            self._upd_action[i, s] = a
-            self._z_true[i, s] = rec[_lib.UPD_Z_TRUE:_lib.UPD_Z_TRUE + 3]
-            if rec[_lib.UPD_OBS_TAKEN] == 1.0:
-                self._y[i, s] = rec[_lib.UPD_Y:_lib.UPD_Y + 3]
-                self._S_sel[i, s] = rec[_lib.UPD_S:_lib.UPD_S + 9].reshape(3, 3)
-                if self.S is not None:
-                    self.S[i, s, a] = self._S_sel[i, s]
-                self.sigmas_h[i, s] = rec[_lib.UPD_SIGMAS_H:_lib.UPD_SIGMAS_H + 39].reshape(13, 3)
-                self.obs_taken[i, s] = True
 
     def _single_sensor(self, what):
         if self.n_sensor > 1:
@@ -599,44 +469,30 @@ class SSA_Tasker_Env(Env):
                                       "use step()" % (what, self.n_sensor))
 
     # ------------------------------------------------------------------ per-step host bookkeeping
-    def _book_update(self, i, a, rec):
-        """update record of step i (:292-315) into the env's sparse histories"""
+    def _book_update(self, i, a, rec, sensor=None):
+        """update record of step i (:292-315) into the env's sparse histories (a sensor network: the record of `sensor`, into its column)"""
         if rec[_lib.UPD_ACTION] >= 0:
-            self._upd_action[i] = int(a)
-            self._z_true[i] = rec[_lib.UPD_Z_TRUE:_lib.UPD_Z_TRUE + 3]
+            a = int(a)
+            at = i if sensor is None else (i, sensor)
+            self._upd_action[at] = a
+            self._z_true[at] = rec[_lib.UPD_Z_TRUE:_lib.UPD_Z_TRUE + 3]
             if rec[_lib.UPD_OBS_TAKEN] == 1.0:
-                self._y[i] = rec[_lib.UPD_Y:_lib.UPD_Y + 3]
-                self._S_sel[i] = rec[_lib.UPD_S:_lib.UPD_S + 9].reshape(3, 3)
+                self._y[at] = rec[_lib.UPD_Y:_lib.UPD_Y + 3]
+                self._S_sel[at] = rec[_lib.UPD_S:_lib.UPD_S + 9].reshape(3, 3)
                 if self.S is not None:
-                    self.S[i, int(a)] = self._S_sel[i]
-                self.sigmas_h[i] = rec[_lib.UPD_SIGMAS_H:_lib.UPD_SIGMAS_H + 39].reshape(13, 3)
-                self.obs_taken[i] = True
+                    self.S[(i, a) if sensor is None else (i, sensor, a)] = self._S_sel[at]
+                self.sigmas_h[at] = rec[_lib.UPD_SIGMAS_H:_lib.UPD_SIGMAS_H + 39].reshape(13, 3)
+                self.obs_taken[at] = True
 
     def _reward_done(self, i, a, st, argmax_sigma_prev):
-        """reward / done of step i from its statistics (:324-354); fills self.rewards[i].  The statistics are taken over all objects
-        whatever the number of sensors; with a sensor network 'shaped' pays its +1/n if ANY sensor tasked np.argmax(sigma_pos[i - 1])"""
-        max_dpos = st[_lib.STAT_MAX_DPOS]
-        done = False
-        if self.reward_type == 'jones':
-            if max_dpos > 5e6:
-                done, self.rewards[i] = True, 0
-            elif max_dpos < 3e4:
-                done, self.rewards[i] = True, 1
-            elif i + 1 >= self.n:
-                done, self.rewards[i] = True, 0
-            else:
-                done, self.rewards[i] = False, 0
-        elif self.reward_type == 'trinary':   # results.py:432
-            self.rewards[i] = (st[_lib.STAT_CNT_LT_1E4] + st[_lib.STAT_CNT_LT_1E7]) / self.m / 2
-        elif self.reward_type == 'shaped':
-            if max_dpos > 5e6:
-                done, self.rewards[i] = True, 0
-            elif max_dpos < 3e4:
-                done, self.rewards[i] = True, 1 - np.sum(self.rewards[:i])
-            elif (a == argmax_sigma_prev) if self.n_sensor == 1 else bool(np.any(np.asarray(a) == argmax_sigma_prev)):
-                self.rewards[i] = 1 / self.n
-            else:
-                self.rewards[i] = -1 / self.n
+        """reward / done of step i from its statistics (:324-354, envs/_config.py: reward_done); fills self.rewards[i].  The statistics
+        are taken over all objects whatever the number of sensors; with a sensor network 'shaped' pays its +1/n if ANY sensor tasked
+        np.argmax(sigma_pos[i - 1])"""
+        if self.reward_type == 'shaped':     # (what the episode has paid: summed on a win only)
+            hit = (a == argmax_sigma_prev) if self.n_sensor == 1 else bool(np.any(np.asarray(a) == argmax_sigma_prev))
+            self.rewards[i], done = reward_done('shaped', st, hit, lambda: np.sum(self.rewards[:i]), i + 1 >= self.n, self.m, self.n)
+        else:
+            self.rewards[i], done = reward_done(self.reward_type, st, False, None, i + 1 >= self.n, self.m, self.n)
         return done
 
     def _returned_reward(self, r):
@@ -669,7 +525,7 @@ class SSA_Tasker_Env(Env):
             self._stats = stats[k]
             if int(stats[k][_lib.STAT_N_FAILED]) != self._n_failed:
                 self._record_failures(at_step=i)
-            done = self._reward_done(i, a, stats[k], self._argmax_sigma) or (i + 1 >= self.n)
+            done = self._reward_done(i, a, stats[k], self._argmax_sigma)
             self._argmax_sigma = int(stats[k][_lib.STAT_ARGMAX_SPOS])      # (-1 unless 'shaped' asked for it)
             actions.append(a)
             rewards.append(self._returned_reward(self.rewards[i]))
@@ -1164,6 +1020,15 @@ class SSA_Tasker_Env(Env):
         P_prev = e.P_filter[prev] if self.i >= 1 else None
         return device.agent_scores(e.x_true[cur], e.x_filter[cur], e.P_filter[cur], P_prev, M, self._consts)
 
+    def _lookahead_parts(self, what, covariances):
+        """the guards of lookahead() and lookahead_sensors(); the covariance parts to ask the launch for"""
+        from .. import engine as _engine
+        if self._engine is None:
+            raise _lib.SsaHipError("no device state: the lookahead runs on the GPU only (no CPU fallback)")
+        if self.i + 1 >= self.n:
+            raise ValueError("%s: the episode has no next step (i = %d, steps = %d)" % (what, self.i, self.n))
+        return _engine.HotPathEngine.LOOKAHEAD_PARTS if covariances else ()
+
     def lookahead(self, covariances=False):
         """One-step tasking lookahead (no reference counterpart; include/ssa_hip.h: ssa_lookahead_f64): for EVERY object j, what step(j)
         would produce for j at the next step, from the current state and in ONE launch -- nothing of the env changes, and nothing
@@ -1175,13 +1040,7 @@ class SSA_Tasker_Env(Env):
         and with covariances=True also x_prior [m, 6], P_prior [m, 6, 6] (the prediction every object gets) and P_post [m, 6, 6] (P_filter
         of the next step after step(j)).  The tensors are the env's lookahead buffers: the next call overwrites them."""
         self._single_sensor('lookahead')
-        from .. import engine as _engine
-        if self._engine is None:
-            raise _lib.SsaHipError("no device state: the lookahead runs on the GPU only (no CPU fallback)")
-        if self.i + 1 >= self.n:
-            raise ValueError("lookahead: the episode has no next step (i = %d, steps = %d)" % (self.i, self.n))
-        e = self._engine
-        want = _engine.HotPathEngine.LOOKAHEAD_PARTS if covariances else ()
+        e, want = self._engine, self._lookahead_parts('lookahead', covariances)
         r = e.launch_lookahead(self.i % e.H, self.i + 1, out=want, stream=self._stream.cuda_stream)
         res = {"score": r["score"].t(), "visible": r["visible"], "status": r["status"]}
         for k in want:
@@ -1199,15 +1058,9 @@ class SSA_Tasker_Env(Env):
             status  [S, m]     int32: the SSA_ST_* code the step would leave on j (a singular S is per sensor)
         and with covariances=True also x_prior [m, 6], P_prior [m, 6, 6] (the prediction, the same for every sensor) and P_post
         [S, m, 6, 6].  The tensors are the env's buffers: the next call overwrites them."""
-        from .. import engine as _engine
-        if self._engine is None:
-            raise _lib.SsaHipError("no device state: the lookahead runs on the GPU only (no CPU fallback)")
-        if self.i + 1 >= self.n:
-            raise ValueError("lookahead_sensors: the episode has no next step (i = %d, steps = %d)" % (self.i, self.n))
+        e, want = self._engine, self._lookahead_parts('lookahead_sensors', covariances)
         if getattr(self, "_look_sites", None) is None:   # (the network's sites; without observers the env's one observer)
             self._look_sites = self._sensors if self.n_sensor > 1 else host.make_sensor_params([self.obs_lla], [self.obs_limit], [self.R], 0)
-        e = self._engine
-        want = _engine.HotPathEngine.LOOKAHEAD_PARTS if covariances else ()
         r = e.launch_lookahead_sensors(self.i % e.H, self.i + 1, self._look_sites, out=want, stream=self._stream.cuda_stream)
         res = {"score": r["score"].permute(0, 2, 1), "visible": r["visible"], "status": r["status"]}
         for k in want:

@@ -11,9 +11,8 @@ consumes noise in a step (ssa_tasker_simple_2.py:301).
 """
 import numpy as np
 
-from .. import _lib, host
-from . import transformations
-from ._config import kernel_consts
+from .. import _lib
+from ._config import draw_initial_state, resolve_config, reward_done
 from ._gymshim import np_random, spaces
 
 
@@ -21,45 +20,31 @@ class SSA_Tasker_VecEnv:
     def __init__(self, config, num_envs, seed=0):
         import torch
         from .. import engine
-        from ._config import resolve_sensors
-        net = resolve_sensors(config)
-        if net is not None and len(net['sites']) > 1:
+        from ._obspool import HostObs
+        c = resolve_config(config)          # (as SSA_Tasker_Env: the same values, constants and options from the same config)
+        if c.n_sensor > 1:
             raise NotImplementedError("SSA_Tasker_VecEnv: not implemented for a sensor network (config['observers'] with %d sensors); "
-                                      "use SSA_Tasker_Env" % len(net['sites']))
-        self.E, self.m, self.n, self.dt = int(num_envs), config['rso_count'], config['steps'], config['time_step']
+                                      "use SSA_Tasker_Env" % c.n_sensor)
+        self.E, self.m, self.n, self.dt = int(num_envs), c.m, c.n, c.dt
         self._bulk_draws = bool(config.get('device_rng', False))
         self.obs_returned, self.reward_type = config['obs_returned'], config['reward_type']
         self.orbits = config['orbits']
-        self.x_sigma = np.array(config['x_sigma'])
-        self.obs_type = config['obs_type']
-        self.z_sigma = (config['z_sigma'] * np.array([host.arcsec2rad, host.arcsec2rad, 1]) if self.obs_type == 'aer'
-                        else np.asarray(config['z_sigma'], dtype=np.float64))
-        self.P_0 = np.diag(self.x_sigma ** 2) if config['P_0'] is None else np.copy(config['P_0'])
-        R = np.diag(self.z_sigma ** 2) if config['R'] is None else np.copy(config['R'])
-        if net is not None and net['z_sigma'] is not None:     # (config['observers'] with one site: that sensor's values)
-            self.z_sigma = net['z_sigma'][0] * (np.array([host.arcsec2rad, host.arcsec2rad, 1]) if self.obs_type == 'aer' else 1.0)
-            R = np.diag(self.z_sigma ** 2)
-        Q = host.Q_discrete_white_noise(dim=2, dt=self.dt, var=config['q_sigma'] ** 2, block_size=3, order_by_dim=False)
-        obs_lla = np.array(config['observer'] if net is None else net['sites'][0]) * [host.deg2rad, host.deg2rad, 1]
-        obs_limit = config['obs_limit'] if net is None or net['obs_limit'] is None else net['obs_limit'][0]
-        self._consts, model = kernel_consts(config, Q, R, self.dt, np.radians(obs_limit), obs_lla)   # as SSA_Tasker_Env
-        trans = (np.asarray(config['trans_matrix']) if config.get('trans_matrix') is not None
-                 else transformations.trans_matrix_table(config['t_0'], self.dt, self.n))
+        self.obs_type, self.x_sigma, self.z_sigma, self.P_0 = c.obs_type, c.x_sigma, c.z_sigma, c.P_0
+        self._consts = c.consts
         self._gen = torch.Generator(device="cuda").manual_seed(int(seed))
         self._zs = torch.as_tensor(self.z_sigma, dtype=torch.float64, device="cuda")
         z = torch.randn((self.E, self.n, 1, 3), dtype=torch.float64, device="cuda", generator=self._gen) * self._zs
-        self._eng = engine.HotPathEngine(self._consts, self.m, self.E, trans, z, history=2,
+        self._eng = engine.HotPathEngine(self._consts, self.m, self.E, c.trans, z, history=2,
                                          zn_stride_env=self.n * 3, zn_stride_time=3, zn_stride_obj=0)
         self._rng = [np_random(seed + e)[0] for e in range(self.E)]
         self.single_action_space = spaces.Discrete(self.m)
-        shp = {'flatten': (self.m * 12,), 'aer': (self.m * 4,)}.get(self.obs_returned, (self.m, 12))
-        self.single_observation_space = spaces.Box(low=np.full(shp, -np.inf), high=np.full(shp, np.inf), dtype=np.float64)
+        self.single_observation_space = c.obs_space
         self.num_envs = self.E
         self._aer = torch.zeros((self.E * self.m, 4), dtype=torch.float64, device="cuda")
         # host side of a step: time indices and actions leave from pinned staging (asynchronous copies), the statistics and the
         # observation vectors arrive in host-mapped pinned memory written by the kernels themselves (the 'aer' block by the step
         # kernel's epilogue, the observation rows as its second destination): one stream synchronisation per vector step, no
-        # device-to-host copy pass.  Two observation buffers alternate: what step k returned stays intact until step k + 2.
+        # device-to-host copy pass.
         self._ta_host = torch.zeros(2 * self.E, dtype=torch.int32).pin_memory()      # [time indices | actions]: one copy per step
         self._time_np, self._act_np = self._ta_host.numpy()[:self.E], self._ta_host.numpy()[self.E:]
         # up to 8 envs: time indices and actions travel BY VALUE in the launch's parameter block (no copy in front of the step, and
@@ -67,35 +52,26 @@ class SSA_Tasker_VecEnv:
         # wavefront that adds to them (SSA_LAUNCH_FOLD_INSIDE): ONE launch per vector step
         self._inline = self.E <= _lib.INLINE_ENVS
         self._stream = torch.cuda.current_stream()
-        # config['obs_device'] = True (opt-in, for policies that live on the GPU): step() returns the observations as ONE CUDA tensor
-        # [E, ...] -- a view of device memory the step kernel wrote -- and nothing but the statistics crosses PCIe
-        self._obs_device = bool(config.get('obs_device', False))
-        # step() returns a FRESH array (gym's vector envs copy their observation buffer by default, and so does the reference's single
-        # env for 'flatten'); config['obs_zero_copy'] = True: a view of the host-mapped ring the kernel writes, valid until step k + 2
-        self._obs_zero_copy = bool(config.get('obs_zero_copy', False))
+        # config['obs_device'] = True: step() returns the observations as ONE CUDA tensor [E, ...] -- a view of device memory the step
+        # kernel wrote.  Otherwise a FRESH array (gym's vector envs copy their observation buffer by default, and so does the reference's
+        # single env for 'flatten'), or with config['obs_zero_copy'] a view of the two-deep host-mapped ring the kernel writes, valid until
+        # step k + 2 (envs/_obspool.py)
+        self._obs_device = c.obs_device
         self._stats_host = torch.zeros((self.E, _lib.STAT_STRIDE), dtype=torch.float64).pin_memory()
         self._stats_np = self._stats_host.numpy()
         per = self.m * (4 if self.obs_returned == 'aer' else 12)
-        oshape = (self.E, self.m, 12) if self.obs_returned not in ('aer', 'flatten') else (self.E, per)
-        # config['obs_dtype'] = 'float32' (EXTENSION; default float64, the reference's): the host-facing observations in single precision,
-        # written that way by the step kernel (SSA_LAUNCH_MIRROR_F32) -- half of the 5 MB a vector step sends over PCIe
-        self._mirror_f32 = np.dtype(config.get('obs_dtype', np.float64)) == np.float32 and not self._obs_device
+        # config['obs_dtype'] = 'float32': the host-facing observations in single precision, written that way by the step kernel
+        # (SSA_LAUNCH_MIRROR_F32) -- half of the 5 MB a vector step sends over PCIe
+        self._mirror_f32 = c.obs_f32 and not self._obs_device
         if self._mirror_f32 and self.reward_type == 'shaped' and not self._eng.supports_argmax:
             raise ValueError("obs_dtype float32 with the 'shaped' reward needs rso_count % 4 == 0 (the one-launch statistics path)")
-        self._obs_ring = [torch.zeros(self.E * per, dtype=torch.float32 if self._mirror_f32 else torch.float64).pin_memory() for _ in range(2)]
-        self._obs_ring_np = [b.numpy().reshape(oshape) for b in self._obs_ring]
-        self._obs_ring_ptr = [b.data_ptr() for b in self._obs_ring]
-        # default hand-out: a buffer nobody holds, written by the kernel, returned as a fresh array and taken back when the consumer lets go
-        # of it (envs/_obspool.py) -- fresh-array semantics without the 5 MB copy per step
-        from ._obspool import ObsPool
-        self._obs_pool = None if (self._obs_zero_copy or self._obs_device) else ObsPool(self.E * per, oshape, cap=int(config.get('obs_pool', 16)),
-                                                                                            dtype=np.float32 if self._mirror_f32 else np.float64)
+        self._obs_host = HostObs(self.E * per, (self.E,) + c.obs_space.shape, self._mirror_f32, 2,
+                                 None if (c.obs_zero_copy or self._obs_device) else config.get('obs_pool', 16))
+        self._obs_pool = self._obs_host.pool
         # config['storage_layout'] = 'regime' (opt-in): every env's objects stored sorted by orbit regime (catalogue.regime_order_env;
         # HotPathEngine.set_layout with one permutation per env) -- actions, rewards and observations stay in the env's own numbering.  It pays
         # where the observations stay on the GPU (obs_device): host-facing rows would leave the kernel one by one instead of tile by tile
-        self._layout = config.get('storage_layout', None)
-        if self._layout not in (None, 'regime'):
-            raise ValueError("storage_layout: None or 'regime'")
+        self._layout = c.storage_layout
         if self._layout and self.m % 4:
             raise ValueError("storage_layout with several envs needs rso_count % 4 == 0")
         self._obs_dev_rows = None       # (layout + obs_device, 'flatten' / rows: the step kernel's second copy of the observation, at the caller's rows)
@@ -107,16 +83,7 @@ class SSA_Tasker_VecEnv:
 
     # ------------------------------------------------------------------
     def _draw(self, e):
-        rs, N = self._rng[e], self.orbits.shape[0]
-        if self._bulk_draws:      # config['device_rng']: bulk draws, 1 ms instead of 40 per env at m = 20 000 (auto-reset cost)
-            xt = self.orbits[rs.randint(low=0, high=N, size=self.m)]
-            return xt, xt + rs.normal(size=(self.m, 6)) * self.x_sigma
-        xt = np.empty((self.m, 6))
-        noise = np.empty((self.m, 6))
-        for j in range(self.m):   # reset() draw order of the reference (:206-209)
-            xt[j] = self.orbits[rs.randint(low=0, high=N), :]
-            noise[j] = rs.normal(size=6) * self.x_sigma
-        return xt, xt + noise
+        return draw_initial_state(self._rng[e], self.orbits, self.m, self.x_sigma, self._bulk_draws)
 
     def _reset_env(self, e, slot, draw=None):
         import torch
@@ -161,7 +128,7 @@ class SSA_Tasker_VecEnv:
                     self._obs_dev_rows[slot].copy_(e.caller_rows(e.obs[slot]))
                 rows = self._obs_dev_rows[slot]
             return rows.view(self.E, self.m * 12) if self.obs_returned == 'flatten' else rows.view(self.E, self.m, 12)
-        cast = (lambda a: a.astype(np.float32)) if self._mirror_f32 else (lambda a: a)
+        cast = self._obs_host.cast
         if self.obs_returned == 'flatten':
             return cast(e.caller_rows(e.obs[slot]).cpu().numpy().reshape(self.E, self.m * 12))
         if self.obs_returned == 'aer':
@@ -191,7 +158,6 @@ class SSA_Tasker_VecEnv:
         self.tick += 1
         sin, sout = (self.tick - 1) % 2, self.tick % 2
         aer = self.obs_returned == 'aer'
-        k = self.tick % 2
         shaped = self.reward_type == 'shaped'
         # 'shaped' needs np.argmax(sigma_pos[i - 1]) per env: from the arg-max slots of the one-launch path when every env is whole
         # tiles (rso_count % 4 == 0), through the three-launch exact statistics otherwise
@@ -199,9 +165,8 @@ class SSA_Tasker_VecEnv:
         if self._obs_device:
             aer_out, mirror = (self._aer.data_ptr() if aer else 0), (self._obs_dev_rows[sout].data_ptr() if (self._layout and not aer) else 0)
         else:
-            kp = self._obs_pool.acquire() if self._obs_pool is not None else None
-            dst = self._obs_pool.ptrs[kp] if kp is not None else self._obs_ring_ptr[k]
-            aer_out, mirror = (dst if aer else 0), (0 if aer else dst)
+            dst = self._obs_host.dest(self.tick)
+            aer_out, mirror = (dst, 0) if aer else (0, dst)
         if self._inline:
             cur = self._stream
             e.launch_step(sin, sout, 0, aer_out=aer_out, obs_mirror=mirror, stats_out=self._stats_host.data_ptr(), stream=cur.cuda_stream,
@@ -218,34 +183,10 @@ class SSA_Tasker_VecEnv:
         st = self._stats_np            # (host-mapped: the step kernel's folds wrote it; stable until the next launch)
         if shaped:
             self._argmax_prev = st[:, _lib.STAT_ARGMAX_SPOS].astype(np.int64)
-        mx = st[:, _lib.STAT_MAX_DPOS]
-        last = self.i + 1 >= self.n
-        if self.reward_type == 'trinary':
-            rewards = (st[:, _lib.STAT_CNT_LT_1E4] + st[:, _lib.STAT_CNT_LT_1E7]) / self.m / 2
-            dones = last
-        elif self.reward_type == 'jones':
-            lost, won = mx > 5e6, mx < 3e4
-            dones = lost | won | last
-            rewards = np.zeros(self.E)
-            rewards[won & ~lost] = 1.0
-        elif self.reward_type == 'shaped':
-            lost, won = mx > 5e6, mx < 3e4
-            hit = actions == argmax_prev
-            rewards = np.where(hit, 1.0 / self.n, -1.0 / self.n)
-            rewards[won] = 1.0 - self.rewards_sum[won]
-            rewards[lost] = 0.0
-            dones = lost | won | last
-        else:
-            rewards, dones = np.zeros(self.E), np.zeros(self.E, dtype=bool)
+        hit = (actions == argmax_prev) if shaped else False
+        rewards, dones = reward_done(self.reward_type, st, hit, self.rewards_sum, self.i + 1 >= self.n, self.m, self.n)
         self.rewards_sum += rewards
-        if self._obs_device:
-            obs = self._obs(sout)
-        elif self._obs_zero_copy:
-            obs = self._obs_ring_np[k]
-        elif kp is not None:
-            obs = self._obs_pool.hand_out(kp)       # fresh array, no copy
-        else:
-            obs = self._obs_ring_np[k].copy()       # (more than `obs_pool` observations alive at once)
+        obs = self._obs(sout) if self._obs_device else self._obs_host.hand_out()
         infos = [{} for _ in range(self.E)]
         if dones.any():   # auto-reset in place; the returned observation of a finished env is its new first one
             for d in np.where(dones)[0]:

@@ -1065,6 +1065,7 @@ def test_float32_observations_are_the_float64_ones_rounded(envs, mode):
     assert ub[0].dtype == np.float32 and np.array_equal(ua[0].astype(np.float32), ub[0])
     va = SSA_Tasker_VecEnv(dict(cfg), num_envs=3, seed=2)
     vb = SSA_Tasker_VecEnv(dict(cfg, obs_dtype=np.float32), num_envs=3, seed=2)
+    assert vb.single_observation_space.dtype == np.float32 and va.single_observation_space.dtype == np.float64
     for k in range(6):
         ra, rb = va.step([k, k + 1, k + 2]), vb.step([k, k + 1, k + 2])
         assert rb[0].dtype == np.float32 and np.array_equal(ra[0].astype(np.float32), rb[0]) and np.array_equal(ra[1], rb[1])
