@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the ssa-gym hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--objects M] [--propagator fg|elements] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--objects M] [--propagator fg|elements] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one call of the reference's SSA_Tasker_Env.step() (ssa_tasker_simple_2.py:243-367)
@@ -18,9 +18,16 @@ reward statistics (parallel.py).  `value` = 20 000-object env-steps per second s
 
 `value` and `ms_per_step` time exactly the K steps after the warm-up, between two fences.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (the fused step kernel)
-against HBM; `cpu_baseline` times the single-threaded C oracle (a port of the reference's
-per-object loop; the reference's numba/filterpy stack is not installable here) on the host.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints the line: nothing else.  Everything else the line can carry runs only
+with --full (its `roofline`, `rollout`, `cpu_baseline`, `cpu_baseline_all_cores` and
+`episode_failures` are null without it, and the N=1 legs are absent): `roofline` prices the
+dominant kernel (the fused step kernel) against HBM over a whole episode of launches of its own;
+`cpu_baseline` times the single-threaded C oracle (a port of the reference's per-object loop; the
+reference's numba/filterpy stack is not installable here) on the host; `rollout` and the legs
+(fg, j2, elements, resample, caller_order, closed loop, gym API, vector env) measure other entry
+points and variants on the same workload.  --no-legs, --no-cpu-baseline and --rollout 0 trim a
+--full run.
 """
 import argparse
 import json
@@ -608,9 +615,12 @@ def main():
     ap.add_argument("--propagator", default="hybrid", choices=["hybrid", "fg", "elements", "j2"],
                     help="hybrid (the env default: behaviour-faithful) / fg / elements: two-body Farnocchia (parity-checked); "
                          "j2: J2+RK4 extension (no reference counterpart)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything it does not need: the roofline of the dominant kernel, the rollout, "
+                         "the N=1 legs, the CPU baselines and the episode failure counts (a plain run measures the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full runs: skip the CPU baselines and the episode failure counts")
     ap.add_argument("--rollout", type=int, default=60,
-                    help="steps per launch of the additional open-loop rollout measurement (0 = skip); never `value`")
+                    help="--full runs: steps per launch of the additional open-loop rollout measurement (0 = skip); never `value`")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the N-rank launch path (gloo, no GPU, no step arithmetic); never a measurement")
     ap.add_argument("--payload", default="trace", choices=["trace", "aer"],
@@ -618,7 +628,7 @@ def main():
                          "covariance-trace obs\") or the four-column (az, el, range, trace P) block of the 'aer' observation mode")
     ap.add_argument("--eager-sharded", action="store_true",
                     help="sharded runs: enqueue every step from the host (default: hipGraph replay of whole units of steps)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the additional N=1 legs (j2, elements, resample, gym_api, closed_loop)")
+    ap.add_argument("--no-legs", action="store_true", help="--full runs: skip the additional N=1 legs (j2, elements, resample, gym_api, closed_loop)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
@@ -887,7 +897,7 @@ def main():
     # ---- dominant kernel, timed live with events on the launch stream: K back-to-back launches
     # of the fused step kernel alone (no statistics kernel, no collective)
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # whole steps exactly as in the timed region, back to back; launch k of the dominant kernel is timed by the
         # HIP event pair bound to that dispatch (on the launch stream)
         nl = min(ep_len - 1, _lib.PROFILE_SLOTS)   # one whole 479-step episode, whatever --steps was
@@ -931,7 +941,7 @@ def main():
     # launch -- what an open-loop schedule such as this protocol's round-robin allows (state resident in LDS across
     # the steps of a launch; every step's outputs still written)
     roll = None
-    if rank == 0 and world == 1 and not use_dist and args.rollout > 0:
+    if rank == 0 and world == 1 and not use_dist and args.full and args.rollout > 0:
         R = args.rollout
 
         def roll_steps(n):      # (the rollout launches keep the engine's storage layout)
@@ -956,7 +966,7 @@ def main():
     # the J2 extension (BASELINE config 3's "J2 on"), the reference-operation-order propagator, the redraw variant of
     # predict() (the UKF default is parity-unpinned: filterpy is absent), and the gym API with the host in the loop
     legs = {}
-    if rank == 0 and world == 1 and not use_dist and not args.no_legs:
+    if rank == 0 and world == 1 and not use_dist and args.full and not args.no_legs:
         Kl, Wl = min(max(K, 200), 1000), min(max(W, 50), 100)   # (legs: at least 200 steps per timed block)
         for name, kw in (("fg", dict(propagator="fg")), ("hybrid", dict(propagator="hybrid")), ("j2", dict(propagator="j2")),
                          ("elements", dict(propagator="elements")), ("resample", dict(propagator=args.propagator, resample=True))):
@@ -1012,7 +1022,7 @@ def main():
             legs["vec_env_device_obs"]["caller_order"] = vec_env_rate(m, obs_device=True)["value"]
 
     cpu, cpu_all, ep_fail = None, None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # reported at N=1 only
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:   # reported at N=1 only
         cpu = cpu_baseline(m)
         cpu_all = cpu_baseline(m, budget_s=8.0, all_cores=True)
         if not args.no_legs:

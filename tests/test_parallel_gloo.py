@@ -316,7 +316,7 @@ def test_sharded_hip_env_world2_shares_one_gpu(cols, exchange, unit):
 def test_bench_two_ranks_rehearsal_on_one_gpu(extra):
     """`python bench.py --gpus 2` end to end with the HIP engine in both ranks (SSA_BENCH_REHEARSAL=1: the ranks share cuda:0 and
     gloo carries the collectives -- the launcher, the warm-up probe of where the all-gather runs, the timed blocks with MAX over
-    ranks, the roofline leg on rank 0 while rank 1 waits, the closing barrier).  The rate it prints is NOT a measurement."""
+    ranks, the roofline leg of --full on rank 0 while rank 1 waits, the closing barrier).  The rate it prints is NOT a measurement."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
@@ -327,7 +327,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(extra):
         env["SSA_ALLGATHER"] = "peer"
     # (`fg`: the variant whose filters survive whole episodes -- how many timed blocks a run takes, and so how far into an episode it gets,
     # depends on the box; the behaviour-faithful default loses filters late in an episode by design and would make `failed_filters` a coin)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--objects", "4000", "--propagator", "fg"] + extra,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--objects", "4000", "--propagator", "fg", "--full"] + extra,
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
