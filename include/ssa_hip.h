@@ -547,6 +547,34 @@ int ssa_env_step_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_
 int ssa_lookahead_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_sensor_params *s_host,
                               const ssa_lookahead_out *out, void *stream);
 
+/* ---------------------------------------------------------------- visibility screen of a synthetic orbit catalogue
+ * catalogue._accepted (orbit_gen.py's acceptance rule) for n candidate element sets, the observer generalised to a network of
+ * n_site ground sites.  Candidate c = elements[c] = (a, ecc, inc, raan, argp, nu) (m, -, rad) is propagated by Kepler's equation
+ * (12 Newton steps from E = M + e sin M) to t = step * i for i < n_time and rotated to ITRS by trans[i].  Sample i passes the
+ * altitude test if |x| - WGS84_A (1 - WGS84_F sin^2 lat) > min_alt, and is visible if asin(up_s / |x - obs_itrs_s|) >= el_min_s for
+ * ANY site s (one site: exactly _accepted).  With worst = the longest run of consecutive invisible samples:
+ *   accept[c] = every sample passes the altitude test && (every sample visible
+ *               || (some sample in [0, first) visible && worst < max_gap))
+ *   worst_gap[c] = worst (optional); flags[c] = bit 0 altitude ok, bit 1 visible in [0, first), bit 2 always visible (optional).
+ * Refused before any launch (SSA_E_INVALID): n < 0, n_time < 1, n_site outside 1 .. SSA_MAX_SENSORS, first < 0, and with n > 0
+ * NULL elements / trans / sites / accept.  n == 0 launches nothing. */
+typedef struct ssa_screen_params {
+    int64_t n;                 /* candidates */
+    int32_t n_time;            /* samples per candidate (T) */
+    int32_t n_site;            /* S */
+    double step;               /* seconds between samples */
+    double min_alt;            /* altitude floor [m] */
+    int32_t first;             /* first-window length [samples] */
+    int32_t max_gap;           /* a run of max_gap invisible samples rejects [samples] */
+    const double *elements;    /* [n][6] */
+    const double *trans;       /* [n_time][3][3] GCRS -> ITRS, row-major (trans_matrix_table) */
+    const double *sites;       /* [n_site][13]: enu[9] (row-major, host.enu_matrix), obs_itrs[3] [m], el_min [rad] */
+    uint8_t *accept;           /* [n] */
+    int32_t *worst_gap;        /* [n] or NULL */
+    uint8_t *flags;            /* [n] or NULL */
+} ssa_screen_params;
+int ssa_catalogue_screen_f64(const ssa_screen_params *p, void *stream);
+
 /* ------------------------------------------------ all-gather by direct peer stores (SURVEY 8e "Collective")
  * The reference runs one env per process and has no exchange step; the sharded env of this library (one env's objects spread over the
  * GPUs of a node) reassembles every step's observation block + statistics words on every rank.  These two entry points do that without a

@@ -73,6 +73,14 @@ class ssa_sensor_params(C.Structure):
     ]
 
 
+class ssa_screen_params(C.Structure):
+    _fields_ = [
+        ("n", C.c_int64), ("n_time", C.c_int32), ("n_site", C.c_int32), ("step", C.c_double), ("min_alt", C.c_double),
+        ("first", C.c_int32), ("max_gap", C.c_int32), ("elements", c_dp), ("trans", c_dp), ("sites", c_dp),
+        ("accept", c_dp), ("worst_gap", c_dp), ("flags", c_dp),
+    ]
+
+
 # constants of include/ssa_hip.h
 E_INVALID, E_LAUNCH, E_UNSUPPORTED = -1, -2, -3
 ABI_VERSION = 23
@@ -145,6 +153,7 @@ SIGNATURES = {
     "ssa_nees_f64": (C.c_int, [c_dp, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_nis_f64": (C.c_int, [c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_chi2_contained_f64": (C.c_int, [c_dp, C.c_int64, C.c_double, C.c_double, c_dp, c_dp]),
+    "ssa_catalogue_screen_f64": (C.c_int, [C.POINTER(ssa_screen_params), c_dp]),
 }
 
 _lib = None

@@ -13,6 +13,8 @@ not the same random stream), including the exactly circular / equatorial rows th
 (farnocchia.py:278-309).  Workload synthesis for bench.py and the tests -- numpy, no device needed: Kepler's equation in closed
 elliptic form for the 96 sample times, the elevation of envs/transformations.py:330-352.
 """
+from datetime import datetime
+
 import numpy as np
 
 MU = 398600441800000.0
@@ -98,23 +100,35 @@ def synthetic_catalogue(n=20000, seed=0, visibility=True):
     key = (int(n), int(seed), bool(visibility))
     if key in _CACHE:
         return _CACHE[key].copy()
-    if visibility:      # the benchmark's catalogue ships as data (ten minutes of numpy to draw: LEO candidates pass the rule once in ~100)
-        import os
+    if visibility:      # the benchmark's catalogue ships as data (eleven minutes of numpy to draw: LEO candidates pass the rule about
+        import os       # once in 1 250; visible_catalogue draws the same rows with the screen on the GPU)
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "synthetic_catalogue_n%d_seed%d.npy" % key[:2])
         if os.path.exists(path):
             _CACHE[key] = np.load(path)
             return _CACHE[key].copy()
-    from datetime import datetime
     from .envs.transformations import trans_matrix_table
     from . import host
-    rs = np.random.RandomState(seed)
-    regime = rs.choice(5, size=n, p=[1 / 3, 1 / 3, 1 / 9, 1 / 9, 1 / 9])   # LEO MEO GEO Tundra Molniya (orbit_gen.py:53)
     step, duration = 150.0, 4 * 3600.0
     T = int(np.ceil(duration / step))
     times = step * np.arange(T)
     M_t = trans_matrix_table(datetime(2020, 5, 4, 0, 0, 0), step, T)
     obs_lla = np.array((38.828198, -77.305352, 20.0)) * [host.deg2rad, host.deg2rad, 1]
     enu, obs_itrs = host.enu_matrix(obs_lla), host.lla2ecef(obs_lla)
+
+    def screen(cand):
+        if not visibility:
+            return np.ones(len(cand[0]), dtype=bool)
+        return _accepted(*cand, M_t, times, enu, obs_itrs, np.radians(15.0), int(45 * 60 / step), int(1.5 * 3600 / step))
+    out = _draw(n, seed, screen)
+    _CACHE[key] = out
+    return out.copy()
+
+
+def _draw(n, seed, screen):
+    """orbit_gen.py's draw loop: a regime per row from RandomState(seed), then per regime batches of max(4096, 4 * missing) candidates
+    (_draw_elements) of which the first ones `screen(cand) -> bool[batch]` accepts fill the regime's rows, in order.  GCRS states [n, 6]."""
+    rs = np.random.RandomState(seed)
+    regime = rs.choice(5, size=n, p=[1 / 3, 1 / 3, 1 / 9, 1 / 9, 1 / 9])   # LEO MEO GEO Tundra Molniya (orbit_gen.py:53)
     el = np.empty((n, 6))
     for k in range(5):
         idx = np.where(regime == k)[0]
@@ -122,15 +136,94 @@ def synthetic_catalogue(n=20000, seed=0, visibility=True):
         while got < idx.size:
             batch = max(4096, 4 * (idx.size - got))
             cand = _draw_elements(rs, k, batch)
-            ok = (_accepted(*cand, M_t, times, enu, obs_itrs, np.radians(15.0), int(45 * 60 / step), int(1.5 * 3600 / step))
-                  if visibility else np.ones(batch, dtype=bool))
+            ok = screen(cand)
             sel = np.where(ok)[0][:idx.size - got]
             el[idx[got:got + sel.size]] = np.stack([c[sel] for c in cand], axis=1)
             got += sel.size
     a, ecc, inc, raan, argp, nu = el.T
-    out = np.ascontiguousarray(coe2rv_host(a * (1 - ecc ** 2), ecc, inc, raan, argp, nu))
-    _CACHE[key] = out
-    return out.copy()
+    return np.ascontiguousarray(coe2rv_host(a * (1 - ecc ** 2), ecc, inc, raan, argp, nu))
+
+
+DEFAULT_SITE = (38.828198, -77.305352, 20.0)    # orbit_gen.py's observer (env_config['observer'])
+MAX_SITES = 8
+
+
+def _site_table(sites, el_min_deg):
+    """[S, 13] rows of ssa_screen_params.sites for 1 .. 8 sites (lat, lon, h) in degrees, degrees, metres, and one elevation mask
+    (degrees) for all of them or one per site.  Anything else raises ValueError."""
+    from . import host
+    try:
+        arr = np.asarray(sites, dtype=np.float64)
+        lim = np.asarray(el_min_deg, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("sites must be a list of (lat, lon, h) and el_min_deg a number or one per site") from None
+    if arr.ndim != 2 or arr.shape[1] != 3 or not 1 <= arr.shape[0] <= MAX_SITES or not np.all(np.isfinite(arr)):
+        raise ValueError("sites must list 1 .. %d finite sites (lat, lon, h), got %r" % (MAX_SITES, sites))
+    S = arr.shape[0]
+    if lim.ndim == 0:
+        lim = np.full(S, float(lim))
+    if lim.shape != (S,) or not np.all(np.isfinite(lim)):
+        raise ValueError("el_min_deg must be one finite elevation mask (degrees) or one per site: %d" % S)
+    tab = np.empty((S, 13))
+    for s in range(S):
+        lla = arr[s] * [host.deg2rad, host.deg2rad, 1]
+        tab[s, :9] = host.enu_matrix(lla).reshape(9)
+        tab[s, 9:12] = host.lla2ecef(lla)
+        tab[s, 12] = np.radians(lim[s])
+    return tab
+
+
+def visible_catalogue(n, seed=0, *, sites=(DEFAULT_SITE,), el_min_deg=15.0, t_0=datetime(2020, 5, 4), step=150.0,
+                      duration=4 * 3600.0, first_window=45 * 60.0, max_gap=1.5 * 3600.0, min_altitude=300e3):
+    """n rows by orbit_gen.py's recipe, screened on the GPU for a network of 1 .. 8 sites (lat, lon, h; deg, deg, m) with elevation
+    masks el_min_deg (one for all or one per site), from epoch t_0: the draw loop of synthetic_catalogue (same RandomState(seed), same
+    regimes, batches and element draws) with _accepted replaced by the device screen (ssa_catalogue_screen_f64), so that with the
+    defaults the rows are those of synthetic_catalogue(n, seed).  A candidate is kept if over `duration`, sampled every `step` seconds,
+    it stays above min_altitude and is either always visible from some site, or visible within first_window and never out of sight
+    of every site for max_gap or longer.  Always draws (no shipped file, no cache); needs the library and a GPU."""
+    n, step, duration = int(n), float(step), float(duration)
+    if n < 0:
+        raise ValueError("n must be >= 0, got %d" % n)
+    if not np.isfinite(step) or step <= 0:
+        raise ValueError("step must be a positive number of seconds, got %r" % step)
+    if not np.isfinite(duration) or duration < step:
+        raise ValueError("duration must be at least one step (%r s), got %r" % (step, duration))
+    for name, v in (("first_window", first_window), ("max_gap", max_gap), ("min_altitude", min_altitude)):
+        if not np.isfinite(float(v)) or (name != "min_altitude" and float(v) < 0):
+            raise ValueError("%s must be a finite%s number, got %r" % (name, "" if name == "min_altitude" else " non-negative", v))
+    tab = _site_table(sites, el_min_deg)
+    T = int(np.ceil(duration / step))
+    first, gap = int(first_window / step), int(max_gap / step)
+    from .envs.transformations import trans_matrix_table
+    from . import _lib, device
+    import torch
+    M_t = trans_matrix_table(t_0, step, T)
+    _lib.load()
+    if not torch.cuda.is_available():
+        raise _lib.SsaHipError("visible_catalogue screens on the GPU (there is no CPU fallback): no device")
+    trans, site_tab = device.as_dev(M_t), device.as_dev(tab)
+
+    def screen(cand):
+        acc = device.catalogue_screen(device.as_dev(np.stack(cand, axis=1)), trans, site_tab, step, min_altitude, first, gap)
+        return acc.cpu().numpy().astype(bool)
+    return _draw(n, seed, screen)
+
+
+def catalogue_for_config(config, n=20000, seed=0, **kw):
+    """visible_catalogue for the sensors of an env_config dict: the sites of config['observers'] (else config['observer']), the masks of
+    config['sensor_obs_limit'] (else el_min_deg, default 15 deg -- not the env's obs_limit, -90 by default, which accepts everything)
+    and config['t_0'].  Keyword arguments override these and pass through to visible_catalogue."""
+    args = {}
+    if config.get('observers') is not None:
+        args['sites'] = [tuple(s) for s in config['observers']]
+        if config.get('sensor_obs_limit') is not None:
+            args['el_min_deg'] = list(config['sensor_obs_limit'])
+    elif config.get('observer') is not None:
+        args['sites'] = [tuple(config['observer'])]
+    if config.get('t_0') is not None:
+        args['t_0'] = config['t_0']
+    args.update(kw)
+    return visible_catalogue(n, seed, **args)
 
 
 def regime_order(x, tile=4, n_xcd=8, one_tile_limit=20480):

@@ -20,6 +20,7 @@
 #include "../../include/ssa_hip.h"
 #include "ssa_math.hpp"
 #include "ssa_conics.hpp"
+#include "ssa_screen.hpp"
 
 namespace ssa {
 
@@ -3892,6 +3893,15 @@ int ssa_visible_mask_at_f64(const double* x_true, const double* trans, const int
     if (n == 0) return SSA_OK;
     hipLaunchKernelGGL(visible_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, x_true, trans, make_geo(c), mask, el, n,
                        env_time, time_offset, n_time);
+    return launch_status();
+}
+
+int ssa_catalogue_screen_f64(const ssa_screen_params* p, void* stream)
+{
+    if (!p || p->n < 0 || p->n_time < 1 || p->n_site < 1 || p->n_site > SSA_MAX_SENSORS || p->first < 0) return SSA_E_INVALID;
+    if (p->n == 0) return SSA_OK;
+    if (!p->elements || !p->trans || !p->sites || !p->accept) return SSA_E_INVALID;
+    hipLaunchKernelGGL(catalogue_screen_kernel, dim3(nblk(p->n, SSA_SCREEN_WAVES)), dim3(64 * SSA_SCREEN_WAVES), 0, (hipStream_t)stream, *p);
     return launch_status();
 }
 

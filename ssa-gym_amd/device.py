@@ -138,6 +138,26 @@ def visible_mask(x_true, M, consts, want_el=False):
     return (mask, el) if want_el else mask
 
 
+
+def catalogue_screen(elements, trans, sites, step, min_alt, first, max_gap, want_gap=False, want_flags=False):
+    """catalogue._accepted for every candidate row of elements[n,6] (a, ecc, inc, raan, argp, nu), seen from a network of sites[S,13]
+    (enu 9 as host.enu_matrix, obs_itrs 3, el_min [rad]) through trans[T,3,3]: accept[n] uint8, plus worst_gap[n] int32 and flags[n]
+    uint8 (bit 0 altitude ok, bit 1 visible in the first window, bit 2 always visible) on request."""
+    lib = _lib.load()
+    n, dev = elements.shape[0], elements.device
+    accept = torch.empty(n, dtype=torch.uint8, device=dev)
+    gap = torch.empty(n, dtype=torch.int32, device=dev) if want_gap else None
+    flags = torch.empty(n, dtype=torch.uint8, device=dev) if want_flags else None
+    p = _lib.ssa_screen_params(n=n, n_time=trans.shape[0], n_site=sites.shape[0], step=float(step), min_alt=float(min_alt),
+                               first=int(first), max_gap=int(max_gap), elements=_chk(elements, "elements"), trans=_chk(trans, "trans"),
+                               sites=_chk(sites, "sites"), accept=_chk(accept, "accept", torch.uint8),
+                               worst_gap=_chk(gap, "worst_gap", torch.int32) if want_gap else None,
+                               flags=_chk(flags, "flags", torch.uint8) if want_flags else None)
+    _lib.check(lib.ssa_catalogue_screen_f64(C.byref(p), _stream()), "ssa_catalogue_screen_f64")
+    if not (want_gap or want_flags):
+        return accept
+    return (accept,) + ((gap,) if want_gap else ()) + ((flags,) if want_flags else ())
+
 def observe(x_true, x, P, obs=None, metrics=None):
     """O1/O2: observations() + error() -> obs[n,12], metrics[4,n]."""
     lib = _lib.load()

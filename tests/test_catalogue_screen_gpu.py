@@ -1,0 +1,152 @@
+"""The visibility screen of a synthetic catalogue on the MI355X (include/ssa_hip.h: ssa_catalogue_screen_f64; catalogue.visible_catalogue,
+catalogue_for_config).
+
+The ground truth is the numpy rule: catalogue._accepted for one site and its network restatement (test_catalogue_screen_host.screen_numpy,
+equal to _accepted bit for bit with one site).  The library is built with -ffp-contract=fast, so the kernel's intermediate values are not
+numpy's bits; the contract is equal decisions (accept, worst gap, flags) for every candidate whose numpy margin is at least 1e-9 rad of
+elevation and 1e-3 m of altitude at every sample.  The draw loop on top must then give the rows of the numpy path exactly."""
+from datetime import datetime
+
+import numpy as np
+import pytest
+
+from test_catalogue_screen_host import _SITES3, screen_numpy, site_rows
+
+pytestmark = pytest.mark.gpu
+
+EL_EPS, ALT_EPS = 1e-9, 1e-3
+
+
+@pytest.fixture(scope="module")
+def dev():
+    import torch
+    import ssa_gym_amd
+    from ssa_gym_amd import _lib, device
+    ssa_gym_amd.build()
+    _lib.load()
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return device
+
+
+def _site_tab(sites, masks):
+    return np.array([np.concatenate([enu.reshape(9), obs, [lim]]) for enu, obs, lim in site_rows(sites, masks)])
+
+
+def _compare(dev, cand, M_t, step, sites, masks, first, max_gap, min_alt=300e3):
+    """kernel against screen_numpy on the candidates `cand`; returns (n compared, n excluded by numpy's margin, n accepted)"""
+    el = np.stack(cand, axis=1)
+    acc, gap, flags = dev.catalogue_screen(dev.as_dev(el), dev.as_dev(M_t), dev.as_dev(_site_tab(sites, masks)), step, min_alt, first,
+                                           max_gap, want_gap=True, want_flags=True)
+    acc, gap, flags = acc.cpu().numpy().astype(bool), gap.cpu().numpy(), flags.cpu().numpy()
+    want = screen_numpy(*cand, M_t, step * np.arange(len(M_t)), site_rows(sites, masks), first, max_gap, min_alt)
+    close = (want[3] < EL_EPS) | (want[4] < ALT_EPS)
+    keep = ~close
+    for name, g, w in (("accept", acc, want[0]), ("worst_gap", gap, want[1]), ("flags", flags, want[2])):
+        bad = np.where(keep & (g != w))[0]
+        assert bad.size == 0, (name, bad[:10], g[bad[:10]], w[bad[:10]], want[3][bad[:10]], want[4][bad[:10]])
+    return len(acc), int(close.sum()), int(want[0].sum())
+
+
+def test_screen_matches_accepted_at_the_default_site(dev):
+    """50 000 candidates per regime at the default site, epoch and step: accept, worst_gap and flags equal numpy's"""
+    from ssa_gym_amd import catalogue
+    from ssa_gym_amd.envs.transformations import trans_matrix_table
+    M_t = trans_matrix_table(datetime(2020, 5, 4), 150.0, 96)
+    rs = np.random.RandomState(2024)
+    for k in range(5):
+        cand = catalogue._draw_elements(rs, k, 50000)
+        n, close, n_acc = _compare(dev, cand, M_t, 150.0, [catalogue.DEFAULT_SITE], [15.0], 18, 36)
+        print("regime %d: %d candidates, %d accepted, %d within numpy's margin" % (k, n, n_acc, close))
+        assert close <= 5
+
+
+def test_screen_matches_numpy_for_a_network(dev):
+    """3 sites with masks 15 / 10 / 20 deg, epoch 2012-06-01, step 120 s over 6 h (180 samples: three chunks of a wavefront)"""
+    from ssa_gym_amd import catalogue
+    from ssa_gym_amd.envs.transformations import trans_matrix_table
+    step, T = 120.0, int(np.ceil(6 * 3600.0 / 120.0))
+    M_t = trans_matrix_table(datetime(2012, 6, 1), step, T)
+    rs = np.random.RandomState(7)
+    total = 0
+    for k in range(5):
+        cand = catalogue._draw_elements(rs, k, 20000)
+        n, close, n_acc = _compare(dev, cand, M_t, step, _SITES3, [15.0, 10.0, 20.0], int(45 * 60 / step), int(1.5 * 3600 / step))
+        print("regime %d: %d candidates, %d accepted, %d within numpy's margin" % (k, n, n_acc, close))
+        assert close <= 5
+        total += n_acc
+    assert total > 0
+
+
+def test_visible_catalogue_gives_the_rows_of_the_numpy_path(dev):
+    """with the defaults, visible_catalogue draws synthetic_catalogue's rows exactly -- the shipped 20 000-row file included"""
+    import os
+    from ssa_gym_amd import catalogue
+    assert np.array_equal(catalogue.visible_catalogue(60, seed=3), catalogue.synthetic_catalogue(60, seed=3))
+    shipped = np.load(os.path.join(os.path.dirname(catalogue.__file__), "data", "synthetic_catalogue_n20000_seed0.npy"))
+    got = catalogue.visible_catalogue(20000, seed=0)
+    diff = np.where(np.any(got != shipped, axis=1))[0]
+    assert diff.size == 0, ("rows that differ from the shipped catalogue", diff[:10])
+
+
+def test_a_network_env_sees_its_catalogue(dev):
+    """a 3-site network (none of them the default site) given a catalogue screened for it sees every drawn object from some site within
+    the first 45 min; given the shipped catalogue (screened for the default site only) it does not"""
+    from ssa_gym_amd import catalogue
+    from ssa_gym_amd import envs as E
+
+    def cfg(orbits):
+        c = dict(E.env_config)
+        c.update(rso_count=200, steps=96, time_step=30.0, observers=_SITES3, sensor_obs_limit=[15.0, 10.0, 20.0], reward_type='trinary',
+                 obs_returned='flatten', seed=5, orbits=orbits)
+        return c
+
+    def unseen(orbits):
+        env = E.make('ssa_tasker_simple-v2', config=cfg(orbits))
+        env.reset()
+        seen = np.zeros(env.m, dtype=bool)
+        for i in range(86):
+            if i % 5 == 0:                   # every 150 s, the screen's samples 0 .. 17
+                for s in range(env.n_sensor):
+                    seen |= env.object_visibility(sensor=s)
+            env.step(np.array([0, 1, 2]))
+        return int((~seen).sum())
+
+    screened = catalogue.catalogue_for_config(cfg(None), n=2000, seed=1, step=150.0)
+    assert screened.shape == (2000, 6)
+    assert unseen(screened) == 0
+    n_shipped = unseen(catalogue.synthetic_catalogue(20000, seed=0))
+    print("objects of the shipped catalogue this network never sees in the first 45 min: %d of 200" % n_shipped)
+    assert n_shipped > 0
+
+
+def test_screen_edge_cases(dev):
+    """no candidates; a single sample; a set that is rejected in full; refused arguments"""
+    import torch
+    from ssa_gym_amd import _lib, catalogue
+    from ssa_gym_amd.envs.transformations import trans_matrix_table
+    M_t = trans_matrix_table(datetime(2020, 5, 4), 150.0, 96)
+    tab = dev.as_dev(_site_tab([catalogue.DEFAULT_SITE], [15.0]))
+    trans = dev.as_dev(M_t)
+    # n == 0: nothing launched, empty outputs; and visible_catalogue(0)
+    acc, gap, fl = dev.catalogue_screen(torch.empty((0, 6), dtype=torch.float64, device="cuda"), trans, tab, 150.0, 300e3, 18, 36,
+                                        want_gap=True, want_flags=True)
+    assert acc.numel() == gap.numel() == fl.numel() == 0
+    assert catalogue.visible_catalogue(0).shape == (0, 6)
+    rs = np.random.RandomState(3)
+    cand = tuple(np.concatenate(c) for c in zip(*(catalogue._draw_elements(rs, k, 2000) for k in range(5))))
+    # T == 1: one sample, first window of one sample
+    n, close, n_acc = _compare(dev, cand, M_t[:1], 150.0, [catalogue.DEFAULT_SITE], [15.0], 1, 36)
+    assert close <= 5 and 0 < n_acc < n
+    # everything rejected: an altitude floor above every orbit
+    el = dev.as_dev(np.stack(cand, axis=1))
+    acc, fl = dev.catalogue_screen(el, trans, tab, 150.0, 1e9, 18, 36, want_flags=True)
+    assert not acc.cpu().numpy().any() and not (fl.cpu().numpy() & 1).any()
+    n, close, n_acc = _compare(dev, cand, M_t, 150.0, [catalogue.DEFAULT_SITE], [15.0], 18, 36, min_alt=1e9)
+    assert n_acc == 0
+    # refused before any launch: 0 or 9 sites, no samples, a negative first window
+    for bad in (dict(sites=tab[:0]), dict(sites=tab.repeat(9, 1)), dict(trans=trans[:0]), dict(first=-1)):
+        kw = dict(trans=trans, sites=tab, first=18)
+        kw.update(bad)
+        with pytest.raises(_lib.SsaHipError):
+            dev.catalogue_screen(el, kw['trans'], kw['sites'].contiguous(), 150.0, 300e3, kw['first'], 36)
