@@ -153,7 +153,9 @@ SSA_DEV double atan2_fast(double y, double x)
     // pi/4 and pi/2 in two parts so that the folded-back angle keeps its last bit
     if (mid) r = 7.85398163397448278999e-01 + (r + 3.06161699786838301793e-17);
     if (swap) r = 1.57079632679489655800e+00 - (r - 6.12323399573676603587e-17);
-    if (__builtin_signbit(x)) r = 3.14159265358979311600e+00 - (r - 1.22464679914735317720e-16);   // (signed zeros as libm)
+    // (signed zeros as libm: x = -0 folds only the angle of y = +-0 to +-pi; beside any other y, r is already +-pi/2, and the two-part fold
+    // would round it one ulp up)
+    if (x < 0.0 || (__builtin_signbit(x) && !swap)) r = 3.14159265358979311600e+00 - (r - 1.22464679914735317720e-16);
     return __builtin_copysign(r, y);
 }
 

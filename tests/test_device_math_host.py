@@ -3,7 +3,11 @@ shimmed away, hardware reciprocal estimates emulated with their 2^-26-class erro
 own farnocchia.py produced.  What this covers without a GPU: the universal-variable solvers of SSA_PROP_FG (series / Halley
 and closed-form / Laguerre, incl. which lanes each one accepts), the strong-elliptic SSA_PROP_ELEMENTS chain with its
 refined-estimate divisions, bounded-argument sincos and the exactness requirements of the equatorial test, the third-order
-reciprocal refinements.  The GPU tests (-m gpu) then only have to show that the device executes the same arithmetic."""
+reciprocal refinements.  The host build cannot see what the device adds: the real v_rcp_f64 / v_rsq_f64 estimates, the
+library's -ffp-contract=fast, the wave votes.  Each test body here therefore takes a numpy-level backend (HostMath below);
+tests/test_device_math_gpu.py runs the same bodies, with the same bounds, on the device through the probe module
+tests/devmath/devmath.hip (compiled with the library's own flags -- test_devmath_probe_cross_compiles builds it without a GPU),
+adds the edges the shim cannot judge, and checks that no item's bits depend on what shares its wavefront."""
 import ctypes as C
 import os
 import subprocess
@@ -16,35 +20,112 @@ from conftest import golden
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-@pytest.fixture(scope="module")
-def hm(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("hostmath") / "libhostmath.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D_GNU_SOURCE", "-fPIC", "-shared", "-ffp-contract=off",
-                           "-I" + os.path.join(HERE, "hostmath"), "-o", so, os.path.join(HERE, "hostmath", "hostmath.cpp")])
-    return C.CDLL(so)
+DEVMATH_SRC = os.path.join(HERE, "devmath", "devmath.hip")
+DEVMATH_LIB = os.path.join(HERE, "devmath", "libdevmath.so")
+
+
+def build_devmath(force=False):
+    """the device-math probe, in-tree next to its source (it travels with the tree, as libssa_hip.so does), with the library's
+    hipcc flags; rebuilt when it is older than its source or the product headers"""
+    from ssa_gym_amd import _build
+    deps = [DEVMATH_SRC, os.path.join(_build.HERE, "csrc", "ssa_math.hpp"), os.path.join(_build.HERE, "csrc", "ssa_conics.hpp")]
+    if force or _build.stale(DEVMATH_LIB, deps):
+        _build.hipcc_shared(DEVMATH_SRC, DEVMATH_LIB)
+    return DEVMATH_LIB
 
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def _run(fn, x, dt, *pre):
-    x = np.ascontiguousarray(x, dtype=np.float64)
-    out = np.empty_like(x)
-    flag = np.zeros(len(x), dtype=np.int32)
-    fn(_p(x), C.c_long(len(x)), C.c_double(dt), *pre, _p(out), _p(flag))
-    return out, flag.astype(bool)
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+class HostMath:
+    """numpy-level backend over tests/hostmath (ctypes).  States x[n, 6] -> (y[n, 6], flag[n] bool); scalars elementwise."""
+
+    def __init__(self, lib):
+        self.lib = lib
+
+    def _states(self, fn, x, dt, *pre):
+        x = _f64(x)
+        out = np.empty_like(x)
+        flag = np.zeros(len(x), dtype=np.int32)
+        fn(_p(x), C.c_long(len(x)), C.c_double(dt), *pre, _p(out), _p(flag))
+        return out, flag.astype(bool)
+
+    def propagate(self, x, dt, prop):
+        return self._states(self.lib.hm_propagate, x, dt, C.c_int(prop))
+
+    def uv_fast(self, x, dt):
+        return self._states(self.lib.hm_uv_fast, x, dt)
+
+    def uv_general(self, x, dt):
+        return self._states(self.lib.hm_uv_general, x, dt)
+
+    def general_libm(self, x, dt):
+        return self._states(self.lib.hm_general_libm, x, dt)
+
+    def general_fast(self, x, dt):
+        return self._states(self.lib.hm_general_fast, x, dt)
+
+    def conic_lean(self, x, dt):
+        return self._states(self.lib.hm_conic_lean, x, dt)
+
+    def band(self, nu, ecc, q, tof):
+        nu, ecc, q = _f64(nu), _f64(ecc), _f64(q)
+        fast, libm = np.empty_like(nu), np.empty_like(nu)
+        self.lib.hm_band(_p(nu), _p(ecc), _p(q), C.c_long(len(nu)), C.c_double(tof), _p(fast), _p(libm))
+        return fast, libm
+
+    def log_pos(self, x):
+        x = _f64(x)
+        r = np.empty_like(x)
+        self.lib.hm_log_pos(_p(x), C.c_long(len(x)), _p(r))
+        return r
+
+    def sincos(self, x):
+        x = _f64(x)
+        s, c = np.empty_like(x), np.empty_like(x)
+        self.lib.hm_sincos_fast(_p(x), C.c_long(len(x)), _p(s), _p(c))
+        return s, c
+
+    def atan2(self, y, x):
+        y, x = _f64(y), _f64(x)
+        r = np.empty_like(x)
+        self.lib.hm_atan2_fast(_p(y), _p(x), C.c_long(len(x)), _p(r))
+        return r
+
+    def exp(self, x):
+        x = _f64(x)
+        r = np.empty_like(x)
+        self.lib.hm_exp_fast(_p(x), C.c_long(len(x)), _p(r))
+        return r
+
+    def recip(self, x):
+        x = _f64(x)
+        r, q = np.empty_like(x), np.empty_like(x)
+        self.lib.hm_recip(_p(x), C.c_long(len(x)), _p(r), _p(q))
+        return r, q
+
+
+@pytest.fixture(scope="module")
+def hm(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("hostmath") / "libhostmath.so")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D_GNU_SOURCE", "-fPIC", "-shared", "-ffp-contract=off",
+                           "-I" + os.path.join(HERE, "hostmath"), "-o", so, os.path.join(HERE, "hostmath", "hostmath.cpp")])
+    return HostMath(C.CDLL(so))
 
 
 def relnorm(a, b, sl):
     return np.linalg.norm((a - b)[:, sl], axis=1) / np.linalg.norm(b[:, sl], axis=1)
 
 
-@pytest.mark.parametrize("idt", range(5))
-def test_fg_universal_solvers_vs_reference_golden(hm, idt):
+def check_fg_universal_solvers_vs_reference_golden(mm, idt):
     g = golden("kepler_golden.npz")
     dt = float(g["dts"][idt])
-    y, ok = _run(hm.hm_propagate, g["x"], dt, C.c_int(1))
+    y, ok = mm.propagate(g["x"], dt, 1)
     assert ok.all()
     ref = g["y"][idt]
     inc = g["inter"][idt][:, 2]
@@ -53,13 +134,13 @@ def test_fg_universal_solvers_vs_reference_golden(hm, idt):
     assert relnorm(y, ref, slice(0, 3)).max() < 5e-10
     # which solver took which lane: every catalogue state at the env's step sizes is a series / Halley lane; at 5 400 s the
     # long-period orbits still are, at one day none is (closed-form / Laguerre for all)
-    _, handled = _run(hm.hm_uv_fast, g["x"], dt)
+    _, handled = mm.uv_fast(g["x"], dt)
     assert handled.all() if dt <= 150 else (0 < handled.sum() < len(handled) if dt < 8e4 else not handled.any())
-    yg, okg = _run(hm.hm_uv_general, g["x"], dt)
+    yg, okg = mm.uv_general(g["x"], dt)
     assert okg.all() and relnorm(yg, ref, slice(0, 3))[good].max() < 2e-12      # the general solver alone covers everything
 
 
-def test_fg_hyperbolic_and_near_parabolic_states(hm, oracle_ld):
+def check_fg_hyperbolic_and_near_parabolic_states(mm, oracle_ld):
     """diverged filter states (scaled velocities): every conic through the same equation, against the 80-bit oracle"""
     cat = golden("catalogue_subset.npy")
     rs = np.random.RandomState(0)
@@ -67,7 +148,7 @@ def test_fg_hyperbolic_and_near_parabolic_states(hm, oracle_ld):
         x = cat.copy()
         x[:, 3:] *= rs.uniform(lo, hi, size=len(x))[:, None]
         for dt in (20.0, 150.0):
-            y, ok = _run(hm.hm_propagate, x, dt, C.c_int(1))
+            y, ok = mm.propagate(x, dt, 1)
             ref = oracle_ld.propagate(x, dt)
             fin = np.isfinite(ref).all(1)
             assert ok[fin].all()
@@ -86,7 +167,7 @@ def _conic_states(rs, m):
     return x, ecc
 
 
-def test_conic_branches_lean_form_vs_restatements_and_oracle(hm, oracle_ld):
+def check_conic_branches_lean_form_vs_restatements_and_oracle(mm, oracle_ld):
     """What SSA_PROP_HYBRID (and the fallback of SSA_PROP_ELEMENTS) runs beyond the series solver -- kepler_conic_lean: the reference's
     anomaly chain with the orbit's orientation carried by the state's own unit vectors, the near-parabolic bands through genf:: --
     against (a) the libm-level restatement of farnocchia() (gen::, every branch), (b) the fast restatement with Euler angles (round 3's
@@ -99,9 +180,9 @@ def test_conic_branches_lean_form_vs_restatements_and_oracle(hm, oracle_ld):
     x, ecc = _conic_states(rs, 10000)
     for dt in (20.0, 5400.0):
         ref = oracle_ld.propagate(x, dt)
-        yl, _ = _run(hm.hm_general_libm, x, dt)
-        yf, _ = _run(hm.hm_general_fast, x, dt)
-        yh, okh = _run(hm.hm_conic_lean, x, dt)
+        yl, _ = mm.general_libm(x, dt)
+        yf, _ = mm.general_fast(x, dt)
+        yh, okh = mm.conic_lean(x, dt)
         assert okh.all()                                            # general orientation: the lean form takes every conic
         assert np.array_equal(np.isfinite(yh).all(1), np.isfinite(yl).all(1)) and np.array_equal(np.isfinite(yf).all(1), np.isfinite(yl).all(1))
         fin = np.isfinite(ref).all(1) & np.isfinite(yl).all(1)
@@ -120,8 +201,8 @@ def test_conic_branches_lean_form_vs_restatements_and_oracle(hm, oracle_ld):
         xs = oracle_ld.propagate(xs, T)
         xs = xs[np.isfinite(xs).all(1)]
         ref = oracle_ld.propagate(xs, 20.0)
-        yf, _ = _run(hm.hm_general_fast, xs, 20.0)
-        yh, okh = _run(hm.hm_conic_lean, xs, 20.0)
+        yf, _ = mm.general_fast(xs, 20.0)
+        yh, okh = mm.conic_lean(xs, 20.0)
         sel = okh & np.isfinite(ref).all(1) & np.isfinite(yh).all(1) & np.isfinite(yf).all(1)
         assert sel.sum() > 250                                      # (the exactly equatorial catalogue rows are declined: rv2coe's special branch)
         ef, eh = np.linalg.norm((yf - ref)[sel, :3], axis=1), np.linalg.norm((yh - ref)[sel, :3], axis=1)
@@ -131,7 +212,7 @@ def test_conic_branches_lean_form_vs_restatements_and_oracle(hm, oracle_ld):
         assert 0.5 * np.median(ef) <= np.median(eh) <= 2.0 * np.median(ef) and np.median(d) <= 1e-3 * max(np.median(ef), 1e-9) + 1e-13 * np.median(r)
 
 
-def test_near_parabolic_bands_fast_vs_libm(hm):
+def check_near_parabolic_bands_fast_vs_libm(mm):
     """genf::delta_t_from_nu_band / nu_from_delta_t_band (farnocchia.py:847-1006 for |ecc - 1| <= 1e-2, exact parabola, elliptic beyond the
     series): branch by branch the libm-level restatement with the fast primitives -- same NaN pattern, true anomalies to the bands'
     conditioning (3e-13 rad at worst: the Newton solves stop at a step of 1.5e-8 in D, as the reference's)."""
@@ -147,8 +228,7 @@ def test_near_parabolic_bands_fast_vs_libm(hm):
     nu[:50] = np.sign(nu[:50]) * 3.1                                  # next to the wrap
     nu[m // 4:m // 4 + 50] = 0.5 * (nu_max[m // 4:m // 4 + 50] / 0.95 + np.pi)   # between the asymptote and pi: NaN (:885-888)
     for tof in (20.0, 150.0, 5400.0):
-        fast, libm = np.empty(m), np.empty(m)
-        hm.hm_band(_p(nu), _p(ecc), _p(q), C.c_long(m), C.c_double(tof), _p(fast), _p(libm))
+        fast, libm = mm.band(nu, ecc, q, tof)
         assert np.array_equal(np.isfinite(fast), np.isfinite(libm)) and np.isnan(fast[m // 4:m // 4 + 50]).all() and np.isnan(fast[-1])
         both = np.isfinite(fast)
         d = np.abs(fast - libm)[both]
@@ -156,8 +236,7 @@ def test_near_parabolic_bands_fast_vs_libm(hm):
         assert d.max() < 2e-12 and np.quantile(d, 0.99) < 1e-13, (tof, d.max())
     # log_pos is total: the special arguments libm's log handles
     xs = np.array([1.0, 2.0, 1e-320, 5e-324, 1e308, 0.0, -1.0, np.inf, np.nan, 0.7, 1e-300])
-    r = np.empty_like(xs)
-    hm.hm_log_pos(_p(xs), C.c_long(len(xs)), _p(r))
+    r = mm.log_pos(xs)
     with np.errstate(all="ignore"):
         want = np.log(xs)
     assert np.array_equal(np.isnan(r), np.isnan(want)) and np.array_equal(np.isinf(r), np.isinf(want))
@@ -165,10 +244,9 @@ def test_near_parabolic_bands_fast_vs_libm(hm):
     assert np.abs(r[ok] - want[ok]).max() <= 2e-16 * np.abs(want[ok]).max() + 2e-16
 
 
-@pytest.mark.parametrize("idt", range(3))
-def test_elements_strong_elliptic_chain_vs_reference_golden(hm, idt):
+def check_elements_strong_elliptic_chain_vs_reference_golden(mm, idt):
     g = golden("kepler_golden.npz")
-    y, ok = _run(hm.hm_propagate, g["x"], float(g["dts"][idt]), C.c_int(0))
+    y, ok = mm.propagate(g["x"], float(g["dts"][idt]), 0)
     assert ok.all() and np.isfinite(y).all()        # incl. the exactly equatorial / circular rows: acos(h_z / |h|) must see exactly 1
     ref = g["y"][idt]
     inc = g["inter"][idt][:, 2]
@@ -177,11 +255,10 @@ def test_elements_strong_elliptic_chain_vs_reference_golden(hm, idt):
     assert relnorm(y, ref, slice(0, 3)).max() < 5e-10 and relnorm(y, ref, slice(3, 6)).max() < 2e-9
 
 
-def test_fast_sincos_and_reciprocals(hm):
+def check_fast_sincos_and_reciprocals(mm):
     rs = np.random.RandomState(1)
     x = np.concatenate([rs.uniform(-63.9, 63.9, 200000), [0.0, np.pi / 2, -np.pi, np.pi, 2 * np.pi, 1e-300, 100.0, -1e6]])
-    s, c = np.empty_like(x), np.empty_like(x)
-    hm.hm_sincos_fast(_p(x), C.c_long(len(x)), _p(s), _p(c))
+    s, c = mm.sincos(x)
     ls, lc = np.sin(x.astype(np.longdouble)), np.cos(x.astype(np.longdouble))
     # 1.5 ulp for results of ordinary size; next to a zero of sin / cos the two-part reduction leaves an ABSOLUTE error of
     # ~1e-17 (libm reduces further): the element chain only multiplies these by O(1) quantities
@@ -190,12 +267,11 @@ def test_fast_sincos_and_reciprocals(hm):
     assert es[:-2].max() < 2.0 and ec[:-2].max() < 2.0, (es.max(), ec.max())
     assert np.abs((s - ls).astype(np.float64))[-2:].max() < 1e-15          # |x| >= 64: the libm branch
     v = 10.0 ** rs.uniform(-8, 20, 100000)
-    r, q = np.empty_like(v), np.empty_like(v)
-    hm.hm_recip(_p(v), C.c_long(len(v)), _p(r), _p(q))
+    r, q = mm.recip(v)
     assert np.abs(r * v - 1).max() < 4.5e-16 and np.abs(q * q * v - 1).max() < 9e-16     # from a 1e-8 estimate: third order
 
 
-def test_fast_atan2(hm):
+def check_fast_atan2(mm):
     """atan2_fast (azimuth, and elevation as atan2(u, hypot(e, n))): error < 1.5 ulp (6e-16 at pi) over every octant, the fold points
     and the axes; atan2(0, 0) = 0 and the sign conventions of libm (azimuth wraps to [0, 2 pi) from those)."""
     rs = np.random.RandomState(2)
@@ -203,8 +279,7 @@ def test_fast_atan2(hm):
     rad = 10.0 ** rs.uniform(-3, 8, len(ang))
     y = np.concatenate([rad * np.sin(ang), [0.0, 0.0, 0.0, 1.0, -1.0, 1.0, 1.0, -1.0, np.tan(np.pi / 8), 1e-300, 3.0]])
     x = np.concatenate([rad * np.cos(ang), [0.0, 1.0, -1.0, 0.0, 0.0, 1.0, -1.0, -1.0, 1.0, 1.0, 1e300]])
-    r = np.empty_like(x)
-    hm.hm_atan2_fast(_p(y), _p(x), C.c_long(len(x)), _p(r))
+    r = mm.atan2(y, x)
     ref = np.arctan2(y.astype(np.longdouble), x.astype(np.longdouble))
     err = np.abs((r - ref).astype(np.float64))
     assert err.max() < 6e-16 and (err / np.spacing(np.maximum(np.abs(r), 0.5))).max() < 1.5, (err.max(), np.argmax(err))
@@ -213,18 +288,62 @@ def test_fast_atan2(hm):
     assert r[-11] == 0.0 and r[-10] == 0.0 and r[-9] == np.pi and r[-8] == np.pi / 2 and r[-7] == -np.pi / 2
     # elevation: asin(u / r) == atan2(u, hypot(e, n))
     e, n, u = rs.normal(size=(3, 100000)) * 1e6
-    el = np.empty_like(u)
-    hm.hm_atan2_fast(_p(u), _p(np.hypot(e, n)), C.c_long(len(u)), _p(el))
+    el = mm.atan2(u, np.hypot(e, n))
     el_, nl, ul = (v.astype(np.longdouble) for v in (e, n, u))
     ref = np.arcsin(ul / np.sqrt(el_ * el_ + nl * nl + ul * ul))      # (in fp64 asin(u / r) itself loses digits towards the zenith)
     assert np.abs((el - ref).astype(np.float64)).max() < 4e-16
 
 
-def test_fast_exp(hm):
+def check_fast_exp(mm):
     """exp_fast on [0, 700) (the hyperbolic Stumpff functions of the general solver): < 2 ulp."""
     rs = np.random.RandomState(3)
     x = np.concatenate([rs.uniform(0.0, 700.0, 200000), rs.uniform(0.0, 2.0, 50000), [0.0, 0.5, np.log(2.0) / 2, 699.999]])
-    r = np.empty_like(x)
-    hm.hm_exp_fast(_p(x), C.c_long(len(x)), _p(r))
+    r = mm.exp(x)
     ref = np.exp(x.astype(np.longdouble))
     assert (np.abs((r - ref) / ref).astype(np.float64)).max() < 4.5e-16
+
+
+# ---- the bodies on the host (tests/test_device_math_gpu.py runs them on the device)
+
+@pytest.mark.parametrize("idt", range(5))
+def test_fg_universal_solvers_vs_reference_golden(hm, idt):
+    check_fg_universal_solvers_vs_reference_golden(hm, idt)
+
+
+def test_fg_hyperbolic_and_near_parabolic_states(hm, oracle_ld):
+    check_fg_hyperbolic_and_near_parabolic_states(hm, oracle_ld)
+
+
+def test_conic_branches_lean_form_vs_restatements_and_oracle(hm, oracle_ld):
+    check_conic_branches_lean_form_vs_restatements_and_oracle(hm, oracle_ld)
+
+
+def test_near_parabolic_bands_fast_vs_libm(hm):
+    check_near_parabolic_bands_fast_vs_libm(hm)
+
+
+@pytest.mark.parametrize("idt", range(3))
+def test_elements_strong_elliptic_chain_vs_reference_golden(hm, idt):
+    check_elements_strong_elliptic_chain_vs_reference_golden(hm, idt)
+
+
+def test_fast_sincos_and_reciprocals(hm):
+    check_fast_sincos_and_reciprocals(hm)
+
+
+def test_fast_atan2(hm):
+    check_fast_atan2(hm)
+
+
+def test_fast_exp(hm):
+    check_fast_exp(hm)
+
+
+def test_devmath_probe_cross_compiles():
+    """the probe module of the GPU tests (tests/devmath) builds for gfx950 with the library's flags and exports every entry point: a
+    header change that breaks it fails here, without a GPU"""
+    so = build_devmath(force=True)
+    lib = C.CDLL(so)
+    for name in ("propagate", "uv_fast", "uv_general", "general_libm", "general_fast", "conic_lean", "band", "log_pos", "sincos_fast",
+                 "atan2_fast", "exp_fast", "recip"):
+        assert hasattr(lib, "dm_" + name), name

@@ -103,7 +103,7 @@ def test_propagate_edge_cases(hip, oracle):
                   [7.0e6, 0, 0, 0, -7.5e3, 0.1],        # retrograde, nearly equatorial
                   [4.2164e7, 0, 0, 0, 3074.66, 0.0]])   # GEO circular equatorial
     ref = oracle.propagate(x, 20.0)
-    for prop in (0, 1):
+    for prop in (0, 1, 3):
         y = hip.dev.propagate(hip.up(x), 20.0, propagator=prop).cpu().numpy()
         assert relnorm(y, ref, slice(0, 3)).max() < 1e-9, prop
     # sweep across the conic boundary: near-parabolic elliptic / parabolic-ish / hyperbolic branches of
@@ -120,15 +120,16 @@ def test_propagate_edge_cases(hip, oracle):
         ref = oracle.propagate(xs, dt)
         fin = np.isfinite(ref).all(axis=1)
         assert fin.mean() > 0.95
-        for prop in (0, 1):
+        for prop in (0, 1, 3):
             y = hip.dev.propagate(hip.up(xs), dt, propagator=prop).cpu().numpy()
             assert np.array_equal(np.isfinite(y).all(axis=1), fin)
             assert relnorm(y[fin], ref[fin], slice(0, 3)).max() < 1e-8, (prop, dt)
     # NaN in -> NaN out (newton returns NaN; the env turns that into a failed filter)
     bad = x.copy()
     bad[0, 0] = np.nan
-    y = hip.dev.propagate(hip.up(bad), 20.0).cpu().numpy()
-    assert np.all(np.isnan(y[0])) and np.all(np.isfinite(y[1:]))
+    for prop in (1, 3):
+        y = hip.dev.propagate(hip.up(bad), 20.0, propagator=prop).cpu().numpy()
+        assert np.all(np.isnan(y[0])) and np.all(np.isfinite(y[1:])), prop
 
 
 def test_kepler_elements_branches_vs_reference(hip):

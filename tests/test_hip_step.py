@@ -1334,7 +1334,7 @@ def test_resample_variant_fails_in_the_predict_that_draws_the_points(hip, oracle
     assert np.array_equal(eng.x_filter[0].cpu().numpy(), np.tile(hip.host.X_FAILED, (m, 1)))
 
 
-@pytest.mark.parametrize("prop", ["hybrid", "fg"])
+@pytest.mark.parametrize("prop", ["hybrid", "fg", "elements"])
 def test_an_objects_arithmetic_does_not_depend_on_its_position(hip, prop):
     """The storage layout of round 4 (catalogue.regime_order + HotPathEngine.set_layout: objects of one regime share wavefronts) rests on this:
     the same objects, filter states and noise stored in another order give, object by object, the SAME BITS -- states, covariances, truth,
