@@ -547,6 +547,29 @@ int ssa_env_step_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_
 int ssa_lookahead_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_sensor_params *s_host,
                               const ssa_lookahead_out *out, void *stream);
 
+/* ---------------------------------------------------------------- the rollout of a sensor network: a K-step tasking schedule in one launch
+ * The K launches ssa_env_step_sensors_f64 would make for the rows 0 .. K-1 of `actions`, starting from history slot slot_out - 1, with
+ * every output bit-identical to them: every surviving ring slot (x_true, x, P, obs, metrics), `status`, the failure log and count, the
+ * statistics of the last min(K, H) steps (np.argmax of sigma_pos included when spos_tiles is given) and the per-sensor update records of
+ * the last min(K, H) steps -- but each wavefront keeps its objects' state in LDS across the steps, as ssa_env_rollout_f64 does.
+ *   actions: row k = the sensors' objects at step k, SSA_MAX_SENSORS words per row whatever S is (one aligned 32-byte read per step;
+ *            the base 32-byte aligned).  Entries s >= n_sensor are ignored; < 0 or >= n_obj: sensor s is idle at that step; two sensors on
+ *            one object: the lowest-numbered one updates it -- as ssa_sensor_params.action.
+ *   upd_ring: the records of step k go to slot (slot_out + k) mod H, [S][SSA_UPD_STRIDE] per slot, written only by the step that finally
+ *            owns the slot (k >= K - H); a sensor that updates nobody gets the cleared record, as in the step.
+ * `first` and `r` are read as ssa_env_rollout_f64 reads them, obj_ids included (r->actions and r->upd_ring are not read); of `sites`:
+ * n_sensor, enu, obs_itrs, obs_limit, R and zn_stride_sensor (its action and upd are not read).  Two launches: the rollout and the
+ * fold of the per-step statistics.
+ * Refused before any launch: every refusal of ssa_env_rollout_f64 (r->actions may be NULL); NULL blocks or NULL / misaligned actions,
+ * n_sensor outside 1 .. SSA_MAX_SENSORS, a NaN elevation mask, zn_stride_sensor < 0 or == 0 with S >= 2 (SSA_E_INVALID);
+ * n_env != 1 (SSA_E_UNSUPPORTED). */
+typedef struct ssa_rollout_sensors_params {
+    const int32_t *actions;   /* [K][SSA_MAX_SENSORS] device words */
+    double *upd_ring;         /* [H][S][SSA_UPD_STRIDE] or NULL */
+} ssa_rollout_sensors_params;
+int ssa_env_rollout_sensors_f64(const ssa_consts *c_host, const ssa_step_params *first, const ssa_rollout_params *r,
+                                const ssa_sensor_params *sites, const ssa_rollout_sensors_params *rs, void *stream);
+
 /* ---------------------------------------------------------------- visibility screen of a synthetic orbit catalogue
  * catalogue._accepted (orbit_gen.py's acceptance rule) for n candidate element sets, the observer generalised to a network of
  * n_site ground sites.  Candidate c = elements[c] = (a, ecc, inc, raan, argp, nu) (m, -, rad) is propagated by Kepler's equation

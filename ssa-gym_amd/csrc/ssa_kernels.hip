@@ -1023,18 +1023,48 @@ struct ActSensors {
     SSA_DEV int get() { return -1; }
     SSA_DEV void before_wait(Tiles&, int, int) {}
     SSA_DEV void mid_step(Tiles&, int) {}
+    // the sensors' actions (all of them: indexable; one of them) and the records' base, through the pointer process_wave holds the sites by
+    SSA_DEV const int32_t* actions(const ssa_sensor_params* sp) const { return sp->action; }
+    SSA_DEV int action(const ssa_sensor_params* sp, int k) const { return sp->action[k]; }
+    SSA_DEV double* records(const ssa_sensor_params* sp) const { return sp->upd; }
+};
+// ActSchedule (rollout_sensors_kernel, ssa_env_rollout_sensors_f64; one env): ActSensors for the steps of a rollout, where the sensors'
+// actions and the records' destination change with every step while the sites do not.  `s` points at the kernel's argument block as
+// ActSensors' does (its action words and record pointer are not read); `row` is the step's row of the schedule in device memory --
+// SSA_MAX_SENSORS words, 32-byte aligned, read-only for the launch: one wave-uniform scalar load of eight words whatever S is; `upd` is
+// the step's record slot, null for a step that does not end up owning it.
+struct ActSchedule {
+    static constexpr bool late = false;
+    const ssa_sensor_params* s;
+    const int32_t* row;
+    double* upd;
+    SSA_DEV int get() { return -1; }
+    SSA_DEV void before_wait(Tiles&, int, int) {}
+    SSA_DEV void mid_step(Tiles&, int) {}
+    typedef int row_t __attribute__((ext_vector_type(SSA_MAX_SENSORS)));
+    typedef const __attribute__((address_space(4))) int32_t* WordPtr;   // (constant for the launch: the scalar cache may serve it)
+    SSA_DEV row_t actions(const ssa_sensor_params*) const
+    {
+        typedef const __attribute__((address_space(4))) row_t* RowPtr;
+        return *(RowPtr)__builtin_assume_aligned(row, sizeof(row_t));
+    }
+    SSA_DEV int action(const ssa_sensor_params*, int k) const { return ((WordPtr)row)[k]; }   // (k not known at compile time: one word)
+    SSA_DEV double* records(const ssa_sensor_params*) const { return upd; }
 };
 // the sensor that updates the object the caller calls `jid`: the lowest-numbered one whose action it is, -1 for none
-SSA_DEV int sensor_index(const ssa_sensor_params* s, int64_t jid)
+template <class ACT>
+SSA_DEV int sensor_index(const ACT& a, const ssa_sensor_params* s, int64_t jid)
 {
     int sid = -1;
+    const auto act = a.actions(s);
 #pragma unroll
     for (int k = SSA_MAX_SENSORS - 1; k >= 0; --k)
-        if (k < s->n_sensor && s->action[k] >= 0 && (int64_t)s->action[k] == jid) sid = k;
+        if (k < s->n_sensor && act[k] >= 0 && (int64_t)act[k] == jid) sid = k;
     return sid;
 }
 template <class ACT> struct ActIsSensors { static constexpr bool v = false; };
 template <> struct ActIsSensors<ActSensors> { static constexpr bool v = true; };
+template <> struct ActIsSensors<ActSchedule> { static constexpr bool v = true; };
 // ActLookSensors (lookahead_sensors_kernel, ssa_lookahead_sensors_f64; one env): ActAll for every sensor of a network.  The predict
 // runs once; the update block and the outputs then run once per sensor (a pass), from that sensor's site with its elevation mask and R
 // -- wave-uniform: scalar loads of the argument block, no waterfall.  Sensor s's outputs go to row s * n_obj + the caller's index; the
@@ -1052,6 +1082,7 @@ template <> struct ActIsLookSensors<ActLookSensors> { static constexpr bool v = 
 template <> struct ActIsAll<ActLookSensors> { static constexpr bool v = true; };
 template <class ACT> SSA_DEV const ssa_sensor_params* sensors_of(const ACT&) { return nullptr; }
 template <> SSA_DEV const ssa_sensor_params* sensors_of<ActSensors>(const ActSensors& a) { return a.s; }
+template <> SSA_DEV const ssa_sensor_params* sensors_of<ActSchedule>(const ActSchedule& a) { return a.s; }
 template <> SSA_DEV const ssa_sensor_params* sensors_of<ActLookSensors>(const ActLookSensors& a) { return a.s; }
 // a pointer into the argument segment that the optimiser cannot see through: the (scalar) loads from it stay inside ActLookSensors'
 // passes instead of being hoisted in front of them, where their results would hold scalar registers across every pass
@@ -1193,7 +1224,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     }
     int sid = -1;   // (ActSensors: the sensor that updates this row's object, -1 for none)
     if constexpr (SENS) {
-        sid = valid ? sensor_index(sensors_of(asrc), jid) : -1;
+        sid = valid ? sensor_index(asrc, sensors_of(asrc), jid) : -1;
         act = (sid >= 0) ? (int)jid : -1;
     }
     bool my_update = ALL ? (valid && interval_ok) : SENS ? (sid >= 0 && interval_ok)
@@ -1404,7 +1435,7 @@ look_pass:
     bool look_vis = false, look_taken = false;   // (ActAll: the row's visibility and whether its update ran, for the outputs)
     // (ActSensors: the row's sensor matched again here rather than carried across the propagator)
     const ssa_sensor_params* SP = PASS_ARGS ? kernarg_opaque(sensors_of(asrc)) : sensors_of(asrc);
-    if constexpr (SENS) sid = valid ? sensor_index(SP, p.obj_ids ? (int64_t)t.Oid[g] : obj) : -1;
+    if constexpr (SENS) sid = valid ? sensor_index(asrc, SP, p.obj_ids ? (int64_t)t.Oid[g] : obj) : -1;
     if (__any(my_update)) {   // whole-wave branch: a wavefront without a selected object skips the block, its variables included
     bool upd_go = false, taken = false, visible = false, attempted = false;
     double z[3] = {0.0, 0.0, 0.0}, y_row[3] = {0.0, 0.0, 0.0};   // (y_row: lane 13 of the row keeps the innovation)
@@ -1416,7 +1447,7 @@ look_pass:
     static_assert(offsetof(Tiles, D) == offsetof(Tiles, UA) + sizeof(double) * OBJ_PER_WAVE * 36, "UA and D contiguous");
     static_assert(4 * 117 <= OBJ_PER_WAVE * 36 + 330 && 330 + 57 <= 408, "update staging fits");
     if (my_update) {
-        if constexpr (SENS) rec = SP->upd ? SP->upd + (int64_t)sid * SSA_UPD_STRIDE : nullptr;
+        if constexpr (SENS) rec = asrc.records(SP) ? asrc.records(SP) + (int64_t)sid * SSA_UPD_STRIDE : nullptr;
         else rec = (!ALL && p.upd) ? p.upd + (int64_t)e * SSA_UPD_STRIDE : nullptr;
         // a filter that has failed (earlier, or in this step's predict) is skipped entirely (:293): no z_true, no record
         attempted = (st_new == SSA_ST_OK);
@@ -1676,14 +1707,14 @@ look_pass:
       }
     }
     if constexpr (SENS) {   // sensors that update nobody -- idle, out of range, a lower sensor's object, a step the interval skips: a cleared record
-        if (SP->upd && valid && obj == 0 && l == 0) {
+        if (asrc.records(SP) && valid && obj == 0 && l == 0) {
             for (int k = 0; k < SP->n_sensor; ++k) {
-                const int a = SP->action[k];
+                const int a = asrc.action(SP, k);
                 bool owns = a >= 0 && (int64_t)a < p.n_obj && interval_ok;
                 for (int q = 0; q < k; ++q)
-                    if (SP->action[q] == a) owns = false;
+                    if (asrc.action(SP, q) == a) owns = false;
                 if (!owns) {
-                    double* rec = SP->upd + (int64_t)k * SSA_UPD_STRIDE;
+                    double* rec = asrc.records(SP) + (int64_t)k * SSA_UPD_STRIDE;
                     rec[SSA_UPD_OBS_TAKEN] = 0.0;
                     rec[SSA_UPD_VISIBLE] = 0.0;
                     rec[SSA_UPD_ACTION] = -1.0;
@@ -2055,71 +2086,99 @@ struct RollK {   // ONE kernel argument, so that the per-step re-derivation belo
     StepK k;
     ssa_rollout_params r;
 };
-template <int PROP>
-__global__ void __launch_bounds__(64, SSA_STEP_WAVES) rollout_kernel(const RollK a, int ntiles, int nwork)
+// ... and a sensor network's: its sites and its schedule behind the rollout's block (ssa_env_rollout_sensors_f64)
+struct RollSensK {
+    RollK k;
+    ssa_sensor_params s;
+    ssa_rollout_sensors_params rs;
+};
+SSA_DEV const RollK& roll_of(const RollK& a) { return a; }
+SSA_DEV const RollK& roll_of(const RollSensK& a) { return a.k; }
+// the envs of the launch: a sensor network's is one (nothing per env is formed or carried, as WALK_ONE_ENV in the tile kernels)
+SSA_DEV int roll_envs(const RollK& a) { return a.k.p.n_env; }
+SSA_DEV int roll_envs(const RollSensK&) { return 1; }
+// the ACT policy of step kk, which writes ring slot `so` (owns: it is the step that finally owns the slot) -- after pk's own fields
+SSA_DEV ActEarly roll_act(const RollK&, ssa_step_params&, int, int, bool) { return ActEarly(); }
+SSA_DEV ActSchedule roll_act(const RollSensK& a, ssa_step_params& pk, int kk, int so, bool owns)
 {
-    const StepK& k_arg = a.k;
-    __shared__ Tiles t;
-    int lane = threadIdx.x;
-    const int64_t total = (int64_t)k_arg.p.n_env * k_arg.p.n_obj;
-    const int E = k_arg.p.n_env, H = a.r.history, K = a.r.n_steps;
-    const int64_t sx = total * 6, sP = total * 36, so_ = total * 12, sm = (int64_t)E * 4 * k_arg.p.n_obj, su = (int64_t)E * SSA_UPD_STRIDE;
-    TileRegs pf;
-    typedef const __attribute__((address_space(4))) RollK* RollArgPtr;
-    RollArgPtr kp = (RollArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    for (int tile = xcd_tile((int)blockIdx.x, nwork); tile < ntiles; tile += nwork) {
-        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
-        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
-        {   // the tile's state from the input slot
-            const int si0 = (a.r.slot_out + H - 1) % H;
-            ssa_step_params p0 = k_arg.p;
-            p0.x_true_in = a.r.x_true_ring + si0 * sx;
-            p0.x_in = a.r.x_ring + si0 * sx;
-            p0.P_in = a.r.P_ring + si0 * sP;
-            wave_lds_sync();   // the previous tile's last stores have read the tiles
-            tile_issue(pf, p0, lane, base, cnt);
-            tile_commit(t, pf, lane);
-            if (lane < 36) t.Q[lane] = k_arg.c.Q[lane];   // process_wave<.., 2> expects the process noise in place
-        }
-        unsigned wave_slot;   // the wavefront's slot on its SIMD (HW_ID bits 3:0)
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(wave_slot));
-        for (int kk = 0; kk < K; ++kk) {
-            // The SIMD arbiter serves the oldest wavefront first: left alone, the 5 co-resident wavefronts finish
-            // their K steps one after the other and the SIMD runs the tail of the launch with 4, 3, 2, 1 of them
-            // (latency-bound).  Rotating the issue priority per step keeps them level, so all stay resident and
-            // the stages of different wavefronts interleave until the end.
-            switch ((wave_slot + (unsigned)kk) & 3u) {
-                case 0: __builtin_amdgcn_s_setprio(0); break;
-                case 1: __builtin_amdgcn_s_setprio(1); break;
-                case 2: __builtin_amdgcn_s_setprio(2); break;
-                default: __builtin_amdgcn_s_setprio(3); break;
-            }
-            asm volatile("" : "+s"(kp));      // per step, as per tile in the tile kernels: nothing carried around the loop
-            asm volatile("" : "+v"(lane));
-            const StepK& k = ((const RollK*)kp)->k;
-            const ssa_rollout_params& r = ((const RollK*)kp)->r;
-            const int so = (r.slot_out + kk) % H, si = (so + H - 1) % H;
-            ssa_step_params pk = k.p;
-            pk.time_offset = k.p.time_offset + kk;
-            pk.x_true_in = r.x_true_ring + si * sx;  pk.x_true_out = r.x_true_ring + so * sx;
-            pk.x_in = r.x_ring + si * sx;            pk.x_out = r.x_ring + so * sx;
-            pk.P_in = r.P_ring + si * sP;            pk.P_out = r.P_ring + so * sP;
-            pk.obs = r.obs_ring + so * so_;
-            pk.metrics = r.metrics_ring + so * sm;
-            // per-ENV outputs are written by whichever wavefront owns the selected object, and wavefronts advance at
-            // their own pace: only the step that finally owns a ring slot may write it (per-object outputs have one
-            // writer, in order)
-            pk.upd = (r.upd_ring && kk >= K - H) ? r.upd_ring + so * su : nullptr;
-            pk.actions = r.actions + (int64_t)kk * E;
-            pk.stat_shards = r.stat_shards + (int64_t)kk * E * SSA_STAT_SHARDS * SSA_STAT_SHARD_WORDS;
-            pk.spos_tiles = r.spos_tiles ? r.spos_tiles + (int64_t)kk * ntiles * 2 : nullptr;
-            pk.aer_out = nullptr;
-            ActEarly early;
-            process_wave<PROP, 2>(t, k.c, pk, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, early);
-            wave_lds_sync();
-        }
-    }
+    pk.upd = nullptr;       // (the env's action word and record are not read, as in the network's step)
+    pk.actions = nullptr;
+    return ActSchedule{&a.s, a.rs.actions + (int64_t)kk * SSA_MAX_SENSORS,
+                       (a.rs.upd_ring && owns) ? a.rs.upd_ring + (int64_t)so * a.s.n_sensor * SSA_UPD_STRIDE : nullptr};
 }
+// One rollout kernel: NAME<PROP>(const K a, ntiles, nwork).  Written once and expanded into each kernel's body, as the tile kernels'
+// walk is (SSA_TILE_KERNEL): process_wave has to be inlined straight into the kernel.
+#define SSA_ROLLOUT_KERNEL(NAME, K)                                                                                                           \
+    template <int PROP>                                                                                                                       \
+    __global__ void __launch_bounds__(64, SSA_STEP_WAVES) NAME(const K a, int ntiles, int nwork)                                              \
+    {                                                                                                                                         \
+        const StepK& k_arg = roll_of(a).k;                                                                                                    \
+        __shared__ Tiles t;                                                                                                                   \
+        int lane = threadIdx.x;                                                                                                               \
+        const int E = roll_envs(a), H = roll_of(a).r.history, K_steps = roll_of(a).r.n_steps;                                                 \
+        const int64_t total = (int64_t)E * k_arg.p.n_obj;                                                                                     \
+        const int64_t sx = total * 6, sP = total * 36, so_ = total * 12, sm = (int64_t)E * 4 * k_arg.p.n_obj,                                 \
+                      su = (int64_t)E * SSA_UPD_STRIDE;                                                                                       \
+        TileRegs pf;                                                                                                                          \
+        typedef const __attribute__((address_space(4))) K* RollArgPtr;                                                                        \
+        RollArgPtr kp = (RollArgPtr)__builtin_amdgcn_kernarg_segment_ptr();                                                                   \
+        for (int tile = xcd_tile((int)blockIdx.x, nwork); tile < ntiles; tile += nwork) {                                                     \
+            const int64_t base = (int64_t)tile * OBJ_PER_WAVE;                                                                                \
+            const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);                                             \
+            {   /* the tile's state from the input slot */                                                                                    \
+                const int si0 = (roll_of(a).r.slot_out + H - 1) % H;                                                                          \
+                ssa_step_params p0 = k_arg.p;                                                                                                 \
+                p0.x_true_in = roll_of(a).r.x_true_ring + si0 * sx;                                                                           \
+                p0.x_in = roll_of(a).r.x_ring + si0 * sx;                                                                                     \
+                p0.P_in = roll_of(a).r.P_ring + si0 * sP;                                                                                     \
+                wave_lds_sync();   /* the previous tile's last stores have read the tiles */                                                  \
+                tile_issue(pf, p0, lane, base, cnt);                                                                                          \
+                tile_commit(t, pf, lane);                                                                                                     \
+                if (lane < 36) t.Q[lane] = k_arg.c.Q[lane];   /* process_wave<.., 2> expects the process noise in place */                    \
+            }                                                                                                                                 \
+            unsigned wave_slot;   /* the wavefront's slot on its SIMD (HW_ID bits 3:0) */                                                     \
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(wave_slot));                                                     \
+            for (int kk = 0; kk < K_steps; ++kk) {                                                                                            \
+                /* The SIMD arbiter serves the oldest wavefront first: left alone, the 5 co-resident wavefronts finish                        \
+                   their K steps one after the other and the SIMD runs the tail of the launch with 4, 3, 2, 1 of them                         \
+                   (latency-bound).  Rotating the issue priority per step keeps them level, so all stay resident and                          \
+                   the stages of different wavefronts interleave until the end. */                                                            \
+                switch ((wave_slot + (unsigned)kk) & 3u) {                                                                                    \
+                    case 0: __builtin_amdgcn_s_setprio(0); break;                                                                             \
+                    case 1: __builtin_amdgcn_s_setprio(1); break;                                                                             \
+                    case 2: __builtin_amdgcn_s_setprio(2); break;                                                                             \
+                    default: __builtin_amdgcn_s_setprio(3); break;                                                                            \
+                }                                                                                                                             \
+                asm volatile("" : "+s"(kp));      /* per step, as per tile in the tile kernels: nothing carried around the loop */            \
+                asm volatile("" : "+v"(lane));                                                                                                \
+                const K& ka = *(const K*)kp;                                                                                                  \
+                const StepK& k = roll_of(ka).k;                                                                                               \
+                const ssa_rollout_params& r = roll_of(ka).r;                                                                                  \
+                const int so = (r.slot_out + kk) % H, si = (so + H - 1) % H;                                                                  \
+                ssa_step_params pk = k.p;                                                                                                     \
+                pk.time_offset = k.p.time_offset + kk;                                                                                        \
+                pk.x_true_in = r.x_true_ring + si * sx;  pk.x_true_out = r.x_true_ring + so * sx;                                             \
+                pk.x_in = r.x_ring + si * sx;            pk.x_out = r.x_ring + so * sx;                                                       \
+                pk.P_in = r.P_ring + si * sP;            pk.P_out = r.P_ring + so * sP;                                                       \
+                pk.obs = r.obs_ring + so * so_;                                                                                               \
+                pk.metrics = r.metrics_ring + so * sm;                                                                                        \
+                /* per-ENV outputs are written by whichever wavefront owns the selected object, and wavefronts advance at                     \
+                   their own pace: only the step that finally owns a ring slot may write it (per-object outputs have one                      \
+                   writer, in order) */                                                                                                       \
+                pk.upd = (r.upd_ring && kk >= K_steps - H) ? r.upd_ring + so * su : nullptr;                                                  \
+                pk.actions = r.actions + (int64_t)kk * E;                                                                                     \
+                pk.stat_shards = r.stat_shards + (int64_t)kk * E * SSA_STAT_SHARDS * SSA_STAT_SHARD_WORDS;                                    \
+                pk.spos_tiles = r.spos_tiles ? r.spos_tiles + (int64_t)kk * ntiles * 2 : nullptr;                                             \
+                pk.aer_out = nullptr;                                                                                                         \
+                auto act = roll_act(ka, pk, kk, so, kk >= K_steps - H);                                                                       \
+                process_wave<PROP, 2>(t, k.c, pk, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, act);               \
+                wave_lds_sync();                                                                                                              \
+            }                                                                                                                                 \
+        }                                                                                                                                     \
+    }
+SSA_ROLLOUT_KERNEL(rollout_kernel, RollK)                  // an env's schedule (ssa_env_rollout_f64)
+SSA_ROLLOUT_KERNEL(rollout_sensors_kernel, RollSensK)      // a sensor network's (ssa_env_rollout_sensors_f64)
+#undef SSA_ROLLOUT_KERNEL
 // grid (n_steps, n_env): folds step k's shard set into the statistics slot of step k -- when that slot still
 // belongs to step k at the end of the rollout (the last `history` steps) -- and clears it
 __global__ void __launch_bounds__(64) rollout_fold_kernel(unsigned long long* __restrict__ shards, double* __restrict__ stats_ring,
@@ -3666,18 +3725,20 @@ int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, con
     });
     return launch_status();
 }
-int ssa_env_rollout_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, void* stream)
+// the checks and the argument block shared by ssa_env_rollout_f64 and ssa_env_rollout_sensors_f64 (sens: r->actions is not read); SSA_OK or
+// the refusal
+static int rollout_args(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, bool sens, RollK& rk)
 {
     if (!c || !p || !r || p->n_obj <= 0 || p->n_env <= 0 || r->n_steps < 1 || r->history < 2) return SSA_E_INVALID;
     if (r->slot_out < 0 || r->slot_out >= r->history) return SSA_E_INVALID;
-    if (!r->x_true_ring || !r->x_ring || !r->P_ring || !r->obs_ring || !r->metrics_ring || !r->stats_ring || !r->actions || !r->stat_shards)
+    if (!r->x_true_ring || !r->x_ring || !r->P_ring || !r->obs_ring || !r->metrics_ring || !r->stats_ring || (!sens && !r->actions) ||
+        !r->stat_shards)
         return SSA_E_INVALID;
     if (!p->status || !p->trans || !p->env_time || !p->z_noise) return SSA_E_INVALID;
     if (!consts_ok(c)) return SSA_E_INVALID;
     const int64_t total = (int64_t)p->n_env * p->n_obj;
     if (total >= ((int64_t)1 << 31)) return SSA_E_INVALID;
     if (r->spos_tiles && p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;
-    RollK rk;
     rk.k.c = *c;
     rk.k.p = *p;
     rk.k.p.aer_out = nullptr;
@@ -3685,14 +3746,50 @@ int ssa_env_rollout_f64(const ssa_consts* c, const ssa_step_params* p, const ssa
     rk.k.p.spos_tiles_prev = nullptr;
     if (p->obj_ids && p->n_env != 1) return SSA_E_UNSUPPORTED;
     rk.r = *r;
-    int64_t ntiles, per_wave;
-    int nwork;
-    tile_grid(total, ntiles, nwork, per_wave);
-    hipStream_t s = (hipStream_t)stream;
-    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(rollout_kernel<P>, dim3(nwork), dim3(64), 0, s, rk, (int)ntiles, nwork); });
+    return SSA_OK;
+}
+// the fold of a rollout's per-step statistics, behind its kernel
+static int rollout_fold(const ssa_step_params* p, const ssa_rollout_params* r, int64_t ntiles, hipStream_t s)
+{
     hipLaunchKernelGGL(rollout_fold_kernel, dim3(r->n_steps, p->n_env), dim3(64), 0, s, (unsigned long long*)r->stat_shards, r->stats_ring,
                        p->n_env, r->n_steps, r->slot_out, r->history, (const unsigned long long*)r->spos_tiles, p->n_obj, ntiles);
     return launch_status();
+}
+int ssa_env_rollout_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, void* stream)
+{
+    RollK rk;
+    const int rc = rollout_args(c, p, r, false, rk);
+    if (rc != SSA_OK) return rc;
+    int64_t ntiles, per_wave;
+    int nwork;
+    tile_grid((int64_t)p->n_env * p->n_obj, ntiles, nwork, per_wave);
+    hipStream_t s = (hipStream_t)stream;
+    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(rollout_kernel<P>, dim3(nwork), dim3(64), 0, s, rk, (int)ntiles, nwork); });
+    return rollout_fold(p, r, ntiles, s);
+}
+int ssa_env_rollout_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, const ssa_sensor_params* sp,
+                                const ssa_rollout_sensors_params* rs, void* stream)
+{
+    if (!c || !p || !r || !sp || !rs) return SSA_E_INVALID;
+    RollSensK rk;
+    int rc = rollout_args(c, p, r, true, rk.k);
+    if (rc != SSA_OK) return rc;
+    rc = sensors_ok(sp, p);
+    if (rc != SSA_OK) return rc;
+    if (sp->zn_stride_sensor < 0 || (sp->n_sensor > 1 && sp->zn_stride_sensor == 0)) return SSA_E_INVALID;
+    if (!rs->actions || ((uintptr_t)rs->actions % (SSA_MAX_SENSORS * sizeof(int32_t))) != 0) return SSA_E_INVALID;
+    rk.k.r.actions = nullptr;    // (the env's action words and record ring are not read)
+    rk.k.r.upd_ring = nullptr;
+    rk.s = *sp;
+    rk.s.upd = nullptr;          // (the schedule's rows and the record ring take their place)
+    for (int q = 0; q < SSA_MAX_SENSORS; ++q) rk.s.action[q] = -1;
+    rk.rs = *rs;
+    int64_t ntiles, per_wave;
+    int nwork;
+    tile_grid(p->n_obj, ntiles, nwork, per_wave);
+    hipStream_t s = (hipStream_t)stream;
+    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(rollout_sensors_kernel<P>, dim3(nwork), dim3(64), 0, s, rk, (int)ntiles, nwork); });
+    return rollout_fold(p, r, ntiles, s);
 }
 int64_t ssa_closed_loop_workspace_bytes(int64_t n_obj, int32_t n_env)
 {

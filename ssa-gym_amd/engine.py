@@ -463,15 +463,24 @@ class HotPathEngine:
                 and actions.dim() == 2 and actions.shape[1] == self.E and actions.shape[0] >= 1):
             raise _lib.SsaHipError("rollout: actions must be a contiguous CUDA int32 tensor [K][n_env]")
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        r = self._rollout_params(slot_in, time_offset, int(actions.shape[0]), argmax_spos, s)
+        r.upd_ring, r.actions = self._bu, actions.data_ptr()
+        rc = self._lib.ssa_env_rollout_f64(self._cref, self._pref, C.byref(r), s)
+        if rc:
+            raise _lib.SsaHipError("ssa_env_rollout_f64 failed with code %d" % rc)
+
+    def _rollout_params(self, slot_in, time_offset, K, argmax_spos, s):
+        """what launch_rollout and launch_rollout_sensors share: pending statistics folded, the ssa_rollout_params block of K steps from
+        history slot `slot_in` (rings, per-step shard sets and -- argmax_spos -- arg-max slots; actions and record ring left to the
+        caller) and self._p made the parameter block of the first step"""
         self.flush_stats(s)
-        K = int(actions.shape[0])
         if getattr(self, "_roll_shards", None) is None or self._roll_shards.shape[0] < K:
             self._roll_shards = torch.zeros((K, self.E, _lib.STAT_SHARDS, _lib.STAT_SHARD_WORDS), dtype=torch.int64, device=self.dev)
         r = _lib.ssa_rollout_params()
         r.n_steps, r.history, r.slot_out = K, self.H, (int(slot_in) + 1) % self.H
         r.x_true_ring, r.x_ring, r.P_ring = self._bx_t, self._bx, self._bP
-        r.obs_ring, r.metrics_ring, r.upd_ring, r.stats_ring = self._bo, self._bm, self._bu, self._bs
-        r.actions, r.stat_shards = actions.data_ptr(), self._roll_shards.data_ptr()
+        r.obs_ring, r.metrics_ring, r.stats_ring = self._bo, self._bm, self._bs
+        r.upd_ring, r.actions, r.stat_shards = 0, 0, self._roll_shards.data_ptr()
         r.spos_tiles = 0
         if argmax_spos:     # per-step arg-max slots: every step's statistics carry np.argmax(sigma_pos) (the 'shaped' reward)
             if not self.supports_argmax:
@@ -483,9 +492,37 @@ class HotPathEngine:
         p.time_offset = int(time_offset)
         p.launch_mask, p.stat_shards_prev, p.stats_prev, p.aer_out = 0, 0, 0, 0
         p.spos_tiles, p.spos_tiles_prev = 0, 0
-        rc = self._lib.ssa_env_rollout_f64(self._cref, self._pref, C.byref(r), s)
+        return r
+
+    def launch_rollout_sensors(self, slot_in, time_offset, sensors, actions, stream=None, argmax_spos=False):
+        """launch_rollout for a sensor network (include/ssa_hip.h: ssa_env_rollout_sensors_f64; one env): the K = actions.shape[0] launches
+        launch_step_sensors would make for the rows of `actions`, in one launch and bit-identical to them.  `sensors`:
+        host.make_sensor_params() (its action words and record pointer are not read); `actions`: a contiguous CUDA int32 tensor [K, S]
+        or [K, MAX_SENSORS] (row k = the sensors' objects at step k; < 0: idle; two sensors on one object: the lower one updates it).
+        The per-sensor update records of the last min(K, H) steps are in self.upd_sensors [H, S, UPD_STRIDE] (allocated on first use,
+        again when S changes), slot (slot_in + k + 1) % H for step k.  Asynchronous, no host sync."""
+        if self.E != 1:
+            raise _lib.SsaHipError("a sensor network's rollout covers one env (n_env == 1)")
+        S = int(sensors.n_sensor)
+        if not (isinstance(actions, torch.Tensor) and actions.is_cuda and actions.dtype == torch.int32 and actions.is_contiguous()
+                and actions.dim() == 2 and actions.shape[1] in (S, _lib.MAX_SENSORS) and actions.shape[0] >= 1):
+            raise _lib.SsaHipError("rollout: actions must be a contiguous CUDA int32 tensor [K][%d] or [K][%d]" % (S, _lib.MAX_SENSORS))
+        need = (S - 1) * int(sensors.zn_stride_sensor) + (self.n_time - 1) * self.zn_stride_time + (self.m - 1) * int(self._p.zn_stride_obj) + 3
+        if self.z_noise.numel() < need:
+            raise _lib.SsaHipError("z_noise: %d values needed for %d sensors, got %d" % (need, S, self.z_noise.numel()))
+        if actions.shape[1] != _lib.MAX_SENSORS:      # (the ABI's row stride: one aligned 32-byte read per step)
+            actions = torch.nn.functional.pad(actions, (0, _lib.MAX_SENSORS - S), value=-1)
+        self._roll_sched = actions      # (kept until the next launch: the kernel reads it whatever stream it runs in)
+        upd = getattr(self, "upd_sensors", None)
+        if upd is None or upd.shape[1] != S:
+            upd = self.upd_sensors = torch.zeros((self.H, S, _lib.UPD_STRIDE), dtype=f64, device=self.dev)
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        r = self._rollout_params(slot_in, time_offset, int(actions.shape[0]), argmax_spos, s)
+        rs = _lib.ssa_rollout_sensors_params()
+        rs.actions, rs.upd_ring = actions.data_ptr(), upd.data_ptr()
+        rc = self._lib.ssa_env_rollout_sensors_f64(self._cref, self._pref, C.byref(r), C.byref(sensors), C.byref(rs), s)
         if rc:
-            raise _lib.SsaHipError("ssa_env_rollout_f64 failed with code %d" % rc)
+            raise _lib.SsaHipError("ssa_env_rollout_sensors_f64 failed with code %d" % rc)
 
     def launch_closed_loop(self, slot_in, time_offset, kind, actions, stats_out, upd_out=None, fallback=None, picks=None, stream=None,
                            argmax_spos=False, wait_ticks=0, debug_withhold=False):

@@ -466,7 +466,7 @@ class SSA_Tasker_Env(Env):
     def _single_sensor(self, what):
         if self.n_sensor > 1:
             raise NotImplementedError("%s: not implemented for a sensor network (config['observers'] with %d sensors); "
-                                      "use step()" % (what, self.n_sensor))
+                                      "use step()%s" % (what, self.n_sensor, " or rollout_sensors()" if what == 'rollout' else ""))
 
     # ------------------------------------------------------------------ per-step host bookkeeping
     def _book_update(self, i, a, rec, sensor=None):
@@ -510,18 +510,26 @@ class SSA_Tasker_Env(Env):
         """the bookkeeping of consecutive step() calls for steps self.i + 1, ... of a multi-step launch (rollout, run_agent, run_policy):
         actions, update records, failures, rewards, dones, arg-max of sigma_pos, in step order, up to the first `done`.  `ring_head`: the
         newest step the history rings hold; check_actions: a ValueError for an action outside 0 .. m-1 before its step is booked
-        (run_policy).  Appends the booked steps to the caller's lists out = (actions, rewards, dones), rewards as step() hands them
+        (run_policy).  A sensor network (rollout_sensors): acts[k] holds one object per sensor and upd[k] one record per sensor.
+        Appends the booked steps to the caller's lists out = (actions, rewards, dones), rewards as step() hands them
         out; returns the `done` of the last booked step."""
         self._ring_head = ring_head
         self._fail_chunk_total = int(stats[-1][_lib.STAT_N_FAILED])      # (the chunk's last LAUNCHED step, even when booking stops early)
         actions, rewards, dones = out
         for k in range(len(acts)):
             self.i += 1
-            i, a = self.i, int(acts[k])
-            if check_actions and not (0 <= a < self.m):
-                raise ValueError("run_policy: the policy chose action %d at step %d (valid: 0 .. %d)" % (a, i, self.m - 1))
-            self.actions[i] = a
-            self._book_update(i, a, upd[k])
+            i = self.i
+            if self.n_sensor > 1:      # (a sensor network: acts[k] one object per sensor, upd[k] one record per sensor)
+                a = np.asarray(acts[k], dtype=np.int64)
+                self.actions[i] = a
+                for q in range(self.n_sensor):
+                    self._book_update(i, a[q], upd[k][q], sensor=q)
+            else:
+                a = int(acts[k])
+                if check_actions and not (0 <= a < self.m):
+                    raise ValueError("run_policy: the policy chose action %d at step %d (valid: 0 .. %d)" % (a, i, self.m - 1))
+                self.actions[i] = a
+                self._book_update(i, a, upd[k])
             self._stats = stats[k]
             if int(stats[k][_lib.STAT_N_FAILED]) != self._n_failed:
                 self._record_failures(at_step=i)
@@ -559,6 +567,49 @@ class SSA_Tasker_Env(Env):
             e.launch_rollout(i0 % e.H, i0 + 1, act, argmax_spos=shaped)
             stats, upd = self._ring_chunk(i0, kk)
             done = self._book_steps(actions[pos:pos + kk], stats, upd, i0 + kk, ([], rewards, dones))
+            pos += kk
+        return self._obs_out(refresh_aer_dev=True), np.asarray(rewards), np.asarray(dones, dtype=bool), {}
+
+    def rollout_sensors(self, actions):
+        """rollout() for a sensor network (no reference counterpart; include/ssa_hip.h: ssa_env_rollout_sensors_f64):
+        apply the tasking schedule `actions` [K, S] -- row k one object per sensor, all different, as step() takes them -- as consecutive
+        step() calls would, with up to H-1 steps per kernel launch and results bit-identical to step()'s.  Stops at the first `done`.
+        Returns what rollout() returns: (observation after the last executed step, rewards[k], dones[k], info); books per step and per
+        sensor what step() books.  Without config['observers'] (S = 1: the env's own observer as a one-site network) it equals
+        rollout(actions[:, 0]) bit for bit.  A row that step() would refuse is refused before anything is launched."""
+        if self._engine is None:
+            raise _lib.SsaHipError("no device state: a sensor network's rollout runs on the GPU only (no CPU fallback)")
+        S = self.n_sensor
+        actions = np.asarray(actions)
+        if actions.ndim != 2 or actions.shape[1] != S or actions.dtype.kind not in "iu":
+            raise AssertionError("rollout_sensors: an integer schedule [K, %d] (one object per sensor and step), got %s %s"
+                                 % (S, actions.dtype, actions.shape))
+        actions = actions.astype(np.int64)
+        for k, row in enumerate(actions):
+            if not (self.action_space.contains(row) if S > 1 else self.action_space.contains(int(row[0]))):
+                raise AssertionError("rollout_sensors: row %d (%s) invalid: one object in 0 .. %d per sensor (%d sensors)"
+                                     % (k, row, self.m - 1, S))
+            if len(np.unique(row)) != S:
+                raise ValueError("rollout_sensors: row %d tasks two sensors to the same object (%s)" % (k, row))
+        self._caller_order()
+        import torch
+        shaped = self.reward_type == 'shaped'     # (np.argmax(sigma_pos) of every step from the arg-max slots of the rollout)
+        e = self._engine
+        if S == 1 and getattr(self, "_look_sites", None) is None:   # (without observers: the env's one observer, as lookahead_sensors)
+            self._look_sites = host.make_sensor_params([self.obs_lla], [self.obs_limit], [self.R], 0)
+        sites = self._sensors if S > 1 else self._look_sites
+        K = min(len(actions), self.n - 1 - self.i)
+        rewards, dones = [], []
+        pos, done = 0, False
+        while pos < K and not done:
+            kk = min(K - pos, e.H - 1)
+            i0 = self.i
+            act = torch.as_tensor(actions[pos:pos + kk].astype(np.int32)).to(e.dev)
+            e.launch_rollout_sensors(i0 % e.H, i0 + 1, sites, act, argmax_spos=shaped)
+            slots = [(i0 + 1 + k) % e.H for k in range(kk)]
+            stats, upd = e.stats[slots, 0].cpu().numpy(), e.upd_sensors[slots].cpu().numpy()     # synchronises the stream
+            acts = actions[pos:pos + kk]
+            done = self._book_steps(acts if S > 1 else acts[:, 0], stats, upd if S > 1 else upd[:, 0], i0 + kk, ([], rewards, dones))
             pos += kk
         return self._obs_out(refresh_aer_dev=True), np.asarray(rewards), np.asarray(dones, dtype=bool), {}
 
