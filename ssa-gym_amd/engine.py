@@ -102,6 +102,11 @@ class HotPathEngine:
         self._spos_sets = None
         self._actions_ptr = self.actions.data_ptr()
         self._order = None             # storage layout (set_layout): position -> the caller's index, or None
+        # allocated by the first launch that needs them:
+        self._roll_shards = self._roll_spos = None      # per-step shard sets and arg-max slots of a rollout (_rollout_params)
+        self._roll_sched = self.upd_sensors = None      # launch_rollout_sensors: its schedule (kept until the next launch), its record ring
+        self._loop_ws = self._agent_ws = None           # workspaces of launch_closed_loop (with loop_error) and launch_agent_select
+        self._look = self._look_s = None                # output buffers of launch_lookahead / launch_lookahead_sensors
         self._pcache = {}
         self._cref = C.byref(self.consts)
         self._pref = C.byref(self._p)
@@ -362,6 +367,13 @@ class HotPathEngine:
             self._fold_pending = (self._shard_cur, stats_ptr, argmax)
             self._shard_cur ^= 1
 
+    def _check_sensor_noise(self, sensors):
+        """the extent of z_noise that the sensors of `sensors` index: sensor s reads z_noise[s * sensors.zn_stride_sensor ...]"""
+        S = int(sensors.n_sensor)
+        need = (S - 1) * int(sensors.zn_stride_sensor) + (self.n_time - 1) * self.zn_stride_time + (self.m - 1) * int(self._p.zn_stride_obj) + 3
+        if self.z_noise.numel() < need:
+            raise _lib.SsaHipError("z_noise: %d values needed for %d sensors, got %d" % (need, S, self.z_noise.numel()))
+
     def launch_step_sensors(self, slot_in, slot_out, time_offset, sensors, actions, upd_out, stream=None, **kw):
         """enqueue the step of a sensor network (include/ssa_hip.h: ssa_env_step_sensors_f64; one env): sensor s observes object
         actions[s] (< 0: idle; two sensors on one object: the lower one updates it) with its own site, elevation mask, R and noise table
@@ -373,9 +385,7 @@ class HotPathEngine:
         S = int(sensors.n_sensor)
         if len(actions) != S:
             raise _lib.SsaHipError("launch_step_sensors: %d actions for %d sensors" % (len(actions), S))
-        need = (S - 1) * int(sensors.zn_stride_sensor) + (self.n_time - 1) * self.zn_stride_time + (self.m - 1) * int(self._p.zn_stride_obj) + 3
-        if self.z_noise.numel() < need:
-            raise _lib.SsaHipError("z_noise: %d values needed for %d sensors, got %d" % (need, S, self.z_noise.numel()))
+        self._check_sensor_noise(sensors)
         for k in range(S):
             sensors.action[k] = int(actions[k])
         sensors.upd = int(upd_out)
@@ -391,7 +401,7 @@ class HotPathEngine:
         bad = [k for k in want if k not in self.LOOKAHEAD_PARTS]
         if bad:
             raise ValueError("%s: unknown output(s) %s (choose from %s)" % (name, bad, self.LOOKAHEAD_PARTS))
-        look = getattr(self, attr, None)
+        look = getattr(self, attr)
         if look is None or tuple(look["status"].shape) != lead:
             look = {"score": torch.empty(lead + (_lib.LOOK_NSCORE,), dtype=f64, device=self.dev),
                     "status": torch.empty(lead, dtype=torch.int32, device=self.dev),
@@ -474,7 +484,7 @@ class HotPathEngine:
         history slot `slot_in` (rings, per-step shard sets and -- argmax_spos -- arg-max slots; actions and record ring left to the
         caller) and self._p made the parameter block of the first step"""
         self.flush_stats(s)
-        if getattr(self, "_roll_shards", None) is None or self._roll_shards.shape[0] < K:
+        if self._roll_shards is None or self._roll_shards.shape[0] < K:
             self._roll_shards = torch.zeros((K, self.E, _lib.STAT_SHARDS, _lib.STAT_SHARD_WORDS), dtype=torch.int64, device=self.dev)
         r = _lib.ssa_rollout_params()
         r.n_steps, r.history, r.slot_out = K, self.H, (int(slot_in) + 1) % self.H
@@ -485,14 +495,18 @@ class HotPathEngine:
         if argmax_spos:     # per-step arg-max slots: every step's statistics carry np.argmax(sigma_pos) (the 'shaped' reward)
             if not self.supports_argmax:
                 raise _lib.SsaHipError("argmax_spos needs whole tiles per env (n_env == 1 or n_obj % 4 == 0)")
-            if getattr(self, "_roll_spos", None) is None or self._roll_spos.shape[0] < K:
+            if self._roll_spos is None or self._roll_spos.shape[0] < K:
                 self._roll_spos = torch.zeros((K, self.ntiles, 2), dtype=torch.int64, device=self.dev)
             r.spos_tiles = self._roll_spos.data_ptr()
+        self._first_step_block(time_offset)
+        return r
+
+    def _first_step_block(self, time_offset):
+        """self._p made the parameter block of the first step of a multi-step launch (rollout, closed loop)"""
         p = self._p
         p.time_offset = int(time_offset)
         p.launch_mask, p.stat_shards_prev, p.stats_prev, p.aer_out = 0, 0, 0, 0
         p.spos_tiles, p.spos_tiles_prev = 0, 0
-        return r
 
     def launch_rollout_sensors(self, slot_in, time_offset, sensors, actions, stream=None, argmax_spos=False):
         """launch_rollout for a sensor network (include/ssa_hip.h: ssa_env_rollout_sensors_f64; one env): the K = actions.shape[0] launches
@@ -507,13 +521,11 @@ class HotPathEngine:
         if not (isinstance(actions, torch.Tensor) and actions.is_cuda and actions.dtype == torch.int32 and actions.is_contiguous()
                 and actions.dim() == 2 and actions.shape[1] in (S, _lib.MAX_SENSORS) and actions.shape[0] >= 1):
             raise _lib.SsaHipError("rollout: actions must be a contiguous CUDA int32 tensor [K][%d] or [K][%d]" % (S, _lib.MAX_SENSORS))
-        need = (S - 1) * int(sensors.zn_stride_sensor) + (self.n_time - 1) * self.zn_stride_time + (self.m - 1) * int(self._p.zn_stride_obj) + 3
-        if self.z_noise.numel() < need:
-            raise _lib.SsaHipError("z_noise: %d values needed for %d sensors, got %d" % (need, S, self.z_noise.numel()))
+        self._check_sensor_noise(sensors)
         if actions.shape[1] != _lib.MAX_SENSORS:      # (the ABI's row stride: one aligned 32-byte read per step)
             actions = torch.nn.functional.pad(actions, (0, _lib.MAX_SENSORS - S), value=-1)
         self._roll_sched = actions      # (kept until the next launch: the kernel reads it whatever stream it runs in)
-        upd = getattr(self, "upd_sensors", None)
+        upd = self.upd_sensors
         if upd is None or upd.shape[1] != S:
             upd = self.upd_sensors = torch.zeros((self.H, S, _lib.UPD_STRIDE), dtype=f64, device=self.dev)
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
@@ -548,7 +560,7 @@ class HotPathEngine:
                 continue
             if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= n):
                 raise _lib.SsaHipError("closed loop: %s must be a contiguous CUDA %s tensor of >= %d elements" % (nm, dt, n))
-        if getattr(self, "_loop_ws", None) is None:
+        if self._loop_ws is None:
             nb = int(self._lib.ssa_closed_loop_workspace_bytes(self.m, self.E))
             if nb <= 0:
                 return False
@@ -571,10 +583,7 @@ class HotPathEngine:
         r.wait_ticks = int(wait_ticks)
         r.flags = (_lib.LOOP_ARGMAX_SPOS if argmax_spos else 0) | (_lib.LOOP_DEBUG_WITHHOLD if debug_withhold else 0)
         r.slot_of = self._slot_of32.data_ptr() if self._order is not None else 0     # (a storage layout: its inverse table)
-        p = self._p
-        p.time_offset = int(time_offset)
-        p.launch_mask, p.stat_shards_prev, p.stats_prev, p.aer_out = 0, 0, 0, 0
-        p.spos_tiles, p.spos_tiles_prev = 0, 0
+        self._first_step_block(time_offset)
         rc = self._lib.ssa_env_closed_loop_f64(self._cref, self._pref, C.byref(r), s)
         if rc == _lib.E_UNSUPPORTED:
             return False
@@ -586,7 +595,7 @@ class HotPathEngine:
         """enqueue the device-side agent (include/ssa_hip.h: ssa_agent_select_f64): choose, for every env, the action of
         the NEXT step from history slot `slot_cur` (and the slot before it for the Shannon agent) and store it in the
         int32 word(s) at `action_ptr` -- the pointer the next launch_step() is given as actions_ptr.  No host sync."""
-        if getattr(self, "_agent_ws", None) is None:
+        if self._agent_ws is None:
             nb = self._lib.ssa_agent_select_workspace_bytes(self.m, self.E)
             self._agent_ws = torch.empty(max(int(nb), 16), dtype=torch.uint8, device=self.dev)
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream

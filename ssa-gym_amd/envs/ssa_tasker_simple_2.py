@@ -7,7 +7,6 @@ order, one launch per step, one small device->host copy for reward/done, lazy nu
 the device-resident history.  Citations: ssa_tasker_simple_2.py:line in the reference.
 """
 import time
-from copy import copy
 from datetime import timedelta
 
 import numpy as np
@@ -15,143 +14,11 @@ import numpy as np
 from .. import _lib, host
 from ._config import draw_initial_state, resolve_config, reward_done
 from ._gymshim import Env, np_random, spaces
-from .results import error_failed
+from ._policy import _PolicyLoop
+from ._views import _FailureMessages, _History, _Sparse
 
 
-class _History:
-    """numpy-indexable view of a device-resident history tensor [H][E*m][...] for ONE env.
-
-    `hist[i]` -> numpy array of step i (copied from HBM on access); `hist[i, j]`, `hist[i][mask]`,
-    negative indices and slices over the time axis work like on the reference's (n, m, ...) arrays.
-    Only the last H steps are resident when the env was built with a shorter history."""
-
-    def __init__(self, env, tensor, m_axis_len, tail_shape):
-        self._env, self._t = env, tensor
-        self.shape = (env.n, m_axis_len) + tuple(tail_shape)
-        self.dtype = np.dtype(np.float64)
-        self.ndim = len(self.shape)
-
-    def __len__(self):
-        return self.shape[0]
-
-    def _slot(self, i):
-        env = self._env
-        i = int(i)
-        if i < 0:
-            i += env.n
-        if not 0 <= i < env.n:
-            raise IndexError(i)
-        env._caller_order()       # (the history arrays are read as the env numbers the objects: a storage layout ends here)
-        H = env._engine.H
-        if i > env.i or i <= env.i - H:
-            if i > env.i:   # not simulated yet: the reference arrays hold zeros there after reset()
-                return np.zeros(self.shape[1:])
-            raise IndexError("step %d is no longer resident (history depth %d, current step %d); build the env "
-                             "with config['history'] = 'full'" % (i, H, env.i))
-        return self._t[i % H].cpu().numpy().reshape(self.shape[1:])
-
-    def __getitem__(self, idx):
-        if isinstance(idx, tuple):
-            head, rest = idx[0], idx[1:]
-        else:
-            head, rest = idx, ()
-        if isinstance(head, slice):
-            arr = np.stack([self._slot(i) for i in range(*head.indices(self.shape[0]))])
-            return arr[(slice(None),) + rest] if rest else arr
-        arr = self._slot(head)
-        return arr[rest] if rest else arr
-
-    def __array__(self, dtype=None, copy=None):
-        a = np.stack([self._slot(i) for i in range(self.shape[0])])
-        return a.astype(dtype) if dtype is not None else a
-
-
-class _Sparse:
-    """reference-shaped (n, m, k...) view of a quantity the reference stores only at [i, action]
-    (z_true, y: NaN elsewhere -- ssa_tasker_simple_2.py:139-142, 202)."""
-
-    def __init__(self, env, store, tail):
-        self._env, self._s = env, store
-        self.shape = (env.n, env.m) + tuple(tail)
-
-    def __getitem__(self, idx):
-        env = self._env
-        if isinstance(idx, tuple):
-            i, rest = idx[0], idx[1:]
-        else:
-            i, rest = idx, ()
-        if isinstance(i, slice):
-            return np.stack([self[k] for k in range(*i.indices(env.n))])[(slice(None),) + rest]
-        i = int(i) + (env.n if int(i) < 0 else 0)
-        row = np.full(self.shape[1:], np.nan)
-        a = env._upd_action[i]
-        if a >= 0:
-            row[a] = self._s[i]
-        return row[rest] if rest else row
-
-    def __array__(self, dtype=None, copy=None):
-        return np.stack([self[i] for i in range(self.shape[0])])
-
-
-class _FailureMessages:
-    """`failed_filters_msg` of the reference (ssa_tasker_simple_2.py:147, 380): a list of m entries, "None" until filter j fails, then
-    [message].  The message -- 'Object j failed on predict step i, LinAlgError. [dpos dvel spos svel]' -- is FORMATTED WHEN IT IS READ, from the
-    record the kernel wrote at the failure: an episode of the default env loses a few filters per step late on, and formatting each as it
-    happened cost a gym-style step tens of microseconds."""
-    KINDS = {_lib.ST_PREDICT_NAN: ('predict', ', predict returned nan. '), _lib.ST_PREDICT_LINALG: ('predict', ', LinAlgError. '),
-             _lib.ST_UPDATE_NAN: ('update', ', update returned nan. '), _lib.ST_UPDATE_LINALG: ('update', ', LinAlgError. ')}
-
-    def __init__(self, m):
-        self._m, self._rec = int(m), {}
-
-    def record(self, j, step, status, err):
-        self._rec[j] = (step, status, err)
-
-    def __len__(self):
-        return self._m
-
-    def __getitem__(self, j):
-        if isinstance(j, slice):
-            return [self[k] for k in range(*j.indices(self._m))]
-        j = int(j)
-        if j < 0:
-            j += self._m
-        if not 0 <= j < self._m:
-            raise IndexError(j)
-        r = self._rec.get(j)
-        if r is None:
-            return "None"
-        activity, error_type = self.KINDS[r[1]]
-        return ["".join(['Object ', str(j), ' failed on ', activity, ' step ', str(r[0]), error_type, str(np.round(r[2], 2))])]
-
-    def __iter__(self):
-        return (self[j] for j in range(self._m))
-
-
-def _action_word(a):
-    """what a policy handed back, as the int32 word the next step launch reads: a CUDA int32 tensor with one element, or -- what torch.argmax
-    returns -- an int64 one, whose LOW word is the action (little endian; -1 stays -1): no cast kernel (5 us at 20 000 objects inside a replayed
-    graph, profiles/r04_run_policy_timeline.txt)."""
-    import torch
-    if isinstance(a, torch.Tensor) and a.is_cuda and a.numel() == 1:
-        if a.dtype == torch.int32:
-            return a
-        if a.dtype == torch.int64:
-            return a.reshape(1).view(torch.int32)[:1]
-    raise TypeError("run_policy: the policy must return a CUDA int32 (or int64) tensor with one element (the action)")
-
-
-def _never_destroy(graph):
-    """a torch.cuda.CUDAGraph whose capture FAILED must not be finalised: capture_end() threw before the graph let go of the RNG generator
-    state it registered with, and in this torch build (2.10 + ROCm 7) its destructor then fails a TORCH_CHECK ("The graph should be registered
-    to the state") -- an exception out of a C++ destructor: the process aborts, whenever the object happens to be freed (at the return of the
-    capturing function, or later by the garbage collector).  One leaked reference keeps the few hundred bytes alive for the life of the
-    process (tests/test_env_gpu.py::test_run_policy_replayed_from_a_graph_equals_the_eager_loop)."""
-    import ctypes
-    ctypes.pythonapi.Py_IncRef(ctypes.py_object(graph))
-
-
-class SSA_Tasker_Env(Env):
+class SSA_Tasker_Env(_PolicyLoop, Env):
     metadata = {'render.modes': ['live', 'none']}
     visualization = None
     n_sensor = 1      # sensors of the network (config['observers']); one observer without
@@ -238,6 +105,9 @@ class SSA_Tasker_Env(Env):
         self._obs_device = c.obs_device
         # run_agent(): the persistent closed-loop kernel (one launch per chunk) unless config['closed_loop'] == 'per_step'
         self._closed_loop_persistent = config.get('closed_loop', 'persistent') != 'per_step'
+        self.loop_gave_up = 0                  # persistent launches of run_agent that gave up and were re-run per step
+        # run_policy's graphs by (id(policy), chunk length, history phase), None where the policy cannot be captured (policy_graph_error: why);
+        self._policy_graphs, self._policy_refs, self.policy_graph_error = {}, {}, None      # _policy_refs: those policies, kept alive
         self.np_random = None
         self.init_seed = self.seed(config.get('seed'))[0]
         self.reset()
@@ -256,6 +126,9 @@ class SSA_Tasker_Env(Env):
         import torch
         self._aer_dev = torch.zeros(self.m * 4, dtype=torch.float64, device="cuda")
         self._stream = torch.cuda.current_stream()
+        self._look_sites = None                # the sites of the env as a network (_sites); this and the next two: made on first use
+        self._argmax_ws, self._argmax_ws_n = None, 0     # PolicyView.argmax's workspace (owned by the env: its launches share a stream)
+        self._policy_streams = None            # capture / replay stream and the copy stream of the pipelined chunks: one pair per env
         # host-mapped mailboxes (pinned memory is addressable from the GPU): the kernels read the action
         # from / write statistics and the update record to host memory directly, so a step needs one
         # stream synchronisation and one observation copy instead of four blocking transfers
@@ -500,11 +373,12 @@ class SSA_Tasker_Env(Env):
         'flatten' mode, which returns it as it is"""
         return r if (self.obs_returned == 'flatten' or np.isfinite(r)) else np.float64(0.5)
 
-    def _ring_chunk(self, i0, kk):
-        """(statistics, update records) of steps i0 + 1 .. i0 + kk from the engine's history rings; synchronises the stream"""
+    def _ring_chunk(self, i0, kk, upd_ring):
+        """(statistics, update records) of steps i0 + 1 .. i0 + kk from the engine's statistics ring and the record ring `upd_ring`
+        [H, ...] (run_agent: the engine's own, e.upd[:, 0]); synchronises the stream"""
         e = self._engine
         slots = [(i0 + 1 + k) % e.H for k in range(kk)]
-        return e.stats[slots, 0].cpu().numpy(), e.upd[slots, 0].cpu().numpy()
+        return e.stats[slots, 0].cpu().numpy(), upd_ring[slots].cpu().numpy()
 
     def _book_steps(self, acts, stats, upd, ring_head, out, check_actions=False):
         """the bookkeeping of consecutive step() calls for steps self.i + 1, ... of a multi-step launch (rollout, run_agent, run_policy):
@@ -551,24 +425,11 @@ class SSA_Tasker_Env(Env):
         sigma_pos of every step comes from the rollout's arg-max slots, ssa_rollout_params.spos_tiles)."""
         self._single_sensor('rollout')
         self._caller_order()
-        import torch
-        shaped = self.reward_type == 'shaped'     # (np.argmax(sigma_pos) of every step from the arg-max slots of the rollout)
         actions = np.asarray(actions, dtype=np.int64).ravel()
         for a in actions:
             assert self.action_space.contains(int(a)), "%r invalid" % (a,)
         e = self._engine
-        K = min(len(actions), self.n - 1 - self.i)
-        rewards, dones = [], []
-        pos, done = 0, False
-        while pos < K and not done:
-            kk = min(K - pos, e.H - 1)
-            i0 = self.i
-            act = torch.as_tensor(actions[pos:pos + kk].astype(np.int32)).view(kk, 1).to(e.dev)
-            e.launch_rollout(i0 % e.H, i0 + 1, act, argmax_spos=shaped)
-            stats, upd = self._ring_chunk(i0, kk)
-            done = self._book_steps(actions[pos:pos + kk], stats, upd, i0 + kk, ([], rewards, dones))
-            pos += kk
-        return self._obs_out(refresh_aer_dev=True), np.asarray(rewards), np.asarray(dones, dtype=bool), {}
+        return self._run_schedule(actions, actions.reshape(-1, 1), e.launch_rollout, lambda: e.upd[:, 0])
 
     def rollout_sensors(self, actions):
         """rollout() for a sensor network (no reference counterpart; include/ssa_hip.h: ssa_env_rollout_sensors_f64):
@@ -592,26 +453,36 @@ class SSA_Tasker_Env(Env):
             if len(np.unique(row)) != S:
                 raise ValueError("rollout_sensors: row %d tasks two sensors to the same object (%s)" % (k, row))
         self._caller_order()
+        e, sites = self._engine, self._sites()
+        return self._run_schedule(actions if S > 1 else actions[:, 0], actions,
+                                  lambda slot, t, act, **kw: e.launch_rollout_sensors(slot, t, sites, act, **kw),
+                                  lambda: e.upd_sensors if S > 1 else e.upd_sensors[:, 0])      # (allocated by the first launch)
+
+    def _run_schedule(self, acts, sched, launch, upd_ring):
+        """the chunk loop of rollout() and rollout_sensors(): the validated schedule -- acts[k] as _book_steps takes step k, sched[k] its
+        row of the launch's device tensor -- in chunks of up to H-1 steps, each enqueued by launch(slot_in, time index, rows on the
+        device, argmax_spos=) and booked from the statistics ring and the record ring upd_ring(), up to the first `done`.  Returns
+        what both return."""
         import torch
         shaped = self.reward_type == 'shaped'     # (np.argmax(sigma_pos) of every step from the arg-max slots of the rollout)
         e = self._engine
-        if S == 1 and getattr(self, "_look_sites", None) is None:   # (without observers: the env's one observer, as lookahead_sensors)
-            self._look_sites = host.make_sensor_params([self.obs_lla], [self.obs_limit], [self.R], 0)
-        sites = self._sensors if S > 1 else self._look_sites
-        K = min(len(actions), self.n - 1 - self.i)
+        K = min(len(acts), self.n - 1 - self.i)
         rewards, dones = [], []
         pos, done = 0, False
         while pos < K and not done:
             kk = min(K - pos, e.H - 1)
             i0 = self.i
-            act = torch.as_tensor(actions[pos:pos + kk].astype(np.int32)).to(e.dev)
-            e.launch_rollout_sensors(i0 % e.H, i0 + 1, sites, act, argmax_spos=shaped)
-            slots = [(i0 + 1 + k) % e.H for k in range(kk)]
-            stats, upd = e.stats[slots, 0].cpu().numpy(), e.upd_sensors[slots].cpu().numpy()     # synchronises the stream
-            acts = actions[pos:pos + kk]
-            done = self._book_steps(acts if S > 1 else acts[:, 0], stats, upd if S > 1 else upd[:, 0], i0 + kk, ([], rewards, dones))
+            launch(i0 % e.H, i0 + 1, torch.as_tensor(sched[pos:pos + kk].astype(np.int32)).to(e.dev), argmax_spos=shaped)
+            stats, upd = self._ring_chunk(i0, kk, upd_ring())
+            done = self._book_steps(acts[pos:pos + kk], stats, upd, i0 + kk, ([], rewards, dones))
             pos += kk
         return self._obs_out(refresh_aer_dev=True), np.asarray(rewards), np.asarray(dones, dtype=bool), {}
+
+    def _sites(self):
+        """the sites of the env as a network: its own; without config['observers'] the env's one observer as a one-site block, built once"""
+        if self._look_sites is None:
+            self._look_sites = self._sensors if self.n_sensor > 1 else host.make_sensor_params([self.obs_lla], [self.obs_limit], [self.R], 0)
+        return self._look_sites
 
     AGENT_KINDS = {'agent_naive_greedy': _lib.AGENT_NAIVE_GREEDY, 'agent_visible_greedy': _lib.AGENT_VISIBLE_GREEDY,
                    'agent_visible_greedy_aer': _lib.AGENT_VISIBLE_GREEDY, 'agent_shannon': _lib.AGENT_SHANNON,
@@ -676,7 +547,7 @@ class SSA_Tasker_Env(Env):
                         e.restore_state(i0 % e.H, snap)
                         log[pos:pos + 1].copy_(first)
                         log[pos + 1:pos + kk + 1].fill_(-1)
-                        self.loop_gave_up = getattr(self, "loop_gave_up", 0) + 1
+                        self.loop_gave_up += 1
                         self._closed_loop_persistent = False
                         used = False
                 if not used:
@@ -691,231 +562,10 @@ class SSA_Tasker_Env(Env):
                     if pos + k + 1 < K:     # (the decision for the step after this one)
                         e.launch_agent_select(i, i, kind, log.data_ptr() + 4 * (pos + k + 1), fallback_ptr=fb.data_ptr() + 4 * (pos + k + 1))
                 e.flush_stats()
-                stats, upd = self._ring_chunk(i0, kk)
+                stats, upd = self._ring_chunk(i0, kk, e.upd[:, 0])
             done = self._book_steps(log[pos:pos + kk].cpu().numpy(), stats, upd, i0 + kk, (actions, rewards, dones))
             pos += kk
         return self._obs_out(refresh_aer_dev=True), np.asarray(actions, dtype=int), np.asarray(rewards), np.asarray(dones, dtype=bool)
-
-    # ------------------------------------------------------------------ closed loop with ANY policy that lives on the GPU
-    class PolicyView:
-        """what a device-side policy sees at decision time: CUDA tensors of the env's CURRENT state (views of the history slot --
-        valid until the next step is launched; nothing is copied, nothing crosses PCIe)."""
-
-        def __init__(self, env, i, tix_off=None):
-            self.env, self.i = env, i
-            # inside a captured graph the step's time index lives on the DEVICE (engine.env_time0, which the graph advances between
-            # replays) and this decision sits `tix_off` steps behind it: the GCRS -> ITRS matrix is then picked by the kernels themselves
-            # (ssa_*_at_f64) instead of by a host integer that a capture would freeze
-            self._tix_off = tix_off
-
-        # (views are formed on access: a tensor slice costs the host 1-2 us, and most policies read one or two of them)
-        obs = property(lambda s: s.env._engine.obs[s.i % s.env._engine.H])            # [m, 12]: x_filter | diag P   (results.py:61)
-        x_filter = property(lambda s: s.env._engine.x_filter[s.i % s.env._engine.H])
-        P_filter = property(lambda s: s.env._engine.P_filter[s.i % s.env._engine.H])
-        x_true = property(lambda s: s.env._engine.x_true[s.i % s.env._engine.H])
-        P_filter_prev = property(lambda s: s.env._engine.P_filter[(s.i - 1) % s.env._engine.H] if s.i >= 1 else None)
-
-        def visible(self):
-            """uint8 CUDA mask [m]: object_visibility() of the true states (ssa_tasker_simple_2.py:427-434)"""
-            from .. import device
-            e = self.env._engine
-            if self._tix_off is not None:
-                return device.visible_mask_at(self.x_true, e.trans, e.env_time0, self._tix_off, self.env._consts)
-            return device.visible_mask(self.x_true, e.trans[self.i % e.n_time].reshape(3, 3), self.env._consts)
-
-        def argmax(self, score, mask=None):
-            """the policy's arg-max head in ONE launch: np.argmax(score[mask != 0]) mapped back to object indices (first maximum, NaN
-            skipped, -1 when nothing is selected) as the int32 CUDA tensor [1] run_policy expects.  torch.argmax + a cast are two launches
-            and 16 us at 20 000 objects (profiles/r04_run_policy_timeline.txt); this is 3-4."""
-            from .. import device
-            env = self.env
-            if getattr(env, "_argmax_ws", None) is None or env._argmax_ws_n < score.shape[0]:     # (owned by the env: its launches share a stream)
-                env._argmax_ws, env._argmax_ws_n = device.masked_argmax_workspace(score.shape[0], score.device), score.shape[0]
-            return device.masked_argmax_action(score, mask, env._argmax_ws)
-
-        def scores(self):
-            """(scores[4, m], mask[m]) of the reference's heuristic agents (trace P, visible, log-det ratio, delta_pos)"""
-            from .. import device
-            e = self.env._engine
-            if self._tix_off is not None:
-                return device.agent_scores_at(self.x_true, self.x_filter, self.P_filter, self.P_filter_prev, e.trans, e.env_time0, self._tix_off,
-                                              self.env._consts)
-            return device.agent_scores(self.x_true, self.x_filter, self.P_filter, self.P_filter_prev, e.trans[self.i % e.n_time].reshape(3, 3),
-                                       self.env._consts)
-
-    # ---- run_policy as a replayed hipGraph: K x [the policy's kernels + the step launch] captured once, replayed per chunk
-    GRAPH_CHUNK = 32
-
-    def _policy_graph(self, policy, K, i0):
-        """capture (once per policy / chunk length / history phase) K steps of the closed loop -- for every step the policy's own kernels on
-        the current history slot, then the step launch reading the action word the policy produced -- into ONE hipGraph.  What changes
-        from replay to replay lives in device memory: the time index (engine.env_time0, advanced by K at the graph's end; the steps
-        read env_time0 + their position), the history slots by parity (K is a multiple of the ring depth).  Returns the cache entry
-        or None when the policy cannot be captured (it synchronises, allocates outside the graph's pool, ...): the caller enqueues
-        eagerly."""
-        import torch
-        e = self._engine
-        key = (id(policy), K, i0 % e.H)
-        ent = self._policy_graphs.get(key)
-        if ent is not None or key in self._policy_graphs:
-            return ent
-        stats_d = torch.zeros((K, _lib.STAT_STRIDE), dtype=torch.float64, device=e.dev)
-        upd_d = torch.zeros((K, _lib.UPD_STRIDE), dtype=torch.float64, device=e.dev)
-        acts_d = torch.full((K,), -1, dtype=torch.int32, device=e.dev)
-        shaped = self.reward_type == 'shaped'
-
-        acts_t = []          # the policy's K action tensors: they live in the graph's memory pool, at the same addresses in every replay
-
-        def enqueue():
-            for k in range(K):
-                i = i0 + k + 1
-                a = _action_word(policy(self.PolicyView(self, i - 1, tix_off=k)))
-                acts_t.append(a)          # (read by the step below; gathered into acts_d ONCE per replay, behind the graph)
-                e.launch_step((i - 1) % e.H, i % e.H, k + 1, actions_ptr=a.data_ptr(), fast_stats=True, defer_fold=True,
-                              stats_out=stats_d[k].data_ptr(), upd_out=upd_d[k].data_ptr(), argmax_spos=shaped)
-            e.flush_stats()
-            torch.cat([a.reshape(1) for a in acts_t], out=acts_d)
-            e.env_time0.add_(K)
-        if getattr(self, "_policy_streams", None) is None:      # capture / replay stream and the copy stream of the pipelined chunks: one pair per env
-            self._policy_streams = (torch.cuda.Stream(device=e.dev), torch.cuda.Stream(device=e.dev))
-        stream, copy_stream = self._policy_streams
-        # two sets of pinned host buffers for the replay's results (statistics, update records, actions): chunk c is booked from one while
-        # the copy behind replay c + 1 fills the other
-        hosts = tuple(tuple(torch.empty(d.shape, dtype=d.dtype, pin_memory=True) for d in (stats_d, upd_d, acts_d)) for _ in range(2))
-        g = torch.cuda.CUDAGraph()
-        ok = True
-        try:
-            policy(self.PolicyView(self, i0))      # (eagerly once, result unused: lazy initialisation must not happen inside the capture)
-            # no garbage collection inside the capture: a collected CUDAGraph of an env that went out of scope is DESTROYED by its finaliser,
-            # hipGraphDestroy is not permitted while a stream captures, and the error thrown from that destructor ends the process
-            # (seen once in the GPU suite under -s; torch.cuda.graph() collects before it captures for the same reason)
-            import gc
-            gc.collect()
-            torch.cuda.synchronize()
-            gc_was_on = gc.isenabled()
-            gc.disable()
-            try:
-                with torch.cuda.stream(stream):
-                    g.capture_begin(capture_error_mode="thread_local")
-                    try:
-                        enqueue()
-                        g.capture_end()
-                    except BaseException:
-                        try:
-                            g.capture_end()
-                        except Exception:  # noqa: BLE001
-                            pass
-                        raise
-            finally:
-                if gc_was_on:
-                    gc.enable()
-        except TypeError:
-            raise
-        except Exception as exc:  # noqa: BLE001  (not capture-safe: remembered, the eager loop takes over)
-            ok = False
-            self.policy_graph_error = repr(exc)
-            e._fold_pending = None
-            _never_destroy(g)
-        torch.cuda.current_stream().wait_stream(stream)
-        ent = (g, stats_d, upd_d, acts_d, stream, hosts, copy_stream) if ok else None
-        self._policy_graphs[key] = ent
-        return ent
-
-    def run_policy(self, policy, n_steps, graph='auto'):
-        """Closed loop with an ARBITRARY policy evaluated on the GPU (a torch module, a hand-written rule):
-            a = policy(view)          # view: SSA_Tasker_Env.PolicyView -- CUDA tensors; returns an int32 (or int64: torch.argmax) CUDA tensor [1]
-            step(a)
-        repeated n_steps times with NO host round trip: the action never leaves the device (the step kernel reads it from the
-        tensor the policy returned), the statistics and update records go to device rings, ONE synchronisation at the end, then the
-        env's bookkeeping (actions, rewards, dones, failures, z_true / y / S records) is filled in as step() would have.  The
-        reference's loop `a = agent(obs, env); env.step(a)` (run_environment.py:26-29) for agents that are not one of the built-in
-        greedy ones (those: run_agent, one persistent launch).  Every reward type; a data-dependent `done` ('jones', 'shaped') is
-        honoured at the bookkeeping -- the steps launched behind it are discarded (chunks of history - 1 steps, as run_agent).
-        Returns (actions[k], rewards[k], dones[k])."""
-        self._single_sensor('run_policy')
-        self._caller_order()          # (the policy's views are the env's own object order)
-        import torch
-        shaped = self.reward_type == 'shaped'
-        e = self._engine
-        K = min(int(n_steps), self.n - 1 - self.i)
-        actions, rewards, dones = [], [], []
-        pos, done = 0, False
-        # graph = 'auto' | True: chunks of GRAPH_CHUNK steps replayed from a captured hipGraph where that is possible -- a reward without a
-        # data-dependent `done` ('trinary': every step of the call is wanted), a history ring whose depth divides the chunk, a policy
-        # that can be captured; everything else (and graph = False) takes the eager loop below, step by step from the host
-        G = self.GRAPH_CHUNK
-        use_graph = bool(graph) and self.reward_type == 'trinary' and G % e.H == 0
-        if not hasattr(self, "_policy_graphs"):
-            self._policy_graphs, self.policy_graph_error = {}, None
-        # The chunks are PIPELINED: replay c + 1 is enqueued before the host books chunk c.  A replay writes its statistics / update records /
-        # actions at fixed device addresses, so right behind every replay a copy stream moves them into one of two pinned host buffers
-        # (12 KB), and the next replay waits for that copy alone; the host then fills in chunk c's bookkeeping (5 us per step) while the
-        # GPU runs chunk c + 1.  (Round 4 measurement, profiles/r04_run_policy_timeline.txt: inside a replay the GPU idles < 1 us between
-        # kernels, but synchronise - copy - book - replay left it idle for 16 us per step at chunk boundaries.)  An invalid action is
-        # therefore reported one chunk late: the steps enqueued behind it have run (with no update: the kernel ignores an action out of range).
-        pend = None            # (host arrays, event) of the replay whose bookkeeping is outstanding
-
-        def book(host, ev):
-            nonlocal done
-            ev.synchronize()
-            stats, upd, acts = host       # (ring head: the replays run ahead of the booking)
-            done = self._book_steps(acts, stats, upd, i_start + launched, (actions, rewards, dones), check_actions=True)
-        launched, i_start, gstream = 0, self.i, None      # steps enqueued by replays (self.i follows as the chunks are booked)
-        try:
-            while use_graph and K - launched >= G and not done:
-                i0 = i_start + launched
-                ent = self._policy_graph(policy, G, i0)
-                if ent is None:
-                    break
-                g, stats_d, upd_d, acts_d, gstream, hosts, copy_stream = ent
-                if launched == 0:
-                    e.flush_stats()
-                    e.env_time0.fill_(i0)
-                    gstream.wait_stream(torch.cuda.current_stream())
-                slot = (launched // G) % 2
-                with torch.cuda.stream(gstream):
-                    g.replay()
-                    ready = torch.cuda.Event()
-                    ready.record(gstream)
-                copy_stream.wait_event(ready)
-                with torch.cuda.stream(copy_stream):
-                    for h, d in zip(hosts[slot], (stats_d, upd_d, acts_d)):
-                        h.copy_(d, non_blocking=True)
-                    copied = torch.cuda.Event()
-                    copied.record(copy_stream)
-                gstream.wait_event(copied)         # the NEXT replay overwrites the device buffers only behind this copy
-                launched += G
-                if pend is not None:
-                    book(*pend)                    # chunk c - 1, while the GPU runs chunk c
-                pend = (tuple(h.numpy() for h in hosts[slot]), copied)
-            if pend is not None:
-                book(*pend)
-        finally:
-            if gstream is not None:
-                torch.cuda.current_stream().wait_stream(gstream)
-                e.env_time0.zero_()
-        pos = launched
-        while pos < K and not done:
-            kk = (K - pos) if self.reward_type == 'trinary' else min(K - pos, e.H - 1)
-            i0 = self.i
-            stats_d = torch.empty((kk, _lib.STAT_STRIDE), dtype=torch.float64, device=e.dev)
-            upd_d = torch.empty((kk, _lib.UPD_STRIDE), dtype=torch.float64, device=e.dev)
-            acts_d = []
-            for k in range(kk):
-                i = i0 + k + 1
-                a = _action_word(policy(self.PolicyView(self, i - 1)))
-                acts_d.append(a)          # (kept alive until the launches that read it have run)
-                e.launch_step((i - 1) % e.H, i % e.H, i, actions_ptr=a.data_ptr(), fast_stats=True, defer_fold=True,
-                              stats_out=stats_d[k].data_ptr(), upd_out=upd_d[k].data_ptr(), argmax_spos=shaped)
-                self.i = i                # (the view of the next decision indexes the history by it)
-            e.flush_stats()
-            stats = stats_d.cpu().numpy()                  # synchronises the stream
-            upd = upd_d.cpu().numpy()
-            acts = torch.cat([a.reshape(1) for a in acts_d]).cpu().numpy()
-            self.i = i0
-            done = self._book_steps(acts, stats, upd, i0 + kk, (actions, rewards, dones), check_actions=True)
-            pos += kk
-        return np.asarray(actions, dtype=int), np.asarray(rewards), np.asarray(dones, dtype=bool)
 
     # ------------------------------------------------------------------ failures (:369-382)
     def _record_failures(self, at_step=None):
@@ -947,8 +597,7 @@ class SSA_Tasker_Env(Env):
     def _latest_resident(self):
         """the newest step the device history holds (a rollout / closed-loop launch has advanced the rings beyond self.i while the
         host is still booking its steps one by one)"""
-        head = getattr(self, "_ring_head", None)
-        return self.i if head is None else head
+        return self.i if self._ring_head is None else self._ring_head
 
     def anees(self):
         """:436-446 -- average normalised estimation error squared over the episode so far: NEES on the device for every
@@ -1110,9 +759,7 @@ class SSA_Tasker_Env(Env):
         and with covariances=True also x_prior [m, 6], P_prior [m, 6, 6] (the prediction, the same for every sensor) and P_post
         [S, m, 6, 6].  The tensors are the env's buffers: the next call overwrites them."""
         e, want = self._engine, self._lookahead_parts('lookahead_sensors', covariances)
-        if getattr(self, "_look_sites", None) is None:   # (the network's sites; without observers the env's one observer)
-            self._look_sites = self._sensors if self.n_sensor > 1 else host.make_sensor_params([self.obs_lla], [self.obs_limit], [self.R], 0)
-        r = e.launch_lookahead_sensors(self.i % e.H, self.i + 1, self._look_sites, out=want, stream=self._stream.cuda_stream)
+        r = e.launch_lookahead_sensors(self.i % e.H, self.i + 1, self._sites(), out=want, stream=self._stream.cuda_stream)
         res = {"score": r["score"].permute(0, 2, 1), "visible": r["visible"], "status": r["status"]}
         for k in want:
             res[k] = r[k]

@@ -23,6 +23,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import _graphs
+
 STAT_STRIDE = 8
 STAT_SHARDS, STAT_SHARD_WORDS = 128, 16   # include/ssa_hip.h: raw statistics shards [128][16] uint64 per env (one 128-byte line each, words 0..2 used)
 RAW_WORDS = STAT_SHARDS * STAT_SHARD_WORDS
@@ -369,22 +371,6 @@ class GraphedShardedSteps:
         if sh._peer is not None:
             sh._peer.advance_on_device(U)
 
-    def _end_stray_capture(self):
-        """after a failed capture: no stream of ours may be left in capture mode (hipStreamIsCapturing / hipStreamEndCapture)"""
-        import ctypes
-        try:
-            hip = ctypes.CDLL("libamdhip64.so")
-        except OSError:
-            return
-        for st in (self._stream, self.sh.comm):
-            status = ctypes.c_int(0)
-            if hip.hipStreamIsCapturing(ctypes.c_void_p(st.cuda_stream), ctypes.byref(status)) == 0 and status.value != 0:
-                graph = ctypes.c_void_p()
-                hip.hipStreamEndCapture(ctypes.c_void_p(st.cuda_stream), ctypes.byref(graph))
-                if graph.value:
-                    hip.hipGraphDestroy(graph)
-        hip.hipGetLastError()     # (the sticky error of the failed capture is consumed here, not by the next launch)
-
     def run_unit(self):
         """replay (capture on first use) the unit for the current phase; returns nothing, synchronises nothing.  A phase whose capture
         fails (a runtime that cannot capture the collective) is remembered and enqueued eagerly from then on -- the same kernels and the
@@ -418,42 +404,16 @@ class GraphedShardedSteps:
         with torch.cuda.stream(self._stream):
             self._enqueue_unit(tick0, k0)
             self._stream.synchronize()
-        # (begin / end by hand instead of `with torch.cuda.graph(...)`: when the capture fails -- a collective that cannot be
-        # captured -- the context manager's exit raises from capture_end() before it restores the current stream, and a stream
-        # left capturing makes the next allocation or copy of the process fail.  Here a failed capture is ended, every stream
-        # is checked, the current stream is restored, and the phase falls back to the eager enqueue.)
-        g = torch.cuda.CUDAGraph()
-        import gc
-        gc.collect()               # (no collection inside the capture: a CUDAGraph finalised there is destroyed while a stream captures -- not
-        torch.cuda.synchronize()   # permitted, and an error thrown from that destructor ends the process)
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        try:
-            with torch.cuda.stream(self._stream):
-                g.capture_begin(capture_error_mode="thread_local")
-                try:
-                    if self._force_capture_failure:
-                        raise RuntimeError("forced capture failure (test)")
-                    self._enqueue_unit(tick0, k0)
-                    g.capture_end()
-                except BaseException:
-                    try:
-                        g.capture_end()
-                    except Exception:  # noqa: BLE001  (an invalidated capture reports its error again here)
-                        pass
-                    self._end_stray_capture()
-                    raise
-            self._graphs[key] = g
-        except Exception as exc:  # noqa: BLE001
-            self._graphs[key] = False
+
+        def enqueue():
+            if self._force_capture_failure:
+                raise RuntimeError("forced capture failure (test)")
+            self._enqueue_unit(tick0, k0)
+        g, exc = _graphs.capture(self._stream, enqueue, (sh.comm,))
+        self._graphs[key] = g if exc is None else False
+        if exc is not None:
             self.capture_failed = repr(exc)
-            import ctypes
-            ctypes.pythonapi.Py_IncRef(ctypes.py_object(g))     # (a graph whose capture failed is never finalised: its destructor aborts the
-            #                                                      process in this torch build -- envs/ssa_tasker_simple_2.py::_never_destroy)
             # (what the aborted capture recorded of the device-side advances never ran; the eager unit above did advance them once: consistent)
-        finally:
-            if gc_was_on:
-                gc.enable()
         cur.wait_stream(self._stream)
 
 
