@@ -570,6 +570,29 @@ typedef struct ssa_rollout_sensors_params {
 int ssa_env_rollout_sensors_f64(const ssa_consts *c_host, const ssa_step_params *first, const ssa_rollout_params *r,
                                 const ssa_sensor_params *sites, const ssa_rollout_sensors_params *rs, void *stream);
 
+/* ---------------------------------------------------------------- the tasking assignment of a sensor network, on the device
+ * One object per sensor from one column of the scores ssa_lookahead_sensors_f64 leaves, in ONE launch and written where the next launch
+ * reads it: the global greedy assignment of agents._assign_lookahead_sensors (S ssa_masked_argmax_f64 launches, S read-backs and the
+ * host's mask edits between them).  Among all remaining (s, j) whose score[(s * n_obj + j) * SSA_LOOK_NSCORE + column] is not NaN the
+ * largest value assigns object j to sensor s (compared by value: -0.0 == 0.0, +-inf are ordinary values; equal values: the lowest
+ * s * n_obj + j, the first maximum of ssa_masked_argmax_f64); sensor s and object j leave the pool; repeated until n_sensor rounds are
+ * done or nothing but NaN is left.
+ * A sensor left without an object: with fallback == NULL it stays idle (-1).  Otherwise fallback holds SSA_MAX_SENSORS device words,
+ * the caller's draws, and the sensors are taken in ascending s: sensor s takes fallback[s] if 0 <= fallback[s] < n_obj and no sensor
+ * holds that object yet -- assigned (any s) or fallen back (a lower s) -- and stays idle otherwise.  No object is named twice.
+ *   action_out: SSA_MAX_SENSORS device words, 32-byte aligned: one row of ssa_rollout_sensors_params.actions; entries s >= n_sensor = -1.
+ *   pick_out  : [SSA_MAX_SENSORS][2] or NULL: per sensor the ASSIGNED object (-1: fallen back or idle; s >= n_sensor: -1) and the bit
+ *               pattern of its winning score (0 without one) -- as the pick_out of ssa_agent_select_f64.
+ *   workspace : ssa_assign_sensors_workspace_bytes(n_obj, n_sensor) bytes of device memory, 16-byte aligned, zeroed ONCE by the caller
+ *               (the last workgroup to arrive leaves its ticket word at zero); one call at a time per workspace (calls in one stream are).
+ * One launch: ceil(n_obj / 512) workgroups keep, per sensor, the S best candidates of their objects; the last one to arrive merges them
+ * and assigns.  Refused before any launch (SSA_E_INVALID): NULL score or action_out, a misaligned action_out, n_sensor outside
+ * 1 .. SSA_MAX_SENSORS, column outside 0 .. SSA_LOOK_NSCORE - 1, n_obj < 1 (or > INT32_MAX: an action is an int32 word), a workspace
+ * that is NULL, misaligned or too small.  ssa_assign_sensors_workspace_bytes returns SSA_E_INVALID for n_obj / n_sensor out of range. */
+int ssa_assign_sensors_f64(const double *score, int64_t n_obj, int32_t n_sensor, int32_t column, const int32_t *fallback,
+                           int32_t *action_out, int64_t *pick_out, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t ssa_assign_sensors_workspace_bytes(int64_t n_obj, int32_t n_sensor);
+
 /* ---------------------------------------------------------------- visibility screen of a synthetic orbit catalogue
  * catalogue._accepted (orbit_gen.py's acceptance rule) for n candidate element sets, the observer generalised to a network of
  * n_site ground sites.  Candidate c = elements[c] = (a, ecc, inc, raan, argp, nu) (m, -, rad) is propagated by Kepler's equation

@@ -102,8 +102,9 @@ def agent_trace_gain(obs, env):                 # argmax tr P- - tr P+ over the 
 # ---- the same baselines for a sensor network (config['observers']): every sensor's lookahead in one launch
 # (env.lookahead_sensors), then a global greedy assignment over the [S, m] score column -- the largest finite score (ties: the lowest
 # s * m + j, the masked arg-max's first maximum) assigns its object to its sensor, that sensor's row and that object's column leave,
-# and so on: one masked arg-max launch per sensor.  A sensor left without a finite score gets an object nobody has, drawn from the action
-# space's generator as _pick's fallback (env.np_random, the env's noise stream, is not touched).
+# and so on: ONE launch for all the rounds (ssa_assign_sensors_f64) and one 32-byte read-back.  A sensor left
+# without a finite score gets an object nobody has, drawn from the action space's generator as _pick's fallback (env.np_random, the
+# env's noise stream, is not touched).  env.run_agent_sensors runs the same agents without the host in the loop.
 def _draw_unassigned(env, taken):
     if len(taken) >= env.m:
         raise ValueError("%d sensors but %d objects: no object left to assign" % (len(taken) + 1, env.m))
@@ -114,21 +115,15 @@ def _draw_unassigned(env, taken):
 
 
 def _assign_lookahead_sensors(env, k):
-    from . import device
     score = env.lookahead_sensors()["score"]               # [S, 3, m]: a view of the engine's [S][m][3] rows
-    S, m = score.shape[0], score.shape[2]
-    flat = score.permute(0, 2, 1).reshape(-1)               # (no copy)
-    mask = _column_mask(env, k, flat.shape[0]).clone()
-    rows = mask.view(S, m, _lib.LOOK_NSCORE)
-    act = np.full(S, -1, dtype=np.int64)
-    for _ in range(S):
-        f = device.masked_argmax(flat, mask)
-        if f < 0:
-            break
-        s, j = divmod(f // _lib.LOOK_NSCORE, m)
-        act[s] = j
-        rows[s] = 0
-        rows[:, j] = 0
+    S = score.shape[0]
+    row = env._engine.assign_row()
+    # the rounds above on the device (ssa_assign_sensors_f64; no fallback words: a sensor without an object comes back -1): one launch
+    # and one 32-byte read-back where S masked arg-max launches and S read-backs were
+    # (permuted back, the view IS the engine's contiguous [S][m][3] block: launch_assign_sensors refuses anything else)
+    env._engine.launch_assign_sensors({"score": score.permute(0, 2, 1)}, k, row, stream=env._stream.cuda_stream)
+    env._stream.synchronize()
+    act = row.cpu().numpy()[:S].astype(np.int64)
     taken = set(act[act >= 0].tolist())
     for s in np.flatnonzero(act < 0):
         act[s] = _draw_unassigned(env, taken)

@@ -3292,6 +3292,156 @@ __global__ void __launch_bounds__(AMAX_T) masked_argmax_blocks_kernel(const doub
     }
 }
 
+// ---- the tasking assignment of a sensor network (include/ssa_hip.h: ssa_assign_sensors_f64): the global greedy assignment of
+// agents._assign_lookahead_sensors over one column of the [S][m][3] scores of ssa_lookahead_sensors_f64 -- S masked arg-max launches, S
+// read-backs and the host's mask edits between them -- in ONE launch that writes the action row the next launch reads.
+// What makes one pass enough: before sensor s gets its turn at most S - 1 objects have left, so its best remaining object is among its S
+// best under the order (value descending, index ascending: agent_merge's).
+//   phase 1: a workgroup takes ASG_CH objects; wavefront w does sensors w, w + 4: ASG_Q scores per lane in registers, S rounds of "the
+//            first candidate after the previous pick" by wavefront shuffles, the S picks stored as one row of the workspace.  Then the
+//            publish of cdna_hip_programming.md (Guideline 16): every wavefront waits for its stores, the barrier, ONE agent-scope release,
+//            the ticket (it wraps to 0 with the last arrival: the workspace needs zeroing once).
+//   phase 2: the last workgroup to arrive acquires at agent scope, merges the chunks' rows into the S x S table (the same S rounds over
+//            nb * S candidates per sensor, loaded once into registers), and ONE wavefront -- lane 8 s + r holds sensor s's r-th candidate -- runs the S greedy rounds
+//            over (value descending, s * m + j ascending), applies the fallback rule in ascending s and stores the eight action words.
+// ws: [ticket | pad to 64 bytes | nb chunks x S sensors x S (value, index) pairs]; one call at a time per workspace.
+constexpr int ASG_T = 256, ASG_CH = 512, ASG_Q = ASG_CH / 64, ASG_HOLD = 8;
+struct AsgCand { double v; long long j; };      // (j < 0: none)
+SSA_DEV void asg_wave_first(double& v, long long& j)     // the first of the wavefront's candidates, in every lane (distinct j: the merge commutes)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double v2 = __shfl_xor(v, off, 64);
+        const long long j2 = __shfl_xor(j, off, 64);
+        agent_merge(v, j, v2, j2);
+    }
+}
+SSA_DEV bool asg_after(double v, long long j, double pv, long long pj)      // does (v, j) come strictly after the pick (pv, pj)?
+{
+    return j >= 0 && (v < pv || (v == pv && j > pj));
+}
+__global__ void __launch_bounds__(ASG_T) assign_sensors_kernel(const double* __restrict__ score, int64_t m, int S, int col,
+                                                               const int32_t* __restrict__ fallback, int32_t* __restrict__ action_out,
+                                                               int64_t* __restrict__ pick_out, unsigned long long* ws)
+{
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    AsgCand* parts = reinterpret_cast<AsgCand*>(ws + 8);
+    const int64_t j0 = (int64_t)blockIdx.x * ASG_CH;
+    for (int s = wave; s < S; s += ASG_T / 64) {
+        double v[ASG_Q];
+        unsigned ok = 0;        // bit q: object j0 + 64 q + lane is a candidate (in range, not NaN)
+#pragma unroll
+        for (int q = 0; q < ASG_Q; ++q) {
+            const int64_t jj = j0 + q * 64 + lane;
+            v[q] = (jj < m) ? score[((int64_t)s * m + jj) * SSA_LOOK_NSCORE + col] : 0.0;
+            ok |= (unsigned)(jj < m && v[q] == v[q]) << q;
+        }
+        double pv = 0.0, kv = 0.0;
+        long long pj = -1, kj = -1;
+        for (int r = 0; r < S; ++r) {
+            double bv = 0.0;
+            long long bj = -1;
+            if (r == 0 || pj >= 0) {      // (an empty round: every later one is empty)
+#pragma unroll
+                for (int q = 0; q < ASG_Q; ++q) {      // (ascending indices per lane)
+                    const long long jq = j0 + q * 64 + lane;
+                    if (((ok >> q) & 1) && (r == 0 || asg_after(v[q], jq, pv, pj))) agent_merge(bv, bj, v[q], jq);
+                }
+                asg_wave_first(bv, bj);
+            }
+            if (lane == r) { kv = bv; kj = bj; }
+            pv = bv; pj = bj;
+        }
+        if (lane < S) {
+            AsgCand c;
+            c.v = kv; c.j = kj;
+            parts[((int64_t)blockIdx.x * S + s) * S + lane] = c;
+        }
+    }
+    constexpr int NTAB = SSA_MAX_SENSORS * SSA_MAX_SENSORS;
+    __shared__ AsgCand tab[NTAB + 1];       // (the one LDS object: the table, and the last-arrival flag in the j of its extra entry)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const bool won = atomicInc(reinterpret_cast<unsigned int*>(ws), gridDim.x - 1) == gridDim.x - 1;
+        if (won) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        tab[NTAB].j = won;
+    }
+    if (t < NTAB) { tab[t].v = 0.0; tab[t].j = -1; }
+    __syncthreads();
+    if (!tab[NTAB].j) return;
+    // lane 8 b + k reads rank k of chunks b, b + 8, ...: no division by S, 32-bit indices (nb * S * S < 2^28).  The first ASG_HOLD of
+    // them -- 8 ASG_HOLD chunks, 32 768 objects -- stay in registers over the S rounds; only what lies beyond is re-read from L2.
+    const int nb = (int)gridDim.x, rk = lane & 7, b0 = lane >> 3;
+    for (int s = wave; s < S; s += ASG_T / 64) {
+        AsgCand held[ASG_HOLD];
+#pragma unroll
+        for (int q = 0; q < ASG_HOLD; ++q) {
+            const int b = b0 + 8 * q;
+            held[q].v = 0.0; held[q].j = -1;
+            if (rk < S && b < nb) held[q] = parts[(b * S + s) * S + rk];
+        }
+        double pv = 0.0, kv = 0.0;
+        long long pj = -1, kj = -1;
+        for (int r = 0; r < S; ++r) {
+            double bv = 0.0;
+            long long bj = -1;
+            if (r == 0 || pj >= 0) {
+#pragma unroll
+                for (int q = 0; q < ASG_HOLD; ++q)
+                    if (r == 0 ? held[q].j >= 0 : asg_after(held[q].v, held[q].j, pv, pj)) agent_merge(bv, bj, held[q].v, held[q].j);
+                if (rk < S)
+                    for (int b = b0 + 8 * ASG_HOLD; b < nb; b += 8) {
+                        const AsgCand a = parts[(b * S + s) * S + rk];
+                        if (r == 0 ? a.j >= 0 : asg_after(a.v, a.j, pv, pj)) agent_merge(bv, bj, a.v, a.j);
+                    }
+                asg_wave_first(bv, bj);
+            }
+            if (lane == r) { kv = bv; kj = bj; }
+            pv = bv; pj = bj;
+        }
+        if (lane < S) { tab[s * SSA_MAX_SENSORS + lane].v = kv; tab[s * SSA_MAX_SENSORS + lane].j = kj; }
+    }
+    __syncthreads();
+    if (t >= 64) return;
+    const int cs = lane >> 3;
+    const double cv = tab[lane].v;
+    long long cj = tab[lane].j;
+    int act = -1;                  // lane s < S: sensor s's object
+    double pick_v = 0.0;
+    for (int r = 0; r < S; ++r) {
+        double bv = cv;
+        long long bf = (cj >= 0) ? (long long)cs * m + cj : -1;      // (ties: the lowest s * m + j, the masked arg-max's first maximum)
+        const long long mine = bf;
+        asg_wave_first(bv, bf);
+        if (bf < 0) break;
+        const int ws_s = (__ffsll((unsigned long long)__ballot(mine == bf)) - 1) >> 3;
+        const long long wj = bf - (long long)ws_s * m;
+        if (lane == ws_s) { act = (int)wj; pick_v = bv; }
+        if (cs == ws_s || cj == wj) cj = -1;       // the sensor and the object leave the pool
+    }
+    const int assigned = act;
+    const int fb = (fallback && lane < S) ? fallback[lane] : -1;
+    for (int s = 0; s < S; ++s) {       // a sensor left without an object: the caller's draw, unless out of range or held by anybody
+        const int a_s = __shfl(act, s, 64), f_s = __shfl(fb, s, 64);
+        if (a_s >= 0 || f_s < 0 || (int64_t)f_s >= m) continue;
+        const bool held = __any(lane < S && act == f_s);
+        if (!held && lane == s) act = f_s;
+    }
+    if (lane < SSA_MAX_SENSORS) {
+        action_out[lane] = (lane < S) ? act : -1;
+        if (pick_out) {
+            pick_out[2 * lane] = (lane < S) ? (int64_t)assigned : -1;
+            pick_out[2 * lane + 1] = __double_as_longlong(pick_v);
+        }
+    }
+}
+
 // ---- diagnostic reductions of SURVEY 8f-4 (ssa_tasker_simple_2.py:436-446, 750-775): NEES = d^T inv(P) d with
 // d = x_true - x_filter, NIS = y^T inv(S) y.  One lane per (step, object): Gaussian elimination with partial pivoting on
 // the augmented system [P | d] (the arithmetic class of numpy.linalg.inv's LU), then the dot product.
@@ -4129,6 +4279,22 @@ int ssa_masked_argmax_ws_f64(const double* score, const uint8_t* mask, int64_t n
     if (workspace_bytes < ssa_masked_argmax_workspace_bytes(n) || nb > 0x7fffffff) return SSA_E_INVALID;
     hipLaunchKernelGGL(masked_argmax_blocks_kernel, dim3((unsigned)nb), dim3(AMAX_T), 0, (hipStream_t)stream, score, mask, n, out,
                        (unsigned long long*)workspace);
+    return launch_status();
+}
+
+int64_t ssa_assign_sensors_workspace_bytes(int64_t n_obj, int32_t n_sensor)
+{
+    if (n_obj < 1 || n_obj > 0x7fffffff || n_sensor < 1 || n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
+    return 64 + ((n_obj + ASG_CH - 1) / ASG_CH) * n_sensor * n_sensor * (int64_t)sizeof(AsgCand);
+}
+int ssa_assign_sensors_f64(const double* score, int64_t n_obj, int32_t n_sensor, int32_t column, const int32_t* fallback,
+                           int32_t* action_out, int64_t* pick_out, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    if (!score || !action_out || ((uintptr_t)action_out & 31) || column < 0 || column >= SSA_LOOK_NSCORE) return SSA_E_INVALID;
+    const int64_t need = ssa_assign_sensors_workspace_bytes(n_obj, n_sensor);      // (refuses n_obj and n_sensor out of range)
+    if (need < 0 || !workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need) return SSA_E_INVALID;
+    hipLaunchKernelGGL(assign_sensors_kernel, dim3(nblk(n_obj, ASG_CH)), dim3(ASG_T), 0, (hipStream_t)stream, score, n_obj, (int)n_sensor,
+                       (int)column, fallback, action_out, pick_out, (unsigned long long*)workspace);
     return launch_status();
 }
 

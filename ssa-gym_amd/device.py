@@ -301,6 +301,40 @@ def masked_argmax_action(score, mask=None, workspace=None):
     return out.view(torch.int32)[:1]
 
 
+def assign_sensors_workspace(n_obj, n_sensor, device):
+    """zeroed workspace of ssa_assign_sensors_f64 for n_sensor sensors over n_obj objects (one call at a time: keep it with the stream
+    that uses it; the kernel leaves it ready for the next call)"""
+    nbytes = int(_lib.load().ssa_assign_sensors_workspace_bytes(int(n_obj), int(n_sensor)))
+    if nbytes < 0:
+        raise _lib.SsaHipError("ssa_assign_sensors_workspace_bytes(%d, %d) failed with code %d" % (n_obj, n_sensor, nbytes))
+    return torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def assign_sensors(score, column, fallback=None, out=None, picks=None, workspace=None):
+    """the tasking assignment of a sensor network on the device (ssa_assign_sensors_f64): the global greedy assignment of
+    agents._assign_lookahead_sensors over column `column` (_lib.LOOK_*) of score [S, m, 3] -- the rows launch_lookahead_sensors leaves --
+    in ONE launch.  fallback: int32 [MAX_SENSORS] draws for the sensors left without an object (taken in ascending s when in range and held
+    by nobody; None: they stay idle, -1).  Returns the int32 CUDA row [MAX_SENSORS] (`out`: a 32-byte aligned row to write, e.g. one row
+    of launch_rollout_sensors' schedule; entries s >= S are -1); picks: int64 [MAX_SENSORS, 2] to receive the assigned objects and their
+    scores' bit patterns.  workspace: assign_sensors_workspace (default: a fresh one).  No host sync."""
+    lib = _lib.load()
+    _chk(score, "score")
+    if score.dim() != 3 or score.shape[2] != _lib.LOOK_NSCORE:
+        raise _lib.SsaHipError("score must be [S, m, %d]" % _lib.LOOK_NSCORE)
+    S, m = int(score.shape[0]), int(score.shape[1])
+    out = torch.empty(_lib.MAX_SENSORS, dtype=torch.int32, device=score.device) if out is None else out
+    ws = assign_sensors_workspace(m, S, score.device) if workspace is None else workspace
+    ptr = {}
+    for t, name, dtype, n in ((out, "out", torch.int32, _lib.MAX_SENSORS), (fallback, "fallback", torch.int32, _lib.MAX_SENSORS),
+                              (picks, "picks", torch.int64, 2 * _lib.MAX_SENSORS)):
+        ptr[name] = None if t is None else _chk(t, name, dtype)
+        if t is not None and t.numel() != n:
+            raise _lib.SsaHipError("%s must hold %d %s words" % (name, n, dtype))
+    _lib.check(lib.ssa_assign_sensors_f64(score.data_ptr(), m, S, int(column), ptr["fallback"], ptr["out"], ptr["picks"],
+                                          _chk(ws, "workspace", torch.int64), ws.numel() * 8, _stream()), "ssa_assign_sensors_f64")
+    return out
+
+
 def env_step(consts, params):
     """E1: the fused step.  `params` is a filled _lib.ssa_step_params."""
     lib = _lib.load()

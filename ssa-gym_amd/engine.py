@@ -107,6 +107,8 @@ class HotPathEngine:
         self._roll_sched = self.upd_sensors = None      # launch_rollout_sensors: its schedule (kept until the next launch), its record ring
         self._loop_ws = self._agent_ws = None           # workspaces of launch_closed_loop (with loop_error) and launch_agent_select
         self._look = self._look_s = None                # output buffers of launch_lookahead / launch_lookahead_sensors
+        self._assign_ws = None                          # (S, workspace) of launch_assign_sensors
+        self._assign_row = None                         # assign_row()'s
         self._pcache = {}
         self._cref = C.byref(self.consts)
         self._pref = C.byref(self._p)
@@ -464,6 +466,40 @@ class HotPathEngine:
         if rc:
             raise _lib.SsaHipError("ssa_lookahead_sensors_f64 failed with code %d" % rc)
         return res
+
+    def launch_assign_sensors(self, look, column, action_row, fallback_row=None, picks=None, stream=None):
+        """enqueue the tasking assignment of a sensor network (include/ssa_hip.h: ssa_assign_sensors_f64) on `look`, the dict
+        launch_lookahead_sensors returned: one object per sensor by the global greedy rule of agents._assign_lookahead_sensors over score
+        column `column` (_lib.LOOK_*), written to `action_row` -- a 32-byte aligned CUDA int32 row of MAX_SENSORS words, e.g. row k of the
+        [K, MAX_SENSORS] tensor whose one-row slice the next launch_rollout_sensors takes: the actions never touch the host.
+        fallback_row: int32 [MAX_SENSORS] draws for the sensors left without an object (None: they stay idle, -1); picks: int64
+        [MAX_SENSORS, 2] or None.  The workspace is this engine's (zeroed once, again when S changes).  Asynchronous, no host sync."""
+        score = look["score"]
+        S = int(score.shape[0]) if isinstance(score, torch.Tensor) and score.dim() == 3 else 0
+        for t, dt, n, nm in ((action_row, torch.int32, _lib.MAX_SENSORS, "action_row"), (fallback_row, torch.int32, _lib.MAX_SENSORS, "fallback_row"),
+                             (picks, torch.int64, 2 * _lib.MAX_SENSORS, "picks")):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == n):
+                raise _lib.SsaHipError("assign: %s must be a contiguous CUDA %s tensor of %d elements" % (nm, dt, n))
+        if action_row is None or not (isinstance(score, torch.Tensor) and score.is_cuda and score.dtype == torch.float64
+                                      and score.is_contiguous() and tuple(score.shape) == (S, self.m, _lib.LOOK_NSCORE)):
+            raise _lib.SsaHipError("assign: an action row and the contiguous CUDA float64 [S, %d, %d] scores of launch_lookahead_sensors "
+                                   "are needed" % (self.m, _lib.LOOK_NSCORE))
+        if self._assign_ws is None or self._assign_ws[0] != S:
+            self._assign_ws = (S, device.assign_sensors_workspace(self.m, S, self.dev))
+        ws = self._assign_ws[1]
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        rc = self._lib.ssa_assign_sensors_f64(score.data_ptr(), self.m, S, int(column), fallback_row.data_ptr() if fallback_row is not None else 0,
+                                              action_row.data_ptr(), picks.data_ptr() if picks is not None else 0, ws.data_ptr(),
+                                              ws.numel() * 8, s)
+        if rc:
+            raise _lib.SsaHipError("ssa_assign_sensors_f64 failed with code %d" % rc)
+
+    def assign_row(self):
+        """this engine's own int32 [MAX_SENSORS] action row, for a caller of launch_assign_sensors that reads one assignment back
+        (agents._assign_lookahead_sensors); allocated on first use"""
+        if self._assign_row is None:
+            self._assign_row = torch.full((_lib.MAX_SENSORS,), -1, dtype=torch.int32, device=self.dev)
+        return self._assign_row
 
     def launch_rollout(self, slot_in, time_offset, actions, stream=None, argmax_spos=False):
         """K = actions.shape[0] consecutive steps in one launch (include/ssa_hip.h: ssa_env_rollout_f64): step k reads

@@ -567,6 +567,60 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
             pos += kk
         return self._obs_out(refresh_aer_dev=True), np.asarray(actions, dtype=int), np.asarray(rewards), np.asarray(dones, dtype=bool)
 
+    SENSOR_AGENT_COLUMNS = {'agent_info_gain_sensors': _lib.LOOK_INFO_GAIN, 'agent_trace_gain_sensors': _lib.LOOK_TRACE_GAIN}
+
+    def run_agent_sensors(self, agent, n_steps, fallback_actions=None):
+        """run_agent() for a sensor network (no reference counterpart): the loop
+            a = agent(obs, env); obs, r, done, _ = env.step(a)
+        for agents.agent_info_gain_sensors / agent_trace_gain_sensors (`agent`: the function or its name) with the assignment computed on
+        the GPU (ssa_assign_sensors_f64) and handed to the step in-stream.  Per step three launches in one stream -- every sensor's
+        lookahead, the assignment into row k of a device log, the step that reads that row (ssa_env_rollout_sensors_f64 with a one-row
+        schedule) -- and nothing is read back until a chunk of up to H-1 steps ends.  Stops at the first `done`.  Returns what run_agent
+        returns: (observation after the last executed step, actions [k, S], rewards [k], dones [k]); books per step and per sensor what
+        step() books.  Without config['observers'] (S = 1) the env's own observer runs as a one-site network.
+        `fallback_actions` [K + 1, S]: row k holds the draws for the sensors the scores leave without an object at decision k (default:
+        one action_space.sample() per row; env.np_random is not touched).  The device's rule differs from the host agents' redraw loop:
+        sensor s, in ascending s, takes its draw if no sensor holds that object, and otherwise STAYS IDLE at that step -- booked as action
+        -1 with no update record, a row step() itself cannot express (it wants one object per sensor)."""
+        if self._engine is None:
+            raise _lib.SsaHipError("no device state: a sensor network's closed loop runs on the GPU only (no CPU fallback)")
+        import torch
+        name = agent if isinstance(agent, str) else getattr(agent, "__name__", None)
+        if name not in self.SENSOR_AGENT_COLUMNS:
+            raise NotImplementedError("run_agent_sensors: %r has no device-side version (supported: %s)"
+                                      % (agent, sorted(self.SENSOR_AGENT_COLUMNS)))
+        column = self.SENSOR_AGENT_COLUMNS[name]
+        self._caller_order()
+        shaped = self.reward_type == 'shaped'
+        e, sites, S, W = self._engine, self._sites(), self.n_sensor, _lib.MAX_SENSORS
+        K = max(min(int(n_steps), self.n - 1 - self.i), 0)
+        if fallback_actions is None:
+            fallback_actions = [self.action_space.sample() for _ in range(K + 1)]
+        fbh = np.full((K + 1, W), -1, dtype=np.int32)
+        rows = np.asarray(fallback_actions, dtype=np.int32)
+        if rows.size % S or rows.size < (K + 1) * S:
+            raise ValueError("run_agent_sensors: fallback_actions must be [K + 1, S] = [%d, %d] (one row per decision and one to spare; "
+                             "longer is fine), got shape %s" % (K + 1, S, rows.shape))
+        fbh[:, :S] = rows.reshape(-1, S)[:K + 1]
+        fb = torch.as_tensor(fbh).to(e.dev)                                      # (uploaded once)
+        log = torch.full((K + 1, W), -1, dtype=torch.int32, device=e.dev)        # log[k] = the sensors' objects at step i0 + k + 1
+        actions, rewards, dones = [], [], []
+        pos, done = 0, False
+        while pos < K and not done:
+            kk = min(K - pos, e.H - 1)     # (every step of a chunk stays resident: the one that turns out to be the last is returned)
+            i0 = self.i
+            for k in range(kk):
+                i = i0 + k + 1
+                look = e.launch_lookahead_sensors((i - 1) % e.H, i, sites)
+                e.launch_assign_sensors(look, column, log[pos + k], fallback_row=fb[pos + k])
+                e.launch_rollout_sensors((i - 1) % e.H, i, sites, log[pos + k:pos + k + 1], argmax_spos=shaped)
+            stats, upd = self._ring_chunk(i0, kk, e.upd_sensors if S > 1 else e.upd_sensors[:, 0])
+            acts = log[pos:pos + kk, :S].cpu().numpy()
+            done = self._book_steps(acts if S > 1 else acts[:, 0], stats, upd, i0 + kk, (actions, rewards, dones))
+            pos += kk
+        return (self._obs_out(refresh_aer_dev=True), np.asarray(actions, dtype=int).reshape(len(actions), S), np.asarray(rewards),
+                np.asarray(dones, dtype=bool))
+
     # ------------------------------------------------------------------ failures (:369-382)
     def _record_failures(self, at_step=None):
         """filter_error() bookkeeping (:369-382) for the filters that failed in step self.i (at_step: the step being booked after a rollout
