@@ -17,7 +17,7 @@ sys.path.insert(0, "tests")
 import ssa_gym_amd  # noqa: E402,F401
 from ssa_gym_amd import _lib, agents, device  # noqa: E402
 from ssa_gym_amd import envs as E  # noqa: E402
-from test_sensors_host import SITES8  # noqa: E402
+from support.sensors import SITES8_GEOMETRY  # noqa: E402
 
 S, phase = int(sys.argv[1]), sys.argv[2]
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 8
@@ -27,7 +27,7 @@ m, H = 20000, 64
 cfg = dict(E.env_config)
 cfg.update(rso_count=m, steps=480, obs_limit=15, reward_type='trinary', obs_returned='flatten', seed=3, history=H)
 if S > 1:
-    cfg.update(observers=SITES8[:S], sensor_obs_limit=[15, 10, 20, 0, 5, 10, 20, 15][:S],
+    cfg.update(observers=SITES8_GEOMETRY[:S], sensor_obs_limit=[15, 10, 20, 0, 5, 10, 20, 15][:S],
                sensor_z_sigma=[(1 + 0.5 * k, 1 + 0.5 * k, 1e3) for k in range(S)])
 i0 = 0 if phase == "early" else 299
 

@@ -12,7 +12,7 @@ sys.path.insert(0, "tests")
 import ssa_gym_amd  # noqa: E402
 from ssa_gym_amd import _lib, host  # noqa: E402
 from ssa_gym_amd import envs as E  # noqa: E402
-from test_sensors_host import SITES8, sites_rad  # noqa: E402
+from support.sensors import SITES8_GEOMETRY, sites_rad  # noqa: E402
 
 S, phase = int(sys.argv[1]), sys.argv[2]
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 24
@@ -20,7 +20,7 @@ warm = 3
 m, H = 20000, 64
 cfg = dict(E.env_config)
 cfg.update(rso_count=m, steps=480, obs_limit=15, reward_type='trinary', obs_returned='flatten', seed=3, history=H,
-           observers=SITES8, sensor_obs_limit=[15, 10, 20, 0, 5, 10, 20, 15],
+           observers=SITES8_GEOMETRY, sensor_obs_limit=[15, 10, 20, 0, 5, 10, 20, 15],
            sensor_z_sigma=[(1 + 0.5 * k, 1 + 0.5 * k, 1e3) for k in range(8)])
 env = E.make('ssa_tasker_simple-v2', config=cfg)
 rs = np.random.RandomState(7)

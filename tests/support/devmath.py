@@ -1,0 +1,205 @@
+"""The device-math probe's build and the test bodies that run on both backends: tests/test_device_math_host.py hands them HostMath
+(tests/hostmath, on the CPU), tests/test_device_math_gpu.py DeviceMath (tests/devmath, on the device) -- same bodies, same bounds."""
+import os
+
+import numpy as np
+
+from conftest import golden
+from support.batches import relnorm
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+DEVMATH_SRC = os.path.join(HERE, "devmath", "devmath.hip")
+DEVMATH_LIB = os.path.join(HERE, "devmath", "libdevmath.so")
+
+
+def build_devmath(force=False):
+    """the device-math probe, in-tree next to its source (it travels with the tree, as libssa_hip.so does), with the library's
+    hipcc flags; rebuilt when it is older than its source or the product headers"""
+    from ssa_gym_amd import _build
+    deps = [DEVMATH_SRC, os.path.join(_build.HERE, "csrc", "ssa_math.hpp"), os.path.join(_build.HERE, "csrc", "ssa_conics.hpp")]
+    if force or _build.stale(DEVMATH_LIB, deps):
+        _build.hipcc_shared(DEVMATH_SRC, DEVMATH_LIB)
+    return DEVMATH_LIB
+
+
+def check_fg_universal_solvers_vs_reference_golden(mm, idt):
+    g = golden("kepler_golden.npz")
+    dt = float(g["dts"][idt])
+    y, ok = mm.propagate(g["x"], dt, 1)
+    assert ok.all()
+    ref = g["y"][idt]
+    inc = g["inter"][idt][:, 2]
+    good = (inc > 1e-3) | (inc < 1e-8)       # (near-equatorial rows: the REFERENCE is ill-conditioned there, see test_hip_ops)
+    assert relnorm(y, ref, slice(0, 3))[good].max() < 2e-12 and relnorm(y, ref, slice(3, 6))[good].max() < 2e-12
+    assert relnorm(y, ref, slice(0, 3)).max() < 5e-10
+    # which solver took which lane: every catalogue state at the env's step sizes is a series / Halley lane; at 5 400 s the
+    # long-period orbits still are, at one day none is (closed-form / Laguerre for all)
+    _, handled = mm.uv_fast(g["x"], dt)
+    assert handled.all() if dt <= 150 else (0 < handled.sum() < len(handled) if dt < 8e4 else not handled.any())
+    yg, okg = mm.uv_general(g["x"], dt)
+    assert okg.all() and relnorm(yg, ref, slice(0, 3))[good].max() < 2e-12      # the general solver alone covers everything
+
+
+def check_fg_hyperbolic_and_near_parabolic_states(mm, oracle_ld):
+    """diverged filter states (scaled velocities): every conic through the same equation, against the 80-bit oracle"""
+    cat = golden("catalogue_subset.npy")
+    rs = np.random.RandomState(0)
+    for lo, hi in ((1.45, 2.5), (1.40, 1.43), (1.0, 1.4), (0.3, 0.9), (3.0, 40.0)):
+        x = cat.copy()
+        x[:, 3:] *= rs.uniform(lo, hi, size=len(x))[:, None]
+        for dt in (20.0, 150.0):
+            y, ok = mm.propagate(x, dt, 1)
+            ref = oracle_ld.propagate(x, dt)
+            fin = np.isfinite(ref).all(1)
+            assert ok[fin].all()
+            assert relnorm(y, ref, slice(0, 3))[fin].max() < 1e-12 and relnorm(y, ref, slice(3, 6))[fin].max() < 1e-12
+
+
+def _conic_states(rs, m):
+    """hyperbolic (mild ... e = 3e4), near-parabolic both sides, elliptic: general orientation"""
+    from ssa_gym_amd.catalogue import coe2rv_host
+    k = m // 5
+    ecc = np.concatenate([rs.uniform(1.0101, 1.05, k), rs.uniform(1.05, 3, k), 10 ** rs.uniform(0.5, 4.5, k), rs.uniform(0.9901, 1.0099, k),
+                          rs.uniform(0.05, 0.9899, m - 4 * k)])
+    rp = rs.uniform(6.8e6, 3e7, m)
+    nu_max = np.where(ecc > 1, 0.9 * np.arccos(-1 / np.maximum(ecc, 1.000001)), 2.5)
+    x = coe2rv_host(rp * (1 + ecc), ecc, rs.uniform(0.2, 2.9, m), rs.uniform(0, 6.28, m), rs.uniform(0, 6.28, m), rs.uniform(-1, 1, m) * nu_max)
+    return x, ecc
+
+
+def check_conic_branches_lean_form_vs_restatements_and_oracle(mm, oracle_ld):
+    """What SSA_PROP_HYBRID (and the fallback of SSA_PROP_ELEMENTS) runs beyond the series solver -- kepler_conic_lean: the reference's
+    anomaly chain with the orbit's orientation carried by the state's own unit vectors, the near-parabolic bands through genf:: --
+    against (a) the libm-level restatement of farnocchia() (gen::, every branch), (b) the fast restatement with Euler angles (round 3's
+    arithmetic) and (c) the 80-bit oracle: the same accuracy class everywhere, the same NaN pattern, and on far-out hyperbolic states
+    (a diverged filter: r ~ 1e9-1e11 m) the same ERROR against the exact solution as the reference's chain -- that error, metres to
+    kilometres from the round trips through the true anomaly, is what makes the reference lose filters, and the lean form must keep it
+    (an orientation measured from e / |e| instead of from r / |r| does not: 15 x the reference's median error, and six times its
+    failed filters over an episode -- measured in round 4)."""
+    rs = np.random.RandomState(5)
+    x, ecc = _conic_states(rs, 10000)
+    for dt in (20.0, 5400.0):
+        ref = oracle_ld.propagate(x, dt)
+        yl, _ = mm.general_libm(x, dt)
+        yf, _ = mm.general_fast(x, dt)
+        yh, okh = mm.conic_lean(x, dt)
+        assert okh.all()                                            # general orientation: the lean form takes every conic
+        assert np.array_equal(np.isfinite(yh).all(1), np.isfinite(yl).all(1)) and np.array_equal(np.isfinite(yf).all(1), np.isfinite(yl).all(1))
+        fin = np.isfinite(ref).all(1) & np.isfinite(yl).all(1)
+        for lo, hi, tol in ((0, 6000, 5e-13), (6000, 8000, 5e-11), (8000, 10000, 5e-13)):     # hyperbolic | near-parabolic (ill-conditioned) | elliptic
+            sl = np.zeros(len(x), dtype=bool)
+            sl[lo:hi] = True
+            sl &= fin
+            el, ef, eh = (relnorm(y[sl], ref[sl], slice(0, 3)) for y in (yl, yf, yh))
+            assert eh.max() < tol and np.median(eh) <= 2 * np.median(el) + 1e-16 and np.quantile(eh, 0.99) <= 2 * np.quantile(el, 0.99) + 1e-15, (dt, lo)
+            assert relnorm(yh[sl], yf[sl], slice(0, 3)).max() < tol
+    # far-out hyperbolic states: the reference's own error level is kept (position error in METRES against the 80-bit solution)
+    cat = golden("catalogue_subset.npy")
+    for scale_v, T in ((30.0, 4000.0), (300.0, 6000.0), (2000.0, 8000.0)):
+        xs = cat.copy()
+        xs[:, 3:] *= scale_v * rs.uniform(0.8, 1.2, size=len(xs))[:, None]
+        xs = oracle_ld.propagate(xs, T)
+        xs = xs[np.isfinite(xs).all(1)]
+        ref = oracle_ld.propagate(xs, 20.0)
+        yf, _ = mm.general_fast(xs, 20.0)
+        yh, okh = mm.conic_lean(xs, 20.0)
+        sel = okh & np.isfinite(ref).all(1) & np.isfinite(yh).all(1) & np.isfinite(yf).all(1)
+        assert sel.sum() > 250                                      # (the exactly equatorial catalogue rows are declined: rv2coe's special branch)
+        ef, eh = np.linalg.norm((yf - ref)[sel, :3], axis=1), np.linalg.norm((yh - ref)[sel, :3], axis=1)
+        d = np.linalg.norm((yh - yf)[sel, :3], axis=1)
+        r = np.linalg.norm(xs[sel, :3], axis=1)
+        print("[conics] r ~ %.1e m: |error| median lean %.3e m / Euler-angle form %.3e m; lean vs Euler-angle form median %.1e m" % (np.median(r), np.median(eh), np.median(ef), np.median(d)))
+        assert 0.5 * np.median(ef) <= np.median(eh) <= 2.0 * np.median(ef) and np.median(d) <= 1e-3 * max(np.median(ef), 1e-9) + 1e-13 * np.median(r)
+
+
+def check_near_parabolic_bands_fast_vs_libm(mm):
+    """genf::delta_t_from_nu_band / nu_from_delta_t_band (farnocchia.py:847-1006 for |ecc - 1| <= 1e-2, exact parabola, elliptic beyond the
+    series): branch by branch the libm-level restatement with the fast primitives -- same NaN pattern, true anomalies to the bands'
+    conditioning (3e-13 rad at worst: the Newton solves stop at a step of 1.5e-8 in D, as the reference's)."""
+    rs = np.random.RandomState(6)
+    m = 20000
+    ecc = np.concatenate([rs.uniform(0.9901, 0.99999, m // 4), rs.uniform(1.00001, 1.0099, m // 4), rs.uniform(0.3, 0.9899, m // 4),
+                          1 + 10.0 ** rs.uniform(-9, -2.1, m // 4) * rs.choice([-1, 1], m // 4)])
+    ecc[-3:] = [1.0, 1.0, np.nan]
+    q = rs.uniform(6.8e6, 3e7, m)
+    with np.errstate(invalid="ignore"):
+        nu_max = np.where(ecc > 1, 0.95 * np.arccos(-1 / np.maximum(ecc, 1.000001)), 3.1)
+    nu = rs.uniform(-1, 1, m) * nu_max
+    nu[:50] = np.sign(nu[:50]) * 3.1                                  # next to the wrap
+    nu[m // 4:m // 4 + 50] = 0.5 * (nu_max[m // 4:m // 4 + 50] / 0.95 + np.pi)   # between the asymptote and pi: NaN (:885-888)
+    for tof in (20.0, 150.0, 5400.0):
+        fast, libm = mm.band(nu, ecc, q, tof)
+        assert np.array_equal(np.isfinite(fast), np.isfinite(libm)) and np.isnan(fast[m // 4:m // 4 + 50]).all() and np.isnan(fast[-1])
+        both = np.isfinite(fast)
+        d = np.abs(fast - libm)[both]
+        d = np.minimum(d, np.abs(d - 2 * np.pi))
+        assert d.max() < 2e-12 and np.quantile(d, 0.99) < 1e-13, (tof, d.max())
+    # log_pos is total: the special arguments libm's log handles
+    xs = np.array([1.0, 2.0, 1e-320, 5e-324, 1e308, 0.0, -1.0, np.inf, np.nan, 0.7, 1e-300])
+    r = mm.log_pos(xs)
+    with np.errstate(all="ignore"):
+        want = np.log(xs)
+    assert np.array_equal(np.isnan(r), np.isnan(want)) and np.array_equal(np.isinf(r), np.isinf(want))
+    ok = np.isfinite(want)
+    assert np.abs(r[ok] - want[ok]).max() <= 2e-16 * np.abs(want[ok]).max() + 2e-16
+
+
+def check_elements_strong_elliptic_chain_vs_reference_golden(mm, idt):
+    g = golden("kepler_golden.npz")
+    y, ok = mm.propagate(g["x"], float(g["dts"][idt]), 0)
+    assert ok.all() and np.isfinite(y).all()        # incl. the exactly equatorial / circular rows: acos(h_z / |h|) must see exactly 1
+    ref = g["y"][idt]
+    inc = g["inter"][idt][:, 2]
+    good = (inc > 1e-3) | (inc < 1e-8)
+    assert relnorm(y, ref, slice(0, 3))[good].max() < 2e-12 and relnorm(y, ref, slice(3, 6))[good].max() < 2e-12
+    assert relnorm(y, ref, slice(0, 3)).max() < 5e-10 and relnorm(y, ref, slice(3, 6)).max() < 2e-9
+
+
+def check_fast_sincos_and_reciprocals(mm):
+    rs = np.random.RandomState(1)
+    x = np.concatenate([rs.uniform(-63.9, 63.9, 200000), [0.0, np.pi / 2, -np.pi, np.pi, 2 * np.pi, 1e-300, 100.0, -1e6]])
+    s, c = mm.sincos(x)
+    ls, lc = np.sin(x.astype(np.longdouble)), np.cos(x.astype(np.longdouble))
+    # 1.5 ulp for results of ordinary size; next to a zero of sin / cos the two-part reduction leaves an ABSOLUTE error of
+    # ~1e-17 (libm reduces further): the element chain only multiplies these by O(1) quantities
+    es = np.abs((s - ls).astype(np.float64)) / np.spacing(np.maximum(np.abs(ls.astype(np.float64)), 1e-2))
+    ec = np.abs((c - lc).astype(np.float64)) / np.spacing(np.maximum(np.abs(lc.astype(np.float64)), 1e-2))
+    assert es[:-2].max() < 2.0 and ec[:-2].max() < 2.0, (es.max(), ec.max())
+    assert np.abs((s - ls).astype(np.float64))[-2:].max() < 1e-15          # |x| >= 64: the libm branch
+    v = 10.0 ** rs.uniform(-8, 20, 100000)
+    r, q = mm.recip(v)
+    assert np.abs(r * v - 1).max() < 4.5e-16 and np.abs(q * q * v - 1).max() < 9e-16     # from a 1e-8 estimate: third order
+
+
+def check_fast_atan2(mm):
+    """atan2_fast (azimuth, and elevation as atan2(u, hypot(e, n))): error < 1.5 ulp (6e-16 at pi) over every octant, the fold points
+    and the axes; atan2(0, 0) = 0 and the sign conventions of libm (azimuth wraps to [0, 2 pi) from those)."""
+    rs = np.random.RandomState(2)
+    ang = rs.uniform(-np.pi, np.pi, 300000)
+    rad = 10.0 ** rs.uniform(-3, 8, len(ang))
+    y = np.concatenate([rad * np.sin(ang), [0.0, 0.0, 0.0, 1.0, -1.0, 1.0, 1.0, -1.0, np.tan(np.pi / 8), 1e-300, 3.0]])
+    x = np.concatenate([rad * np.cos(ang), [0.0, 1.0, -1.0, 0.0, 0.0, 1.0, -1.0, -1.0, 1.0, 1.0, 1e300]])
+    r = mm.atan2(y, x)
+    ref = np.arctan2(y.astype(np.longdouble), x.astype(np.longdouble))
+    err = np.abs((r - ref).astype(np.float64))
+    assert err.max() < 6e-16 and (err / np.spacing(np.maximum(np.abs(r), 0.5))).max() < 1.5, (err.max(), np.argmax(err))
+    small = np.abs(ref) < 0.3
+    assert (err[small] / np.maximum(np.abs(ref[small]).astype(np.float64), 1e-300)).max() < 5e-16   # relative where the angle is small
+    assert r[-11] == 0.0 and r[-10] == 0.0 and r[-9] == np.pi and r[-8] == np.pi / 2 and r[-7] == -np.pi / 2
+    # elevation: asin(u / r) == atan2(u, hypot(e, n))
+    e, n, u = rs.normal(size=(3, 100000)) * 1e6
+    el = mm.atan2(u, np.hypot(e, n))
+    el_, nl, ul = (v.astype(np.longdouble) for v in (e, n, u))
+    ref = np.arcsin(ul / np.sqrt(el_ * el_ + nl * nl + ul * ul))      # (in fp64 asin(u / r) itself loses digits towards the zenith)
+    assert np.abs((el - ref).astype(np.float64)).max() < 4e-16
+
+
+def check_fast_exp(mm):
+    """exp_fast on [0, 700) (the hyperbolic Stumpff functions of the general solver): < 2 ulp."""
+    rs = np.random.RandomState(3)
+    x = np.concatenate([rs.uniform(0.0, 700.0, 200000), rs.uniform(0.0, 2.0, 50000), [0.0, 0.5, np.log(2.0) / 2, 699.999]])
+    r = mm.exp(x)
+    ref = np.exp(x.astype(np.longdouble))
+    assert (np.abs((r - ref) / ref).astype(np.float64)).max() < 4.5e-16

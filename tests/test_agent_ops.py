@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import golden
+from support.gpu import namespace
 
 EPS = np.finfo(np.float64).eps
 N_TIME = 480
@@ -229,17 +230,8 @@ def shannon_criterion(dev, P, Pp, tag, classes=None):
 # ------------------------------------------------------------------ GPU
 @pytest.fixture(scope="module")
 def hip():
-    import torch
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib, device, engine, host
-    ssa_gym_amd.build()
-    _lib.load()
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-
-    class H:
-        pass
-    h = H()
-    h.torch, h.lib, h.dev, h.host, h.engine = torch, _lib, device, host, engine
+    h = namespace()
+    torch, device, host = h.torch, h.dev, h.host
     h.up = lambda a, dtype=torch.float64: device.as_dev(np.ascontiguousarray(a), "cuda", dtype)
     g = golden("ukf_step_golden.npz")
     h.g = g

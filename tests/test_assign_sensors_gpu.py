@@ -9,11 +9,9 @@ per-step path: the row read back (or the yardstick's row) followed by launch_ste
 import numpy as np
 import pytest
 
-from test_hip_step import c2t, hip, make_batch  # noqa: F401  (hip: the module fixture)
-from test_lookahead_sensors_gpu import _cfg as _cfg8
-from test_rollout_sensors_gpu import BAD, N_TIME, _assert_same_env, _compare, _same
-from test_sensors_gpu import _cfg, _distinct, envs  # noqa: F401  (envs: the module fixture)
-from test_sensors_host import sites_rad
+from support.batches import c2t, make_batch
+from support.gpu import envs, hip  # noqa: F401  (the module fixtures)
+from support.sensors import BAD, N_TIME, _assert_same_env, _compare, _distinct, _same, cfg3, cfg8, sites_rad
 
 pytestmark = pytest.mark.gpu
 
@@ -267,7 +265,7 @@ def test_real_lookaheads_equal_the_yardstick(envs, propagator, sensors, regime):
     import torch
     from ssa_gym_amd import _lib
     over = dict(propagator=propagator, storage_layout='regime' if regime else None)
-    env = envs.make('ssa_tasker_simple-v2', config=_cfg8(envs, sensors=sensors, **over))
+    env = envs.make('ssa_tasker_simple-v2', config=cfg8(envs, sensors=sensors, **over))
     e, S = env._engine, env.n_sensor
     assert (e._order is not None) == regime and S == sensors
     rs = np.random.RandomState(31)
@@ -402,8 +400,8 @@ def test_env_run_agent_sensors_equals_a_step_loop(envs, reward_type, obs_returne
     step() on both, then n_steps beyond the episode's end.  sensors = 0: no config['observers'], the env's one observer as a network."""
     from ssa_gym_amd import agents
     over = dict(steps=48, history=16, reward_type=reward_type, obs_returned=obs_returned, sensors=sensors)
-    a = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, **over))
-    b = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, **over))
+    a = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, **over))
+    b = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, **over))
     col = type(b).SENSOR_AGENT_COLUMNS[agent]
     S = b.n_sensor
     assert b._engine.H == 16 and S == max(sensors, 1)
@@ -434,7 +432,7 @@ def test_env_run_agent_sensors_equals_a_step_loop(envs, reward_type, obs_returne
 def test_env_run_agent_sensors_default_fallback_and_idle_sensors(envs):
     """the default fallback rows (one action_space.sample() per row; env.np_random untouched) with a site that sees nothing: its sensor
     takes the draw unless another sensor holds that object, and is then booked idle (-1, no update record)"""
-    a = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, steps=48, history=16, sensor_obs_limit=[15, 10, 90]))
+    a = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, steps=48, history=16, sensor_obs_limit=[15, 10, 90]))
     a.action_space.seed(11)
     draws = a.np_random.get_state()[2]
     fb = np.stack([_distinct(np.random.RandomState(k), a.m, 3) for k in range(13)])
@@ -455,7 +453,7 @@ def test_engine_and_env_refuse_malformed_inputs(envs):
     block, float32); run_agent_sensors names the shape it wants when the fallback rows are too few or not rows of S; the env is untouched"""
     import torch
     from ssa_gym_amd import _lib
-    env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, steps=48, history=16))
+    env = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, steps=48, history=16))
     e, S = env._engine, env.n_sensor
     look = e.launch_lookahead_sensors(env.i % e.H, env.i + 1, env._sites())
     row = e.assign_row()
@@ -477,8 +475,8 @@ def test_env_run_agent_sensors_late_in_an_episode(envs):
     """20 000 objects, three sites, 'hybrid': both envs advanced by the same 300 step() calls; then 60 steps of the closed loop against the
     twin's host loop, with filters failing inside the window (asserted on the twin)"""
     from ssa_gym_amd import _lib
-    a = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, m=20000, history=64))
-    b = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, m=20000, history=64))
+    a = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, m=20000, history=64))
+    b = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, m=20000, history=64))
     for env in (a, b):
         rs = np.random.RandomState(7)
         for _ in range(300):

@@ -1,31 +1,23 @@
 """CPU-only checks of a sensor network's device-side assignment (include/ssa_hip.h: ssa_assign_sensors_f64;
 SSA_Tasker_Env.run_agent_sensors): the exports, refusal of bad arguments before any launch, the env's guards without device state, and
 the new kernel's resource budget in the shipped code object."""
-import os
 import re
 
 import pytest
 
-from conftest import ROOT
-from test_sensors_host import _bare_env
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib
-    ssa_gym_amd.build()
-    return _lib.load()
+from support.codeobj import _kernels, header
+from support.gpu import lib  # noqa: F401  (the module fixture)
+from support.sensors import _bare_env
 
 
 def test_assignment_is_exported_and_declared(lib):
     from ssa_gym_amd import _lib
-    header = open(os.path.join(ROOT, "include", "ssa_hip.h")).read()
-    assert re.search(r"\bint ssa_assign_sensors_f64\s*\(", header)
-    assert re.search(r"\bint64_t ssa_assign_sensors_workspace_bytes\s*\(", header)
+    hdr = header()
+    assert re.search(r"\bint ssa_assign_sensors_f64\s*\(", hdr)
+    assert re.search(r"\bint64_t ssa_assign_sensors_workspace_bytes\s*\(", hdr)
     for name in ("ssa_assign_sensors_f64", "ssa_assign_sensors_workspace_bytes"):
         assert name in _lib.SIGNATURES and hasattr(lib, name), name
-    assert re.search(r"#define SSA_ABI_VERSION 23\b", header)
+    assert re.search(r"#define SSA_ABI_VERSION 23\b", hdr)
     assert lib.ssa_abi_version() == _lib.ABI_VERSION == 23          # (additive: the ABI version stays)
 
 
@@ -87,7 +79,6 @@ def test_assign_kernel_budget(tmp_path):
     CUs -- so occupancy never limits it; the bound is the 128 VGPRs at which a SIMD still holds four wavefronts, i.e. a CU four whole
     workgroups, more than the grid puts on one CU below half a million objects.  (Forcing 64 VGPRs -- eight wavefronts per SIMD, which
     nothing here needs -- made the compiler spill.)"""
-    from test_abi_and_host import _kernels
     kern, ins_of = _kernels(tmp_path)
     names = [k for k in kern if "assign_sensors_kernel" in k]
     assert len(names) == 1, names

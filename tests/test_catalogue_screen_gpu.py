@@ -1,7 +1,7 @@
 """The visibility screen of a synthetic catalogue on the MI355X (include/ssa_hip.h: ssa_catalogue_screen_f64; catalogue.visible_catalogue,
 catalogue_for_config).
 
-The ground truth is the numpy rule: catalogue._accepted for one site and its network restatement (test_catalogue_screen_host.screen_numpy,
+The ground truth is the numpy rule: catalogue._accepted for one site and its network restatement (tests/support/screen.py: screen_numpy,
 equal to _accepted bit for bit with one site).  The library is built with -ffp-contract=fast, so the kernel's intermediate values are not
 numpy's bits; the contract is equal decisions (accept, worst gap, flags) for every candidate whose numpy margin is at least 1e-9 rad of
 elevation and 1e-3 m of altitude at every sample.  The draw loop on top must then give the rows of the numpy path exactly."""
@@ -10,23 +10,12 @@ from datetime import datetime
 import numpy as np
 import pytest
 
-from test_catalogue_screen_host import _SITES3, screen_numpy, site_rows
+from support.gpu import dev  # noqa: F401  (the module fixture)
+from support.screen import _SITES3, screen_numpy, site_rows
 
 pytestmark = pytest.mark.gpu
 
 EL_EPS, ALT_EPS = 1e-9, 1e-3
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib, device
-    ssa_gym_amd.build()
-    _lib.load()
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return device
 
 
 def _site_tab(sites, masks):

@@ -10,66 +10,9 @@ from datetime import datetime
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def screen_numpy(a, ecc, inc, raan, argp, nu, M_t, times, sites, first, max_gap, min_alt=300e3):
-    """catalogue._accepted generalised to a network: `sites` = [(enu 3x3, obs_itrs 3, el_min rad)] * S, a sample is visible if any site
-    sees it.  Returns (accept, worst_gap, flags, el_margin, alt_margin): flags bit 0 altitude ok, bit 1 visible in [0, first), bit 2
-    always visible; el_margin = min over samples and sites of |el - el_min| [rad], alt_margin = min over samples of |alt - min_alt| [m]
-    (how far numpy's own decisions are from flipping)."""
-    from ssa_gym_amd.catalogue import MU, WGS84_A, WGS84_F
-    k = len(a)
-    cO, sO, ci, si, cw, sw = np.cos(raan), np.sin(raan), np.cos(inc), np.sin(inc), np.cos(argp), np.sin(argp)
-    P = np.stack([cO * cw - sO * ci * sw, sO * cw + cO * ci * sw, si * sw], axis=1)
-    Q = np.stack([-cO * sw - sO * ci * cw, -sO * sw + cO * ci * cw, si * cw], axis=1)
-    E0 = 2.0 * np.arctan2(np.sqrt(1 - ecc) * np.sin(nu / 2), np.sqrt(1 + ecc) * np.cos(nu / 2))
-    M0 = E0 - ecc * np.sin(E0)
-    n = np.sqrt(MU / a ** 3)
-    b = a * np.sqrt(1 - ecc ** 2)
-    ok_alt = np.ones(k, dtype=bool)
-    el_margin, alt_margin = np.full(k, np.inf), np.full(k, np.inf)
-    vis = np.empty((len(times), k), dtype=bool)
-    for i, t in enumerate(times):
-        M = M0 + n * t
-        E = M + ecc * np.sin(M)
-        for _ in range(12):
-            E = E - (E - ecc * np.sin(E) - M) / (1 - ecc * np.cos(E))
-        r = (a * (np.cos(E) - ecc))[:, None] * P + (b * np.sin(E))[:, None] * Q
-        x = r @ M_t[i].T
-        rn = np.linalg.norm(x, axis=1)
-        lat = np.arcsin(x[:, 2] / rn)
-        alt = rn - WGS84_A * (1 - WGS84_F * np.sin(lat) ** 2)
-        ok_alt &= alt > min_alt
-        alt_margin = np.fmin(alt_margin, np.abs(alt - min_alt))
-        v = np.zeros(k, dtype=bool)
-        for enu, obs_itrs, el_min in sites:
-            d = x - obs_itrs
-            up = d @ enu[:, 2]
-            el = np.arcsin(up / np.linalg.norm(d, axis=1))
-            v |= el >= el_min
-            el_margin = np.fmin(el_margin, np.abs(el - el_min))
-        vis[i] = v
-    run = np.zeros(k, dtype=np.int64)
-    worst = np.zeros(k, dtype=np.int64)
-    for i in range(len(times)):
-        run = np.where(vis[i], 0, run + 1)
-        worst = np.maximum(worst, run)
-    always = vis.all(axis=0)
-    first_vis = vis[:first].any(axis=0)
-    accept = ok_alt & (always | (first_vis & (worst < max_gap)))
-    flags = ok_alt.astype(np.uint8) | (first_vis.astype(np.uint8) << 1) | (always.astype(np.uint8) << 2)
-    return accept, worst, flags, el_margin, alt_margin
-
-
-def site_rows(sites, el_min_deg):
-    """screen_numpy's `sites` for (lat, lon, h) sites in degrees, degrees, metres and per-site masks in degrees"""
-    from ssa_gym_amd import host
-    out = []
-    for s, lim in zip(sites, el_min_deg):
-        lla = np.array(s) * [host.deg2rad, host.deg2rad, 1]
-        out.append((host.enu_matrix(lla), host.lla2ecef(lla), np.radians(lim)))
-    return out
+from conftest import ROOT
+from support.codeobj import header
+from support.screen import _SITES3, screen_numpy, site_rows
 
 
 def test_screen_params_layout_matches_the_header(tmp_path):
@@ -89,7 +32,7 @@ def test_screen_params_layout_matches_the_header(tmp_path):
     exe = tmp_path / "screen_layout"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(c)])
     assert [int(v) for v in subprocess.check_output([str(exe)]).decode().split()] == want
-    hdr = open(os.path.join(ROOT, "include", "ssa_hip.h")).read()
+    hdr = header()
     assert re.search(r"\bint ssa_catalogue_screen_f64\s*\(const ssa_screen_params \*p, void \*stream\);", hdr)
     assert "ssa_catalogue_screen_f64" in _lib.SIGNATURES
     assert int(re.search(r"#define SSA_MAX_SENSORS\s+(\d+)", hdr).group(1)) == catalogue.MAX_SITES
@@ -112,9 +55,6 @@ def test_numpy_restatement_equals_accepted_with_one_site():
         assert np.array_equal(got, want), k
         n_acc += int(want.sum())
     assert n_acc > 100      # the comparison covers accepted candidates too (GEO, Tundra, Molniya pass often)
-
-
-_SITES3 = [(20.7083, -156.2575, 3058.0), (-35.4014, 148.9817, 680.0), (28.3, -16.5097, 2390.0)]   # Maui, Canberra, Tenerife
 
 
 @pytest.mark.parametrize("kw", [

@@ -14,10 +14,11 @@ import numpy as np
 import pytest
 
 from conftest import golden
-from test_device_math_host import (_conic_states, build_devmath, check_conic_branches_lean_form_vs_restatements_and_oracle,
-                                   check_elements_strong_elliptic_chain_vs_reference_golden, check_fast_atan2, check_fast_exp,
-                                   check_fast_sincos_and_reciprocals, check_fg_hyperbolic_and_near_parabolic_states,
-                                   check_fg_universal_solvers_vs_reference_golden, check_near_parabolic_bands_fast_vs_libm)
+from support.devmath import (_conic_states, build_devmath, check_conic_branches_lean_form_vs_restatements_and_oracle,
+                             check_elements_strong_elliptic_chain_vs_reference_golden, check_fast_atan2, check_fast_exp,
+                             check_fast_sincos_and_reciprocals, check_fg_hyperbolic_and_near_parabolic_states,
+                             check_fg_universal_solvers_vs_reference_golden, check_near_parabolic_bands_fast_vs_libm)
+from support.gpu import namespace
 
 pytestmark = pytest.mark.gpu
 
@@ -104,13 +105,8 @@ def dm():
 
 @pytest.fixture(scope="module")
 def hip():
-    import torch
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib, device
-    ssa_gym_amd.build()
-    _lib.load()
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-    return device, torch
+    h = namespace()
+    return h.dev, h.torch
 
 
 # ------------------------------------------------------------------ the host pins, on the device (bounds unchanged)

@@ -5,16 +5,14 @@ import pytest
 
 import oracle as orc
 from conftest import golden
+from support.gpu import namespace
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def envs():
-    import torch
-    import ssa_gym_amd
-    ssa_gym_amd.build()
-    assert torch.cuda.is_available()
+    namespace()
     from ssa_gym_amd import envs as E
     return E
 

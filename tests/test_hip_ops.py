@@ -10,29 +10,17 @@ import pytest
 
 import oracle as orc
 from conftest import golden
+from support.batches import relnorm
+from support.gpu import namespace
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def hip():
-    import torch
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib, device, host
-    ssa_gym_amd.build()
-    _lib.load()
-    assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
-
-    class H:
-        pass
-    h = H()
-    h.torch, h.lib, h.dev, h.host = torch, _lib, device, host
-    h.up = lambda a, dtype=torch.float64: device.as_dev(np.ascontiguousarray(a), "cuda", dtype)
+    h = namespace()
+    h.up = lambda a, dtype=h.torch.float64: h.dev.as_dev(np.ascontiguousarray(a), "cuda", dtype)
     return h
-
-
-def relnorm(a, b, sl):
-    return np.linalg.norm((a - b)[..., sl], axis=-1) / np.linalg.norm(b[..., sl], axis=-1)
 
 
 def default_consts(host, alpha=1e-4, obs_type='aer', propagator='fg', resample=False, obs_limit=-np.pi / 2, dt=20.0):

@@ -17,50 +17,10 @@ import pytest
 
 import oracle as orc
 from conftest import golden
+from support.batches import c2t, errs, make_batch
+from support.gpu import hip  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib, device, host, engine
-    ssa_gym_amd.build()
-    _lib.load()
-    assert torch.cuda.is_available()
-
-    class H:
-        pass
-    h = H()
-    h.torch, h.lib, h.dev, h.host, h.engine = torch, _lib, device, host, engine
-    return h
-
-
-C2T = None
-
-
-def c2t():
-    global C2T
-    if C2T is None:
-        C2T = golden("c2t_2020-05-04_dt20_n480.npy")
-    return C2T
-
-
-def make_batch(m, seed, tight_fraction=0.0):
-    rs = np.random.RandomState(seed)
-    cat = golden("catalogue_subset.npy")
-    g = golden("ukf_step_golden.npz")
-    xt = cat[rs.randint(0, len(cat), m)]
-    x = xt + rs.normal(size=(m, 6)) * np.array([1e5] * 3 + [1e2] * 3)
-    P = np.tile(g["P0"], (m, 1, 1))
-    if tight_fraction > 0:
-        # posterior-like covariances (after an az/el/range update): sample from the golden posteriors
-        k = rs.uniform(size=m) < tight_fraction
-        idx = rs.randint(0, 64, m)
-        P[k] = 0.5 * (g["Pu_a3"][idx[k]] + np.swapaxes(g["Pu_a3"][idx[k]], 1, 2))
-        x[k] = xt[k] + rs.normal(size=(k.sum(), 6)) * np.array([30.0] * 3 + [0.05] * 3)
-    return xt, x, P, g
 
 
 def run_gpu(hip, xt, x, P, g, action, tix, alpha, obs_type='aer', propagator='fg', resample=False,
@@ -99,15 +59,6 @@ def run_oracle(o, xt, x, P, g, action, tix, alpha, obs_type=0, centred=False, re
                    obs_limit, z_noise3, obs_type=obs_type, centred=centred, resample=resample)
     r["status"] = st
     return r
-
-
-def errs(a, b):
-    """per-object relative error of position / velocity blocks and sd-normalised covariance error"""
-    ep = np.linalg.norm((a["x"] - b["x"])[:, :3], axis=1) / np.linalg.norm(b["x"][:, :3], axis=1)
-    ev = np.linalg.norm((a["x"] - b["x"])[:, 3:], axis=1) / np.linalg.norm(b["x"][:, 3:], axis=1)
-    sd = np.sqrt(np.abs(np.einsum('jii->ji', b["P"])))
-    eP = np.max(np.abs(a["P"] - b["P"]) / (sd[:, :, None] * sd[:, None, :]), axis=(1, 2))
-    return ep, ev, eP
 
 
 def assert_states_close(a, b, tol, what=""):

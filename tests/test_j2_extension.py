@@ -5,27 +5,10 @@ import numpy as np
 import pytest
 
 from conftest import golden
+from support.batches import relnorm
+from support.gpu import hip  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib, device, host, engine
-    ssa_gym_amd.build()
-    assert torch.cuda.is_available()
-
-    class H:
-        pass
-    h = H()
-    h.torch, h.lib, h.dev, h.host, h.engine = torch, _lib, device, host, engine
-    return h
-
-
-def relnorm(a, b, sl):
-    return np.linalg.norm((a - b)[..., sl], axis=-1) / np.linalg.norm(b[..., sl], axis=-1)
 
 
 def test_rk4_j2_vs_dop853(hip):

@@ -8,30 +8,20 @@ OTHER object, and status / visible equal to the step's status word and update re
 import numpy as np
 import pytest
 
+from support.batches import c2t, errs, make_batch
+from support.gpu import envs  # noqa: F401  (the module fixture)
+
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def envs():
-    import torch
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib
-    ssa_gym_amd.build()
-    _lib.load()
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from ssa_gym_amd import envs as E
-    return E
-
-
-def _cfg(E, **over):
+def cfg1(E, **over):
     cfg = dict(E.env_config)
     cfg.update(rso_count=2000, steps=480, obs_limit=15, reward_type='trinary', obs_returned='flatten', seed=3)
     cfg.update(over)
     return cfg
 
 
-def _xyz(E):
+def xyz1(E):
     from ssa_gym_amd.envs import dynamics as D
     return dict(obs_type='xyz', z_sigma=(5e2,) * 3, R=np.diag([5e2 ** 2] * 3), hx=D.hx_xyz, mean_z=D.mean_xyz, residual_z=np.subtract)
 
@@ -119,7 +109,7 @@ def check_against_step(env, n=64, seed=0):
 
 def test_bit_identical_to_step_hybrid_20000_early_and_late(envs):
     """the default 'hybrid' env at 20 000 objects: an early step, and a late one (>= 300) where filters are diverging"""
-    env = envs.make(config=_cfg(envs, rso_count=20000, seed=1))
+    env = envs.make(config=cfg1(envs, rso_count=20000, seed=1))
     env.step(5)
     env.step(17)
     check_against_step(env, n=64, seed=1)
@@ -134,8 +124,8 @@ def test_bit_identical_to_step_hybrid_20000_early_and_late(envs):
 def test_bit_identical_to_step_variants(envs, variant):
     from ssa_gym_amd.envs import dynamics as D
     over = {"fg": dict(fx=D.fx_xyz_farnocchia_fg), "elements": dict(fx=D.fx_xyz_farnocchia_elements), "j2": dict(fx=D.fx_xyz_j2_rk4),
-            "xyz": _xyz(envs), "resample": dict(resample_sigmas=True)}[variant]
-    env = envs.make(config=_cfg(envs, seed=11, **over))
+            "xyz": xyz1(envs), "resample": dict(resample_sigmas=True)}[variant]
+    env = envs.make(config=cfg1(envs, seed=11, **over))
     env.step(3)
     check_against_step(env, n=64, seed=3)
     env.run_agent('agent_visible_greedy', 200)
@@ -144,7 +134,7 @@ def test_bit_identical_to_step_variants(envs, variant):
 
 def test_update_interval_update_and_skipped_step(envs):
     from ssa_gym_amd import _lib
-    env = envs.make(config=_cfg(envs, seed=12, update_interval=3))
+    env = envs.make(config=cfg1(envs, seed=12, update_interval=3))
     env.step(1)                                   # i = 1: the next step (2) is skipped by the interval
     look, _ = check_against_step(env, n=64, seed=5)
     assert not look["visible"].any() and np.isnan(look["score"]).all()
@@ -157,7 +147,7 @@ def test_update_interval_update_and_skipped_step(envs):
 def test_no_side_effects_on_an_episode(envs):
     """one episode of 120 steps with lookahead() before every step and the same episode without: bit-identical"""
     import torch
-    cfg = _cfg(envs, seed=21, steps=130)
+    cfg = cfg1(envs, seed=21, steps=130)
     a, b = envs.make(config=cfg), envs.make(config=cfg)
     rs = np.random.RandomState(4)
     acts = rs.randint(0, cfg['rso_count'], 120)
@@ -188,7 +178,6 @@ def test_against_the_oracle(envs, oracle, oracle_ld):
     value as the reference arithmetic, on every object (factor 3 on median and maximum), as check_parity applies it."""
     import torch
     import oracle as orc
-    from test_hip_step import c2t, errs, make_batch
     from ssa_gym_amd import engine, host
     m, alpha, tix = 2000, 1e-3, 1
     xt, x, P, g = make_batch(m, seed=1)
@@ -229,7 +218,7 @@ def test_scores_from_the_returned_covariances(envs):
     run.  The information gain is also NaN where the plain Cholesky factorisation of P- or P+ fails (a covariance that is not positive
     definite in fp64 -- diverged filters), as agent_shannon's log-det ratio is"""
     from ssa_gym_amd import _lib
-    env = envs.make(config=_cfg(envs, rso_count=20000, seed=41))
+    env = envs.make(config=cfg1(envs, rso_count=20000, seed=41))
     env.run_agent('agent_visible_greedy', 320)
     look = _look_np(env)
     ok = (look["status"] == 0) & (look["visible"] == 1)
@@ -274,7 +263,7 @@ def test_layout_and_vector_env(envs):
     """a storage layout never shows; each env of a vector env equals a single env with the same state"""
     import torch
     from ssa_gym_amd.envs.vector_env import SSA_Tasker_VecEnv
-    cfg = _cfg(envs, seed=51)
+    cfg = cfg1(envs, seed=51)
     plain, lay = envs.make(config=cfg), envs.make(config=dict(cfg, storage_layout='regime'))
     acts = np.random.RandomState(5).randint(0, cfg['rso_count'], 40)
     for a in acts:
@@ -310,7 +299,7 @@ def test_layout_and_vector_env(envs):
 
 def test_agents(envs):
     from ssa_gym_amd import _lib, agents
-    env = envs.make(config=_cfg(envs, seed=61))
+    env = envs.make(config=cfg1(envs, seed=61))
     env.step(2)
     for agent, row in ((agents.agent_info_gain, _lib.LOOK_INFO_GAIN), (agents.agent_trace_gain, _lib.LOOK_TRACE_GAIN)):
         a = agent(None, env)
@@ -320,7 +309,7 @@ def test_agents(envs):
     with pytest.raises(NotImplementedError):
         env.run_agent(agents.agent_info_gain, 5)
     # nothing finite: nothing visible -> action_space.sample()
-    blind = envs.make(config=_cfg(envs, seed=62, obs_limit=90))
+    blind = envs.make(config=cfg1(envs, seed=62, obs_limit=90))
     blind.action_space.seed(123)
     want = blind.action_space.sample()
     blind.action_space.seed(123)
@@ -329,7 +318,7 @@ def test_agents(envs):
     # whole episodes
     results = {}
     for agent in (agents.agent_info_gain, agents.agent_trace_gain, agents.agent_visible_greedy):
-        ep = envs.make(config=_cfg(envs, seed=63))
+        ep = envs.make(config=cfg1(envs, seed=63))
         obs, done, k = None, False, 0
         while not done:
             obs, r, done, _ = ep.step(agent(obs, ep))

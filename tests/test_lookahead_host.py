@@ -8,23 +8,13 @@ import subprocess
 import pytest
 
 from conftest import ROOT
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib
-    ssa_gym_amd.build()
-    return _lib.load()
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "ssa_hip.h")).read()
+from support.codeobj import _kernels, header, stray_scratch
+from support.gpu import lib  # noqa: F401  (the module fixture)
 
 
 def test_lookahead_is_exported_and_declared(lib):
     from ssa_gym_amd import _lib
-    assert re.search(r"\bssa_lookahead_f64\s*\(", _header())
+    assert re.search(r"\bssa_lookahead_f64\s*\(", header())
     assert "ssa_lookahead_f64" in _lib.SIGNATURES
     assert hasattr(lib, "ssa_lookahead_f64")
     assert lib.ssa_abi_version() == _lib.ABI_VERSION == 23
@@ -45,7 +35,7 @@ def test_lookahead_out_layout_and_constants_match_the_header(lib, tmp_path):
     exe = tmp_path / "look"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(c)])
     assert [int(v) for v in subprocess.check_output([str(exe)]).decode().split()] == want
-    hdr = _header()
+    hdr = header()
     for name in ("LOOK_NSCORE", "LOOK_TRACE_GAIN", "LOOK_POS_TRACE_GAIN", "LOOK_INFO_GAIN"):
         m = re.search(r"#define SSA_%s\s+(\d+)" % name, hdr)
         assert m and int(m.group(1)) == getattr(_lib, name), name
@@ -73,7 +63,6 @@ def test_env_lookahead_has_no_cpu_fallback(lib):
 def test_lookahead_kernels_keep_the_step_kernels_budget(tmp_path):
     """the lookahead instances fit the step kernel's register budget and LDS, and touch scratch only where the step kernel does:
     the save / restore around the out-of-line calls of SSA_PROP_ELEMENTS / SSA_PROP_HYBRID -- none on the common path"""
-    from test_abi_and_host import _kernels, stray_scratch
     kern, ins_of = _kernels(tmp_path)
     look = [k for k in kern if "lookahead_kernel" in k]
     assert len(look) == 8, look                    # 4 propagators x {one tile, multi tile}

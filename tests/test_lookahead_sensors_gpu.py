@@ -9,40 +9,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_sensors_gpu import SITES, _Relaunch, _distinct
+from support.gpu import envs  # noqa: F401  (the module fixture)
+from support.sensors import _advance, _distinct, _Relaunch, cfg8, xyz_net
 
 pytestmark = pytest.mark.gpu
-
-SITES8 = SITES + [(51.5, -0.1, 50.0), (35.7, 139.7, 40.0), (-33.9, 18.4, 10.0), (64.8, -147.7, 150.0), (19.8, -155.5, 4200.0)]
-
-
-@pytest.fixture(scope="module")
-def envs():
-    import torch
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib
-    ssa_gym_amd.build()
-    _lib.load()
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from ssa_gym_amd import envs as E
-    return E
-
-
-def _cfg(E, m=2000, sensors=3, **over):
-    cfg = dict(E.env_config)
-    cfg.update(rso_count=m, steps=480, obs_limit=15, reward_type='trinary', obs_returned='flatten', seed=3)
-    if sensors:
-        cfg.update(observers=SITES8[:sensors], sensor_obs_limit=[15, 10, 20, 12, 18, 8, 25, 15][:sensors],
-                   sensor_z_sigma=[(1 + 0.5 * k, 1 + 0.5 * k, 1e3 / (1 + k)) for k in range(sensors)])
-    cfg.update(over)
-    return cfg
-
-
-def _xyz():
-    from ssa_gym_amd.envs import dynamics as D
-    return dict(obs_type='xyz', z_sigma=(5e2,) * 3, R=np.diag([5e2 ** 2] * 3), hx=D.hx_xyz, mean_z=D.mean_xyz, residual_z=np.subtract,
-                sensor_z_sigma=[(5e2,) * 3, (3e2,) * 3, (8e2,) * 3])
 
 
 def _np(r):
@@ -122,16 +92,11 @@ def check_against_step(env, net, rs, n=24):
     return seen
 
 
-def _advance(env, rs, k):
-    for _ in range(k):
-        env.step(_distinct(rs, env.m, env.n_sensor) if env.n_sensor > 1 else int(rs.randint(env.m)))
-
-
 @pytest.mark.parametrize("S", [3, 8])
 def test_slices_and_step_at_20000_early_and_late(envs, S):
     """20 000 objects, 'hybrid': step 2, and a step past 300 with failed filters -- every slice against the single-sensor lookahead,
     sampled pairs against the sensor step"""
-    env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, m=20000, sensors=S))
+    env = envs.make('ssa_tasker_simple-v2', config=cfg8(envs, m=20000, sensors=S))
     rs = np.random.RandomState(S)
     _advance(env, rs, 2)
     net = check_slices(env)
@@ -145,8 +110,8 @@ def test_slices_and_step_at_20000_early_and_late(envs, S):
 
 @pytest.mark.parametrize("variant", ["fg", "elements", "j2", "xyz"])
 def test_slices_for_the_other_propagators_and_xyz(envs, variant):
-    over = _xyz() if variant == "xyz" else dict(propagator=variant)
-    env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, **over))
+    over = xyz_net() if variant == "xyz" else dict(propagator=variant)
+    env = envs.make('ssa_tasker_simple-v2', config=cfg8(envs, **over))
     rs = np.random.RandomState(11)
     _advance(env, rs, 3)
     net = check_slices(env)
@@ -154,7 +119,7 @@ def test_slices_for_the_other_propagators_and_xyz(envs, variant):
 
 
 def test_update_interval_on_an_update_step_and_a_skipped_step(envs):
-    env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, update_interval=3))
+    env = envs.make('ssa_tasker_simple-v2', config=cfg8(envs, update_interval=3))
     rs = np.random.RandomState(5)
     _advance(env, rs, 4)        # next step 5: skipped
     net = check_slices(env)
@@ -167,8 +132,8 @@ def test_update_interval_on_an_update_step_and_a_skipped_step(envs):
 
 
 def test_regime_layout_gives_the_same_bits(envs):
-    a = envs.make('ssa_tasker_simple-v2', config=_cfg(envs))
-    b = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, storage_layout='regime'))
+    a = envs.make('ssa_tasker_simple-v2', config=cfg8(envs))
+    b = envs.make('ssa_tasker_simple-v2', config=cfg8(envs, storage_layout='regime'))
     assert b._engine._order is not None
     rs = np.random.RandomState(9)
     for k in range(40):
@@ -183,7 +148,7 @@ def test_regime_layout_gives_the_same_bits(envs):
 
 
 def test_multi_tile_instance_above_20480_objects(envs):
-    env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, m=24000, sensors=2))
+    env = envs.make('ssa_tasker_simple-v2', config=cfg8(envs, m=24000, sensors=2))
     rs = np.random.RandomState(13)
     _advance(env, rs, 2)
     net = check_slices(env)
@@ -192,7 +157,7 @@ def test_multi_tile_instance_above_20480_objects(envs):
 
 def test_one_sensor_equals_the_existing_lookahead(envs):
     """S = 1 -- an env without observers and a one-site network -- is env.lookahead() bit for bit"""
-    base = _cfg(envs, sensors=0)
+    base = cfg8(envs, sensors=0)
     one = dict(base, observers=[tuple(base['observer'])])
     for cfg in (base, one):
         env = envs.make('ssa_tasker_simple-v2', config=cfg)
@@ -212,7 +177,7 @@ def test_one_sensor_equals_the_existing_lookahead(envs):
 def test_no_side_effects_on_an_episode(envs):
     """120 steps with lookahead_sensors() before every step and the same episode without: states, rewards and failures bit for bit"""
     import torch
-    cfg = _cfg(envs, seed=21, steps=130)
+    cfg = cfg8(envs, seed=21, steps=130)
     a, b = envs.make('ssa_tasker_simple-v2', config=cfg), envs.make('ssa_tasker_simple-v2', config=cfg)
     rs = np.random.RandomState(4)
     ra, rb = [], []
@@ -252,7 +217,7 @@ def _greedy_np(score):
 
 def test_agents_assign_distinct_objects_greedily(envs):
     from ssa_gym_amd import _lib, agents
-    env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, seed=5))
+    env = envs.make('ssa_tasker_simple-v2', config=cfg8(envs, seed=5))
     env.action_space.seed(3)
     rs = np.random.RandomState(6)
     _advance(env, rs, 2)
@@ -268,7 +233,7 @@ def test_agents_assign_distinct_objects_greedily(envs):
 
 def test_a_sensor_without_a_reachable_object_gets_an_unused_one(envs):
     from ssa_gym_amd import agents
-    env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, seed=7, sensor_obs_limit=[15, 10, 90]))   # (sensor 2 sees nothing)
+    env = envs.make('ssa_tasker_simple-v2', config=cfg8(envs, seed=7, sensor_obs_limit=[15, 10, 90]))   # (sensor 2 sees nothing)
     env.action_space.seed(1)
     rs = np.random.RandomState(8)
     _advance(env, rs, 2)
@@ -286,7 +251,7 @@ def test_a_sensor_without_a_reachable_object_gets_an_unused_one(envs):
 
 def test_one_sensor_agents_match_the_single_sensor_agents(envs):
     from ssa_gym_amd import agents
-    env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, sensors=0, seed=9))
+    env = envs.make('ssa_tasker_simple-v2', config=cfg8(envs, sensors=0, seed=9))
     rs = np.random.RandomState(10)
     _advance(env, rs, 2)
     for _ in range(5):

@@ -2,25 +2,17 @@
 the export, refusal of bad arguments before any launch, no CPU fallback, and the new kernels' resource budget in the shipped code object
 against the single-sensor lookahead's."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
-from conftest import ROOT
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib
-    ssa_gym_amd.build()
-    return _lib.load()
+from support.codeobj import _kernels, header, stray_scratch
+from support.gpu import lib  # noqa: F401  (the module fixture)
 
 
 def test_lookahead_sensors_is_exported_and_declared(lib):
     from ssa_gym_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "ssa_hip.h")).read()
+    hdr = header()
     assert re.search(r"\bint\s+ssa_lookahead_sensors_f64\s*\(\s*const ssa_consts\s*\*\s*\w+\s*,\s*const ssa_step_params\s*\*\s*\w+\s*,"
                      r"\s*const ssa_sensor_params\s*\*\s*\w+\s*,\s*const ssa_lookahead_out\s*\*\s*\w+\s*,\s*void\s*\*\s*\w+\s*\)", hdr)
     assert "ssa_lookahead_sensors_f64" in _lib.SIGNATURES
@@ -93,7 +85,6 @@ def test_lookahead_sensors_kernels_keep_the_lookahead_kernels_budget(tmp_path):
     """each of the eight instances (4 propagators x {one tile, multi tile}) within lookahead_kernel of the same propagator and launch
     form: at most 96 VGPRs, the same LDS, no more scratch and no more VGPR spills; scratch touched only around the out-of-line calls of
     SSA_PROP_ELEMENTS / SSA_PROP_HYBRID; FG and J2 without calls or scratch"""
-    from test_abi_and_host import _kernels, stray_scratch
     kern, ins_of = _kernels(tmp_path)
     new = sorted(k for k in kern if "lookahead_sensors_kernel" in k)
     assert len(new) == 8, new

@@ -12,10 +12,7 @@ import pytest
 
 import oracle as orc
 from conftest import golden
-
-
-def relnorm(a, b, sl):
-    return np.linalg.norm((a - b)[..., sl], axis=-1) / np.linalg.norm(b[..., sl], axis=-1)
+from support.batches import relnorm
 
 
 # --------------------------------------------------------------------- P1-P5

@@ -6,14 +6,12 @@ The yardstick is the project's own per-step path, which this feature leaves unto
 import numpy as np
 import pytest
 
-from test_hip_step import c2t, hip, make_batch  # noqa: F401  (hip: the module fixture)
-from test_sensors_gpu import _cfg, _distinct, envs  # noqa: F401  (envs: the module fixture)
-from test_sensors_host import sites_rad
+from support.batches import c2t, make_batch
+from support.gpu import envs, hip  # noqa: F401  (the module fixtures)
+from support.sensors import BAD, N_TIME, _assert_same_env, _compare, _distinct, _same, cfg3, sites_rad
 
 pytestmark = pytest.mark.gpu
 
-N_TIME = 16           # rows of the GCRS -> ITRS table and of the noise tables the engine tests use (time indices stay below it)
-BAD = 9               # the object whose filter state is NaN: it fails in the first step's predict
 MASKS_DEG = [15.0, -90.0, 30.0, 0.0, 5.0, -10.0, 20.0, -30.0]
 ALL_ITEMS = {"tile", "idle", "dup", "oor", "cross", "failed", "taken"}
 
@@ -28,19 +26,6 @@ def _net(host, S, obs_type, stride):
         sig = [np.array([5e2 / (1 + 0.25 * k)] * 3) for k in range(S)]
     Rs = [np.diag(s ** 2) for s in sig]
     return lla, lim, Rs, sig, host.make_sensor_params(lla, lim, Rs, stride)
-
-
-def _defined_fields(L, u):
-    """an update record defines its flags always, z_true when the update was attempted (the action word is the object), y / S / sigmas_h
-    when the observation was taken; the other words of a slot are leftovers of whatever used it before"""
-    u = u.copy()
-    att, taken = u[..., L.UPD_ACTION] >= 0, u[..., L.UPD_OBS_TAKEN] == 1.0
-    keep = np.zeros(u.shape, dtype=bool)
-    keep[..., [L.UPD_OBS_TAKEN, L.UPD_VISIBLE, L.UPD_ACTION]] = True
-    keep[..., L.UPD_Z_TRUE:L.UPD_Z_TRUE + 3] = att[..., None]
-    keep[..., L.UPD_Y:L.UPD_SIGMAS_H + 39] = taken[..., None]
-    u[~keep] = 0.0
-    return u
 
 
 def _build_schedule(rs, m, S, K, H, interval, vis, order=None):
@@ -188,28 +173,6 @@ def _run_both(hip, consts, m, K, H, xt, x, P, trans, zn, sp, sched, argmax, layo
     return outs
 
 
-def _compare(L, a, b, K, H, argmax):
-    for nme in ("x_true", "x_filter", "P_filter", "obs", "metrics", "status"):
-        u, v = a[nme], b[nme]
-        if nme == "metrics" or u.ndim == 1 or K >= H:
-            assert np.array_equal(u, v, equal_nan=True), nme
-        else:   # slots never written keep their initial fill
-            sl = [s_ % H for s_ in range(0, K + 1)]
-            assert np.array_equal(u[sl], v[sl], equal_nan=True), nme
-    words = [L.STAT_MAX_DPOS, L.STAT_CNT_LT_1E4, L.STAT_CNT_LT_1E7, L.STAT_N_FAILED] + ([L.STAT_ARGMAX_SPOS, L.STAT_MAX_SPOS] if argmax else [])
-    ua, ub = _defined_fields(L, a["upd"]), _defined_fields(L, b["upd"])
-    for k in range(max(0, K - H), K):                     # statistics and records of the steps whose slot survives
-        so = (k + 1) % H
-        for w in words:
-            assert np.array_equal(a["stats"][so, :, w], b["stats"][so, :, w], equal_nan=True), (k, w)
-        assert np.array_equal(ua[so], ub[so], equal_nan=True), ("upd", k)
-    # the failure log: the same records (the order in which concurrent wavefronts append is not defined on either path)
-    assert a["fail_count"] == b["fail_count"]
-    key = lambda r: tuple(np.nan_to_num(r, nan=-1.0))      # noqa: E731
-    assert np.array_equal(np.array(sorted(a["fail_log"].tolist(), key=key)), np.array(sorted(b["fail_log"].tolist(), key=key)), equal_nan=True)
-    assert not b["shards"].any()                           # every per-step shard set of the rollout is folded and cleared
-
-
 def _engine_case(hip, S, m, K, H, propagator, obs_type, resample, interval, argmax, layout=False):
     torch, L, host = hip.torch, hip.lib, hip.host
     xt, x, P, g = make_batch(m, seed=123)
@@ -314,38 +277,6 @@ def test_engine_refuses_several_envs_a_short_noise_table_and_a_wrong_schedule(hi
 
 
 # ---------------------------------------------------------------- the env
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")
-
-
-def _assert_same_env(a, b, what):
-    """everything step() leaves: the device state (bit for bit) and every host-side history"""
-    import torch
-    from ssa_gym_amd import _lib
-    torch.cuda.synchronize()
-    assert a.i == b.i, what
-    for name in ("x_true", "x_filter", "P_filter", "obs", "metrics", "status"):
-        u, v = getattr(a._engine, name), getattr(b._engine, name)
-        if name != "status":
-            u, v = u.view(torch.int64), v.view(torch.int64)
-        assert torch.equal(u, v), (what, name)
-    for name in ("actions", "obs_taken", "sigmas_h", "S", "rewards", "_y", "_z_true", "_S_sel", "_upd_action"):
-        u, v = getattr(a, name), getattr(b, name)
-        assert (u is None and v is None) or _same(u, v), (what, name)
-    # failures: the same filters, dated to the same steps, with the same messages.  (Filters that fail in ONE step are listed in the order
-    # their wavefronts reached the failure log, which no path defines -- two step() twins differ there too: the ids are compared step by step.)
-    def by_step(env):
-        return sorted((env.failed_filters_msg._rec[j][0], j) for j in env.failed_filters_id)
-    assert len(a.failed_filters_id) == len(set(a.failed_filters_id)) == len(b.failed_filters_id) and by_step(a) == by_step(b), what
-    assert [env.failed_filters_msg._rec[j][0] for env in (a, b) for j in env.failed_filters_id] == \
-        sorted(env.failed_filters_msg._rec[j][0] for env in (a,) for j in env.failed_filters_id) * 2, what      # (in step order, both)
-    assert list(a.failed_filters_msg) == list(b.failed_filters_msg), what
-    assert a._n_failed == b._n_failed and a._argmax_sigma == b._argmax_sigma, (what, a._argmax_sigma, b._argmax_sigma)
-    words = [_lib.STAT_MAX_DPOS, _lib.STAT_CNT_LT_1E4, _lib.STAT_CNT_LT_1E7, _lib.STAT_N_FAILED]
-    assert _same(a._stats[words], b._stats[words]), what
-
-
 def _steps(env, rows):
     """rows by step(), up to the first done: (last observation, rewards, dones)"""
     obs, rewards, dones = None, [], []
@@ -366,8 +297,8 @@ def test_env_rollout_sensors_equals_a_step_loop(envs, reward_type, obs_returned,
     both, then a schedule longer than the episode.  'shaped': every other row tasks the previous arg-max of sigma_pos from sensor 2.
     regime: the rollout's env stores its objects by orbit regime until the rollout puts them back (as rollout() does)."""
     over = dict(steps=48, history=16, reward_type=reward_type, obs_returned=obs_returned)
-    a = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, **over))
-    b = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, storage_layout='regime' if regime else None, **over))
+    a = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, **over))
+    b = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, storage_layout='regime' if regime else None, **over))
     assert a._engine.H == 16 and b.n_sensor == 3
     rs = np.random.RandomState(21)
     # 25 rows by step() on the yardstick, built as it goes ('shaped' needs its arg-max of the step before); then a few more rows, which a
@@ -417,8 +348,8 @@ def test_env_rollout_sensors_late_in_an_episode(envs):
     and by rollout_sensors on the other -- with filters failing during those steps and an already-failed filter among the tasked
     (asserted on the step() twin, the yardstick)"""
     from ssa_gym_amd import _lib
-    a = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, m=20000, history=64))
-    b = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, m=20000, history=64))
+    a = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, m=20000, history=64))
+    b = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, m=20000, history=64))
     for env in (a, b):
         rs = np.random.RandomState(7)
         for _ in range(300):
@@ -448,8 +379,8 @@ def test_env_rollout_sensors_late_in_an_episode(envs):
 def test_without_observers_rollout_sensors_is_rollout(envs, reward_type, obs_returned):
     """no config['observers']: rollout_sensors with [K, 1] runs the env's one observer as a one-site network and equals rollout with [K]"""
     over = dict(steps=48, history=16, reward_type=reward_type, obs_returned=obs_returned)
-    a = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, sensors=0, **over))
-    b = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, sensors=0, **over))
+    a = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, sensors=0, **over))
+    b = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, sensors=0, **over))
     assert b.n_sensor == 1
     acts = np.random.RandomState(2).randint(a.m, size=40)
     oa, ra, da, _ = a.rollout(acts)

@@ -10,21 +10,15 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_sensors_host import _bare_env
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib
-    ssa_gym_amd.build()
-    return _lib.load()
+from support.codeobj import _kernels, header, stray_scratch
+from support.gpu import lib  # noqa: F401  (the module fixture)
+from support.sensors import _bare_env
 
 
 def test_sensor_rollout_is_exported_and_declared(lib):
     from ssa_gym_amd import _lib
-    header = open(os.path.join(ROOT, "include", "ssa_hip.h")).read()
-    assert re.search(r"\bint ssa_env_rollout_sensors_f64\s*\(", header)
+    hdr = header()
+    assert re.search(r"\bint ssa_env_rollout_sensors_f64\s*\(", hdr)
     assert "ssa_env_rollout_sensors_f64" in _lib.SIGNATURES
     assert hasattr(lib, "ssa_env_rollout_sensors_f64")
     assert lib.ssa_abi_version() == _lib.ABI_VERSION == 23          # (additive: the ABI version stays)
@@ -130,7 +124,6 @@ def test_sensor_rollout_kernels_keep_the_rollout_kernels_budget(tmp_path):
     """the four rollout_sensors_kernel instances fit 96 VGPRs (5 wavefronts per SIMD), use the LDS of rollout_kernel of the same
     propagator and no more scratch or VGPR spills than it, and touch scratch only around the out-of-line calls (SSA_PROP_ELEMENTS /
     SSA_PROP_HYBRID) -- FG and J2 none at all"""
-    from test_abi_and_host import _kernels, stray_scratch
     kern, ins_of = _kernels(tmp_path)
     sens = [k for k in kern if "rollout_sensors_kernel" in k]
     assert len(sens) == 4, sens

@@ -4,95 +4,13 @@ The ground truth is the project's own single-sensor step.  A step reads history 
 launched again with the status words and the failure counter restored: the sensor step of actions a[0..S-1] must leave every object a[s]
 bit-identical to a single-sensor step with action a[s] and sensor s's site, elevation mask, R and noise table, its update record s equal to
 that step's record, and every other object bit-identical to a step with no update."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+from support.gpu import envs  # noqa: F401  (the module fixture)
+from support.sensors import _advance, _distinct, _Relaunch, cfg3, xyz_net
+
 pytestmark = pytest.mark.gpu
-
-SITES = [(38.8, -104.5, 1800.0), (28.4, -80.6, 3.0), (-31.9, 115.9, 20.0)]
-
-
-@pytest.fixture(scope="module")
-def envs():
-    import torch
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib
-    ssa_gym_amd.build()
-    _lib.load()
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from ssa_gym_amd import envs as E
-    return E
-
-
-def _cfg(E, m=2000, sensors=3, **over):
-    cfg = dict(E.env_config)
-    cfg.update(rso_count=m, steps=480, obs_limit=15, reward_type='trinary', obs_returned='flatten', seed=3)
-    if sensors:
-        cfg.update(observers=SITES[:sensors], sensor_obs_limit=[15, 10, 20][:sensors],
-                   sensor_z_sigma=[(1, 1, 1e3), (2, 2, 5e2), (0.5, 0.5, 2e3)][:sensors])
-    cfg.update(over)
-    return cfg
-
-
-def _xyz(E):
-    from ssa_gym_amd.envs import dynamics as D
-    return dict(obs_type='xyz', z_sigma=(5e2,) * 3, R=np.diag([5e2 ** 2] * 3), hx=D.hx_xyz, mean_z=D.mean_xyz, residual_z=np.subtract,
-                sensor_z_sigma=[(5e2,) * 3, (3e2,) * 3, (8e2,) * 3])
-
-
-def _bits(t):
-    return t.contiguous().view(__import__("torch").int64).cpu().numpy()
-
-
-def _distinct(rs, m, S):
-    return rs.permutation(m)[:S]
-
-
-class _Relaunch:
-    """launches of the step from the env's current state (slot i -> slot i + 1), each from the same status words and failure counter"""
-
-    def __init__(self, env):
-        import torch
-        self.env, self.e = env, env._engine
-        torch.cuda.synchronize()
-        self.st0, self.fc0 = self.e.status.clone(), self.e.fail_count.clone()
-        self.upd = torch.zeros((env.n_sensor, 64), dtype=torch.float64, device="cuda")
-
-    def _out(self):
-        import torch
-        torch.cuda.synchronize()
-        e, sl = self.e, (self.env.i + 1) % self.e.H
-        out = dict(x=_bits(e.x_filter[sl]), P=_bits(e.P_filter[sl]).reshape(-1, 36), xt=_bits(e.x_true[sl]), st=e.status.cpu().numpy().copy(),
-                   upd=self.upd.cpu().numpy().copy())
-        e.status.copy_(self.st0)
-        e.fail_count.copy_(self.fc0)
-        return out
-
-    def sensors(self, acts, sp=None):
-        env, e, i = self.env, self.e, self.env.i
-        self.upd.zero_()
-        e.launch_step_sensors(i % e.H, (i + 1) % e.H, i + 1, env._sensors if sp is None else sp, list(acts), self.upd.data_ptr(),
-                              fast_stats=True, fold_inside=True)
-        return self._out()
-
-    def single(self, s, act):
-        """the plain step with sensor s's site, mask and R (its kernel constants) and its noise table"""
-        env, e, i = self.env, self.e, self.env.i
-        self.upd.zero_()
-        z0, c0, r0 = e._p.z_noise, e.consts, e._cref
-        try:
-            e._p.z_noise = e.z_noise.data_ptr() + s * int(env._sensors.zn_stride_sensor) * 8 if env.n_sensor > 1 else z0
-            e._pcache.clear()
-            e.consts = env._sensor_consts[s]
-            e._cref = C.byref(e.consts)
-            e.launch_step(i % e.H, (i + 1) % e.H, i + 1, action=int(act), upd_out=self.upd.data_ptr(), fast_stats=True, fold_inside=True)
-            return self._out()
-        finally:
-            e._p.z_noise, e.consts, e._cref = z0, c0, r0
-            e._pcache.clear()
 
 
 def check_decomposition(env, acts):
@@ -159,16 +77,11 @@ def _scenarios(env, rs, failed=False):
     return out
 
 
-def _advance(env, rs, k):
-    for _ in range(k):
-        env.step(_distinct(rs, env.m, env.n_sensor))
-
-
 def test_one_site_network_is_the_default_env_bit_for_bit(envs):
     """observers=[observer]: 120 steps at 2 000 objects ('hybrid') -- states, covariances, observations, rewards, failures identical"""
     import torch
-    base = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, sensors=0))
-    cfg = _cfg(envs, sensors=0)
+    base = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, sensors=0))
+    cfg = cfg3(envs, sensors=0)
     cfg['observers'] = [tuple(cfg['observer'])]
     one = envs.make('ssa_tasker_simple-v2', config=cfg)
     assert one.n_sensor == 1 and np.allclose(one.sensor_lla[0], one.obs_lla) and one.action_space.n == one.m
@@ -190,7 +103,7 @@ def test_one_site_network_is_the_default_env_bit_for_bit(envs):
 def test_one_sensor_kernel_equals_the_step_kernel(envs):
     """ssa_env_step_sensors_f64 with S = 1 leaves the same bits and the same record as ssa_env_step_f64, at every step of 120"""
     from ssa_gym_amd import host
-    cfg = _cfg(envs, sensors=0)
+    cfg = cfg3(envs, sensors=0)
     env = envs.make('ssa_tasker_simple-v2', config=cfg)
     sp = host.make_sensor_params([env.obs_lla], [env.obs_limit], [env.R], 0)
     env._sensors = sp
@@ -210,7 +123,7 @@ def test_one_sensor_kernel_equals_the_step_kernel(envs):
 def test_three_sensors_decompose_into_single_sensor_steps_at_20000(envs, late):
     """step 2 and step 310 (failed filters among the tasked) at 20 000 objects, 'hybrid': three objects in one tile, an object hidden from
     its sensor but visible to another, an idle sensor, two sensors on one object (the lower one updates it)"""
-    env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, m=20000))
+    env = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, m=20000))
     rs = np.random.RandomState(7)
     _advance(env, rs, 309 if late else 1)
     taken = 0
@@ -221,8 +134,8 @@ def test_three_sensors_decompose_into_single_sensor_steps_at_20000(envs, late):
 
 
 def test_xyz_and_the_other_propagators_decompose(envs):
-    for over in (_xyz(envs), dict(propagator='fg'), dict(propagator='elements'), dict(propagator='j2')):
-        env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, **over))
+    for over in (xyz_net(), dict(propagator='fg'), dict(propagator='elements'), dict(propagator='j2')):
+        env = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, **over))
         rs = np.random.RandomState(11)
         _advance(env, rs, 3)
         for acts in _scenarios(env, rs):
@@ -230,7 +143,7 @@ def test_xyz_and_the_other_propagators_decompose(envs):
 
 
 def test_update_interval_on_an_update_step_and_a_skipped_step(envs):
-    env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, update_interval=3))
+    env = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, update_interval=3))
     rs = np.random.RandomState(5)
     _advance(env, rs, 4)        # next step 5: skipped
     got, taken = check_decomposition(env, [1, 2, 3])
@@ -241,8 +154,8 @@ def test_update_interval_on_an_update_step_and_a_skipped_step(envs):
 
 
 def test_regime_layout_gives_the_same_bits(envs):
-    a_env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs))
-    b_env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, storage_layout='regime'))
+    a_env = envs.make('ssa_tasker_simple-v2', config=cfg3(envs))
+    b_env = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, storage_layout='regime'))
     rs = np.random.RandomState(9)
     for _ in range(60):
         a = _distinct(rs, a_env.m, 3)
@@ -257,7 +170,7 @@ def test_regime_layout_gives_the_same_bits(envs):
 def test_reward_types_and_the_any_sensor_shaped_rule(envs):
     from ssa_gym_amd import _lib
     for rt in ('jones', 'trinary', 'shaped'):
-        env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, reward_type=rt))
+        env = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, reward_type=rt))
         rs = np.random.RandomState(4)
         hits = 0
         for k in range(40):
@@ -280,7 +193,7 @@ def test_reward_types_and_the_any_sensor_shaped_rule(envs):
 
 
 def test_480_step_episode_at_20000_with_three_sensors(envs):
-    env = envs.make('ssa_tasker_simple-v2', config=_cfg(envs, m=20000))
+    env = envs.make('ssa_tasker_simple-v2', config=cfg3(envs, m=20000))
     rs = np.random.RandomState(3)
     done, steps = False, 0
     while not done:

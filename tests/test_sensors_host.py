@@ -10,26 +10,17 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib
-    ssa_gym_amd.build()
-    return _lib.load()
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "ssa_hip.h")).read()
+from support.codeobj import _kernels, header, stray_scratch
+from support.gpu import lib  # noqa: F401  (the module fixture)
+from support.sensors import _bare_env, sites_rad
 
 
 def test_sensor_step_is_exported_and_declared(lib):
     from ssa_gym_amd import _lib
-    assert re.search(r"\bssa_env_step_sensors_f64\s*\(", _header())
+    assert re.search(r"\bssa_env_step_sensors_f64\s*\(", header())
     assert "ssa_env_step_sensors_f64" in _lib.SIGNATURES
     assert hasattr(lib, "ssa_env_step_sensors_f64")
-    m = re.search(r"#define SSA_MAX_SENSORS\s+(\d+)", _header())
+    m = re.search(r"#define SSA_MAX_SENSORS\s+(\d+)", header())
     assert m and int(m.group(1)) == _lib.MAX_SENSORS == 8
 
 
@@ -92,20 +83,6 @@ def test_config_parser_accepts_and_refuses():
             resolve_sensors(bad)
 
 
-def _bare_env(S, m=10, n=6, seed=5):
-    """an env object without device state (what a machine without a GPU has), with just what the host-side paths read"""
-    from ssa_gym_amd import host
-    from ssa_gym_amd.envs._gymshim import np_random, spaces
-    from ssa_gym_amd.envs.ssa_tasker_simple_2 import SSA_Tasker_Env
-    env = SSA_Tasker_Env.__new__(SSA_Tasker_Env)
-    env._engine, env.i, env.n, env.m, env.n_sensor = None, 0, n, m, S
-    env.z_sigma = np.array([1.0, 1.0, 1e3]) * [host.arcsec2rad, host.arcsec2rad, 1]
-    env.sensor_z_sigma = np.stack([env.z_sigma * (k + 1) for k in range(S)])
-    env.np_random, _ = np_random(seed)
-    env.action_space = spaces.MultiDiscrete([m] * S) if S > 1 else spaces.Discrete(m)
-    return env
-
-
 def test_noise_stream_of_one_sensor_is_todays_and_the_others_follow_it():
     from ssa_gym_amd.envs._gymshim import np_random
     one = _bare_env(1)._draw_z_noise()
@@ -145,7 +122,6 @@ def test_sensor_kernels_keep_the_step_kernels_budget(tmp_path):
     """the eight sensor-network kernels (4 propagators x {one tile, multi tile}) fit the step kernel's register budget and LDS, use no
     more scratch than the step kernel of the same propagator and launch form, and touch it only around the out-of-line calls
     (SSA_PROP_ELEMENTS / SSA_PROP_HYBRID) -- FG and J2 none at all"""
-    from test_abi_and_host import _kernels, stray_scratch
     kern, ins_of = _kernels(tmp_path)
     sens = [k for k in kern if "step_sensors_kernel" in k]
     assert len(sens) == 8, sens
@@ -168,15 +144,6 @@ def test_sensor_kernels_keep_the_step_kernels_budget(tmp_path):
 
 
 # ---- the network's geometry at eight sites against the oracle's own (oracle/ssa_oracle.c: lla2ecef, ecef2aer), not the host's formulas.
-# (lat [deg], lon [deg], h [m]): the default observer, south-east, high altitude, the antimeridian, far north, far south, a pole, (0, 0)
-SITES8 = [(38.828198, -77.305352, 20.0), (-31.9, 115.9, 20.0), (19.8, -155.5, 4200.0), (-17.7, 179.95, 5.0),
-          (78.2, 15.6, 500.0), (-77.8, 166.7, 200.0), (89.9995, 45.0, 10.0), (0.0, 0.0, 0.0)]
-
-
-def sites_rad(sites=SITES8):
-    return [np.array([np.radians(la), np.radians(lo), h]) for la, lo, h in sites]
-
-
 def _net8():
     from ssa_gym_amd import host
     lla = sites_rad()

@@ -5,7 +5,7 @@ tests/test_sensors_gpu.py and tests/test_lookahead_sensors_gpu.py hold the netwo
 whose constants come from the same host code (host.enu_matrix, host.lla2ecef) and which run the same device geometry.  Here the ground
 truth is oracle/ssa_oracle.c, which builds its own observer position (lla2ecef) and local frame (ecef2aer) from the site: every site is
 handed to it as (lat, lon, h) in radians with oracle.lla2ecef(site) as its position, never through the host.  The sites
-(tests/test_sensors_host.py: SITES8) are south of the equator, east of Greenwich, high, at the antimeridian, near both poles and at
+(tests/support/sensors.py: SITES8_GEOMETRY) are south of the equator, east of Greenwich, high, at the antimeridian, near both poles and at
 (0, 0); the states are built where the geometry is delicate: near the zenith, across north, within 1e-9 rad of an elevation mask.
 
 Three values as in tests/test_hip_step.py: the kernel, the oracle in fp64 (the reference's arithmetic) and in 80-bit (the exact value).
@@ -15,8 +15,9 @@ import numpy as np
 import pytest
 
 import oracle as orc
-from test_hip_step import c2t, errs, make_batch
-from test_sensors_host import SITES8, sites_rad
+from support.batches import c2t, errs, make_batch
+from support.gpu import namespace
+from support.sensors import SITES8_GEOMETRY, sites_rad
 
 pytestmark = pytest.mark.gpu
 
@@ -31,13 +32,7 @@ ARCSEC = np.pi / 648000.0
 
 @pytest.fixture(scope="module")
 def hip():
-    import torch
-    import ssa_gym_amd
-    from ssa_gym_amd import _lib
-    ssa_gym_amd.build()
-    _lib.load()
-    assert torch.cuda.is_available()
-    return torch
+    return namespace().torch
 
 
 def _wrap(a):
@@ -183,7 +178,7 @@ def test_geometry_at_eight_sites(hip, oracle, oracle_ld):
                       north_east=int((north & (_wrap(zl[:, 0]) > 0)).sum()), north_west=int((north & (_wrap(zl[:, 0]) < 0)).sum()),
                       near_mask=int(near_mask.sum()), visible=int(vis.sum()))
         print("[geometry] site %d %s mask %g deg: %s; max |el| err %.1e |az| err %.1e (away from the zenith)"
-              % (s, SITES8[s], MASKS_DEG[s], counts, e_el[far].max(), e_az[far].max()))
+              % (s, SITES8_GEOMETRY[s], MASKS_DEG[s], counts, e_el[far].max(), e_az[far].max()))
         assert all(v > 0 for k, v in counts.items() if k != "visible"), (s, counts)
         if MASKS_DEG[s] == 90.0:
             assert not vis.any()
@@ -558,9 +553,9 @@ def test_env_steps_against_the_oracle(hip, oracle, oracle_ld):
     from ssa_gym_amd import envs as E
     cfg = dict(E.env_config)
     cfg.update(rso_count=2000, steps=480, reward_type='trinary', obs_returned='flatten', seed=11, alpha=ALPHA,
-               observers=[SITES8[k] for k in ENV_SITES], sensor_obs_limit=ENV_MASKS, sensor_z_sigma=ENV_SIGMAS)
+               observers=[SITES8_GEOMETRY[k] for k in ENV_SITES], sensor_obs_limit=ENV_MASKS, sensor_z_sigma=ENV_SIGMAS)
     env = E.make('ssa_tasker_simple-v2', config=cfg)
-    lla = [np.array([np.radians(SITES8[k][0]), np.radians(SITES8[k][1]), SITES8[k][2]]) for k in ENV_SITES]
+    lla = [np.array([np.radians(SITES8_GEOMETRY[k][0]), np.radians(SITES8_GEOMETRY[k][1]), SITES8_GEOMETRY[k][2]]) for k in ENV_SITES]
     itrs = [oracle.lla2ecef(s) for s in lla]
     lim = np.radians(ENV_MASKS)
     R = [np.diag((np.array(z) * [ARCSEC, ARCSEC, 1.0]) ** 2) for z in ENV_SIGMAS]
