@@ -226,6 +226,8 @@ typedef struct ssa_step_params {
                                   stats[SSA_STAT_ARGMAX_SPOS] carry obj_ids values (np.argmax's first maximum = the lowest such index), and the
                                   HOST-FACING copies of the observation -- obs_mirror rows, aer_out rows -- are written at row obj_ids[i].  x / P / x_true /
                                   status / obs / metrics stay in storage order.  An object's arithmetic does not depend on its position. */
+    const double *metrics_prev;/* with SSA_LAUNCH_STATS_FROM_METRICS and stat_shards_prev: the `metrics` block [4][m] the PREVIOUS step wrote (it must
+                                  still hold that step's rows: the service wavefronts of this launch reduce its delta_pos row) */
 } ssa_step_params;
 #define SSA_FAIL_STRIDE 8
 #define SSA_FAIL_ENV 0
@@ -264,6 +266,17 @@ int ssa_env_step_f64(const ssa_consts *c_host, const ssa_step_params *p_host, vo
                                          anyway (every RL framework does).  `obs` (the device-resident rows) stays double. */
 #define SSA_LAUNCH_INLINE_ENVS 64u   /* time indices and actions of all envs are ssa_step_params.inline_time / inline_action (n_env <= 8);
                                         time_offset is still added */
+#define SSA_LAUNCH_STATS_FROM_METRICS 256u /* with SSA_LAUNCH_DEFER_FOLD (one env, one tile per wavefront, no sensor network, no
+                                        SSA_LAUNCH_FOLD_INSIDE, no stat_shards_clear; SSA_E_UNSUPPORTED otherwise): the step kernel's wavefronts
+                                        leave the statistics block out of their epilogue -- only the number of failed filters of a tile that has
+                                        one is added to word 2 of its shard (status is updated in place: it cannot be re-read a launch later).
+                                        Max delta_pos and the trinary counts of step k are reduced from the metrics rows step k stored, 64 objects
+                                        per instruction, by the ssa_stats_from_metrics_waves() service wavefronts that ride in launch k + 1 (given
+                                        stat_shards_prev, stats_prev, metrics_prev) in place of the single fold wavefront: each leaves one partial
+                                        in words 0 / 1 of its own shard line of stat_shards_prev and takes a ticket (word 4 of shard 0); the last
+                                        one folds the lines into stats_prev and clears them.  Same bits as the atomics path: max, counts and the
+                                        first arg-max do not depend on the order.  Both launches of a hand-over carry the bit;
+                                        ssa_stats_fold_metrics_f64() folds the last step. */
 int ssa_env_step_profiled_f64(const ssa_consts *c_host, const ssa_step_params *p_host, void *stream, int32_t slot);
 /* waits for slot's kernel and writes its duration in milliseconds */
 int ssa_env_step_profile_ms(int32_t slot, float *kernel_ms);
@@ -297,6 +310,13 @@ int ssa_env_rollout_f64(const ssa_consts *c_host, const ssa_step_params *first, 
 int ssa_stats_fold_f64(uint64_t *stat_shards, double *stats, int32_t n_env, void *stream);
 /* the same with the arg-max slots of that step (ssa_step_params.spos_tiles; NULL = as ssa_stats_fold_f64) */
 int ssa_stats_fold_spos_f64(uint64_t *stat_shards, const uint64_t *spos_tiles, double *stats, int64_t n_obj, int32_t n_env, void *stream);
+/* SSA_LAUNCH_STATS_FROM_METRICS: the service wavefronts per launch for n_env envs of n_obj objects on this device, or 0 where the path
+ * does not apply (several envs, more than one tile per wavefront) */
+int32_t ssa_stats_from_metrics_waves(int64_t n_obj, int32_t n_env);
+/* the stand-alone fold of a step launched with SSA_LAUNCH_STATS_FROM_METRICS (one env): `metrics` [4][m] and `stat_shards` of THAT step,
+ * its arg-max slots or NULL; writes stats[SSA_STAT_STRIDE] and clears the shard set.  One launch. */
+int ssa_stats_fold_metrics_f64(const double *metrics, uint64_t *stat_shards, const uint64_t *spos_tiles, double *stats, int64_t n_obj,
+                               void *stream);
 /* historical: size of the `work` buffer (now unused); returns a token size */
 int64_t ssa_env_step_work_bytes(int64_t n_obj, int32_t n_env);
 

@@ -37,7 +37,7 @@ class ssa_step_params(C.Structure):
         ("inline_time", C.c_int32 * 8), ("inline_action", C.c_int32 * 8),
         ("spos_tiles", c_dp), ("spos_tiles_prev", c_dp),
         ("fail_log", c_dp), ("fail_count", c_dp), ("fail_cap", C.c_int32), ("reserved1", C.c_int32),
-        ("obj_ids", c_dp),
+        ("obj_ids", c_dp), ("metrics_prev", c_dp),
     ]
 
 
@@ -102,6 +102,7 @@ LAUNCH_INLINE_ACTION = 16
 LAUNCH_FOLD_INSIDE = 32
 LAUNCH_INLINE_ENVS = 64
 LAUNCH_MIRROR_F32 = 128
+LAUNCH_STATS_FROM_METRICS = 256
 INLINE_ENVS = 8
 LOOP_ARGMAX_SPOS, LOOP_DEBUG_WITHHOLD = 1, 2
 FAIL_STRIDE, FAIL_ENV, FAIL_OBJ, FAIL_STATUS, FAIL_TIME, FAIL_ERR = 8, 0, 1, 2, 3, 4
@@ -119,6 +120,8 @@ SIGNATURES = {
     "ssa_env_step_profile_ms": (C.c_int, [C.c_int32, C.POINTER(C.c_float)]),
     "ssa_stats_fold_f64": (C.c_int, [c_dp, c_dp, C.c_int32, c_dp]),
     "ssa_stats_fold_spos_f64": (C.c_int, [c_dp, c_dp, c_dp, C.c_int64, C.c_int32, c_dp]),
+    "ssa_stats_from_metrics_waves": (C.c_int32, [C.c_int64, C.c_int32]),
+    "ssa_stats_fold_metrics_f64": (C.c_int, [c_dp, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_ladder_probe_f64": (C.c_int, [c_dp, C.c_double, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_env_rollout_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_rollout_params), c_dp]),
     "ssa_env_closed_loop_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_closed_loop_params), c_dp]),

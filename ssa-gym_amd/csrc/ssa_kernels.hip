@@ -913,6 +913,63 @@ SSA_DEV void fold_stat_shards_inside(unsigned long long* __restrict__ shards, do
     }
 }
 
+// SSA_LAUNCH_STATS_FROM_METRICS: service wavefront w of nserv (<= SSA_STAT_SHARDS) reduces its slice of the delta_pos row the previous
+// step stored -- every load issued before the first use, 64 objects per instruction -- into ONE partial: max as ordered bits and the
+// packed trinary counts, exactly the words the step kernel's atomics would have summed.  The partial goes to words 0 / 1 of shard line w
+// (plain agent-scope stores: the line is this wavefront's own), then one returning atomic takes a ticket on word 4 of shard 0; whoever
+// draws the last ticket folds the lines -- the partials and the failure counts the step's own wavefronts added to word 2 -- as the
+// last tile of SSA_LAUNCH_FOLD_INSIDE does, and leaves lines and ticket word zero.
+constexpr int STAT_SERVICE_WAVES = 32, STAT_SERVICE_ILP = 10;   // (20 000 objects: 625 per wavefront, one pass of ten loads per lane)
+static_assert(STAT_SERVICE_WAVES <= SSA_STAT_SHARDS, "one shard line per service wavefront");
+SSA_DEV void stats_service_wave(const double* __restrict__ dpos, unsigned long long* __restrict__ shards, double* __restrict__ stats,
+                                const unsigned long long* __restrict__ spos, int64_t n_obj, int w, int nserv, int lane)
+{
+    const uint32_t n = (uint32_t)n_obj;                       // (n_env * n_obj < 2^31: the launcher)
+    const uint32_t per = (n + (uint32_t)nserv - 1u) / (uint32_t)nserv;
+    const uint32_t lo = (uint32_t)w * per < n ? (uint32_t)w * per : n;
+    const uint32_t hi = n - lo < per ? n : lo + per;
+    unsigned long long mx = 0ull, cn = 0ull;
+    for (uint32_t b = lo; b < hi; b += 64u * STAT_SERVICE_ILP) {
+        double v[STAT_SERVICE_ILP];
+#pragma unroll
+        for (int q = 0; q < STAT_SERVICE_ILP; ++q) {
+            const uint32_t i = b + (uint32_t)(q * 64 + lane);
+            v[q] = i < hi ? dpos[i] : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < STAT_SERVICE_ILP; ++q) {
+            const uint32_t i = b + (uint32_t)(q * 64 + lane);
+            if (i < hi) {
+                const unsigned long long bits = (unsigned long long)__double_as_longlong(v[q]) & 0x7fffffffffffffffull;
+                mx = bits > mx ? bits : mx;
+                cn += (unsigned long long)(v[q] < 1e4) + ((unsigned long long)(v[q] < 1e7) << 32);
+            }
+        }
+    }
+    mx = wave_fold_u64(mx, OpMax());
+    cn = wave_fold_u64(cn, OpAdd());
+    bool last = false;
+    if (lane == 0) {
+        unsigned long long* sh = shards + (int64_t)w * SSA_STAT_SHARD_WORDS;
+        __hip_atomic_store(sh, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(sh + 1, cn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the partial is in before its ticket is drawn
+        const unsigned old = (unsigned)__hip_atomic_fetch_add(shards + 4, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == (unsigned)nserv - 1u) {
+            __hip_atomic_store(shards + 4, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            last = true;
+        }
+    }
+    if (__any(last)) {
+        fold_stat_shards_inside(shards, stats, lane);
+        if (spos) {     // (the slots were written by the previous launch: a kernel boundary lies in between)
+            int t_lo, t_hi;
+            env_tile_range(n_obj, 0, t_lo, t_hi);
+            fold_spos_tiles<false>(spos, t_lo, t_hi, stats, lane);
+        }
+    }
+}
+
 // One wavefront advances up to 4 consecutive objects (one per 16-lane row) by one env step, complete semantics:
 // the robust_cholesky ladder is inline, conic branches beyond the strong-elliptic one are out-of-line calls taken
 // only by the lanes that need them.
@@ -1162,6 +1219,8 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // a grid-stride launch end together, and the 128 shard-complete increments per env land on ONE word one after the other -- the vector
     // env's step 123.9 -> 130.4 us although its host side got 4 us shorter.)
     constexpr bool FOLD_OK = (TILE == 0);
+    // SSA_LAUNCH_STATS_FROM_METRICS: the one-tile step kernel only (the launcher refuses it everywhere else)
+    constexpr bool FROM_METRICS = (TILE == 0) && !ACT::late && !ActIsAll<ACT>::v && !ActIsSensors<ACT>::v && !ActIsLookSensors<ACT>::v;
     constexpr bool ALL = ActIsAll<ACT>::v;   // the lookahead: every row updated hypothetically, nothing committed (ActAll)
     constexpr bool SENS = ActIsSensors<ACT>::v;   // a sensor network: one update per sensor, each with its own site (ActSensors)
     constexpr bool LSENS = ActIsLookSensors<ACT>::v;   // the lookahead of a sensor network: ALL, one pass per sensor (ActLookSensors)
@@ -1798,7 +1857,16 @@ look_pass:
         // O3 by sharded atomics: max delta_pos (as ordered bits: non-negative doubles and NaN order like unsigned
         // integers, so NaN wins exactly as in np.max), trinary counts (packed in one word), failures
         const bool one_env = p.n_env == 1 || ((uint32_t)base / (uint32_t)p.n_obj == (uint32_t)(base + cnt - 1) / (uint32_t)p.n_obj);
-        if (p.stat_shards && one_env) {
+        if (FROM_METRICS && (p.launch_mask & SSA_LAUNCH_STATS_FROM_METRICS)) {
+            // (one env, stat_shards given: the launcher.)  Max delta_pos and the counts are reduced from the metrics rows just stored by the
+            // service wavefronts of the NEXT launch (stats_service_wave); only the failed filters are counted here -- the status words
+            // are updated in place -- and only by a tile that has one: the row's status is still in a register, no LDS read, no wait
+            const unsigned long long failed = __ballot(valid && st_new != 0) & 0x0001000100010001ull;
+            if (failed && lane == 63) {
+                unsigned long long* sh = (unsigned long long*)p.stat_shards + (int64_t)(tile & (SSA_STAT_SHARDS - 1)) * SSA_STAT_SHARD_WORDS;
+                atomicAdd(sh + 2, (unsigned long long)__popcll(failed));
+            }
+        } else if (p.stat_shards && one_env) {
             // common case, the tile lies in one env.  Every lane of a row reads its row's delta_pos, so the COUNTS are ballots:
             // one bit per row (lanes 0, 16, 32, 48) of the comparison's mask, counted by the scalar unit -- no packing into
             // words, no cross-row adds.  The maximum crosses rows by two DPP steps (row_bcast:15 into rows 1 and 3, row_bcast:31
@@ -1936,6 +2004,13 @@ __global__ void __launch_bounds__(64) reward_fold_kernel(unsigned long long* __r
     fold_stat_shards(shards, stats, blockIdx.x, threadIdx.x, spos, n_obj);
 }
 
+// the service wavefronts on their own (ssa_stats_fold_metrics_f64: the last step of a sequence), one per block
+__global__ void __launch_bounds__(64) reward_service_kernel(const double* __restrict__ dpos, unsigned long long* __restrict__ shards,
+                                                            double* __restrict__ stats, const unsigned long long* __restrict__ spos, int64_t n_obj)
+{
+    stats_service_wave(dpos, shards, stats, spos, n_obj, blockIdx.x, gridDim.x, threadIdx.x);
+}
+
 // Workgroup -> tile, XCD-aware.  Workgroups are handed to the eight XCDs round-robin (block b runs on XCD b % 8) and every XCD
 // has its own L2.  With tile = b, neighbouring tiles -- which share the 128-byte lines of x / x_true (192 B per tile), the
 // metrics (32-byte runs) and the status words -- always sat on different XCDs: both fetched the shared input lines and both
@@ -2019,8 +2094,12 @@ enum : unsigned {
         const int unit = (int)blockIdx.x;                                                                                                     \
         if (((WALK) & WALK_STEP) && unit >= nwork) {                                                                                          \
             const ssa_step_params& p = step_of(k_arg).p;                                                                                      \
-            fold_stat_shards((unsigned long long*)p.stat_shards_prev, p.stats_prev, unit - nwork, lane,                                       \
-                             (const unsigned long long*)p.spos_tiles_prev, p.n_obj);                                                          \
+            if (!MULTI && !((WALK) & WALK_ONE_ENV) && (p.launch_mask & SSA_LAUNCH_STATS_FROM_METRICS))                                        \
+                stats_service_wave(p.metrics_prev, (unsigned long long*)p.stat_shards_prev, p.stats_prev,                                     \
+                                   (const unsigned long long*)p.spos_tiles_prev, p.n_obj, unit - nwork, (int)gridDim.x - nwork, lane);        \
+            else                                                                                                                              \
+                fold_stat_shards((unsigned long long*)p.stat_shards_prev, p.stats_prev, unit - nwork, lane,                                   \
+                                 (const unsigned long long*)p.spos_tiles_prev, p.n_obj);                                                      \
             return;                                                                                                                           \
         }                                                                                                                                     \
         const int64_t total = ((WALK) & WALK_ONE_ENV) ? step_of(k_arg).p.n_obj : (int64_t)step_of(k_arg).p.n_env * step_of(k_arg).p.n_obj;    \
@@ -3741,7 +3820,13 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     const bool fast_stats = p->stat_shards != nullptr;   // statistics by the common-path kernel's atomics
     const bool defer = fast_stats && (p->launch_mask & SSA_LAUNCH_DEFER_FOLD);
     if (defer && p->stat_shards_prev && (!p->stats_prev || p->stat_shards_prev == p->stat_shards)) return SSA_E_INVALID;
-    const int nfold = (defer && p->stat_shards_prev) ? p->n_env : 0;
+    const bool from_metrics = (p->launch_mask & SSA_LAUNCH_STATS_FROM_METRICS) != 0;
+    if (from_metrics) {   // (the one-tile step kernel of one env, deferred fold: see the bit)
+        if (!defer || sens || p->n_env != 1 || per_wave != 1 || (p->launch_mask & SSA_LAUNCH_FOLD_INSIDE) || p->stat_shards_clear)
+            return SSA_E_UNSUPPORTED;
+        if (p->stat_shards_prev && !p->metrics_prev) return SSA_E_INVALID;
+    }
+    const int nfold = (defer && p->stat_shards_prev) ? (from_metrics ? STAT_SERVICE_WAVES : p->n_env) : 0;
     dim3 grid((unsigned)(nwork + nfold)), block(64);
     const int nparts = post_parts(p->n_obj, p->n_env);
     StatAcc* parts = (StatAcc*)p->stat_ws;
@@ -3777,6 +3862,22 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     // folds the per-block statistics
     if ((mask & 4u) && p->stats)
         hipLaunchKernelGGL(reward_final_kernel, dim3(p->n_env), dim3(64), 0, s, (const StatAcc*)parts, p->stats, nparts);
+    return launch_status();
+}
+int32_t ssa_stats_from_metrics_waves(int64_t n_obj, int32_t n_env)
+{
+    if (n_obj <= 0 || n_env != 1) return 0;
+    int64_t ntiles, per_wave;
+    int nwork;
+    tile_grid(n_obj, ntiles, nwork, per_wave);
+    return per_wave == 1 ? STAT_SERVICE_WAVES : 0;
+}
+int ssa_stats_fold_metrics_f64(const double* metrics, uint64_t* stat_shards, const uint64_t* spos_tiles, double* stats, int64_t n_obj,
+                               void* stream)
+{
+    if (!metrics || !stat_shards || !stats || n_obj <= 0 || n_obj >= ((int64_t)1 << 31)) return SSA_E_INVALID;
+    hipLaunchKernelGGL(reward_service_kernel, dim3(STAT_SERVICE_WAVES), dim3(64), 0, (hipStream_t)stream, metrics,
+                       (unsigned long long*)stat_shards, stats, (const unsigned long long*)spos_tiles, n_obj);
     return launch_status();
 }
 int ssa_env_step_f64(const ssa_consts* c, const ssa_step_params* p, void* stream)
@@ -3830,6 +3931,7 @@ static int lookahead_args(const ssa_consts* c, const ssa_step_params* p, const s
     q.x_true_out = nullptr; q.x_out = nullptr; q.P_out = nullptr; q.obs = nullptr; q.metrics = nullptr; q.upd = nullptr;
     q.actions = nullptr; q.z_noise = nullptr; q.stats = nullptr; q.work = nullptr; q.stat_ws = nullptr;
     q.stat_shards = nullptr; q.stat_shards_prev = nullptr; q.stats_prev = nullptr; q.aer_out = nullptr; q.stat_shards_clear = nullptr;
+    q.metrics_prev = nullptr;
     q.obs_mirror = nullptr; q.spos_tiles = nullptr; q.spos_tiles_prev = nullptr; q.fail_log = nullptr; q.fail_count = nullptr;
     q.fail_cap = 0;
     q.launch_mask = p->launch_mask & SSA_LAUNCH_INLINE_ENVS;

@@ -93,7 +93,10 @@ class HotPathEngine:
         self._shard_sets = torch.zeros((2, self.E, _lib.STAT_SHARDS, _lib.STAT_SHARD_WORDS), dtype=torch.int64, device=d)
         self.stat_shards = self._shard_sets[0]
         self._shard_cur = 0
-        self._fold_pending = None      # (shard set index, stats destination) of a step whose fold was deferred
+        self._fold_pending = None      # (shard set index, stats destination, arg-max slots?, metrics block or 0) of a step whose fold was deferred
+        # SSA_LAUNCH_STATS_FROM_METRICS: a deferred step of ONE env (one tile per wavefront) leaves max delta_pos and the trinary counts
+        # to service wavefronts of the next launch, which reduce them from the metrics rows it stored (0: the path does not apply)
+        self.stats_from_metrics = int(self._lib.ssa_stats_from_metrics_waves(self.m, self.E)) > 0
         self._shard_ptr = [self._shard_sets[0].data_ptr(), self._shard_sets[1].data_ptr()]
         # arg-max slots of sigma_pos (ssa_step_params.spos_tiles: the 'shaped' reward on the one-launch paths), one set per shard set;
         # the step kernel needs whole tiles per env for them
@@ -199,6 +202,7 @@ class HotPathEngine:
         """reset(): place the initial truth / estimates / covariances in history slot `slot`
         and compute obs + metrics + stats for it (ssa_tasker_simple_2.py:228-229)."""
         N = self.m * self.E
+        self.flush_stats()      # (a pending fold may read the metrics rows this slot holds)
         self.x_true[slot].copy_(device.as_dev(np.asarray(x_true).reshape(N, 6), self.dev))
         self.x_filter[slot].copy_(device.as_dev(np.asarray(x_filter).reshape(N, 6), self.dev))
         self.P_filter[slot].copy_(device.as_dev(np.asarray(P_filter).reshape(N, 6, 6), self.dev))
@@ -248,6 +252,7 @@ class HotPathEngine:
         if (order is None) != (self._order is None) or (order is not None and not np.array_equal(order, self._order)):
             self.flush_stats()
             self.set_layout(order)
+        self.flush_stats()      # (a pending fold may read the metrics rows this slot holds)
         xt, x, P, obs, met, st = snap[:6]
         self.x_true[slot].copy_(xt)
         self.x_filter[slot].copy_(x)
@@ -297,14 +302,14 @@ class HotPathEngine:
             p.aer_out = aer_out
             p.stat_shards = self._shard_sets[shard_set].data_ptr() if shard_set >= 0 else 0
             p.stat_shards_prev, p.stats_prev, p.launch_mask = 0, 0, 0
-            p.stat_shards_clear = 0
+            p.stat_shards_clear, p.metrics_prev = 0, 0
             p.spos_tiles = self._spos_ptr(shard_set) if (argmax and shard_set >= 0) else 0
             p.spos_tiles_prev = 0
             p.aer_cols = int(aer_cols)
             p.obs_mirror = obs_mirror
             if shards_out:      # raw-shard consumer (include/ssa_hip.h: stat_shards_clear): no fold, no `stats`
                 p.stat_shards, p.stats, p.stat_shards_clear = shards_out, 0, shards_clear
-            ent = (p, C.byref(p), int(p.stats or 0))
+            ent = (p, C.byref(p), int(p.stats or 0), int(p.metrics))
             if len(self._pcache) > 4096:
                 self._pcache.clear()
             self._pcache[key] = ent
@@ -327,12 +332,14 @@ class HotPathEngine:
         if shards_out:
             fast_stats, defer_fold = True, False
         defer = bool(defer_fold and fast_stats)
-        if not defer and self._fold_pending is not None:
-            self.flush_stats(s)       # a deferred step is followed by an immediate one: fold it first (same stream, in order)
+        # (statistics from the metrics rows: the plain deferred step of one env -- every other form keeps its atomics)
+        from_metrics = defer and self.stats_from_metrics and not fold_inside and sensors is None
+        if self._fold_pending is not None and (not defer or bool(self._fold_pending[3]) != from_metrics):
+            self.flush_stats(s)       # a deferred step is followed by an immediate one, or by one of the other form: fold it first (same stream, in order)
         argmax = bool(argmax_spos and fast_stats and not shards_out)
         if argmax and not self.supports_argmax:
             raise _lib.SsaHipError("argmax_spos on the one-launch paths needs whole tiles per env (n_env == 1 or n_obj % 4 == 0)")
-        p, pref, stats_ptr = self._step_params(slot_in, slot_out, aer_out, stats_out, upd_out, self._shard_cur if fast_stats else -1,
+        p, pref, stats_ptr, metrics_ptr = self._step_params(slot_in, slot_out, aer_out, stats_out, upd_out, self._shard_cur if fast_stats else -1,
                                                shards_out, shards_clear, aer_cols, obs_mirror, argmax)
         p.time_offset = int(time_offset)
         p.actions = self._actions_ptr if actions_ptr is None else actions_ptr
@@ -347,14 +354,17 @@ class HotPathEngine:
             p.action0, inline = int(action), inline | _lib.LAUNCH_INLINE_ACTION
         if fold_inside and fast_stats and not defer and not shards_out:
             inline |= _lib.LAUNCH_FOLD_INSIDE      # (the step kernel's last wavefront folds the statistics: no fold launch)
+        if from_metrics:
+            inline |= _lib.LAUNCH_STATS_FROM_METRICS
         if defer and self._fold_pending is not None:
             p.launch_mask = _lib.LAUNCH_DEFER_FOLD | inline
             p.stat_shards_prev = self._shard_ptr[self._fold_pending[0]]
             p.stats_prev = self._fold_pending[1]
             p.spos_tiles_prev = self._spos_ptr(self._fold_pending[0]) if self._fold_pending[2] else 0
+            p.metrics_prev = self._fold_pending[3]
         else:
             p.launch_mask = (_lib.LAUNCH_DEFER_FOLD if defer else 0) | inline
-            p.stat_shards_prev, p.stats_prev, p.spos_tiles_prev = 0, 0, 0
+            p.stat_shards_prev, p.stats_prev, p.spos_tiles_prev, p.metrics_prev = 0, 0, 0, 0
         if sensors is not None:
             if profile_slot is not None:
                 raise _lib.SsaHipError("profile_slot: the step of a sensor network is not profiled by event pairs")
@@ -366,7 +376,7 @@ class HotPathEngine:
         if rc:
             raise _lib.SsaHipError("%s failed with code %d" % ("ssa_env_step_sensors_f64" if sensors is not None else "ssa_env_step_f64", rc))
         if defer:
-            self._fold_pending = (self._shard_cur, stats_ptr, argmax)
+            self._fold_pending = (self._shard_cur, stats_ptr, argmax, metrics_ptr if from_metrics else 0)
             self._shard_cur ^= 1
 
     def _check_sensor_noise(self, sensors):
@@ -541,7 +551,7 @@ class HotPathEngine:
         """self._p made the parameter block of the first step of a multi-step launch (rollout, closed loop)"""
         p = self._p
         p.time_offset = int(time_offset)
-        p.launch_mask, p.stat_shards_prev, p.stats_prev, p.aer_out = 0, 0, 0, 0
+        p.launch_mask, p.stat_shards_prev, p.stats_prev, p.aer_out, p.metrics_prev = 0, 0, 0, 0, 0
         p.spos_tiles, p.spos_tiles_prev = 0, 0
 
     def launch_rollout_sensors(self, slot_in, time_offset, sensors, actions, stream=None, argmax_spos=False):
@@ -659,8 +669,10 @@ class HotPathEngine:
         if self._fold_pending is None:
             return
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        k, dst, argmax = self._fold_pending
-        if argmax:
+        k, dst, argmax, metrics = self._fold_pending
+        if metrics:     # (a step whose statistics come from its metrics rows: the service wavefronts on their own)
+            rc = self._lib.ssa_stats_fold_metrics_f64(metrics, self._shard_sets[k].data_ptr(), self._spos_ptr(k) if argmax else 0, dst, self.m, s)
+        elif argmax:
             rc = self._lib.ssa_stats_fold_spos_f64(self._shard_sets[k].data_ptr(), self._spos_ptr(k), dst, self.m, self.E, s)
         else:
             rc = self._lib.ssa_stats_fold_f64(self._shard_sets[k].data_ptr(), dst, self.E, s)
