@@ -167,18 +167,22 @@ SSA_DEV void tile_commit(Tiles& t, const TileRegs& r, int lane)
 // ~80 vector instructions on lane-range selects, 64-bit address arithmetic and the commit).  A ragged last tile (cnt < 4) takes
 // the register path, which zero-fills what it does not load.  Completion: s_waitcnt vmcnt(0) (tile_dma_wait) -- the compiler
 // does not know these loads write LDS.
+// the objects of a launch (a sensor network: one env)
+SSA_DEV int64_t tile_total(const ssa_step_params& p, bool one_env) { return one_env ? p.n_obj : (int64_t)p.n_env * p.n_obj; }
 typedef const __attribute__((address_space(1))) void* GlobalVoidPtr;
 typedef __attribute__((address_space(3))) void* LdsVoidPtr;
 SSA_DEV void glds16(const double* src, double* lds_base)
 {
     __builtin_amdgcn_global_load_lds((GlobalVoidPtr)src, (LdsVoidPtr)lds_base, 16, 0, 0);
 }
+// `whole` comes from the kernel's preloaded arguments alone, so the DMA loads leave before any scalar load has returned; the object total --
+// a scalar load from the argument segment -- is read by the ragged tile only.
 SSA_DEV void tile_dma_issue(Tiles& t, TileRegs& r, const double* P_in, const double* x_in, const double* x_true_in, const int32_t* status,
-                            int lane, int64_t base, int cnt)
+                            int lane, int64_t base, bool whole, const ssa_step_params& p, bool one_env)
 {
-    r.dma = cnt == OBJ_PER_WAVE;
-    if (!r.dma) {
-        tile_issue_from(r, P_in, x_in, x_true_in, status, lane, base, cnt);
+    r.dma = whole;
+    if (!whole) {
+        tile_issue_from(r, P_in, x_in, x_true_in, status, lane, base, (int)(tile_total(p, one_env) - base));
         return;
     }
     r.st = SSA_ST_PREDICT_NAN;
@@ -688,16 +692,50 @@ SSA_DEV int inline_word(const int32_t (&w)[SSA_INLINE_ENVS], int e)
 }
 // INL = false: the instance never sees SSA_LAUNCH_INLINE_ENVS (rollout and closed-loop kernels, whose per-step copy of the block
 // stays in scalar registers only while nothing indexes into it)
-template <bool INL = true>
+// SEG = true: `p` IS the parameter block of a one-tile kernel, in its argument segment (process_wave<.., 0>).  The word then has ONE source
+// address -- device memory or the word's copy in the segment, which are the same address space to a load -- selected from launch_mask, and one
+// load: with one env a scalar load from the constant address space (wave-uniform; no wavefront of a step launch writes these words, and the
+// scalar cache starts every kernel empty, so what an earlier launch wrote is seen), with several a per-lane global load.  Written as
+// `mask ? p.action0 : p.actions[e]` the compiler forms the same select of two addresses, but of generic ones, and loads through the FLAT
+// segment: a vector-memory AND an LDS-queue wait behind the tile's loads.
+template <class T> using ConstPtr = const __attribute__((address_space(4))) T*;
+typedef const __attribute__((address_space(1))) int32_t* GlobalWords;
+typedef int v4i __attribute__((ext_vector_type(4)));
+SSA_DEV ConstPtr<ssa_step_params> tile_kernel_params();   // (the one-tile kernels' block in the segment: defined behind TileArgs)
+template <bool TIME>
+SSA_DEV ConstPtr<int32_t> segment_word_src(uint32_t m, const int32_t* mem)   // env 0's word: formed from scalars alone
+{
+    const ConstPtr<ssa_step_params> seg = tile_kernel_params();
+    if (TIME) return (m & SSA_LAUNCH_INLINE_ENVS) ? seg->inline_time : (ConstPtr<int32_t>)mem;
+    return (m & SSA_LAUNCH_INLINE_ENVS) ? seg->inline_action : (m & SSA_LAUNCH_INLINE_ACTION) ? &seg->action0 : (ConstPtr<int32_t>)mem;
+}
+// (several envs: env e's word, per lane.  It is waited for HERE, inside the caller's branch: at the join with the one-env path the compiler
+// would otherwise have to assume a vector load outstanding on either path, and put the one-env path's first use behind the tile's loads)
+SSA_DEV int segment_lane_word(ConstPtr<int32_t> src, int e)
+{
+    int w = ((GlobalWords)src)[e];
+    asm volatile("" : "+v"(w));
+    return w;
+}
+template <bool TIME>
+SSA_DEV int segment_env_word(const ssa_step_params& p, int e)
+{
+    const ConstPtr<int32_t> src = segment_word_src<TIME>(p.launch_mask, TIME ? p.env_time : p.actions);
+    if (p.n_env > 1) return segment_lane_word(src, e);
+    return *src;
+}
+template <bool INL = true, bool SEG = false>
 SSA_DEV int env_action(const ssa_step_params& p, int e)
 {
+    if (SEG) return segment_env_word<false>(p, e);
     if (INL && (p.launch_mask & SSA_LAUNCH_INLINE_ENVS)) return inline_word(p.inline_action, e);
     return (p.launch_mask & SSA_LAUNCH_INLINE_ACTION) ? p.action0 : p.actions[e];
 }
 // ... and its time index (before time_offset): the word in memory, or the parameter block's (SSA_LAUNCH_INLINE_ENVS)
-template <bool INL = true>
+template <bool INL = true, bool SEG = false>
 SSA_DEV int env_time_of(const ssa_step_params& p, int e)
 {
+    if (SEG) return segment_env_word<true>(p, e);
     return (INL && (p.launch_mask & SSA_LAUNCH_INLINE_ENVS)) ? inline_word(p.inline_time, e) : p.env_time[e];
 }
 // tix % n_time, the division (a ~25-instruction sequence on the vector unit) only when the index has actually wrapped
@@ -751,7 +789,7 @@ SSA_DEV void aer_obs_tile_at(const Tiles& t, const ssa_step_params& p, const ssa
     if (p.launch_mask & SSA_LAUNCH_MIRROR_F32) reinterpret_cast<float*>(p.aer_out)[obj * 4 + l] = (float)w;
     else p.aer_out[obj * 4 + l] = w;
 }
-template <bool INL>
+template <bool INL, bool SEG>
 SSA_DEV void aer_obs_tile(const Tiles& t, const ssa_step_params& p, const ssa_consts& C, int g, int l, int e, int64_t obj)
 {
     if (p.aer_cols == 1) {   // trace P only: lane 0 of the row
@@ -765,8 +803,8 @@ SSA_DEV void aer_obs_tile(const Tiles& t, const ssa_step_params& p, const ssa_co
         return;
     }
     // one env: the time index is wave-uniform, so the GCRS->ITRS matrix arrives by scalar loads (nine per-lane loads otherwise)
-    if (p.n_env > 1) aer_obs_tile_at(t, p, C, g, l, obj, env_time_of<INL>(p, e) + p.time_offset);
-    else aer_obs_tile_at(t, p, C, g, l, obj, env_time_of<INL>(p, 0) + p.time_offset);
+    if (p.n_env > 1) aer_obs_tile_at(t, p, C, g, l, obj, env_time_of<INL, SEG>(p, e) + p.time_offset);
+    else aer_obs_tile_at(t, p, C, g, l, obj, env_time_of<INL, SEG>(p, 0) + p.time_offset);
 }
 
 
@@ -1211,6 +1249,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
                           int64_t base, int cnt, TileRegs& pf, int64_t next_base, int next_cnt, int tile, ACT& asrc)
 {
     constexpr bool INL = (TILE != 2) && !ACT::late;   // (the per-step launches: SSA_LAUNCH_INLINE_ENVS may be set)
+    constexpr bool SEG = (TILE == 0);                 // (`p` is the kernel's own argument block: env_action)
     // SSA_LAUNCH_FOLD_INSIDE exists in the one-tile instance only: counting a tile means waiting for its atomics' acknowledgement
     // and for a returning atomic -- once, at the end of a one-tile wavefront's life, but ~1.5 us per tile in the grid-stride
     // instance (8 x 20 000 objects: 100.7 us per step instead of 89.0); the launcher sends those launches a fold kernel instead.
@@ -1233,25 +1272,58 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     constexpr bool PASS_ARGS = LSENS && !(TILE == 1 && PROP == 0);
     int g = lane >> 4, l = lane & 15;
     int64_t obj = obj_in;
-    // (TILE 0: the kernel issued the tile's loads from its preloaded pointer arguments before anything else.)  First thing here,
-    // so that these scalar loads complete with the action / time words' below -- placed behind the wait for the tile they
-    // put one more scalar-memory round trip between the tile's arrival and its commit to LDS
+    // (TILE 0: the kernel issued the tile's loads from its preloaded pointer arguments, whole tile or not decided from them too, before
+    // any scalar load.)  Everything else the head needs from memory is requested HERE, behind them and in front of the one wait for the
+    // tile: the process noise (a per-lane load from the argument segment, committed to LDS behind that wait -- placed there it was a
+    // dependent vector-memory round trip of its own), then the scalar loads of the action / time words and of the tile's obj_ids.
+    double q_in = 0.0;
+    if (TILE == 0 && lane < 36) q_in = C.Q[lane];
+    // ... and ONE round trip to the argument segment for every scalar the head decides by: held through an empty asm statement as
+    // in/out operands, so that the selects and loads below start from registers (the value used is the statement's result, which the
+    // compiler cannot get by loading the word again) -- left to itself the compiler loads launch_mask, branches on it, loads the pointer
+    // the branch picked, then the word: four scalar round trips in a row.
+    struct { uint32_t mask; const int32_t *actions, *env_time, *obj_ids; int n_env, time_offset, update_interval; } hw =
+        {p.launch_mask, p.actions, p.env_time, p.obj_ids, p.n_env, p.time_offset, C.update_interval};
     if (TILE == 0 && !ALL) {
-        // the epilogue's output pointers are fetched NOW: their scalar loads (kernarg segment) overlap the tile's HBM round
-        // trip instead of each adding a scalar-memory round trip to the store path of a latency-bound wavefront
-        asm volatile("" ::"s"(p.P_out), "s"(p.x_out), "s"(p.x_true_out), "s"(p.obs), "s"(p.metrics), "s"(p.stat_shards), "s"(p.upd),
-                     "s"(p.aer_out), "s"(p.n_obj));
+        // the epilogue's output pointers are fetched NOW as well: their scalar loads (kernarg segment) overlap the tile's HBM round
+        // trip instead of each adding a scalar-memory round trip to the store path of a latency-bound wavefront.  (As inputs only: the
+        // compiler is free to drop them again, and does so with p.obs and p.metrics -- the store stage loads those a second time.)
+        asm volatile("" : "+s"(hw.mask), "+s"(hw.actions), "+s"(hw.env_time), "+s"(hw.obj_ids), "+s"(hw.n_env), "+s"(hw.time_offset),
+                          "+s"(hw.update_interval)
+                     : "s"(p.P_out), "s"(p.x_out), "s"(p.x_true_out), "s"(p.obs), "s"(p.metrics), "s"(p.stat_shards), "s"(p.upd), "s"(p.aer_out),
+                       "s"(p.n_obj));
+    } else if (TILE == 0) {
+        asm volatile("" : "+s"(hw.mask), "+s"(hw.env_time), "+s"(hw.obj_ids), "+s"(hw.n_env), "+s"(hw.time_offset), "+s"(hw.update_interval));
     }
 
     // env of the object: no division for the single-env case, a 32-bit one otherwise (n_env * n_obj < 2^31)
-    int e = (valid && p.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
+    int e = (valid && hw.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
     const int64_t j = valid ? obj - (int64_t)e * p.n_obj : 0;
     // the action / time index of this object's env, fetched early (used after the transform)
-    // (one env: wave-uniform scalar loads; per-lane loads with their 64-bit address arithmetic only for vectorised envs)
+    // (one env: wave-uniform loads -- scalar ones from the constant address space in the one-tile instances, see env_action; the
+    // grid-stride instance's still compile to loads through the FLAT segment --; per-lane loads with their 64-bit address arithmetic only
+    // for vectorised envs)
     int act, tix;
+    int id0 = 0, id1 = 0, id2 = 0, id3 = 0;   // (the one-tile instances: the tile's obj_ids)
     if (ACT::late) {   // (one env; the action arrives behind the predict)
         act = -1;
         tix = valid ? p.env_time[0] + p.time_offset : 0;
+    } else if (SEG) {   // (the one-tile instances: no action for the lookahead, where every row is selected, nor for a sensor network)
+        // env 0's words and the tile's obj_ids: three scalar loads, issued together and waited for once (the asm statement needs all of them)
+        const ConstPtr<int32_t> t_src = segment_word_src<true>(hw.mask, hw.env_time), a_src = segment_word_src<false>(hw.mask, hw.actions);
+        int t0 = *t_src, a0 = -1;
+        if (!ALL && !SENS) a0 = *a_src;
+        if (hw.obj_ids) {
+            const v4i w = *(ConstPtr<v4i>)(hw.obj_ids + base);
+            id0 = w.x; id1 = w.y; id2 = w.z; id3 = w.w;
+        }
+        asm volatile("" : "+s"(t0), "+s"(a0), "+s"(id0), "+s"(id1), "+s"(id2), "+s"(id3));
+        if (hw.n_env > 1) {
+            t0 = segment_lane_word(t_src, e);
+            if (!ALL && !SENS) a0 = segment_lane_word(a_src, e);
+        }
+        act = valid ? a0 : -1;
+        tix = valid ? t0 + hw.time_offset : 0;
     } else if (ALL) {   // (no action: every row is selected)
         act = -1;
         tix = valid ? env_time_of<INL>(p, e) + p.time_offset : 0;
@@ -1269,14 +1341,18 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // ---- the one update of this env (ssa_tasker_simple_2.py:292-315) runs in the row that owns the selected object.  Its
     // wavefront is the longest-living one of the launch, so its inputs (this step's GCRS->ITRS matrix, the measurement noise)
     // leave HBM now and wait in LDS, instead of costing two memory round trips when the update starts
-    const bool interval_ok = (C.update_interval <= 1) || (tix % C.update_interval == 0);
+    const bool interval_ok = (hw.update_interval <= 1) || (tix % hw.update_interval == 0);
     // ssa_step_params.obj_ids (the per-step kernels; per env, indices within the env): the objects are stored in another order than the caller numbers them; the
     // action, the failure records, the arg-max of sigma_pos and the host-facing observation rows speak the CALLER's indices
     int64_t jid = j;
-    if (p.obj_ids) {
-        // (the tile's four indices by ONE wave-uniform 16-byte load -- scalar memory: it does not queue behind the tile's vector loads, which a
-        // per-lane load would, and the update's input prefetch below hangs on `my_update`; the table is padded to whole tiles)
-        const int4 ids = *reinterpret_cast<const int4*>(p.obj_ids + base);
+    if (hw.obj_ids) {
+        // (the tile's four indices by ONE wave-uniform 16-byte load; the update's input prefetch below hangs on `my_update`; the table is
+        // padded to whole tiles.  The one-tile instances read it through the constant address space, which makes it a scalar load next to
+        // the action word's: as a plain load the compiler cannot tell that no store of the kernel reaches the table, and issues a vector
+        // load that queues behind the tile's.  The rollout / closed-loop instances run behind launches' worth of their own stores: plain.)
+        int4 ids;
+        if (TILE == 0) ids = make_int4(id0, id1, id2, id3);   // (loaded with the action / time words above)
+        else ids = *reinterpret_cast<const int4*>(hw.obj_ids + base);
         const int mine = (g == 0) ? ids.x : (g == 1) ? ids.y : (g == 2) ? ids.z : ids.w;
         jid = valid ? (int64_t)mine : 0;
         if (l == 0) t.Oid[g] = mine;
@@ -1309,7 +1385,9 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     if (TILE == 0 && pf.dma) tile_dma_wait(t, pf, lane);   // (the one-tile kernels: the tile came by LDS-DMA)
     else if (TILE != 2) tile_commit(t, pf, lane);        // TILE 1: requested one tile ago (or by the kernel prologue)
     if (lane < 8) t.Z[lane] = 0.0;
-    if (TILE != 2 && lane < 36) t.Q[lane] = C.Q[lane];   // (a rollout's later steps find it in place)
+    if (TILE == 0) {
+        if (lane < 36) t.Q[lane] = q_in;                 // (requested at the top)
+    } else if (TILE != 2 && lane < 36) t.Q[lane] = C.Q[lane];   // (a rollout's later steps find it in place)
     wave_lds_sync();
 
     const int st_in = t.St[g];
@@ -1739,7 +1817,7 @@ look_pass:
         rec[SSA_UPD_OBS_TAKEN] = taken ? 1.0 : 0.0;
         rec[SSA_UPD_VISIBLE] = visible ? 1.0 : 0.0;
         if constexpr (SENS) rec[SSA_UPD_ACTION] = attempted ? (double)(p.obj_ids ? (int64_t)t.Oid[g] : obj) : -1.0;   // (the sensor's action IS this object)
-        else rec[SSA_UPD_ACTION] = attempted ? (double)(ACT::late ? act : env_action<INL>(p, e)) : -1.0;   // (my_update: the env's action IS this object)
+        else rec[SSA_UPD_ACTION] = attempted ? (double)(ACT::late ? act : env_action<INL, SEG>(p, e)) : -1.0;   // (my_update: the env's action IS this object)
     }
     if constexpr (ALL) {
         look_vis = visible;
@@ -1757,7 +1835,7 @@ look_pass:
     }   // wavefronts holding a selected object
     // envs whose action selects nobody still get a cleared record (written by object 0's row)
     if (!ALL && valid && p.upd && obj == (int64_t)e * p.n_obj && l == 0) {   // (object 0 of an env: one lane per env)
-      const int a_env = ACT::late ? act : env_action<INL>(p, e);
+      const int a_env = ACT::late ? act : env_action<INL, SEG>(p, e);
       if (!(a_env >= 0 && interval_ok && (int64_t)a_env < p.n_obj)) {
         double* rec = p.upd + (int64_t)e * SSA_UPD_STRIDE;
         rec[SSA_UPD_OBS_TAKEN] = 0.0;
@@ -1805,7 +1883,7 @@ look_pass:
                 rec[SSA_FAIL_ENV] = (double)e;
                 rec[SSA_FAIL_OBJ] = p.obj_ids ? (double)t.Oid[g] : (double)(obj - (int64_t)e * p.n_obj);
                 rec[SSA_FAIL_STATUS] = (double)st_new;
-                rec[SSA_FAIL_TIME] = (double)((ACT::late ? p.env_time[0] : env_time_of<INL>(p, e)) + p.time_offset);
+                rec[SSA_FAIL_TIME] = (double)((ACT::late ? p.env_time[0] : env_time_of<INL, SEG>(p, e)) + p.time_offset);
                 rec[SSA_FAIL_ERR + 0] = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
                 rec[SSA_FAIL_ERR + 1] = sqrt(b0 * b0 + b1 * b1 + b2 * b2);
                 rec[SSA_FAIL_ERR + 2] = sqrt(Pd[0] + Pd[7] + Pd[14]);
@@ -1842,7 +1920,7 @@ look_pass:
     // observation mode and the multi-GPU all-gather payload -- from the tiles, so that no second pass over x / P (the
     // former post kernel: 6.7 MB re-read per 20 000 objects plus a launch) is needed
     if (p.aer_out && p.stat_shards) {
-        if (l < 4 && valid) aer_obs_tile<INL>(t, p, C, g, l, e, p.obj_ids ? (int64_t)e * p.n_obj + t.Oid[g] : obj);
+        if (l < 4 && valid) aer_obs_tile<INL, SEG>(t, p, C, g, l, e, p.obj_ids ? (int64_t)e * p.n_obj + t.Oid[g] : obj);
     }
     wave_lds_sync();
     if (!ACT::late) {   // (closed_loop_kernel stores the tile itself, AFTER it has announced its part of the decision)
@@ -2035,13 +2113,22 @@ SSA_DEV int xcd_tile(int b, int n)
 // The leading arguments -- the two tile counts and the pointers k.p.{P_in, x_in, x_true_in, status} repeated -- are plain
 // scalars: they are PRELOADED into SGPRs at wavefront launch (-amdgpu-kernarg-preload-count, _build.py), so the tile's loads --
 // the first link of every wavefront's dependency chain -- leave without waiting for a scalar-memory round trip to the segment.
+// That holds only while NOTHING in front of the loads reads the block: the one-tile instance therefore gets the count of WHOLE tiles
+// in `ntiles` (tile_count_arg) and decides "LDS-DMA or the ragged tile's register path" from it -- decided from n_env x n_obj, as
+// it was, the loads stood behind a scalar load of both and its wait.  The grid-stride instance keeps the tile count there.
 template <class K> struct TileArgs {
     int ntiles, nwork;
     const double *pre_P_in, *pre_x_in, *pre_x_true_in;
     const int32_t* pre_status;
     K k;
 };
-template <class K> using KernargPtr = const __attribute__((address_space(4))) K*;
+template <class K> using KernargPtr = ConstPtr<K>;
+// every tile kernel's block starts with the step's, at the same place behind the preloaded arguments
+static_assert(offsetof(TileArgs<StepK>, k) == 40 && offsetof(StepK, p) == sizeof(ssa_consts), "the step's parameter block in the argument segment");
+SSA_DEV ConstPtr<ssa_step_params> tile_kernel_params()
+{
+    return (ConstPtr<ssa_step_params>)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(TileArgs<StepK>, k) + offsetof(StepK, p));
+}
 // The argument blocks: the step's own (StepK); the lookahead's outputs, at the caller's rows, behind it (LookK); a sensor
 // network's sites behind the step's (SensK) or the lookahead's (LookSensK) block.
 struct LookK {
@@ -2075,7 +2162,7 @@ enum : unsigned {
     WALK_BASE_PER_TILE = 8  // the grid-stride loop carries the segment's base and adds the block's offset per tile (step_fast_kernel),
                             // not the block's address formed once in front of the loop
 };
-// One tile kernel: NAME<PROP, MULTI>(ntiles, nwork, pre_P_in, pre_x_in, pre_x_true_in, pre_status, const K k_arg).
+// One tile kernel: NAME<PROP, MULTI>(ntiles (MULTI; else the whole tiles), nwork, pre_P_in, pre_x_in, pre_x_true_in, pre_status, const K k_arg).
 // The walk is written out once, here, but expands into the body of each kernel rather than living in a device function they call:
 // process_wave has to be inlined straight into the kernel.  Behind a device function its body is optimised once more, on its own
 // and without the kernel's launch bounds, before it reaches the kernel -- which reorders the step kernel's instructions (and
@@ -2107,8 +2194,13 @@ enum : unsigned {
         int tile = xcd_tile(unit, nwork);                                                                                                     \
         if (!MULTI) {                                                                                                                         \
             const int64_t base = (int64_t)tile * OBJ_PER_WAVE;                                                                                \
-            const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);                                             \
-            tile_dma_issue(t, pf, pre_P_in, pre_x_in, pre_x_true_in, pre_status, lane, base, cnt);                                            \
+            const bool whole = tile < ntiles;   /* (this instance: the count of WHOLE tiles, tile_count_arg) */                               \
+            /* (the object total -- scalar loads and a wait -- is formed where it is used: by the ragged tile, and behind the loads) */       \
+            tile_dma_issue(t, pf, pre_P_in, pre_x_in, pre_x_true_in, pre_status, lane, base, whole, step_of(k_arg).p,                         \
+                           ((WALK) & WALK_ONE_ENV) != 0);                                                                                     \
+            int cnt = OBJ_PER_WAVE;                                                                                                           \
+            asm volatile("" : "+s"(cnt));                                                                                                     \
+            if (!whole) cnt = (int)(tile_total(step_of(k_arg).p, ((WALK) & WALK_ONE_ENV) != 0) - base);                                       \
             const K& ka = ((WALK) & WALK_ACT_SEGMENT)                                                                                         \
                               ? *(const K*)(KernargPtr<K>)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(TileArgs<K>, k))    \
                               : k_arg;                                                                                                        \
@@ -3774,6 +3866,12 @@ static void tile_grid(int64_t total, int64_t& ntiles, int& nwork, int64_t& per_w
     per_wave = (ntiles + slots - 1) / slots;
     nwork = (int)((ntiles + per_wave - 1) / per_wave);
 }
+// the tile kernels' first argument: the grid-stride walk's tile count; the one-tile instance's count of WHOLE tiles (a tile below it
+// takes the LDS-DMA path, decided from a preloaded argument: SSA_TILE_KERNEL)
+static int tile_count_arg(int64_t total, int64_t ntiles, int64_t per_wave)
+{
+    return per_wave != 1 ? (int)ntiles : (int)(total / OBJ_PER_WAVE);
+}
 // the checks of a sensor network's sites that its step and its lookahead share; SSA_OK or the refusal
 static int sensors_ok(const ssa_sensor_params* sp, const ssa_step_params* p)
 {
@@ -3833,7 +3931,7 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     hipStream_t s = (hipStream_t)stream;
     const unsigned mask = (p->launch_mask & 7u) ? (p->launch_mask & 7u) : 7u;   // diagnostic: time one launch alone
     const int prop = c->propagator;
-    const int nt = (int)ntiles;
+    const int nt = tile_count_arg(total, ntiles, per_wave);
     if ((mask & 1u) && sens) {
         SensK ks;
         ks.k = k;
@@ -3945,7 +4043,7 @@ int ssa_lookahead_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_l
     int64_t ntiles, per_wave;
     int nwork;
     tile_grid((int64_t)p->n_env * p->n_obj, ntiles, nwork, per_wave);
-    const int nt = (int)ntiles;
+    const int nt = tile_count_arg((int64_t)p->n_env * p->n_obj, ntiles, per_wave);
     dim3 grid((unsigned)nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
     with_prop(c->propagator, per_wave != 1, [&](auto P, auto M) {
@@ -3969,7 +4067,7 @@ int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, con
     int64_t ntiles, per_wave;
     int nwork;
     tile_grid(p->n_obj, ntiles, nwork, per_wave);
-    const int nt = (int)ntiles;
+    const int nt = tile_count_arg(p->n_obj, ntiles, per_wave);
     dim3 grid((unsigned)nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
     with_prop(c->propagator, per_wave != 1, [&](auto P, auto M) {
