@@ -590,6 +590,31 @@ typedef struct ssa_rollout_sensors_params {
 int ssa_env_rollout_sensors_f64(const ssa_consts *c_host, const ssa_step_params *first, const ssa_rollout_params *r,
                                 const ssa_sensor_params *sites, const ssa_rollout_sensors_params *rs, void *stream);
 
+/* ---------------------------------------------------------------- the tasking forecast of a sensor network: H lookaheads in one launch
+ * From the state ssa_lookahead_sensors_f64 reads (ssa_step_params inputs: slot i, time index time_offset), for h = 0 .. H-1 what
+ * ssa_lookahead_sensors_f64 would write if ssa_env_step_sensors_f64 had first been run h times with every sensor idle -- the pass
+ * forecast (visible), the covariance growth (P_prior) and the gain of an observation by sensor s at step i + 1 + h (score, P_post), for
+ * every sensor and object -- bit for bit, with the state of each wavefront's objects resident in LDS across the steps as in
+ * ssa_env_rollout_sensors_f64.  Step h has time index time_offset + h; the NaN rules, status codes and update_interval handling are the
+ * lookahead's, per step.  The status a row carries from step h to h + 1 is the predict's: SSA_ST_UPDATE_LINALG of a hypothetical
+ * update shows in output (h, s, j) only.  A row that fails inside the horizon reports the failure sentinels from then on; a row that
+ * had failed before the launch passes through from the input slot.
+ * Outputs, ssa_lookahead_out with a leading step axis, m = n_obj, S = n_sensor, the caller's object numbering (obj_ids):
+ *   score [H][S*m][SSA_LOOK_NSCORE], status [H][S*m], visible [H][S*m] (required), P_post [H][S*m][36] (or NULL): row (h*S + s)*m + j;
+ *   x_prior [H][m][6], P_prior [H][m][36] (or NULL): row h*m + j.
+ * Reads the ssa_step_params fields ssa_lookahead_sensors_f64 reads, except that launch_mask is not honoured (the time word is
+ * env_time[0]), and the same fields of ssa_sensor_params.  Nothing of the caller's state is written: no ring slot, status word,
+ * statistics shard, failure record, update record, observation or metrics row; the measurement noise is never read.  One launch.
+ * Refused before any launch: every refusal of ssa_lookahead_sensors_f64 (with `f->out` as its outputs), a NULL `f`, n_steps < 1
+ * (SSA_E_INVALID). */
+typedef struct ssa_forecast_params {
+    int32_t n_steps;         /* H >= 1 */
+    int32_t reserved;
+    ssa_lookahead_out out;   /* each block with the leading step axis above */
+} ssa_forecast_params;
+int ssa_forecast_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_sensor_params *s_host,
+                             const ssa_forecast_params *f, void *stream);
+
 /* ---------------------------------------------------------------- the tasking assignment of a sensor network, on the device
  * One object per sensor from one column of the scores ssa_lookahead_sensors_f64 leaves, in ONE launch and written where the next launch
  * reads it: the global greedy assignment of agents._assign_lookahead_sensors (S ssa_masked_argmax_f64 launches, S read-backs and the

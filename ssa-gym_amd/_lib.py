@@ -77,6 +77,10 @@ class ssa_rollout_sensors_params(C.Structure):
     _fields_ = [("actions", c_dp), ("upd_ring", c_dp)]
 
 
+class ssa_forecast_params(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("reserved", C.c_int32), ("out", ssa_lookahead_out)]
+
+
 class ssa_screen_params(C.Structure):
     _fields_ = [
         ("n", C.c_int64), ("n_time", C.c_int32), ("n_site", C.c_int32), ("step", C.c_double), ("min_alt", C.c_double),
@@ -129,6 +133,8 @@ SIGNATURES = {
     "ssa_env_step_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params), c_dp]),
     "ssa_lookahead_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
                                             C.POINTER(ssa_lookahead_out), c_dp]),
+    "ssa_forecast_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
+                                           C.POINTER(ssa_forecast_params), c_dp]),
     "ssa_env_rollout_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_rollout_params),
                                               C.POINTER(ssa_sensor_params), C.POINTER(ssa_rollout_sensors_params), c_dp]),
     "ssa_closed_loop_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),

@@ -137,3 +137,54 @@ def agent_info_gain_sensors(obs, env):          # one object per sensor, greedy 
 
 def agent_trace_gain_sensors(obs, env):         # one object per sensor, greedy over tr P- - tr P+ from every site
     return _assign_lookahead_sensors(env, _lib.LOOK_TRACE_GAIN)
+
+
+# ---- non-myopic planning for a sensor network: the schedules env.rollout_sensors() executes.  ONE forecast
+# launch (env.forecast_sensors: every sensor's lookahead at each of the next H' steps, nobody observed in between), then the global
+# greedy assignment above on slab h for h = 0 .. H'-1 in order (ssa_assign_sensors_f64 on the slab's base address), with the objects
+# planned at an earlier step of this plan removed from the slab first: the forecast's gains assume no update before h, so an object
+# is planned at most once per plan.  Everything in-stream, one read-back at the end.  No device fallback row: a sensor the scores leave
+# without an object comes back -1 and is filled here by _assign_lookahead_sensors' rule.
+def _fill_plan(env, plan):
+    """the -1 entries of a plan [H', S] filled row by row, sensors ascending: an object no sensor of that row holds, drawn from the
+    action space's generator (env.np_random is not touched).  Such a sensor has no healthy visible object left at that step, so its
+    draw updates nothing the forecast counted on."""
+    plan = np.array(plan, dtype=np.int64)
+    for row in plan:
+        taken = set(row[row >= 0].tolist())
+        for s in np.flatnonzero(row < 0):
+            row[s] = _draw_unassigned(env, taken)
+            taken.add(int(row[s]))
+    return plan
+
+
+def _plan_assigned(env, horizon, k):
+    """the device's part of a plan: int64 [H', S], -1 where the scores leave a sensor without an object"""
+    import torch
+    with torch.cuda.stream(env._stream):
+        score = env.forecast_sensors(horizon)["score"]         # [H', S, m, 3]
+        Hp, S, m = score.shape[:3]
+        e = env._engine
+        rows = torch.full((Hp, _lib.MAX_SENSORS), -1, dtype=torch.int32, device=score.device)
+        planned = torch.zeros(m + 1, dtype=torch.bool, device=score.device)     # (slot m: where the -1 entries of a row land)
+        for h in range(Hp):
+            slab = score[h] if h == 0 else score[h].masked_fill(planned[:m].view(1, m, 1), float("nan"))
+            e.launch_assign_sensors({"score": slab}, k, rows[h], stream=env._stream.cuda_stream)
+            r = rows[h].long()
+            planned[torch.where(r >= 0, r, torch.full_like(r, m))] = True
+    env._stream.synchronize()
+    return rows.cpu().numpy()[:, :S].astype(np.int64)
+
+
+def _plan_lookahead_sensors(env, horizon, k):
+    if env._engine is None:
+        raise _lib.SsaHipError("no device state: a plan comes from the forecast, which runs on the GPU only (no CPU fallback)")
+    return _fill_plan(env, _plan_assigned(env, horizon, k))
+
+
+def plan_info_gain_sensors(env, horizon):       # a schedule [H', S] for env.rollout_sensors(): greedy over 1/2 ln(det P- / det P+) per step
+    return _plan_lookahead_sensors(env, horizon, _lib.LOOK_INFO_GAIN)
+
+
+def plan_trace_gain_sensors(env, horizon):      # ... over tr P- - tr P+
+    return _plan_lookahead_sensors(env, horizon, _lib.LOOK_TRACE_GAIN)

@@ -1179,6 +1179,36 @@ template <class ACT> SSA_DEV const ssa_sensor_params* sensors_of(const ACT&) { r
 template <> SSA_DEV const ssa_sensor_params* sensors_of<ActSensors>(const ActSensors& a) { return a.s; }
 template <> SSA_DEV const ssa_sensor_params* sensors_of<ActSchedule>(const ActSchedule& a) { return a.s; }
 template <> SSA_DEV const ssa_sensor_params* sensors_of<ActLookSensors>(const ActLookSensors& a) { return a.s; }
+// ActForecastSensors (forecast_sensors_kernel, ssa_forecast_sensors_f64; one env): ActLookSensors for step h of a forecast, whose tile
+// stays in LDS from step to step with every sensor idle.  Three things differ from the one-step lookahead, each behind ActIsForecast
+// in process_wave: the outputs go to slab h of the blocks `o` names (slab()); the status the tile carries to step h + 1 is the
+// predict's (a singular S of a hypothetical update shows in that step's outputs only); and a row that failed INSIDE the horizon is
+// handed on as the failure sentinels -- there is no ring slot to re-read, and the input slot holds its healthy state.
+struct ActForecastSensors {
+    static constexpr bool late = false;
+    const ssa_lookahead_out* o;
+    const ssa_sensor_params* s;
+    int h;
+    SSA_DEV int get() { return -1; }
+    SSA_DEV void before_wait(Tiles&, int, int) {}
+    SSA_DEV void mid_step(Tiles&, int) {}
+    // the output block of step h: [H][S * m] rows per sensor output, [H][m] rows of the prior
+    SSA_DEV void slab(ssa_lookahead_out& os, int64_t m, int S) const
+    {
+        const int64_t rs = (int64_t)h * S * m, rp = (int64_t)h * m;
+        os.score += rs * SSA_LOOK_NSCORE;
+        os.status += rs;
+        os.visible += rs;
+        if (os.P_post) os.P_post += rs * 36;
+        if (os.x_prior) os.x_prior += rp * 6;
+        if (os.P_prior) os.P_prior += rp * 36;
+    }
+};
+template <class ACT> struct ActIsForecast { static constexpr bool v = false; };
+template <> struct ActIsForecast<ActForecastSensors> { static constexpr bool v = true; };
+template <> struct ActIsLookSensors<ActForecastSensors> { static constexpr bool v = true; };
+template <> struct ActIsAll<ActForecastSensors> { static constexpr bool v = true; };
+template <> SSA_DEV const ssa_sensor_params* sensors_of<ActForecastSensors>(const ActForecastSensors& a) { return a.s; }
 // a pointer into the argument segment that the optimiser cannot see through: the (scalar) loads from it stay inside ActLookSensors'
 // passes instead of being hoisted in front of them, where their results would hold scalar registers across every pass
 template <class T> SSA_DEV const T* kernarg_opaque(const T* q)
@@ -1263,6 +1293,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     constexpr bool ALL = ActIsAll<ACT>::v;   // the lookahead: every row updated hypothetically, nothing committed (ActAll)
     constexpr bool SENS = ActIsSensors<ACT>::v;   // a sensor network: one update per sensor, each with its own site (ActSensors)
     constexpr bool LSENS = ActIsLookSensors<ACT>::v;   // the lookahead of a sensor network: ALL, one pass per sensor (ActLookSensors)
+    constexpr bool FCAST = ActIsForecast<ACT>::v;      // ... as step h of a forecast: LSENS on a resident tile (ActForecastSensors)
     // (ActLookSensors, multi-tile instance: the next tile's loads leave once, behind the last pass -- except with SSA_PROP_ELEMENTS, whose
     // out-of-line call then spills 8 more VGPRs: there they are issued as in every other kernel, after the propagator and again at the end
     // of each pass's update)
@@ -1891,17 +1922,32 @@ look_pass:
             }
         }
     }
+    if constexpr (FCAST) {
+        // a forecast has no ring: a row that had failed when the launch started passes through from the input slot, as below; one that
+        // failed at an earlier step of the horizon carries the sentinels F1 gave it then (its input slot holds the healthy state)
+        if (valid && st_in != SSA_ST_OK) {
+            const bool at_entry = p.status[obj] != SSA_ST_OK;   // (the caller's word: never written by this launch)
+            for (int idx = l; idx < 36; idx += 16) {
+                const int a = idx / 6, b = idx - a * 6;
+                t.P[g * 36 + idx] = at_entry ? p.P_in[obj * 36 + idx] : ((a == b) ? (a < 3 ? X_FAILED_POS : X_FAILED_VEL) : 0.0);
+            }
+            if (l < 6) t.X[g * 6 + l] = at_entry ? p.x_in[obj * 6 + l] : ((l < 3) ? X_FAILED_POS : X_FAILED_VEL);
+        }
+        if (l == 0) t.St[g] = st_pred;   // (the predict's outcome alone travels to the next step)
+    } else {
     if (valid && st_in != SSA_ST_OK) {  // already failed: the filter state passes through unchanged (:272)
         if (ACT::late) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (its previous state left for HBM earlier in THIS step)
         for (int idx = l; idx < 36; idx += 16) t.P[g * 36 + idx] = p.P_in[obj * 36 + idx];
         if (l < 6) t.X[g * 6 + l] = p.x_in[obj * 6 + l];
     }
     if (l == 0) t.St[g] = st_new;
+    }
     wave_lds_sync();
     if constexpr (LSENS) {   // sensor look_s's outputs (one env), then the next sensor's pass
         const bool last = look_s + 1 >= SP->n_sensor;
         if (TILE == 1 && ISSUE_LAST && last) tile_issue(pf, p, lane, next_base, next_cnt);
         ssa_lookahead_out os = PASS_ARGS ? *kernarg_opaque(asrc.o) : *asrc.o;
+        if constexpr (FCAST) asrc.slab(os, p.n_obj, SP->n_sensor);   // (a forecast: this step's slab of every block)
         if (look_s > 0) os.x_prior = os.P_prior = nullptr;   // (no sensor axis: the first pass wrote them)
         if (valid) lookahead_store<1>(t, os, g, l, (int64_t)look_s * p.n_obj + (p.obj_ids ? (int64_t)t.Oid[g] : obj), st_new, look_vis, look_taken);
         if (!last) {
@@ -2350,6 +2396,53 @@ SSA_DEV ActSchedule roll_act(const RollSensK& a, ssa_step_params& pk, int kk, in
 SSA_ROLLOUT_KERNEL(rollout_kernel, RollK)                  // an env's schedule (ssa_env_rollout_f64)
 SSA_ROLLOUT_KERNEL(rollout_sensors_kernel, RollSensK)      // a sensor network's (ssa_env_rollout_sensors_f64)
 #undef SSA_ROLLOUT_KERNEL
+
+// Forecast: the lookahead of a sensor network at each of H consecutive steps, every sensor idle in between, in ONE launch
+// (ssa_forecast_sensors_f64).  A sibling of the rollout kernels: a wavefront loads its tile once and runs H predicts on it with state,
+// covariance, truth and status resident in LDS -- what the passes of ActLookSensors leave in t.X / t.P IS what an idle step would have
+// stored -- and writes nothing but slab h of the outputs.  No ring, no statistics, no records: the caller's state is only read.
+struct ForeSensK {   // ONE kernel argument (see RollK)
+    StepK k;
+    ssa_sensor_params s;
+    ssa_forecast_params f;
+};
+template <int PROP>
+__global__ void __launch_bounds__(64, SSA_STEP_WAVES) forecast_sensors_kernel(const ForeSensK a, int ntiles, int nwork)
+{
+    __shared__ Tiles t;
+    int lane = threadIdx.x;
+    const int H = a.f.n_steps;
+    const int64_t total = a.k.p.n_obj;
+    TileRegs pf;
+    typedef const __attribute__((address_space(4))) ForeSensK* ForeArgPtr;
+    ForeArgPtr kp = (ForeArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    for (int tile = xcd_tile((int)blockIdx.x, nwork); tile < ntiles; tile += nwork) {
+        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
+        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
+        wave_lds_sync();   // the previous tile's last stores have read the tiles
+        tile_issue(pf, a.k.p, lane, base, cnt);
+        tile_commit(t, pf, lane);
+        if (lane < 36) t.Q[lane] = a.k.c.Q[lane];   // process_wave<.., 2> expects the process noise in place
+        unsigned wave_slot;   // the wavefront's slot on its SIMD: the issue priority rotates per step, as in the rollout
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(wave_slot));
+        for (int h = 0; h < H; ++h) {
+            switch ((wave_slot + (unsigned)h) & 3u) {
+                case 0: __builtin_amdgcn_s_setprio(0); break;
+                case 1: __builtin_amdgcn_s_setprio(1); break;
+                case 2: __builtin_amdgcn_s_setprio(2); break;
+                default: __builtin_amdgcn_s_setprio(3); break;
+            }
+            asm volatile("" : "+s"(kp));      // per step: nothing carried around the loop
+            asm volatile("" : "+v"(lane));
+            const ForeSensK& ka = *(const ForeSensK*)kp;
+            ssa_step_params pk = ka.k.p;
+            pk.time_offset = ka.k.p.time_offset + h;
+            ActForecastSensors act{&ka.f.out, &ka.s, h};   // (pointers into the segment: kernarg_opaque in process_wave)
+            process_wave<PROP, 2>(t, ka.k.c, pk, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, act);
+            wave_lds_sync();
+        }
+    }
+}
 // grid (n_steps, n_env): folds step k's shard set into the statistics slot of step k -- when that slot still
 // belongs to step k at the end of the rollout (the last `history` steps) -- and clears it
 __global__ void __launch_bounds__(64) rollout_fold_kernel(unsigned long long* __restrict__ shards, double* __restrict__ stats_ring,
@@ -4073,6 +4166,31 @@ int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, con
     with_prop(c->propagator, per_wave != 1, [&](auto P, auto M) {
         hipLaunchKernelGGL((lookahead_sensors_kernel<P, M>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
     });
+    return launch_status();
+}
+int ssa_forecast_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_forecast_params* f,
+                             void* stream)
+{
+    if (!c || !p || !sp || !f) return SSA_E_INVALID;
+    int rc = sensors_ok(sp, p);
+    if (rc != SSA_OK) return rc;
+    LookK lk;
+    rc = lookahead_args(c, p, &f->out, lk);
+    if (rc != SSA_OK) return rc;
+    if ((int64_t)sp->n_sensor * p->n_obj >= ((int64_t)1 << 31)) return SSA_E_INVALID;
+    if (f->n_steps < 1) return SSA_E_INVALID;
+    ForeSensK k;
+    k.k = lk.k;
+    k.k.p.launch_mask = 0;   // (the time word is read from env_time: a resident tile's steps do not see SSA_LAUNCH_INLINE_ENVS)
+    k.s = *sp;
+    k.s.upd = nullptr;       // (its action words and record destination are not read)
+    for (int q = 0; q < SSA_MAX_SENSORS; ++q) k.s.action[q] = -1;
+    k.f = *f;
+    int64_t ntiles, per_wave;
+    int nwork;
+    tile_grid(p->n_obj, ntiles, nwork, per_wave);
+    hipStream_t s = (hipStream_t)stream;
+    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(forecast_sensors_kernel<P>, dim3(nwork), dim3(64), 0, s, k, (int)ntiles, nwork); });
     return launch_status();
 }
 // the checks and the argument block shared by ssa_env_rollout_f64 and ssa_env_rollout_sensors_f64 (sens: r->actions is not read); SSA_OK or

@@ -110,6 +110,7 @@ class HotPathEngine:
         self._roll_sched = self.upd_sensors = None      # launch_rollout_sensors: its schedule (kept until the next launch), its record ring
         self._loop_ws = self._agent_ws = None           # workspaces of launch_closed_loop (with loop_error) and launch_agent_select
         self._look = self._look_s = None                # output buffers of launch_lookahead / launch_lookahead_sensors
+        self._fore = None                               # ... and of launch_forecast_sensors
         self._assign_ws = None                          # (S, workspace) of launch_assign_sensors
         self._assign_row = None                         # assign_row()'s
         self._pcache = {}
@@ -475,6 +476,29 @@ class HotPathEngine:
         rc = self._lib.ssa_lookahead_sensors_f64(self._cref, C.byref(p), C.byref(sensors), C.byref(o), s)
         if rc:
             raise _lib.SsaHipError("ssa_lookahead_sensors_f64 failed with code %d" % rc)
+        return res
+
+    def launch_forecast_sensors(self, slot_in, time_offset, sensors, n_steps, out=(), stream=None):
+        """enqueue the tasking forecast of a sensor network (include/ssa_hip.h: ssa_forecast_sensors_f64; one env): what
+        launch_lookahead_sensors would return at each of H = n_steps consecutive steps -- time indices time_offset .. time_offset + H - 1
+        -- if every sensor stayed idle in between, in ONE launch that keeps the objects' state on chip across the steps.  Nothing of the
+        engine's state is written.  Returns a dict of this engine's output tensors, objects at the caller's indices: score [H, S, m, 3],
+        status [H, S, m] int32, visible [H, S, m] uint8 and the parts of LOOKAHEAD_PARTS asked for in `out` (x_prior [H, m, 6], P_prior
+        [H, m, 6, 6], P_post [H, S, m, 6, 6]).  The buffers are allocated on first use (again when H or S changes) and reused by the next
+        call; the scores alone are 24 * H * S * m bytes, P_post 288 * H * S * m.  Asynchronous, no host sync."""
+        if self.E != 1:
+            raise _lib.SsaHipError("the forecast of a sensor network covers one env (n_env == 1)")
+        H = int(n_steps)
+        if H < 1:
+            raise _lib.SsaHipError("launch_forecast_sensors: n_steps must be >= 1, got %d" % H)
+        f = _lib.ssa_forecast_params()
+        f.n_steps = H
+        f.out, res = self._lookahead_out("launch_forecast_sensors", "_fore", (H, int(sensors.n_sensor), self.m), (H, self.m), out)
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        p = self._lookahead_params(slot_in, time_offset)
+        rc = self._lib.ssa_forecast_sensors_f64(self._cref, C.byref(p), C.byref(sensors), C.byref(f), s)
+        if rc:
+            raise _lib.SsaHipError("ssa_forecast_sensors_f64 failed with code %d" % rc)
         return res
 
     def launch_assign_sensors(self, look, column, action_row, fallback_row=None, picks=None, stream=None):

@@ -819,6 +819,25 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
             res[k] = r[k]
         return res
 
+    def forecast_sensors(self, horizon, covariances=False):
+        """The H-step tasking forecast of the network (no reference counterpart; include/ssa_hip.h: ssa_forecast_sensors_f64; DESIGN.md
+        section 8h): from the state at step i, what lookahead_sensors() would return at each of the steps i+1 .. i+H' -- H' =
+        min(horizon, steps - 1 - i) -- if every sensor stayed idle until then: when each object passes over each site, how far its
+        covariance has grown by then, and what an observation from that site at that step would gain.  ONE launch, and nothing of the
+        env changes: an env can be asked about its future without spending it.  A dict of CUDA tensors, objects in the env's own order,
+        S = n_sensor (1 without config['observers']: the env's own observer as a one-site network):
+            score   [H', S, m, 3]  float64: columns _lib.LOOK_*; NaN unless status == OK and visible from s at that step
+            visible [H', S, m]     uint8
+            status  [H', S, m]     int32
+        and with covariances=True also x_prior [H', m, 6], P_prior [H', m, 6, 6] and P_post [H', S, m, 6, 6].  Slab h assumes no update
+        before step i+1+h.  Memory: the scores are 24 * H' * S * m bytes (3.8 MB at 20 000 objects, 8 steps, one site), P_post twelve
+        times that.  The tensors are the env's buffers: the next call overwrites them."""
+        e, want = self._engine, self._lookahead_parts('forecast_sensors', covariances)
+        H = min(int(horizon), self.n - 1 - self.i)
+        if H < 1:
+            raise ValueError("forecast_sensors: a horizon of at least one step, got %r" % (horizon,))
+        return dict(e.launch_forecast_sensors(self.i % e.H, self.i + 1, self._sites(), H, out=want, stream=self._stream.cuda_stream))
+
     def aer_obs(self, obs):
         """:834-840 -- [az, el, range, trace(P)] per object, NaN/inf -> 0.001."""
         from .. import device
