@@ -1008,6 +1008,20 @@ SSA_DEV void stats_service_wave(const double* __restrict__ dpos, unsigned long l
     }
 }
 
+// ActBase: what an action source is unless it says otherwise -- the action is in memory (get() = -1: nothing to wait for, nothing to do
+// while waiting or in mid-step), no kind of process_wave's applies, and there are no sensor sites.  Each source below states only what
+// sets it apart: its kind as the flags process_wave reads, and sites().
+struct ActBase {
+    static constexpr bool late = false;           // the action is decided on the device while the step runs (ActLate)
+    static constexpr bool all = false;            // the lookahead: every row updated hypothetically, nothing committed
+    static constexpr bool sensors = false;        // a sensor network: one update per sensor, each with its own site
+    static constexpr bool look_sensors = false;   // the lookahead of a sensor network: `all`, one pass per sensor
+    static constexpr bool forecast = false;       // ... as step h of a forecast: `look_sensors` on a resident tile
+    SSA_DEV int get() { return -1; }
+    SSA_DEV void before_wait(Tiles&, int, int) {}
+    SSA_DEV void mid_step(Tiles&, int) {}
+    SSA_DEV const ssa_sensor_params* sites() const { return nullptr; }
+};
 // One wavefront advances up to 4 consecutive objects (one per 16-lane row) by one env step, complete semantics:
 // the robust_cholesky ladder is inline, conic branches beyond the strong-elliptic one are out-of-line calls taken
 // only by the lanes that need them.
@@ -1017,19 +1031,14 @@ SSA_DEV void stats_service_wave(const double* __restrict__ dpos, unsigned long l
 // rollouts).  ActLate (closed_loop_kernel, one env): the action of step k is decided ON THE DEVICE from the state step k - 1
 // left, while the predicts of step k are already running -- a wavefront asks for it only where the update needs it, behind
 // its predict, and every row prefetches the update's inputs for its OWN object in case it turns out to be the selected one.
-struct ActEarly {
-    static constexpr bool late = false;
-    SSA_DEV int get() { return -1; }
-    SSA_DEV void before_wait(Tiles&, int, int) {}
-    SSA_DEV void mid_step(Tiles&, int) {}
-};
+struct ActEarly : ActBase {};
 struct ActLate;
 struct LoopK;
 SSA_DEV void closed_loop_prescore(ActLate& a, Tiles& t, int lane, int cnt);   // (defined with the closed-loop kernel)
 SSA_DEV void closed_loop_store(const LoopK* lk, Tiles& t, int lane, int kk, int64_t base, int cnt);
 constexpr unsigned CL_ABORT_GEN = 0xFFFFFFFFu;            // decision number that means "give up" (a wavefront timed out)
 constexpr unsigned long long CL_TIMEOUT_TICKS = 200000000ull;   // default bound of a wait: 2 s of the 100 MHz wall clock (ssa_closed_loop_params.wait_ticks)
-struct ActLate {
+struct ActLate : ActBase {
     static constexpr bool late = true;
     unsigned long long* flag;        // this wavefront's group flag: (decision number << 32) | action
     unsigned long long* all_flags;   // [nflags] flags, 16 words apart (abort broadcast)
@@ -1099,25 +1108,18 @@ struct ActLate {
 // had chosen it (P+ = P- - K S K^T does not depend on the measured value), nothing committed.  The update block then runs Phase 1 in
 // all four rows at once and Phase 2 in four turns; the outputs go to `o` at the caller's rows, the measurement noise is never read,
 // and no history slot, status word, failure record, update record or statistics word is written.
-struct ActAll {
-    static constexpr bool late = false;
+struct ActAll : ActBase {
+    static constexpr bool all = true;
     const ssa_lookahead_out* o;
-    SSA_DEV int get() { return -1; }
-    SSA_DEV void before_wait(Tiles&, int, int) {}
-    SSA_DEV void mid_step(Tiles&, int) {}
 };
-template <class ACT> struct ActIsAll { static constexpr bool v = false; };
-template <> struct ActIsAll<ActAll> { static constexpr bool v = true; };
 // ActSensors (step_sensors_kernel, ssa_env_step_sensors_f64; one env): up to SSA_MAX_SENSORS sites each select one object.  A row is
 // selected if any sensor's action is its caller index; it then carries the lowest such sensor's index, and the update block reads that
 // sensor's site, elevation mask, R, noise table and record slot instead of ssa_consts' / ssa_step_params'.  `s` points at the kernel's
 // argument block: the actions and the geometry are wave-uniform (scalar) loads.
-struct ActSensors {
-    static constexpr bool late = false;
+struct ActSensors : ActBase {
+    static constexpr bool sensors = true;
     const ssa_sensor_params* s;
-    SSA_DEV int get() { return -1; }
-    SSA_DEV void before_wait(Tiles&, int, int) {}
-    SSA_DEV void mid_step(Tiles&, int) {}
+    SSA_DEV const ssa_sensor_params* sites() const { return s; }
     // the sensors' actions (all of them: indexable; one of them) and the records' base, through the pointer process_wave holds the sites by
     SSA_DEV const int32_t* actions(const ssa_sensor_params* sp) const { return sp->action; }
     SSA_DEV int action(const ssa_sensor_params* sp, int k) const { return sp->action[k]; }
@@ -1128,14 +1130,12 @@ struct ActSensors {
 // ActSensors' does (its action words and record pointer are not read); `row` is the step's row of the schedule in device memory --
 // SSA_MAX_SENSORS words, 32-byte aligned, read-only for the launch: one wave-uniform scalar load of eight words whatever S is; `upd` is
 // the step's record slot, null for a step that does not end up owning it.
-struct ActSchedule {
-    static constexpr bool late = false;
+struct ActSchedule : ActBase {
+    static constexpr bool sensors = true;
     const ssa_sensor_params* s;
     const int32_t* row;
     double* upd;
-    SSA_DEV int get() { return -1; }
-    SSA_DEV void before_wait(Tiles&, int, int) {}
-    SSA_DEV void mid_step(Tiles&, int) {}
+    SSA_DEV const ssa_sensor_params* sites() const { return s; }
     typedef int row_t __attribute__((ext_vector_type(SSA_MAX_SENSORS)));
     typedef const __attribute__((address_space(4))) int32_t* WordPtr;   // (constant for the launch: the scalar cache may serve it)
     SSA_DEV row_t actions(const ssa_sensor_params*) const
@@ -1157,41 +1157,27 @@ SSA_DEV int sensor_index(const ACT& a, const ssa_sensor_params* s, int64_t jid)
         if (k < s->n_sensor && act[k] >= 0 && (int64_t)act[k] == jid) sid = k;
     return sid;
 }
-template <class ACT> struct ActIsSensors { static constexpr bool v = false; };
-template <> struct ActIsSensors<ActSensors> { static constexpr bool v = true; };
-template <> struct ActIsSensors<ActSchedule> { static constexpr bool v = true; };
 // ActLookSensors (lookahead_sensors_kernel, ssa_lookahead_sensors_f64; one env): ActAll for every sensor of a network.  The predict
 // runs once; the update block and the outputs then run once per sensor (a pass), from that sensor's site with its elevation mask and R
 // -- wave-uniform: scalar loads of the argument block, no waterfall.  Sensor s's outputs go to row s * n_obj + the caller's index; the
 // prior (x_prior / P_prior) is written by the first pass only.
-struct ActLookSensors {
-    static constexpr bool late = false;
+struct ActLookSensors : ActBase {
+    static constexpr bool all = true, look_sensors = true;
     const ssa_lookahead_out* o;
     const ssa_sensor_params* s;
-    SSA_DEV int get() { return -1; }
-    SSA_DEV void before_wait(Tiles&, int, int) {}
-    SSA_DEV void mid_step(Tiles&, int) {}
+    SSA_DEV const ssa_sensor_params* sites() const { return s; }
 };
-template <class ACT> struct ActIsLookSensors { static constexpr bool v = false; };
-template <> struct ActIsLookSensors<ActLookSensors> { static constexpr bool v = true; };
-template <> struct ActIsAll<ActLookSensors> { static constexpr bool v = true; };
-template <class ACT> SSA_DEV const ssa_sensor_params* sensors_of(const ACT&) { return nullptr; }
-template <> SSA_DEV const ssa_sensor_params* sensors_of<ActSensors>(const ActSensors& a) { return a.s; }
-template <> SSA_DEV const ssa_sensor_params* sensors_of<ActSchedule>(const ActSchedule& a) { return a.s; }
-template <> SSA_DEV const ssa_sensor_params* sensors_of<ActLookSensors>(const ActLookSensors& a) { return a.s; }
 // ActForecastSensors (forecast_sensors_kernel, ssa_forecast_sensors_f64; one env): ActLookSensors for step h of a forecast, whose tile
-// stays in LDS from step to step with every sensor idle.  Three things differ from the one-step lookahead, each behind ActIsForecast
+// stays in LDS from step to step with every sensor idle.  Three things differ from the one-step lookahead, each behind `forecast`
 // in process_wave: the outputs go to slab h of the blocks `o` names (slab()); the status the tile carries to step h + 1 is the
 // predict's (a singular S of a hypothetical update shows in that step's outputs only); and a row that failed INSIDE the horizon is
 // handed on as the failure sentinels -- there is no ring slot to re-read, and the input slot holds its healthy state.
-struct ActForecastSensors {
-    static constexpr bool late = false;
+struct ActForecastSensors : ActBase {
+    static constexpr bool all = true, look_sensors = true, forecast = true;
     const ssa_lookahead_out* o;
     const ssa_sensor_params* s;
     int h;
-    SSA_DEV int get() { return -1; }
-    SSA_DEV void before_wait(Tiles&, int, int) {}
-    SSA_DEV void mid_step(Tiles&, int) {}
+    SSA_DEV const ssa_sensor_params* sites() const { return s; }
     // the output block of step h: [H][S * m] rows per sensor output, [H][m] rows of the prior
     SSA_DEV void slab(ssa_lookahead_out& os, int64_t m, int S) const
     {
@@ -1204,11 +1190,6 @@ struct ActForecastSensors {
         if (os.P_prior) os.P_prior += rp * 36;
     }
 };
-template <class ACT> struct ActIsForecast { static constexpr bool v = false; };
-template <> struct ActIsForecast<ActForecastSensors> { static constexpr bool v = true; };
-template <> struct ActIsLookSensors<ActForecastSensors> { static constexpr bool v = true; };
-template <> struct ActIsAll<ActForecastSensors> { static constexpr bool v = true; };
-template <> SSA_DEV const ssa_sensor_params* sensors_of<ActForecastSensors>(const ActForecastSensors& a) { return a.s; }
 // a pointer into the argument segment that the optimiser cannot see through: the (scalar) loads from it stay inside ActLookSensors'
 // passes instead of being hoisted in front of them, where their results would hold scalar registers across every pass
 template <class T> SSA_DEV const T* kernarg_opaque(const T* q)
@@ -1289,11 +1270,11 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // env's step 123.9 -> 130.4 us although its host side got 4 us shorter.)
     constexpr bool FOLD_OK = (TILE == 0);
     // SSA_LAUNCH_STATS_FROM_METRICS: the one-tile step kernel only (the launcher refuses it everywhere else)
-    constexpr bool FROM_METRICS = (TILE == 0) && !ACT::late && !ActIsAll<ACT>::v && !ActIsSensors<ACT>::v && !ActIsLookSensors<ACT>::v;
-    constexpr bool ALL = ActIsAll<ACT>::v;   // the lookahead: every row updated hypothetically, nothing committed (ActAll)
-    constexpr bool SENS = ActIsSensors<ACT>::v;   // a sensor network: one update per sensor, each with its own site (ActSensors)
-    constexpr bool LSENS = ActIsLookSensors<ACT>::v;   // the lookahead of a sensor network: ALL, one pass per sensor (ActLookSensors)
-    constexpr bool FCAST = ActIsForecast<ACT>::v;      // ... as step h of a forecast: LSENS on a resident tile (ActForecastSensors)
+    constexpr bool FROM_METRICS = (TILE == 0) && !ACT::late && !ACT::all && !ACT::sensors && !ACT::look_sensors;
+    constexpr bool ALL = ACT::all;   // the lookahead: every row updated hypothetically, nothing committed (ActAll)
+    constexpr bool SENS = ACT::sensors;   // a sensor network: one update per sensor, each with its own site (ActSensors)
+    constexpr bool LSENS = ACT::look_sensors;   // the lookahead of a sensor network: ALL, one pass per sensor (ActLookSensors)
+    constexpr bool FCAST = ACT::forecast;      // ... as step h of a forecast: LSENS on a resident tile (ActForecastSensors)
     // (ActLookSensors, multi-tile instance: the next tile's loads leave once, behind the last pass -- except with SSA_PROP_ELEMENTS, whose
     // out-of-line call then spills 8 more VGPRs: there they are issued as in every other kernel, after the propagator and again at the end
     // of each pass's update)
@@ -1390,7 +1371,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     }
     int sid = -1;   // (ActSensors: the sensor that updates this row's object, -1 for none)
     if constexpr (SENS) {
-        sid = valid ? sensor_index(asrc, sensors_of(asrc), jid) : -1;
+        sid = valid ? sensor_index(asrc, asrc.sites(), jid) : -1;
         act = (sid >= 0) ? (int)jid : -1;
     }
     bool my_update = ALL ? (valid && interval_ok) : SENS ? (sid >= 0 && interval_ok)
@@ -1408,7 +1389,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         const double* src = (l < 9) ? p.trans + (int64_t)tmod * 9 + l
                                     : p.z_noise + (int64_t)e * p.zn_stride_env + (int64_t)tmod * p.zn_stride_time + aobj * p.zn_stride_obj + (l - 9);
         if constexpr (SENS) {
-            if (l >= 9) src += (int64_t)sid * sensors_of(asrc)->zn_stride_sensor;   // (the sensor's own noise table)
+            if (l >= 9) src += (int64_t)sid * asrc.sites()->zn_stride_sensor;   // (the sensor's own noise table)
         }
         upd_in = *src;
     }
@@ -1602,7 +1583,7 @@ look_pass:
     if constexpr (LSENS) st_new = st_pred;
     bool look_vis = false, look_taken = false;   // (ActAll: the row's visibility and whether its update ran, for the outputs)
     // (ActSensors: the row's sensor matched again here rather than carried across the propagator)
-    const ssa_sensor_params* SP = PASS_ARGS ? kernarg_opaque(sensors_of(asrc)) : sensors_of(asrc);
+    const ssa_sensor_params* SP = PASS_ARGS ? kernarg_opaque(asrc.sites()) : asrc.sites();
     if constexpr (SENS) sid = valid ? sensor_index(asrc, SP, p.obj_ids ? (int64_t)t.Oid[g] : obj) : -1;
     if (__any(my_update)) {   // whole-wave branch: a wavefront without a selected object skips the block, its variables included
     bool upd_go = false, taken = false, visible = false, attempted = false;
@@ -2147,6 +2128,21 @@ SSA_DEV int xcd_tile(int b, int n)
     return x * q + (x < r ? x : r) + i;
 }
 
+// The issue priority of a wavefront for its next turn (a tile of a grid-stride step, a step of a resident tile), rotated by its slot on
+// its SIMD (HW_ID bits 3:0).  The SIMD arbiter serves the oldest wavefront first: left alone, the 5 co-resident wavefronts finish their
+// K steps one after the other and the SIMD runs the tail of the launch with 4, 3, 2, 1 of them (latency-bound).  Rotating the issue
+// priority per turn keeps them level, so all stay resident and the stages of different wavefronts interleave until the end.
+// (s_setprio takes an immediate: hence the switch.)
+SSA_DEV void rotate_issue_priority(unsigned wave_slot, unsigned turn)
+{
+    switch ((wave_slot + turn) & 3u) {
+        case 0: __builtin_amdgcn_s_setprio(0); break;
+        case 1: __builtin_amdgcn_s_setprio(1); break;
+        case 2: __builtin_amdgcn_s_setprio(2); break;
+        default: __builtin_amdgcn_s_setprio(3); break;
+    }
+}
+
 // The tile walk of the four tile kernels: step_fast_kernel (ActEarly), step_sensors_kernel (ActSensors), lookahead_kernel (ActAll)
 // and lookahead_sensors_kernel (ActLookSensors).  MULTI = false is the one-tile-per-wavefront instance (every launch up to
 // 20 480 objects): no loop, no staging registers.  MULTI = true is the grid-stride walk: wavefront w advances tiles w, w + G,
@@ -2160,7 +2156,7 @@ SSA_DEV int xcd_tile(int b, int n)
 // scalars: they are PRELOADED into SGPRs at wavefront launch (-amdgpu-kernarg-preload-count, _build.py), so the tile's loads --
 // the first link of every wavefront's dependency chain -- leave without waiting for a scalar-memory round trip to the segment.
 // That holds only while NOTHING in front of the loads reads the block: the one-tile instance therefore gets the count of WHOLE tiles
-// in `ntiles` (tile_count_arg) and decides "LDS-DMA or the ragged tile's register path" from it -- decided from n_env x n_obj, as
+// in `ntiles` (TileGrid::arg) and decides "LDS-DMA or the ragged tile's register path" from it -- decided from n_env x n_obj, as
 // it was, the loads stood behind a scalar load of both and its wait.  The grid-stride instance keeps the tile count there.
 template <class K> struct TileArgs {
     int ntiles, nwork;
@@ -2194,14 +2190,14 @@ SSA_DEV const StepK& step_of(const StepK& k) { return k; }
 SSA_DEV const StepK& step_of(const LookK& k) { return k.k; }
 SSA_DEV const StepK& step_of(const SensK& k) { return k.k; }
 SSA_DEV const StepK& step_of(const LookSensK& k) { return k.k.k; }
-SSA_DEV ActEarly act_of(const StepK&) { return ActEarly(); }
-SSA_DEV ActAll act_of(const LookK& k) { return ActAll{&k.o}; }
-SSA_DEV ActSensors act_of(const SensK& k) { return ActSensors{&k.s}; }
-SSA_DEV ActLookSensors act_of(const LookSensK& k) { return ActLookSensors{&k.k.o, &k.s}; }
+SSA_DEV ActEarly act_of(const StepK&) { return ActEarly(); }   // (the leading {} below: ActBase, which has no members)
+SSA_DEV ActAll act_of(const LookK& k) { return ActAll{{}, &k.o}; }
+SSA_DEV ActSensors act_of(const SensK& k) { return ActSensors{{}, &k.s}; }
+SSA_DEV ActLookSensors act_of(const LookSensK& k) { return ActLookSensors{{}, &k.k.o, &k.s}; }
 // WALK: what sets the four kernels apart
 enum : unsigned {
     WALK_STEP = 1,          // a step: the deferred fold of the previous step's statistics in the extra wavefronts (unit >= nwork, one
-                            // per env) and the issue priority rotated per tile (see rollout_kernel)
+                            // per env) and the issue priority rotated per tile (rotate_issue_priority)
     WALK_ONE_ENV = 2,       // a sensor network: one env, n_obj objects
     WALK_ACT_SEGMENT = 4,   // the one-tile instance takes the ACT's pointers by the argument segment's address, not the argument's:
                             // kernarg_opaque (process_wave) needs a pointer into the segment
@@ -2240,7 +2236,7 @@ enum : unsigned {
         int tile = xcd_tile(unit, nwork);                                                                                                     \
         if (!MULTI) {                                                                                                                         \
             const int64_t base = (int64_t)tile * OBJ_PER_WAVE;                                                                                \
-            const bool whole = tile < ntiles;   /* (this instance: the count of WHOLE tiles, tile_count_arg) */                               \
+            const bool whole = tile < ntiles;   /* (this instance: the count of WHOLE tiles, TileGrid::arg)   */                               \
             /* (the object total -- scalar loads and a wait -- is formed where it is used: by the ragged tile, and behind the loads) */       \
             tile_dma_issue(t, pf, pre_P_in, pre_x_in, pre_x_true_in, pre_status, lane, base, whole, step_of(k_arg).p,                         \
                            ((WALK) & WALK_ONE_ENV) != 0);                                                                                     \
@@ -2264,14 +2260,7 @@ enum : unsigned {
         unsigned wave_slot, turn = 0;                                                                                                         \
         if ((WALK) & WALK_STEP) asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(wave_slot));                                 \
         for (; tile < ntiles; tile += nwork) {                                                                                                \
-            if ((WALK) & WALK_STEP) {                                                                                                         \
-                switch ((wave_slot + turn++) & 3u) {                                                                                          \
-                    case 0: __builtin_amdgcn_s_setprio(0); break;                                                                             \
-                    case 1: __builtin_amdgcn_s_setprio(1); break;                                                                             \
-                    case 2: __builtin_amdgcn_s_setprio(2); break;                                                                             \
-                    default: __builtin_amdgcn_s_setprio(3); break;                                                                            \
-                }                                                                                                                             \
-            }                                                                                                                                 \
+            if ((WALK) & WALK_STEP) rotate_issue_priority(wave_slot, turn++);                                                                 \
             asm volatile("" : "+s"(kp));                                                                                                      \
             asm volatile("" : "+v"(lane));                                                                                                    \
             const K& k = *(const K*)((const char*)kp + (offsetof(TileArgs<K>, k) - pre_off));                                                 \
@@ -2309,140 +2298,144 @@ struct RollSensK {
     ssa_sensor_params s;
     ssa_rollout_sensors_params rs;
 };
+// What sets the resident-tile kernels apart, chosen by the argument-block type (as step_of / act_of for the tile kernels): the step's
+// block (step_of), what the launch fixes -- its steps, its objects, a ring's strides (roll_plan) --, the block the tile is first loaded
+// from (roll_source), and the block and the ACT of step kk (roll_act).
 SSA_DEV const RollK& roll_of(const RollK& a) { return a; }
 SSA_DEV const RollK& roll_of(const RollSensK& a) { return a.k; }
+SSA_DEV const StepK& step_of(const RollK& a) { return a.k; }
+SSA_DEV const StepK& step_of(const RollSensK& a) { return a.k.k; }
 // the envs of the launch: a sensor network's is one (nothing per env is formed or carried, as WALK_ONE_ENV in the tile kernels)
 SSA_DEV int roll_envs(const RollK& a) { return a.k.p.n_env; }
 SSA_DEV int roll_envs(const RollSensK&) { return 1; }
-// the ACT policy of step kk, which writes ring slot `so` (owns: it is the step that finally owns the slot) -- after pk's own fields
-SSA_DEV ActEarly roll_act(const RollK&, ssa_step_params&, int, int, bool) { return ActEarly(); }
-SSA_DEV ActSchedule roll_act(const RollSensK& a, ssa_step_params& pk, int kk, int so, bool owns)
+// A rollout's plan: the ring of E envs -- slots, steps, objects and the strides of a slot -- formed once, in front of the walk's loops.
+struct Ring {
+    int E, H, K_steps;
+    int64_t total, sx, sP, so_, sm, su;
+};
+SSA_DEV Ring ring_of(const RollK& a, int E)
+{
+    const int H = a.r.history, K_steps = a.r.n_steps;
+    const int64_t total = (int64_t)E * a.k.p.n_obj;
+    return Ring{E, H, K_steps, total, total * 6, total * 36, total * 12, (int64_t)E * 4 * a.k.p.n_obj, (int64_t)E * SSA_UPD_STRIDE};
+}
+SSA_DEV Ring roll_plan(const RollK& a) { return ring_of(a, roll_envs(a)); }
+SSA_DEV Ring roll_plan(const RollSensK& a) { return ring_of(a.k, roll_envs(a)); }
+// the tile's state comes from the ring's input slot ...
+SSA_DEV ssa_step_params roll_source(const RollK& a, const Ring& g)
+{
+    const int si0 = (a.r.slot_out + g.H - 1) % g.H;
+    ssa_step_params p0 = a.k.p;
+    p0.x_true_in = a.r.x_true_ring + si0 * g.sx;
+    p0.x_in = a.r.x_ring + si0 * g.sx;
+    p0.P_in = a.r.P_ring + si0 * g.sP;
+    return p0;
+}
+SSA_DEV ssa_step_params roll_source(const RollSensK& a, const Ring& g) { return roll_source(a.k, g); }
+// the ACT policy of a rollout's step kk, which writes ring slot `so` (owns: it is the step that finally owns the slot) -- after pk's own fields
+SSA_DEV ActEarly ring_act(const RollK&, ssa_step_params&, int, int, bool) { return ActEarly(); }
+SSA_DEV ActSchedule ring_act(const RollSensK& a, ssa_step_params& pk, int kk, int so, bool owns)
 {
     pk.upd = nullptr;       // (the env's action word and record are not read, as in the network's step)
     pk.actions = nullptr;
-    return ActSchedule{&a.s, a.rs.actions + (int64_t)kk * SSA_MAX_SENSORS,
+    return ActSchedule{{}, &a.s, a.rs.actions + (int64_t)kk * SSA_MAX_SENSORS,
                        (a.rs.upd_ring && owns) ? a.rs.upd_ring + (int64_t)so * a.s.n_sensor * SSA_UPD_STRIDE : nullptr};
 }
-// One rollout kernel: NAME<PROP>(const K a, ntiles, nwork).  Written once and expanded into each kernel's body, as the tile kernels'
-// walk is (SSA_TILE_KERNEL): process_wave has to be inlined straight into the kernel.
-#define SSA_ROLLOUT_KERNEL(NAME, K)                                                                                                           \
+// ... and step kk reads slot si and writes slot so: the block (pk) and the ACT policy of step kk; `ka` is the block as re-derived for
+// this step.  One body for both rollouts, and the plan's scalars in locals of its own: the slot's derivation and ring_act's arguments
+// have to meet in ONE function with plain values to work on -- halves in functions of their own, or values read through `g` where they
+// are used, are optimised apart before they reach the kernel, which then compiles to other instructions.
+template <class K>
+SSA_DEV auto roll_act(const Ring& g, const K& ka, ssa_step_params& pk, int kk, int ntiles)
+{
+    const int E = g.E, H = g.H, K_steps = g.K_steps;
+    const int64_t sx = g.sx, sP = g.sP, so_ = g.so_, sm = g.sm, su = g.su;
+    const StepK& k = roll_of(ka).k;
+    const ssa_rollout_params& r = roll_of(ka).r;
+    const int so = (r.slot_out + kk) % H, si = (so + H - 1) % H;
+    pk = k.p;
+    pk.time_offset = k.p.time_offset + kk;
+    pk.x_true_in = r.x_true_ring + si * sx;  pk.x_true_out = r.x_true_ring + so * sx;
+    pk.x_in = r.x_ring + si * sx;            pk.x_out = r.x_ring + so * sx;
+    pk.P_in = r.P_ring + si * sP;            pk.P_out = r.P_ring + so * sP;
+    pk.obs = r.obs_ring + so * so_;
+    pk.metrics = r.metrics_ring + so * sm;
+    // per-ENV outputs are written by whichever wavefront owns the selected object, and wavefronts advance at their own pace: only the
+    // step that finally owns a ring slot may write it (per-object outputs have one writer, in order)
+    pk.upd = (r.upd_ring && kk >= K_steps - H) ? r.upd_ring + so * su : nullptr;
+    pk.actions = r.actions + (int64_t)kk * E;
+    pk.stat_shards = r.stat_shards + (int64_t)kk * E * SSA_STAT_SHARDS * SSA_STAT_SHARD_WORDS;
+    pk.spos_tiles = r.spos_tiles ? r.spos_tiles + (int64_t)kk * ntiles * 2 : nullptr;
+    pk.aer_out = nullptr;
+    return ring_act(ka, pk, kk, so, kk >= K_steps - H);
+}
+// One resident-tile kernel: NAME<PROP>(const K a, ntiles, nwork).  A wavefront loads its tile once and advances it plan.K_steps steps
+// in LDS.  Written once and expanded into each kernel's body, as the tile kernels' walk is (SSA_TILE_KERNEL): process_wave has to be
+// inlined straight into the kernel.
+#define SSA_RESIDENT_KERNEL(NAME, K)                                                                                                          \
     template <int PROP>                                                                                                                       \
     __global__ void __launch_bounds__(64, SSA_STEP_WAVES) NAME(const K a, int ntiles, int nwork)                                              \
     {                                                                                                                                         \
-        const StepK& k_arg = roll_of(a).k;                                                                                                    \
         __shared__ Tiles t;                                                                                                                   \
         int lane = threadIdx.x;                                                                                                               \
-        const int E = roll_envs(a), H = roll_of(a).r.history, K_steps = roll_of(a).r.n_steps;                                                 \
-        const int64_t total = (int64_t)E * k_arg.p.n_obj;                                                                                     \
-        const int64_t sx = total * 6, sP = total * 36, so_ = total * 12, sm = (int64_t)E * 4 * k_arg.p.n_obj,                                 \
-                      su = (int64_t)E * SSA_UPD_STRIDE;                                                                                       \
+        const auto plan = roll_plan(a);                                                                                                       \
+        const int K_steps = plan.K_steps;                                                                                                     \
+        const int64_t total = plan.total;                                                                                                     \
         TileRegs pf;                                                                                                                          \
         typedef const __attribute__((address_space(4))) K* RollArgPtr;                                                                        \
         RollArgPtr kp = (RollArgPtr)__builtin_amdgcn_kernarg_segment_ptr();                                                                   \
         for (int tile = xcd_tile((int)blockIdx.x, nwork); tile < ntiles; tile += nwork) {                                                     \
             const int64_t base = (int64_t)tile * OBJ_PER_WAVE;                                                                                \
             const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);                                             \
-            {   /* the tile's state from the input slot */                                                                                    \
-                const int si0 = (roll_of(a).r.slot_out + H - 1) % H;                                                                          \
-                ssa_step_params p0 = k_arg.p;                                                                                                 \
-                p0.x_true_in = roll_of(a).r.x_true_ring + si0 * sx;                                                                           \
-                p0.x_in = roll_of(a).r.x_ring + si0 * sx;                                                                                     \
-                p0.P_in = roll_of(a).r.P_ring + si0 * sP;                                                                                     \
+            {                                                                                                                                 \
+                const ssa_step_params p0 = roll_source(a, plan);                                                                              \
                 wave_lds_sync();   /* the previous tile's last stores have read the tiles */                                                  \
                 tile_issue(pf, p0, lane, base, cnt);                                                                                          \
                 tile_commit(t, pf, lane);                                                                                                     \
-                if (lane < 36) t.Q[lane] = k_arg.c.Q[lane];   /* process_wave<.., 2> expects the process noise in place */                    \
+                if (lane < 36) t.Q[lane] = step_of(a).c.Q[lane];   /* process_wave<.., 2> expects the process noise in place */               \
             }                                                                                                                                 \
             unsigned wave_slot;   /* the wavefront's slot on its SIMD (HW_ID bits 3:0) */                                                     \
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(wave_slot));                                                     \
             for (int kk = 0; kk < K_steps; ++kk) {                                                                                            \
-                /* The SIMD arbiter serves the oldest wavefront first: left alone, the 5 co-resident wavefronts finish                        \
-                   their K steps one after the other and the SIMD runs the tail of the launch with 4, 3, 2, 1 of them                         \
-                   (latency-bound).  Rotating the issue priority per step keeps them level, so all stay resident and                          \
-                   the stages of different wavefronts interleave until the end. */                                                            \
-                switch ((wave_slot + (unsigned)kk) & 3u) {                                                                                    \
-                    case 0: __builtin_amdgcn_s_setprio(0); break;                                                                             \
-                    case 1: __builtin_amdgcn_s_setprio(1); break;                                                                             \
-                    case 2: __builtin_amdgcn_s_setprio(2); break;                                                                             \
-                    default: __builtin_amdgcn_s_setprio(3); break;                                                                            \
-                }                                                                                                                             \
+                rotate_issue_priority(wave_slot, (unsigned)kk);                                                                               \
                 asm volatile("" : "+s"(kp));      /* per step, as per tile in the tile kernels: nothing carried around the loop */            \
                 asm volatile("" : "+v"(lane));                                                                                                \
                 const K& ka = *(const K*)kp;                                                                                                  \
-                const StepK& k = roll_of(ka).k;                                                                                               \
-                const ssa_rollout_params& r = roll_of(ka).r;                                                                                  \
-                const int so = (r.slot_out + kk) % H, si = (so + H - 1) % H;                                                                  \
-                ssa_step_params pk = k.p;                                                                                                     \
-                pk.time_offset = k.p.time_offset + kk;                                                                                        \
-                pk.x_true_in = r.x_true_ring + si * sx;  pk.x_true_out = r.x_true_ring + so * sx;                                             \
-                pk.x_in = r.x_ring + si * sx;            pk.x_out = r.x_ring + so * sx;                                                       \
-                pk.P_in = r.P_ring + si * sP;            pk.P_out = r.P_ring + so * sP;                                                       \
-                pk.obs = r.obs_ring + so * so_;                                                                                               \
-                pk.metrics = r.metrics_ring + so * sm;                                                                                        \
-                /* per-ENV outputs are written by whichever wavefront owns the selected object, and wavefronts advance at                     \
-                   their own pace: only the step that finally owns a ring slot may write it (per-object outputs have one                      \
-                   writer, in order) */                                                                                                       \
-                pk.upd = (r.upd_ring && kk >= K_steps - H) ? r.upd_ring + so * su : nullptr;                                                  \
-                pk.actions = r.actions + (int64_t)kk * E;                                                                                     \
-                pk.stat_shards = r.stat_shards + (int64_t)kk * E * SSA_STAT_SHARDS * SSA_STAT_SHARD_WORDS;                                    \
-                pk.spos_tiles = r.spos_tiles ? r.spos_tiles + (int64_t)kk * ntiles * 2 : nullptr;                                             \
-                pk.aer_out = nullptr;                                                                                                         \
-                auto act = roll_act(ka, pk, kk, so, kk >= K_steps - H);                                                                       \
-                process_wave<PROP, 2>(t, k.c, pk, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, act);               \
+                ssa_step_params pk;                                                                                                           \
+                auto act = roll_act(plan, ka, pk, kk, ntiles);                                                                                \
+                process_wave<PROP, 2>(t, step_of(ka).c, pk, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, act);     \
                 wave_lds_sync();                                                                                                              \
             }                                                                                                                                 \
         }                                                                                                                                     \
     }
-SSA_ROLLOUT_KERNEL(rollout_kernel, RollK)                  // an env's schedule (ssa_env_rollout_f64)
-SSA_ROLLOUT_KERNEL(rollout_sensors_kernel, RollSensK)      // a sensor network's (ssa_env_rollout_sensors_f64)
-#undef SSA_ROLLOUT_KERNEL
+SSA_RESIDENT_KERNEL(rollout_kernel, RollK)                  // an env's schedule (ssa_env_rollout_f64)
+SSA_RESIDENT_KERNEL(rollout_sensors_kernel, RollSensK)      // a sensor network's (ssa_env_rollout_sensors_f64)
 
 // Forecast: the lookahead of a sensor network at each of H consecutive steps, every sensor idle in between, in ONE launch
-// (ssa_forecast_sensors_f64).  A sibling of the rollout kernels: a wavefront loads its tile once and runs H predicts on it with state,
+// (ssa_forecast_sensors_f64).  The third resident-tile kernel: a wavefront loads its tile once and runs H predicts on it with state,
 // covariance, truth and status resident in LDS -- what the passes of ActLookSensors leave in t.X / t.P IS what an idle step would have
-// stored -- and writes nothing but slab h of the outputs.  No ring, no statistics, no records: the caller's state is only read.
+// stored -- and writes nothing but slab h of the outputs.  No ring, no statistics, no records: the caller's state is only read -- the
+// tile comes from the caller's block, and step h's block differs from it in the time alone.
 struct ForeSensK {   // ONE kernel argument (see RollK)
     StepK k;
     ssa_sensor_params s;
     ssa_forecast_params f;
 };
-template <int PROP>
-__global__ void __launch_bounds__(64, SSA_STEP_WAVES) forecast_sensors_kernel(const ForeSensK a, int ntiles, int nwork)
+SSA_DEV const StepK& step_of(const ForeSensK& a) { return a.k; }
+struct ForePlan {   // (no ring: the steps and the objects)
+    int K_steps;
+    int64_t total;
+};
+SSA_DEV ForePlan roll_plan(const ForeSensK& a) { return ForePlan{a.f.n_steps, a.k.p.n_obj}; }
+SSA_DEV ssa_step_params roll_source(const ForeSensK& a, ForePlan) { return a.k.p; }
+SSA_DEV ActForecastSensors roll_act(ForePlan, const ForeSensK& ka, ssa_step_params& pk, int h, int)
 {
-    __shared__ Tiles t;
-    int lane = threadIdx.x;
-    const int H = a.f.n_steps;
-    const int64_t total = a.k.p.n_obj;
-    TileRegs pf;
-    typedef const __attribute__((address_space(4))) ForeSensK* ForeArgPtr;
-    ForeArgPtr kp = (ForeArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    for (int tile = xcd_tile((int)blockIdx.x, nwork); tile < ntiles; tile += nwork) {
-        const int64_t base = (int64_t)tile * OBJ_PER_WAVE;
-        const int cnt = (int)((total - base) < OBJ_PER_WAVE ? (total - base) : OBJ_PER_WAVE);
-        wave_lds_sync();   // the previous tile's last stores have read the tiles
-        tile_issue(pf, a.k.p, lane, base, cnt);
-        tile_commit(t, pf, lane);
-        if (lane < 36) t.Q[lane] = a.k.c.Q[lane];   // process_wave<.., 2> expects the process noise in place
-        unsigned wave_slot;   // the wavefront's slot on its SIMD: the issue priority rotates per step, as in the rollout
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(wave_slot));
-        for (int h = 0; h < H; ++h) {
-            switch ((wave_slot + (unsigned)h) & 3u) {
-                case 0: __builtin_amdgcn_s_setprio(0); break;
-                case 1: __builtin_amdgcn_s_setprio(1); break;
-                case 2: __builtin_amdgcn_s_setprio(2); break;
-                default: __builtin_amdgcn_s_setprio(3); break;
-            }
-            asm volatile("" : "+s"(kp));      // per step: nothing carried around the loop
-            asm volatile("" : "+v"(lane));
-            const ForeSensK& ka = *(const ForeSensK*)kp;
-            ssa_step_params pk = ka.k.p;
-            pk.time_offset = ka.k.p.time_offset + h;
-            ActForecastSensors act{&ka.f.out, &ka.s, h};   // (pointers into the segment: kernarg_opaque in process_wave)
-            process_wave<PROP, 2>(t, ka.k.c, pk, lane, base + (lane >> 4), (lane >> 4) < cnt, base, cnt, pf, 0, 0, tile, act);
-            wave_lds_sync();
-        }
-    }
+    pk = ka.k.p;
+    pk.time_offset = ka.k.p.time_offset + h;
+    return ActForecastSensors{{}, &ka.f.out, &ka.s, h};   // (pointers into the segment: kernarg_opaque in process_wave)
 }
+SSA_RESIDENT_KERNEL(forecast_sensors_kernel, ForeSensK)
+#undef SSA_RESIDENT_KERNEL
 // grid (n_steps, n_env): folds step k's shard set into the statistics slot of step k -- when that slot still
 // belongs to step k at the end of the rollout (the last `history` steps) -- and clears it
 __global__ void __launch_bounds__(64) rollout_fold_kernel(unsigned long long* __restrict__ shards, double* __restrict__ stats_ring,
@@ -3345,16 +3338,11 @@ __global__ void __launch_bounds__(64, SSA_STEP_WAVES) closed_loop_kernel(const L
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(wave_slot));
     bool boost = false;   // this wavefront ran the previous step's update: it is behind the others
     for (int kk = 0; kk < K; ++kk) {
-        // issue priority rotated per step (see rollout_kernel) -- except for the wavefront that ran the update: it lost
+        // issue priority rotated per step (rotate_issue_priority) -- except for the wavefront that ran the update: it lost
         // microseconds the others spent on the next predict, and if it stays behind it is the last to announce its part of
         // the NEXT step too, with every wavefront waiting for it.  It catches up at top priority.
         if (boost) __builtin_amdgcn_s_setprio(3);
-        else switch ((wave_slot + (unsigned)kk) & 3u) {
-            case 0: __builtin_amdgcn_s_setprio(0); break;
-            case 1: __builtin_amdgcn_s_setprio(1); break;
-            case 2: __builtin_amdgcn_s_setprio(2); break;
-            default: __builtin_amdgcn_s_setprio(3); break;
-        }
+        else rotate_issue_priority(wave_slot, (unsigned)kk);
         asm volatile("" : "+s"(kp));
         asm volatile("" : "+v"(lane));
         const StepK& k = ((const LoopK*)kp)->k;
@@ -3952,18 +3940,21 @@ static bool consts_ok(const ssa_consts* c)
 }
 // the tile kernels' grid: tiles per wavefront T = ceil(tiles / resident wavefront slots); G = ceil(tiles / T) wavefronts.  T = 1:
 // the one-tile instance, else the grid-stride walk.
-static void tile_grid(int64_t total, int64_t& ntiles, int& nwork, int64_t& per_wave)
-{
-    ntiles = (total + OBJ_PER_WAVE - 1) / OBJ_PER_WAVE;
-    const int64_t slots = (int64_t)device_cu_count() * 4 * SSA_STEP_WAVES;
-    per_wave = (ntiles + slots - 1) / slots;
-    nwork = (int)((ntiles + per_wave - 1) / per_wave);
-}
-// the tile kernels' first argument: the grid-stride walk's tile count; the one-tile instance's count of WHOLE tiles (a tile below it
+// `arg`, the tile kernels' first argument: the grid-stride walk's tile count; the one-tile instance's count of WHOLE tiles (a tile below it
 // takes the LDS-DMA path, decided from a preloaded argument: SSA_TILE_KERNEL)
-static int tile_count_arg(int64_t total, int64_t ntiles, int64_t per_wave)
+struct TileGrid {
+    int64_t ntiles, per_wave;
+    int nwork, arg;
+};
+static TileGrid tile_grid(int64_t total)
 {
-    return per_wave != 1 ? (int)ntiles : (int)(total / OBJ_PER_WAVE);
+    TileGrid g;
+    g.ntiles = (total + OBJ_PER_WAVE - 1) / OBJ_PER_WAVE;
+    const int64_t slots = (int64_t)device_cu_count() * 4 * SSA_STEP_WAVES;
+    g.per_wave = (g.ntiles + slots - 1) / slots;
+    g.nwork = (int)((g.ntiles + g.per_wave - 1) / g.per_wave);
+    g.arg = g.per_wave != 1 ? (int)g.ntiles : (int)(total / OBJ_PER_WAVE);
+    return g;
 }
 // the checks of a sensor network's sites that its step and its lookahead share; SSA_OK or the refusal
 static int sensors_ok(const ssa_sensor_params* sp, const ssa_step_params* p)
@@ -3973,6 +3964,19 @@ static int sensors_ok(const ssa_sensor_params* sp, const ssa_step_params* p)
     for (int k = 0; k < sp->n_sensor; ++k)
         if (!(sp->obs_limit[k] == sp->obs_limit[k])) return SSA_E_INVALID;
     return SSA_OK;
+}
+// ... and of the sensors' own noise tables, where the measurement noise is read
+static bool noise_stride_ok(const ssa_sensor_params* sp)
+{
+    return sp->zn_stride_sensor >= 0 && (sp->n_sensor <= 1 || sp->zn_stride_sensor != 0);
+}
+// a network's sites as the kernels take them that read neither its action words nor its record destination
+static ssa_sensor_params idle_sites(const ssa_sensor_params* sp)
+{
+    ssa_sensor_params s = *sp;
+    s.upd = nullptr;
+    for (int q = 0; q < SSA_MAX_SENSORS; ++q) s.action[q] = -1;
+    return s;
 }
 
 // sens: a sensor network's step (ssa_env_step_sensors_f64; checked by the caller) -- step_sensors_kernel instead of step_fast_kernel
@@ -4005,26 +4009,23 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     k.p = *p;
     const int64_t total = (int64_t)p->n_env * p->n_obj;
     if (total >= ((int64_t)1 << 31)) return SSA_E_INVALID;
-    int64_t ntiles, per_wave;
-    int nwork;
-    tile_grid(total, ntiles, nwork, per_wave);
+    const TileGrid g = tile_grid(total);
     const bool fast_stats = p->stat_shards != nullptr;   // statistics by the common-path kernel's atomics
     const bool defer = fast_stats && (p->launch_mask & SSA_LAUNCH_DEFER_FOLD);
     if (defer && p->stat_shards_prev && (!p->stats_prev || p->stat_shards_prev == p->stat_shards)) return SSA_E_INVALID;
     const bool from_metrics = (p->launch_mask & SSA_LAUNCH_STATS_FROM_METRICS) != 0;
     if (from_metrics) {   // (the one-tile step kernel of one env, deferred fold: see the bit)
-        if (!defer || sens || p->n_env != 1 || per_wave != 1 || (p->launch_mask & SSA_LAUNCH_FOLD_INSIDE) || p->stat_shards_clear)
+        if (!defer || sens || p->n_env != 1 || g.per_wave != 1 || (p->launch_mask & SSA_LAUNCH_FOLD_INSIDE) || p->stat_shards_clear)
             return SSA_E_UNSUPPORTED;
         if (p->stat_shards_prev && !p->metrics_prev) return SSA_E_INVALID;
     }
     const int nfold = (defer && p->stat_shards_prev) ? (from_metrics ? STAT_SERVICE_WAVES : p->n_env) : 0;
-    dim3 grid((unsigned)(nwork + nfold)), block(64);
+    dim3 grid((unsigned)(g.nwork + nfold)), block(64);
     const int nparts = post_parts(p->n_obj, p->n_env);
     StatAcc* parts = (StatAcc*)p->stat_ws;
     hipStream_t s = (hipStream_t)stream;
     const unsigned mask = (p->launch_mask & 7u) ? (p->launch_mask & 7u) : 7u;   // diagnostic: time one launch alone
     const int prop = c->propagator;
-    const int nt = tile_count_arg(total, ntiles, per_wave);
     if ((mask & 1u) && sens) {
         SensK ks;
         ks.k = k;
@@ -4032,17 +4033,17 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
         ks.k.p.actions = nullptr;
         ks.k.p.launch_mask &= ~SSA_LAUNCH_INLINE_ACTION;
         ks.s = *sens;
-        with_prop(prop, per_wave != 1, [&](auto P, auto M) {
-            hipExtLaunchKernelGGL((step_sensors_kernel<P, M>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
+        with_prop(prop, g.per_wave != 1, [&](auto P, auto M) {
+            hipExtLaunchKernelGGL((step_sensors_kernel<P, M>), grid, block, 0, s, ev0, ev1, 0, g.arg, g.nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
         });
     } else if (mask & 1u) {   // (ev0, ev1: dispatch timestamps of this kernel for ssa_env_step_profiled_f64, else null)
-        with_prop(prop, per_wave != 1, [&](auto P, auto M) {
-            hipExtLaunchKernelGGL((step_fast_kernel<P, M>), grid, block, 0, s, ev0, ev1, 0, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+        with_prop(prop, g.per_wave != 1, [&](auto P, auto M) {
+            hipExtLaunchKernelGGL((step_fast_kernel<P, M>), grid, block, 0, s, ev0, ev1, 0, g.arg, g.nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
         });
     }
     if (fast_stats) {   // (the aer_out payload, if any, was the step kernel's epilogue) a one-wave fold finishes the step
                         // (2 launches), unless deferred (1 launch)
-        if ((p->launch_mask & SSA_LAUNCH_FOLD_INSIDE) && per_wave == 1) return launch_status();   // (folded by the step kernel's last wavefronts)
+        if ((p->launch_mask & SSA_LAUNCH_FOLD_INSIDE) && g.per_wave == 1) return launch_status();   // (folded by the step kernel's last wavefronts)
         if ((mask & 6u) && !defer && p->stats)   // (stats NULL: the caller consumes the raw shard words, see stat_shards_clear)
             hipLaunchKernelGGL(reward_fold_kernel, dim3(p->n_env), dim3(64), 0, s, (unsigned long long*)p->stat_shards, p->stats,
                                (const unsigned long long*)p->spos_tiles, p->n_obj);
@@ -4058,10 +4059,7 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
 int32_t ssa_stats_from_metrics_waves(int64_t n_obj, int32_t n_env)
 {
     if (n_obj <= 0 || n_env != 1) return 0;
-    int64_t ntiles, per_wave;
-    int nwork;
-    tile_grid(n_obj, ntiles, nwork, per_wave);
-    return per_wave == 1 ? STAT_SERVICE_WAVES : 0;
+    return tile_grid(n_obj).per_wave == 1 ? STAT_SERVICE_WAVES : 0;
 }
 int ssa_stats_fold_metrics_f64(const double* metrics, uint64_t* stat_shards, const uint64_t* spos_tiles, double* stats, int64_t n_obj,
                                void* stream)
@@ -4080,7 +4078,7 @@ int ssa_env_step_sensors_f64(const ssa_consts* c, const ssa_step_params* p, cons
     if (!c || !p || !sp) return SSA_E_INVALID;
     const int rc = sensors_ok(sp, p);
     if (rc != SSA_OK) return rc;
-    if (sp->zn_stride_sensor < 0 || (sp->n_sensor > 1 && sp->zn_stride_sensor == 0)) return SSA_E_INVALID;
+    if (!noise_stride_ok(sp)) return SSA_E_INVALID;
     return step_launch(c, p, stream, nullptr, nullptr, sp);
 }
 // dispatch-timestamp event pairs, created on first use (a ring, so that back-to-back launches can be timed
@@ -4133,64 +4131,56 @@ int ssa_lookahead_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_l
     LookK k;
     const int rc = lookahead_args(c, p, o, k);
     if (rc != SSA_OK) return rc;
-    int64_t ntiles, per_wave;
-    int nwork;
-    tile_grid((int64_t)p->n_env * p->n_obj, ntiles, nwork, per_wave);
-    const int nt = tile_count_arg((int64_t)p->n_env * p->n_obj, ntiles, per_wave);
-    dim3 grid((unsigned)nwork), block(64);
+    const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
+    dim3 grid((unsigned)g.nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
-    with_prop(c->propagator, per_wave != 1, [&](auto P, auto M) {
-        hipLaunchKernelGGL((lookahead_kernel<P, M>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+    with_prop(c->propagator, g.per_wave != 1, [&](auto P, auto M) {
+        hipLaunchKernelGGL((lookahead_kernel<P, M>), grid, block, 0, s, g.arg, g.nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
     });
     return launch_status();
 }
-int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_lookahead_out* o,
-                              void* stream)
+// ... and by ssa_lookahead_sensors_f64 and ssa_forecast_sensors_f64 on top of it: the network's checks, and its sites in `sites`
+static int lookahead_sensors_args(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_lookahead_out* o,
+                                  LookK& k, ssa_sensor_params& sites)
 {
     if (!c || !p || !sp || !o) return SSA_E_INVALID;
     int rc = sensors_ok(sp, p);
     if (rc != SSA_OK) return rc;
-    LookSensK k;
-    rc = lookahead_args(c, p, o, k.k);
+    rc = lookahead_args(c, p, o, k);
     if (rc != SSA_OK) return rc;
     if ((int64_t)sp->n_sensor * p->n_obj >= ((int64_t)1 << 31)) return SSA_E_INVALID;
-    k.s = *sp;
-    k.s.upd = nullptr;   // (its action words and record destination are not read)
-    for (int q = 0; q < SSA_MAX_SENSORS; ++q) k.s.action[q] = -1;
-    int64_t ntiles, per_wave;
-    int nwork;
-    tile_grid(p->n_obj, ntiles, nwork, per_wave);
-    const int nt = tile_count_arg(p->n_obj, ntiles, per_wave);
-    dim3 grid((unsigned)nwork), block(64);
+    sites = idle_sites(sp);
+    return SSA_OK;
+}
+int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_lookahead_out* o,
+                              void* stream)
+{
+    LookSensK k;
+    const int rc = lookahead_sensors_args(c, p, sp, o, k.k, k.s);
+    if (rc != SSA_OK) return rc;
+    const TileGrid g = tile_grid(p->n_obj);
+    dim3 grid((unsigned)g.nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
-    with_prop(c->propagator, per_wave != 1, [&](auto P, auto M) {
-        hipLaunchKernelGGL((lookahead_sensors_kernel<P, M>), grid, block, 0, s, nt, nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+    with_prop(c->propagator, g.per_wave != 1, [&](auto P, auto M) {
+        hipLaunchKernelGGL((lookahead_sensors_kernel<P, M>), grid, block, 0, s, g.arg, g.nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
     });
     return launch_status();
 }
 int ssa_forecast_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_forecast_params* f,
                              void* stream)
 {
-    if (!c || !p || !sp || !f) return SSA_E_INVALID;
-    int rc = sensors_ok(sp, p);
-    if (rc != SSA_OK) return rc;
+    if (!f) return SSA_E_INVALID;
     LookK lk;
-    rc = lookahead_args(c, p, &f->out, lk);
-    if (rc != SSA_OK) return rc;
-    if ((int64_t)sp->n_sensor * p->n_obj >= ((int64_t)1 << 31)) return SSA_E_INVALID;
-    if (f->n_steps < 1) return SSA_E_INVALID;
     ForeSensK k;
+    const int rc = lookahead_sensors_args(c, p, sp, &f->out, lk, k.s);
+    if (rc != SSA_OK) return rc;
+    if (f->n_steps < 1) return SSA_E_INVALID;
     k.k = lk.k;
     k.k.p.launch_mask = 0;   // (the time word is read from env_time: a resident tile's steps do not see SSA_LAUNCH_INLINE_ENVS)
-    k.s = *sp;
-    k.s.upd = nullptr;       // (its action words and record destination are not read)
-    for (int q = 0; q < SSA_MAX_SENSORS; ++q) k.s.action[q] = -1;
     k.f = *f;
-    int64_t ntiles, per_wave;
-    int nwork;
-    tile_grid(p->n_obj, ntiles, nwork, per_wave);
+    const TileGrid g = tile_grid(p->n_obj);
     hipStream_t s = (hipStream_t)stream;
-    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(forecast_sensors_kernel<P>, dim3(nwork), dim3(64), 0, s, k, (int)ntiles, nwork); });
+    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(forecast_sensors_kernel<P>, dim3(g.nwork), dim3(64), 0, s, k, (int)g.ntiles, g.nwork); });
     return launch_status();
 }
 // the checks and the argument block shared by ssa_env_rollout_f64 and ssa_env_rollout_sensors_f64 (sens: r->actions is not read); SSA_OK or
@@ -4228,12 +4218,10 @@ int ssa_env_rollout_f64(const ssa_consts* c, const ssa_step_params* p, const ssa
     RollK rk;
     const int rc = rollout_args(c, p, r, false, rk);
     if (rc != SSA_OK) return rc;
-    int64_t ntiles, per_wave;
-    int nwork;
-    tile_grid((int64_t)p->n_env * p->n_obj, ntiles, nwork, per_wave);
+    const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     hipStream_t s = (hipStream_t)stream;
-    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(rollout_kernel<P>, dim3(nwork), dim3(64), 0, s, rk, (int)ntiles, nwork); });
-    return rollout_fold(p, r, ntiles, s);
+    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(rollout_kernel<P>, dim3(g.nwork), dim3(64), 0, s, rk, (int)g.ntiles, g.nwork); });
+    return rollout_fold(p, r, g.ntiles, s);
 }
 int ssa_env_rollout_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, const ssa_sensor_params* sp,
                                 const ssa_rollout_sensors_params* rs, void* stream)
@@ -4244,20 +4232,16 @@ int ssa_env_rollout_sensors_f64(const ssa_consts* c, const ssa_step_params* p, c
     if (rc != SSA_OK) return rc;
     rc = sensors_ok(sp, p);
     if (rc != SSA_OK) return rc;
-    if (sp->zn_stride_sensor < 0 || (sp->n_sensor > 1 && sp->zn_stride_sensor == 0)) return SSA_E_INVALID;
+    if (!noise_stride_ok(sp)) return SSA_E_INVALID;
     if (!rs->actions || ((uintptr_t)rs->actions % (SSA_MAX_SENSORS * sizeof(int32_t))) != 0) return SSA_E_INVALID;
     rk.k.r.actions = nullptr;    // (the env's action words and record ring are not read)
     rk.k.r.upd_ring = nullptr;
-    rk.s = *sp;
-    rk.s.upd = nullptr;          // (the schedule's rows and the record ring take their place)
-    for (int q = 0; q < SSA_MAX_SENSORS; ++q) rk.s.action[q] = -1;
+    rk.s = idle_sites(sp);       // (the schedule's rows and the record ring take their place)
     rk.rs = *rs;
-    int64_t ntiles, per_wave;
-    int nwork;
-    tile_grid(p->n_obj, ntiles, nwork, per_wave);
+    const TileGrid g = tile_grid(p->n_obj);
     hipStream_t s = (hipStream_t)stream;
-    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(rollout_sensors_kernel<P>, dim3(nwork), dim3(64), 0, s, rk, (int)ntiles, nwork); });
-    return rollout_fold(p, r, ntiles, s);
+    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(rollout_sensors_kernel<P>, dim3(g.nwork), dim3(64), 0, s, rk, (int)g.ntiles, g.nwork); });
+    return rollout_fold(p, r, g.ntiles, s);
 }
 int64_t ssa_closed_loop_workspace_bytes(int64_t n_obj, int32_t n_env)
 {
