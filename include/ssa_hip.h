@@ -538,7 +538,8 @@ int ssa_lookahead_f64(const ssa_consts *c_host, const ssa_step_params *p_host, c
  *   An idle sensor, every sensor of a step the update_interval skips, and a sensor whose object has failed get a record with
  *   SSA_UPD_ACTION = -1 (OBS_TAKEN = VISIBLE = 0 unless the update was attempted).
  *   Measurement noise of sensor s: z_noise + s*zn_stride_sensor + i*zn_stride_time + action[s]*zn_stride_obj (ssa_step_params strides).
- * n_env == 1 only (SSA_E_UNSUPPORTED otherwise); 1 <= n_sensor <= SSA_MAX_SENSORS. */
+ * n_env == 1 only (SSA_E_UNSUPPORTED otherwise; a network in each of several envs: ssa_env_step_sensors_envs_f64 below);
+ * 1 <= n_sensor <= SSA_MAX_SENSORS. */
 #define SSA_MAX_SENSORS 8
 typedef struct ssa_sensor_params {
     int32_t n_sensor;                      /* S */
@@ -552,6 +553,31 @@ typedef struct ssa_sensor_params {
     double *upd;                           /* [S][SSA_UPD_STRIDE] update record per sensor, or NULL */
 } ssa_sensor_params;
 int ssa_env_step_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_sensor_params *s_host, void *stream);
+
+/* ---------------------------------------------------------------- a sensor network in each of E envs, one launch
+ * ssa_env_step_sensors_f64 for every env of a vector launch: the sites (`sites`: n_sensor, enu, obs_itrs, obs_limit, R,
+ * zn_stride_sensor -- its `action` and `upd` are not read) are shared by all envs; each env tasks them on its own objects.  Per env the
+ * semantics are exactly ssa_env_step_sensors_f64's: an action < 0 or >= n_obj is an idle sensor; two sensors of ONE env on one object --
+ * the lowest-numbered one updates it; the same object index in two envs is two objects, both updated; a failed filter or a step the
+ * update_interval skips leaves a record with SSA_UPD_ACTION = -1.
+ *   rows   : env e's sensors task actions[e*SSA_MAX_SENSORS + s] (SSA_MAX_SENSORS words per row whatever S is: one aligned 32-byte read
+ *            per tile) or, with SSA_LAUNCH_INLINE_ENVS, inline_action[e][s] -- the time word is then ssa_step_params.inline_time[e],
+ *            else env_time[e].
+ *   records: sensor s of env e writes upd + (e*S + s)*SSA_UPD_STRIDE.
+ *   noise  : z_noise + e*zn_stride_env + s*zn_stride_sensor + i*zn_stride_time + a*zn_stride_obj, a = the sensor's action.
+ * Of ssa_step_params it reads what ssa_env_step_sensors_f64 reads, with the same meaning, and env_time[e] / inline_time[e] and
+ * zn_stride_env.  Several envs need whole tiles per env (n_obj % 4 == 0).  n_env == 1 is accepted for any n_obj and gives exactly
+ * what ssa_env_step_sensors_f64 gives for row 0.
+ * Refused before any launch, SSA_E_INVALID: every refusal of ssa_env_step_sensors_f64 but its n_env one, a NULL `envs`, NULL or
+ * misaligned `actions` without SSA_LAUNCH_INLINE_ENVS, SSA_LAUNCH_INLINE_ENVS with n_env > SSA_INLINE_ENVS, SSA_LAUNCH_INLINE_ACTION;
+ * SSA_E_UNSUPPORTED: n_env > 1 with n_obj % 4 != 0, SSA_LAUNCH_STATS_FROM_METRICS. */
+typedef struct ssa_sensor_envs_params {
+    const int32_t *actions;   /* [E][SSA_MAX_SENSORS] device words, base 32-byte aligned; not read (may be NULL) with SSA_LAUNCH_INLINE_ENVS */
+    double *upd;              /* [E][S][SSA_UPD_STRIDE] update records, or NULL */
+    int32_t inline_action[SSA_INLINE_ENVS][SSA_MAX_SENSORS];   /* with SSA_LAUNCH_INLINE_ENVS (n_env <= SSA_INLINE_ENVS) */
+} ssa_sensor_envs_params;
+int ssa_env_step_sensors_envs_f64(const ssa_consts *c, const ssa_step_params *p, const ssa_sensor_params *sites,
+                                  const ssa_sensor_envs_params *envs, void *stream);
 
 /* ---------------------------------------------------------------- the lookahead of a sensor network
  * ssa_lookahead_f64 for every sensor of ssa_sensor_params, in one launch (one env).  For sensor s and object j the outputs are what

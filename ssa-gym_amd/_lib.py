@@ -77,6 +77,10 @@ class ssa_rollout_sensors_params(C.Structure):
     _fields_ = [("actions", c_dp), ("upd_ring", c_dp)]
 
 
+class ssa_sensor_envs_params(C.Structure):
+    _fields_ = [("actions", c_dp), ("upd", c_dp), ("inline_action", (C.c_int32 * 8) * 8)]
+
+
 class ssa_forecast_params(C.Structure):
     _fields_ = [("n_steps", C.c_int32), ("reserved", C.c_int32), ("out", ssa_lookahead_out)]
 
@@ -131,6 +135,8 @@ SIGNATURES = {
     "ssa_env_closed_loop_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_closed_loop_params), c_dp]),
     "ssa_lookahead_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_lookahead_out), c_dp]),
     "ssa_env_step_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params), c_dp]),
+    "ssa_env_step_sensors_envs_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
+                                                C.POINTER(ssa_sensor_envs_params), c_dp]),
     "ssa_lookahead_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
                                             C.POINTER(ssa_lookahead_out), c_dp]),
     "ssa_forecast_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),

@@ -1017,6 +1017,7 @@ struct ActBase {
     static constexpr bool sensors = false;        // a sensor network: one update per sensor, each with its own site
     static constexpr bool look_sensors = false;   // the lookahead of a sensor network: `all`, one pass per sensor
     static constexpr bool forecast = false;       // ... as step h of a forecast: `look_sensors` on a resident tile
+    static constexpr bool envs = false;           // `sensors` in each of several envs: a row of actions per env (ActSensorEnvs)
     SSA_DEV int get() { return -1; }
     SSA_DEV void before_wait(Tiles&, int, int) {}
     SSA_DEV void mid_step(Tiles&, int) {}
@@ -1144,6 +1145,34 @@ struct ActSchedule : ActBase {
         return *(RowPtr)__builtin_assume_aligned(row, sizeof(row_t));
     }
     SSA_DEV int action(const ssa_sensor_params*, int k) const { return ((WordPtr)row)[k]; }   // (k not known at compile time: one word)
+    SSA_DEV double* records(const ssa_sensor_params*) const { return upd; }
+};
+// ActSensorEnvs (vector_sensors_kernel, ssa_env_step_sensors_envs_f64): ActSensors in each of E envs.  The sites are shared; an env has
+// its own row of SSA_MAX_SENSORS action words, its own block of S update records, its own time word and its own noise tables.  Several
+// envs come in whole tiles (n_obj % 4 == 0: the launcher), so a tile's env is wave-uniform -- enter() forms it once per tile, as a scalar --
+// and the env's row is what a schedule's row is to ActSchedule: one scalar load of eight words through the constant address space, from
+// device memory (`actions`, 32-byte aligned) or, with SSA_LAUNCH_INLINE_ENVS, from the kernel's own argument block (`inline_action`).
+// Three things of process_wave's `sensors` path take the env's value, each behind `envs`: the time word, the row that clears the idle
+// sensors' records (the env's first) with the records' base, and the caller's index of a row (its index within the env).
+SSA_DEV ConstPtr<int32_t> vector_sensors_inline_rows();   // (inline_action in the argument segment: defined behind VecSensK)
+struct ActSensorEnvs : ActBase {
+    static constexpr bool sensors = true, envs = true;
+    const ssa_sensor_params* s;
+    const ssa_sensor_envs_params* v;   // (in the kernel's argument block, as `s`)
+    int env;                           // the tile's env
+    ConstPtr<int32_t> row;             // ... its action words
+    double* upd;                       // ... its records, or null
+    SSA_DEV const ssa_sensor_params* sites() const { return s; }
+    SSA_DEV void enter(uint32_t mask, int n_env, int64_t n_obj, int64_t base)
+    {
+        env = (n_env > 1) ? __builtin_amdgcn_readfirstlane((int)((uint32_t)base / (uint32_t)n_obj)) : 0;
+        const ConstPtr<int32_t> rows = (mask & SSA_LAUNCH_INLINE_ENVS) ? vector_sensors_inline_rows() : (ConstPtr<int32_t>)v->actions;
+        row = rows + (int64_t)env * SSA_MAX_SENSORS;
+        upd = v->upd ? v->upd + (int64_t)env * s->n_sensor * SSA_UPD_STRIDE : nullptr;
+    }
+    typedef int row_t __attribute__((ext_vector_type(SSA_MAX_SENSORS)));
+    SSA_DEV row_t actions(const ssa_sensor_params*) const { return *(ConstPtr<row_t>)__builtin_assume_aligned(row, sizeof(row_t)); }
+    SSA_DEV int action(const ssa_sensor_params*, int k) const { return row[k]; }
     SSA_DEV double* records(const ssa_sensor_params*) const { return upd; }
 };
 // the sensor that updates the object the caller calls `jid`: the lowest-numbered one whose action it is, -1 for none
@@ -1275,6 +1304,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     constexpr bool SENS = ACT::sensors;   // a sensor network: one update per sensor, each with its own site (ActSensors)
     constexpr bool LSENS = ACT::look_sensors;   // the lookahead of a sensor network: ALL, one pass per sensor (ActLookSensors)
     constexpr bool FCAST = ACT::forecast;      // ... as step h of a forecast: LSENS on a resident tile (ActForecastSensors)
+    constexpr bool ENVS = ACT::envs;           // SENS in each of several envs, whole tiles per env (ActSensorEnvs)
     // (ActLookSensors, multi-tile instance: the next tile's loads leave once, behind the last pass -- except with SSA_PROP_ELEMENTS, whose
     // out-of-line call then spills 8 more VGPRs: there they are issued as in every other kernel, after the propagator and again at the end
     // of each pass's update)
@@ -1308,8 +1338,10 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         asm volatile("" : "+s"(hw.mask), "+s"(hw.env_time), "+s"(hw.obj_ids), "+s"(hw.n_env), "+s"(hw.time_offset), "+s"(hw.update_interval));
     }
 
+    if constexpr (ENVS) asrc.enter(hw.mask, hw.n_env, p.n_obj, base);   // (the tile's env, a scalar: its action row, records and time word)
     // env of the object: no division for the single-env case, a 32-bit one otherwise (n_env * n_obj < 2^31)
     int e = (valid && hw.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
+    if constexpr (ENVS) e = asrc.env;   // (whole tiles per env: no division per lane)
     const int64_t j = valid ? obj - (int64_t)e * p.n_obj : 0;
     // the action / time index of this object's env, fetched early (used after the transform)
     // (one env: wave-uniform loads -- scalar ones from the constant address space in the one-tile instances, see env_action; the
@@ -1324,13 +1356,14 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         // env 0's words and the tile's obj_ids: three scalar loads, issued together and waited for once (the asm statement needs all of them)
         const ConstPtr<int32_t> t_src = segment_word_src<true>(hw.mask, hw.env_time), a_src = segment_word_src<false>(hw.mask, hw.actions);
         int t0 = *t_src, a0 = -1;
+        if constexpr (ENVS) t0 = t_src[asrc.env];   // (the tile's env: still a scalar load)
         if (!ALL && !SENS) a0 = *a_src;
         if (hw.obj_ids) {
             const v4i w = *(ConstPtr<v4i>)(hw.obj_ids + base);
             id0 = w.x; id1 = w.y; id2 = w.z; id3 = w.w;
         }
         asm volatile("" : "+s"(t0), "+s"(a0), "+s"(id0), "+s"(id1), "+s"(id2), "+s"(id3));
-        if (hw.n_env > 1) {
+        if (!ENVS && hw.n_env > 1) {
             t0 = segment_lane_word(t_src, e);
             if (!ALL && !SENS) a0 = segment_lane_word(a_src, e);
         }
@@ -1341,7 +1374,8 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         tix = valid ? env_time_of<INL>(p, e) + p.time_offset : 0;
     } else if (SENS) {   // (one env; the sensors' actions are matched below, against the row's caller index)
         act = -1;
-        tix = valid ? env_time_of<INL>(p, 0) + p.time_offset : 0;
+        if constexpr (ENVS) tix = valid ? env_time_of<INL>(p, asrc.env) + p.time_offset : 0;
+        else tix = valid ? env_time_of<INL>(p, 0) + p.time_offset : 0;
     } else if (p.n_env > 1) {
         act = valid ? env_action<INL>(p, e) : -1;
         tix = valid ? env_time_of<INL>(p, e) + p.time_offset : 0;
@@ -1503,6 +1537,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // again where the rare paths below need it (a scalar load here would sit in front of every LDS wait that follows)
     obj = base + g;
     e = (valid && p.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
+    if constexpr (ENVS) e = asrc.env;
     // the next tile's inputs: in flight during the transform / covariance / observation / store of this one
     if (TILE == 1 && !ISSUE_LAST) tile_issue(pf, p, lane, next_base, next_cnt);
 
@@ -1584,7 +1619,8 @@ look_pass:
     bool look_vis = false, look_taken = false;   // (ActAll: the row's visibility and whether its update ran, for the outputs)
     // (ActSensors: the row's sensor matched again here rather than carried across the propagator)
     const ssa_sensor_params* SP = PASS_ARGS ? kernarg_opaque(asrc.sites()) : asrc.sites();
-    if constexpr (SENS) sid = valid ? sensor_index(asrc, SP, p.obj_ids ? (int64_t)t.Oid[g] : obj) : -1;
+    if constexpr (ENVS) sid = valid ? sensor_index(asrc, SP, p.obj_ids ? (int64_t)t.Oid[g] : obj - (int64_t)asrc.env * p.n_obj) : -1;
+    else if constexpr (SENS) sid = valid ? sensor_index(asrc, SP, p.obj_ids ? (int64_t)t.Oid[g] : obj) : -1;
     if (__any(my_update)) {   // whole-wave branch: a wavefront without a selected object skips the block, its variables included
     bool upd_go = false, taken = false, visible = false, attempted = false;
     double z[3] = {0.0, 0.0, 0.0}, y_row[3] = {0.0, 0.0, 0.0};   // (y_row: lane 13 of the row keeps the innovation)
@@ -1828,7 +1864,8 @@ look_pass:
     if (my_update && rec && l == 0) {
         rec[SSA_UPD_OBS_TAKEN] = taken ? 1.0 : 0.0;
         rec[SSA_UPD_VISIBLE] = visible ? 1.0 : 0.0;
-        if constexpr (SENS) rec[SSA_UPD_ACTION] = attempted ? (double)(p.obj_ids ? (int64_t)t.Oid[g] : obj) : -1.0;   // (the sensor's action IS this object)
+        if constexpr (ENVS) rec[SSA_UPD_ACTION] = attempted ? (double)(p.obj_ids ? (int64_t)t.Oid[g] : obj - (int64_t)asrc.env * p.n_obj) : -1.0;
+        else if constexpr (SENS) rec[SSA_UPD_ACTION] = attempted ? (double)(p.obj_ids ? (int64_t)t.Oid[g] : obj) : -1.0;   // (the sensor's action IS this object)
         else rec[SSA_UPD_ACTION] = attempted ? (double)(ACT::late ? act : env_action<INL, SEG>(p, e)) : -1.0;   // (my_update: the env's action IS this object)
     }
     if constexpr (ALL) {
@@ -1843,6 +1880,7 @@ look_pass:
     l = lane & 15;
     obj = base + g;
     e = (valid && p.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
+    if constexpr (ENVS) e = asrc.env;
     if (TILE == 1 && !ISSUE_LAST) tile_issue(pf, p, lane, next_base, next_cnt);
     }   // wavefronts holding a selected object
     // envs whose action selects nobody still get a cleared record (written by object 0's row)
@@ -1855,7 +1893,23 @@ look_pass:
         rec[SSA_UPD_ACTION] = -1.0;
       }
     }
-    if constexpr (SENS) {   // sensors that update nobody -- idle, out of range, a lower sensor's object, a step the interval skips: a cleared record
+    if constexpr (ENVS) {   // (ActSensorEnvs: the block below once per env -- by the first row of the tile's env, into that env's records.  Written
+                            // out a second time: the one-env kernels' instructions do not survive any rewording of their own block)
+        if (asrc.records(SP) && valid && obj == (int64_t)asrc.env * p.n_obj && l == 0) {
+            for (int k = 0; k < SP->n_sensor; ++k) {
+                const int a = asrc.action(SP, k);
+                bool owns = a >= 0 && (int64_t)a < p.n_obj && interval_ok;
+                for (int q = 0; q < k; ++q)
+                    if (asrc.action(SP, q) == a) owns = false;
+                if (!owns) {
+                    double* rec = asrc.records(SP) + (int64_t)k * SSA_UPD_STRIDE;
+                    rec[SSA_UPD_OBS_TAKEN] = 0.0;
+                    rec[SSA_UPD_VISIBLE] = 0.0;
+                    rec[SSA_UPD_ACTION] = -1.0;
+                }
+            }
+        }
+    } else if constexpr (SENS) {   // sensors that update nobody -- idle, out of range, a lower sensor's object, a step the interval skips: a cleared record
         if (asrc.records(SP) && valid && obj == 0 && l == 0) {
             for (int k = 0; k < SP->n_sensor; ++k) {
                 const int a = asrc.action(SP, k);
@@ -2185,15 +2239,27 @@ struct LookSensK {
     LookK k;
     ssa_sensor_params s;
 };
+struct VecSensK {   // ... and, behind SensK's, the envs' action rows and records (ssa_env_step_sensors_envs_f64)
+    StepK k;
+    ssa_sensor_params s;
+    ssa_sensor_envs_params v;
+};
 // what a block hands process_wave: the step's constants and parameters, and the ACT policy (its pointers into the block)
 SSA_DEV const StepK& step_of(const StepK& k) { return k; }
 SSA_DEV const StepK& step_of(const LookK& k) { return k.k; }
 SSA_DEV const StepK& step_of(const SensK& k) { return k.k; }
 SSA_DEV const StepK& step_of(const LookSensK& k) { return k.k.k; }
+SSA_DEV ConstPtr<int32_t> vector_sensors_inline_rows()   // (by the segment's address, as tile_kernel_params: rows indexed by the tile's env)
+{
+    return (ConstPtr<int32_t>)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(TileArgs<VecSensK>, k) + offsetof(VecSensK, v) +
+                               offsetof(ssa_sensor_envs_params, inline_action));
+}
+SSA_DEV const StepK& step_of(const VecSensK& k) { return k.k; }
 SSA_DEV ActEarly act_of(const StepK&) { return ActEarly(); }   // (the leading {} below: ActBase, which has no members)
 SSA_DEV ActAll act_of(const LookK& k) { return ActAll{{}, &k.o}; }
 SSA_DEV ActSensors act_of(const SensK& k) { return ActSensors{{}, &k.s}; }
 SSA_DEV ActLookSensors act_of(const LookSensK& k) { return ActLookSensors{{}, &k.k.o, &k.s}; }
+SSA_DEV ActSensorEnvs act_of(const VecSensK& k) { return ActSensorEnvs{{}, &k.s, &k.v, 0, nullptr, nullptr}; }   // (process_wave enters the tile's env)
 // WALK: what sets the four kernels apart
 enum : unsigned {
     WALK_STEP = 1,          // a step: the deferred fold of the previous step's statistics in the extra wavefronts (unit >= nwork, one
@@ -2281,6 +2347,7 @@ SSA_TILE_KERNEL(step_fast_kernel, StepK, WALK_STEP | WALK_BASE_PER_TILE)        
 SSA_TILE_KERNEL(lookahead_kernel, LookK, 0)                                                // the lookahead (ssa_lookahead_f64)
 SSA_TILE_KERNEL(lookahead_sensors_kernel, LookSensK, WALK_ONE_ENV | WALK_ACT_SEGMENT)      // a sensor network's lookahead
 SSA_TILE_KERNEL(step_sensors_kernel, SensK, WALK_STEP | WALK_ONE_ENV)                      // a sensor network's step
+SSA_TILE_KERNEL(vector_sensors_kernel, VecSensK, WALK_STEP)                                // ... in each of several envs
 #undef SSA_TILE_KERNEL
 
 // Rollout: K consecutive env steps of the same objects in ONE launch.  An object's trajectory depends on no other
@@ -3980,8 +4047,9 @@ static ssa_sensor_params idle_sites(const ssa_sensor_params* sp)
 }
 
 // sens: a sensor network's step (ssa_env_step_sensors_f64; checked by the caller) -- step_sensors_kernel instead of step_fast_kernel
+// envs: ... in each of n_env envs (ssa_env_step_sensors_envs_f64; checked by the caller) -- vector_sensors_kernel
 static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stream, hipEvent_t ev0, hipEvent_t ev1,
-                       const ssa_sensor_params* sens = nullptr)
+                       const ssa_sensor_params* sens = nullptr, const ssa_sensor_envs_params* envs = nullptr)
 {
     if (!c || !p || p->n_obj <= 0 || p->n_env <= 0) return SSA_E_INVALID;
     if (!p->x_true_in || !p->x_true_out || !p->x_in || !p->x_out || !p->P_in || !p->P_out || !p->status ||
@@ -4026,7 +4094,17 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     hipStream_t s = (hipStream_t)stream;
     const unsigned mask = (p->launch_mask & 7u) ? (p->launch_mask & 7u) : 7u;   // diagnostic: time one launch alone
     const int prop = c->propagator;
-    if ((mask & 1u) && sens) {
+    if ((mask & 1u) && envs) {
+        VecSensK kv;
+        kv.k = k;
+        kv.k.p.upd = nullptr;
+        kv.k.p.actions = nullptr;
+        kv.s = idle_sites(sens);
+        kv.v = *envs;
+        with_prop(prop, g.per_wave != 1, [&](auto P, auto M) {
+            hipExtLaunchKernelGGL((vector_sensors_kernel<P, M>), grid, block, 0, s, ev0, ev1, 0, g.arg, g.nwork, p->P_in, p->x_in, p->x_true_in, p->status, kv);
+        });
+    } else if ((mask & 1u) && sens) {
         SensK ks;
         ks.k = k;
         ks.k.p.upd = nullptr;
@@ -4080,6 +4158,22 @@ int ssa_env_step_sensors_f64(const ssa_consts* c, const ssa_step_params* p, cons
     if (rc != SSA_OK) return rc;
     if (!noise_stride_ok(sp)) return SSA_E_INVALID;
     return step_launch(c, p, stream, nullptr, nullptr, sp);
+}
+int ssa_env_step_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp,
+                                  const ssa_sensor_envs_params* envs, void* stream)
+{
+    if (!c || !p || !sp || !envs) return SSA_E_INVALID;
+    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
+    for (int k = 0; k < sp->n_sensor; ++k)
+        if (!(sp->obs_limit[k] == sp->obs_limit[k])) return SSA_E_INVALID;
+    if (!noise_stride_ok(sp)) return SSA_E_INVALID;
+    if (p->launch_mask & SSA_LAUNCH_INLINE_ACTION) return SSA_E_INVALID;
+    if (p->launch_mask & SSA_LAUNCH_INLINE_ENVS) {
+        if (p->n_env > SSA_INLINE_ENVS) return SSA_E_INVALID;
+    } else if (!envs->actions || ((uintptr_t)envs->actions & 31u)) return SSA_E_INVALID;
+    if (p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // whole tiles per env: a tile's env is wave-uniform
+    if (p->launch_mask & SSA_LAUNCH_STATS_FROM_METRICS) return SSA_E_UNSUPPORTED;
+    return step_launch(c, p, stream, nullptr, nullptr, sp, envs);
 }
 // dispatch-timestamp event pairs, created on first use (a ring, so that back-to-back launches can be timed
 // without draining the queue after each of them)

@@ -113,6 +113,7 @@ class HotPathEngine:
         self._fore = None                               # ... and of launch_forecast_sensors
         self._assign_ws = None                          # (S, workspace) of launch_assign_sensors
         self._assign_row = None                         # assign_row()'s
+        self._sensor_envs = None                        # launch_step_sensors_envs: its block, the [E][8] action table and its staging
         self._pcache = {}
         self._cref = C.byref(self.consts)
         self._pref = C.byref(self._p)
@@ -318,7 +319,7 @@ class HotPathEngine:
 
     def launch_step(self, slot_in, slot_out, time_offset, actions_ptr=None, stream=None, aer_out=0, stats_out=0, upd_out=0,
                     fast_stats=False, defer_fold=False, profile_slot=None, shards_out=0, shards_clear=0, aer_cols=4, action=None,
-                    obs_mirror=0, fold_inside=False, env_words=None, argmax_spos=False, mirror_f32=False, sensors=None):
+                    obs_mirror=0, fold_inside=False, env_words=None, argmax_spos=False, mirror_f32=False, sensors=None, sensor_envs=None):
         """enqueue the step; asynchronous, no host sync.  fast_stats: statistics by the step kernel's atomics (two
         launches, no arg-max of sigma_pos).  defer_fold (with fast_stats): ONE launch -- this step's
         statistics are folded by extra wavefronts of the NEXT deferred step, or by flush_stats().  action (one env): the
@@ -328,7 +329,9 @@ class HotPathEngine:
         argmax_spos (with fast_stats): np.argmax / np.max of sigma_pos in the step's statistics on the one-launch paths as well
         (ssa_step_params.spos_tiles; the 'shaped' reward) -- needs self.supports_argmax.
         sensors: an ssa_sensor_params block (host.make_sensor_params, actions and record destination set): the step of a sensor network
-        (ssa_env_step_sensors_f64; see launch_step_sensors) -- `action` / actions_ptr / upd_out are then not used."""
+        (ssa_env_step_sensors_f64; see launch_step_sensors) -- `action` / actions_ptr / upd_out are then not used.
+        sensor_envs (with sensors): an ssa_sensor_envs_params block, the network in each of the engine's envs
+        (ssa_env_step_sensors_envs_f64; see launch_step_sensors_envs)."""
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
         if shards_out:
             fast_stats, defer_fold = True, False
@@ -369,21 +372,28 @@ class HotPathEngine:
         if sensors is not None:
             if profile_slot is not None:
                 raise _lib.SsaHipError("profile_slot: the step of a sensor network is not profiled by event pairs")
-            rc = self._lib.ssa_env_step_sensors_f64(self._cref, pref, C.byref(sensors), s)
+            if sensor_envs is not None:
+                rc = self._lib.ssa_env_step_sensors_envs_f64(self._cref, pref, C.byref(sensors), C.byref(sensor_envs), s)
+            else:
+                rc = self._lib.ssa_env_step_sensors_f64(self._cref, pref, C.byref(sensors), s)
         elif profile_slot is None:
             rc = self._lib.ssa_env_step_f64(self._cref, pref, s)
         else:   # the dominant launch bracketed by event pair `profile_slot` (read back with profile_ms)
             rc = self._lib.ssa_env_step_profiled_f64(self._cref, pref, s, int(profile_slot))
         if rc:
-            raise _lib.SsaHipError("%s failed with code %d" % ("ssa_env_step_sensors_f64" if sensors is not None else "ssa_env_step_f64", rc))
+            raise _lib.SsaHipError("%s failed with code %d" % ("ssa_env_step_sensors_envs_f64" if sensor_envs is not None else
+                                                               "ssa_env_step_sensors_f64" if sensors is not None else "ssa_env_step_f64", rc))
         if defer:
             self._fold_pending = (self._shard_cur, stats_ptr, argmax, metrics_ptr if from_metrics else 0)
             self._shard_cur ^= 1
 
-    def _check_sensor_noise(self, sensors):
-        """the extent of z_noise that the sensors of `sensors` index: sensor s reads z_noise[s * sensors.zn_stride_sensor ...]"""
+    def _check_sensor_noise(self, sensors, envs=False):
+        """the extent of z_noise that the sensors of `sensors` index: sensor s reads z_noise[s * sensors.zn_stride_sensor ...]; envs: in
+        every env of the engine, env e's tables zn_stride_env behind env e - 1's"""
         S = int(sensors.n_sensor)
         need = (S - 1) * int(sensors.zn_stride_sensor) + (self.n_time - 1) * self.zn_stride_time + (self.m - 1) * int(self._p.zn_stride_obj) + 3
+        if envs:
+            need += (self.E - 1) * self.zn_stride_env
         if self.z_noise.numel() < need:
             raise _lib.SsaHipError("z_noise: %d values needed for %d sensors, got %d" % (need, S, self.z_noise.numel()))
 
@@ -403,6 +413,48 @@ class HotPathEngine:
             sensors.action[k] = int(actions[k])
         sensors.upd = int(upd_out)
         self.launch_step(slot_in, slot_out, time_offset, stream=stream, sensors=sensors, **kw)
+
+    def launch_step_sensors_envs(self, slot_in, slot_out, time_offset, sensors, actions, upd_out=0, stream=None, env_words=None, **kw):
+        """enqueue the step of a sensor network in EVERY env of the engine, one launch (include/ssa_hip.h: ssa_env_step_sensors_envs_f64):
+        per env what launch_step_sensors does for one.  `sensors`: host.make_sensor_params(), the sites all envs share (its action words
+        and record pointer are not read); `actions` [E][S]: sensor s of env e observes object actions[e][s] of that env (< 0 or >= n_obj:
+        idle; two sensors of one env on one object: the lower one updates it), with the noise table z_noise[e * zn_stride_env +
+        s * sensors.zn_stride_sensor ...]; the update records go to `upd_out` (a pointer to [E][S][UPD_STRIDE] doubles, may be 0).
+        env_words: the envs' time words (E <= 8) -- rows and times then travel by value in the launch's argument block
+        (SSA_LAUNCH_INLINE_ENVS); otherwise the rows travel through this engine's [E][8] int32 device table (a blocking copy in the
+        current stream, which a launch still running from that table must not share a race with: synchronise between such launches, as
+        the vector env does) and the times are the engine's env_time0 words.  Several envs need n_obj % 4 == 0.  Every other keyword as launch_step.
+        Asynchronous, no host sync."""
+        S, W = int(sensors.n_sensor), _lib.MAX_SENSORS
+        a = np.asarray(actions, dtype=np.int64)
+        if a.shape != (self.E, S):
+            raise _lib.SsaHipError("launch_step_sensors_envs: actions must be [%d][%d] (envs x sensors), got %s" % (self.E, S, a.shape))
+        if self.E > 1 and self.m % 4:
+            raise _lib.SsaHipError("a sensor network in several envs needs n_obj % 4 == 0 (whole tiles per env)")
+        self._check_sensor_noise(sensors, envs=True)
+        if self._sensor_envs is None:
+            self._sensor_envs = (_lib.ssa_sensor_envs_params(), torch.full((self.E, W), -1, dtype=torch.int32, device=self.dev),
+                                 np.full((self.E, W), -1, dtype=np.int32))
+        v, table, rows_np = self._sensor_envs
+        v.upd = int(upd_out)
+        a = np.clip(a, -1, 2 ** 31 - 1)      # (an int32 word; anything < 0 is idle, anything >= n_obj too)
+        if env_words is not None:
+            if self.E > _lib.INLINE_ENVS:
+                raise _lib.SsaHipError("env_words: at most %d envs travel in the parameter block" % _lib.INLINE_ENVS)
+            v.actions = 0
+            rows = a.tolist()
+            for e in range(self.E):
+                v.inline_action[e][:S] = rows[e]
+            words = ([int(t) for t in env_words], [-1] * self.E)
+        else:
+            # (a blocking copy from ordinary host memory, E x 32 bytes: it has left the host array when it returns, so the next call may
+            # rewrite it, and it is in the table before anything is enqueued here, whatever stream the launch goes to.  The table itself is
+            # the caller's to keep intact until the launch has run -- as the engine's action words are)
+            rows_np[:, :S] = a
+            table.copy_(torch.from_numpy(rows_np))
+            v.actions = table.data_ptr()
+            words = None
+        self.launch_step(slot_in, slot_out, time_offset, stream=stream, sensors=sensors, sensor_envs=v, env_words=words, **kw)
 
     LOOKAHEAD_PARTS = ("x_prior", "P_prior", "P_post")
 

@@ -8,6 +8,10 @@ while the others continue (the usual vector-env auto-reset).  Semantics per env 
 SSA_Tasker_Env (same reward / done logic, same RNG draw order for reset, seed = base seed + env index);
 measurement noise is drawn on the device per (env, time step) -- only the object the action selects
 consumes noise in a step (ssa_tasker_simple_2.py:301).
+
+A sensor network (config['observers'] with S > 1 sites, EXTENSION): every env tasks the same S sites, each sensor to its own object;
+`step(actions)` takes [E, S] and is still ONE launch (ssa_env_step_sensors_envs_f64).  Noise is then drawn per
+(env, sensor, time step).
 """
 import numpy as np
 
@@ -16,16 +20,39 @@ from ._config import draw_initial_state, resolve_config, reward_done
 from ._gymshim import np_random, spaces
 
 
+def check_sensor_actions(actions, E, S, m):
+    """the [E, S] action table of a vector step of a sensor network, checked as SSA_Tasker_Env.step checks one env's row -- every entry
+    an object in 0 .. m-1 (AssertionError), no two sensors of ONE env on one object (ValueError; the same index in two envs is two
+    objects) -- and returned as int64.  Needs no device state."""
+    a = np.asarray(actions)
+    if a.shape != (E, S) or a.dtype.kind not in "iu" or not (np.all(a >= 0) and np.all(a < m)):
+        raise AssertionError("%r (%s) invalid: one object in 0 .. %d per sensor (%d envs x %d sensors)" % (actions, type(actions), m - 1, E, S))
+    a = a.astype(np.int64)
+    for e in range(E):
+        if len(np.unique(a[e])) != S:
+            raise ValueError("step: two sensors tasked to the same object (%s) in env %d" % (a[e], e))
+    return a
+
+
+def shaped_hit(actions, argmax_prev):
+    """per env: did its action -- with a sensor network ANY of its sensors' ([E, S]) -- task np.argmax(sigma_pos[i - 1])?  (the 'shaped'
+    reward's +1/n, as SSA_Tasker_Env._reward_done)"""
+    a = np.asarray(actions)
+    prev = np.asarray(argmax_prev)
+    return (a == prev) if a.ndim == 1 else np.any(a == prev[:, None], axis=1)
+
+
 class SSA_Tasker_VecEnv:
     def __init__(self, config, num_envs, seed=0):
         import torch
         from .. import engine
         from ._obspool import HostObs
         c = resolve_config(config)          # (as SSA_Tasker_Env: the same values, constants and options from the same config)
-        if c.n_sensor > 1:
-            raise NotImplementedError("SSA_Tasker_VecEnv: not implemented for a sensor network (config['observers'] with %d sensors); "
-                                      "use SSA_Tasker_Env" % c.n_sensor)
         self.E, self.m, self.n, self.dt = int(num_envs), c.m, c.n, c.dt
+        # (a sensor network, S > 1 sites: sensor 0 is the primary sensor, the env's observer; one site takes the plain path, as SSA_Tasker_Env)
+        self.n_sensor = S = c.n_sensor
+        if S > 1 and self.E > 1 and self.m % 4:
+            raise ValueError("a sensor network in several envs needs rso_count % 4 == 0 (whole tiles per env), got " + str(self.m))
         self._bulk_draws = bool(config.get('device_rng', False))
         self.obs_returned, self.reward_type = config['obs_returned'], config['reward_type']
         self.orbits = config['orbits']
@@ -33,11 +60,16 @@ class SSA_Tasker_VecEnv:
         self._consts = c.consts
         self._gen = torch.Generator(device="cuda").manual_seed(int(seed))
         self._zs = torch.as_tensor(self.z_sigma, dtype=torch.float64, device="cuda")
-        z = torch.randn((self.E, self.n, 1, 3), dtype=torch.float64, device="cuda", generator=self._gen) * self._zs
+        if S > 1:      # (noise per (env, sensor, time step): [E, S, n, 1, 3], sensor s scaled by its own z_sigma)
+            from .. import host
+            self._zs = torch.as_tensor(c.net.z_sigma, dtype=torch.float64, device="cuda").view(S, 1, 1, 3)
+            self._sensors = host.make_sensor_params(c.net.lla, c.net.obs_limit, c.net.R, self.n * 3)
+        self._z_shape = (S, self.n, 1, 3) if S > 1 else (self.n, 1, 3)
+        z = torch.randn((self.E,) + self._z_shape, dtype=torch.float64, device="cuda", generator=self._gen) * self._zs
         self._eng = engine.HotPathEngine(self._consts, self.m, self.E, c.trans, z, history=2,
-                                         zn_stride_env=self.n * 3, zn_stride_time=3, zn_stride_obj=0)
+                                         zn_stride_env=S * self.n * 3, zn_stride_time=3, zn_stride_obj=0)
         self._rng = [np_random(seed + e)[0] for e in range(self.E)]
-        self.single_action_space = spaces.Discrete(self.m)
+        self.single_action_space = spaces.MultiDiscrete([self.m] * S) if S > 1 else spaces.Discrete(self.m)
         self.single_observation_space = c.obs_space
         self.num_envs = self.E
         self._aer = torch.zeros((self.E * self.m, 4), dtype=torch.float64, device="cuda")
@@ -92,7 +124,7 @@ class SSA_Tasker_VecEnv:
             from ..catalogue import regime_order_env
             self._eng.set_env_layout(e, regime_order_env(xt, e, self.E))
         self._eng.load_env_state(slot, e, xt, xf, self.P_0)
-        self._eng.z_noise[e].copy_(torch.randn((self.n, 1, 3), dtype=torch.float64, device="cuda", generator=self._gen) * self._zs)
+        self._eng.z_noise[e].copy_(torch.randn(self._z_shape, dtype=torch.float64, device="cuda", generator=self._gen) * self._zs)
         self.i[e] = 0
         self.rewards_sum[e] = 0.0
 
@@ -150,8 +182,12 @@ class SSA_Tasker_VecEnv:
 
     def step(self, actions):
         import torch
-        actions = np.asarray(actions, dtype=np.int64).reshape(self.E)
-        assert 0 <= int(actions.min()) and int(actions.max()) < self.m, "invalid action"
+        S = self.n_sensor
+        if S > 1:
+            actions = check_sensor_actions(actions, self.E, S, self.m)
+        else:
+            actions = np.asarray(actions, dtype=np.int64).reshape(self.E)
+            assert 0 <= int(actions.min()) and int(actions.max()) < self.m, "invalid action"
         e = self._eng
         argmax_prev = self._argmax_prev
         self.i += 1
@@ -167,7 +203,18 @@ class SSA_Tasker_VecEnv:
         else:
             dst = self._obs_host.dest(self.tick)
             aer_out, mirror = (dst, 0) if aer else (0, dst)
-        if self._inline:
+        if S > 1:      # (a sensor network: the same single launch, a row of S actions per env; the update records stay on the device side)
+            kw = dict(aer_out=aer_out, obs_mirror=mirror, stats_out=self._stats_host.data_ptr(), fast_stats=fast, fold_inside=True,
+                      argmax_spos=shaped and fast, mirror_f32=self._mirror_f32 and fast)
+            if self._inline:
+                cur = self._stream
+                e.launch_step_sensors_envs(sin, sout, 0, self._sensors, actions, stream=cur.cuda_stream, env_words=self.i.tolist(), **kw)
+            else:
+                self._time_np[:] = self.i
+                e.time_actions.copy_(self._ta_host, non_blocking=True)
+                cur = torch.cuda.current_stream()
+                e.launch_step_sensors_envs(sin, sout, 0, self._sensors, actions, stream=cur.cuda_stream, **kw)
+        elif self._inline:
             cur = self._stream
             e.launch_step(sin, sout, 0, aer_out=aer_out, obs_mirror=mirror, stats_out=self._stats_host.data_ptr(), stream=cur.cuda_stream,
                           fast_stats=fast, fold_inside=True, env_words=(self.i.tolist(), actions.tolist()), argmax_spos=shaped and fast,
@@ -183,7 +230,7 @@ class SSA_Tasker_VecEnv:
         st = self._stats_np            # (host-mapped: the step kernel's folds wrote it; stable until the next launch)
         if shaped:
             self._argmax_prev = st[:, _lib.STAT_ARGMAX_SPOS].astype(np.int64)
-        hit = (actions == argmax_prev) if shaped else False
+        hit = shaped_hit(actions, argmax_prev) if shaped else False
         rewards, dones = reward_done(self.reward_type, st, hit, self.rewards_sum, self.i + 1 >= self.n, self.m, self.n)
         self.rewards_sum += rewards
         obs = self._obs(sout) if self._obs_device else self._obs_host.hand_out()
@@ -205,6 +252,9 @@ class SSA_Tasker_VecEnv:
         order.  Nothing of the envs changes; the next call overwrites the tensors."""
         import torch
         from .. import engine as _engine
+        if self.n_sensor > 1:
+            raise NotImplementedError("lookahead: not implemented for a sensor network in a vector env (config['observers'] with %d "
+                                      "sensors); use SSA_Tasker_Env.lookahead_sensors" % self.n_sensor)
         if np.any(self.i + 1 >= self.n):
             raise ValueError("lookahead: an env has no next step")
         e = self._eng
