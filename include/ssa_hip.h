@@ -592,6 +592,19 @@ int ssa_env_step_sensors_envs_f64(const ssa_consts *c, const ssa_step_params *p,
  * (SSA_E_INVALID); n_env != 1 (SSA_E_UNSUPPORTED); and every refusal of ssa_lookahead_f64. */
 int ssa_lookahead_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_sensor_params *s_host,
                               const ssa_lookahead_out *out, void *stream);
+/* ... in each of E envs, one launch: ssa_lookahead_sensors_f64 for every env of a vector launch.  The sites are shared by all envs; env
+ * e's time word is env_time[e] or, with SSA_LAUNCH_INLINE_ENVS (n_env <= SSA_INLINE_ENVS), inline_time[e], as ssa_lookahead_f64 reads
+ * them.  Per env the semantics are exactly ssa_lookahead_sensors_f64's.  Output rows, with E = n_env, m = n_obj, S = n_sensor and each
+ * env's own object numbering (obj_ids honoured per env):
+ *   score [E*S*m][SSA_LOOK_NSCORE], status [E*S*m], visible [E*S*m], P_post [E*S*m][36] (or NULL): row (e*S + s)*m + j;
+ *   x_prior [E*m][6], P_prior [E*m][36] (or NULL): row e*m + j
+ * -- env e's slab of every block is byte for byte what ssa_lookahead_sensors_f64 writes for that env alone, and what
+ * ssa_assign_sensors_envs_f64 / ssa_assign_sensors_f64 take.  Nothing is written but `out`.
+ * Refused before any launch: every refusal of ssa_lookahead_sensors_f64 but its n_env one; n_env * n_sensor * n_obj >= 2^31
+ * (SSA_E_INVALID); several envs with n_obj % 4 != 0 (SSA_E_UNSUPPORTED: whole tiles per env, the rule of
+ * ssa_env_step_sensors_envs_f64).  n_env == 1 is accepted for any n_obj and gives exactly what ssa_lookahead_sensors_f64 gives. */
+int ssa_lookahead_sensors_envs_f64(const ssa_consts *c, const ssa_step_params *p, const ssa_sensor_params *sites,
+                                   const ssa_lookahead_out *out, void *stream);
 
 /* ---------------------------------------------------------------- the rollout of a sensor network: a K-step tasking schedule in one launch
  * The K launches ssa_env_step_sensors_f64 would make for the rows 0 .. K-1 of `actions`, starting from history slot slot_out - 1, with
@@ -663,6 +676,25 @@ int ssa_forecast_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_
 int ssa_assign_sensors_f64(const double *score, int64_t n_obj, int32_t n_sensor, int32_t column, const int32_t *fallback,
                            int32_t *action_out, int64_t *pick_out, void *workspace, int64_t workspace_bytes, void *stream);
 int64_t ssa_assign_sensors_workspace_bytes(int64_t n_obj, int32_t n_sensor);
+/* ... of every env of a vector launch, one launch, written into the [E][SSA_MAX_SENSORS] action table ssa_env_step_sensors_envs_f64
+ * reads (ssa_sensor_envs_params.actions).  Env e's row and picks are exactly what ssa_assign_sensors_f64 writes for env e's slab of
+ * `score`, env e's fallback row and a workspace of its own: the same order, tie rule, NaN rule, fallback rule and -1 beyond S.  The same
+ * object index may be assigned in two envs: they are two objects.
+ *   score     : [E][S][m][SSA_LOOK_NSCORE], as ssa_lookahead_sensors_envs_f64 leaves it
+ *   fallback  : NULL, or [E][SSA_MAX_SENSORS] device words
+ *   action_out: [E][SSA_MAX_SENSORS] device words, the base 32-byte aligned
+ *   pick_out  : NULL, or [E][SSA_MAX_SENSORS][2]
+ *   workspace : ssa_assign_sensors_envs_workspace_bytes(n_obj, n_sensor, n_env) bytes of device memory, 64-byte aligned, zeroed ONCE by
+ *               the caller: n_env parts, each the one-env workspace rounded up to 64 bytes, with a ticket word of its own that its
+ *               env's last arrival leaves at zero; one call at a time per workspace.
+ * One launch of ceil(n_obj / 512) x n_env workgroups; the last workgroup to arrive FOR ITS ENV merges and assigns that env.
+ * Refused before any launch (SSA_E_INVALID): the refusals of ssa_assign_sensors_f64, n_env < 1 (or > 65535: the grid's second
+ * dimension), n_env * n_sensor * n_obj >= 2^31, a workspace that is NULL, not 64-byte aligned or smaller than the query.
+ * ssa_assign_sensors_envs_workspace_bytes returns SSA_E_INVALID for n_obj / n_sensor / n_env out of range. */
+int ssa_assign_sensors_envs_f64(const double *score, int64_t n_obj, int32_t n_sensor, int32_t n_env, int32_t column,
+                                const int32_t *fallback, int32_t *action_out, int64_t *pick_out,
+                                void *workspace, int64_t workspace_bytes, void *stream);
+int64_t ssa_assign_sensors_envs_workspace_bytes(int64_t n_obj, int32_t n_sensor, int32_t n_env);
 
 /* ---------------------------------------------------------------- visibility screen of a synthetic orbit catalogue
  * catalogue._accepted (orbit_gen.py's acceptance rule) for n candidate element sets, the observer generalised to a network of

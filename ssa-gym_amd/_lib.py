@@ -139,6 +139,8 @@ SIGNATURES = {
                                                 C.POINTER(ssa_sensor_envs_params), c_dp]),
     "ssa_lookahead_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
                                             C.POINTER(ssa_lookahead_out), c_dp]),
+    "ssa_lookahead_sensors_envs_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
+                                                 C.POINTER(ssa_lookahead_out), c_dp]),
     "ssa_forecast_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
                                            C.POINTER(ssa_forecast_params), c_dp]),
     "ssa_env_rollout_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_rollout_params),
@@ -165,6 +167,8 @@ SIGNATURES = {
     "ssa_masked_argmax_workspace_bytes": (C.c_int64, [C.c_int64]),
     "ssa_assign_sensors_f64": (C.c_int, [c_dp, C.c_int64, C.c_int32, C.c_int32, c_dp, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_assign_sensors_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "ssa_assign_sensors_envs_f64": (C.c_int, [c_dp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
+    "ssa_assign_sensors_envs_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "ssa_peer_push_f64": (C.c_int, [c_dp, C.c_int64, c_dp, c_dp, C.c_int32, c_dp, C.c_uint64, c_dp, C.c_int64, c_dp, c_dp, c_dp]),
     "ssa_peer_wait": (C.c_int, [c_dp, C.c_int32, c_dp, C.c_uint64, C.c_int64, c_dp, c_dp]),
     "ssa_aer_obs_f64": (C.c_int, [c_dp, c_dp, c_dp, C.POINTER(ssa_consts), c_dp, C.c_int64, c_dp]),

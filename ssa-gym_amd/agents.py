@@ -11,7 +11,11 @@ either factorisation fails, not only where the ratio of determinants is <= 0.  A
 therefore gets no score here but a finite one in the reference; in a filter's own covariances this happens late in an episode
 (1-3 objects per step of the seed-7 test episode from step 300 on), on matrices whose negative eigenvalue is at rounding level
 (at most 3e-16 of the largest, diagonal entries 1e18 .. 1e21), where the reference's score is set by rounding, not by the
-filter.  On those steps the two agents may pick different objects."""
+filter.  On those steps the two agents may pick different objects.
+
+The lookahead agents of a sensor network (agent_info_gain_sensors, agent_trace_gain_sensors) also take a vector env
+(SSA_Tasker_VecEnv) and then return [E, S]: one lookahead launch and one assignment launch for all envs and one read-back of
+E x 32 bytes; vec.step_agent(agent) is the vector step that takes their rows without the host in between."""
 import numpy as np
 
 from . import _lib
@@ -105,16 +109,33 @@ def agent_trace_gain(obs, env):                 # argmax tr P- - tr P+ over the 
 # and so on: ONE launch for all the rounds (ssa_assign_sensors_f64) and one 32-byte read-back.  A sensor left
 # without a finite score gets an object nobody has, drawn from the action space's generator as _pick's fallback (env.np_random, the
 # env's noise stream, is not touched).  env.run_agent_sensors runs the same agents without the host in the loop.
+# On a vector env (SSA_Tasker_VecEnv) the same two agents return [E, S]: ONE lookahead launch and ONE assignment
+# launch for all envs (ssa_lookahead_sensors_envs_f64, ssa_assign_sensors_envs_f64) and one read-back of E x 32 bytes; a sensor left
+# without an object draws by the same rule from single_action_space, envs in ascending order (the envs' own generators are not touched).
+# vec.step_agent(agent) is the step that takes the rows without the host in between.
 def _draw_unassigned(env, taken):
     if len(taken) >= env.m:
         raise ValueError("%d sensors but %d objects: no object left to assign" % (len(taken) + 1, env.m))
+    space = env.single_action_space if hasattr(env, "single_action_space") else env.action_space
     while True:
-        for j in np.atleast_1d(env.action_space.sample()):
+        for j in np.atleast_1d(space.sample()):
             if int(j) not in taken:
                 return int(j)
 
 
+def _assign_lookahead_sensors_envs(vec, k):
+    acts = vec.assign_sensors(k)                            # int64 [E, S], -1 where the scores leave a sensor without an object
+    for act in acts:                                        # (envs ascending, sensors ascending)
+        taken = set(act[act >= 0].tolist())
+        for s in np.flatnonzero(act < 0):
+            act[s] = _draw_unassigned(vec, taken)
+            taken.add(int(act[s]))
+    return acts
+
+
 def _assign_lookahead_sensors(env, k):
+    if hasattr(env, "num_envs"):                           # (a vector env: every env's row)
+        return _assign_lookahead_sensors_envs(env, k)
     score = env.lookahead_sensors()["score"]               # [S, 3, m]: a view of the engine's [S][m][3] rows
     S = score.shape[0]
     row = env._engine.assign_row()

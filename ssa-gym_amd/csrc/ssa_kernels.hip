@@ -1018,6 +1018,7 @@ struct ActBase {
     static constexpr bool look_sensors = false;   // the lookahead of a sensor network: `all`, one pass per sensor
     static constexpr bool forecast = false;       // ... as step h of a forecast: `look_sensors` on a resident tile
     static constexpr bool envs = false;           // `sensors` in each of several envs: a row of actions per env (ActSensorEnvs)
+    static constexpr bool look_envs = false;      // `look_sensors` in each of several envs (ActLookSensorEnvs)
     SSA_DEV int get() { return -1; }
     SSA_DEV void before_wait(Tiles&, int, int) {}
     SSA_DEV void mid_step(Tiles&, int) {}
@@ -1219,6 +1220,33 @@ struct ActForecastSensors : ActBase {
         if (os.P_prior) os.P_prior += rp * 36;
     }
 };
+// ActLookSensorEnvs (lookahead_sensor_envs_kernel, ssa_lookahead_sensors_envs_f64): ActLookSensors in each of E envs, as ActSensorEnvs
+// is ActSensors in each of them.  The sites are shared; several envs come in whole tiles (n_obj % 4 == 0: the launcher), so a tile's env
+// is wave-uniform -- enter() forms it once per tile, as a scalar -- and its time word is a scalar load indexed by it.  Two things of
+// process_wave's `look_sensors` path take the env's value, each behind `look_envs`: the time word, and in every pass the env's slab of
+// the blocks `o` names (slab()) with the caller's index of a row (its index within the env).
+struct ActLookSensorEnvs : ActBase {
+    static constexpr bool all = true, look_sensors = true, look_envs = true;
+    const ssa_lookahead_out* o;
+    const ssa_sensor_params* s;
+    int env;                           // the tile's env
+    SSA_DEV const ssa_sensor_params* sites() const { return s; }
+    SSA_DEV void enter(int n_env, int64_t n_obj, int64_t base)
+    {
+        env = (n_env > 1) ? __builtin_amdgcn_readfirstlane((int)((uint32_t)base / (uint32_t)n_obj)) : 0;
+    }
+    // the env's output block: [E][S * m] rows per sensor output, [E][m] rows of the prior
+    SSA_DEV void slab(ssa_lookahead_out& os, int64_t m, int S) const
+    {
+        const int64_t rs = (int64_t)env * S * m, rp = (int64_t)env * m;
+        os.score += rs * SSA_LOOK_NSCORE;
+        os.status += rs;
+        os.visible += rs;
+        if (os.P_post) os.P_post += rs * 36;
+        if (os.x_prior) os.x_prior += rp * 6;
+        if (os.P_prior) os.P_prior += rp * 36;
+    }
+};
 // a pointer into the argument segment that the optimiser cannot see through: the (scalar) loads from it stay inside ActLookSensors'
 // passes instead of being hoisted in front of them, where their results would hold scalar registers across every pass
 template <class T> SSA_DEV const T* kernarg_opaque(const T* q)
@@ -1305,6 +1333,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     constexpr bool LSENS = ACT::look_sensors;   // the lookahead of a sensor network: ALL, one pass per sensor (ActLookSensors)
     constexpr bool FCAST = ACT::forecast;      // ... as step h of a forecast: LSENS on a resident tile (ActForecastSensors)
     constexpr bool ENVS = ACT::envs;           // SENS in each of several envs, whole tiles per env (ActSensorEnvs)
+    constexpr bool LENVS = ACT::look_envs;     // LSENS in each of several envs, whole tiles per env (ActLookSensorEnvs)
     // (ActLookSensors, multi-tile instance: the next tile's loads leave once, behind the last pass -- except with SSA_PROP_ELEMENTS, whose
     // out-of-line call then spills 8 more VGPRs: there they are issued as in every other kernel, after the propagator and again at the end
     // of each pass's update)
@@ -1342,6 +1371,10 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // env of the object: no division for the single-env case, a 32-bit one otherwise (n_env * n_obj < 2^31)
     int e = (valid && hw.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
     if constexpr (ENVS) e = asrc.env;   // (whole tiles per env: no division per lane)
+    if constexpr (LENVS) {              // (the same for a network's lookahead: the tile's env, a scalar)
+        asrc.enter(hw.n_env, p.n_obj, base);
+        e = asrc.env;
+    }
     const int64_t j = valid ? obj - (int64_t)e * p.n_obj : 0;
     // the action / time index of this object's env, fetched early (used after the transform)
     // (one env: wave-uniform loads -- scalar ones from the constant address space in the one-tile instances, see env_action; the
@@ -1357,13 +1390,14 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         const ConstPtr<int32_t> t_src = segment_word_src<true>(hw.mask, hw.env_time), a_src = segment_word_src<false>(hw.mask, hw.actions);
         int t0 = *t_src, a0 = -1;
         if constexpr (ENVS) t0 = t_src[asrc.env];   // (the tile's env: still a scalar load)
+        if constexpr (LENVS) t0 = t_src[asrc.env];
         if (!ALL && !SENS) a0 = *a_src;
         if (hw.obj_ids) {
             const v4i w = *(ConstPtr<v4i>)(hw.obj_ids + base);
             id0 = w.x; id1 = w.y; id2 = w.z; id3 = w.w;
         }
         asm volatile("" : "+s"(t0), "+s"(a0), "+s"(id0), "+s"(id1), "+s"(id2), "+s"(id3));
-        if (!ENVS && hw.n_env > 1) {
+        if (!ENVS && !LENVS && hw.n_env > 1) {
             t0 = segment_lane_word(t_src, e);
             if (!ALL && !SENS) a0 = segment_lane_word(a_src, e);
         }
@@ -1983,8 +2017,14 @@ look_pass:
         if (TILE == 1 && ISSUE_LAST && last) tile_issue(pf, p, lane, next_base, next_cnt);
         ssa_lookahead_out os = PASS_ARGS ? *kernarg_opaque(asrc.o) : *asrc.o;
         if constexpr (FCAST) asrc.slab(os, p.n_obj, SP->n_sensor);   // (a forecast: this step's slab of every block)
+        if constexpr (LENVS) asrc.slab(os, p.n_obj, SP->n_sensor);   // (several envs: the env's slab of every block)
         if (look_s > 0) os.x_prior = os.P_prior = nullptr;   // (no sensor axis: the first pass wrote them)
+        if constexpr (LENVS) {
+            if (valid) lookahead_store<1>(t, os, g, l, (int64_t)look_s * p.n_obj + (p.obj_ids ? (int64_t)t.Oid[g] : obj - (int64_t)asrc.env * p.n_obj),
+                                          st_new, look_vis, look_taken);
+        } else {
         if (valid) lookahead_store<1>(t, os, g, l, (int64_t)look_s * p.n_obj + (p.obj_ids ? (int64_t)t.Oid[g] : obj), st_new, look_vis, look_taken);
+        }
         if (!last) {
             ++look_s;
             wave_lds_sync();   // (this pass's reads of P+ precede the next pass's staging)
@@ -2239,6 +2279,10 @@ struct LookSensK {
     LookK k;
     ssa_sensor_params s;
 };
+struct VecLookSensK {   // (LookSensK's layout under a name of its own: the type selects ActLookSensorEnvs)
+    LookK k;
+    ssa_sensor_params s;
+};
 struct VecSensK {   // ... and, behind SensK's, the envs' action rows and records (ssa_env_step_sensors_envs_f64)
     StepK k;
     ssa_sensor_params s;
@@ -2249,6 +2293,7 @@ SSA_DEV const StepK& step_of(const StepK& k) { return k; }
 SSA_DEV const StepK& step_of(const LookK& k) { return k.k; }
 SSA_DEV const StepK& step_of(const SensK& k) { return k.k; }
 SSA_DEV const StepK& step_of(const LookSensK& k) { return k.k.k; }
+SSA_DEV const StepK& step_of(const VecLookSensK& k) { return k.k.k; }
 SSA_DEV ConstPtr<int32_t> vector_sensors_inline_rows()   // (by the segment's address, as tile_kernel_params: rows indexed by the tile's env)
 {
     return (ConstPtr<int32_t>)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(TileArgs<VecSensK>, k) + offsetof(VecSensK, v) +
@@ -2259,6 +2304,7 @@ SSA_DEV ActEarly act_of(const StepK&) { return ActEarly(); }   // (the leading {
 SSA_DEV ActAll act_of(const LookK& k) { return ActAll{{}, &k.o}; }
 SSA_DEV ActSensors act_of(const SensK& k) { return ActSensors{{}, &k.s}; }
 SSA_DEV ActLookSensors act_of(const LookSensK& k) { return ActLookSensors{{}, &k.k.o, &k.s}; }
+SSA_DEV ActLookSensorEnvs act_of(const VecLookSensK& k) { return ActLookSensorEnvs{{}, &k.k.o, &k.s, 0}; }   // (process_wave enters the tile's env)
 SSA_DEV ActSensorEnvs act_of(const VecSensK& k) { return ActSensorEnvs{{}, &k.s, &k.v, 0, nullptr, nullptr}; }   // (process_wave enters the tile's env)
 // WALK: what sets the four kernels apart
 enum : unsigned {
@@ -2348,6 +2394,7 @@ SSA_TILE_KERNEL(lookahead_kernel, LookK, 0)                                     
 SSA_TILE_KERNEL(lookahead_sensors_kernel, LookSensK, WALK_ONE_ENV | WALK_ACT_SEGMENT)      // a sensor network's lookahead
 SSA_TILE_KERNEL(step_sensors_kernel, SensK, WALK_STEP | WALK_ONE_ENV)                      // a sensor network's step
 SSA_TILE_KERNEL(vector_sensors_kernel, VecSensK, WALK_STEP)                                // ... in each of several envs
+SSA_TILE_KERNEL(lookahead_sensor_envs_kernel, VecLookSensK, WALK_ACT_SEGMENT)           // a network's lookahead in each of several envs
 #undef SSA_TILE_KERNEL
 
 // Rollout: K consecutive env steps of the same objects in ONE launch.  An object's trajectory depends on no other
@@ -3639,9 +3686,10 @@ SSA_DEV bool asg_after(double v, long long j, double pv, long long pj)      // d
 {
     return j >= 0 && (v < pv || (v == pv && j > pj));
 }
-__global__ void __launch_bounds__(ASG_T) assign_sensors_kernel(const double* __restrict__ score, int64_t m, int S, int col,
-                                                               const int32_t* __restrict__ fallback, int32_t* __restrict__ action_out,
-                                                               int64_t* __restrict__ pick_out, unsigned long long* ws)
+// (one body for one env -- assign_sensors_kernel -- and for E of them -- assign_sensors_envs_kernel, which hands it each env's
+// scores, rows and part of the workspace: the grid's x axis walks the chunks, the hand-over is among the gridDim.x workgroups of an env)
+SSA_DEV void assign_sensors_body(const double* __restrict__ score, int64_t m, int S, int col, const int32_t* __restrict__ fallback,
+                                 int32_t* __restrict__ action_out, int64_t* __restrict__ pick_out, unsigned long long* ws)
 {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     AsgCand* parts = reinterpret_cast<AsgCand*>(ws + 8);
@@ -3759,6 +3807,23 @@ __global__ void __launch_bounds__(ASG_T) assign_sensors_kernel(const double* __r
             pick_out[2 * lane + 1] = __double_as_longlong(pick_v);
         }
     }
+}
+__global__ void __launch_bounds__(ASG_T) assign_sensors_kernel(const double* __restrict__ score, int64_t m, int S, int col,
+                                                               const int32_t* __restrict__ fallback, int32_t* __restrict__ action_out,
+                                                               int64_t* __restrict__ pick_out, unsigned long long* ws)
+{
+    assign_sensors_body(score, m, S, col, fallback, action_out, pick_out, ws);
+}
+// ... of every env of a vector launch (ssa_assign_sensors_envs_f64): grid (chunks, envs).  Env e = blockIdx.y has its [S][m][3] slab of
+// the scores, its rows of `fallback`, `action_out` and `pick_out`, and its own ticket and candidate area, `ws_words` words apart
+// (64-byte aligned); the last workgroup to arrive FOR ITS ENV merges and assigns that env.
+__global__ void __launch_bounds__(ASG_T) assign_sensors_envs_kernel(const double* __restrict__ score, int64_t m, int S, int col,
+                                                                    const int32_t* __restrict__ fallback, int32_t* __restrict__ action_out,
+                                                                    int64_t* __restrict__ pick_out, unsigned long long* ws, int64_t ws_words)
+{
+    const int64_t e = blockIdx.y;
+    assign_sensors_body(score + e * S * m * SSA_LOOK_NSCORE, m, S, col, fallback ? fallback + e * SSA_MAX_SENSORS : nullptr,
+                        action_out + e * SSA_MAX_SENSORS, pick_out ? pick_out + e * SSA_MAX_SENSORS * 2 : nullptr, ws + e * ws_words);
 }
 
 // ---- diagnostic reductions of SURVEY 8f-4 (ssa_tasker_simple_2.py:436-446, 750-775): NEES = d^T inv(P) d with
@@ -4260,6 +4325,27 @@ int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, con
     });
     return launch_status();
 }
+int ssa_lookahead_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_lookahead_out* o,
+                                   void* stream)
+{
+    if (!c || !p || !sp || !o) return SSA_E_INVALID;
+    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
+    for (int k = 0; k < sp->n_sensor; ++k)
+        if (!(sp->obs_limit[k] == sp->obs_limit[k])) return SSA_E_INVALID;
+    VecLookSensK k;
+    const int rc = lookahead_args(c, p, o, k.k);
+    if (rc != SSA_OK) return rc;
+    if ((int64_t)p->n_env * sp->n_sensor * p->n_obj >= ((int64_t)1 << 31)) return SSA_E_INVALID;
+    if (p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // whole tiles per env: a tile's env is wave-uniform
+    k.s = idle_sites(sp);
+    const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
+    dim3 grid((unsigned)g.nwork), block(64);
+    hipStream_t s = (hipStream_t)stream;
+    with_prop(c->propagator, g.per_wave != 1, [&](auto P, auto M) {
+        hipLaunchKernelGGL((lookahead_sensor_envs_kernel<P, M>), grid, block, 0, s, g.arg, g.nwork, p->P_in, p->x_in, p->x_true_in, p->status, k);
+    });
+    return launch_status();
+}
 int ssa_forecast_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_forecast_params* f,
                              void* stream)
 {
@@ -4691,6 +4777,24 @@ int ssa_assign_sensors_f64(const double* score, int64_t n_obj, int32_t n_sensor,
     if (need < 0 || !workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need) return SSA_E_INVALID;
     hipLaunchKernelGGL(assign_sensors_kernel, dim3(nblk(n_obj, ASG_CH)), dim3(ASG_T), 0, (hipStream_t)stream, score, n_obj, (int)n_sensor,
                        (int)column, fallback, action_out, pick_out, (unsigned long long*)workspace);
+    return launch_status();
+}
+// every env's part of the workspace: the one-env workspace rounded up to 64 bytes
+int64_t ssa_assign_sensors_envs_workspace_bytes(int64_t n_obj, int32_t n_sensor, int32_t n_env)
+{
+    const int64_t one = ssa_assign_sensors_workspace_bytes(n_obj, n_sensor);
+    if (one < 0 || n_env < 1) return SSA_E_INVALID;
+    return n_env * ((one + 63) / 64 * 64);
+}
+int ssa_assign_sensors_envs_f64(const double* score, int64_t n_obj, int32_t n_sensor, int32_t n_env, int32_t column, const int32_t* fallback,
+                                int32_t* action_out, int64_t* pick_out, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    if (!score || !action_out || ((uintptr_t)action_out & 31) || column < 0 || column >= SSA_LOOK_NSCORE) return SSA_E_INVALID;
+    const int64_t need = ssa_assign_sensors_envs_workspace_bytes(n_obj, n_sensor, n_env);      // (refuses n_obj, n_sensor and n_env out of range)
+    if (need < 0 || !workspace || ((uintptr_t)workspace & 63) || workspace_bytes < need) return SSA_E_INVALID;
+    if ((int64_t)n_env * n_sensor * n_obj >= ((int64_t)1 << 31) || n_env > 65535) return SSA_E_INVALID;
+    hipLaunchKernelGGL(assign_sensors_envs_kernel, dim3(nblk(n_obj, ASG_CH), (unsigned)n_env), dim3(ASG_T), 0, (hipStream_t)stream, score,
+                       n_obj, (int)n_sensor, (int)column, fallback, action_out, pick_out, (unsigned long long*)workspace, need / n_env / 8);
     return launch_status();
 }
 

@@ -335,6 +335,40 @@ def assign_sensors(score, column, fallback=None, out=None, picks=None, workspace
     return out
 
 
+def assign_sensors_envs_workspace(n_obj, n_sensor, n_env, device):
+    """zeroed workspace of ssa_assign_sensors_envs_f64 for n_env envs of n_sensor sensors over n_obj objects each (one call at a time:
+    keep it with the stream that uses it; the kernel leaves it ready for the next call)"""
+    nbytes = int(_lib.load().ssa_assign_sensors_envs_workspace_bytes(int(n_obj), int(n_sensor), int(n_env)))
+    if nbytes < 0:
+        raise _lib.SsaHipError("ssa_assign_sensors_envs_workspace_bytes(%d, %d, %d) failed with code %d" % (n_obj, n_sensor, n_env, nbytes))
+    return torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
+
+
+def assign_sensors_envs(score, column, fallback=None, out=None, picks=None, workspace=None):
+    """the tasking assignment of a sensor network in each of E envs (ssa_assign_sensors_envs_f64): assign_sensors for every env's slab of
+    score [E, S, m, 3] -- the rows launch_lookahead_sensors_envs leaves -- in ONE launch.  fallback: int32 [E, MAX_SENSORS] draws per env
+    (None: a sensor left without an object stays idle, -1).  Returns the int32 CUDA table [E, MAX_SENSORS] (`out`: a 32-byte aligned
+    table to write, e.g. the action table the next launch_step_sensors_envs reads; entries s >= S are -1); picks: int64
+    [E, MAX_SENSORS, 2] to receive the assigned objects and their scores' bit patterns.  workspace: assign_sensors_envs_workspace
+    (default: a fresh one).  No host sync."""
+    lib = _lib.load()
+    _chk(score, "score")
+    if score.dim() != 4 or score.shape[3] != _lib.LOOK_NSCORE:
+        raise _lib.SsaHipError("score must be [E, S, m, %d]" % _lib.LOOK_NSCORE)
+    E, S, m = (int(v) for v in score.shape[:3])
+    W = _lib.MAX_SENSORS
+    out = torch.empty((E, W), dtype=torch.int32, device=score.device) if out is None else out
+    ws = assign_sensors_envs_workspace(m, S, E, score.device) if workspace is None else workspace
+    ptr = {}
+    for t, name, dtype, n in ((out, "out", torch.int32, E * W), (fallback, "fallback", torch.int32, E * W), (picks, "picks", torch.int64, 2 * E * W)):
+        ptr[name] = None if t is None else _chk(t, name, dtype)
+        if t is not None and t.numel() != n:
+            raise _lib.SsaHipError("%s must hold %d %s words" % (name, n, dtype))
+    _lib.check(lib.ssa_assign_sensors_envs_f64(score.data_ptr(), m, S, E, int(column), ptr["fallback"], ptr["out"], ptr["picks"],
+                                               _chk(ws, "workspace", torch.int64), ws.numel() * 8, _stream()), "ssa_assign_sensors_envs_f64")
+    return out
+
+
 def env_step(consts, params):
     """E1: the fused step.  `params` is a filled _lib.ssa_step_params."""
     lib = _lib.load()

@@ -114,6 +114,8 @@ class HotPathEngine:
         self._assign_ws = None                          # (S, workspace) of launch_assign_sensors
         self._assign_row = None                         # assign_row()'s
         self._sensor_envs = None                        # launch_step_sensors_envs: its block, the [E][8] action table and its staging
+        self._look_se = None                            # output buffers of launch_lookahead_sensors_envs
+        self._assign_envs_ws = None                     # (S, workspace) of launch_assign_sensors_envs
         self._pcache = {}
         self._cref = C.byref(self.consts)
         self._pref = C.byref(self._p)
@@ -414,7 +416,20 @@ class HotPathEngine:
         sensors.upd = int(upd_out)
         self.launch_step(slot_in, slot_out, time_offset, stream=stream, sensors=sensors, **kw)
 
-    def launch_step_sensors_envs(self, slot_in, slot_out, time_offset, sensors, actions, upd_out=0, stream=None, env_words=None, **kw):
+    def _sensor_envs_block(self):
+        """(ssa_sensor_envs_params, the [E][8] int32 device action table, its host staging) of this engine; allocated on first use"""
+        if self._sensor_envs is None:
+            W = _lib.MAX_SENSORS
+            self._sensor_envs = (_lib.ssa_sensor_envs_params(), torch.full((self.E, W), -1, dtype=torch.int32, device=self.dev),
+                                 np.full((self.E, W), -1, dtype=np.int32))
+        return self._sensor_envs
+
+    def action_table(self):
+        """this engine's [E][MAX_SENSORS] int32 device action table: what launch_step_sensors_envs copies rows into, what
+        launch_assign_sensors_envs writes and what launch_step_sensors_envs(actions=None) reads"""
+        return self._sensor_envs_block()[1]
+
+    def launch_step_sensors_envs(self, slot_in, slot_out, time_offset, sensors, actions=None, upd_out=0, stream=None, env_words=None, **kw):
         """enqueue the step of a sensor network in EVERY env of the engine, one launch (include/ssa_hip.h: ssa_env_step_sensors_envs_f64):
         per env what launch_step_sensors does for one.  `sensors`: host.make_sensor_params(), the sites all envs share (its action words
         and record pointer are not read); `actions` [E][S]: sensor s of env e observes object actions[e][s] of that env (< 0 or >= n_obj:
@@ -424,19 +439,26 @@ class HotPathEngine:
         (SSA_LAUNCH_INLINE_ENVS); otherwise the rows travel through this engine's [E][8] int32 device table (a blocking copy in the
         current stream, which a launch still running from that table must not share a race with: synchronise between such launches, as
         the vector env does) and the times are the engine's env_time0 words.  Several envs need n_obj % 4 == 0.  Every other keyword as launch_step.
+        actions=None: the table is read as launch_assign_sensors_envs left it -- no copy, the rows from device memory, the times from
+        env_time0 (env_words is refused): the actions never touch the host.
         Asynchronous, no host sync."""
-        S, W = int(sensors.n_sensor), _lib.MAX_SENSORS
-        a = np.asarray(actions, dtype=np.int64)
-        if a.shape != (self.E, S):
-            raise _lib.SsaHipError("launch_step_sensors_envs: actions must be [%d][%d] (envs x sensors), got %s" % (self.E, S, a.shape))
+        S = int(sensors.n_sensor)
+        if actions is None:
+            if env_words is not None:
+                raise _lib.SsaHipError("launch_step_sensors_envs: actions=None reads the rows and the time words from device memory (no env_words)")
+        else:
+            a = np.asarray(actions, dtype=np.int64)
+            if a.shape != (self.E, S):
+                raise _lib.SsaHipError("launch_step_sensors_envs: actions must be [%d][%d] (envs x sensors), got %s" % (self.E, S, a.shape))
         if self.E > 1 and self.m % 4:
             raise _lib.SsaHipError("a sensor network in several envs needs n_obj % 4 == 0 (whole tiles per env)")
         self._check_sensor_noise(sensors, envs=True)
-        if self._sensor_envs is None:
-            self._sensor_envs = (_lib.ssa_sensor_envs_params(), torch.full((self.E, W), -1, dtype=torch.int32, device=self.dev),
-                                 np.full((self.E, W), -1, dtype=np.int32))
-        v, table, rows_np = self._sensor_envs
+        v, table, rows_np = self._sensor_envs_block()
         v.upd = int(upd_out)
+        if actions is None:
+            v.actions = table.data_ptr()
+            self.launch_step(slot_in, slot_out, time_offset, stream=stream, sensors=sensors, sensor_envs=v, env_words=None, **kw)
+            return
         a = np.clip(a, -1, 2 ** 31 - 1)      # (an int32 word; anything < 0 is idle, anything >= n_obj too)
         if env_words is not None:
             if self.E > _lib.INLINE_ENVS:
@@ -529,6 +551,56 @@ class HotPathEngine:
         if rc:
             raise _lib.SsaHipError("ssa_lookahead_sensors_f64 failed with code %d" % rc)
         return res
+
+    def launch_lookahead_sensors_envs(self, slot_in, time_offset, sensors, out=(), stream=None, env_times=None):
+        """enqueue the lookahead of a sensor network in EVERY env of the engine, one launch (include/ssa_hip.h:
+        ssa_lookahead_sensors_envs_f64): per env what launch_lookahead_sensors does for one, the sites of `sensors` shared by all envs.
+        env_times: as launch_lookahead's (the envs' time words by value, n_env <= 8; else the engine's env_time0 words).  Nothing of the
+        engine's state is written.  Returns a dict of this engine's output tensors, objects at each env's own caller indices: score
+        [E, S, m, 3], status [E, S, m] int32, visible [E, S, m] uint8 and the parts of LOOKAHEAD_PARTS asked for in `out` (x_prior
+        [E, m, 6], P_prior [E, m, 6, 6], P_post [E, S, m, 6, 6]).  The buffers are its own, allocated on first use (again when S changes)
+        and reused by the next call.  Several envs need n_obj % 4 == 0.  Asynchronous, no host sync."""
+        o, res = self._lookahead_out("launch_lookahead_sensors_envs", "_look_se", (self.E, int(sensors.n_sensor), self.m), (self.E, self.m), out)
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        p = self._lookahead_params(slot_in, time_offset)
+        if env_times is not None:
+            if self.E > _lib.INLINE_ENVS:
+                raise _lib.SsaHipError("env_times: at most %d envs travel in the parameter block" % _lib.INLINE_ENVS)
+            p.inline_time[:self.E] = [int(v) for v in env_times]
+            p.launch_mask = _lib.LAUNCH_INLINE_ENVS
+        rc = self._lib.ssa_lookahead_sensors_envs_f64(self._cref, C.byref(p), C.byref(sensors), C.byref(o), s)
+        if rc:
+            raise _lib.SsaHipError("ssa_lookahead_sensors_envs_f64 failed with code %d" % rc)
+        return res
+
+    def launch_assign_sensors_envs(self, look, column, fallback=None, picks=None, stream=None):
+        """enqueue every env's tasking assignment, one launch (include/ssa_hip.h: ssa_assign_sensors_envs_f64), on `look`, the dict
+        launch_lookahead_sensors_envs returned: per env what launch_assign_sensors does for one, written into this engine's own
+        [E][MAX_SENSORS] action table (action_table()) -- the one launch_step_sensors_envs(actions=None) then reads: the actions never
+        touch the host.  fallback: int32 CUDA [E, MAX_SENSORS] draws (None: a sensor left without an object stays idle, -1); picks:
+        int64 CUDA [E, MAX_SENSORS, 2] or None.  The workspace is this engine's (zeroed once, again when S changes).  Returns the table.
+        Asynchronous, no host sync."""
+        score = look["score"]
+        S = int(score.shape[1]) if isinstance(score, torch.Tensor) and score.dim() == 4 else 0
+        W = _lib.MAX_SENSORS
+        for t, dt, n, nm in ((fallback, torch.int32, self.E * W, "fallback"), (picks, torch.int64, 2 * self.E * W, "picks")):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == n):
+                raise _lib.SsaHipError("assign: %s must be a contiguous CUDA %s tensor of %d elements" % (nm, dt, n))
+        if not (isinstance(score, torch.Tensor) and score.is_cuda and score.dtype == torch.float64 and score.is_contiguous()
+                and tuple(score.shape) == (self.E, S, self.m, _lib.LOOK_NSCORE)):
+            raise _lib.SsaHipError("assign: the contiguous CUDA float64 [%d, S, %d, %d] scores of launch_lookahead_sensors_envs are needed"
+                                   % (self.E, self.m, _lib.LOOK_NSCORE))
+        if self._assign_envs_ws is None or self._assign_envs_ws[0] != S:
+            self._assign_envs_ws = (S, device.assign_sensors_envs_workspace(self.m, S, self.E, self.dev))
+        ws = self._assign_envs_ws[1]
+        table = self.action_table()
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        rc = self._lib.ssa_assign_sensors_envs_f64(score.data_ptr(), self.m, S, self.E, int(column), fallback.data_ptr() if fallback is not None else 0,
+                                                   table.data_ptr(), picks.data_ptr() if picks is not None else 0, ws.data_ptr(),
+                                                   ws.numel() * 8, s)
+        if rc:
+            raise _lib.SsaHipError("ssa_assign_sensors_envs_f64 failed with code %d" % rc)
+        return table
 
     def launch_forecast_sensors(self, slot_in, time_offset, sensors, n_steps, out=(), stream=None):
         """enqueue the tasking forecast of a sensor network (include/ssa_hip.h: ssa_forecast_sensors_f64; one env): what

@@ -12,6 +12,12 @@ consumes noise in a step (ssa_tasker_simple_2.py:301).
 A sensor network (config['observers'] with S > 1 sites, EXTENSION): every env tasks the same S sites, each sensor to its own object;
 `step(actions)` takes [E, S] and is still ONE launch (ssa_env_step_sensors_envs_f64).  Noise is then drawn per
 (env, sensor, time step).
+
+Around the step: `lookahead_sensors()` is every sensor's lookahead in every env from ONE launch
+(ssa_lookahead_sensors_envs_f64) -- the action mask and the gains an RL user trains against; `step_agent(agent)` is a vector step whose
+actions a lookahead agent decides ON THE DEVICE: lookahead, every env's greedy assignment (ssa_assign_sensors_envs_f64) into the
+engine's action table, and the step reading that table -- three launches in one stream, one synchronisation, the actions never on the
+host in between.  agents.agent_info_gain_sensors / agent_trace_gain_sensors take a vector env and return [E, S].
 """
 import numpy as np
 
@@ -32,6 +38,32 @@ def check_sensor_actions(actions, E, S, m):
         if len(np.unique(a[e])) != S:
             raise ValueError("step: two sensors tasked to the same object (%s) in env %d" % (a[e], e))
     return a
+
+
+SENSOR_AGENTS = {'agent_info_gain_sensors': _lib.LOOK_INFO_GAIN, 'agent_trace_gain_sensors': _lib.LOOK_TRACE_GAIN}
+
+
+def sensor_agent_column(agent):
+    """the score column of a lookahead agent of a sensor network, given as the function of agents.py or its name; anything else has
+    no device form in a vector env (NotImplementedError).  Needs no device state."""
+    name = agent if isinstance(agent, str) else getattr(agent, '__name__', None)
+    if name not in SENSOR_AGENTS:
+        raise NotImplementedError("step_agent: %r is not implemented; the agents of a sensor network that decide on the device are %s"
+                                  % (agent, " and ".join(sorted(SENSOR_AGENTS))))
+    return SENSOR_AGENTS[name]
+
+
+def check_fallback_actions(fallback, E, S):
+    """the [E, S] fallback rows of step_agent as int32 [E, MAX_SENSORS] words (-1 beyond S): any integer is taken as given -- an entry
+    outside 0 .. m-1 leaves its sensor idle when it gets no object -- any other shape or dtype is a ValueError naming the shape.  Needs
+    no device state."""
+    a = np.asarray(fallback)
+    if a.shape != (E, S) or a.dtype.kind not in "iu":
+        raise ValueError("step_agent: fallback_actions must be an integer array of shape (%d, %d) (envs x sensors), got shape %s (%s)"
+                         % (E, S, a.shape, a.dtype))
+    rows = np.full((E, _lib.MAX_SENSORS), -1, dtype=np.int32)
+    rows[:, :S] = np.clip(a.astype(np.int64), -1, 2 ** 31 - 1)
+    return rows
 
 
 def shaped_hit(actions, argmax_prev):
@@ -64,6 +96,9 @@ class SSA_Tasker_VecEnv:
             from .. import host
             self._zs = torch.as_tensor(c.net.z_sigma, dtype=torch.float64, device="cuda").view(S, 1, 1, 3)
             self._sensors = host.make_sensor_params(c.net.lla, c.net.obs_limit, c.net.R, self.n * 3)
+        self._site = (c.obs_lla, c.obs_limit, c.R)      # (the env's own observer: a one-site network for lookahead_sensors)
+        self._look_sites = None
+        self._rows_host = None                          # step_agent: pinned [E, MAX_SENSORS] read-back of the action table
         self._z_shape = (S, self.n, 1, 3) if S > 1 else (self.n, 1, 3)
         z = torch.randn((self.E,) + self._z_shape, dtype=torch.float64, device="cuda", generator=self._gen) * self._zs
         self._eng = engine.HotPathEngine(self._consts, self.m, self.E, c.trans, z, history=2,
@@ -181,13 +216,35 @@ class SSA_Tasker_VecEnv:
                 self._aer[sl].copy_(e.env_caller_rows(k, self._aer[sl]))
 
     def step(self, actions):
-        import torch
         S = self.n_sensor
         if S > 1:
             actions = check_sensor_actions(actions, self.E, S, self.m)
         else:
             actions = np.asarray(actions, dtype=np.int64).reshape(self.E)
             assert 0 <= int(actions.min()) and int(actions.max()) < self.m, "invalid action"
+        return self._step(actions)
+
+    def step_agent(self, agent, fallback_actions=None):
+        """One vector step of a sensor network whose actions a lookahead agent decides ON THE DEVICE: every
+        sensor's lookahead in every env, every env's greedy assignment into the engine's action table, and the step reading that
+        table -- three launches in one stream, one synchronisation; the actions reach the host only afterwards, for the 'shaped' hit and
+        for the caller.  `agent`: agents.agent_info_gain_sensors or agents.agent_trace_gain_sensors, or its name.  fallback_actions:
+        what a sensor the scores leave without an object gets -- None: one single_action_space.sample() row per env; an [E, S] integer
+        array: taken as given, sensors ascending, unless out of 0 .. m-1 or held by another sensor of the env (the sensor then stays
+        idle).  Returns step()'s 4-tuple -- rewards, dones, auto-reset and observations are step()'s -- with infos[e]['action'] the int64
+        [S] row env e executed (-1: the sensor stayed idle)."""
+        column = sensor_agent_column(agent)
+        if self.n_sensor < 2:
+            raise NotImplementedError("step_agent: not implemented without a sensor network (config['observers'])")
+        if fallback_actions is None:
+            fallback_actions = np.stack([np.atleast_1d(self.single_action_space.sample()) for _ in range(self.E)])
+        return self._step(None, decide=(column, check_fallback_actions(fallback_actions, self.E, self.n_sensor)))
+
+    def _step(self, actions, decide=None):
+        """the vector step: `actions` as step() checked them, or -- decide = (score column, fallback words [E, MAX_SENSORS]) -- decided
+        on the device in front of the step's launch (step_agent) and read back behind the one synchronisation"""
+        import torch
+        S = self.n_sensor
         e = self._eng
         argmax_prev = self._argmax_prev
         self.i += 1
@@ -206,7 +263,18 @@ class SSA_Tasker_VecEnv:
         if S > 1:      # (a sensor network: the same single launch, a row of S actions per env; the update records stay on the device side)
             kw = dict(aer_out=aer_out, obs_mirror=mirror, stats_out=self._stats_host.data_ptr(), fast_stats=fast, fold_inside=True,
                       argmax_spos=shaped and fast, mirror_f32=self._mirror_f32 and fast)
-            if self._inline:
+            if decide is not None:     # (lookahead -> assignment -> step, all reading the time words and the rows from device memory)
+                self._time_np[:] = self.i
+                e.time_actions.copy_(self._ta_host, non_blocking=True)
+                fb = torch.from_numpy(decide[1]).to("cuda")
+                cur = torch.cuda.current_stream()
+                look = e.launch_lookahead_sensors_envs(sin, 0, self._sensors, stream=cur.cuda_stream)
+                table = e.launch_assign_sensors_envs(look, decide[0], fallback=fb, stream=cur.cuda_stream)
+                e.launch_step_sensors_envs(sin, sout, 0, self._sensors, None, stream=cur.cuda_stream, **kw)
+                if self._rows_host is None:
+                    self._rows_host = torch.zeros((self.E, _lib.MAX_SENSORS), dtype=torch.int32).pin_memory()
+                self._rows_host.copy_(table, non_blocking=True)
+            elif self._inline:
                 cur = self._stream
                 e.launch_step_sensors_envs(sin, sout, 0, self._sensors, actions, stream=cur.cuda_stream, env_words=self.i.tolist(), **kw)
             else:
@@ -227,6 +295,8 @@ class SSA_Tasker_VecEnv:
             e.launch_step(sin, sout, 0, aer_out=aer_out, obs_mirror=mirror, stats_out=self._stats_host.data_ptr(), stream=cur.cuda_stream,
                           fast_stats=fast, fold_inside=True, argmax_spos=shaped and fast, mirror_f32=self._mirror_f32 and fast)
         cur.synchronize()
+        if decide is not None:
+            actions = self._rows_host.numpy()[:, :S].astype(np.int64)
         st = self._stats_np            # (host-mapped: the step kernel's folds wrote it; stable until the next launch)
         if shaped:
             self._argmax_prev = st[:, _lib.STAT_ARGMAX_SPOS].astype(np.int64)
@@ -234,7 +304,7 @@ class SSA_Tasker_VecEnv:
         rewards, dones = reward_done(self.reward_type, st, hit, self.rewards_sum, self.i + 1 >= self.n, self.m, self.n)
         self.rewards_sum += rewards
         obs = self._obs(sout) if self._obs_device else self._obs_host.hand_out()
-        infos = [{} for _ in range(self.E)]
+        infos = [{'action': actions[k]} for k in range(self.E)] if decide is not None else [{} for _ in range(self.E)]
         if dones.any():   # auto-reset in place; the returned observation of a finished env is its new first one
             for d in np.where(dones)[0]:
                 infos[d]['terminal_observation'] = obs[d].clone() if self._obs_device else obs[d].copy()
@@ -254,7 +324,7 @@ class SSA_Tasker_VecEnv:
         from .. import engine as _engine
         if self.n_sensor > 1:
             raise NotImplementedError("lookahead: not implemented for a sensor network in a vector env (config['observers'] with %d "
-                                      "sensors); use SSA_Tasker_Env.lookahead_sensors" % self.n_sensor)
+                                      "sensors); use lookahead_sensors" % self.n_sensor)
         if np.any(self.i + 1 >= self.n):
             raise ValueError("lookahead: an env has no next step")
         e = self._eng
@@ -272,6 +342,51 @@ class SSA_Tasker_VecEnv:
         for k in want:
             res[k] = r[k].view(shapes[k])
         return res
+
+    def _sites(self):
+        """the sites of the envs as a network: their own; without config['observers'] the envs' one observer as a one-site block"""
+        if self._look_sites is None:
+            from .. import host
+            lla, lim, R = self._site
+            self._look_sites = self._sensors if self.n_sensor > 1 else host.make_sensor_params([lla], [lim], [R], 0)
+        return self._look_sites
+
+    def _launch_lookahead_sensors(self, want=()):
+        """the network's lookahead of every env enqueued for the step each env takes next (time words by value up to 8 envs, through
+        env_time0 beyond); the engine's result dict"""
+        import torch
+        if np.any(self.i + 1 >= self.n):
+            raise ValueError("lookahead_sensors: an env has no next step")
+        e = self._eng
+        times = [int(v) + 1 for v in self.i]
+        if self._inline:
+            return e.launch_lookahead_sensors_envs(self.tick % 2, 0, self._sites(), out=want, stream=self._stream.cuda_stream, env_times=times)
+        e.env_time0.copy_(torch.as_tensor(times, dtype=torch.int32))      # (a synchronous copy: the pinned staging is the step's)
+        return e.launch_lookahead_sensors_envs(self.tick % 2, 0, self._sites(), out=want)
+
+    def lookahead_sensors(self, covariances=False):
+        """SSA_Tasker_Env.lookahead_sensors() of every env from ONE launch (ssa_lookahead_sensors_envs_f64): the
+        same dict with a leading [n_env] axis, S = n_sensor (1 without config['observers']: the envs' own observer, and then equal to
+        lookahead() bit for bit) -- score [E, S, 3, m], visible / status [E, S, m], and with covariances=True x_prior [E, m, 6],
+        P_prior [E, m, 6, 6] and P_post [E, S, m, 6, 6]; objects in each env's own order.  visible is the action mask of the next step,
+        the scores are the greedy baselines' gains.  Nothing of the envs changes; the next call overwrites the tensors."""
+        from .. import engine as _engine
+        want = _engine.HotPathEngine.LOOKAHEAD_PARTS if covariances else ()
+        r = self._launch_lookahead_sensors(want)
+        res = {"score": r["score"].permute(0, 1, 3, 2), "visible": r["visible"], "status": r["status"]}
+        for k in want:
+            res[k] = r[k]
+        return res
+
+    def assign_sensors(self, column):
+        """the lookahead of every env and every env's greedy assignment over score column `column` (_lib.LOOK_*): two launches and one
+        read-back of E x 32 bytes.  int64 [E, S]; -1: the scores left that sensor without an object.  Nothing of the envs changes."""
+        import torch
+        look = self._launch_lookahead_sensors()
+        cur = self._stream if self._inline else torch.cuda.current_stream()
+        table = self._eng.launch_assign_sensors_envs(look, column, stream=cur.cuda_stream)
+        cur.synchronize()
+        return table.cpu().numpy()[:, :self.n_sensor].astype(np.int64)
 
     # inspection helpers (per env)
     def P_filter(self, e):
