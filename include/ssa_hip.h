@@ -653,6 +653,23 @@ typedef struct ssa_forecast_params {
 } ssa_forecast_params;
 int ssa_forecast_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_sensor_params *s_host,
                              const ssa_forecast_params *f, void *stream);
+/* ... in each of E envs, one launch: ssa_forecast_sensors_f64 for every env of a vector launch, as ssa_lookahead_sensors_envs_f64 is
+ * ssa_lookahead_sensors_f64 for every env.  The sites are shared by all envs; env e's time word is env_time[e] or, with
+ * SSA_LAUNCH_INLINE_ENVS (n_env <= SSA_INLINE_ENVS), inline_time[e] -- the only launch_mask bit honoured --, and its step h has time
+ * index (time word) + time_offset + h.  Per env the semantics are exactly ssa_forecast_sensors_f64's; obj_ids is honoured per env.
+ * `f` is ssa_forecast_params unchanged, its blocks with the leading axes [H][E], E = n_env, m = n_obj, S = n_sensor:
+ *   score [H][E][S*m][SSA_LOOK_NSCORE], status / visible [H][E][S*m] (required), P_post [H][E][S*m][36] (or NULL):
+ *       row ((h*E + e)*S + s)*m + j;
+ *   x_prior [H][E][m][6], P_prior [H][E][m][36] (or NULL): row (h*E + e)*m + j
+ * (64-bit offsets) -- slab h of the scores is the contiguous [E][S][m][SSA_LOOK_NSCORE] block ssa_assign_sensors_envs_f64 takes, and
+ * env e's part of slab h is byte for byte what ssa_forecast_sensors_f64 writes into slab h for that env alone.  The measurement noise
+ * is never read; nothing is written but `f->out`.  One launch.
+ * Refused before any launch: every refusal of ssa_forecast_sensors_f64 but its n_env one; n_env * n_sensor * n_obj >= 2^31
+ * (SSA_E_INVALID); SSA_LAUNCH_INLINE_ENVS with n_env > SSA_INLINE_ENVS (SSA_E_INVALID); several envs with n_obj % 4 != 0
+ * (SSA_E_UNSUPPORTED: whole tiles per env).  n_env == 1 is accepted for any n_obj, runs the same kernel and gives exactly what
+ * ssa_forecast_sensors_f64 gives. */
+int ssa_forecast_sensors_envs_f64(const ssa_consts *c, const ssa_step_params *p, const ssa_sensor_params *sites,
+                                  const ssa_forecast_params *f, void *stream);
 
 /* ---------------------------------------------------------------- the tasking assignment of a sensor network, on the device
  * One object per sensor from one column of the scores ssa_lookahead_sensors_f64 leaves, in ONE launch and written where the next launch

@@ -143,6 +143,8 @@ SIGNATURES = {
                                                  C.POINTER(ssa_lookahead_out), c_dp]),
     "ssa_forecast_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
                                            C.POINTER(ssa_forecast_params), c_dp]),
+    "ssa_forecast_sensors_envs_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
+                                                C.POINTER(ssa_forecast_params), c_dp]),
     "ssa_env_rollout_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_rollout_params),
                                               C.POINTER(ssa_sensor_params), C.POINTER(ssa_rollout_sensors_params), c_dp]),
     "ssa_closed_loop_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),

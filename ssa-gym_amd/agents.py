@@ -15,7 +15,8 @@ filter.  On those steps the two agents may pick different objects.
 
 The lookahead agents of a sensor network (agent_info_gain_sensors, agent_trace_gain_sensors) also take a vector env
 (SSA_Tasker_VecEnv) and then return [E, S]: one lookahead launch and one assignment launch for all envs and one read-back of
-E x 32 bytes; vec.step_agent(agent) is the vector step that takes their rows without the host in between."""
+E x 32 bytes; vec.step_agent(agent) is the vector step that takes their rows without the host in between.
+The planners (plan_info_gain_sensors, plan_trace_gain_sensors) take a vector env too and then return [E, H', S] (section 8k)."""
 import numpy as np
 
 from . import _lib
@@ -166,6 +167,10 @@ def agent_trace_gain_sensors(obs, env):         # one object per sensor, greedy 
 # planned at an earlier step of this plan removed from the slab first: the forecast's gains assume no update before h, so an object
 # is planned at most once per plan.  Everything in-stream, one read-back at the end.  No device fallback row: a sensor the scores leave
 # without an object comes back -1 and is filled here by _assign_lookahead_sensors' rule.
+# On a vector env (SSA_Tasker_VecEnv) the same two planners return [E, H', S] -- plan[:, h] is what vec.step()
+# takes at step h: ONE forecast launch for all envs (ssa_forecast_sensors_envs_f64), then per step ONE assignment launch for all envs
+# on the contiguous slab h, each env's earlier picks removed from its own part of the slab; one read-back, the -1 entries filled per
+# env, envs ascending, from single_action_space.
 def _fill_plan(env, plan):
     """the -1 entries of a plan [H', S] filled row by row, sensors ascending: an object no sensor of that row holds, drawn from the
     action space's generator (env.np_random is not touched).  Such a sensor has no healthy visible object left at that step, so its
@@ -197,13 +202,50 @@ def _plan_assigned(env, horizon, k):
     return rows.cpu().numpy()[:, :S].astype(np.int64)
 
 
+def _fill_plan_envs(vec, plan):
+    """a vector env's plan [E, H', S]: _fill_plan for every env, envs ascending, from single_action_space (the envs' _rng is not touched)"""
+    plan = np.asarray(plan, dtype=np.int64)
+    if plan.ndim != 3 or plan.shape[0] != vec.num_envs:
+        raise ValueError("a vector env's plan is [%d, H', S], got shape %s" % (vec.num_envs, plan.shape))
+    return np.stack([_fill_plan(vec, plan[e]) for e in range(plan.shape[0])])
+
+
+def _plan_assigned_envs(vec, horizon, k):
+    """the device's part of a vector env's plan: int64 [E, H', S], -1 where the scores leave a sensor without an object.  ONE forecast
+    launch for all envs, then per step ONE assignment launch for all envs (ssa_assign_sensors_envs_f64) on the contiguous slab
+    score[h] = [E, S, m, 3], into row h of a table of the planner's own (not the engine's action table), with ONE workspace; what an
+    env planned at an earlier step is NaN in a copy of its part of the slab."""
+    import torch
+    from . import device
+    cur = vec._stream if vec._inline else torch.cuda.current_stream()
+    with torch.cuda.stream(cur):
+        score = vec._launch_forecast_sensors(horizon)["score"]     # [H', E, S, m, 3]
+        Hp, E, S, m = score.shape[:4]
+        rows = torch.full((Hp, E, _lib.MAX_SENSORS), -1, dtype=torch.int32, device=score.device)
+        planned = torch.zeros((E, m + 1), dtype=torch.bool, device=score.device)     # (slot m: where the -1 entries of a row land)
+        env_ix = torch.arange(E, device=score.device).view(E, 1)
+        ws = device.assign_sensors_envs_workspace(m, S, E, score.device)
+        for h in range(Hp):
+            slab = score[h] if h == 0 else score[h].masked_fill(planned[:, :m].view(E, 1, m, 1), float("nan"))
+            device.assign_sensors_envs(slab, k, out=rows[h], workspace=ws)
+            r = rows[h].long()
+            planned[env_ix, torch.where(r >= 0, r, torch.full_like(r, m))] = True
+    cur.synchronize()
+    return np.ascontiguousarray(rows.cpu().numpy()[:, :, :S].astype(np.int64).transpose(1, 0, 2))
+
+
 def _plan_lookahead_sensors(env, horizon, k):
+    if hasattr(env, "num_envs"):                           # (a vector env: every env's plan, [E, H', S])
+        if env._eng is None:
+            raise _lib.SsaHipError("no device state: a plan comes from the forecast, which runs on the GPU only (no CPU fallback)")
+        return _fill_plan_envs(env, _plan_assigned_envs(env, horizon, k))
     if env._engine is None:
         raise _lib.SsaHipError("no device state: a plan comes from the forecast, which runs on the GPU only (no CPU fallback)")
     return _fill_plan(env, _plan_assigned(env, horizon, k))
 
 
-def plan_info_gain_sensors(env, horizon):       # a schedule [H', S] for env.rollout_sensors(): greedy over 1/2 ln(det P- / det P+) per step
+def plan_info_gain_sensors(env, horizon):       # a schedule [H', S] for env.rollout_sensors() ([E, H', S] of a vector env): greedy over
+                                                # 1/2 ln(det P- / det P+) per step
     return _plan_lookahead_sensors(env, horizon, _lib.LOOK_INFO_GAIN)
 
 

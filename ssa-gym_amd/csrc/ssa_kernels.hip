@@ -1247,6 +1247,44 @@ struct ActLookSensorEnvs : ActBase {
         if (os.P_prior) os.P_prior += rp * 36;
     }
 };
+// ActForecastSensorEnvs (forecast_sensor_envs_kernel, ssa_forecast_sensors_envs_f64): ActForecastSensors in each of E envs -- both of
+// the above at once: step h of a forecast on a resident tile whose env is a scalar.  What `forecast` and `look_envs` each put into
+// process_wave holds for it unchanged (the status carried to h + 1, the pass-through against the sentinels by the storage row's own
+// status word, the row's index within its env); what the two would do twice is done once: slab() offsets every block to step h, then
+// env e -- rows ((h E + e) S + s) m + j per sensor output, (h E + e) m + j of the prior, so that slab h of the scores is one
+// contiguous [E][S][m][3] block, what ssa_assign_sensors_envs_f64 takes.  The env's time word is a scalar load indexed by the env, from
+// device memory or -- SSA_LAUNCH_INLINE_ENVS -- from the kernel's own argument block (time_word()).
+SSA_DEV ConstPtr<int32_t> forecast_envs_inline_time();   // (inline_time in the argument segment: defined behind VecForeSensK)
+struct ActForecastSensorEnvs : ActBase {
+    static constexpr bool all = true, look_sensors = true, forecast = true, look_envs = true;
+    const ssa_lookahead_out* o;
+    const ssa_sensor_params* s;
+    int h;
+    int n_env;                         // E of the launch (the slab's stride)
+    int env;                           // the tile's env
+    SSA_DEV const ssa_sensor_params* sites() const { return s; }
+    SSA_DEV void enter(int n_env_, int64_t n_obj, int64_t base)
+    {
+        env = (n_env_ > 1) ? __builtin_amdgcn_readfirstlane((int)((uint32_t)base / (uint32_t)n_obj)) : 0;
+    }
+    SSA_DEV int time_word(uint32_t mask, const int32_t* mem) const
+    {
+        const ConstPtr<int32_t> src = (mask & SSA_LAUNCH_INLINE_ENVS) ? forecast_envs_inline_time() : (ConstPtr<int32_t>)mem;
+        return src[env];
+    }
+    // the output block of step h and env e: [H][E][S * m] rows per sensor output, [H][E][m] rows of the prior
+    SSA_DEV void slab(ssa_lookahead_out& os, int64_t m, int S) const
+    {
+        const int64_t he = (int64_t)h * n_env + env;
+        const int64_t rs = he * S * m, rp = he * m;
+        os.score += rs * SSA_LOOK_NSCORE;
+        os.status += rs;
+        os.visible += rs;
+        if (os.P_post) os.P_post += rs * 36;
+        if (os.x_prior) os.x_prior += rp * 6;
+        if (os.P_prior) os.P_prior += rp * 36;
+    }
+};
 // a pointer into the argument segment that the optimiser cannot see through: the (scalar) loads from it stay inside ActLookSensors'
 // passes instead of being hoisted in front of them, where their results would hold scalar registers across every pass
 template <class T> SSA_DEV const T* kernarg_opaque(const T* q)
@@ -1405,7 +1443,8 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         tix = valid ? t0 + hw.time_offset : 0;
     } else if (ALL) {   // (no action: every row is selected)
         act = -1;
-        tix = valid ? env_time_of<INL>(p, e) + p.time_offset : 0;
+        if constexpr (FCAST && LENVS) tix = valid ? asrc.time_word(hw.mask, hw.env_time) + p.time_offset : 0;   // (the tile's env: a scalar load)
+        else tix = valid ? env_time_of<INL>(p, e) + p.time_offset : 0;
     } else if (SENS) {   // (one env; the sensors' actions are matched below, against the row's caller index)
         act = -1;
         if constexpr (ENVS) tix = valid ? env_time_of<INL>(p, asrc.env) + p.time_offset : 0;
@@ -1572,6 +1611,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     obj = base + g;
     e = (valid && p.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
     if constexpr (ENVS) e = asrc.env;
+    if constexpr (FCAST && LENVS) e = asrc.env;   // (a forecast in several envs: no division per lane anywhere)
     // the next tile's inputs: in flight during the transform / covariance / observation / store of this one
     if (TILE == 1 && !ISSUE_LAST) tile_issue(pf, p, lane, next_base, next_cnt);
 
@@ -1915,6 +1955,7 @@ look_pass:
     obj = base + g;
     e = (valid && p.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
     if constexpr (ENVS) e = asrc.env;
+    if constexpr (FCAST && LENVS) e = asrc.env;   // (a forecast in several envs: no division per lane anywhere)
     if (TILE == 1 && !ISSUE_LAST) tile_issue(pf, p, lane, next_base, next_cnt);
     }   // wavefronts holding a selected object
     // envs whose action selects nobody still get a cleared record (written by object 0's row)
@@ -2017,7 +2058,8 @@ look_pass:
         if (TILE == 1 && ISSUE_LAST && last) tile_issue(pf, p, lane, next_base, next_cnt);
         ssa_lookahead_out os = PASS_ARGS ? *kernarg_opaque(asrc.o) : *asrc.o;
         if constexpr (FCAST) asrc.slab(os, p.n_obj, SP->n_sensor);   // (a forecast: this step's slab of every block)
-        if constexpr (LENVS) asrc.slab(os, p.n_obj, SP->n_sensor);   // (several envs: the env's slab of every block)
+        if constexpr (LENVS && !FCAST) asrc.slab(os, p.n_obj, SP->n_sensor);   // (several envs: the env's slab of every block; a forecast
+                                                                               // in several envs: the one slab() above is step h's AND the env's)
         if (look_s > 0) os.x_prior = os.P_prior = nullptr;   // (no sensor axis: the first pass wrote them)
         if constexpr (LENVS) {
             if (valid) lookahead_store<1>(t, os, g, l, (int64_t)look_s * p.n_obj + (p.obj_ids ? (int64_t)t.Oid[g] : obj - (int64_t)asrc.env * p.n_obj),
@@ -2549,6 +2591,29 @@ SSA_DEV ActForecastSensors roll_act(ForePlan, const ForeSensK& ka, ssa_step_para
     return ActForecastSensors{{}, &ka.f.out, &ka.s, h};   // (pointers into the segment: kernarg_opaque in process_wave)
 }
 SSA_RESIDENT_KERNEL(forecast_sensors_kernel, ForeSensK)
+// ... in each of several envs (ssa_forecast_sensors_envs_f64): the fourth resident-tile kernel.  The tiles walk all E * m rows of the
+// caller's block -- whole tiles per env with several envs (the launcher), so a tile's env is a scalar --, step h's block differs from the
+// caller's in the time alone, and the outputs carry the leading [H][E] axes (ActForecastSensorEnvs::slab).
+struct VecForeSensK {   // (ForeSensK's layout under a name of its own: the type selects ActForecastSensorEnvs)
+    StepK k;
+    ssa_sensor_params s;
+    ssa_forecast_params f;
+};
+SSA_DEV ConstPtr<int32_t> forecast_envs_inline_time()   // (by the segment's address: the block is the kernel's first argument)
+{
+    return (ConstPtr<int32_t>)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(VecForeSensK, k) + offsetof(StepK, p) +
+                               offsetof(ssa_step_params, inline_time));
+}
+SSA_DEV const StepK& step_of(const VecForeSensK& a) { return a.k; }
+SSA_DEV ForePlan roll_plan(const VecForeSensK& a) { return ForePlan{a.f.n_steps, (int64_t)a.k.p.n_env * a.k.p.n_obj}; }
+SSA_DEV ssa_step_params roll_source(const VecForeSensK& a, ForePlan) { return a.k.p; }
+SSA_DEV ActForecastSensorEnvs roll_act(ForePlan, const VecForeSensK& ka, ssa_step_params& pk, int h, int)
+{
+    pk = ka.k.p;
+    pk.time_offset = ka.k.p.time_offset + h;
+    return ActForecastSensorEnvs{{}, &ka.f.out, &ka.s, h, ka.k.p.n_env, 0};   // (process_wave enters the tile's env)
+}
+SSA_RESIDENT_KERNEL(forecast_sensor_envs_kernel, VecForeSensK)
 #undef SSA_RESIDENT_KERNEL
 // grid (n_steps, n_env): folds step k's shard set into the statistics slot of step k -- when that slot still
 // belongs to step k at the end of the rollout (the last `history` steps) -- and clears it
@@ -4361,6 +4426,28 @@ int ssa_forecast_sensors_f64(const ssa_consts* c, const ssa_step_params* p, cons
     const TileGrid g = tile_grid(p->n_obj);
     hipStream_t s = (hipStream_t)stream;
     with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(forecast_sensors_kernel<P>, dim3(g.nwork), dim3(64), 0, s, k, (int)g.ntiles, g.nwork); });
+    return launch_status();
+}
+int ssa_forecast_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_forecast_params* f,
+                                  void* stream)
+{
+    if (!c || !p || !sp || !f) return SSA_E_INVALID;
+    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
+    for (int q = 0; q < sp->n_sensor; ++q)
+        if (!(sp->obs_limit[q] == sp->obs_limit[q])) return SSA_E_INVALID;
+    LookK lk;
+    const int rc = lookahead_args(c, p, &f->out, lk);
+    if (rc != SSA_OK) return rc;
+    if ((int64_t)p->n_env * sp->n_sensor * p->n_obj >= ((int64_t)1 << 31)) return SSA_E_INVALID;
+    if (p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // whole tiles per env: a tile's env is wave-uniform
+    if (f->n_steps < 1) return SSA_E_INVALID;
+    VecForeSensK k;
+    k.k = lk.k;   // (launch_mask: SSA_LAUNCH_INLINE_ENVS alone survives lookahead_args, and the kernel reads inline_time by it)
+    k.s = idle_sites(sp);
+    k.f = *f;
+    const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
+    hipStream_t s = (hipStream_t)stream;
+    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(forecast_sensor_envs_kernel<P>, dim3(g.nwork), dim3(64), 0, s, k, (int)g.ntiles, g.nwork); });
     return launch_status();
 }
 // the checks and the argument block shared by ssa_env_rollout_f64 and ssa_env_rollout_sensors_f64 (sens: r->actions is not read); SSA_OK or

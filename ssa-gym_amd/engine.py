@@ -116,6 +116,7 @@ class HotPathEngine:
         self._sensor_envs = None                        # launch_step_sensors_envs: its block, the [E][8] action table and its staging
         self._look_se = None                            # output buffers of launch_lookahead_sensors_envs
         self._assign_envs_ws = None                     # (S, workspace) of launch_assign_sensors_envs
+        self._fore_e = None                             # output buffers of launch_forecast_sensors_envs
         self._pcache = {}
         self._cref = C.byref(self.consts)
         self._pref = C.byref(self._p)
@@ -623,6 +624,35 @@ class HotPathEngine:
         rc = self._lib.ssa_forecast_sensors_f64(self._cref, C.byref(p), C.byref(sensors), C.byref(f), s)
         if rc:
             raise _lib.SsaHipError("ssa_forecast_sensors_f64 failed with code %d" % rc)
+        return res
+
+    def launch_forecast_sensors_envs(self, slot_in, time_offset, sensors, n_steps, out=(), stream=None, env_times=None):
+        """enqueue the tasking forecast of a sensor network in EVERY env of the engine, one launch (include/ssa_hip.h:
+        ssa_forecast_sensors_envs_f64): per env what launch_forecast_sensors does for one, the sites of `sensors` shared by all envs --
+        env e's steps have the time indices (e's time word) + time_offset .. + H - 1.  env_times: as launch_lookahead_sensors_envs' (the
+        envs' time words by value, n_env <= 8; else the engine's env_time0 words).  Nothing of the engine's state is written.  Returns a
+        dict of this engine's output tensors, objects at each env's own caller indices: score [H, E, S, m, 3], status [H, E, S, m] int32,
+        visible [H, E, S, m] uint8 and the parts of LOOKAHEAD_PARTS asked for in `out` (x_prior [H, E, m, 6], P_prior [H, E, m, 6, 6],
+        P_post [H, E, S, m, 6, 6]) -- score[h] is the contiguous [E, S, m, 3] block launch_assign_sensors_envs takes.  The buffers are
+        its own, allocated on first use (again when H or S changes) and reused by the next call; the scores alone are 24 * H * E * S * m
+        bytes, P_post 288 * H * E * S * m.  Several envs need n_obj % 4 == 0.  Asynchronous, no host sync."""
+        H = int(n_steps)
+        if H < 1:
+            raise _lib.SsaHipError("launch_forecast_sensors_envs: n_steps must be >= 1, got %d" % H)
+        f = _lib.ssa_forecast_params()
+        f.n_steps = H
+        f.out, res = self._lookahead_out("launch_forecast_sensors_envs", "_fore_e", (H, self.E, int(sensors.n_sensor), self.m),
+                                         (H, self.E, self.m), out)
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        p = self._lookahead_params(slot_in, time_offset)
+        if env_times is not None:
+            if self.E > _lib.INLINE_ENVS:
+                raise _lib.SsaHipError("env_times: at most %d envs travel in the parameter block" % _lib.INLINE_ENVS)
+            p.inline_time[:self.E] = [int(v) for v in env_times]
+            p.launch_mask = _lib.LAUNCH_INLINE_ENVS
+        rc = self._lib.ssa_forecast_sensors_envs_f64(self._cref, C.byref(p), C.byref(sensors), C.byref(f), s)
+        if rc:
+            raise _lib.SsaHipError("ssa_forecast_sensors_envs_f64 failed with code %d" % rc)
         return res
 
     def launch_assign_sensors(self, look, column, action_row, fallback_row=None, picks=None, stream=None):

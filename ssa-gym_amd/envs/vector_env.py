@@ -18,6 +18,10 @@ Around the step: `lookahead_sensors()` is every sensor's 
 actions a lookahead agent decides ON THE DEVICE: lookahead, every env's greedy assignment (ssa_assign_sensors_envs_f64) into the
 engine's action table, and the step reading that table -- three launches in one stream, one synchronisation, the actions never on the
 host in between.  agents.agent_info_gain_sensors / agent_trace_gain_sensors take a vector env and return [E, S].
+
+Ahead of the step: `forecast_sensors(horizon)` is every sensor's lookahead at each of the next H' steps of every
+env from ONE launch (ssa_forecast_sensors_envs_f64) -- the action masks, the covariance growth and the gains of the steps to come, read
+only; agents.plan_info_gain_sensors / plan_trace_gain_sensors take a vector env and return the greedy plan [E, H', S].
 """
 import numpy as np
 
@@ -377,6 +381,41 @@ class SSA_Tasker_VecEnv:
         for k in want:
             res[k] = r[k]
         return res
+
+    def _launch_forecast_sensors(self, horizon, want=()):
+        """the network's H'-step forecast of every env enqueued from the step each env takes next, H' = min(horizon, the fewest steps
+        an env has left) (time words by value up to 8 envs, through env_time0 beyond); the engine's result dict, [H', E, ...]"""
+        import torch
+        if int(horizon) < 1:
+            raise ValueError("forecast_sensors: a horizon of at least one step, got %r" % (horizon,))
+        if np.any(self.i + 1 >= self.n):
+            raise ValueError("forecast_sensors: an env has no next step")
+        H = min(int(horizon), int(self.n - 1 - self.i.max()))
+        e = self._eng
+        times = [int(v) + 1 for v in self.i]
+        if self._inline:
+            return e.launch_forecast_sensors_envs(self.tick % 2, 0, self._sites(), H, out=want, stream=self._stream.cuda_stream, env_times=times)
+        e.env_time0.copy_(torch.as_tensor(times, dtype=torch.int32))      # (a synchronous copy: the pinned staging is the step's)
+        return e.launch_forecast_sensors_envs(self.tick % 2, 0, self._sites(), H, out=want)
+
+    def forecast_sensors(self, horizon, covariances=False):
+        """SSA_Tasker_Env.forecast_sensors() of every env from ONE launch (ssa_forecast_sensors_envs_f64): from
+        env e's state at its step i_e, what lookahead_sensors() would return at each of the steps i_e + 1 .. i_e + H' if every sensor
+        stayed idle until then, with ONE horizon for all envs, H' = min(horizon, min_e(steps - 1 - i_e)).  ValueError if an env has no
+        next step (the rule of lookahead_sensors()) or horizon < 1.  The single env's dict with a leading [n_env] axis, S = n_sensor (1
+        without config['observers']: the envs' own observer as a one-site network), objects in each env's own order:
+            score   [E, H', S, m, 3]  float64: columns _lib.LOOK_*; NaN unless status == OK and visible from s at that step
+            visible [E, H', S, m]     uint8: the action mask of each of the next H' steps
+            status  [E, H', S, m]     int32
+        and with covariances=True also x_prior [E, H', m, 6], P_prior [E, H', m, 6, 6] and P_post [E, H', S, m, 6, 6] -- views of the
+        engine's [H', E, ...] tensors with the first two axes swapped (not contiguous).  Nothing of the envs changes: no step is spent,
+        no auto-reset, no bookkeeping; the next call overwrites the tensors.  Memory: the scores are 24 * H' * E * S * m bytes and
+        P_post is twelve times that -- at 8 x 20 000 objects, H' = 8 and S = 8 that is 245 MB and 2.9 GB: covariances are for short
+        horizons."""
+        from .. import engine as _engine
+        want = _engine.HotPathEngine.LOOKAHEAD_PARTS if covariances else ()
+        r = self._launch_forecast_sensors(horizon, want)
+        return {k: v.transpose(0, 1) for k, v in r.items()}
 
     def assign_sensors(self, column):
         """the lookahead of every env and every env's greedy assignment over score column `column` (_lib.LOOK_*): two launches and one

@@ -1,0 +1,379 @@
+"""A sensor network's H-step forecast and plan for E envs at once on the MI355X (include/ssa_hip.h: ssa_forecast_sensors_envs_f64;
+HotPathEngine.launch_forecast_sensors_envs; SSA_Tasker_VecEnv.forecast_sensors; agents.plan_info_gain_sensors /
+plan_trace_gain_sensors on a vector env).
+
+The yardstick is the project's own one-env path, which this feature leaves untouched: E one-env engines (E single envs), each holding
+env e's state slice, asked by launch_forecast_sensors (forecast_sensors) at env e's time index.  Everything is compared bit for bit;
+there is no tolerance anywhere."""
+import numpy as np
+import pytest
+
+from support.gpu import envs, hip  # noqa: F401  (the module fixtures)
+from support.sensors import cfg3
+from support.vector_forecast import KEYS, SENTINEL, bits, plan_np, state_bytes
+from support.vector_lookahead import Engines, bad_of, numpy_np, single_envs
+
+pytestmark = pytest.mark.gpu
+
+
+# ---------------------------------------------------------------------------------------------------------------- engine level
+def _vector_fore(hip, g, slot, k, H, by_value):
+    parts = hip.engine.HotPathEngine.LOOKAHEAD_PARTS
+    if by_value:
+        r = g.vec.launch_forecast_sensors_envs(slot, 0, g.sp, H, out=parts, env_times=[t + 1 + k for t in g.t0])
+    else:
+        r = g.vec.launch_forecast_sensors_envs(slot, 1 + k, g.sp, H, out=parts)
+    return numpy_np(hip.torch, r)
+
+
+def _fore_case(hip, E, m, S, H, by_value=None, **kw):
+    """the vector launch against E one-env launches, from the loaded state (slot 0: the NaN filter fails at h = 0 of THIS launch) and
+    after one vector step with every sensor idle (slot 1: it had failed before the launch); returns the engines, the one-env twins and
+    both pairs of outputs"""
+    torch, L = hip.torch, hip.lib
+    by_value = (E <= L.INLINE_ENVS) if by_value is None else by_value
+    g = Engines(hip, E, m, S, **kw)
+    assert max(g.t0) + 2 + H <= 16                                              # every time index below N_TIME
+    ones = [g.one(e) for e in range(E)]
+    parts = hip.engine.HotPathEngine.LOOKAHEAD_PARTS
+    runs = []
+    for k in (0, 1):
+        if k == 1:       # one step, nobody observed: the state moves on, the NaN filter's status word is set
+            g.vec.launch_step_sensors_envs(0, 1, 1, g.sp, np.full((E, S), -1), fast_stats=True)
+            for e in range(E):
+                ones[e].launch_step_sensors(0, 1, g.t0[e] + 1, g.sp, [-1] * S, 0, fast_stats=True)
+        before = state_bytes(torch, g.vec)
+        vec = _vector_fore(hip, g, k, k, H, by_value)
+        after = state_bytes(torch, g.vec)
+        assert before.keys() == after.keys() and {"status", "stats", "fail_count", "x_filter", "upd"} <= before.keys()
+        for name in before:      # nothing of the engine's state is written
+            assert before[name] == after[name], "the forecast wrote the engine's %s" % name
+        assert vec["score"].shape == (H, E, S, m, 3) and vec["status"].shape == (H, E, S, m) and vec["visible"].shape == (H, E, S, m)
+        assert vec["x_prior"].shape == (H, E, m, 6) and vec["P_prior"].shape == (H, E, m, 6, 6) and vec["P_post"].shape == (H, E, S, m, 6, 6)
+        yard = [numpy_np(torch, ones[e].launch_forecast_sensors(k, g.t0[e] + 1 + k, g.sp, H, out=parts)) for e in range(E)]
+        for e in range(E):
+            for name in KEYS:
+                bad = bits(vec[name][:, e]) != bits(yard[e][name])
+                assert not bad.any(), (k, e, name, int(bad.sum()), np.argwhere(bad)[:4])
+        runs.append((vec, yard))
+    return g, ones, runs
+
+
+def _assert_fore_conditions(hip, g, ones, runs, interval=1):
+    """what the cases were built for, found again in the YARDSTICK's outputs"""
+    L, torch = hip.lib, hip.torch
+    E, m, S = g.E, g.m, g.S
+    bad = bad_of(m)
+    assert E == 1 or len(set(g.t0)) == E                                        # envs at different time indices
+    (_, y0), (_, y1) = runs
+    H = y0[0]["status"].shape[0]
+    for e in range(E):
+        # a NaN filter that fails at h = 0 of this launch and shows the sentinels from then on
+        assert np.isin(y0[e]["status"][:, :, bad], (L.ST_PREDICT_NAN, L.ST_PREDICT_LINALG)).all(), e
+        assert not y0[e]["visible"][:, :, bad].any() and np.isnan(y0[e]["score"][:, :, bad]).all(), e
+        for h in range(H):
+            assert np.array_equal(y0[e]["x_prior"][h, bad], SENTINEL) and np.array_equal(y0[e]["P_prior"][h, bad], np.diag(SENTINEL)), (e, h)
+        # a filter that had failed before the launch: its stored state, in every slab
+        assert (y1[e]["status"][:, :, bad] != L.ST_OK).all() and not y1[e]["visible"][:, :, bad].any(), e
+        stored_x = ones[e].caller_rows(ones[e].x_filter[1]).cpu().numpy()[bad]
+        stored_P = ones[e].caller_rows(ones[e].P_filter[1]).cpu().numpy()[bad]
+        for h in range(H):
+            assert np.array_equal(bits(y1[e]["x_prior"][h, bad]), bits(stored_x)), (e, h)
+            assert np.array_equal(bits(y1[e]["P_prior"][h, bad]), bits(stored_P)), (e, h)
+            assert all(np.array_equal(bits(y1[e]["P_post"][h, s, bad]), bits(stored_P)) for s in range(S)), (e, h)
+    if interval == 1 and S >= 2:
+        vis, st = y0[0]["visible"].astype(bool), y0[0]["status"]
+        assert (~vis[:, 0] & vis[:, 1] & (st[:, 1] == L.ST_OK)).any(), "no object below sensor 0's mask and above sensor 1's"
+        assert np.isfinite(y0[0]["score"][:, 1]).any() and np.isnan(y0[0]["score"][:, 0][~vis[:, 0]]).all()
+    assert any(np.isfinite(y["score"]).any() for y in y0)
+
+
+@pytest.mark.parametrize("E,m,S,H", [(2, 4, 2, 3), (3, 8, 3, 5), (9, 12, 8, 4), (1, 7, 3, 4), (6, 4000, 2, 5)])
+def test_vector_forecast_equals_one_env_forecasts(hip, E, m, S, H):
+    """(2, 4, 2, 3): one tile per env; (3, 8, 3, 5): two tiles per env, time words by value; (9, 12, 8, 4): more envs than travel by
+    value -- the time words come from memory -- and every sensor slot; (1, 7, 3, 4): one env with a partial tile; (6, 4000, 2, 5):
+    24 000 objects, several tiles (of several envs) per wavefront"""
+    g, ones, runs = _fore_case(hip, E, m, S, H)
+    _assert_fore_conditions(hip, g, ones, runs)
+    if m == 4000:      # an (e, s, j) whose visibility changes inside the horizon, among the filters healthy throughout
+        changes = 0
+        for y in runs[0][1]:
+            healthy = (y["status"] == hip.lib.ST_OK).all(axis=(0, 1))
+            v = y["visible"].astype(bool)[:, :, healthy]
+            changes += int((v.any(axis=0) & ~v.all(axis=0)).sum())
+        print("(e, s, j) whose visibility changes inside the horizon:", changes)
+        assert changes >= 1
+
+
+@pytest.mark.parametrize("propagator,obs_type", [("fg", "aer"), ("j2", "aer"), ("elements", "aer"), ("hybrid", "xyz")])
+def test_vector_forecast_every_propagator_and_the_xyz_observation(hip, propagator, obs_type):
+    g, ones, runs = _fore_case(hip, 3, 8, 3, 5, propagator=propagator, obs_type=obs_type)
+    _assert_fore_conditions(hip, g, ones, runs)
+
+
+def test_vector_forecast_time_words_by_value_and_from_memory(hip):
+    a = _fore_case(hip, 3, 8, 3, 5, by_value=True)
+    b = _fore_case(hip, 3, 8, 3, 5, by_value=False)
+    _assert_fore_conditions(hip, *a)
+    _assert_fore_conditions(hip, *b)
+    for k in (0, 1):
+        for name in KEYS:
+            assert np.array_equal(bits(a[2][k][0][name]), bits(b[2][k][0][name])), (k, name)
+    _fore_case(hip, 1, 7, 3, 4, by_value=False)
+
+
+def test_vector_forecast_with_per_env_layouts(hip):
+    """per-env obj_ids (set_layout with [E][m] permutations): the output rows are each env's own object numbering"""
+    g, ones, runs = _fore_case(hip, 3, 8, 3, 5, layout=True)
+    _assert_fore_conditions(hip, g, ones, runs)
+    _, _, runs_plain = _fore_case(hip, 3, 8, 3, 5)
+    for name in KEYS:      # (a storage layout never shows)
+        assert np.array_equal(bits(runs[0][0][name]), bits(runs_plain[0][0][name])), name
+
+
+def test_vector_forecast_update_interval_envs_update_at_different_steps(hip):
+    """update_interval = 3: env e's step h is an update step when (t0[e] + 1 + h) % 3 == 0 -- at other steps in every env"""
+    g, ones, runs = _fore_case(hip, 3, 8, 3, 5, interval=3)
+    _assert_fore_conditions(hip, g, ones, runs, interval=3)
+    y0 = runs[0][1]
+    upd = np.array([[(t + 1 + h) % 3 == 0 for h in range(5)] for t in g.t0])      # [E, H]
+    assert len({tuple(u) for u in upd.tolist()}) >= 2 and upd.any(axis=1).all() and not upd.all(axis=0).any()
+    for e in range(3):
+        for h in range(5):
+            if upd[e, h]:
+                continue
+            assert not y0[e]["visible"][h].any() and np.isnan(y0[e]["score"][h]).all(), (e, h)
+            assert all(np.array_equal(bits(y0[e]["P_post"][h, s]), bits(y0[e]["P_prior"][h])) for s in range(3)), (e, h)
+    assert any(y0[e]["visible"][upd[e]].any() for e in range(3))
+
+
+def test_slab_0_equals_the_vector_lookahead_of_the_same_engine(hip):
+    torch = hip.torch
+    parts = hip.engine.HotPathEngine.LOOKAHEAD_PARTS
+    for E, m, S in ((3, 8, 3), (9, 12, 8), (1, 7, 3)):
+        g = Engines(hip, E, m, S)
+        fc = numpy_np(torch, g.vec.launch_forecast_sensors_envs(0, 1, g.sp, 3, out=parts))
+        look = numpy_np(torch, g.vec.launch_lookahead_sensors_envs(0, 1, g.sp, out=parts))
+        assert np.isfinite(look["score"]).any() and (look["status"] != 0).any()
+        for name in KEYS:
+            assert np.array_equal(bits(fc[name][0]), bits(look[name])), (E, name)
+
+
+def test_forecast_equals_lookaheads_between_idle_vector_steps(hip):
+    """against the vector path itself: H x (launch_lookahead_sensors_envs + an all-idle launch_step_sensors_envs) on a second engine"""
+    torch = hip.torch
+    parts = hip.engine.HotPathEngine.LOOKAHEAD_PARTS
+    E, m, S, H = 3, 8, 3, 5
+    g, twin = Engines(hip, E, m, S), Engines(hip, E, m, S)
+    fc = numpy_np(torch, g.vec.launch_forecast_sensors_envs(0, 1, g.sp, H, out=parts))
+    for h in range(H):
+        look = numpy_np(torch, twin.vec.launch_lookahead_sensors_envs(h % 2, 1 + h, twin.sp, out=parts))
+        twin.vec.launch_step_sensors_envs(h % 2, (h + 1) % 2, 1 + h, twin.sp, np.full((E, S), -1), fast_stats=True)
+        torch.cuda.synchronize()
+        for name in KEYS:
+            assert np.array_equal(bits(fc[name][h]), bits(look[name])), (h, name)
+    assert np.isfinite(fc["score"]).any()
+
+
+# ---------------------------------------------------------------------------------------------------------------- env level
+def _vec_cfg(envs, **over):
+    return cfg3(envs, m=8, steps=12, update_interval=1, **over)
+
+
+def _open_sky(envs, **over):
+    """every sensor sees (nearly) every object: each gets one from the scores"""
+    return _vec_cfg(envs, sensor_obs_limit=[-89.0, -89.0, -89.0], **over)
+
+
+def _np_env(r):
+    import torch
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy().copy() for k, v in r.items()}
+
+
+def _same_tensor(a, b):
+    import torch
+    torch.cuda.synchronize()
+    return torch.equal(a, b)
+
+
+def _actions(rs, E, S, m):
+    return np.stack([rs.permutation(m)[:S] for _ in range(E)])
+
+
+def test_vector_env_forecast_equals_single_envs(envs):
+    from ssa_gym_amd.envs.vector_env import SSA_Tasker_VecEnv
+    cfg = _vec_cfg(envs)
+    E, S, m = 3, 3, 8
+    vec = SSA_Tasker_VecEnv(cfg, E, seed=10)
+    singles = single_envs(envs, cfg, vec, 10)
+    rs = np.random.RandomState(4)
+    finite = 0
+    for k in range(4):
+        got = _np_env(vec.forecast_sensors(4, covariances=True))
+        assert got["score"].shape == (E, 4, S, m, 3) and got["visible"].shape == got["status"].shape == (E, 4, S, m)
+        assert got["x_prior"].shape == (E, 4, m, 6) and got["P_prior"].shape == (E, 4, m, 6, 6) and got["P_post"].shape == (E, 4, S, m, 6, 6)
+        assert set(vec.forecast_sensors(2)) == {"score", "visible", "status"}
+        for e in range(E):
+            one = _np_env(singles[e].forecast_sensors(4, covariances=True))
+            assert set(one) == set(got)
+            for name in one:
+                assert np.array_equal(bits(got[name][e]), bits(one[name])), (k, e, name)
+        finite += int(np.isfinite(got["score"]).sum())
+        acts = _actions(rs, E, S, m)
+        vec.step(acts)
+        for e in range(E):
+            singles[e].step(acts[e])
+    assert finite, "no object was ever visible: nothing but NaN compared"
+
+
+def test_forecast_before_every_step_leaves_the_episode_alone(envs):
+    """an episode of 12 steps with a forecast before every step against its twin without: observations, rewards and dones identical;
+    H' shrinks towards the episode's end; no step left, no forecast"""
+    from ssa_gym_amd.envs.vector_env import SSA_Tasker_VecEnv
+    cfg = _vec_cfg(envs)
+    E, S, m = 3, 3, 8
+    vec = SSA_Tasker_VecEnv(cfg, E, seed=10)
+    twin = SSA_Tasker_VecEnv(cfg, E, seed=10)
+    twin._eng.z_noise.copy_(vec._eng.z_noise)
+    rs = np.random.RandomState(4)
+    horizons = []
+    for k in range(11):
+        states = [r.get_state()[2] for r in vec._rng]
+        r = vec.forecast_sensors(4, covariances=bool(k % 2))
+        horizons.append(r["status"].shape[1])
+        assert r["score"].shape == (E, min(4, 11 - k), S, m, 3)
+        assert states == [g.get_state()[2] for g in vec._rng] and np.all(vec.i == k) and vec.tick == k
+        acts = _actions(rs, E, S, m)
+        oa, ra, da, _ = vec.step(acts)
+        ob, rb, db, _ = twin.step(acts)
+        assert np.array_equal(oa.view(np.int64), ob.view(np.int64)) and np.array_equal(ra, rb) and np.array_equal(da, db), k
+        for e in range(E):
+            for nme in ("x_true", "x_filter", "P_filter"):
+                assert np.array_equal(bits(getattr(vec, nme)(e)), bits(getattr(twin, nme)(e))), (k, e, nme)
+    assert horizons == [4] * 8 + [3, 2, 1] and da.all() and np.all(vec.i == 0)      # (step 11 ended the episode: the envs were reset in place)
+    assert vec.forecast_sensors(10)["status"].shape == (E, 10, S, m)
+    saved = vec.i.copy()
+    vec.i[1] = vec.n - 1                                                        # (an env on its last index: no next step)
+    with pytest.raises(ValueError, match="no next step"):
+        vec.forecast_sensors(3)
+    vec.i[1] = vec.n - 2
+    assert vec.forecast_sensors(3)["status"].shape == (E, 1, S, m)              # (one H' for all envs: the shortest)
+    vec.i[:] = saved
+    with pytest.raises(ValueError, match="horizon"):
+        vec.forecast_sensors(0)
+
+
+def test_vector_env_without_observers_slab_0_equals_lookahead(envs):
+    from ssa_gym_amd.envs.vector_env import SSA_Tasker_VecEnv
+    for E in (3, 9):
+        vec = SSA_Tasker_VecEnv(_vec_cfg(envs, sensors=0), E, seed=10)
+        rs = np.random.RandomState(2)
+        for _ in range(3):
+            vec.step(rs.randint(0, 8, size=E))
+        fc = _np_env(vec.forecast_sensors(3, covariances=True))
+        one = _np_env(vec.lookahead(covariances=True))
+        assert fc["score"].shape == (E, 3, 1, 8, 3) and np.isfinite(one["score"]).any()
+        assert np.array_equal(bits(fc["score"][:, 0, 0]), bits(one["score"].transpose(0, 2, 1)))
+        for name in ("status", "visible", "P_post"):
+            assert np.array_equal(bits(fc[name][:, 0, 0]), bits(one[name])), (E, name)
+        for name in ("x_prior", "P_prior"):
+            assert np.array_equal(bits(fc[name][:, 0]), bits(one[name])), (E, name)
+
+
+def test_forecast_nine_envs_equal_eight(envs):
+    """time words by value (8 envs) against from memory (9 envs), on the envs they share"""
+    from ssa_gym_amd.envs.vector_env import SSA_Tasker_VecEnv
+    cfg = _vec_cfg(envs)
+    a = SSA_Tasker_VecEnv(cfg, 8, seed=20)
+    b = SSA_Tasker_VecEnv(cfg, 9, seed=20)
+    assert a._inline and not b._inline
+    b._eng.z_noise[:8].copy_(a._eng.z_noise)                      # (b draws for 9 envs from one generator: the shared envs take a's draws)
+    rs = np.random.RandomState(6)
+    for k in range(4):
+        fa, fb = _np_env(a.forecast_sensors(4, covariances=True)), _np_env(b.forecast_sensors(4, covariances=True))
+        assert np.isfinite(fa["score"]).any()
+        for name in fa:
+            assert np.array_equal(bits(fa[name]), bits(fb[name][:8])), (k, name)
+        acts = _actions(rs, 9, 3, 8)
+        a.step(acts[:8])
+        b.step(acts)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the planners
+@pytest.mark.parametrize("sky", ["default", "open"])
+def test_vector_planners_follow_the_rule(envs, sky):
+    """the device part against the single envs' _plan_assigned per env and against the numpy restatement on the read-back forecast;
+    m = 8 objects against H' S = 12 entries: every env's pool is smaller than its plan"""
+    from ssa_gym_amd import _lib, agents
+    from ssa_gym_amd.envs.vector_env import SSA_Tasker_VecEnv
+    cfg = (_open_sky if sky == "open" else _vec_cfg)(envs)
+    E, S, m, H = 3, 3, 8, 4
+    vec = SSA_Tasker_VecEnv(cfg, E, seed=10)
+    singles = single_envs(envs, cfg, vec, 10)
+    vec.single_action_space.seed(1)
+    rs = np.random.RandomState(8)
+    for _ in range(2):
+        acts = _actions(rs, E, S, m)
+        vec.step(acts)
+        for e in range(E):
+            singles[e].step(acts[e])
+    states = [r.get_state()[2] for r in vec._rng]
+    fc = _np_env(vec.forecast_sensors(H))
+    table = vec._eng.action_table().clone()
+    for planner, col in ((agents.plan_info_gain_sensors, _lib.LOOK_INFO_GAIN), (agents.plan_trace_gain_sensors, _lib.LOOK_TRACE_GAIN)):
+        raw = agents._plan_assigned_envs(vec, H, col)
+        assert raw.shape == (E, H, S) and raw.dtype == np.int64
+        want = plan_np(fc["score"][..., col])
+        assert np.array_equal(raw, want), (sky, col, raw, want)
+        for e in range(E):
+            one = agents._plan_assigned(singles[e], H, col)
+            assert np.array_equal(raw[e], one), (sky, col, e, raw[e], one)
+            got = raw[e][raw[e] >= 0]
+            assert len(set(got.tolist())) == len(got), (e, raw[e])             # no object twice per env
+        assert (raw == -1).any()                                               # (12 entries, 8 objects)
+        if sky == "open":
+            assert all((raw[e] >= 0).sum() >= 6 for e in range(E)), raw
+        plan = planner(vec, H)
+        assert plan.dtype == np.int64 and plan.shape == (E, H, S)
+        assert np.array_equal(plan[want >= 0], want[want >= 0])
+        assert ((plan >= 0) & (plan < m)).all() and all(len(set(r.tolist())) == S for env in plan for r in env)
+    assert states == [r.get_state()[2] for r in vec._rng]                      # (the envs' own generators are not touched)
+    assert _same_tensor(table, vec._eng.action_table())                           # (nor the engine's action table)
+    for h in range(H):                                                         # plan[:, h] is what vec.step() takes at step h
+        vec.step(plan[:, h])
+    assert np.all(vec.i == 2 + H)
+
+
+def test_forecast_against_execution(envs):
+    """the plan executed by vec.step(plan[:, h]): every planned update that was taken leaves the forecast's P_post -- an object's
+    trajectory depends on no other object, and a plan observes each object of an env once"""
+    from ssa_gym_amd import _lib, agents
+    from ssa_gym_amd.envs.vector_env import SSA_Tasker_VecEnv
+    E, S, m, H = 3, 3, 8, 4
+    vec = SSA_Tasker_VecEnv(_open_sky(envs), E, seed=10)
+    vec.single_action_space.seed(3)
+    rs = np.random.RandomState(6)
+    for _ in range(2):
+        vec.step(_actions(rs, E, S, m))
+    fc = _np_env(vec.forecast_sensors(H, covariances=True))
+    raw = agents._plan_assigned_envs(vec, H, _lib.LOOK_INFO_GAIN)
+    plan = agents._fill_plan_envs(vec, raw)
+    taken = 0
+    for h in range(H):
+        _, _, done, _ = vec.step(plan[:, h])
+        assert not done.any()
+        status = vec._eng.status.cpu().numpy().reshape(E, m)
+        for e in range(E):
+            Pf = vec.P_filter(e)
+            for s in range(S):
+                j = int(raw[e, h, s])
+                if j < 0:                                                      # (a fill-in: nothing the forecast counted on)
+                    continue
+                assert fc["status"][e, h, s, j] == _lib.ST_OK and fc["visible"][e, h, s, j] == 1, (e, h, s, j)
+                if status[e, j] != _lib.ST_OK:                                 # (an update that failed on the drawn noise: not foreseen)
+                    continue
+                assert np.array_equal(bits(Pf[j]), bits(fc["P_post"][e, h, s, j])), (e, h, s, j)
+                taken += 1
+    print("[vector forecast vs execution] %d planned updates taken and compared" % taken)
+    assert taken >= 2 * E * S                                                  # (the first two steps of every env's plan at least)
