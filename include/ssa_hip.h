@@ -628,6 +628,30 @@ typedef struct ssa_rollout_sensors_params {
 } ssa_rollout_sensors_params;
 int ssa_env_rollout_sensors_f64(const ssa_consts *c_host, const ssa_step_params *first, const ssa_rollout_params *r,
                                 const ssa_sensor_params *sites, const ssa_rollout_sensors_params *rs, void *stream);
+/* ... in each of E envs, one launch: exactly the K launches ssa_env_step_sensors_envs_f64 would make for the rows actions[k], with every
+ * output bit-identical to them: the ring slots (slot_out + k) mod H of x_true, x, P, obs and metrics (H = 2: the two slots alternate),
+ * `status`, the failure log and count, the statistics and the update records of EVERY step (stats_out, upd_out -- whatever H is), and
+ * the statistics ring's slots of the last min(K, H) steps as ssa_env_rollout_f64 leaves them -- with each wavefront's objects resident
+ * in LDS across the steps.  The sites are shared by all envs; env e's time index at step k is env_time[e] + time_offset + k (the time
+ * words come from memory: launch_mask is not honoured); the noise is per (env, sensor, time) as in ssa_env_step_sensors_envs_f64;
+ * obj_ids is honoured per env.
+ *   actions  : [K][E][SSA_MAX_SENSORS] device words, 32-byte aligned, read-only for the launch.  Row (k, e) = the objects of env e's
+ *              sensors at step k in env e's own numbering; entries s >= n_sensor are ignored; < 0 or >= n_obj: idle; two sensors of one
+ *              env on one object: the lowest-numbered one updates it.
+ *   stats_out: [K][E][SSA_STAT_STRIDE], required: the statistics of every step (np.argmax of sigma_pos included when r->spos_tiles is given).
+ *   upd_out  : [K][E][S][SSA_UPD_STRIDE] or NULL: every step's per-sensor update records (every step owns its block).
+ * `first` and `r` are read as ssa_env_rollout_sensors_f64 reads them (r->actions and r->upd_ring are not read).  Two launches: the
+ * rollout and the fold of the per-step statistics.
+ * Refused before any launch: every refusal of ssa_env_rollout_sensors_f64 but its n_env one; SSA_LAUNCH_INLINE_ENVS in launch_mask,
+ * n_env * n_obj >= 2^31, NULL or misaligned `actions`, NULL `stats_out` (SSA_E_INVALID); several envs with n_obj % 4 != 0
+ * (SSA_E_UNSUPPORTED: whole tiles per env).  n_env == 1 is accepted for any n_obj and runs the same kernel. */
+typedef struct ssa_rollout_sensors_envs_params {
+    const int32_t *actions;   /* [K][E][SSA_MAX_SENSORS] device words */
+    double *stats_out;        /* [K][E][SSA_STAT_STRIDE] */
+    double *upd_out;          /* [K][E][S][SSA_UPD_STRIDE] or NULL */
+} ssa_rollout_sensors_envs_params;
+int ssa_env_rollout_sensors_envs_f64(const ssa_consts *c_host, const ssa_step_params *first, const ssa_rollout_params *r,
+                                     const ssa_sensor_params *sites, const ssa_rollout_sensors_envs_params *re, void *stream);
 
 /* ---------------------------------------------------------------- the tasking forecast of a sensor network: H lookaheads in one launch
  * From the state ssa_lookahead_sensors_f64 reads (ssa_step_params inputs: slot i, time index time_offset), for h = 0 .. H-1 what

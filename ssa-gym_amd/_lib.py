@@ -77,6 +77,10 @@ class ssa_rollout_sensors_params(C.Structure):
     _fields_ = [("actions", c_dp), ("upd_ring", c_dp)]
 
 
+class ssa_rollout_sensors_envs_params(C.Structure):
+    _fields_ = [("actions", c_dp), ("stats_out", c_dp), ("upd_out", c_dp)]
+
+
 class ssa_sensor_envs_params(C.Structure):
     _fields_ = [("actions", c_dp), ("upd", c_dp), ("inline_action", (C.c_int32 * 8) * 8)]
 
@@ -147,6 +151,8 @@ SIGNATURES = {
                                                 C.POINTER(ssa_forecast_params), c_dp]),
     "ssa_env_rollout_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_rollout_params),
                                               C.POINTER(ssa_sensor_params), C.POINTER(ssa_rollout_sensors_params), c_dp]),
+    "ssa_env_rollout_sensors_envs_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_rollout_params),
+                                                   C.POINTER(ssa_sensor_params), C.POINTER(ssa_rollout_sensors_envs_params), c_dp]),
     "ssa_closed_loop_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
     "ssa_env_step_work_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
     "ssa_reward_stats_f64": (C.c_int, [c_dp, c_dp, c_dp, c_dp, C.c_int64, C.c_int32, c_dp]),

@@ -168,7 +168,7 @@ def agent_trace_gain_sensors(obs, env):         # one object per sensor, greedy 
 # is planned at most once per plan.  Everything in-stream, one read-back at the end.  No device fallback row: a sensor the scores leave
 # without an object comes back -1 and is filled here by _assign_lookahead_sensors' rule.
 # On a vector env (SSA_Tasker_VecEnv) the same two planners return [E, H', S] -- plan[:, h] is what vec.step()
-# takes at step h: ONE forecast launch for all envs (ssa_forecast_sensors_envs_f64), then per step ONE assignment launch for all envs
+# takes at step h, and the whole plan is what vec.rollout_sensors() takes (section 8l): ONE forecast launch for all envs (ssa_forecast_sensors_envs_f64), then per step ONE assignment launch for all envs
 # on the contiguous slab h, each env's earlier picks removed from its own part of the slab; one read-back, the -1 entries filled per
 # env, envs ascending, from single_action_space.
 def _fill_plan(env, plan):
@@ -246,6 +246,8 @@ def _plan_lookahead_sensors(env, horizon, k):
 
 def plan_info_gain_sensors(env, horizon):       # a schedule [H', S] for env.rollout_sensors() ([E, H', S] of a vector env): greedy over
                                                 # 1/2 ln(det P- / det P+) per step
+    """A single env runs the plan with env.rollout_sensors(plan); a vector env's plan [E, H', S] runs with vec.rollout_sensors(plan)
+    (DESIGN.md section 8l): one launch per chunk, stopping after the first step at which any env is done."""
     return _plan_lookahead_sensors(env, horizon, _lib.LOOK_INFO_GAIN)
 
 

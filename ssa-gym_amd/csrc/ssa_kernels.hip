@@ -1176,6 +1176,32 @@ struct ActSensorEnvs : ActBase {
     SSA_DEV int action(const ssa_sensor_params*, int k) const { return row[k]; }
     SSA_DEV double* records(const ssa_sensor_params*) const { return upd; }
 };
+// ActScheduleEnvs (rollout_sensor_envs_kernel, ssa_env_rollout_sensors_envs_f64): ActSchedule in each of E envs, as ActSensorEnvs is
+// ActSensors in each of them -- step kk of a schedule on a resident tile whose env is a scalar.  enter() forms the tile's env once per
+// tile and step; row (kk, env) of the schedule is one scalar load of eight words through the constant address space, and the records
+// of (kk, env) are a block of their own: every step owns its block, so every step writes it.  What `sensors` and `envs` put into
+// process_wave holds for it unchanged; the time word comes from memory (a resident tile's steps do not see SSA_LAUNCH_INLINE_ENVS).
+struct ActScheduleEnvs : ActBase {
+    static constexpr bool sensors = true, envs = true;
+    const ssa_sensor_params* s;
+    const ssa_rollout_sensors_envs_params* v;   // (in the kernel's argument block, as `s`)
+    int kk;                            // the step
+    int env;                           // the tile's env
+    ConstPtr<int32_t> row;             // ... its action words at step kk
+    double* upd;                       // ... its records of step kk, or null
+    SSA_DEV const ssa_sensor_params* sites() const { return s; }
+    SSA_DEV void enter(uint32_t, int n_env, int64_t n_obj, int64_t base)
+    {
+        env = (n_env > 1) ? __builtin_amdgcn_readfirstlane((int)((uint32_t)base / (uint32_t)n_obj)) : 0;
+        const int64_t ke = (int64_t)kk * n_env + env;
+        row = (ConstPtr<int32_t>)v->actions + ke * SSA_MAX_SENSORS;
+        upd = v->upd_out ? v->upd_out + ke * s->n_sensor * SSA_UPD_STRIDE : nullptr;
+    }
+    typedef int row_t __attribute__((ext_vector_type(SSA_MAX_SENSORS)));
+    SSA_DEV row_t actions(const ssa_sensor_params*) const { return *(ConstPtr<row_t>)__builtin_assume_aligned(row, sizeof(row_t)); }
+    SSA_DEV int action(const ssa_sensor_params*, int k) const { return row[k]; }
+    SSA_DEV double* records(const ssa_sensor_params*) const { return upd; }
+};
 // the sensor that updates the object the caller calls `jid`: the lowest-numbered one whose action it is, -1 for none
 template <class ACT>
 SSA_DEV int sensor_index(const ACT& a, const ssa_sensor_params* s, int64_t jid)
@@ -2614,6 +2640,26 @@ SSA_DEV ActForecastSensorEnvs roll_act(ForePlan, const VecForeSensK& ka, ssa_ste
     return ActForecastSensorEnvs{{}, &ka.f.out, &ka.s, h, ka.k.p.n_env, 0};   // (process_wave enters the tile's env)
 }
 SSA_RESIDENT_KERNEL(forecast_sensor_envs_kernel, VecForeSensK)
+// A sensor network's schedule in each of several envs (ssa_env_rollout_sensors_envs_f64): the fifth resident-tile kernel, and the
+// second combination of two existing halves -- the ring and the per-step block of the rollouts (roll_act's template as it stands)
+// with the tile's env as a scalar (ActScheduleEnvs).  The tiles walk all E * m rows of the ring, whole tiles per env with several
+// envs (the launcher); the block's type selects the overloads.
+struct VecRollSensK {
+    RollK k;
+    ssa_sensor_params s;
+    ssa_rollout_sensors_envs_params v;
+};
+SSA_DEV const RollK& roll_of(const VecRollSensK& a) { return a.k; }
+SSA_DEV const StepK& step_of(const VecRollSensK& a) { return a.k.k; }
+SSA_DEV Ring roll_plan(const VecRollSensK& a) { return ring_of(a.k, a.k.k.p.n_env); }
+SSA_DEV ssa_step_params roll_source(const VecRollSensK& a, const Ring& g) { return roll_source(a.k, g); }
+SSA_DEV ActScheduleEnvs ring_act(const VecRollSensK& a, ssa_step_params& pk, int kk, int, bool)
+{
+    pk.upd = nullptr;       // (the envs' action words and records are not read, as in the network's step)
+    pk.actions = nullptr;
+    return ActScheduleEnvs{{}, &a.s, &a.v, kk, 0, nullptr, nullptr};   // (process_wave enters the tile's env)
+}
+SSA_RESIDENT_KERNEL(rollout_sensor_envs_kernel, VecRollSensK)
 #undef SSA_RESIDENT_KERNEL
 // grid (n_steps, n_env): folds step k's shard set into the statistics slot of step k -- when that slot still
 // belongs to step k at the end of the rollout (the last `history` steps) -- and clears it
@@ -2626,6 +2672,24 @@ __global__ void __launch_bounds__(64) rollout_fold_kernel(unsigned long long* __
     double* dst = (kk >= n_steps - history) ? stats_ring + (int64_t)so * n_env * SSA_STAT_STRIDE : nullptr;
     fold_stat_shards(shards + (int64_t)kk * n_env * SSA_STAT_SHARDS * SSA_STAT_SHARD_WORDS, dst, e, threadIdx.x,
                      spos ? spos + (int64_t)kk * ntiles * 2 : nullptr, n_obj);
+}
+// ... and for ssa_env_rollout_sensors_envs_f64, same grid: step k's shard set folded into stats_out[k] -- every step's statistics,
+// whatever the history -- and copied into the statistics ring's slot where step k still owns it at the end (lane 0 wrote every word of
+// the block: it copies what it wrote)
+__global__ void __launch_bounds__(64) rollout_fold_steps_kernel(unsigned long long* __restrict__ shards, double* stats_out, double* stats_ring,
+                                                                int n_env, int n_steps, int slot_out, int history,
+                                                                const unsigned long long* __restrict__ spos, int64_t n_obj, int64_t ntiles)
+{
+    const int kk = blockIdx.x, e = blockIdx.y;
+    double* dst = stats_out + (int64_t)kk * n_env * SSA_STAT_STRIDE;
+    fold_stat_shards(shards + (int64_t)kk * n_env * SSA_STAT_SHARDS * SSA_STAT_SHARD_WORDS, dst, e, threadIdx.x,
+                     spos ? spos + (int64_t)kk * ntiles * 2 : nullptr, n_obj);
+    if (threadIdx.x == 0 && kk >= n_steps - history) {
+        const unsigned long long* w = reinterpret_cast<const unsigned long long*>(dst + (int64_t)e * SSA_STAT_STRIDE);
+        unsigned long long* ring = reinterpret_cast<unsigned long long*>(stats_ring + ((int64_t)((slot_out + kk) % history) * n_env + e) * SSA_STAT_STRIDE);
+#pragma unroll
+        for (int q = 0; q < SSA_STAT_STRIDE; ++q) ring[q] = w[q];
+    }
 }
 
 // Post kernel, grid (nparts, n_env) x 256 threads, launched when a payload or the exact statistics are wanted:
@@ -4452,7 +4516,8 @@ int ssa_forecast_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p,
 }
 // the checks and the argument block shared by ssa_env_rollout_f64 and ssa_env_rollout_sensors_f64 (sens: r->actions is not read); SSA_OK or
 // the refusal
-static int rollout_args(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, bool sens, RollK& rk)
+// (ids_per_env: the kernel honours obj_ids per env -- whole tiles per env, the caller's check)
+static int rollout_args(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, bool sens, RollK& rk, bool ids_per_env = false)
 {
     if (!c || !p || !r || p->n_obj <= 0 || p->n_env <= 0 || r->n_steps < 1 || r->history < 2) return SSA_E_INVALID;
     if (r->slot_out < 0 || r->slot_out >= r->history) return SSA_E_INVALID;
@@ -4469,7 +4534,7 @@ static int rollout_args(const ssa_consts* c, const ssa_step_params* p, const ssa
     rk.k.p.aer_out = nullptr;
     rk.k.p.spos_tiles = nullptr;
     rk.k.p.spos_tiles_prev = nullptr;
-    if (p->obj_ids && p->n_env != 1) return SSA_E_UNSUPPORTED;
+    if (p->obj_ids && p->n_env != 1 && !ids_per_env) return SSA_E_UNSUPPORTED;
     rk.r = *r;
     return SSA_OK;
 }
@@ -4509,6 +4574,31 @@ int ssa_env_rollout_sensors_f64(const ssa_consts* c, const ssa_step_params* p, c
     hipStream_t s = (hipStream_t)stream;
     with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(rollout_sensors_kernel<P>, dim3(g.nwork), dim3(64), 0, s, rk, (int)g.ntiles, g.nwork); });
     return rollout_fold(p, r, g.ntiles, s);
+}
+int ssa_env_rollout_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, const ssa_sensor_params* sp,
+                                     const ssa_rollout_sensors_envs_params* re, void* stream)
+{
+    if (!c || !p || !r || !sp || !re) return SSA_E_INVALID;
+    VecRollSensK rk;
+    const int rc = rollout_args(c, p, r, true, rk.k, true);
+    if (rc != SSA_OK) return rc;
+    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
+    for (int q = 0; q < sp->n_sensor; ++q)
+        if (!(sp->obs_limit[q] == sp->obs_limit[q])) return SSA_E_INVALID;
+    if (!noise_stride_ok(sp)) return SSA_E_INVALID;
+    if (p->launch_mask & SSA_LAUNCH_INLINE_ENVS) return SSA_E_INVALID;   // (a resident tile's steps read the time words from memory)
+    if (p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // whole tiles per env: a tile's env is wave-uniform
+    if (!re->actions || ((uintptr_t)re->actions % (SSA_MAX_SENSORS * sizeof(int32_t))) != 0 || !re->stats_out) return SSA_E_INVALID;
+    rk.k.r.actions = nullptr;    // (the envs' action words and record ring are not read)
+    rk.k.r.upd_ring = nullptr;
+    rk.s = idle_sites(sp);       // (the schedule's rows and the per-step records take their place)
+    rk.v = *re;
+    const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
+    hipStream_t s = (hipStream_t)stream;
+    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(rollout_sensor_envs_kernel<P>, dim3(g.nwork), dim3(64), 0, s, rk, (int)g.ntiles, g.nwork); });
+    hipLaunchKernelGGL(rollout_fold_steps_kernel, dim3(r->n_steps, p->n_env), dim3(64), 0, s, (unsigned long long*)r->stat_shards, re->stats_out,
+                       r->stats_ring, p->n_env, r->n_steps, r->slot_out, r->history, (const unsigned long long*)r->spos_tiles, p->n_obj, g.ntiles);
+    return launch_status();
 }
 int64_t ssa_closed_loop_workspace_bytes(int64_t n_obj, int32_t n_env)
 {

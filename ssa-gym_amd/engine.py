@@ -108,6 +108,7 @@ class HotPathEngine:
         # allocated by the first launch that needs them:
         self._roll_shards = self._roll_spos = None      # per-step shard sets and arg-max slots of a rollout (_rollout_params)
         self._roll_sched = self.upd_sensors = None      # launch_rollout_sensors: its schedule (kept until the next launch), its record ring
+        self._roll_envs_out = None      # launch_rollout_sensors_envs: its per-step statistics and records (grown as _roll_shards is)
         self._loop_ws = self._agent_ws = None           # workspaces of launch_closed_loop (with loop_error) and launch_agent_select
         self._look = self._look_s = None                # output buffers of launch_lookahead / launch_lookahead_sensors
         self._fore = None                               # ... and of launch_forecast_sensors
@@ -704,7 +705,7 @@ class HotPathEngine:
             raise _lib.SsaHipError("ssa_env_rollout_f64 failed with code %d" % rc)
 
     def _rollout_params(self, slot_in, time_offset, K, argmax_spos, s):
-        """what launch_rollout and launch_rollout_sensors share: pending statistics folded, the ssa_rollout_params block of K steps from
+        """what launch_rollout, launch_rollout_sensors and launch_rollout_sensors_envs share: pending statistics folded, the ssa_rollout_params block of K steps from
         history slot `slot_in` (rings, per-step shard sets and -- argmax_spos -- arg-max slots; actions and record ring left to the
         caller) and self._p made the parameter block of the first step"""
         self.flush_stats(s)
@@ -759,6 +760,41 @@ class HotPathEngine:
         rc = self._lib.ssa_env_rollout_sensors_f64(self._cref, self._pref, C.byref(r), C.byref(sensors), C.byref(rs), s)
         if rc:
             raise _lib.SsaHipError("ssa_env_rollout_sensors_f64 failed with code %d" % rc)
+
+    def launch_rollout_sensors_envs(self, slot_in, time_offset, sensors, actions, stream=None, argmax_spos=False, records=False):
+        """launch_rollout_sensors in EVERY env of the engine (include/ssa_hip.h: ssa_env_rollout_sensors_envs_f64): the K = actions.shape[0]
+        launches launch_step_sensors_envs would make for the rows actions[k], in one launch and bit-identical to them -- step k reads
+        history slot (slot_in + k) % H, writes (slot_in + k + 1) % H, and env e's time index is env_time0[e] + time_offset + k.
+        `sensors`: host.make_sensor_params(), the sites all envs share; `actions`: a contiguous CUDA int32 tensor [K, E, S] or
+        [K, E, MAX_SENSORS] (row (k, e) = the objects of env e's sensors at step k; < 0 or >= n_obj: idle; two sensors of one env on one
+        object: the lower one updates it), kept alive until the next launch.  Returns (stats [K, E, STAT_STRIDE], upd
+        [K, E, S, UPD_STRIDE] or None without `records`): device tensors of the engine's own -- every step's statistics and per-sensor
+        update records whatever H is --, reused (and rewritten) by the next call.  Several envs need n_obj % 4 == 0.  Asynchronous, no
+        host sync."""
+        S = int(sensors.n_sensor)
+        if not (isinstance(actions, torch.Tensor) and actions.is_cuda and actions.dtype == torch.int32 and actions.is_contiguous()
+                and actions.dim() == 3 and actions.shape[1] == self.E and actions.shape[2] in (S, _lib.MAX_SENSORS) and actions.shape[0] >= 1):
+            raise _lib.SsaHipError("rollout: actions must be a contiguous CUDA int32 tensor [K][%d][%d] or [K][%d][%d]"
+                                   % (self.E, S, self.E, _lib.MAX_SENSORS))
+        if self.E > 1 and self.m % 4:
+            raise _lib.SsaHipError("a sensor network in several envs needs n_obj % 4 == 0 (whole tiles per env)")
+        self._check_sensor_noise(sensors, envs=True)
+        if actions.shape[2] != _lib.MAX_SENSORS:      # (the ABI's row stride: one aligned 32-byte read per tile and step)
+            actions = torch.nn.functional.pad(actions, (0, _lib.MAX_SENSORS - S), value=-1)
+        self._roll_sched = actions      # (kept until the next launch: the kernel reads it whatever stream it runs in)
+        K = int(actions.shape[0])
+        out = self._roll_envs_out
+        if out is None or out[0].shape[0] < K or out[1].shape[2] != S or (records and out[1].shape[0] < K):
+            out = self._roll_envs_out = (torch.zeros((K, self.E, _lib.STAT_STRIDE), dtype=f64, device=self.dev),
+                                         torch.zeros((K if records else 0, self.E, S, _lib.UPD_STRIDE), dtype=f64, device=self.dev))
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        r = self._rollout_params(slot_in, time_offset, K, argmax_spos, s)
+        re = _lib.ssa_rollout_sensors_envs_params()
+        re.actions, re.stats_out, re.upd_out = actions.data_ptr(), out[0].data_ptr(), out[1].data_ptr() if records else 0
+        rc = self._lib.ssa_env_rollout_sensors_envs_f64(self._cref, self._pref, C.byref(r), C.byref(sensors), C.byref(re), s)
+        if rc:
+            raise _lib.SsaHipError("ssa_env_rollout_sensors_envs_f64 failed with code %d" % rc)
+        return out[0][:K], (out[1][:K] if records else None)
 
     def launch_closed_loop(self, slot_in, time_offset, kind, actions, stats_out, upd_out=None, fallback=None, picks=None, stream=None,
                            argmax_spos=False, wait_ticks=0, debug_withhold=False):

@@ -22,6 +22,10 @@ host in between.  agents.agent_info_gain_sensors / agent_trace_gain_sensors take
 Ahead of the step: `forecast_sensors(horizon)` is every sensor's lookahead at each of the next H' steps of every
 env from ONE launch (ssa_forecast_sensors_envs_f64) -- the action masks, the covariance growth and the gains of the steps to come, read
 only; agents.plan_info_gain_sensors / plan_trace_gain_sensors take a vector env and return the greedy plan [E, H', S].
+
+A schedule: `rollout_sensors(actions [E, K, S])` runs such a plan -- or any fixed tasking schedule -- as the K
+step() calls would, in one launch per chunk with the envs' state resident on chip (ssa_env_rollout_sensors_envs_f64); `rollout([E, K])`
+is the same without a network.
 """
 import numpy as np
 
@@ -78,7 +82,51 @@ def shaped_hit(actions, argmax_prev):
     return (a == prev) if a.ndim == 1 else np.any(a == prev[:, None], axis=1)
 
 
+def book_rollout(reward_type, stats, actions, rewards_sum, argmax_prev, i, m, n):
+    """The bookkeeping of a chunk of a vector rollout, as C consecutive step() calls would do it: stats [C, E, STAT_STRIDE] (every
+    step's statistics), actions [C, E, S] (the rows the chunk ran), rewards_sum / argmax_prev / i [E] (what the episodes have paid,
+    np.argmax(sigma_pos) of the step before, the envs' step indices -- all in front of the chunk), m objects, n steps per episode.
+    Step k has the index i + k + 1 and is an episode's last when i + k + 2 >= n; the 'shaped' hit of step k is against the arg-max of
+    step k - 1 (stats[k - 1], argmax_prev for k = 0) and its win pays 1 - (the rewards summed up to k - 1).  The chunk is kept up to
+    and including the first step at which ANY env is done.  Returns (rewards [E, keep], dones [E, keep], rewards_sum, argmax_prev,
+    keep), the sums and arg-maxes behind step keep - 1; the inputs are not written.  Needs no device."""
+    st = np.asarray(stats)
+    paid = np.array(rewards_sum, dtype=np.float64)
+    prev = np.array(argmax_prev, dtype=np.int64)
+    i = np.asarray(i, dtype=np.int64)
+    shaped = reward_type == 'shaped'
+    rewards, dones = [], []
+    for k in range(st.shape[0]):
+        hit = shaped_hit(actions[k], prev) if shaped else False
+        r, d = reward_done(reward_type, st[k], hit, paid, i + k + 2 >= n, m, n)
+        paid = paid + r
+        if shaped:
+            prev = st[k][:, _lib.STAT_ARGMAX_SPOS].astype(np.int64)
+        rewards.append(np.asarray(r, dtype=np.float64))
+        dones.append(np.asarray(d, dtype=bool))
+        if dones[-1].any():
+            break
+    return np.stack(rewards, axis=1), np.stack(dones, axis=1), paid, prev, len(rewards)
+
+
+def check_schedule(actions, E, S, m, name="rollout_sensors"):
+    """the [E, K, S] schedule of a vector rollout as int64: any other shape or dtype is a ValueError naming the shape, and every
+    actions[:, k] is checked as step() checks its table (check_sensor_actions), the error naming step k.  Needs no device state."""
+    a = np.asarray(actions)
+    if a.ndim != 3 or a.shape[0] != E or a.shape[2] != S or a.shape[1] < 1 or a.dtype.kind not in "iu":
+        raise ValueError("%s: actions must be an integer array of shape (%d, K, %d) (envs x steps x sensors), K >= 1, got shape %s (%s)"
+                         % (name, E, S, a.shape, a.dtype))
+    for k in range(a.shape[1]):
+        try:
+            check_sensor_actions(a[:, k], E, S, m)
+        except (AssertionError, ValueError) as err:
+            raise type(err)("%s: step %d: %s" % (name, k, err)) from None
+    return a.astype(np.int64)
+
+
 class SSA_Tasker_VecEnv:
+    ROLLOUT_CHUNK = 64      # rollout_sensors(): at most this many steps per launch
+
     def __init__(self, config, num_envs, seed=0):
         import torch
         from .. import engine
@@ -318,6 +366,80 @@ class SSA_Tasker_VecEnv:
             obs = self._obs(sout, reset=(self.obs_returned == 'aer') or bool(self._layout))
         # (ssa_tasker_simple_2.py:365-367 passes the reward of the other modes through nan_to_num(nan=.5, inf=.5): the rewards formed above are
         # finite by construction -- counts of comparisons, constants -- so there is nothing for it to replace)
+        return obs, rewards, dones, infos
+
+    def rollout(self, actions):
+        """rollout_sensors() for a vector env without config['observers']: `actions` integer [E, K], one object per env and step."""
+        if self.n_sensor > 1:
+            raise NotImplementedError("rollout: not implemented for a sensor network in a vector env (config['observers'] with %d "
+                                      "sensors); use rollout_sensors" % self.n_sensor)
+        a = np.asarray(actions)
+        if a.ndim != 2:
+            raise ValueError("rollout: actions must be an integer array of shape (%d, K) (envs x steps), got shape %s" % (self.E, a.shape))
+        return self.rollout_sensors(a[..., None])
+
+    def rollout_sensors(self, actions):
+        """A K-step tasking schedule of every env in one launch per chunk (ssa_env_rollout_sensors_envs_f64):
+        `actions` integer [E, K, S] -- a plan of agents.plan_info_gain_sensors as it comes; S = 1 without config['observers'], the
+        envs' own observer as a one-site network -- applied as the consecutive step(actions[:, k]) calls would be, state, rewards and
+        bookkeeping bit for bit.  Stops after the first step at which ANY env is done; the envs done there auto-reset as step() resets
+        them, and the caller goes on with actions[:, K':] in a new call.  Returns (obs, rewards [E, K'], dones [E, K'], infos): obs and
+        infos what the last executed step() would have returned.  ValueError: a schedule of the wrong shape or dtype, an env without
+        a next step, several envs with rso_count % 4 != 0; a bad row raises what step() raises, naming its step.
+        At most ROLLOUT_CHUNK steps per launch and never more than the fewest steps an env has left, so the time limit ends a chunk;
+        one copy of the time words and one synchronisation per chunk.  'jones' and 'shaped' can end an episode inside a chunk: the chunk
+        then starts from a snapshot, and is launched again up to that step (the launch is deterministic)."""
+        import torch
+        S, E = self.n_sensor, self.E
+        a = check_schedule(actions, E, S, self.m)
+        if np.any(self.i + 1 >= self.n):
+            raise ValueError("rollout_sensors: an env has no next step")
+        if E > 1 and self.m % 4:
+            raise ValueError("rollout_sensors: several envs need rso_count % 4 == 0 (whole tiles per env), got " + str(self.m))
+        e = self._eng
+        if e is None:
+            raise _lib.SsaHipError("no device state: a rollout runs on the GPU only (no CPU fallback)")
+        shaped = self.reward_type == 'shaped'
+        if shaped and not e.supports_argmax:
+            raise ValueError("rollout_sensors: the 'shaped' reward needs rso_count % 4 == 0 (every step's arg-max of sigma_pos)")
+        undo = self.reward_type in ('jones', 'shaped')      # (a win or a loss may turn up inside a chunk)
+        rows = np.ascontiguousarray(a.transpose(1, 0, 2))   # [K, E, S]
+        sched = torch.from_numpy(rows.astype(np.int32)).to("cuda")
+        sites = self._sites()
+        K, k0 = rows.shape[0], 0
+        rewards, dones = [], []
+        while k0 < K:
+            C = min(int(self.ROLLOUT_CHUNK), K - k0, int((self.n - 1 - self.i).min()))
+            sin = self.tick % 2
+            snap = e.snapshot_state(sin) if (undo and C > 1) else None
+            e.env_time0.copy_(torch.as_tensor(self.i + 1, dtype=torch.int32))      # (a synchronous copy: the pinned staging is the step's)
+            st = e.launch_rollout_sensors_envs(sin, 0, sites, sched[k0:k0 + C], argmax_spos=shaped)[0].cpu().numpy()
+            r, d, paid, prev, keep = book_rollout(self.reward_type, st, rows[k0:k0 + C], self.rewards_sum, self._argmax_prev, self.i,
+                                                  self.m, self.n)
+            if keep < C:      # the device ran past a done: the same rows again from the snapshot, up to that step -- the same bits
+                e.restore_state(sin, snap)
+                e.launch_rollout_sensors_envs(sin, 0, sites, sched[k0:k0 + keep], argmax_spos=shaped)
+                torch.cuda.current_stream().synchronize()
+            self.i += keep
+            self.tick += keep
+            self.rewards_sum[:] = paid
+            self._argmax_prev = prev
+            rewards.append(r)
+            dones.append(d)
+            k0 += keep
+            if d[:, -1].any():
+                break
+        rewards, dones = np.concatenate(rewards, axis=1), np.concatenate(dones, axis=1)
+        slot, last = self.tick % 2, dones[:, -1]
+        obs = self._obs(slot, reset=True)      # (the path a reset's observation takes: the step kernel's host-mapped destinations are not used)
+        infos = [{} for _ in range(E)]
+        if last.any():
+            for d in np.where(last)[0]:
+                infos[d]['terminal_observation'] = obs[d].clone() if self._obs_device else obs[d].copy()
+                self._reset_env(int(d), slot)
+            st_dev = e.stats[slot].cpu().numpy()
+            self._argmax_prev[last] = st_dev[last, _lib.STAT_ARGMAX_SPOS].astype(np.int64)
+            obs = self._obs(slot, reset=True)
         return obs, rewards, dones, infos
 
     def lookahead(self, covariances=False):
