@@ -4217,15 +4217,27 @@ static TileGrid tile_grid(int64_t total)
     g.arg = g.per_wave != 1 ? (int)g.ntiles : (int)(total / OBJ_PER_WAVE);
     return g;
 }
-// the checks of a sensor network's sites that its step and its lookahead share; SSA_OK or the refusal
-static int sensors_ok(const ssa_sensor_params* sp, const ssa_step_params* p)
+// ---- the argument rules the entries share, each written once.  An entry calls them in ITS order: the order decides the code of a block
+// that breaks two rules, and it differs between siblings (tests/test_refusal_order_host.py pins it).
+// several envs without whole tiles per env (a tile's env is wave-uniform); a * b * c rows below 2^31 (they are addressed with 32 bits); a
+// row of SSA_MAX_SENSORS action words, there and aligned to its 32 bytes; no more envs by value than SSA_LAUNCH_INLINE_ENVS carries
+static bool ragged_envs(int64_t n_obj, int32_t n_env) { return n_env > 1 && (n_obj % OBJ_PER_WAVE) != 0; }
+static bool ragged_envs(const ssa_step_params* p) { return ragged_envs(p->n_obj, p->n_env); }
+static bool rows_fit(int64_t a, int64_t b, int64_t c = 1) { return a * b * c < ((int64_t)1 << 31); }
+static bool row_aligned(const int32_t* row) { return row && ((uintptr_t)row % (SSA_MAX_SENSORS * sizeof(int32_t))) == 0; }
+static bool inline_envs_fit(const ssa_step_params* p) { return !(p->launch_mask & SSA_LAUNCH_INLINE_ENVS) || p->n_env <= SSA_INLINE_ENVS; }
+// a network's sites: 1..SSA_MAX_SENSORS of them, no NaN elevation mask; SSA_OK or the refusal.  `between`: a refusal of the caller's
+// that ranks behind the count and before the masks
+static int sites_ok(const ssa_sensor_params* sp, int between = SSA_OK)
 {
     if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
-    if (p->n_env != 1) return SSA_E_UNSUPPORTED;
+    if (between != SSA_OK) return between;
     for (int k = 0; k < sp->n_sensor; ++k)
         if (!(sp->obs_limit[k] == sp->obs_limit[k])) return SSA_E_INVALID;
     return SSA_OK;
 }
+// ... of the one-env entries: several envs are the *_envs entries'
+static int sensors_ok(const ssa_sensor_params* sp, const ssa_step_params* p) { return sites_ok(sp, p->n_env != 1 ? SSA_E_UNSUPPORTED : SSA_OK); }
 // ... and of the sensors' own noise tables, where the measurement noise is read
 static bool noise_stride_ok(const ssa_sensor_params* sp)
 {
@@ -4251,7 +4263,7 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
         return SSA_E_INVALID;
     if (sens) {   // (the actions are the sensors'; the env's action word and record are not read)
     } else if (p->launch_mask & SSA_LAUNCH_INLINE_ENVS) {
-        if (p->n_env > SSA_INLINE_ENVS || (p->launch_mask & SSA_LAUNCH_INLINE_ACTION)) return SSA_E_INVALID;
+        if (!inline_envs_fit(p) || (p->launch_mask & SSA_LAUNCH_INLINE_ACTION)) return SSA_E_INVALID;
     } else if (p->launch_mask & SSA_LAUNCH_INLINE_ACTION) {
         if (p->n_env != 1) return SSA_E_INVALID;
     } else if (!p->actions) return SSA_E_INVALID;
@@ -4262,16 +4274,15 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     if ((p->launch_mask & SSA_LAUNCH_MIRROR_F32) && !p->stat_shards) return SSA_E_UNSUPPORTED;   // (the post kernel writes aer_out in double)
     // (the statistics of the one-launch paths: the post kernel's arg-max would speak storage positions; several envs: one table row per env,
     // indices within the env, whole tiles per env)
-    if (p->obj_ids && (!p->stat_shards || (p->n_env != 1 && (p->n_obj % OBJ_PER_WAVE) != 0))) return SSA_E_UNSUPPORTED;
-    if ((p->spos_tiles || p->spos_tiles_prev) && p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // whole tiles per env
+    if (p->obj_ids && (!p->stat_shards || ragged_envs(p))) return SSA_E_UNSUPPORTED;
+    if ((p->spos_tiles || p->spos_tiles_prev) && ragged_envs(p)) return SSA_E_UNSUPPORTED;
     if (!consts_ok(c)) return SSA_E_INVALID;
     if (p->aer_cols != 0 && p->aer_cols != 1 && p->aer_cols != 4) return SSA_E_INVALID;
     StepK k;
     k.c = *c;
     k.p = *p;
-    const int64_t total = (int64_t)p->n_env * p->n_obj;
-    if (total >= ((int64_t)1 << 31)) return SSA_E_INVALID;
-    const TileGrid g = tile_grid(total);
+    if (!rows_fit(p->n_env, p->n_obj)) return SSA_E_INVALID;
+    const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     const bool fast_stats = p->stat_shards != nullptr;   // statistics by the common-path kernel's atomics
     const bool defer = fast_stats && (p->launch_mask & SSA_LAUNCH_DEFER_FOLD);
     if (defer && p->stat_shards_prev && (!p->stats_prev || p->stat_shards_prev == p->stat_shards)) return SSA_E_INVALID;
@@ -4357,16 +4368,10 @@ int ssa_env_step_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p,
                                   const ssa_sensor_envs_params* envs, void* stream)
 {
     if (!c || !p || !sp || !envs) return SSA_E_INVALID;
-    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
-    for (int k = 0; k < sp->n_sensor; ++k)
-        if (!(sp->obs_limit[k] == sp->obs_limit[k])) return SSA_E_INVALID;
-    if (!noise_stride_ok(sp)) return SSA_E_INVALID;
-    if (p->launch_mask & SSA_LAUNCH_INLINE_ACTION) return SSA_E_INVALID;
-    if (p->launch_mask & SSA_LAUNCH_INLINE_ENVS) {
-        if (p->n_env > SSA_INLINE_ENVS) return SSA_E_INVALID;
-    } else if (!envs->actions || ((uintptr_t)envs->actions & 31u)) return SSA_E_INVALID;
-    if (p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // whole tiles per env: a tile's env is wave-uniform
-    if (p->launch_mask & SSA_LAUNCH_STATS_FROM_METRICS) return SSA_E_UNSUPPORTED;
+    if (sites_ok(sp) != SSA_OK || !noise_stride_ok(sp)) return SSA_E_INVALID;
+    if ((p->launch_mask & SSA_LAUNCH_INLINE_ACTION) || !inline_envs_fit(p)) return SSA_E_INVALID;
+    if (!(p->launch_mask & SSA_LAUNCH_INLINE_ENVS) && !row_aligned(envs->actions)) return SSA_E_INVALID;   // (by value: not read)
+    if (ragged_envs(p) || (p->launch_mask & SSA_LAUNCH_STATS_FROM_METRICS)) return SSA_E_UNSUPPORTED;
     return step_launch(c, p, stream, nullptr, nullptr, sp, envs);
 }
 // dispatch-timestamp event pairs, created on first use (a ring, so that back-to-back launches can be timed
@@ -4395,11 +4400,9 @@ static int lookahead_args(const ssa_consts* c, const ssa_step_params* p, const s
     if (!c || !p || !o || p->n_obj <= 0 || p->n_env <= 0) return SSA_E_INVALID;
     if (!p->x_true_in || !p->x_in || !p->P_in || !p->status || !p->trans || !p->env_time) return SSA_E_INVALID;
     if (!o->score || !o->status || !o->visible) return SSA_E_INVALID;
-    if ((p->launch_mask & SSA_LAUNCH_INLINE_ENVS) && p->n_env > SSA_INLINE_ENVS) return SSA_E_INVALID;
-    if (p->obj_ids && p->n_env != 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // (whole tiles per env, as the step)
-    if (!consts_ok(c)) return SSA_E_INVALID;
-    const int64_t total = (int64_t)p->n_env * p->n_obj;
-    if (total >= ((int64_t)1 << 31)) return SSA_E_INVALID;
+    if (!inline_envs_fit(p)) return SSA_E_INVALID;
+    if (p->obj_ids && ragged_envs(p)) return SSA_E_UNSUPPORTED;   // (as the step)
+    if (!consts_ok(c) || !rows_fit(p->n_env, p->n_obj)) return SSA_E_INVALID;
     k.k.c = *c;
     k.k.p = *p;
     k.o = *o;
@@ -4427,16 +4430,18 @@ int ssa_lookahead_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_l
     });
     return launch_status();
 }
-// ... and by ssa_lookahead_sensors_f64 and ssa_forecast_sensors_f64 on top of it: the network's checks, and its sites in `sites`
+// ... and by a network's lookahead and forecast entries on top of it: the network's checks, and its sites in `sites`
+// (envs: the *_envs entries -- several envs, whole tiles each)
 static int lookahead_sensors_args(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_lookahead_out* o,
-                                  LookK& k, ssa_sensor_params& sites)
+                                  bool envs, LookK& k, ssa_sensor_params& sites)
 {
     if (!c || !p || !sp || !o) return SSA_E_INVALID;
-    int rc = sensors_ok(sp, p);
+    int rc = envs ? sites_ok(sp) : sensors_ok(sp, p);
     if (rc != SSA_OK) return rc;
     rc = lookahead_args(c, p, o, k);
     if (rc != SSA_OK) return rc;
-    if ((int64_t)sp->n_sensor * p->n_obj >= ((int64_t)1 << 31)) return SSA_E_INVALID;
+    if (!rows_fit(p->n_env, sp->n_sensor, p->n_obj)) return SSA_E_INVALID;
+    if (ragged_envs(p)) return SSA_E_UNSUPPORTED;
     sites = idle_sites(sp);
     return SSA_OK;
 }
@@ -4444,7 +4449,7 @@ int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, con
                               void* stream)
 {
     LookSensK k;
-    const int rc = lookahead_sensors_args(c, p, sp, o, k.k, k.s);
+    const int rc = lookahead_sensors_args(c, p, sp, o, false, k.k, k.s);
     if (rc != SSA_OK) return rc;
     const TileGrid g = tile_grid(p->n_obj);
     dim3 grid((unsigned)g.nwork), block(64);
@@ -4457,16 +4462,9 @@ int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, con
 int ssa_lookahead_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_lookahead_out* o,
                                    void* stream)
 {
-    if (!c || !p || !sp || !o) return SSA_E_INVALID;
-    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
-    for (int k = 0; k < sp->n_sensor; ++k)
-        if (!(sp->obs_limit[k] == sp->obs_limit[k])) return SSA_E_INVALID;
     VecLookSensK k;
-    const int rc = lookahead_args(c, p, o, k.k);
+    const int rc = lookahead_sensors_args(c, p, sp, o, true, k.k, k.s);
     if (rc != SSA_OK) return rc;
-    if ((int64_t)p->n_env * sp->n_sensor * p->n_obj >= ((int64_t)1 << 31)) return SSA_E_INVALID;
-    if (p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // whole tiles per env: a tile's env is wave-uniform
-    k.s = idle_sites(sp);
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     dim3 grid((unsigned)g.nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
@@ -4481,7 +4479,7 @@ int ssa_forecast_sensors_f64(const ssa_consts* c, const ssa_step_params* p, cons
     if (!f) return SSA_E_INVALID;
     LookK lk;
     ForeSensK k;
-    const int rc = lookahead_sensors_args(c, p, sp, &f->out, lk, k.s);
+    const int rc = lookahead_sensors_args(c, p, sp, &f->out, false, lk, k.s);
     if (rc != SSA_OK) return rc;
     if (f->n_steps < 1) return SSA_E_INVALID;
     k.k = lk.k;
@@ -4495,19 +4493,13 @@ int ssa_forecast_sensors_f64(const ssa_consts* c, const ssa_step_params* p, cons
 int ssa_forecast_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_forecast_params* f,
                                   void* stream)
 {
-    if (!c || !p || !sp || !f) return SSA_E_INVALID;
-    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
-    for (int q = 0; q < sp->n_sensor; ++q)
-        if (!(sp->obs_limit[q] == sp->obs_limit[q])) return SSA_E_INVALID;
+    if (!f) return SSA_E_INVALID;
     LookK lk;
-    const int rc = lookahead_args(c, p, &f->out, lk);
-    if (rc != SSA_OK) return rc;
-    if ((int64_t)p->n_env * sp->n_sensor * p->n_obj >= ((int64_t)1 << 31)) return SSA_E_INVALID;
-    if (p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // whole tiles per env: a tile's env is wave-uniform
-    if (f->n_steps < 1) return SSA_E_INVALID;
     VecForeSensK k;
+    const int rc = lookahead_sensors_args(c, p, sp, &f->out, true, lk, k.s);
+    if (rc != SSA_OK) return rc;
+    if (f->n_steps < 1) return SSA_E_INVALID;
     k.k = lk.k;   // (launch_mask: SSA_LAUNCH_INLINE_ENVS alone survives lookahead_args, and the kernel reads inline_time by it)
-    k.s = idle_sites(sp);
     k.f = *f;
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     hipStream_t s = (hipStream_t)stream;
@@ -4526,9 +4518,8 @@ static int rollout_args(const ssa_consts* c, const ssa_step_params* p, const ssa
         return SSA_E_INVALID;
     if (!p->status || !p->trans || !p->env_time || !p->z_noise) return SSA_E_INVALID;
     if (!consts_ok(c)) return SSA_E_INVALID;
-    const int64_t total = (int64_t)p->n_env * p->n_obj;
-    if (total >= ((int64_t)1 << 31)) return SSA_E_INVALID;
-    if (r->spos_tiles && p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;
+    if (!rows_fit(p->n_env, p->n_obj)) return SSA_E_INVALID;
+    if (r->spos_tiles && ragged_envs(p)) return SSA_E_UNSUPPORTED;
     rk.k.c = *c;
     rk.k.p = *p;
     rk.k.p.aer_out = nullptr;
@@ -4555,20 +4546,32 @@ int ssa_env_rollout_f64(const ssa_consts* c, const ssa_step_params* p, const ssa
     with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(rollout_kernel<P>, dim3(g.nwork), dim3(64), 0, s, rk, (int)g.ntiles, g.nwork); });
     return rollout_fold(p, r, g.ntiles, s);
 }
+// ... and by a network's two rollout entries on top of it: the network's checks, the schedule's rows (`actions`) in place of the env's
+// action words and record ring, and its sites in `sites` (envs: ssa_env_rollout_sensors_envs_f64 -- several envs, whole tiles each)
+static int rollout_sensors_args(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, const ssa_sensor_params* sp,
+                                const int32_t* actions, bool envs, RollK& rk, ssa_sensor_params& sites)
+{
+    if (!c || !p || !r || !sp) return SSA_E_INVALID;
+    int rc = rollout_args(c, p, r, true, rk, envs);
+    if (rc != SSA_OK) return rc;
+    rc = envs ? sites_ok(sp) : sensors_ok(sp, p);
+    if (rc != SSA_OK) return rc;
+    if (!noise_stride_ok(sp)) return SSA_E_INVALID;
+    if (envs && (p->launch_mask & SSA_LAUNCH_INLINE_ENVS)) return SSA_E_INVALID;   // (a resident tile's steps read the time words from memory)
+    if (ragged_envs(p)) return SSA_E_UNSUPPORTED;
+    if (!row_aligned(actions)) return SSA_E_INVALID;
+    rk.r.actions = nullptr;
+    rk.r.upd_ring = nullptr;
+    sites = idle_sites(sp);
+    return SSA_OK;
+}
 int ssa_env_rollout_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, const ssa_sensor_params* sp,
                                 const ssa_rollout_sensors_params* rs, void* stream)
 {
-    if (!c || !p || !r || !sp || !rs) return SSA_E_INVALID;
+    if (!rs) return SSA_E_INVALID;
     RollSensK rk;
-    int rc = rollout_args(c, p, r, true, rk.k);
+    const int rc = rollout_sensors_args(c, p, r, sp, rs->actions, false, rk.k, rk.s);
     if (rc != SSA_OK) return rc;
-    rc = sensors_ok(sp, p);
-    if (rc != SSA_OK) return rc;
-    if (!noise_stride_ok(sp)) return SSA_E_INVALID;
-    if (!rs->actions || ((uintptr_t)rs->actions % (SSA_MAX_SENSORS * sizeof(int32_t))) != 0) return SSA_E_INVALID;
-    rk.k.r.actions = nullptr;    // (the env's action words and record ring are not read)
-    rk.k.r.upd_ring = nullptr;
-    rk.s = idle_sites(sp);       // (the schedule's rows and the record ring take their place)
     rk.rs = *rs;
     const TileGrid g = tile_grid(p->n_obj);
     hipStream_t s = (hipStream_t)stream;
@@ -4578,20 +4581,11 @@ int ssa_env_rollout_sensors_f64(const ssa_consts* c, const ssa_step_params* p, c
 int ssa_env_rollout_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_rollout_params* r, const ssa_sensor_params* sp,
                                      const ssa_rollout_sensors_envs_params* re, void* stream)
 {
-    if (!c || !p || !r || !sp || !re) return SSA_E_INVALID;
+    if (!re) return SSA_E_INVALID;
     VecRollSensK rk;
-    const int rc = rollout_args(c, p, r, true, rk.k, true);
+    const int rc = rollout_sensors_args(c, p, r, sp, re->actions, true, rk.k, rk.s);
     if (rc != SSA_OK) return rc;
-    if (sp->n_sensor < 1 || sp->n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
-    for (int q = 0; q < sp->n_sensor; ++q)
-        if (!(sp->obs_limit[q] == sp->obs_limit[q])) return SSA_E_INVALID;
-    if (!noise_stride_ok(sp)) return SSA_E_INVALID;
-    if (p->launch_mask & SSA_LAUNCH_INLINE_ENVS) return SSA_E_INVALID;   // (a resident tile's steps read the time words from memory)
-    if (p->n_env > 1 && (p->n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;   // whole tiles per env: a tile's env is wave-uniform
-    if (!re->actions || ((uintptr_t)re->actions % (SSA_MAX_SENSORS * sizeof(int32_t))) != 0 || !re->stats_out) return SSA_E_INVALID;
-    rk.k.r.actions = nullptr;    // (the envs' action words and record ring are not read)
-    rk.k.r.upd_ring = nullptr;
-    rk.s = idle_sites(sp);       // (the schedule's rows and the per-step records take their place)
+    if (!re->stats_out) return SSA_E_INVALID;
     rk.v = *re;
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     hipStream_t s = (hipStream_t)stream;
@@ -4677,7 +4671,7 @@ int ssa_stats_fold_f64(uint64_t* stat_shards, double* stats, int32_t n_env, void
 int ssa_stats_fold_spos_f64(uint64_t* stat_shards, const uint64_t* spos_tiles, double* stats, int64_t n_obj, int32_t n_env, void* stream)
 {
     if (!stat_shards || !stats || n_env <= 0 || n_obj <= 0) return SSA_E_INVALID;
-    if (spos_tiles && n_env > 1 && (n_obj % OBJ_PER_WAVE) != 0) return SSA_E_UNSUPPORTED;
+    if (spos_tiles && ragged_envs(n_obj, n_env)) return SSA_E_UNSUPPORTED;
     hipLaunchKernelGGL(reward_fold_kernel, dim3(n_env), dim3(64), 0, (hipStream_t)stream, (unsigned long long*)stat_shards, stats,
                        (const unsigned long long*)spos_tiles, n_obj);
     return launch_status();

@@ -14,7 +14,7 @@ import pytest
 
 import oracle as orc
 from conftest import ROOT, golden
-from support.codeobj import _kernels, header, stray_scratch
+from support.codeobj import KERNEL_FAMILIES, _kernels, family, header, stray_scratch
 from support.gpu import pkg  # noqa: F401  (the module fixture)
 
 
@@ -183,6 +183,12 @@ def test_step_kernels_keep_their_register_budget(tmp_path):
             assert kern[name]["private_segment_fixed_size"] == 0 and kern[name]["vgpr_spill_count"] == 0, (name, kern[name])
         checked += 1
     assert checked == 16
+
+
+def test_kernel_families_have_their_instance_counts(tmp_path):
+    """the families the host tests count kernels by, read exactly from the mangled names: each has the instances its table says"""
+    kern, _ = _kernels(tmp_path)
+    assert {name: len(family(kern, name)) for name in KERNEL_FAMILIES} == KERNEL_FAMILIES
 
 
 def test_acceleration_tokens_and_covariance_form_resolve_on_the_host(pkg):

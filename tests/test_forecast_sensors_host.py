@@ -11,8 +11,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from support.codeobj import _kernels, header, stray_scratch
+from support.codeobj import KERNEL_FAMILIES, _kernels, assert_family_budget, header
 from support.gpu import lib  # noqa: F401  (the module fixture)
+from support.refusals import LOOK_PTRS, OUT_PTRS, bad_rk4, nan_mask, refused
 from support.sensors import _bare_env
 
 
@@ -46,57 +47,22 @@ def test_forecast_params_layout_matches_the_header(lib, tmp_path):
     assert [int(v) for v in subprocess.check_output([str(exe)]).decode().split()] == want
 
 
-def _valid_blocks():
-    """blocks that pass every check (the pointers are never dereferenced on the host: a refusal comes before any launch) -- each case
-    below spoils exactly one field"""
-    from ssa_gym_amd import _lib, host
-    c = host.make_consts(np.eye(6), np.eye(3), 1e-4, 2.0, -3, 20.0, -np.pi / 2, np.array([0.6, -1.3, 20.0]))
-    p, sp, f = _lib.ssa_step_params(), _lib.ssa_sensor_params(), _lib.ssa_forecast_params()
-    p.n_obj, p.n_env = 8, 1
-    p.x_true_in = p.x_in = p.P_in = p.status = p.trans = p.env_time = 0x1000
-    sp.n_sensor = 2
-    f.n_steps = 3
-    f.out.score = f.out.status = f.out.visible = 0x1000
-    return c, p, sp, f
-
-
 def test_forecast_refuses_bad_arguments_before_any_launch(lib):
     """every refusal of ssa_lookahead_sensors_f64, n_steps < 1 and a NULL required output: each with its code and nothing launched (no
     device is touched: this runs without a GPU).  Every case spoils ONE field of blocks that are otherwise complete."""
     from ssa_gym_amd import _lib
     fn = lib.ssa_forecast_sensors_f64
-
-    def call(spoil=None, null=None):
-        c, p, sp, f = _valid_blocks()
-        if spoil:
-            spoil(c, p, sp, f)
-        args = [C.byref(c), C.byref(p), C.byref(sp), C.byref(f)]
-        if null is not None:
-            args[null] = None
-        return fn(*args, None)
-
-    def setter(which, name, value):
-        def spoil(c, p, sp, f):
-            setattr(dict(c=c, p=p, sp=sp, f=f, o=f.out)[which], name, value)
-        return spoil
     for k in range(4):                                                     # NULL blocks
-        assert call(null=k) == _lib.E_INVALID, k
+        assert refused(fn, None, null=k) == _lib.E_INVALID, k
     invalid = [("f", "n_steps", 0), ("f", "n_steps", -2), ("p", "n_obj", 0), ("p", "n_obj", -4),
                ("c", "propagator", 7), ("c", "obs_type", 5), ("sp", "n_sensor", 0), ("sp", "n_sensor", -1), ("sp", "n_sensor", 9),
                ("p", "n_obj", (1 << 31) // 2)]                             # (S * m = 2^31 rows)
-    invalid += [("o", nm, 0) for nm in ("score", "status", "visible")]
-    invalid += [("p", nm, 0) for nm in ("x_true_in", "x_in", "P_in", "status", "trans", "env_time")]
-    for which, name, value in invalid:
-        assert call(setter(which, name, value)) == _lib.E_INVALID, (which, name, value)
-
-    def nan_mask(c, p, sp, f):
-        sp.obs_limit[1] = float("nan")
-    assert call(nan_mask) == _lib.E_INVALID
-
-    def bad_rk4(c, p, sp, f):
-        c.propagator, c.rk4_substeps = _lib.PROP_J2_RK4, 0
-    assert call(bad_rk4) == _lib.E_INVALID
-    assert call(setter("p", "n_env", 2)) == _lib.E_UNSUPPORTED
+    invalid += [("o", nm, 0) for nm in OUT_PTRS] + [("p", nm, 0) for nm in LOOK_PTRS]
+    for case in invalid:
+        assert refused(fn, None, case) == _lib.E_INVALID, case
+    assert refused(fn, None, spoil=nan_mask) == _lib.E_INVALID
+    assert refused(fn, None, spoil=bad_rk4) == _lib.E_INVALID
+    assert refused(fn, None, ("p", "n_env", 2)) == _lib.E_UNSUPPORTED
 
 
 def test_env_and_planners_raise_without_device_state():
@@ -144,22 +110,4 @@ def test_forecast_kernels_keep_the_lookahead_kernels_budget(tmp_path):
     one-tile instance of the same propagator and no more scratch or VGPR spills than it, and touch scratch only around the out-of-line
     calls (SSA_PROP_ELEMENTS / SSA_PROP_HYBRID) -- FG and J2 none at all"""
     kern, ins_of = _kernels(tmp_path)
-    new = [k for k in kern if "forecast_sensors_kernel" in k]
-    assert len(new) == 4, new
-    checked = 0
-    for name, ins in ins_of.items():
-        if "forecast_sensors_kernel" not in name:
-            continue
-        prop = re.search(r"ILi(\d)E", name).group(1)
-        ref = [k for k in kern if "lookahead_sensors_kernel" in k and "ILi%sELb0E" % prop in k]
-        assert len(ref) == 1, (name, ref)
-        k, b = kern[name], kern[ref[0]]
-        assert k["vgpr_count"] <= 96 and k["group_segment_fixed_size"] == b["group_segment_fixed_size"], (name, k, b)
-        assert k["private_segment_fixed_size"] <= b["private_segment_fixed_size"], (name, k, b)
-        assert k["vgpr_spill_count"] <= b["vgpr_spill_count"], (name, k, b)
-        calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
-        assert not stray_scratch(ins), (name, stray_scratch(ins)[:8])
-        if prop not in "03":
-            assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)
-        checked += 1
-    assert checked == 4
+    assert_family_budget(kern, ins_of, "forecast_sensors_kernel", "lookahead_sensors_kernel", KERNEL_FAMILIES["forecast_sensors_kernel"])

@@ -8,8 +8,9 @@ import subprocess
 import pytest
 
 from conftest import ROOT
-from support.codeobj import _kernels, header, stray_scratch
+from support.codeobj import KERNEL_FAMILIES, _kernels, assert_family_budget, family, header
 from support.gpu import lib  # noqa: F401  (the module fixture)
+from support.refusals import LOOK_PTRS, OUT_PTRS, refused
 
 
 def test_lookahead_is_exported_and_declared(lib):
@@ -42,13 +43,14 @@ def test_lookahead_out_layout_and_constants_match_the_header(lib, tmp_path):
 
 
 def test_lookahead_refuses_bad_arguments_before_any_launch(lib):
-    """argument checks come first: NULL blocks / required outputs are refused with SSA_E_INVALID, no device is touched"""
+    """argument checks come first: NULL blocks / inputs / required outputs are refused with SSA_E_INVALID, no device is touched"""
     from ssa_gym_amd import _lib
-    assert lib.ssa_lookahead_f64(None, None, None, None) == _lib.E_INVALID
-    c, p, o = _lib.ssa_consts(), _lib.ssa_step_params(), _lib.ssa_lookahead_out()
-    p.n_obj, p.n_env = 4, 1
-    p.x_true_in = p.x_in = p.P_in = p.status = p.trans = p.env_time = 16      # (never dereferenced: o.score is missing)
-    assert lib.ssa_lookahead_f64(C.byref(c), C.byref(p), C.byref(o), None) == _lib.E_INVALID
+    f = lib.ssa_lookahead_f64
+    assert f(None, None, None, None) == _lib.E_INVALID
+    for k in range(3):
+        assert refused(f, None, null=k) == _lib.E_INVALID, k
+    for case in [("o", nm, 0) for nm in OUT_PTRS] + [("p", nm, 0) for nm in LOOK_PTRS]:
+        assert refused(f, None, ("p", "n_obj", 4), case) == _lib.E_INVALID, case
 
 
 def test_env_lookahead_has_no_cpu_fallback(lib):
@@ -64,18 +66,6 @@ def test_lookahead_kernels_keep_the_step_kernels_budget(tmp_path):
     """the lookahead instances fit the step kernel's register budget and LDS, and touch scratch only where the step kernel does:
     the save / restore around the out-of-line calls of SSA_PROP_ELEMENTS / SSA_PROP_HYBRID -- none on the common path"""
     kern, ins_of = _kernels(tmp_path)
-    look = [k for k in kern if "lookahead_kernel" in k]
-    assert len(look) == 8, look                    # 4 propagators x {one tile, multi tile}
-    checked = 0
-    for name, ins in ins_of.items():
-        if "lookahead_kernel" not in name:
-            continue
-        k = kern[name]
-        assert k["vgpr_count"] <= 96 and k["group_segment_fixed_size"] <= 160 * 1024 // 20, (name, k)
-        calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
-        stray = stray_scratch(ins)
-        assert not stray, (name, stray[:8])
-        if "ILi0E" not in name and "ILi3E" not in name:     # FG / J2: no call, no scratch at all
-            assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)
-        checked += 1
-    assert checked == 8
+    assert_family_budget(kern, ins_of, "lookahead_kernel", None, KERNEL_FAMILIES["lookahead_kernel"])      # 4 propagators x {one tile, multi tile}
+    for name in family(kern, "lookahead_kernel"):
+        assert kern[name]["group_segment_fixed_size"] <= 160 * 1024 // 20, (name, kern[name])

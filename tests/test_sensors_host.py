@@ -10,8 +10,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from support.codeobj import _kernels, header, stray_scratch
+from support.codeobj import KERNEL_FAMILIES, _kernels, assert_family_budget, header
 from support.gpu import lib  # noqa: F401  (the module fixture)
+from support.refusals import STEP_PTRS, refused
 from support.sensors import _bare_env, sites_rad
 
 
@@ -42,27 +43,19 @@ def test_sensor_params_layout_matches_the_header(lib, tmp_path):
 
 
 def test_sensor_step_refuses_bad_arguments_before_any_launch(lib):
-    """NULL blocks, 0 or more than 8 sensors -> SSA_E_INVALID; several envs -> SSA_E_UNSUPPORTED; missing step pointers -> SSA_E_INVALID.
-    Nothing is launched (no device is touched: this runs without a GPU)."""
+    """NULL blocks, 0 or more than 8 sensors -> SSA_E_INVALID; several envs -> SSA_E_UNSUPPORTED; a missing step pointer -> SSA_E_INVALID.
+    Nothing is launched (no device is touched: this runs without a GPU).  Every case spoils ONE field of blocks that are otherwise
+    complete."""
     from ssa_gym_amd import _lib
     f = lib.ssa_env_step_sensors_f64
-    c, p, sp = _lib.ssa_consts(), _lib.ssa_step_params(), _lib.ssa_sensor_params()
-    p.n_obj, p.n_env = 8, 1
-    sp.n_sensor = 2
-    sp.zn_stride_sensor = 8 * 3
-    assert f(None, C.byref(p), C.byref(sp), None) == _lib.E_INVALID
-    assert f(C.byref(c), None, C.byref(sp), None) == _lib.E_INVALID
-    assert f(C.byref(c), C.byref(p), None, None) == _lib.E_INVALID
+    for k in range(3):                                                     # NULL blocks
+        assert refused(f, None, null=k) == _lib.E_INVALID, k
     for bad in (0, -1, 9):
-        sp.n_sensor = bad
-        assert f(C.byref(c), C.byref(p), C.byref(sp), None) == _lib.E_INVALID, bad
-    sp.n_sensor = 2
-    p.n_env = 2
-    assert f(C.byref(c), C.byref(p), C.byref(sp), None) == _lib.E_UNSUPPORTED
-    p.n_env = 1
-    assert f(C.byref(c), C.byref(p), C.byref(sp), None) == _lib.E_INVALID      # (x_true_in & co. are NULL)
-    sp.zn_stride_sensor = 0                                                     # two sensors cannot share one noise table
-    assert f(C.byref(c), C.byref(p), C.byref(sp), None) == _lib.E_INVALID
+        assert refused(f, None, ("sp", "n_sensor", bad)) == _lib.E_INVALID, bad
+    assert refused(f, None, ("p", "n_env", 2)) == _lib.E_UNSUPPORTED
+    for ptr in STEP_PTRS:
+        assert refused(f, None, ("p", ptr, 0)) == _lib.E_INVALID, ptr
+    assert refused(f, None, ("sp", "zn_stride_sensor", 0)) == _lib.E_INVALID      # two sensors cannot share one noise table
 
 
 def test_config_parser_accepts_and_refuses():
@@ -123,24 +116,7 @@ def test_sensor_kernels_keep_the_step_kernels_budget(tmp_path):
     more scratch than the step kernel of the same propagator and launch form, and touch it only around the out-of-line calls
     (SSA_PROP_ELEMENTS / SSA_PROP_HYBRID) -- FG and J2 none at all"""
     kern, ins_of = _kernels(tmp_path)
-    sens = [k for k in kern if "step_sensors_kernel" in k]
-    assert len(sens) == 8, sens
-    checked = 0
-    for name, ins in ins_of.items():
-        if "step_sensors_kernel" not in name:
-            continue
-        k = kern[name]
-        step = kern[name.replace("19step_sensors_kernel", "16step_fast_kernel").replace("NS_5SensKE", "NS_5StepKE")]
-        assert k["vgpr_count"] <= 96 and k["group_segment_fixed_size"] == step["group_segment_fixed_size"], (name, k)
-        assert k["private_segment_fixed_size"] <= step["private_segment_fixed_size"], (name, k, step)
-        assert k["vgpr_spill_count"] <= step["vgpr_spill_count"], (name, k, step)
-        calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
-        stray = stray_scratch(ins)
-        assert not stray, (name, stray[:8])
-        if "ILi0E" not in name and "ILi3E" not in name:
-            assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)
-        checked += 1
-    assert checked == 8
+    assert_family_budget(kern, ins_of, "step_sensors_kernel", "step_fast_kernel", KERNEL_FAMILIES["step_sensors_kernel"])
 
 
 # ---- the network's geometry at eight sites against the oracle's own (oracle/ssa_oracle.c: lla2ecef, ecef2aer), not the host's formulas.

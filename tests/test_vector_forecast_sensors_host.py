@@ -8,8 +8,9 @@ import re
 import numpy as np
 import pytest
 
-from support.codeobj import _kernels, header, stray_scratch
+from support.codeobj import KERNEL_FAMILIES, _kernels, assert_family_budget, header
 from support.gpu import lib  # noqa: F401  (the module fixture)
+from support.refusals import LOOK_PTRS, OUT_PTRS, bad_rk4, nan_mask, refused, valid_blocks
 from support.vector_forecast import bare_vec
 
 
@@ -25,73 +26,41 @@ def test_the_entry_is_exported_declared_and_bound(lib):
     assert re.search(r"#define\s+SSA_ABI_VERSION\s+23\b", hdr)
 
 
-def _valid_blocks():
-    """blocks that pass every check (the pointers are never dereferenced on the host: a refusal comes before any launch) -- each case
-    below spoils exactly one field, so nothing is ever launched"""
-    from ssa_gym_amd import _lib, host
-    c = host.make_consts(np.eye(6), np.eye(3), 1e-4, 2.0, -3, 20.0, -np.pi / 2, np.array([0.6, -1.3, 20.0]))
-    p, sp, f = _lib.ssa_step_params(), _lib.ssa_sensor_params(), _lib.ssa_forecast_params()
-    p.n_obj, p.n_env = 8, 2
-    for nm in ("x_true_in", "x_in", "P_in", "status", "trans", "env_time"):
-        setattr(p, nm, 0x1000)
-    sp.n_sensor = 2
-    f.n_steps = 3
-    f.out.score = f.out.status = f.out.visible = 0x1000
-    return c, p, sp, f
-
-
 def test_vector_forecast_refuses_bad_arguments_before_any_launch(lib):
     """every refusal of ssa_forecast_sensors_f64 but its n_env one, and those of ssa_lookahead_sensors_envs_f64: each with its code and
     nothing launched (no device is touched: this runs without a GPU).  Every case spoils ONE field of blocks that are otherwise
     complete."""
     from ssa_gym_amd import _lib
     fn = lib.ssa_forecast_sensors_envs_f64
-
-    def call(*fields, null=None, spoil=None):
-        c, p, sp, f = _valid_blocks()
-        for which, name, value in fields:
-            setattr(dict(c=c, p=p, sp=sp, f=f, o=f.out)[which], name, value)
-        if spoil:
-            spoil(c, p, sp, f)
-        args = [C.byref(c), C.byref(p), C.byref(sp), C.byref(f)]
-        if null is not None:
-            args[null] = None
-        return fn(*args, None)
-
     for k in range(4):                                                     # NULL blocks
-        assert call(null=k) == _lib.E_INVALID, k
+        assert refused(fn, None, null=k) == _lib.E_INVALID, k
     invalid = [("f", "n_steps", 0), ("f", "n_steps", -2), ("p", "n_obj", 0), ("p", "n_obj", -4), ("p", "n_env", 0), ("p", "n_env", -1),
                ("c", "propagator", 7), ("c", "obs_type", 5), ("sp", "n_sensor", 0), ("sp", "n_sensor", -1), ("sp", "n_sensor", 9)]
-    invalid += [("o", nm, 0) for nm in ("score", "status", "visible")]     # a NULL required output
-    invalid += [("p", nm, 0) for nm in ("x_true_in", "x_in", "P_in", "status", "trans", "env_time")]
+    invalid += [("o", nm, 0) for nm in OUT_PTRS] + [("p", nm, 0) for nm in LOOK_PTRS]      # a NULL required output, a NULL input
     for case in invalid:
-        assert call(case) == _lib.E_INVALID, case
-    assert call(spoil=lambda c, p, sp, f: sp.obs_limit.__setitem__(1, float("nan"))) == _lib.E_INVALID
-
-    def bad_rk4(c, p, sp, f):
-        c.propagator, c.rk4_substeps = _lib.PROP_J2_RK4, 0
-    assert call(spoil=bad_rk4) == _lib.E_INVALID
+        assert refused(fn, None, case) == _lib.E_INVALID, case
+    assert refused(fn, None, spoil=nan_mask) == _lib.E_INVALID
+    assert refused(fn, None, spoil=bad_rk4) == _lib.E_INVALID
     # inline envs: at most SSA_INLINE_ENVS travel by value
     assert _lib.INLINE_ENVS == 8
-    assert call(("p", "n_env", 9), ("p", "n_obj", 8), ("p", "launch_mask", _lib.LAUNCH_INLINE_ENVS)) == _lib.E_INVALID
+    assert refused(fn, None, ("p", "n_env", 9), ("p", "n_obj", 8), ("p", "launch_mask", _lib.LAUNCH_INLINE_ENVS)) == _lib.E_INVALID
     # a step's rows are 32-bit: n_env * n_obj and n_env * n_sensor * n_obj below 2^31 (whole tiles per env in all three)
-    assert call(("p", "n_obj", 1 << 30)) == _lib.E_INVALID                                      # 2 x 2^30 objects
-    assert call(("p", "n_obj", 1 << 28), ("sp", "n_sensor", 4)) == _lib.E_INVALID               # 2 x 4 x 2^28 rows
-    assert call(("p", "n_env", 1), ("p", "n_obj", 1 << 28), ("sp", "n_sensor", 8)) == _lib.E_INVALID
+    assert refused(fn, None, ("p", "n_obj", 1 << 30)) == _lib.E_INVALID                                      # 2 x 2^30 objects
+    assert refused(fn, None, ("p", "n_obj", 1 << 28), ("sp", "n_sensor", 4)) == _lib.E_INVALID               # 2 x 4 x 2^28 rows
+    assert refused(fn, None, ("p", "n_env", 1), ("p", "n_obj", 1 << 28), ("sp", "n_sensor", 8)) == _lib.E_INVALID
     # whole tiles per env
-    assert call(("p", "n_obj", 6)) == _lib.E_UNSUPPORTED                                        # n_env = 2, n_obj = 6
-    assert call(("p", "n_env", 3), ("p", "n_obj", 7)) == _lib.E_UNSUPPORTED
-    assert call(("p", "n_obj", 6), ("p", "obj_ids", 0x1000)) == _lib.E_UNSUPPORTED
+    assert refused(fn, None, ("p", "n_obj", 6)) == _lib.E_UNSUPPORTED                                        # n_env = 2, n_obj = 6
+    assert refused(fn, None, ("p", "n_env", 3), ("p", "n_obj", 7)) == _lib.E_UNSUPPORTED
+    assert refused(fn, None, ("p", "n_obj", 6), ("p", "obj_ids", 0x1000)) == _lib.E_UNSUPPORTED
     # n_env == 1 takes any n_obj: what is refused for these blocks is one of the forecast's own checks
-    assert call(("p", "n_env", 1), ("p", "n_obj", 7), ("f", "n_steps", 0)) == _lib.E_INVALID
-    assert call(("p", "n_env", 1), ("p", "n_obj", 7), ("o", "score", 0)) == _lib.E_INVALID
+    assert refused(fn, None, ("p", "n_env", 1), ("p", "n_obj", 7), ("f", "n_steps", 0)) == _lib.E_INVALID
+    assert refused(fn, None, ("p", "n_env", 1), ("p", "n_obj", 7), ("o", "score", 0)) == _lib.E_INVALID
 
 
 def test_one_env_forecast_still_refuses_several_envs(lib):
     from ssa_gym_amd import _lib
-    c, p, sp, f = _valid_blocks()
-    assert p.n_env == 2
-    assert lib.ssa_forecast_sensors_f64(C.byref(c), C.byref(p), C.byref(sp), C.byref(f), None) == _lib.E_UNSUPPORTED
+    fn = lib.ssa_forecast_sensors_f64
+    assert refused(fn, valid_blocks(fn.__name__, n_env=2)) == _lib.E_UNSUPPORTED
 
 
 def test_engine_keeps_the_one_env_refusal_and_checks_the_horizon():
@@ -157,37 +126,11 @@ def test_planner_fills_unassigned_entries_per_env_on_the_host():
         agents._fill_plan_envs(bare_vec(3, E=1, m=2), np.array([[[0, 1, -1]]]))
 
 
-COUNTED_ELSEWHERE = ("step_sensors_kernel", "rollout_sensors_kernel", "lookahead_sensors_kernel", "forecast_sensors_kernel", "lookahead_kernel",
-                     "rollout_kernel", "closed_loop_kernel", "step_fast_kernel", "vector_sensors_kernel", "assign_sensors_kernel",
-                     "lookahead_sensor_envs_kernel", "assign_sensors_envs_kernel")
-
-
 def test_new_kernels_keep_the_forecast_kernels_budget(tmp_path):
     """exactly four forecast_sensor_envs_kernel instances, none under a name another host test counts kernels by; each fits 96 VGPRs,
     uses the LDS of forecast_sensors_kernel's instance of the same propagator and no more scratch or VGPR spills than it, has its
     argument layout (ForeSensK's), and touches scratch only around the out-of-line calls (SSA_PROP_ELEMENTS / SSA_PROP_HYBRID) -- FG and
     J2 none at all"""
     kern, ins_of = _kernels(tmp_path)
-    new = [k for k in kern if "forecast_sensor_envs_kernel" in k]
-    assert len(new) == 4, new
-    for other in COUNTED_ELSEWHERE:
-        assert not any(other in k for k in new), other
-    assert len([k for k in kern if "forecast_sensors_kernel" in k]) == 4                      # (the one-env kernels are all still there)
-    checked = 0
-    for name in new:
-        ins = ins_of[name]
-        prop = re.search(r"ILi(\d)E", name).group(1)
-        ref = [k for k in kern if "forecast_sensors_kernel" in k and "ILi%sE" % prop in k]
-        assert len(ref) == 1, (name, ref)
-        k, b = kern[name], kern[ref[0]]
-        print(name, k, "against", b)
-        assert k["vgpr_count"] <= 96 and k["group_segment_fixed_size"] == b["group_segment_fixed_size"], (name, k, b)
-        assert k["private_segment_fixed_size"] <= b["private_segment_fixed_size"], (name, k, b)
-        assert k["vgpr_spill_count"] <= b["vgpr_spill_count"], (name, k, b)
-        assert k["arg_kinds"] == b["arg_kinds"] and k["by_value_offsets"] == b["by_value_offsets"], name
-        calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
-        assert not stray_scratch(ins), (name, stray_scratch(ins)[:8])
-        if prop not in "03":
-            assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)
-        checked += 1
-    assert checked == 4
+    assert_family_budget(kern, ins_of, "forecast_sensor_envs_kernel", "forecast_sensors_kernel",
+                         KERNEL_FAMILIES["forecast_sensor_envs_kernel"], same_args=True)

@@ -8,8 +8,10 @@ import re
 import numpy as np
 import pytest
 
-from support.codeobj import _kernels, header, stray_scratch
+from support.codeobj import KERNEL_FAMILIES, _kernels, assert_family_budget, family, header
 from support.gpu import lib  # noqa: F401  (the module fixture)
+from support.refusals import LOOK_PTRS, OUT_PTRS, bad_rk4, nan_mask, refused, valid_blocks
+from support.vector_forecast import bare_vec as _bare_vec
 
 NEW = ("ssa_lookahead_sensors_envs_f64", "ssa_assign_sensors_envs_f64", "ssa_assign_sensors_envs_workspace_bytes")
 
@@ -28,68 +30,37 @@ def test_the_three_entries_are_exported_declared_and_bound(lib):
     assert re.search(r"#define\s+SSA_ABI_VERSION\s+23\b", hdr)
 
 
-def _valid_blocks():
-    """blocks that pass every check (the pointers are never dereferenced on the host: a refusal comes before any launch) -- each case
-    below spoils exactly one field, so nothing is ever launched"""
-    from ssa_gym_amd import _lib, host
-    c = host.make_consts(np.eye(6), np.eye(3), 1e-4, 2.0, -3, 20.0, -np.pi / 2, np.array([0.6, -1.3, 20.0]))
-    p, sp, o = _lib.ssa_step_params(), _lib.ssa_sensor_params(), _lib.ssa_lookahead_out()
-    p.n_obj, p.n_env = 8, 2
-    for nm in ("x_true_in", "x_in", "P_in", "status", "trans", "env_time"):
-        setattr(p, nm, 0x1000)
-    sp.n_sensor = 2
-    o.score, o.status, o.visible = 0x1000, 0x1000, 0x1000
-    return c, p, sp, o
-
-
 def test_vector_lookahead_refuses_bad_arguments_before_any_launch(lib):
     """everything ssa_lookahead_sensors_f64 refuses but its n_env rule, and the entry's own: each with its code and nothing launched (no
     device is touched: this runs without a GPU).  Every case spoils ONE field of blocks that are otherwise complete."""
     from ssa_gym_amd import _lib
     fn = lib.ssa_lookahead_sensors_envs_f64
-
-    def call(*fields, null=None, spoil=None):
-        c, p, sp, o = _valid_blocks()
-        for which, name, value in fields:
-            setattr(dict(c=c, p=p, sp=sp, o=o)[which], name, value)
-        if spoil:
-            spoil(c, p, sp, o)
-        args = [C.byref(c), C.byref(p), C.byref(sp), C.byref(o)]
-        if null is not None:
-            args[null] = None
-        return fn(*args, None)
-
     for k in range(4):                                                     # NULL blocks
-        assert call(null=k) == _lib.E_INVALID, k
+        assert refused(fn, None, null=k) == _lib.E_INVALID, k
     invalid = [("p", "n_obj", 0), ("p", "n_obj", -4), ("p", "n_env", 0), ("p", "n_env", -1), ("c", "propagator", 7), ("c", "obs_type", 5),
-               ("sp", "n_sensor", 0), ("sp", "n_sensor", -1), ("sp", "n_sensor", 9),
-               ("o", "score", 0), ("o", "status", 0), ("o", "visible", 0)]
-    invalid += [("p", nm, 0) for nm in ("x_true_in", "x_in", "P_in", "status", "trans", "env_time")]
+               ("sp", "n_sensor", 0), ("sp", "n_sensor", -1), ("sp", "n_sensor", 9)]
+    invalid += [("o", nm, 0) for nm in OUT_PTRS] + [("p", nm, 0) for nm in LOOK_PTRS]
     for case in invalid:
-        assert call(case) == _lib.E_INVALID, case
-    assert call(("p", "n_env", 9), ("p", "launch_mask", _lib.LAUNCH_INLINE_ENVS)) == _lib.E_INVALID      # more envs than travel by value
-    assert call(spoil=lambda c, p, sp, o: sp.obs_limit.__setitem__(1, float("nan"))) == _lib.E_INVALID
-
-    def bad_rk4(c, p, sp, o):
-        c.propagator, c.rk4_substeps = _lib.PROP_J2_RK4, 0
-    assert call(spoil=bad_rk4) == _lib.E_INVALID
+        assert refused(fn, None, case) == _lib.E_INVALID, case
+    assert refused(fn, None, ("p", "n_env", 9), ("p", "launch_mask", _lib.LAUNCH_INLINE_ENVS)) == _lib.E_INVALID      # more envs than travel by value
+    assert refused(fn, None, spoil=nan_mask) == _lib.E_INVALID
+    assert refused(fn, None, spoil=bad_rk4) == _lib.E_INVALID
     # the output rows are 32-bit: n_env * n_obj and n_env * n_sensor * n_obj below 2^31 (whole tiles per env in both)
-    assert call(("p", "n_obj", 1 << 30)) == _lib.E_INVALID                                      # 2 x 2^30 objects
-    assert call(("p", "n_obj", 1 << 28), ("sp", "n_sensor", 4)) == _lib.E_INVALID               # 2 x 4 x 2^28 rows
-    assert call(("p", "n_env", 1), ("p", "n_obj", 1 << 28), ("sp", "n_sensor", 8)) == _lib.E_INVALID
+    assert refused(fn, None, ("p", "n_obj", 1 << 30)) == _lib.E_INVALID                                      # 2 x 2^30 objects
+    assert refused(fn, None, ("p", "n_obj", 1 << 28), ("sp", "n_sensor", 4)) == _lib.E_INVALID               # 2 x 4 x 2^28 rows
+    assert refused(fn, None, ("p", "n_env", 1), ("p", "n_obj", 1 << 28), ("sp", "n_sensor", 8)) == _lib.E_INVALID
     # whole tiles per env
-    assert call(("p", "n_obj", 6)) == _lib.E_UNSUPPORTED                                        # n_env = 2, n_obj = 6
-    assert call(("p", "n_env", 3), ("p", "n_obj", 7)) == _lib.E_UNSUPPORTED
-    assert call(("p", "n_obj", 6), ("p", "obj_ids", 0x1000)) == _lib.E_UNSUPPORTED
+    assert refused(fn, None, ("p", "n_obj", 6)) == _lib.E_UNSUPPORTED                                        # n_env = 2, n_obj = 6
+    assert refused(fn, None, ("p", "n_env", 3), ("p", "n_obj", 7)) == _lib.E_UNSUPPORTED
+    assert refused(fn, None, ("p", "n_obj", 6), ("p", "obj_ids", 0x1000)) == _lib.E_UNSUPPORTED
     # n_env == 1 takes any n_obj: what is refused for these blocks is one of the lookahead's own checks
-    assert call(("p", "n_env", 1), ("p", "n_obj", 7), ("o", "score", 0)) == _lib.E_INVALID
+    assert refused(fn, None, ("p", "n_env", 1), ("p", "n_obj", 7), ("o", "score", 0)) == _lib.E_INVALID
 
 
 def test_one_env_lookahead_still_refuses_several_envs(lib):
     from ssa_gym_amd import _lib
-    c, p, sp, o = _valid_blocks()
-    assert p.n_env == 2
-    assert lib.ssa_lookahead_sensors_f64(C.byref(c), C.byref(p), C.byref(sp), C.byref(o), None) == _lib.E_UNSUPPORTED
+    fn = lib.ssa_lookahead_sensors_f64
+    assert refused(fn, valid_blocks(fn.__name__, n_env=2)) == _lib.E_UNSUPPORTED
 
 
 def test_envs_workspace_query_is_the_one_env_query_rounded_per_env(lib):
@@ -129,18 +100,6 @@ def test_envs_assignment_refuses_bad_arguments_before_any_launch(lib):
     big = dict(n_obj=1 << 28, n_sensor=4, n_env=2)
     assert call(workspace_bytes=lib.ssa_assign_sensors_envs_workspace_bytes(1 << 28, 4, 2), **big) == _lib.E_INVALID
     assert call(n_obj=1 << 28, n_sensor=8, n_env=1, workspace_bytes=lib.ssa_assign_sensors_envs_workspace_bytes(1 << 28, 8, 1)) == _lib.E_INVALID
-
-
-def _bare_vec(S, E=3, m=8, n=12, seed=5):
-    """a vector env object without device state (what a machine without a GPU has), with just what the guards read"""
-    from ssa_gym_amd.envs._gymshim import spaces
-    from ssa_gym_amd.envs.vector_env import SSA_Tasker_VecEnv
-    vec = SSA_Tasker_VecEnv.__new__(SSA_Tasker_VecEnv)
-    vec.E, vec.num_envs, vec.m, vec.n, vec.n_sensor = E, E, m, n, S
-    vec.i, vec.tick, vec._eng = np.zeros(E, dtype=np.int64), 0, None
-    vec.single_action_space = spaces.MultiDiscrete([m] * S) if S > 1 else spaces.Discrete(m)
-    vec.single_action_space.seed(seed)
-    return vec
 
 
 def test_step_agent_guards_come_before_the_gpu_is_touched():
@@ -212,34 +171,10 @@ def test_new_kernels_keep_their_budgets(tmp_path):
     (SSA_PROP_ELEMENTS / SSA_PROP_HYBRID) -- FG and J2 none at all; assign_sensors_envs_kernel meets assign_sensors_kernel's budget: no
     scratch, no spills, at most 128 VGPRs, LDS for the table and the flag only"""
     kern, ins_of = _kernels(tmp_path)
-    new = [k for k in kern if "lookahead_sensor_envs_kernel" in k]
-    assert len(new) == 8, new
-    for other in ("step_sensors_kernel", "rollout_sensors_kernel", "lookahead_sensors_kernel", "forecast_sensors_kernel", "lookahead_kernel",
-                  "rollout_kernel", "closed_loop_kernel", "step_fast_kernel", "vector_sensors_kernel", "assign_sensors_kernel"):
-        assert not any(other in k for k in new), other                      # (the names the other host tests count kernels by)
-    checked = 0
-    for name, ins in ins_of.items():
-        if "lookahead_sensor_envs_kernel" not in name:
-            continue
-        form = re.search(r"ILi(\d)ELb([01])E", name)
-        prop = form.group(1)
-        ref = [k for k in kern if "lookahead_sensors_kernel" in k and form.group(0) in k]
-        assert len(ref) == 1, (name, ref)
-        k, b = kern[name], kern[ref[0]]
-        assert k["vgpr_count"] <= 96 and k["group_segment_fixed_size"] == b["group_segment_fixed_size"], (name, k, b)
-        assert k["private_segment_fixed_size"] <= b["private_segment_fixed_size"], (name, k, b)
-        assert k["vgpr_spill_count"] <= b["vgpr_spill_count"], (name, k, b)
-        assert k["arg_kinds"] == b["arg_kinds"] and k["by_value_offsets"] == b["by_value_offsets"], name      # (LookSensK's layout)
-        calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
-        assert not stray_scratch(ins), (name, stray_scratch(ins)[:8])
-        if prop not in "03":
-            assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)
-        checked += 1
-    assert checked == 8
-    asg = [k for k in kern if "assign_sensors_envs_kernel" in k]
-    assert len(asg) == 1 and len([k for k in kern if "assign_sensors_kernel" in k]) == 1
+    assert_family_budget(kern, ins_of, "lookahead_sensor_envs_kernel", "lookahead_sensors_kernel",
+                         KERNEL_FAMILIES["lookahead_sensor_envs_kernel"], same_args=True)      # (LookSensK's layout)
     from ssa_gym_amd import _lib
-    for name in asg + [k for k in kern if "assign_sensors_kernel" in k]:
+    for name in family(kern, "assign_sensors_envs_kernel") + family(kern, "assign_sensors_kernel"):
         k = kern[name]
         assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["vgpr_count"] <= 128, (name, k)
         assert k["group_segment_fixed_size"] == 16 * (_lib.MAX_SENSORS ** 2 + 1), (name, k)

@@ -10,8 +10,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from support.codeobj import _kernels, header, stray_scratch
+from support.codeobj import KERNEL_FAMILIES, _kernels, assert_family_budget, family, header, twin
 from support.gpu import lib  # noqa: F401  (the module fixture)
+from support.refusals import RING_PTRS, ROLL_PTRS, bad_rk4, nan_mask, refused, valid_blocks
 from support.vector_rollout import bare_vec
 
 ENTRY = "ssa_env_rollout_sensors_envs_f64"
@@ -47,84 +48,44 @@ def test_the_new_block_has_the_compilers_layout(tmp_path):
     assert got == [C.sizeof(st)] + [getattr(st, f).offset for f in names]
 
 
-def _valid_blocks():
-    """blocks that pass every check (the pointers are never dereferenced on the host: a refusal comes before any launch) -- each case
-    below spoils exactly one field, so nothing is ever launched"""
-    from ssa_gym_amd import _lib, host
-    c = host.make_consts(np.eye(6), np.eye(3), 1e-4, 2.0, -3, 20.0, -np.pi / 2, np.array([0.6, -1.3, 20.0]))
-    p, r, sp, re_ = _lib.ssa_step_params(), _lib.ssa_rollout_params(), _lib.ssa_sensor_params(), _lib.ssa_rollout_sensors_envs_params()
-    p.n_obj, p.n_env, p.n_time = 8, 2, 16
-    for nm in ("status", "trans", "env_time", "z_noise"):
-        setattr(p, nm, 0x1000)
-    r.n_steps, r.history, r.slot_out = 3, 2, 1
-    for nm in ("x_true_ring", "x_ring", "P_ring", "obs_ring", "metrics_ring", "stats_ring", "stat_shards"):
-        setattr(r, nm, 0x1000)
-    sp.n_sensor, sp.zn_stride_sensor = 2, 384
-    re_.actions, re_.stats_out = 0x1000, 0x1000
-    return c, p, r, sp, re_
-
-
-def _call(fn, *fields, null=None, spoil=None):
-    c, p, r, sp, re_ = _valid_blocks()
-    for which, name, value in fields:
-        setattr(dict(c=c, p=p, r=r, sp=sp, re=re_)[which], name, value)
-    if spoil:
-        spoil(c, p, r, sp, re_)
-    args = [C.byref(c), C.byref(p), C.byref(r), C.byref(sp), C.byref(re_)]
-    if null is not None:
-        args[null] = None
-    return fn(*args, None)
-
-
 def test_vector_rollout_refuses_bad_arguments_before_any_launch(lib):
     """every refusal of ssa_env_rollout_sensors_f64 but its n_env one, and the entry's own: each with its code and nothing launched (no
     device is touched: this runs without a GPU).  Every case spoils ONE field of blocks that are otherwise complete."""
     from ssa_gym_amd import _lib
     fn = getattr(lib, ENTRY)
-
-    def call(*fields, **kw):
-        return _call(fn, *fields, **kw)
-
     for k in range(5):                                                     # NULL blocks
-        assert call(null=k) == _lib.E_INVALID, k
+        assert refused(fn, None, null=k) == _lib.E_INVALID, k
     invalid = [("r", "n_steps", 0), ("r", "n_steps", -1), ("r", "history", 1), ("r", "slot_out", -1), ("r", "slot_out", 2),
                ("p", "n_obj", 0), ("p", "n_obj", -4), ("p", "n_env", 0), ("p", "n_env", -1), ("c", "propagator", 7), ("c", "obs_type", 5),
                ("sp", "n_sensor", 0), ("sp", "n_sensor", -1), ("sp", "n_sensor", 9), ("sp", "zn_stride_sensor", -1),
                ("sp", "zn_stride_sensor", 0)]
-    invalid += [("r", nm, 0) for nm in ("x_true_ring", "x_ring", "P_ring", "obs_ring", "metrics_ring", "stats_ring", "stat_shards")]
-    invalid += [("p", nm, 0) for nm in ("status", "trans", "env_time", "z_noise")]
+    invalid += [("r", nm, 0) for nm in RING_PTRS] + [("p", nm, 0) for nm in ROLL_PTRS]
     invalid += [("re", "actions", 0), ("re", "actions", 0x1004), ("re", "actions", 0x1010), ("re", "stats_out", 0)]
     invalid += [("p", "launch_mask", _lib.LAUNCH_INLINE_ENVS)]             # a resident tile reads the time words from memory
     for case in invalid:
-        assert call(case) == _lib.E_INVALID, case
-    assert call(spoil=lambda c, p, r, sp, re_: sp.obs_limit.__setitem__(1, float("nan"))) == _lib.E_INVALID
-
-    def bad_rk4(c, p, r, sp, re_):
-        c.propagator, c.rk4_substeps = _lib.PROP_J2_RK4, 0
-    assert call(spoil=bad_rk4) == _lib.E_INVALID
-    assert call(("p", "n_obj", 1 << 30)) == _lib.E_INVALID                                      # 2 x 2^30 objects
+        assert refused(fn, None, case) == _lib.E_INVALID, case
+    assert refused(fn, None, spoil=nan_mask) == _lib.E_INVALID
+    assert refused(fn, None, spoil=bad_rk4) == _lib.E_INVALID
+    assert refused(fn, None, ("p", "n_obj", 1 << 30)) == _lib.E_INVALID                                      # 2 x 2^30 objects
     # whole tiles per env
-    assert call(("p", "n_obj", 6)) == _lib.E_UNSUPPORTED                                        # n_env = 2, n_obj = 6
-    assert call(("p", "n_env", 3), ("p", "n_obj", 7)) == _lib.E_UNSUPPORTED
-    assert call(("p", "n_obj", 6), ("r", "spos_tiles", 0x1000)) == _lib.E_UNSUPPORTED
+    assert refused(fn, None, ("p", "n_obj", 6)) == _lib.E_UNSUPPORTED                                        # n_env = 2, n_obj = 6
+    assert refused(fn, None, ("p", "n_env", 3), ("p", "n_obj", 7)) == _lib.E_UNSUPPORTED
+    assert refused(fn, None, ("p", "n_obj", 6), ("r", "spos_tiles", 0x1000)) == _lib.E_UNSUPPORTED
     # n_env == 1 takes any n_obj, several envs take obj_ids: what is refused for these blocks is one of the entry's other checks
-    assert call(("p", "n_env", 1), ("p", "n_obj", 7), ("r", "n_steps", 0)) == _lib.E_INVALID
-    assert call(("p", "n_env", 1), ("p", "n_obj", 7), ("re", "stats_out", 0)) == _lib.E_INVALID
-    assert call(("p", "obj_ids", 0x1000), ("re", "stats_out", 0)) == _lib.E_INVALID
-    assert call(("p", "obj_ids", 0x1000), ("p", "n_obj", 6)) == _lib.E_UNSUPPORTED
-    assert call(("re", "upd_out", 0), ("re", "stats_out", 0)) == _lib.E_INVALID                 # (upd_out may be NULL; stats_out may not)
+    assert refused(fn, None, ("p", "n_env", 1), ("p", "n_obj", 7), ("r", "n_steps", 0)) == _lib.E_INVALID
+    assert refused(fn, None, ("p", "n_env", 1), ("p", "n_obj", 7), ("re", "stats_out", 0)) == _lib.E_INVALID
+    assert refused(fn, None, ("p", "obj_ids", 0x1000), ("re", "stats_out", 0)) == _lib.E_INVALID
+    assert refused(fn, None, ("p", "obj_ids", 0x1000), ("p", "n_obj", 6)) == _lib.E_UNSUPPORTED
+    assert refused(fn, None, ("re", "upd_out", 0), ("re", "stats_out", 0)) == _lib.E_INVALID                 # (upd_out may be NULL; stats_out may not)
 
 
 def test_one_env_entries_keep_their_refusals(lib):
     """ssa_env_rollout_sensors_f64 still answers SSA_E_UNSUPPORTED for two envs, and ssa_env_rollout_f64 for obj_ids with several envs"""
     from ssa_gym_amd import _lib
-    c, p, r, sp, _ = _valid_blocks()
-    rs = _lib.ssa_rollout_sensors_params()
-    rs.actions = 0x1000
-    assert p.n_env == 2
-    assert lib.ssa_env_rollout_sensors_f64(C.byref(c), C.byref(p), C.byref(r), C.byref(sp), C.byref(rs), None) == _lib.E_UNSUPPORTED
-    r.actions, p.obj_ids = 0x1000, 0x1000
-    assert lib.ssa_env_rollout_f64(C.byref(c), C.byref(p), C.byref(r), None) == _lib.E_UNSUPPORTED
+    fn = lib.ssa_env_rollout_sensors_f64
+    assert refused(fn, valid_blocks(fn.__name__, n_env=2)) == _lib.E_UNSUPPORTED
+    fn = lib.ssa_env_rollout_f64
+    assert refused(fn, valid_blocks(fn.__name__, n_env=2), ("p", "obj_ids", 0x1000)) == _lib.E_UNSUPPORTED
 
 
 def test_engine_keeps_the_one_env_refusal():
@@ -248,43 +209,14 @@ def test_booking_on_hand_made_statistics():
     assert np.array_equal(r[:, 0], r1) and np.array_equal(d[:, 0], d1)
 
 
-COUNTED_ELSEWHERE = ("step_sensors_kernel", "rollout_sensors_kernel", "lookahead_sensors_kernel", "forecast_sensors_kernel", "lookahead_kernel",
-                     "rollout_kernel", "closed_loop_kernel", "step_fast_kernel", "vector_sensors_kernel", "assign_sensors_kernel",
-                     "lookahead_sensor_envs_kernel", "assign_sensors_envs_kernel", "forecast_sensor_envs_kernel", "rollout_fold_kernel",
-                     "reward_fold_kernel")
-
-
 def test_new_kernels_keep_the_rollout_kernels_budget(tmp_path):
     """exactly four rollout_sensor_envs_kernel instances, none under a name another host test counts kernels by, and one
     rollout_fold_steps_kernel; each instance fits 96 VGPRs, uses the LDS of rollout_sensors_kernel's instance of the same propagator
     (7 296 bytes) and no more scratch or VGPR spills than rollout_kernel's (which carries n_env at run time too), and touches scratch
     only around the out-of-line calls (SSA_PROP_ELEMENTS / SSA_PROP_HYBRID) -- FG and J2 none at all"""
     kern, ins_of = _kernels(tmp_path)
-    new = [k for k in kern if "rollout_sensor_envs_kernel" in k]
-    assert len(new) == 4, new
-    fold = [k for k in kern if "rollout_fold_steps_kernel" in k]
-    assert len(fold) == 1, fold
-    for other in COUNTED_ELSEWHERE:
-        assert not any(other in k for k in new + fold), other
-    assert len([k for k in kern if "rollout_sensors_kernel" in k]) == 4 and len([k for k in kern if "rollout_kernel" in k]) == 4
-    assert len([k for k in kern if "rollout_fold_kernel" in k]) == 1
-    checked = 0
-    for name in new:
-        ins = ins_of[name]
-        prop = re.search(r"ILi(\d)E", name).group(1)
-        sens = [k for k in kern if "rollout_sensors_kernel" in k and "ILi%sE" % prop in k]
-        plain = [k for k in kern if "rollout_kernel" in k and "ILi%sE" % prop in k]
-        assert len(sens) == 1 and len(plain) == 1, (name, sens, plain)
-        k, s, b = kern[name], kern[sens[0]], kern[plain[0]]
-        print(name, k, "against", s, "and", b)
-        assert k["vgpr_count"] <= 96, (name, k)
-        assert k["group_segment_fixed_size"] == s["group_segment_fixed_size"] == 7296, (name, k, s)
-        assert k["private_segment_fixed_size"] <= b["private_segment_fixed_size"], (name, k, b)
-        assert k["vgpr_spill_count"] <= b["vgpr_spill_count"], (name, k, b)
-        assert k["arg_kinds"] == s["arg_kinds"], name
-        calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
-        assert not stray_scratch(ins), (name, stray_scratch(ins)[:8])
-        if prop not in "03":
-            assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)
-        checked += 1
-    assert checked == 4
+    assert len(family(kern, "rollout_fold_steps_kernel")) == KERNEL_FAMILIES["rollout_fold_steps_kernel"] == 1
+    assert_family_budget(kern, ins_of, "rollout_sensor_envs_kernel", "rollout_sensors_kernel", KERNEL_FAMILIES["rollout_sensor_envs_kernel"],
+                         same_args="kinds", scratch_against="rollout_kernel")
+    for name in family(kern, "rollout_sensor_envs_kernel"):
+        assert kern[twin(kern, name, "rollout_sensors_kernel")]["group_segment_fixed_size"] == 7296, name

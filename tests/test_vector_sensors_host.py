@@ -12,8 +12,9 @@ import pytest
 
 from conftest import ROOT
 from support.batches import c2t
-from support.codeobj import _kernels, header, stray_scratch
+from support.codeobj import KERNEL_FAMILIES, _kernels, assert_family_budget, header
 from support.gpu import lib  # noqa: F401  (the module fixture)
+from support.refusals import STEP_PTRS, bad_rk4, nan_mask, refused, valid_blocks
 from support.sensors import cfg3
 
 
@@ -49,80 +50,43 @@ def test_sensor_envs_params_layout_matches_the_header(lib, tmp_path):
     assert [int(v) for v in subprocess.check_output([str(exe)]).decode().split()] == want
 
 
-def _valid_blocks():
-    """blocks that pass every check (the pointers are never dereferenced on the host: a refusal comes before any launch) -- each case
-    below spoils exactly one field, so nothing is ever launched"""
-    from ssa_gym_amd import _lib, host
-    c = host.make_consts(np.eye(6), np.eye(3), 1e-4, 2.0, -3, 20.0, -np.pi / 2, np.array([0.6, -1.3, 20.0]))
-    p, sp, v = _lib.ssa_step_params(), _lib.ssa_sensor_params(), _lib.ssa_sensor_envs_params()
-    p.n_obj, p.n_env = 8, 2
-    for nm in ("x_true_in", "x_true_out", "x_in", "x_out", "P_in", "P_out", "status", "obs", "metrics", "trans", "env_time", "z_noise",
-               "stat_ws"):
-        setattr(p, nm, 0x1000)
-    sp.n_sensor, sp.zn_stride_sensor = 2, 48
-    v.actions = 0x1000
-    return c, p, sp, v
-
-
 def test_vector_sensor_step_refuses_bad_arguments_before_any_launch(lib):
     """every refusal of ssa_env_step_sensors_f64 but its n_env one, and the entry's own: each with its code and nothing launched (no device
     is touched: this runs without a GPU).  Every case spoils ONE field of blocks that are otherwise complete."""
     from ssa_gym_amd import _lib
     fn = lib.ssa_env_step_sensors_envs_f64
-
-    def call(spoil=None, null=None):
-        c, p, sp, v = _valid_blocks()
-        if spoil:
-            spoil(c, p, sp, v)
-        args = [C.byref(c), C.byref(p), C.byref(sp), C.byref(v)]
-        if null is not None:
-            args[null] = None
-        return fn(*args, None)
-
-    def setter(*fields):
-        def spoil(c, p, sp, v):
-            for which, name, value in fields:
-                setattr(dict(c=c, p=p, sp=sp, v=v)[which], name, value)
-        return spoil
     for k in range(4):                                                     # NULL blocks (`envs` among them)
-        assert call(null=k) == _lib.E_INVALID, k
+        assert refused(fn, None, null=k) == _lib.E_INVALID, k
     invalid = [("p", "n_obj", 0), ("p", "n_obj", -4), ("p", "n_env", 0), ("c", "propagator", 7), ("c", "obs_type", 5),
                ("sp", "n_sensor", 0), ("sp", "n_sensor", -1), ("sp", "n_sensor", 9), ("sp", "zn_stride_sensor", -1),
                ("sp", "zn_stride_sensor", 0), ("p", "aer_cols", 3), ("p", "n_obj", (1 << 30)),
                ("v", "actions", 0), ("v", "actions", 0x1004), ("v", "actions", 0x1010),      # NULL / misaligned rows
                ("p", "launch_mask", _lib.LAUNCH_INLINE_ACTION), ("p", "launch_mask", _lib.LAUNCH_FOLD_INSIDE),
                ("p", "spos_tiles", 0x1000), ("p", "fail_log", 0x1000)]
-    invalid += [("p", nm, 0) for nm in ("x_true_in", "x_true_out", "x_in", "x_out", "P_in", "P_out", "status", "obs", "metrics", "trans",
-                                        "env_time", "z_noise", "stat_ws")]
-    for which, name, value in invalid:
-        assert call(setter((which, name, value))) == _lib.E_INVALID, (which, name, value)
-    assert call(setter(("p", "n_env", 9), ("p", "launch_mask", _lib.LAUNCH_INLINE_ENVS))) == _lib.E_INVALID      # more envs than travel by value
-    assert call(setter(("p", "n_env", 9), ("p", "launch_mask", _lib.LAUNCH_INLINE_ENVS), ("v", "actions", 0))) == _lib.E_INVALID
-
-    def nan_mask(c, p, sp, v):
-        sp.obs_limit[1] = float("nan")
-    assert call(nan_mask) == _lib.E_INVALID
-
-    def bad_rk4(c, p, sp, v):
-        c.propagator, c.rk4_substeps = _lib.PROP_J2_RK4, 0
-    assert call(bad_rk4) == _lib.E_INVALID
+    invalid += [("p", nm, 0) for nm in STEP_PTRS]
+    for case in invalid:
+        assert refused(fn, None, case) == _lib.E_INVALID, case
+    nine = (("p", "n_env", 9), ("p", "launch_mask", _lib.LAUNCH_INLINE_ENVS))      # more envs than travel by value
+    assert refused(fn, None, *nine) == _lib.E_INVALID
+    assert refused(fn, None, *nine, ("v", "actions", 0)) == _lib.E_INVALID
+    assert refused(fn, None, spoil=nan_mask) == _lib.E_INVALID
+    assert refused(fn, None, spoil=bad_rk4) == _lib.E_INVALID
     # whole tiles per env; the statistics from the metrics rows are the plain one-env step's
-    assert call(setter(("p", "n_obj", 6))) == _lib.E_UNSUPPORTED
-    assert call(setter(("p", "n_env", 3), ("p", "n_obj", 7))) == _lib.E_UNSUPPORTED
-    assert call(setter(("p", "launch_mask", _lib.LAUNCH_STATS_FROM_METRICS))) == _lib.E_UNSUPPORTED
-    assert call(setter(("p", "launch_mask", _lib.LAUNCH_STATS_FROM_METRICS | _lib.LAUNCH_DEFER_FOLD), ("p", "stat_shards", 0x1000))) == \
-        _lib.E_UNSUPPORTED
-    assert call(setter(("p", "launch_mask", _lib.LAUNCH_MIRROR_F32))) == _lib.E_UNSUPPORTED      # (as the step: needs the one-launch statistics)
-    assert call(setter(("p", "obj_ids", 0x1000))) == _lib.E_UNSUPPORTED
+    assert refused(fn, None, ("p", "n_obj", 6)) == _lib.E_UNSUPPORTED
+    assert refused(fn, None, ("p", "n_env", 3), ("p", "n_obj", 7)) == _lib.E_UNSUPPORTED
+    assert refused(fn, None, ("p", "launch_mask", _lib.LAUNCH_STATS_FROM_METRICS)) == _lib.E_UNSUPPORTED
+    assert refused(fn, None, ("p", "launch_mask", _lib.LAUNCH_STATS_FROM_METRICS | _lib.LAUNCH_DEFER_FOLD),
+                   ("p", "stat_shards", 0x1000)) == _lib.E_UNSUPPORTED
+    assert refused(fn, None, ("p", "launch_mask", _lib.LAUNCH_MIRROR_F32)) == _lib.E_UNSUPPORTED      # (as the step: needs the one-launch statistics)
+    assert refused(fn, None, ("p", "obj_ids", 0x1000)) == _lib.E_UNSUPPORTED
     # n_env == 1 takes any n_obj: the refusal that remains for these blocks is one of the step's own
-    assert call(setter(("p", "n_env", 1), ("p", "n_obj", 7), ("p", "stat_ws", 0))) == _lib.E_INVALID
+    assert refused(fn, None, ("p", "n_env", 1), ("p", "n_obj", 7), ("p", "stat_ws", 0)) == _lib.E_INVALID
 
 
 def test_one_env_sensor_entry_still_refuses_several_envs(lib):
     from ssa_gym_amd import _lib
-    c, p, sp, _ = _valid_blocks()
-    assert p.n_env == 2
-    assert lib.ssa_env_step_sensors_f64(C.byref(c), C.byref(p), C.byref(sp), None) == _lib.E_UNSUPPORTED
+    fn = lib.ssa_env_step_sensors_f64
+    assert refused(fn, valid_blocks(fn.__name__, n_env=2)) == _lib.E_UNSUPPORTED
 
 
 def test_vector_env_refuses_ragged_envs_before_the_gpu_is_touched(lib):
@@ -177,26 +141,4 @@ def test_vector_sensor_kernels_keep_the_sensor_step_kernels_budget(tmp_path):
     the same propagator and launch form and no more scratch or VGPR spills than it, and touch scratch only around the out-of-line calls
     (SSA_PROP_ELEMENTS / SSA_PROP_HYBRID) -- FG and J2 none at all"""
     kern, ins_of = _kernels(tmp_path)
-    new = [k for k in kern if "vector_sensors_kernel" in k]
-    assert len(new) == 8, new
-    for other in ("step_sensors_kernel", "rollout_sensors_kernel", "lookahead_sensors_kernel", "forecast_sensors_kernel", "lookahead_kernel",
-                  "rollout_kernel", "closed_loop_kernel", "step_fast_kernel"):
-        assert not any(other in k for k in new), other                      # (the names the other host tests count kernels by)
-    checked = 0
-    for name, ins in ins_of.items():
-        if "vector_sensors_kernel" not in name:
-            continue
-        form = re.search(r"ILi(\d)ELb([01])E", name)
-        prop = form.group(1)
-        ref = [k for k in kern if "step_sensors_kernel" in k and form.group(0) in k]
-        assert len(ref) == 1, (name, ref)
-        k, b = kern[name], kern[ref[0]]
-        assert k["vgpr_count"] <= 96 and k["group_segment_fixed_size"] == b["group_segment_fixed_size"], (name, k, b)
-        assert k["private_segment_fixed_size"] <= b["private_segment_fixed_size"], (name, k, b)
-        assert k["vgpr_spill_count"] <= b["vgpr_spill_count"], (name, k, b)
-        calls = [i for i, op in enumerate(ins) if op == "s_swappc_b64"]
-        assert not stray_scratch(ins), (name, stray_scratch(ins)[:8])
-        if prop not in "03":
-            assert not calls and k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, (name, k)
-        checked += 1
-    assert checked == 8
+    assert_family_budget(kern, ins_of, "vector_sensors_kernel", "step_sensors_kernel", KERNEL_FAMILIES["vector_sensors_kernel"])
