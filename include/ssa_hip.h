@@ -737,6 +737,28 @@ int ssa_assign_sensors_envs_f64(const double *score, int64_t n_obj, int32_t n_se
                                 void *workspace, int64_t workspace_bytes, void *stream);
 int64_t ssa_assign_sensors_envs_workspace_bytes(int64_t n_obj, int32_t n_sensor, int32_t n_env);
 
+/* ---------------------------------------------------------------- the OPTIMAL assignment of a sensor network, on the device
+ * The arguments, the workspace (layout, size queries, alignment, zeroed once), the refusals and their order, action_out, pick_out and the
+ * fallback rule of ssa_assign_sensors_f64 / ssa_assign_sensors_envs_f64 -- but the exact one-step optimum instead of the greedy rounds.
+ * A pair (s, j) is a CANDIDATE iff its score[(s * n_obj + j) * SSA_LOOK_NSCORE + column] is finite and of magnitude <= 2^1020.  NaN is
+ * "not a candidate", as for the greedy rule; UNLIKE the greedy rule, where +-inf are ordinary values, +-inf and anything above 2^1020
+ * are not candidates either: a sum that contains them has no order (or overflows: the rule compares sums of up to eight scores).
+ * Among all assignments of distinct objects to sensors over candidates the result has
+ *   1. the largest number of tasked sensors (so a sensor whose only candidate scores below zero is still tasked), and
+ *   2. among those, the largest sum of scores.  With the gains ssa_lookahead_sensors_f64 writes (>= 0) the two agree.
+ * The only rounding in the decision is that of the sums of at most n_sensor scores it compares, each added up in ascending object
+ * index: the result's sum is within 2 S (S - 1) 2^-53 max|score| of the optimum's, and IS the optimum where those sums are exact.
+ * Ties (-0.0 == 0.0) are broken by one fixed rule -- objects are taken in ascending index, a sensor subset keeps the assignment it has
+ * unless a sum is strictly greater, among sensors that give equal sums the lowest s; at the end the subset of most sensors, then of
+ * largest sum, then the lowest read as a binary number (bit s: sensor s) -- so the row is a pure function of the input bits: the same from
+ * every call and from both entries.  With n_sensor == 1 and finite scores it is the greedy row (first maximum, lowest j).
+ * One workspace may serve greedy and optimal calls in any order without being zeroed again. */
+int ssa_match_sensors_f64(const double *score, int64_t n_obj, int32_t n_sensor, int32_t column, const int32_t *fallback,
+                          int32_t *action_out, int64_t *pick_out, void *workspace, int64_t workspace_bytes, void *stream);
+int ssa_match_sensors_envs_f64(const double *score, int64_t n_obj, int32_t n_sensor, int32_t n_env, int32_t column,
+                               const int32_t *fallback, int32_t *action_out, int64_t *pick_out,
+                               void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------- visibility screen of a synthetic orbit catalogue
  * catalogue._accepted (orbit_gen.py's acceptance rule) for n candidate element sets, the observer generalised to a network of
  * n_site ground sites.  Candidate c = elements[c] = (a, ecc, inc, raan, argp, nu) (m, -, rad) is propagated by Kepler's equation

@@ -177,6 +177,8 @@ SIGNATURES = {
     "ssa_assign_sensors_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
     "ssa_assign_sensors_envs_f64": (C.c_int, [c_dp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_assign_sensors_envs_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "ssa_match_sensors_f64": (C.c_int, [c_dp, C.c_int64, C.c_int32, C.c_int32, c_dp, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
+    "ssa_match_sensors_envs_f64": (C.c_int, [c_dp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_peer_push_f64": (C.c_int, [c_dp, C.c_int64, c_dp, c_dp, C.c_int32, c_dp, C.c_uint64, c_dp, C.c_int64, c_dp, c_dp, c_dp]),
     "ssa_peer_wait": (C.c_int, [c_dp, C.c_int32, c_dp, C.c_uint64, C.c_int64, c_dp, c_dp]),
     "ssa_aer_obs_f64": (C.c_int, [c_dp, c_dp, c_dp, C.POINTER(ssa_consts), c_dp, C.c_int64, c_dp]),

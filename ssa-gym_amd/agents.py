@@ -124,8 +124,9 @@ def _draw_unassigned(env, taken):
                 return int(j)
 
 
-def _assign_lookahead_sensors_envs(vec, k):
-    acts = vec.assign_sensors(k)                            # int64 [E, S], -1 where the scores leave a sensor without an object
+def _assign_lookahead_sensors_envs(vec, k, rule='greedy'):
+    # int64 [E, S], -1 where the scores leave a sensor without an object
+    acts = vec.assign_sensors(k) if rule == 'greedy' else vec.assign_sensors(k, rule=rule)
     for act in acts:                                        # (envs ascending, sensors ascending)
         taken = set(act[act >= 0].tolist())
         for s in np.flatnonzero(act < 0):
@@ -134,16 +135,16 @@ def _assign_lookahead_sensors_envs(vec, k):
     return acts
 
 
-def _assign_lookahead_sensors(env, k):
+def _assign_lookahead_sensors(env, k, rule='greedy'):
     if hasattr(env, "num_envs"):                           # (a vector env: every env's row)
-        return _assign_lookahead_sensors_envs(env, k)
+        return _assign_lookahead_sensors_envs(env, k, rule)
     score = env.lookahead_sensors()["score"]               # [S, 3, m]: a view of the engine's [S][m][3] rows
     S = score.shape[0]
     row = env._engine.assign_row()
     # the rounds above on the device (ssa_assign_sensors_f64; no fallback words: a sensor without an object comes back -1): one launch
     # and one 32-byte read-back where S masked arg-max launches and S read-backs were
     # (permuted back, the view IS the engine's contiguous [S][m][3] block: launch_assign_sensors refuses anything else)
-    env._engine.launch_assign_sensors({"score": score.permute(0, 2, 1)}, k, row, stream=env._stream.cuda_stream)
+    env._engine.launch_assign_sensors({"score": score.permute(0, 2, 1)}, k, row, stream=env._stream.cuda_stream, rule=rule)
     env._stream.synchronize()
     act = row.cpu().numpy()[:S].astype(np.int64)
     taken = set(act[act >= 0].tolist())
@@ -159,6 +160,17 @@ def agent_info_gain_sensors(obs, env):          # one object per sensor, greedy 
 
 def agent_trace_gain_sensors(obs, env):         # one object per sensor, greedy over tr P- - tr P+ from every site
     return _assign_lookahead_sensors(env, _lib.LOOK_TRACE_GAIN)
+
+
+# ... and with the exact one-step optimum where the greedy rounds were (ssa_match_sensors_f64 / ssa_match_sensors_envs_f64; DESIGN.md
+# section 8n): as many sensors tasked as the finite scores allow, then the largest sum of gains -- the upper bound of every myopic rule.
+# The launches, the read-back and the host's fill of the -1 entries are those of the greedy twins.
+def agent_info_gain_sensors_optimal(obs, env):  # one object per sensor, the largest total 1/2 ln(det P- / det P+)
+    return _assign_lookahead_sensors(env, _lib.LOOK_INFO_GAIN, 'optimal')
+
+
+def agent_trace_gain_sensors_optimal(obs, env):  # one object per sensor, the largest total tr P- - tr P+
+    return _assign_lookahead_sensors(env, _lib.LOOK_TRACE_GAIN, 'optimal')
 
 
 # ---- non-myopic planning for a sensor network: the schedules env.rollout_sensors() executes.  ONE forecast
@@ -184,7 +196,7 @@ def _fill_plan(env, plan):
     return plan
 
 
-def _plan_assigned(env, horizon, k):
+def _plan_assigned(env, horizon, k, rule='greedy'):
     """the device's part of a plan: int64 [H', S], -1 where the scores leave a sensor without an object"""
     import torch
     with torch.cuda.stream(env._stream):
@@ -195,7 +207,7 @@ def _plan_assigned(env, horizon, k):
         planned = torch.zeros(m + 1, dtype=torch.bool, device=score.device)     # (slot m: where the -1 entries of a row land)
         for h in range(Hp):
             slab = score[h] if h == 0 else score[h].masked_fill(planned[:m].view(1, m, 1), float("nan"))
-            e.launch_assign_sensors({"score": slab}, k, rows[h], stream=env._stream.cuda_stream)
+            e.launch_assign_sensors({"score": slab}, k, rows[h], stream=env._stream.cuda_stream, rule=rule)
             r = rows[h].long()
             planned[torch.where(r >= 0, r, torch.full_like(r, m))] = True
     env._stream.synchronize()
@@ -210,7 +222,7 @@ def _fill_plan_envs(vec, plan):
     return np.stack([_fill_plan(vec, plan[e]) for e in range(plan.shape[0])])
 
 
-def _plan_assigned_envs(vec, horizon, k):
+def _plan_assigned_envs(vec, horizon, k, rule='greedy'):
     """the device's part of a vector env's plan: int64 [E, H', S], -1 where the scores leave a sensor without an object.  ONE forecast
     launch for all envs, then per step ONE assignment launch for all envs (ssa_assign_sensors_envs_f64) on the contiguous slab
     score[h] = [E, S, m, 3], into row h of a table of the planner's own (not the engine's action table), with ONE workspace; what an
@@ -227,29 +239,32 @@ def _plan_assigned_envs(vec, horizon, k):
         ws = device.assign_sensors_envs_workspace(m, S, E, score.device)
         for h in range(Hp):
             slab = score[h] if h == 0 else score[h].masked_fill(planned[:, :m].view(E, 1, m, 1), float("nan"))
-            device.assign_sensors_envs(slab, k, out=rows[h], workspace=ws)
+            device.assign_sensors_envs(slab, k, out=rows[h], workspace=ws, rule=rule)
             r = rows[h].long()
             planned[env_ix, torch.where(r >= 0, r, torch.full_like(r, m))] = True
     cur.synchronize()
     return np.ascontiguousarray(rows.cpu().numpy()[:, :, :S].astype(np.int64).transpose(1, 0, 2))
 
 
-def _plan_lookahead_sensors(env, horizon, k):
+def _plan_lookahead_sensors(env, horizon, k, rule='greedy'):
+    from . import device
+    device.assign_entry(rule)                              # (an unknown rule: refused before anything else)
     if hasattr(env, "num_envs"):                           # (a vector env: every env's plan, [E, H', S])
         if env._eng is None:
             raise _lib.SsaHipError("no device state: a plan comes from the forecast, which runs on the GPU only (no CPU fallback)")
-        return _fill_plan_envs(env, _plan_assigned_envs(env, horizon, k))
+        return _fill_plan_envs(env, _plan_assigned_envs(env, horizon, k, rule))
     if env._engine is None:
         raise _lib.SsaHipError("no device state: a plan comes from the forecast, which runs on the GPU only (no CPU fallback)")
-    return _fill_plan(env, _plan_assigned(env, horizon, k))
+    return _fill_plan(env, _plan_assigned(env, horizon, k, rule))
 
 
-def plan_info_gain_sensors(env, horizon):       # a schedule [H', S] for env.rollout_sensors() ([E, H', S] of a vector env): greedy over
-                                                # 1/2 ln(det P- / det P+) per step
-    """A single env runs the plan with env.rollout_sensors(plan); a vector env's plan [E, H', S] runs with vec.rollout_sensors(plan)
+def plan_info_gain_sensors(env, horizon, rule='greedy'):       # a schedule [H', S] for env.rollout_sensors() ([E, H', S] of a vector
+                                                               # env): greedy over 1/2 ln(det P- / det P+) per step
+    """rule='optimal': each step's row is the exact optimum of its masked slab (ssa_match_sensors_f64) instead of the greedy rounds.
+    A single env runs the plan with env.rollout_sensors(plan); a vector env's plan [E, H', S] runs with vec.rollout_sensors(plan)
     (DESIGN.md section 8l): one launch per chunk, stopping after the first step at which any env is done."""
-    return _plan_lookahead_sensors(env, horizon, _lib.LOOK_INFO_GAIN)
+    return _plan_lookahead_sensors(env, horizon, _lib.LOOK_INFO_GAIN, rule)
 
 
-def plan_trace_gain_sensors(env, horizon):      # ... over tr P- - tr P+
-    return _plan_lookahead_sensors(env, horizon, _lib.LOOK_TRACE_GAIN)
+def plan_trace_gain_sensors(env, horizon, rule='greedy'):      # ... over tr P- - tr P+
+    return _plan_lookahead_sensors(env, horizon, _lib.LOOK_TRACE_GAIN, rule)

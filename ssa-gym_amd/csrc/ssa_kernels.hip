@@ -3815,8 +3815,113 @@ SSA_DEV bool asg_after(double v, long long j, double pv, long long pj)      // d
 {
     return j >= 0 && (v < pv || (v == pv && j > pj));
 }
+// ---- the OPTIMAL assignment of a sensor network (include/ssa_hip.h: ssa_match_sensors_f64): one object per sensor, distinct objects,
+// first as many sensors tasked as possible, then the largest sum of scores -- over the same S x S table as the greedy rule above
+// (assign_sensors_body<true>: the candidates are the finite scores of magnitude <= 2^1020, so that no sum of eight overflows).  The table
+// suffices: if an optimal assignment gives sensor s an object outside its S best, at most S - 1 of those S are held by other sensors, one
+// is free and at least as good, and the swap keeps the number of tasked sensors.
+// The deciding part is a dynamic programme over sensor subsets, run by the whole workgroup that holds the table, one lane per subset:
+//   columns: the distinct objects of the table (<= 64) in ascending object index, ranked by one wavefront; w[c][s]: sensor s's score of
+//            column c's object, -inf where the object is not in its list;
+//   dp[mask]: the best sum that tasks exactly the sensors of `mask` with the columns so far, -inf where there is none (-inf + w stays
+//            -inf and wins no comparison: no branch on the sentinels).  Per column, from the previous column's values,
+//            new[mask] = max(old[mask], max over s in mask of old[mask ^ 1 << s] + w[c][s]), choice[c][mask] = that s, or 8 for "kept";
+//            two buffers, one barrier per column.  The only rounding of the decision is in these sums of at most S scores.
+//   ties:    a mask keeps its value unless a sum is strictly greater; among sensors with equal sums the lowest s; the final mask is the
+//            one of largest popcount, then largest sum, then lowest mask value.  A pure function of the table's bits.
+//   then lane 0 walks `choice` back from the last column, and the first wavefront applies the fallback rule and stores, as for the
+//   greedy rule.
+// LDS: tab 1 040 + dp 4 096 + w 4 096 + choice 16 384 + the columns' objects and their count 272 + the eight results 128 = 26 016 bytes.
+constexpr int ASG_NTAB = SSA_MAX_SENSORS * SSA_MAX_SENSORS;
+constexpr int MSN_COLS = ASG_NTAB, MSN_MASKS = 1 << SSA_MAX_SENSORS, MSN_KEPT = SSA_MAX_SENSORS;
+static_assert(MSN_MASKS == ASG_T && SSA_MAX_SENSORS == 8, "one lane per sensor subset; lane 8 s + r is sensor s's r-th candidate");
+SSA_DEV void msn_better(int& pc, double& bv, int& bm, int p2, double v2, int m2)      // (a total order: the merge commutes)
+{
+    const bool take = p2 > pc || (p2 == pc && (v2 > bv || (v2 == bv && m2 < bm)));
+    if (take) { pc = p2; bv = v2; bm = m2; }
+}
+SSA_DEV void asg_decide_optimal(const AsgCand* tab, int& act, double& pick_v)
+{
+    __shared__ double dp[2][MSN_MASKS];
+    __shared__ double w[MSN_COLS][SSA_MAX_SENSORS];
+    __shared__ unsigned char choice[MSN_COLS][MSN_MASKS];
+    __shared__ int colj[MSN_COLS + 4];          // (column c's object; the number of columns in entry MSN_COLS; a multiple of 16 bytes)
+    __shared__ AsgCand res[SSA_MAX_SENSORS];    // sensor s's object (j < 0: none) and its score
+    const int t = threadIdx.x, lane = t & 63;
+    const double NONE = -__builtin_huge_val();
+    (&w[0][0])[t] = NONE;
+    (&w[0][0])[t + MSN_MASKS] = NONE;
+    dp[0][t] = (t == 0) ? 0.0 : NONE;
+    if (t < SSA_MAX_SENSORS) { res[t].v = 0.0; res[t].j = -1; }
+    __syncthreads();
+    if (t < 64) {
+        const double cv = tab[lane].v;
+        const int cj = (int)tab[lane].j;        // (an object index below 2^31, or -1)
+        unsigned long long firsts = 0;          // bit k: lane k is the lowest lane that names its object
+        int rank = 0;                           // the distinct objects below this lane's
+#pragma unroll 1
+        for (int k = 0; k < MSN_COLS; ++k) {    // (a scalar loop: unrolled, its 64 broadcasts at once run the kernel out of SGPRs)
+            const int jk = __builtin_amdgcn_readlane(cj, k);
+            const bool fk = jk >= 0 && __ffsll((unsigned long long)__ballot(cj == jk)) - 1 == k;
+            firsts |= (unsigned long long)fk << k;
+            rank += (int)(fk && jk < cj);
+        }
+        if (cj >= 0) w[rank][lane >> 3] = cv;
+        if ((firsts >> lane) & 1) colj[rank] = cj;
+        if (lane == 0) colj[MSN_COLS] = __popcll(firsts);
+    }
+    __syncthreads();
+    const int C = colj[MSN_COLS];
+    int cur = 0;
+    for (int c = 0; c < C; ++c) {
+        double best = dp[cur][t];
+        int ch = MSN_KEPT;
+#pragma unroll
+        for (int s = 0; s < SSA_MAX_SENSORS; ++s) {
+            const double cand = ((t >> s) & 1) ? dp[cur][t ^ (1 << s)] + w[c][s] : NONE;
+            if (cand > best) { best = cand; ch = s; }
+        }
+        dp[cur ^ 1][t] = best;
+        choice[c][t] = (unsigned char)ch;
+        cur ^= 1;
+        __syncthreads();
+    }
+    if (t < 64) {
+        int pc = -1, bm = 0;
+        double bv = 0.0;
+#pragma unroll
+        for (int q = 0; q < MSN_MASKS / 64; ++q) {
+            const int mk = lane + 64 * q;
+            const double v = dp[cur][mk];
+            if (v != NONE) msn_better(pc, bv, bm, __popc((unsigned)mk), v, mk);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const int p2 = __shfl_xor(pc, off, 64), m2 = __shfl_xor(bm, off, 64);
+            const double v2 = __shfl_xor(bv, off, 64);
+            msn_better(pc, bv, bm, p2, v2, m2);
+        }
+        if (lane == 0) {
+            int mk = bm;                        // (the empty mask is always reachable: pc >= 0)
+            for (int c = C - 1; c >= 0; --c) {
+                const int ch = choice[c][mk];
+                if (ch == MSN_KEPT) continue;
+                res[ch].v = w[c][ch];
+                res[ch].j = colj[c];
+                mk ^= 1 << ch;
+            }
+        }
+    }
+    __syncthreads();
+    act = (lane < SSA_MAX_SENSORS) ? (int)res[lane & (SSA_MAX_SENSORS - 1)].j : -1;
+    pick_v = res[lane & (SSA_MAX_SENSORS - 1)].v;
+}
 // (one body for one env -- assign_sensors_kernel -- and for E of them -- assign_sensors_envs_kernel, which hands it each env's
-// scores, rows and part of the workspace: the grid's x axis walks the chunks, the hand-over is among the gridDim.x workgroups of an env)
+// scores, rows and part of the workspace: the grid's x axis walks the chunks, the hand-over is among the gridDim.x workgroups of an env.
+// OPTIMAL: the body of match_sensors_kernel / match_sensors_envs_kernel -- the candidates are the finite scores of magnitude <= 2^1020
+// instead of the scores that are not NaN, and asg_decide_optimal decides over the table instead of the S greedy rounds; phases 1 and 2,
+// the hand-over, the fallback rule and the stores are these lines for both.)
+template <bool OPTIMAL>
 SSA_DEV void assign_sensors_body(const double* __restrict__ score, int64_t m, int S, int col, const int32_t* __restrict__ fallback,
                                  int32_t* __restrict__ action_out, int64_t* __restrict__ pick_out, unsigned long long* ws)
 {
@@ -3830,7 +3935,7 @@ SSA_DEV void assign_sensors_body(const double* __restrict__ score, int64_t m, in
         for (int q = 0; q < ASG_Q; ++q) {
             const int64_t jj = j0 + q * 64 + lane;
             v[q] = (jj < m) ? score[((int64_t)s * m + jj) * SSA_LOOK_NSCORE + col] : 0.0;
-            ok |= (unsigned)(jj < m && v[q] == v[q]) << q;
+            ok |= (unsigned)(jj < m && (OPTIMAL ? fabs(v[q]) <= 0x1p1020 : v[q] == v[q])) << q;
         }
         double pv = 0.0, kv = 0.0;
         long long pj = -1, kj = -1;
@@ -3854,7 +3959,7 @@ SSA_DEV void assign_sensors_body(const double* __restrict__ score, int64_t m, in
             parts[((int64_t)blockIdx.x * S + s) * S + lane] = c;
         }
     }
-    constexpr int NTAB = SSA_MAX_SENSORS * SSA_MAX_SENSORS;
+    constexpr int NTAB = ASG_NTAB;
     __shared__ AsgCand tab[NTAB + 1];       // (the one LDS object: the table, and the last-arrival flag in the j of its extra entry)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -3904,22 +4009,27 @@ SSA_DEV void assign_sensors_body(const double* __restrict__ score, int64_t m, in
         if (lane < S) { tab[s * SSA_MAX_SENSORS + lane].v = kv; tab[s * SSA_MAX_SENSORS + lane].j = kj; }
     }
     __syncthreads();
-    if (t >= 64) return;
-    const int cs = lane >> 3;
-    const double cv = tab[lane].v;
-    long long cj = tab[lane].j;
     int act = -1;                  // lane s < S: sensor s's object
     double pick_v = 0.0;
-    for (int r = 0; r < S; ++r) {
-        double bv = cv;
-        long long bf = (cj >= 0) ? (long long)cs * m + cj : -1;      // (ties: the lowest s * m + j, the masked arg-max's first maximum)
-        const long long mine = bf;
-        asg_wave_first(bv, bf);
-        if (bf < 0) break;
-        const int ws_s = (__ffsll((unsigned long long)__ballot(mine == bf)) - 1) >> 3;
-        const long long wj = bf - (long long)ws_s * m;
-        if (lane == ws_s) { act = (int)wj; pick_v = bv; }
-        if (cs == ws_s || cj == wj) cj = -1;       // the sensor and the object leave the pool
+    if constexpr (OPTIMAL) {
+        asg_decide_optimal(tab, act, pick_v);
+        if (t >= 64) return;
+    } else {
+        if (t >= 64) return;
+        const int cs = lane >> 3;
+        const double cv = tab[lane].v;
+        long long cj = tab[lane].j;
+        for (int r = 0; r < S; ++r) {
+            double bv = cv;
+            long long bf = (cj >= 0) ? (long long)cs * m + cj : -1;      // (ties: the lowest s * m + j, the masked arg-max's first maximum)
+            const long long mine = bf;
+            asg_wave_first(bv, bf);
+            if (bf < 0) break;
+            const int ws_s = (__ffsll((unsigned long long)__ballot(mine == bf)) - 1) >> 3;
+            const long long wj = bf - (long long)ws_s * m;
+            if (lane == ws_s) { act = (int)wj; pick_v = bv; }
+            if (cs == ws_s || cj == wj) cj = -1;       // the sensor and the object leave the pool
+        }
     }
     const int assigned = act;
     const int fb = (fallback && lane < S) ? fallback[lane] : -1;
@@ -3941,7 +4051,7 @@ __global__ void __launch_bounds__(ASG_T) assign_sensors_kernel(const double* __r
                                                                const int32_t* __restrict__ fallback, int32_t* __restrict__ action_out,
                                                                int64_t* __restrict__ pick_out, unsigned long long* ws)
 {
-    assign_sensors_body(score, m, S, col, fallback, action_out, pick_out, ws);
+    assign_sensors_body<false>(score, m, S, col, fallback, action_out, pick_out, ws);
 }
 // ... of every env of a vector launch (ssa_assign_sensors_envs_f64): grid (chunks, envs).  Env e = blockIdx.y has its [S][m][3] slab of
 // the scores, its rows of `fallback`, `action_out` and `pick_out`, and its own ticket and candidate area, `ws_words` words apart
@@ -3951,8 +4061,24 @@ __global__ void __launch_bounds__(ASG_T) assign_sensors_envs_kernel(const double
                                                                     int64_t* __restrict__ pick_out, unsigned long long* ws, int64_t ws_words)
 {
     const int64_t e = blockIdx.y;
-    assign_sensors_body(score + e * S * m * SSA_LOOK_NSCORE, m, S, col, fallback ? fallback + e * SSA_MAX_SENSORS : nullptr,
+    assign_sensors_body<false>(score + e * S * m * SSA_LOOK_NSCORE, m, S, col, fallback ? fallback + e * SSA_MAX_SENSORS : nullptr,
                         action_out + e * SSA_MAX_SENSORS, pick_out ? pick_out + e * SSA_MAX_SENSORS * 2 : nullptr, ws + e * ws_words);
+}
+// the optimal rule's kernels: the arguments, grids and workspaces of the two above
+__global__ void __launch_bounds__(ASG_T) match_sensors_kernel(const double* __restrict__ score, int64_t m, int S, int col,
+                                                              const int32_t* __restrict__ fallback, int32_t* __restrict__ action_out,
+                                                              int64_t* __restrict__ pick_out, unsigned long long* ws)
+{
+    assign_sensors_body<true>(score, m, S, col, fallback, action_out, pick_out, ws);
+}
+// ... of every env of a vector launch (ssa_match_sensors_envs_f64): the grid and the workspace of assign_sensors_envs_kernel
+__global__ void __launch_bounds__(ASG_T) match_sensors_envs_kernel(const double* __restrict__ score, int64_t m, int S, int col,
+                                                                   const int32_t* __restrict__ fallback, int32_t* __restrict__ action_out,
+                                                                   int64_t* __restrict__ pick_out, unsigned long long* ws, int64_t ws_words)
+{
+    const int64_t e = blockIdx.y;
+    assign_sensors_body<true>(score + e * S * m * SSA_LOOK_NSCORE, m, S, col, fallback ? fallback + e * SSA_MAX_SENSORS : nullptr,
+                       action_out + e * SSA_MAX_SENSORS, pick_out ? pick_out + e * SSA_MAX_SENSORS * 2 : nullptr, ws + e * ws_words);
 }
 
 // ---- diagnostic reductions of SURVEY 8f-4 (ssa_tasker_simple_2.py:436-446, 750-775): NEES = d^T inv(P) d with
@@ -4940,13 +5066,32 @@ int64_t ssa_assign_sensors_workspace_bytes(int64_t n_obj, int32_t n_sensor)
     if (n_obj < 1 || n_obj > 0x7fffffff || n_sensor < 1 || n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
     return 64 + ((n_obj + ASG_CH - 1) / ASG_CH) * n_sensor * n_sensor * (int64_t)sizeof(AsgCand);
 }
+// the argument rules of the four assignment entries (greedy and optimal, one env and E of them), in the order they have always been
+// checked: the workspace size of THIS call, or SSA_E_INVALID.  align: what the workspace's address must be a multiple of.
+static int64_t assign_sensors_args(const double* score, int32_t column, const int32_t* action_out, int64_t need, const void* workspace,
+                                   int64_t workspace_bytes, uintptr_t align)
+{
+    if (!score || !row_aligned(action_out) || column < 0 || column >= SSA_LOOK_NSCORE) return SSA_E_INVALID;
+    if (need < 0 || !workspace || ((uintptr_t)workspace & (align - 1)) || workspace_bytes < need) return SSA_E_INVALID;
+    return need;
+}
+static bool assign_envs_fit(int64_t n_obj, int32_t n_sensor, int32_t n_env) { return rows_fit(n_env, n_sensor, n_obj) && n_env <= 65535; }
 int ssa_assign_sensors_f64(const double* score, int64_t n_obj, int32_t n_sensor, int32_t column, const int32_t* fallback,
                            int32_t* action_out, int64_t* pick_out, void* workspace, int64_t workspace_bytes, void* stream)
 {
-    if (!score || !action_out || ((uintptr_t)action_out & 31) || column < 0 || column >= SSA_LOOK_NSCORE) return SSA_E_INVALID;
-    const int64_t need = ssa_assign_sensors_workspace_bytes(n_obj, n_sensor);      // (refuses n_obj and n_sensor out of range)
-    if (need < 0 || !workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need) return SSA_E_INVALID;
+    // (the size query refuses n_obj and n_sensor out of range)
+    if (assign_sensors_args(score, column, action_out, ssa_assign_sensors_workspace_bytes(n_obj, n_sensor), workspace, workspace_bytes, 16) < 0)
+        return SSA_E_INVALID;
     hipLaunchKernelGGL(assign_sensors_kernel, dim3(nblk(n_obj, ASG_CH)), dim3(ASG_T), 0, (hipStream_t)stream, score, n_obj, (int)n_sensor,
+                       (int)column, fallback, action_out, pick_out, (unsigned long long*)workspace);
+    return launch_status();
+}
+int ssa_match_sensors_f64(const double* score, int64_t n_obj, int32_t n_sensor, int32_t column, const int32_t* fallback,
+                          int32_t* action_out, int64_t* pick_out, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    if (assign_sensors_args(score, column, action_out, ssa_assign_sensors_workspace_bytes(n_obj, n_sensor), workspace, workspace_bytes, 16) < 0)
+        return SSA_E_INVALID;
+    hipLaunchKernelGGL(match_sensors_kernel, dim3(nblk(n_obj, ASG_CH)), dim3(ASG_T), 0, (hipStream_t)stream, score, n_obj, (int)n_sensor,
                        (int)column, fallback, action_out, pick_out, (unsigned long long*)workspace);
     return launch_status();
 }
@@ -4960,11 +5105,21 @@ int64_t ssa_assign_sensors_envs_workspace_bytes(int64_t n_obj, int32_t n_sensor,
 int ssa_assign_sensors_envs_f64(const double* score, int64_t n_obj, int32_t n_sensor, int32_t n_env, int32_t column, const int32_t* fallback,
                                 int32_t* action_out, int64_t* pick_out, void* workspace, int64_t workspace_bytes, void* stream)
 {
-    if (!score || !action_out || ((uintptr_t)action_out & 31) || column < 0 || column >= SSA_LOOK_NSCORE) return SSA_E_INVALID;
-    const int64_t need = ssa_assign_sensors_envs_workspace_bytes(n_obj, n_sensor, n_env);      // (refuses n_obj, n_sensor and n_env out of range)
-    if (need < 0 || !workspace || ((uintptr_t)workspace & 63) || workspace_bytes < need) return SSA_E_INVALID;
-    if ((int64_t)n_env * n_sensor * n_obj >= ((int64_t)1 << 31) || n_env > 65535) return SSA_E_INVALID;
+    // (the size query refuses n_obj, n_sensor and n_env out of range)
+    const int64_t need = assign_sensors_args(score, column, action_out, ssa_assign_sensors_envs_workspace_bytes(n_obj, n_sensor, n_env),
+                                             workspace, workspace_bytes, 64);
+    if (need < 0 || !assign_envs_fit(n_obj, n_sensor, n_env)) return SSA_E_INVALID;
     hipLaunchKernelGGL(assign_sensors_envs_kernel, dim3(nblk(n_obj, ASG_CH), (unsigned)n_env), dim3(ASG_T), 0, (hipStream_t)stream, score,
+                       n_obj, (int)n_sensor, (int)column, fallback, action_out, pick_out, (unsigned long long*)workspace, need / n_env / 8);
+    return launch_status();
+}
+int ssa_match_sensors_envs_f64(const double* score, int64_t n_obj, int32_t n_sensor, int32_t n_env, int32_t column, const int32_t* fallback,
+                               int32_t* action_out, int64_t* pick_out, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    const int64_t need = assign_sensors_args(score, column, action_out, ssa_assign_sensors_envs_workspace_bytes(n_obj, n_sensor, n_env),
+                                             workspace, workspace_bytes, 64);
+    if (need < 0 || !assign_envs_fit(n_obj, n_sensor, n_env)) return SSA_E_INVALID;
+    hipLaunchKernelGGL(match_sensors_envs_kernel, dim3(nblk(n_obj, ASG_CH), (unsigned)n_env), dim3(ASG_T), 0, (hipStream_t)stream, score,
                        n_obj, (int)n_sensor, (int)column, fallback, action_out, pick_out, (unsigned long long*)workspace, need / n_env / 8);
     return launch_status();
 }

@@ -301,6 +301,19 @@ def masked_argmax_action(score, mask=None, workspace=None):
     return out.view(torch.int32)[:1]
 
 
+# the assignment rules of a sensor network: rule -> (the one-env entry, its *_envs sibling).  Same arguments, same workspace.
+ASSIGN_RULES = {'greedy': ("ssa_assign_sensors_f64", "ssa_assign_sensors_envs_f64"),
+                'optimal': ("ssa_match_sensors_f64", "ssa_match_sensors_envs_f64")}
+
+
+def assign_entry(rule, envs=False):
+    """the name of the C entry that assigns by `rule` ('greedy': the global greedy rounds; 'optimal': most sensors tasked, then the
+    largest sum of scores -- include/ssa_hip.h: ssa_match_sensors_f64)"""
+    if rule not in ASSIGN_RULES:
+        raise ValueError("rule must be 'greedy' or 'optimal', not %r" % (rule,))
+    return ASSIGN_RULES[rule][bool(envs)]
+
+
 def assign_sensors_workspace(n_obj, n_sensor, device):
     """zeroed workspace of ssa_assign_sensors_f64 for n_sensor sensors over n_obj objects (one call at a time: keep it with the stream
     that uses it; the kernel leaves it ready for the next call)"""
@@ -310,13 +323,15 @@ def assign_sensors_workspace(n_obj, n_sensor, device):
     return torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=device)
 
 
-def assign_sensors(score, column, fallback=None, out=None, picks=None, workspace=None):
+def assign_sensors(score, column, fallback=None, out=None, picks=None, workspace=None, rule='greedy'):
     """the tasking assignment of a sensor network on the device (ssa_assign_sensors_f64): the global greedy assignment of
     agents._assign_lookahead_sensors over column `column` (_lib.LOOK_*) of score [S, m, 3] -- the rows launch_lookahead_sensors leaves --
     in ONE launch.  fallback: int32 [MAX_SENSORS] draws for the sensors left without an object (taken in ascending s when in range and held
     by nobody; None: they stay idle, -1).  Returns the int32 CUDA row [MAX_SENSORS] (`out`: a 32-byte aligned row to write, e.g. one row
     of launch_rollout_sensors' schedule; entries s >= S are -1); picks: int64 [MAX_SENSORS, 2] to receive the assigned objects and their
-    scores' bit patterns.  workspace: assign_sensors_workspace (default: a fresh one).  No host sync."""
+    scores' bit patterns.  workspace: assign_sensors_workspace (default: a fresh one).  rule='optimal': the exact optimum instead
+    (ssa_match_sensors_f64: most sensors tasked, then the largest sum; finite scores only), same arguments, same workspace.  No host sync."""
+    entry = assign_entry(rule)
     lib = _lib.load()
     _chk(score, "score")
     if score.dim() != 3 or score.shape[2] != _lib.LOOK_NSCORE:
@@ -330,8 +345,8 @@ def assign_sensors(score, column, fallback=None, out=None, picks=None, workspace
         ptr[name] = None if t is None else _chk(t, name, dtype)
         if t is not None and t.numel() != n:
             raise _lib.SsaHipError("%s must hold %d %s words" % (name, n, dtype))
-    _lib.check(lib.ssa_assign_sensors_f64(score.data_ptr(), m, S, int(column), ptr["fallback"], ptr["out"], ptr["picks"],
-                                          _chk(ws, "workspace", torch.int64), ws.numel() * 8, _stream()), "ssa_assign_sensors_f64")
+    _lib.check(getattr(lib, entry)(score.data_ptr(), m, S, int(column), ptr["fallback"], ptr["out"], ptr["picks"],
+                                   _chk(ws, "workspace", torch.int64), ws.numel() * 8, _stream()), entry)
     return out
 
 
@@ -344,13 +359,14 @@ def assign_sensors_envs_workspace(n_obj, n_sensor, n_env, device):
     return torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
 
 
-def assign_sensors_envs(score, column, fallback=None, out=None, picks=None, workspace=None):
+def assign_sensors_envs(score, column, fallback=None, out=None, picks=None, workspace=None, rule='greedy'):
     """the tasking assignment of a sensor network in each of E envs (ssa_assign_sensors_envs_f64): assign_sensors for every env's slab of
     score [E, S, m, 3] -- the rows launch_lookahead_sensors_envs leaves -- in ONE launch.  fallback: int32 [E, MAX_SENSORS] draws per env
     (None: a sensor left without an object stays idle, -1).  Returns the int32 CUDA table [E, MAX_SENSORS] (`out`: a 32-byte aligned
     table to write, e.g. the action table the next launch_step_sensors_envs reads; entries s >= S are -1); picks: int64
     [E, MAX_SENSORS, 2] to receive the assigned objects and their scores' bit patterns.  workspace: assign_sensors_envs_workspace
-    (default: a fresh one).  No host sync."""
+    (default: a fresh one).  rule: as assign_sensors ('optimal': ssa_match_sensors_envs_f64).  No host sync."""
+    entry = assign_entry(rule, envs=True)
     lib = _lib.load()
     _chk(score, "score")
     if score.dim() != 4 or score.shape[3] != _lib.LOOK_NSCORE:
@@ -364,8 +380,8 @@ def assign_sensors_envs(score, column, fallback=None, out=None, picks=None, work
         ptr[name] = None if t is None else _chk(t, name, dtype)
         if t is not None and t.numel() != n:
             raise _lib.SsaHipError("%s must hold %d %s words" % (name, n, dtype))
-    _lib.check(lib.ssa_assign_sensors_envs_f64(score.data_ptr(), m, S, E, int(column), ptr["fallback"], ptr["out"], ptr["picks"],
-                                               _chk(ws, "workspace", torch.int64), ws.numel() * 8, _stream()), "ssa_assign_sensors_envs_f64")
+    _lib.check(getattr(lib, entry)(score.data_ptr(), m, S, E, int(column), ptr["fallback"], ptr["out"], ptr["picks"],
+                                   _chk(ws, "workspace", torch.int64), ws.numel() * 8, _stream()), entry)
     return out
 
 

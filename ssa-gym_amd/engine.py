@@ -575,13 +575,15 @@ class HotPathEngine:
             raise _lib.SsaHipError("ssa_lookahead_sensors_envs_f64 failed with code %d" % rc)
         return res
 
-    def launch_assign_sensors_envs(self, look, column, fallback=None, picks=None, stream=None):
+    def launch_assign_sensors_envs(self, look, column, fallback=None, picks=None, stream=None, rule='greedy'):
         """enqueue every env's tasking assignment, one launch (include/ssa_hip.h: ssa_assign_sensors_envs_f64), on `look`, the dict
         launch_lookahead_sensors_envs returned: per env what launch_assign_sensors does for one, written into this engine's own
         [E][MAX_SENSORS] action table (action_table()) -- the one launch_step_sensors_envs(actions=None) then reads: the actions never
         touch the host.  fallback: int32 CUDA [E, MAX_SENSORS] draws (None: a sensor left without an object stays idle, -1); picks:
         int64 CUDA [E, MAX_SENSORS, 2] or None.  The workspace is this engine's (zeroed once, again when S changes).  Returns the table.
+        rule='optimal': every env's exact optimum instead (ssa_match_sensors_envs_f64), same table, same workspace.
         Asynchronous, no host sync."""
+        entry = device.assign_entry(rule, envs=True)
         score = look["score"]
         S = int(score.shape[1]) if isinstance(score, torch.Tensor) and score.dim() == 4 else 0
         W = _lib.MAX_SENSORS
@@ -597,11 +599,10 @@ class HotPathEngine:
         ws = self._assign_envs_ws[1]
         table = self.action_table()
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        rc = self._lib.ssa_assign_sensors_envs_f64(score.data_ptr(), self.m, S, self.E, int(column), fallback.data_ptr() if fallback is not None else 0,
-                                                   table.data_ptr(), picks.data_ptr() if picks is not None else 0, ws.data_ptr(),
-                                                   ws.numel() * 8, s)
+        rc = getattr(self._lib, entry)(score.data_ptr(), self.m, S, self.E, int(column), fallback.data_ptr() if fallback is not None else 0,
+                                       table.data_ptr(), picks.data_ptr() if picks is not None else 0, ws.data_ptr(), ws.numel() * 8, s)
         if rc:
-            raise _lib.SsaHipError("ssa_assign_sensors_envs_f64 failed with code %d" % rc)
+            raise _lib.SsaHipError("%s failed with code %d" % (entry, rc))
         return table
 
     def launch_forecast_sensors(self, slot_in, time_offset, sensors, n_steps, out=(), stream=None):
@@ -656,13 +657,15 @@ class HotPathEngine:
             raise _lib.SsaHipError("ssa_forecast_sensors_envs_f64 failed with code %d" % rc)
         return res
 
-    def launch_assign_sensors(self, look, column, action_row, fallback_row=None, picks=None, stream=None):
+    def launch_assign_sensors(self, look, column, action_row, fallback_row=None, picks=None, stream=None, rule='greedy'):
         """enqueue the tasking assignment of a sensor network (include/ssa_hip.h: ssa_assign_sensors_f64) on `look`, the dict
         launch_lookahead_sensors returned: one object per sensor by the global greedy rule of agents._assign_lookahead_sensors over score
         column `column` (_lib.LOOK_*), written to `action_row` -- a 32-byte aligned CUDA int32 row of MAX_SENSORS words, e.g. row k of the
         [K, MAX_SENSORS] tensor whose one-row slice the next launch_rollout_sensors takes: the actions never touch the host.
         fallback_row: int32 [MAX_SENSORS] draws for the sensors left without an object (None: they stay idle, -1); picks: int64
-        [MAX_SENSORS, 2] or None.  The workspace is this engine's (zeroed once, again when S changes).  Asynchronous, no host sync."""
+        [MAX_SENSORS, 2] or None.  The workspace is this engine's (zeroed once, again when S changes).  rule='optimal': the exact optimum
+        instead (ssa_match_sensors_f64: most sensors tasked, then the largest sum), same row, same workspace.  Asynchronous, no host sync."""
+        entry = device.assign_entry(rule)
         score = look["score"]
         S = int(score.shape[0]) if isinstance(score, torch.Tensor) and score.dim() == 3 else 0
         for t, dt, n, nm in ((action_row, torch.int32, _lib.MAX_SENSORS, "action_row"), (fallback_row, torch.int32, _lib.MAX_SENSORS, "fallback_row"),
@@ -677,11 +680,10 @@ class HotPathEngine:
             self._assign_ws = (S, device.assign_sensors_workspace(self.m, S, self.dev))
         ws = self._assign_ws[1]
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        rc = self._lib.ssa_assign_sensors_f64(score.data_ptr(), self.m, S, int(column), fallback_row.data_ptr() if fallback_row is not None else 0,
-                                              action_row.data_ptr(), picks.data_ptr() if picks is not None else 0, ws.data_ptr(),
-                                              ws.numel() * 8, s)
+        rc = getattr(self._lib, entry)(score.data_ptr(), self.m, S, int(column), fallback_row.data_ptr() if fallback_row is not None else 0,
+                                       action_row.data_ptr(), picks.data_ptr() if picks is not None else 0, ws.data_ptr(), ws.numel() * 8, s)
         if rc:
-            raise _lib.SsaHipError("ssa_assign_sensors_f64 failed with code %d" % rc)
+            raise _lib.SsaHipError("%s failed with code %d" % (entry, rc))
 
     def assign_row(self):
         """this engine's own int32 [MAX_SENSORS] action row, for a caller of launch_assign_sensors that reads one assignment back

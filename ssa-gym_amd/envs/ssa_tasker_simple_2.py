@@ -568,12 +568,16 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         return self._obs_out(refresh_aer_dev=True), np.asarray(actions, dtype=int), np.asarray(rewards), np.asarray(dones, dtype=bool)
 
     SENSOR_AGENT_COLUMNS = {'agent_info_gain_sensors': _lib.LOOK_INFO_GAIN, 'agent_trace_gain_sensors': _lib.LOOK_TRACE_GAIN}
+    # every agent run_agent_sensors takes: name -> (score column, assignment rule of device.ASSIGN_RULES)
+    SENSOR_AGENT_RULES = {'agent_info_gain_sensors': (_lib.LOOK_INFO_GAIN, 'greedy'), 'agent_trace_gain_sensors': (_lib.LOOK_TRACE_GAIN, 'greedy'),
+                          'agent_info_gain_sensors_optimal': (_lib.LOOK_INFO_GAIN, 'optimal'),
+                          'agent_trace_gain_sensors_optimal': (_lib.LOOK_TRACE_GAIN, 'optimal')}
 
     def run_agent_sensors(self, agent, n_steps, fallback_actions=None):
         """run_agent() for a sensor network (no reference counterpart): the loop
             a = agent(obs, env); obs, r, done, _ = env.step(a)
-        for agents.agent_info_gain_sensors / agent_trace_gain_sensors (`agent`: the function or its name) with the assignment computed on
-        the GPU (ssa_assign_sensors_f64) and handed to the step in-stream.  Per step three launches in one stream -- every sensor's
+        for agents.agent_info_gain_sensors / agent_trace_gain_sensors and their *_optimal forms (`agent`: the function or its name) with the
+        assignment computed on the GPU (ssa_assign_sensors_f64; *_optimal: ssa_match_sensors_f64) and handed to the step in-stream.  Per step three launches in one stream -- every sensor's
         lookahead, the assignment into row k of a device log, the step that reads that row (ssa_env_rollout_sensors_f64 with a one-row
         schedule) -- and nothing is read back until a chunk of up to H-1 steps ends.  Stops at the first `done`.  Returns what run_agent
         returns: (observation after the last executed step, actions [k, S], rewards [k], dones [k]); books per step and per sensor what
@@ -586,10 +590,11 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
             raise _lib.SsaHipError("no device state: a sensor network's closed loop runs on the GPU only (no CPU fallback)")
         import torch
         name = agent if isinstance(agent, str) else getattr(agent, "__name__", None)
-        if name not in self.SENSOR_AGENT_COLUMNS:
-            raise NotImplementedError("run_agent_sensors: %r has no device-side version (supported: %s)"
-                                      % (agent, sorted(self.SENSOR_AGENT_COLUMNS)))
-        column = self.SENSOR_AGENT_COLUMNS[name]
+        if name not in self.SENSOR_AGENT_RULES:
+            raise NotImplementedError("run_agent_sensors: %r has no device-side version (supported: %s; with the optimal assignment: %s)"
+                                      % (agent, sorted(self.SENSOR_AGENT_COLUMNS),
+                                         sorted(set(self.SENSOR_AGENT_RULES) - set(self.SENSOR_AGENT_COLUMNS))))
+        column, rule = self.SENSOR_AGENT_RULES[name]
         self._caller_order()
         shaped = self.reward_type == 'shaped'
         e, sites, S, W = self._engine, self._sites(), self.n_sensor, _lib.MAX_SENSORS
@@ -612,7 +617,7 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
             for k in range(kk):
                 i = i0 + k + 1
                 look = e.launch_lookahead_sensors((i - 1) % e.H, i, sites)
-                e.launch_assign_sensors(look, column, log[pos + k], fallback_row=fb[pos + k])
+                e.launch_assign_sensors(look, column, log[pos + k], fallback_row=fb[pos + k], rule=rule)
                 e.launch_rollout_sensors((i - 1) % e.H, i, sites, log[pos + k:pos + k + 1], argmax_spos=shaped)
             stats, upd = self._ring_chunk(i0, kk, e.upd_sensors if S > 1 else e.upd_sensors[:, 0])
             acts = log[pos:pos + kk, :S].cpu().numpy()

@@ -49,16 +49,26 @@ def check_sensor_actions(actions, E, S, m):
 
 
 SENSOR_AGENTS = {'agent_info_gain_sensors': _lib.LOOK_INFO_GAIN, 'agent_trace_gain_sensors': _lib.LOOK_TRACE_GAIN}
+# every agent of a sensor network that decides on the device: name -> (score column, assignment rule of device.ASSIGN_RULES)
+SENSOR_AGENT_RULES = {'agent_info_gain_sensors': (_lib.LOOK_INFO_GAIN, 'greedy'), 'agent_trace_gain_sensors': (_lib.LOOK_TRACE_GAIN, 'greedy'),
+                      'agent_info_gain_sensors_optimal': (_lib.LOOK_INFO_GAIN, 'optimal'),
+                      'agent_trace_gain_sensors_optimal': (_lib.LOOK_TRACE_GAIN, 'optimal')}
+
+
+def sensor_agent_rule(agent):
+    """(score column, assignment rule) of a lookahead agent of a sensor network, given as the function of agents.py or its name;
+    anything else has no device form in a vector env (NotImplementedError).  Needs no device state."""
+    name = agent if isinstance(agent, str) else getattr(agent, '__name__', None)
+    if name not in SENSOR_AGENT_RULES:
+        raise NotImplementedError("step_agent: %r is not implemented; the agents of a sensor network that decide on the device are %s, "
+                                  "and with the optimal assignment %s"
+                                  % (agent, " and ".join(sorted(SENSOR_AGENTS)), " and ".join(sorted(set(SENSOR_AGENT_RULES) - set(SENSOR_AGENTS)))))
+    return SENSOR_AGENT_RULES[name]
 
 
 def sensor_agent_column(agent):
-    """the score column of a lookahead agent of a sensor network, given as the function of agents.py or its name; anything else has
-    no device form in a vector env (NotImplementedError).  Needs no device state."""
-    name = agent if isinstance(agent, str) else getattr(agent, '__name__', None)
-    if name not in SENSOR_AGENTS:
-        raise NotImplementedError("step_agent: %r is not implemented; the agents of a sensor network that decide on the device are %s"
-                                  % (agent, " and ".join(sorted(SENSOR_AGENTS))))
-    return SENSOR_AGENTS[name]
+    """the score column of sensor_agent_rule(agent)"""
+    return sensor_agent_rule(agent)[0]
 
 
 def check_fallback_actions(fallback, E, S):
@@ -280,20 +290,21 @@ class SSA_Tasker_VecEnv:
         """One vector step of a sensor network whose actions a lookahead agent decides ON THE DEVICE: every
         sensor's lookahead in every env, every env's greedy assignment into the engine's action table, and the step reading that
         table -- three launches in one stream, one synchronisation; the actions reach the host only afterwards, for the 'shaped' hit and
-        for the caller.  `agent`: agents.agent_info_gain_sensors or agents.agent_trace_gain_sensors, or its name.  fallback_actions:
+        for the caller.  `agent`: agents.agent_info_gain_sensors or agents.agent_trace_gain_sensors, or its name; their
+        *_optimal forms decide by the exact one-step optimum instead of the greedy rounds (ssa_match_sensors_envs_f64).  fallback_actions:
         what a sensor the scores leave without an object gets -- None: one single_action_space.sample() row per env; an [E, S] integer
         array: taken as given, sensors ascending, unless out of 0 .. m-1 or held by another sensor of the env (the sensor then stays
         idle).  Returns step()'s 4-tuple -- rewards, dones, auto-reset and observations are step()'s -- with infos[e]['action'] the int64
         [S] row env e executed (-1: the sensor stayed idle)."""
-        column = sensor_agent_column(agent)
+        column, rule = sensor_agent_rule(agent)
         if self.n_sensor < 2:
             raise NotImplementedError("step_agent: not implemented without a sensor network (config['observers'])")
         if fallback_actions is None:
             fallback_actions = np.stack([np.atleast_1d(self.single_action_space.sample()) for _ in range(self.E)])
-        return self._step(None, decide=(column, check_fallback_actions(fallback_actions, self.E, self.n_sensor)))
+        return self._step(None, decide=(column, check_fallback_actions(fallback_actions, self.E, self.n_sensor), rule))
 
     def _step(self, actions, decide=None):
-        """the vector step: `actions` as step() checked them, or -- decide = (score column, fallback words [E, MAX_SENSORS]) -- decided
+        """the vector step: `actions` as step() checked them, or -- decide = (score column, fallback words [E, MAX_SENSORS], rule) -- decided
         on the device in front of the step's launch (step_agent) and read back behind the one synchronisation"""
         import torch
         S = self.n_sensor
@@ -321,7 +332,7 @@ class SSA_Tasker_VecEnv:
                 fb = torch.from_numpy(decide[1]).to("cuda")
                 cur = torch.cuda.current_stream()
                 look = e.launch_lookahead_sensors_envs(sin, 0, self._sensors, stream=cur.cuda_stream)
-                table = e.launch_assign_sensors_envs(look, decide[0], fallback=fb, stream=cur.cuda_stream)
+                table = e.launch_assign_sensors_envs(look, decide[0], fallback=fb, stream=cur.cuda_stream, rule=decide[2])
                 e.launch_step_sensors_envs(sin, sout, 0, self._sensors, None, stream=cur.cuda_stream, **kw)
                 if self._rows_host is None:
                     self._rows_host = torch.zeros((self.E, _lib.MAX_SENSORS), dtype=torch.int32).pin_memory()
@@ -539,13 +550,18 @@ class SSA_Tasker_VecEnv:
         r = self._launch_forecast_sensors(horizon, want)
         return {k: v.transpose(0, 1) for k, v in r.items()}
 
-    def assign_sensors(self, column):
-        """the lookahead of every env and every env's greedy assignment over score column `column` (_lib.LOOK_*): two launches and one
-        read-back of E x 32 bytes.  int64 [E, S]; -1: the scores left that sensor without an object.  Nothing of the envs changes."""
+    def assign_sensors(self, column, rule='greedy'):
+        """the lookahead of every env and every env's assignment over score column `column` (_lib.LOOK_*) by `rule` ('greedy', or
+        'optimal': most sensors tasked, then the largest sum): two launches and one read-back of E x 32 bytes.  int64 [E, S]; -1: the
+        scores left that sensor without an object.  Nothing of the envs changes."""
         import torch
+        from .. import device
+        device.assign_entry(rule)                     # (an unknown rule: refused before anything is launched)
+        if self._eng is None:
+            raise _lib.SsaHipError("no device state: the assignment comes from the lookahead, which runs on the GPU only (no CPU fallback)")
         look = self._launch_lookahead_sensors()
         cur = self._stream if self._inline else torch.cuda.current_stream()
-        table = self._eng.launch_assign_sensors_envs(look, column, stream=cur.cuda_stream)
+        table = self._eng.launch_assign_sensors_envs(look, column, stream=cur.cuda_stream, rule=rule)
         cur.synchronize()
         return table.cpu().numpy()[:, :self.n_sensor].astype(np.int64)
 
