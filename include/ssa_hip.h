@@ -277,6 +277,17 @@ int ssa_env_step_f64(const ssa_consts *c_host, const ssa_step_params *p_host, vo
                                         one folds the lines into stats_prev and clears them.  Same bits as the atomics path: max, counts and the
                                         first arg-max do not depend on the order.  Both launches of a hand-over carry the bit;
                                         ssa_stats_fold_metrics_f64() folds the last step. */
+#define SSA_LAUNCH_GENERIC 512u  /* ABI 23, additive: keep this launch on the generic step kernel.  Without the bit ssa_env_step_f64 sends the
+                                    PLAIN launch form to an instance of the one-tile step kernel compiled for exactly that form
+                                    (step_plain_kernel: what the generic one decides per wavefront from its arguments is a constant there;
+                                    same arithmetic, bit-identical results).  The plain form: no sensor network, n_env == 1, one tile per
+                                    wavefront, SSA_LAUNCH_DEFER_FOLD | SSA_LAUNCH_STATS_FROM_METRICS and none of SSA_LAUNCH_INLINE_ACTION,
+                                    SSA_LAUNCH_INLINE_ENVS, SSA_LAUNCH_FOLD_INSIDE, SSA_LAUNCH_MIRROR_F32 nor the diagnostic bits 1 / 2 / 4,
+                                    `actions` given, aer_out / obs_mirror / spos_tiles / spos_tiles_prev / stat_shards_clear NULL,
+                                    update_interval <= 1, no SSA_FLAG_RESAMPLE, SSA_OBS_AER.  For tests and A/B measurements. */
+/* which instance ssa_env_step_f64 would launch for this block: 1 = the plain form's, 0 = the generic one, or the negative SSA_E_* code
+ * with which ssa_env_step_f64 refuses the block.  Host only: nothing is launched, no pointer is followed. */
+int ssa_env_step_instance(const ssa_consts *c_host, const ssa_step_params *p_host);
 int ssa_env_step_profiled_f64(const ssa_consts *c_host, const ssa_step_params *p_host, void *stream, int32_t slot);
 /* waits for slot's kernel and writes its duration in milliseconds */
 int ssa_env_step_profile_ms(int32_t slot, float *kernel_ms);

@@ -9,7 +9,7 @@ for d in sys.argv[1:]:
         continue
     acc = {}
     for r in csv.DictReader(open(fs[0])):
-        if 'step_fast_kernel' not in r['Kernel_Name']:
+        if 'step_fast_kernel' not in r['Kernel_Name'] and 'step_plain_kernel' not in r['Kernel_Name']:   # (the workload's launches take the plain form)
             continue
         if out["kernel"] is None:
             out["kernel"] = r['Kernel_Name'].split('(')[0]

@@ -115,6 +115,7 @@ LAUNCH_FOLD_INSIDE = 32
 LAUNCH_INLINE_ENVS = 64
 LAUNCH_MIRROR_F32 = 128
 LAUNCH_STATS_FROM_METRICS = 256
+LAUNCH_GENERIC = 512      # (ABI 23, additive: keep the launch on the generic step kernel; ssa_env_step_instance tells which one it gets)
 INLINE_ENVS = 8
 LOOP_ARGMAX_SPOS, LOOP_DEBUG_WITHHOLD = 1, 2
 FAIL_STRIDE, FAIL_ENV, FAIL_OBJ, FAIL_STATUS, FAIL_TIME, FAIL_ERR = 8, 0, 1, 2, 3, 4
@@ -128,6 +129,7 @@ SIGNATURES = {
     "ssa_abi_version": (C.c_int, []),
     "ssa_build_info": (C.c_char_p, []),
     "ssa_env_step_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), c_dp]),
+    "ssa_env_step_instance": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params)]),
     "ssa_env_step_profiled_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), c_dp, C.c_int32]),
     "ssa_env_step_profile_ms": (C.c_int, [C.c_int32, C.POINTER(C.c_float)]),
     "ssa_stats_fold_f64": (C.c_int, [c_dp, c_dp, C.c_int32, c_dp]),

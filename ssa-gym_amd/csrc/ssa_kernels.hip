@@ -214,7 +214,8 @@ SSA_DEV int64_t env_row0(const ssa_step_params& p, int64_t base)
 {
     return p.n_env > 1 ? (int64_t)((uint32_t)base / (uint32_t)p.n_obj) * p.n_obj : 0;
 }
-template <bool NT>
+// PLAIN (step_plain_kernel, see ActPlain): one env and no obs_mirror, known when the kernel was compiled
+template <bool NT, bool PLAIN = false>
 SSA_DEV void store_tile(const Tiles& t, const ssa_step_params& p, int lane, int64_t base, int cnt)
 {
 #define SSA_SKIP(b) 0   // (no store is skipped; without the ragged tile's `skip` below the multi-tile step kernel allocates its registers differently)
@@ -245,7 +246,7 @@ SSA_DEV void store_tile(const Tiles& t, const ssa_step_params& p, int lane, int6
             }
             if (NT) __builtin_nontemporal_store(pair, reinterpret_cast<v2d*>(dst));
             else *reinterpret_cast<v2d*>(dst) = pair;
-            if (p.obs_mirror) {   // (e.g. host-mapped memory; with obj_ids: row by row at the caller's index of the object)
+            if (!PLAIN && p.obs_mirror) {   // (e.g. host-mapped memory; with obj_ids: row by row at the caller's index of the object)
                 // (in observation entries; several envs: the table holds indices within the env, whose rows start at env_row0)
                 const int64_t at = p.obj_ids ? (env_row0(p, base) + t.Oid[jj]) * 12 + r : base * 12 - 64 + 2 * lane;
                 if (p.launch_mask & SSA_LAUNCH_MIRROR_F32)      // the host-facing copy in single precision: half the bytes over PCIe
@@ -257,7 +258,7 @@ SSA_DEV void store_tile(const Tiles& t, const ssa_step_params& p, int lane, int6
         if (!SSA_SKIP(8) && lane < 16) {   // metrics [E][4][m]: four 32-byte runs per tile
             const int kk = lane >> 2, jj = lane & 3;
             const int64_t obj = base + jj;
-            if (p.n_env == 1) {   // (scalar row stride, one 64-bit multiply-add per lane)
+            if (PLAIN || p.n_env == 1) {   // (scalar row stride, one 64-bit multiply-add per lane)
                 p.metrics[(int64_t)kk * p.n_obj + obj] = t.Met[jj * 4 + kk];
             } else {
                 const int64_t e = (int64_t)((uint32_t)obj / (uint32_t)p.n_obj), j = obj - e * p.n_obj;
@@ -277,7 +278,7 @@ SSA_DEV void store_tile(const Tiles& t, const ssa_step_params& p, int lane, int6
         const double* src = sO ? t.Obs : sP ? t.P + 128 : sT ? t.T : t.X;
         const bool skip = sO ? SSA_SKIP(2) : sP ? SSA_SKIP(1) : SSA_SKIP(4);
         if (!skip && i < lim) store16<NT>(dst + 2 * i, src + 2 * i);
-        if (sO && p.obs_mirror && i < lim) {
+        if (!PLAIN && sO && p.obs_mirror && i < lim) {
             const int jj = (i * 43) >> 8;     // i / 6: the object (rows beyond cnt are masked by `lim`)
             const int64_t at = p.obj_ids ? (env_row0(p, base) + t.Oid[jj]) * 12 + (2 * i - 12 * jj) : base * 12 + 2 * i;
             if (p.launch_mask & SSA_LAUNCH_MIRROR_F32)
@@ -293,7 +294,7 @@ SSA_DEV void store_tile(const Tiles& t, const ssa_step_params& p, int lane, int6
         const int kk = lane >> 2, jj = lane & 3;
         if (jj < cnt) {
             const int64_t obj = base + jj;
-            if (p.n_env == 1) {   // (scalar row stride, one 64-bit multiply-add per lane)
+            if (PLAIN || p.n_env == 1) {   // (scalar row stride, one 64-bit multiply-add per lane)
                 p.metrics[(int64_t)kk * p.n_obj + obj] = t.Met[jj * 4 + kk];
             } else {
                 const int64_t e = (int64_t)((uint32_t)obj / (uint32_t)p.n_obj), j = obj - e * p.n_obj;
@@ -1019,6 +1020,7 @@ struct ActBase {
     static constexpr bool forecast = false;       // ... as step h of a forecast: `look_sensors` on a resident tile
     static constexpr bool envs = false;           // `sensors` in each of several envs: a row of actions per env (ActSensorEnvs)
     static constexpr bool look_envs = false;      // `look_sensors` in each of several envs (ActLookSensorEnvs)
+    static constexpr bool plain = false;          // the plain one-env launch form, decided by the launcher (ActPlain)
     SSA_DEV int get() { return -1; }
     SSA_DEV void before_wait(Tiles&, int, int) {}
     SSA_DEV void mid_step(Tiles&, int) {}
@@ -1034,6 +1036,13 @@ struct ActBase {
 // left, while the predicts of step k are already running -- a wavefront asks for it only where the update needs it, behind
 // its predict, and every row prefetches the update's inputs for its OWN object in case it turns out to be the selected one.
 struct ActEarly : ActBase {};
+// ActPlain (step_plain_kernel): ActEarly for the launch form the launcher has already recognised (step_plain_form) -- one env, the action
+// and time words in memory, statistics from the metrics rows with a deferred fold, an update in every step, no resampling, az-el-range
+// measurements, no aer_out / obs_mirror / spos_tiles / stat_shards_clear.  What process_wave decides per wavefront from the argument
+// segment for every other form is a constant here; the arithmetic is the same, instruction for instruction.
+struct ActPlain : ActBase {
+    static constexpr bool plain = true;
+};
 struct ActLate;
 struct LoopK;
 SSA_DEV void closed_loop_prescore(ActLate& a, Tiles& t, int lane, int cnt);   // (defined with the closed-loop kernel)
@@ -1398,6 +1407,9 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     constexpr bool FCAST = ACT::forecast;      // ... as step h of a forecast: LSENS on a resident tile (ActForecastSensors)
     constexpr bool ENVS = ACT::envs;           // SENS in each of several envs, whole tiles per env (ActSensorEnvs)
     constexpr bool LENVS = ACT::look_envs;     // LSENS in each of several envs, whole tiles per env (ActLookSensorEnvs)
+    constexpr bool PLAIN = ACT::plain;         // the launcher's plain form (ActPlain): the decisions below marked PLAIN are constants
+    static_assert(!PLAIN || (!ACT::late && !ALL && !SENS && !LSENS), "ActPlain: a step kernel's form");   // (and launched as the one-tile instance only)
+#define SSA_NENV (PLAIN ? 1 : p.n_env)   /* (at the place of use: every other instance reads the word where it did) */
     // (ActLookSensors, multi-tile instance: the next tile's loads leave once, behind the last pass -- except with SSA_PROP_ELEMENTS, whose
     // out-of-line call then spills 8 more VGPRs: there they are issued as in every other kernel, after the propagator and again at the end
     // of each pass's update)
@@ -1418,8 +1430,12 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // compiler cannot get by loading the word again) -- left to itself the compiler loads launch_mask, branches on it, loads the pointer
     // the branch picked, then the word: four scalar round trips in a row.
     struct { uint32_t mask; const int32_t *actions, *env_time, *obj_ids; int n_env, time_offset, update_interval; } hw =
-        {p.launch_mask, p.actions, p.env_time, p.obj_ids, p.n_env, p.time_offset, C.update_interval};
-    if (TILE == 0 && !ALL) {
+        {PLAIN ? (SSA_LAUNCH_DEFER_FOLD | SSA_LAUNCH_STATS_FROM_METRICS) : p.launch_mask, p.actions, p.env_time, p.obj_ids, SSA_NENV,
+         p.time_offset, PLAIN ? 1 : C.update_interval};
+    if constexpr (PLAIN) {   // (the mask, the env count and the interval are not fetched: known)
+        asm volatile("" : "+s"(hw.actions), "+s"(hw.env_time), "+s"(hw.obj_ids), "+s"(hw.time_offset)
+                     : "s"(p.P_out), "s"(p.x_out), "s"(p.x_true_out), "s"(p.obs), "s"(p.metrics), "s"(p.stat_shards), "s"(p.upd), "s"(p.n_obj));
+    } else if (TILE == 0 && !ALL) {
         // the epilogue's output pointers are fetched NOW as well: their scalar loads (kernarg segment) overlap the tile's HBM round
         // trip instead of each adding a scalar-memory round trip to the store path of a latency-bound wavefront.  (As inputs only: the
         // compiler is free to drop them again, and does so with p.obs and p.metrics -- the store stage loads those a second time.)
@@ -1635,7 +1651,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // propagator: 24 bytes per lane and tile = 61 MB of scratch writes per 160 000-object step); the action word is read
     // again where the rare paths below need it (a scalar load here would sit in front of every LDS wait that follows)
     obj = base + g;
-    e = (valid && p.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
+    e = (valid && SSA_NENV > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
     if constexpr (ENVS) e = asrc.env;
     if constexpr (FCAST && LENVS) e = asrc.env;   // (a forecast in several envs: no division per lane anywhere)
     // the next tile's inputs: in flight during the transform / covariance / observation / store of this one
@@ -1691,7 +1707,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // SSA_FLAG_RESAMPLE (the predict() of filterpy's development branch): sigma_points(x_prior, P_prior) is drawn at the
     // end of predict() for EVERY filter, so an exhausted robust_cholesky ladder fails the filter in THIS step's predict
     // (not one step later); the update then uses those points (t.U holds the factor rows)
-    if (C.flags & SSA_FLAG_RESAMPLE) {
+    if (!PLAIN && (C.flags & SSA_FLAG_RESAMPLE)) {
         const int rg = robust_chol_row_lds(t, C.scale, g, l);
         wave_lds_sync();
         if (active && st_new == SSA_ST_OK && rg == 16) st_new = SSA_ST_PREDICT_LINALG;
@@ -1746,7 +1762,7 @@ look_pass:
                 sf[c] = o[c];
                 xb[c] = t.X[g * 6 + c];   // the prior mean
             }
-            if ((C.flags & SSA_FLAG_RESAMPLE) && (!LSENS || look_s == 0)) {
+            if (!PLAIN && (C.flags & SSA_FLAG_RESAMPLE) && (!LSENS || look_s == 0)) {
                 const int krow = is_pm ? (l - 1) % 6 : 0;
                 const double sgn = (l >= 1 && l <= 6) ? 1.0 : ((l >= 7 && l <= 12) ? -1.0 : 0.0);
 #pragma unroll
@@ -1794,7 +1810,7 @@ look_pass:
                     lim = SP->obs_limit[look_s];
                 } else hx_aer_enu(sf, Mm, C.enu, C.obs_itrs, aer, enu_vec);
                 el_mine = aer[1];
-                if (C.obs_type == SSA_OBS_AER) { z[0] = aer[0]; z[1] = aer[1]; z[2] = aer[2]; }
+                if (PLAIN || C.obs_type == SSA_OBS_AER) { z[0] = aer[0]; z[1] = aer[1]; z[2] = aer[2]; }
                 else { z[0] = sf[0]; z[1] = sf[1]; z[2] = sf[2]; }
             }
             if constexpr (SENS || LSENS) visible = row_bcast<13>(el_mine) >= lim;   // (as seen from the row's sensor)
@@ -1807,7 +1823,7 @@ look_pass:
                 // H3/H5: predicted measurement
                 double zp[3];
                 const double wl = (l == 0) ? C.Wc0 : (is_pm ? C.Wi : 0.0);
-                if (C.obs_type == SSA_OBS_AER) {
+                if (PLAIN || C.obs_type == SSA_OBS_AER) {
                     double um[3];   // mean_z_uvw (dynamics.py:343): aer2uvw of a sigma point is its local vector enu_vec
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
@@ -1836,7 +1852,7 @@ look_pass:
 #pragma unroll
                         for (int c = 0; c < 3; ++c) zin[c] = z[c];
                     }
-                    if (C.obs_type == SSA_OBS_AER) residual_z_aer_wrapped(zin, zp, rz);
+                    if (PLAIN || C.obs_type == SSA_OBS_AER) residual_z_aer_wrapped(zin, zp, rz);
                     else {
 #pragma unroll
                         for (int c = 0; c < 3; ++c) rz[c] = zin[c] - zp[c];
@@ -1966,7 +1982,7 @@ look_pass:
         rec[SSA_UPD_VISIBLE] = visible ? 1.0 : 0.0;
         if constexpr (ENVS) rec[SSA_UPD_ACTION] = attempted ? (double)(p.obj_ids ? (int64_t)t.Oid[g] : obj - (int64_t)asrc.env * p.n_obj) : -1.0;
         else if constexpr (SENS) rec[SSA_UPD_ACTION] = attempted ? (double)(p.obj_ids ? (int64_t)t.Oid[g] : obj) : -1.0;   // (the sensor's action IS this object)
-        else rec[SSA_UPD_ACTION] = attempted ? (double)(ACT::late ? act : env_action<INL, SEG>(p, e)) : -1.0;   // (my_update: the env's action IS this object)
+        else rec[SSA_UPD_ACTION] = attempted ? (double)(ACT::late ? act : PLAIN ? *(ConstPtr<int32_t>)p.actions : env_action<INL, SEG>(p, e)) : -1.0;   // (my_update: the env's action IS this object)
     }
     if constexpr (ALL) {
         look_vis = visible;
@@ -1979,14 +1995,14 @@ look_pass:
     g = lane >> 4;
     l = lane & 15;
     obj = base + g;
-    e = (valid && p.n_env > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
+    e = (valid && SSA_NENV > 1) ? (int)((uint32_t)obj / (uint32_t)p.n_obj) : 0;
     if constexpr (ENVS) e = asrc.env;
     if constexpr (FCAST && LENVS) e = asrc.env;   // (a forecast in several envs: no division per lane anywhere)
     if (TILE == 1 && !ISSUE_LAST) tile_issue(pf, p, lane, next_base, next_cnt);
     }   // wavefronts holding a selected object
     // envs whose action selects nobody still get a cleared record (written by object 0's row)
     if (!ALL && valid && p.upd && obj == (int64_t)e * p.n_obj && l == 0) {   // (object 0 of an env: one lane per env)
-      const int a_env = ACT::late ? act : env_action<INL, SEG>(p, e);
+      const int a_env = ACT::late ? act : PLAIN ? *(ConstPtr<int32_t>)p.actions : env_action<INL, SEG>(p, e);
       if (!(a_env >= 0 && interval_ok && (int64_t)a_env < p.n_obj)) {
         double* rec = p.upd + (int64_t)e * SSA_UPD_STRIDE;
         rec[SSA_UPD_OBS_TAKEN] = 0.0;
@@ -2050,7 +2066,7 @@ look_pass:
                 rec[SSA_FAIL_ENV] = (double)e;
                 rec[SSA_FAIL_OBJ] = p.obj_ids ? (double)t.Oid[g] : (double)(obj - (int64_t)e * p.n_obj);
                 rec[SSA_FAIL_STATUS] = (double)st_new;
-                rec[SSA_FAIL_TIME] = (double)((ACT::late ? p.env_time[0] : env_time_of<INL, SEG>(p, e)) + p.time_offset);
+                rec[SSA_FAIL_TIME] = (double)((ACT::late ? p.env_time[0] : PLAIN ? *(ConstPtr<int32_t>)p.env_time : env_time_of<INL, SEG>(p, e)) + p.time_offset);
                 rec[SSA_FAIL_ERR + 0] = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
                 rec[SSA_FAIL_ERR + 1] = sqrt(b0 * b0 + b1 * b1 + b2 * b2);
                 rec[SSA_FAIL_ERR + 2] = sqrt(Pd[0] + Pd[7] + Pd[14]);
@@ -2108,23 +2124,23 @@ look_pass:
     // O4 in the epilogue (atomics-statistics path): the (az, el, range, trace P) block of the NEW state -- the 'aer'
     // observation mode and the multi-GPU all-gather payload -- from the tiles, so that no second pass over x / P (the
     // former post kernel: 6.7 MB re-read per 20 000 objects plus a launch) is needed
-    if (p.aer_out && p.stat_shards) {
+    if (!PLAIN && p.aer_out && p.stat_shards) {
         if (l < 4 && valid) aer_obs_tile<INL, SEG>(t, p, C, g, l, e, p.obj_ids ? (int64_t)e * p.n_obj + t.Oid[g] : obj);
     }
     wave_lds_sync();
     if (!ACT::late) {   // (closed_loop_kernel stores the tile itself, AFTER it has announced its part of the decision)
-        if (p.spos_tiles && p.stat_shards && lane == 0) {   // the tile's first maximum of sigma_pos (np.argmax for the 'shaped' reward): one slot, no atomics
+        if (!PLAIN && p.spos_tiles && p.stat_shards && lane == 0) {   // the tile's first maximum of sigma_pos (np.argmax for the 'shaped' reward): one slot, no atomics
             unsigned long long key, idx;
             spos_tile_best(t, cnt, obj - (int64_t)e * p.n_obj, key, idx, p.obj_ids != nullptr);
             unsigned long long* slot = (unsigned long long*)p.spos_tiles + 2 * (int64_t)tile;
             __hip_atomic_store(slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (agent scope: SSA_LAUNCH_FOLD_INSIDE reads them in this launch)
             __hip_atomic_store(slot + 1, idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        store_tile<TILE != 1>(t, p, lane, base, cnt);
+        store_tile<TILE != 1, PLAIN>(t, p, lane, base, cnt);
         // O3 by sharded atomics: max delta_pos (as ordered bits: non-negative doubles and NaN order like unsigned
         // integers, so NaN wins exactly as in np.max), trinary counts (packed in one word), failures
-        const bool one_env = p.n_env == 1 || ((uint32_t)base / (uint32_t)p.n_obj == (uint32_t)(base + cnt - 1) / (uint32_t)p.n_obj);
-        if (FROM_METRICS && (p.launch_mask & SSA_LAUNCH_STATS_FROM_METRICS)) {
+        const bool one_env = SSA_NENV == 1 || ((uint32_t)base / (uint32_t)p.n_obj == (uint32_t)(base + cnt - 1) / (uint32_t)p.n_obj);
+        if (FROM_METRICS && (PLAIN || (p.launch_mask & SSA_LAUNCH_STATS_FROM_METRICS))) {
             // (one env, stat_shards given: the launcher.)  Max delta_pos and the counts are reduced from the metrics rows just stored by the
             // service wavefronts of the NEXT launch (stats_service_wave); only the failed filters are counted here -- the status words
             // are updated in place -- and only by a tile that has one: the row's status is still in a register, no LDS read, no wait
@@ -2219,13 +2235,14 @@ look_pass:
         }
         // raw-shard consumers (stat_shards_clear): the first tile's wavefront zeroes the shard set the NEXT step accumulates
         // into -- at the very end, so that no wavefront waits for this pointer's kernarg line before its tile loads
-        if (tile == 0) {
+        if (!PLAIN && tile == 0) {
             if (p.stat_shards_clear) {
                 unsigned long long* z = (unsigned long long*)p.stat_shards_clear;
                 for (int i = lane; i < p.n_env * SSA_STAT_SHARDS * 4; i += 64) z[(i >> 2) * SSA_STAT_SHARD_WORDS + (i & 3)] = 0ull;   // (the used words)
             }
         }
     }
+#undef SSA_NENV
 }
 
 // folds the SSA_STAT_SHARDS accumulators of the atomics path of env e into stats and clears them (one wavefront)
@@ -2351,6 +2368,9 @@ struct VecLookSensK {   // (LookSensK's layout under a name of its own: the type
     LookK k;
     ssa_sensor_params s;
 };
+struct PlainK {   // (StepK's layout under a name of its own: the type selects ActPlain)
+    StepK k;
+};
 struct VecSensK {   // ... and, behind SensK's, the envs' action rows and records (ssa_env_step_sensors_envs_f64)
     StepK k;
     ssa_sensor_params s;
@@ -2359,6 +2379,7 @@ struct VecSensK {   // ... and, behind SensK's, the envs' action rows and record
 // what a block hands process_wave: the step's constants and parameters, and the ACT policy (its pointers into the block)
 SSA_DEV const StepK& step_of(const StepK& k) { return k; }
 SSA_DEV const StepK& step_of(const LookK& k) { return k.k; }
+SSA_DEV const StepK& step_of(const PlainK& k) { return k.k; }
 SSA_DEV const StepK& step_of(const SensK& k) { return k.k; }
 SSA_DEV const StepK& step_of(const LookSensK& k) { return k.k.k; }
 SSA_DEV const StepK& step_of(const VecLookSensK& k) { return k.k.k; }
@@ -2369,6 +2390,7 @@ SSA_DEV ConstPtr<int32_t> vector_sensors_inline_rows()   // (by the segment's ad
 }
 SSA_DEV const StepK& step_of(const VecSensK& k) { return k.k; }
 SSA_DEV ActEarly act_of(const StepK&) { return ActEarly(); }   // (the leading {} below: ActBase, which has no members)
+SSA_DEV ActPlain act_of(const PlainK&) { return ActPlain(); }
 SSA_DEV ActAll act_of(const LookK& k) { return ActAll{{}, &k.o}; }
 SSA_DEV ActSensors act_of(const SensK& k) { return ActSensors{{}, &k.s}; }
 SSA_DEV ActLookSensors act_of(const LookSensK& k) { return ActLookSensors{{}, &k.k.o, &k.s}; }
@@ -2381,8 +2403,9 @@ enum : unsigned {
     WALK_ONE_ENV = 2,       // a sensor network: one env, n_obj objects
     WALK_ACT_SEGMENT = 4,   // the one-tile instance takes the ACT's pointers by the argument segment's address, not the argument's:
                             // kernarg_opaque (process_wave) needs a pointer into the segment
-    WALK_BASE_PER_TILE = 8  // the grid-stride loop carries the segment's base and adds the block's offset per tile (step_fast_kernel),
+    WALK_BASE_PER_TILE = 8, // the grid-stride loop carries the segment's base and adds the block's offset per tile (step_fast_kernel),
                             // not the block's address formed once in front of the loop
+    WALK_PLAIN = 16         // the launcher's plain form (ActPlain; one-tile instance only): one env, statistics from the metrics rows
 };
 // One tile kernel: NAME<PROP, MULTI>(ntiles (MULTI; else the whole tiles), nwork, pre_P_in, pre_x_in, pre_x_true_in, pre_status, const K k_arg).
 // The walk is written out once, here, but expands into the body of each kernel rather than living in a device function they call:
@@ -2403,7 +2426,7 @@ enum : unsigned {
         const int unit = (int)blockIdx.x;                                                                                                     \
         if (((WALK) & WALK_STEP) && unit >= nwork) {                                                                                          \
             const ssa_step_params& p = step_of(k_arg).p;                                                                                      \
-            if (!MULTI && !((WALK) & WALK_ONE_ENV) && (p.launch_mask & SSA_LAUNCH_STATS_FROM_METRICS))                                        \
+            if (!MULTI && !((WALK) & WALK_ONE_ENV) && (((WALK) & WALK_PLAIN) || (p.launch_mask & SSA_LAUNCH_STATS_FROM_METRICS)))             \
                 stats_service_wave(p.metrics_prev, (unsigned long long*)p.stat_shards_prev, p.stats_prev,                                     \
                                    (const unsigned long long*)p.spos_tiles_prev, p.n_obj, unit - nwork, (int)gridDim.x - nwork, lane);        \
             else                                                                                                                              \
@@ -2419,10 +2442,10 @@ enum : unsigned {
             const bool whole = tile < ntiles;   /* (this instance: the count of WHOLE tiles, TileGrid::arg)   */                               \
             /* (the object total -- scalar loads and a wait -- is formed where it is used: by the ragged tile, and behind the loads) */       \
             tile_dma_issue(t, pf, pre_P_in, pre_x_in, pre_x_true_in, pre_status, lane, base, whole, step_of(k_arg).p,                         \
-                           ((WALK) & WALK_ONE_ENV) != 0);                                                                                     \
+                           ((WALK) & (WALK_ONE_ENV | WALK_PLAIN)) != 0);                                                                      \
             int cnt = OBJ_PER_WAVE;                                                                                                           \
             asm volatile("" : "+s"(cnt));                                                                                                     \
-            if (!whole) cnt = (int)(tile_total(step_of(k_arg).p, ((WALK) & WALK_ONE_ENV) != 0) - base);                                       \
+            if (!whole) cnt = (int)(tile_total(step_of(k_arg).p, ((WALK) & (WALK_ONE_ENV | WALK_PLAIN)) != 0) - base);                        \
             const K& ka = ((WALK) & WALK_ACT_SEGMENT)                                                                                         \
                               ? *(const K*)(KernargPtr<K>)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(TileArgs<K>, k))    \
                               : k_arg;                                                                                                        \
@@ -2458,6 +2481,7 @@ enum : unsigned {
 
 // The kernels' names are what the profiles, the host tests and bench.py's roofline find them by.
 SSA_TILE_KERNEL(step_fast_kernel, StepK, WALK_STEP | WALK_BASE_PER_TILE)                   // a step (ssa_env_step_f64)
+SSA_TILE_KERNEL(step_plain_kernel, PlainK, WALK_STEP | WALK_PLAIN)                         // ... in the plain one-env form (step_plain_form)
 SSA_TILE_KERNEL(lookahead_kernel, LookK, 0)                                                // the lookahead (ssa_lookahead_f64)
 SSA_TILE_KERNEL(lookahead_sensors_kernel, LookSensK, WALK_ONE_ENV | WALK_ACT_SEGMENT)      // a sensor network's lookahead
 SSA_TILE_KERNEL(step_sensors_kernel, SensK, WALK_STEP | WALK_ONE_ENV)                      // a sensor network's step
@@ -4378,10 +4402,8 @@ static ssa_sensor_params idle_sites(const ssa_sensor_params* sp)
     return s;
 }
 
-// sens: a sensor network's step (ssa_env_step_sensors_f64; checked by the caller) -- step_sensors_kernel instead of step_fast_kernel
-// envs: ... in each of n_env envs (ssa_env_step_sensors_envs_f64; checked by the caller) -- vector_sensors_kernel
-static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stream, hipEvent_t ev0, hipEvent_t ev1,
-                       const ssa_sensor_params* sens = nullptr, const ssa_sensor_envs_params* envs = nullptr)
+// the argument rules of a step launch, in the order step_launch has always applied them; SSA_OK leaves the launch's grid in `g`
+static int step_args(const ssa_consts* c, const ssa_step_params* p, bool sens, TileGrid& g)
 {
     if (!c || !p || p->n_obj <= 0 || p->n_env <= 0) return SSA_E_INVALID;
     if (!p->x_true_in || !p->x_true_out || !p->x_in || !p->x_out || !p->P_in || !p->P_out || !p->status ||
@@ -4404,20 +4426,45 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     if ((p->spos_tiles || p->spos_tiles_prev) && ragged_envs(p)) return SSA_E_UNSUPPORTED;
     if (!consts_ok(c)) return SSA_E_INVALID;
     if (p->aer_cols != 0 && p->aer_cols != 1 && p->aer_cols != 4) return SSA_E_INVALID;
-    StepK k;
-    k.c = *c;
-    k.p = *p;
     if (!rows_fit(p->n_env, p->n_obj)) return SSA_E_INVALID;
-    const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
+    g = tile_grid((int64_t)p->n_env * p->n_obj);
     const bool fast_stats = p->stat_shards != nullptr;   // statistics by the common-path kernel's atomics
     const bool defer = fast_stats && (p->launch_mask & SSA_LAUNCH_DEFER_FOLD);
     if (defer && p->stat_shards_prev && (!p->stats_prev || p->stat_shards_prev == p->stat_shards)) return SSA_E_INVALID;
-    const bool from_metrics = (p->launch_mask & SSA_LAUNCH_STATS_FROM_METRICS) != 0;
-    if (from_metrics) {   // (the one-tile step kernel of one env, deferred fold: see the bit)
+    if (p->launch_mask & SSA_LAUNCH_STATS_FROM_METRICS) {   // (the one-tile step kernel of one env, deferred fold: see the bit)
         if (!defer || sens || p->n_env != 1 || g.per_wave != 1 || (p->launch_mask & SSA_LAUNCH_FOLD_INSIDE) || p->stat_shards_clear)
             return SSA_E_UNSUPPORTED;
         if (p->stat_shards_prev && !p->metrics_prev) return SSA_E_INVALID;
     }
+    return SSA_OK;
+}
+// The plain launch form: what step_plain_kernel (ActPlain) was compiled for.  Every condition is one that process_wave<.., ActPlain> holds
+// as a constant; a block that breaks any of them -- or carries SSA_LAUNCH_GENERIC -- gets step_fast_kernel.  (launch_mask bits 1 / 2 / 4:
+// the diagnostic selection of single launches; SSA_LAUNCH_STATS_FROM_METRICS has passed step_args: one env, one tile per wavefront, a
+// deferred fold, no SSA_LAUNCH_FOLD_INSIDE, no stat_shards_clear -- restated here so that the predicate stands on its own.)
+static bool step_plain_form(const ssa_consts* c, const ssa_step_params* p, bool sens, const TileGrid& g)
+{
+    const uint32_t need = SSA_LAUNCH_DEFER_FOLD | SSA_LAUNCH_STATS_FROM_METRICS;
+    const uint32_t none = SSA_LAUNCH_INLINE_ACTION | SSA_LAUNCH_INLINE_ENVS | SSA_LAUNCH_FOLD_INSIDE | SSA_LAUNCH_MIRROR_F32 | SSA_LAUNCH_GENERIC | 7u;
+    return !sens && p->n_env == 1 && g.per_wave == 1 && (p->launch_mask & need) == need && !(p->launch_mask & none) && p->actions &&
+           !p->aer_out && !p->obs_mirror && !p->spos_tiles && !p->spos_tiles_prev && !p->stat_shards_clear && c->update_interval <= 1 &&
+           !(c->flags & SSA_FLAG_RESAMPLE) && c->obs_type == SSA_OBS_AER;
+}
+
+// sens: a sensor network's step (ssa_env_step_sensors_f64; checked by the caller) -- step_sensors_kernel instead of step_fast_kernel
+// envs: ... in each of n_env envs (ssa_env_step_sensors_envs_f64; checked by the caller) -- vector_sensors_kernel
+static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stream, hipEvent_t ev0, hipEvent_t ev1,
+                       const ssa_sensor_params* sens = nullptr, const ssa_sensor_envs_params* envs = nullptr)
+{
+    TileGrid g;
+    const int rc = step_args(c, p, sens != nullptr, g);
+    if (rc != SSA_OK) return rc;
+    StepK k;
+    k.c = *c;
+    k.p = *p;
+    const bool fast_stats = p->stat_shards != nullptr;   // statistics by the common-path kernel's atomics
+    const bool defer = fast_stats && (p->launch_mask & SSA_LAUNCH_DEFER_FOLD);
+    const bool from_metrics = (p->launch_mask & SSA_LAUNCH_STATS_FROM_METRICS) != 0;
     const int nfold = (defer && p->stat_shards_prev) ? (from_metrics ? STAT_SERVICE_WAVES : p->n_env) : 0;
     dim3 grid((unsigned)(g.nwork + nfold)), block(64);
     const int nparts = post_parts(p->n_obj, p->n_env);
@@ -4444,6 +4491,12 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
         ks.s = *sens;
         with_prop(prop, g.per_wave != 1, [&](auto P, auto M) {
             hipExtLaunchKernelGGL((step_sensors_kernel<P, M>), grid, block, 0, s, ev0, ev1, 0, g.arg, g.nwork, p->P_in, p->x_in, p->x_true_in, p->status, ks);
+        });
+    } else if ((mask & 1u) && step_plain_form(c, p, false, g)) {   // (the plain form: the instance compiled for it)
+        PlainK kp;
+        kp.k = k;
+        with_prop(prop, [&](auto P) {
+            hipExtLaunchKernelGGL((step_plain_kernel<P, false>), grid, block, 0, s, ev0, ev1, 0, g.arg, g.nwork, p->P_in, p->x_in, p->x_true_in, p->status, kp);
         });
     } else if (mask & 1u) {   // (ev0, ev1: dispatch timestamps of this kernel for ssa_env_step_profiled_f64, else null)
         with_prop(prop, g.per_wave != 1, [&](auto P, auto M) {
@@ -4481,6 +4534,12 @@ int ssa_stats_fold_metrics_f64(const double* metrics, uint64_t* stat_shards, con
 int ssa_env_step_f64(const ssa_consts* c, const ssa_step_params* p, void* stream)
 {
     return step_launch(c, p, stream, nullptr, nullptr);
+}
+int ssa_env_step_instance(const ssa_consts* c, const ssa_step_params* p)
+{
+    TileGrid g;
+    const int rc = step_args(c, p, false, g);
+    return rc != SSA_OK ? rc : (step_plain_form(c, p, false, g) ? 1 : 0);
 }
 int ssa_env_step_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, void* stream)
 {

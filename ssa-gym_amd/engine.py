@@ -93,6 +93,7 @@ class HotPathEngine:
         self._shard_sets = torch.zeros((2, self.E, _lib.STAT_SHARDS, _lib.STAT_SHARD_WORDS), dtype=torch.int64, device=d)
         self.stat_shards = self._shard_sets[0]
         self._shard_cur = 0
+        self.force_generic = False     # set: every launch_step carries SSA_LAUNCH_GENERIC (the generic step kernel; tests and A/B runs)
         self._fold_pending = None      # (shard set index, stats destination, arg-max slots?, metrics block or 0) of a step whose fold was deferred
         # SSA_LAUNCH_STATS_FROM_METRICS: a deferred step of ONE env (one tile per wavefront) leaves max delta_pos and the trinary counts
         # to service wavefronts of the next launch, which reduce them from the metrics rows it stored (0: the path does not apply)
@@ -364,6 +365,8 @@ class HotPathEngine:
             inline |= _lib.LAUNCH_FOLD_INSIDE      # (the step kernel's last wavefront folds the statistics: no fold launch)
         if from_metrics:
             inline |= _lib.LAUNCH_STATS_FROM_METRICS
+        if self.force_generic:
+            inline |= _lib.LAUNCH_GENERIC
         if defer and self._fold_pending is not None:
             p.launch_mask = _lib.LAUNCH_DEFER_FOLD | inline
             p.stat_shards_prev = self._shard_ptr[self._fold_pending[0]]
