@@ -770,6 +770,47 @@ int ssa_match_sensors_envs_f64(const double *score, int64_t n_obj, int32_t n_sen
                                const int32_t *fallback, int32_t *action_out, int64_t *pick_out,
                                void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------- the horizon-wide OPTIMAL tasking plan of a sensor network, on the device
+ * A whole forecast turned into a schedule in ONE launch: the plan as ONE assignment problem over all its (step, sensor) pairs, instead of
+ * one assignment per step in time order with the earlier steps' objects masked out (additive: the ABI version stays).
+ * A SLOT is a pair (h, s); there are N = n_step * n_sensor of them, 1 <= N <= SSA_MAX_PLAN_SLOTS.  A triple (h, s, j) is a CANDIDATE iff
+ * its score[(((h * n_env + e) * n_sensor + s) * n_obj + j) * SSA_LOOK_NSCORE + column] is finite and of magnitude <= 2^1020 (the
+ * candidate test of ssa_match_sensors_f64: NaN, +-inf and anything above 2^1020 are not candidates).  A PLAN gives each slot at most one
+ * candidate object and gives no object to two slots of the same env, in any step (the forecast's gains are gains of a FIRST observation).
+ * Among all plans the result has
+ *   1. the most filled slots -- exact for every input: the count is decided on integers, no large constant is added to any double --, and
+ *   2. among those, the largest sum of scores.
+ * Arithmetic of 2.: the scores of the N best candidates of each slot (that table suffices: DESIGN.md section 8o) are rounded ONCE to
+ * int64 multiples of the unit 2^(e - 52), 2^e the smallest power of two above the table's largest magnitude, and everything after that is
+ * exact integer arithmetic.  So the sum IS the exact optimum whenever the table's scores are multiples of that unit -- guaranteed for
+ * dyadic tables (multiples of 2^-10 of magnitude below 2^10) --, and for any other input the result's sum is within
+ *     4 N 2^-53 max|candidate score|
+ * of the optimum's (each of the <= N scores on either side moves by at most half a unit, and the unit is <= 4 * 2^-53 * the largest
+ * magnitude).  -0.0 == 0.0.
+ * Ties are broken by one fixed rule: the slots enter a shortest-augmenting-path solver in ascending h * n_sensor + s; a slot's candidates
+ * are ranked by (score descending, object ascending); costs are pairs (idle slots, -sum) compared lexicographically; the unscanned slot
+ * of least distance is scanned next, the lowest slot among equals; a free object (or the slot's own idleness, ranked last) replaces the
+ * best end found so far only if strictly nearer, within one scan the lowest rank; a slot's distance and predecessor change only for a
+ * strictly smaller distance; the search ends as soon as no unscanned slot is strictly nearer than the best end.  So the plan is a pure
+ * function of the input bits: the same from every call, and the same for an env whether it is planned alone or as one of n_env.  With
+ * N == 1 and finite scores it is the first maximum (lowest j), as for ssa_assign_sensors_f64.  There is no fallback argument: an
+ * unfilled slot is -1.
+ *   score     : [n_step][n_env][n_sensor][n_obj][SSA_LOOK_NSCORE]: exactly what ssa_forecast_sensors_envs_f64 leaves, and with
+ *               n_env == 1 exactly what ssa_forecast_sensors_f64 leaves
+ *   plan_out  : [n_step][n_env][SSA_MAX_SENSORS] device words, the base 32-byte aligned; -1 beyond n_sensor and in unfilled slots: the
+ *               action table ssa_env_rollout_sensors_envs_f64 reads, and with n_env == 1 the one ssa_env_rollout_sensors_f64 reads
+ *   pick_out  : NULL, or [n_step][n_env][SSA_MAX_SENSORS][2]: the object (-1: none) and the bit pattern of its score (0 without one)
+ *   workspace : ssa_plan_sensors_workspace_bytes(n_obj, n_sensor, n_step, n_env) bytes of device memory, 64-byte aligned, zeroed ONCE by
+ *               the caller (per env a ticket word that the env's last workgroup to arrive leaves at zero); one call at a time per workspace.
+ * One launch of ceil(n_obj / 512) x n_env workgroups that reads the scores once.  Refused before any launch (SSA_E_INVALID), in this
+ * order: NULL score or plan_out; a misaligned plan_out; n_sensor outside 1 .. SSA_MAX_SENSORS; n_step < 1; n_step * n_sensor >
+ * SSA_MAX_PLAN_SLOTS; n_env outside 1 .. 65535; column outside 0 .. SSA_LOOK_NSCORE - 1; n_obj < 1; n_step * n_env * n_sensor * n_obj >=
+ * 2^31; a workspace that is NULL, misaligned or too small.  The size query returns SSA_E_INVALID for the same ranges. */
+#define SSA_MAX_PLAN_SLOTS 64
+int ssa_plan_sensors_f64(const double *score, int64_t n_obj, int32_t n_sensor, int32_t n_step, int32_t n_env, int32_t column,
+                         int32_t *plan_out, int64_t *pick_out, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t ssa_plan_sensors_workspace_bytes(int64_t n_obj, int32_t n_sensor, int32_t n_step, int32_t n_env);
+
 /* ---------------------------------------------------------------- visibility screen of a synthetic orbit catalogue
  * catalogue._accepted (orbit_gen.py's acceptance rule) for n candidate element sets, the observer generalised to a network of
  * n_site ground sites.  Candidate c = elements[c] = (a, ecc, inc, raan, argp, nu) (m, -, rad) is propagated by Kepler's equation

@@ -121,6 +121,7 @@ LOOP_ARGMAX_SPOS, LOOP_DEBUG_WITHHOLD = 1, 2
 FAIL_STRIDE, FAIL_ENV, FAIL_OBJ, FAIL_STATUS, FAIL_TIME, FAIL_ERR = 8, 0, 1, 2, 3, 4
 AGENT_NAIVE_GREEDY, AGENT_VISIBLE_GREEDY, AGENT_SHANNON, AGENT_POS_ERROR, AGENT_VEL_ERROR = range(5)
 MAX_SENSORS = 8
+MAX_PLAN_SLOTS = 64
 LOOK_NSCORE, LOOK_TRACE_GAIN, LOOK_POS_TRACE_GAIN, LOOK_INFO_GAIN = 3, 0, 1, 2
 STAT_STRIDE, STAT_MAX_DPOS, STAT_CNT_LT_1E4, STAT_CNT_LT_1E7, STAT_ARGMAX_SPOS, STAT_N_FAILED, STAT_MAX_SPOS = 8, 0, 1, 2, 3, 4, 5
 
@@ -181,6 +182,8 @@ SIGNATURES = {
     "ssa_assign_sensors_envs_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "ssa_match_sensors_f64": (C.c_int, [c_dp, C.c_int64, C.c_int32, C.c_int32, c_dp, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_match_sensors_envs_f64": (C.c_int, [c_dp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
+    "ssa_plan_sensors_f64": (C.c_int, [c_dp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
+    "ssa_plan_sensors_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "ssa_peer_push_f64": (C.c_int, [c_dp, C.c_int64, c_dp, c_dp, C.c_int32, c_dp, C.c_uint64, c_dp, C.c_int64, c_dp, c_dp, c_dp]),
     "ssa_peer_wait": (C.c_int, [c_dp, C.c_int32, c_dp, C.c_uint64, C.c_int64, c_dp, c_dp]),
     "ssa_aer_obs_f64": (C.c_int, [c_dp, c_dp, c_dp, C.POINTER(ssa_consts), c_dp, C.c_int64, c_dp]),

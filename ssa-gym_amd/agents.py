@@ -16,7 +16,8 @@ filter.  On those steps the two agents may pick different objects.
 The lookahead agents of a sensor network (agent_info_gain_sensors, agent_trace_gain_sensors) also take a vector env
 (SSA_Tasker_VecEnv) and then return [E, S]: one lookahead launch and one assignment launch for all envs and one read-back of
 E x 32 bytes; vec.step_agent(agent) is the vector step that takes their rows without the host in between.
-The planners (plan_info_gain_sensors, plan_trace_gain_sensors) take a vector env too and then return [E, H', S] (section 8k)."""
+The planners (plan_info_gain_sensors, plan_trace_gain_sensors) take a vector env too and then return [E, H', S] (section 8k); so do
+the horizon-wide optimal planners (plan_info_gain_sensors_horizon, plan_trace_gain_sensors_horizon; section 8o)."""
 import numpy as np
 
 from . import _lib
@@ -268,3 +269,73 @@ def plan_info_gain_sensors(env, horizon, rule='greedy'):       # a schedule [H',
 
 def plan_trace_gain_sensors(env, horizon, rule='greedy'):      # ... over tr P- - tr P+
     return _plan_lookahead_sensors(env, horizon, _lib.LOOK_TRACE_GAIN, rule)
+
+
+# ---- the horizon-wide optimal plan: the forecast's gains are gains of a FIRST observation, so an object is
+# planned at most once per plan, and that makes the whole plan ONE assignment problem over its H' * S (step, sensor) slots -- the most
+# slots filled, then the largest total gain (ssa_plan_sensors_f64).  The planners above commit step 0 before they look at step 1 (an
+# object that is best now and almost as good later is taken now, and the object that sets before the next step is lost); these do not.
+# ONE forecast launch, ONE plan launch, ONE read-back.  H' * S is at most _lib.MAX_PLAN_SLOTS.
+def _fill_plan_horizon(env, plan):
+    """the -1 entries of a horizon-wide plan [H', S] filled, steps ascending, sensors ascending, from the action space's generator as
+    _draw_unassigned draws (env.np_random is not touched).  _fill_plan's rule would be wrong here: an idle slot can coexist with an
+    object that is visible now and planned LATER, and tasking it now would make its later forecast gain false.  So a filled slot gets an
+    object that appears NOWHERE in this env's plan (planned or filled, at any step).  Such an object cannot be a candidate of that slot
+    -- the plan would have filled the slot with it --, so its draw updates nothing the plan counts on.  If every object appears in the
+    plan already (fewer objects than slots can make it so), the row rule of _fill_plan is all that is left: an object no sensor of that
+    row holds."""
+    plan = np.array(plan, dtype=np.int64)
+    used = set(plan[plan >= 0].tolist())
+    for row in plan:
+        for s in np.flatnonzero(row < 0):
+            taken = used if len(used) < env.m else set(row[row >= 0].tolist())
+            row[s] = _draw_unassigned(env, taken)
+            used.add(int(row[s]))
+    return plan
+
+
+def _plan_horizon_steps(env, horizon):
+    """H' of the forecast a plan would come from, with the cap on H' * S checked: before any launch, before the device state is asked for"""
+    from . import device
+    if int(horizon) < 1:
+        raise ValueError("forecast_sensors: a horizon of at least one step, got %r" % (horizon,))
+    left = int(env.n - 1 - np.max(env.i))
+    Hp = min(int(horizon), left)
+    device.check_plan_slots(Hp, env.n_sensor)
+    return Hp
+
+
+def _plan_horizon_assigned(env, horizon, k):
+    """the device's part of a horizon-wide plan: int64 [H', S] ([E, H', S] of a vector env), -1 in the slots the plan leaves idle"""
+    import torch
+    S = env.n_sensor
+    if hasattr(env, "num_envs"):
+        cur = env._stream if env._inline else torch.cuda.current_stream()
+        with torch.cuda.stream(cur):
+            table = env._eng.launch_plan_sensors(env._launch_forecast_sensors(horizon), k, stream=cur.cuda_stream)
+        cur.synchronize()
+        return np.ascontiguousarray(table.cpu().numpy()[:, :, :S].astype(np.int64).transpose(1, 0, 2))
+    with torch.cuda.stream(env._stream):
+        table = env._engine.launch_plan_sensors(env.forecast_sensors(horizon), k, stream=env._stream.cuda_stream)
+    env._stream.synchronize()
+    return table.cpu().numpy()[:, :S].astype(np.int64)
+
+
+def _plan_horizon(env, horizon, k):
+    _plan_horizon_steps(env, horizon)
+    vector = hasattr(env, "num_envs")
+    if (env._eng if vector else env._engine) is None:
+        raise _lib.SsaHipError("no device state: a plan comes from the forecast, which runs on the GPU only (no CPU fallback)")
+    plan = _plan_horizon_assigned(env, horizon, k)
+    return np.stack([_fill_plan_horizon(env, p) for p in plan]) if vector else _fill_plan_horizon(env, plan)
+
+
+def plan_info_gain_sensors_horizon(env, horizon):              # a schedule [H', S] for env.rollout_sensors() ([E, H', S] of a vector
+                                                               # env, for vec.rollout_sensors()): the plan-wide optimum of 1/2 ln(det P- / det P+)
+    """the most (step, sensor) slots filled, then the largest total gain over the whole horizon, no object twice (ssa_plan_sensors_f64;
+    DESIGN.md section 8o).  H' * S > MAX_PLAN_SLOTS is a ValueError."""
+    return _plan_horizon(env, horizon, _lib.LOOK_INFO_GAIN)
+
+
+def plan_trace_gain_sensors_horizon(env, horizon):             # ... of tr P- - tr P+
+    return _plan_horizon(env, horizon, _lib.LOOK_TRACE_GAIN)

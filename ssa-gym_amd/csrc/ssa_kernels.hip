@@ -4105,6 +4105,348 @@ __global__ void __launch_bounds__(ASG_T) match_sensors_envs_kernel(const double*
                        action_out + e * SSA_MAX_SENSORS, pick_out ? pick_out + e * SSA_MAX_SENSORS * 2 : nullptr, ws + e * ws_words);
 }
 
+// ---- the horizon-wide OPTIMAL tasking plan of a sensor network (include/ssa_hip.h: ssa_plan_sensors_f64): one
+// assignment problem over the N = H' S slots (h, s) of a forecast [H'][E][S][m][3], an object planned at most once per env -- first as
+// many slots filled as possible, then the largest sum of scores -- in ONE launch, grid (chunks, envs), PLN_T threads.
+//   phase 1: a workgroup takes PLN_CH objects of one env; wavefront w does slots w, w + 16, ...: the slot's N best candidates of the chunk
+//            in the total order (score descending, object ascending) as ONE entry per lane, sorted across the wavefront.  A group of 64
+//            scores is sorted by a bitonic network over lane exchanges; the lane-wise better of the list and the reversed group is the
+//            top 64 as a bitonic sequence, six more exchange stages sort it.  A group none of whose candidates beats the list's N-th
+//            entry is skipped (a ballot).  An entry is (key, object): key = the score's bits mapped so that unsigned order is value
+//            order (-0.0 read as +0.0), 0 = none.  The lists go to the workspace; the publish and the ticket are assign_sensors_body's.
+//   phase 2: the last workgroup to arrive FOR ITS ENV merges the chunks' lists per slot the same way (chunk lists are sorted: no sort,
+//            the six merge stages only; a chunk whose best does not beat the list's N-th is skipped) into the N x N table in LDS.
+//   decide : scores -> int64 multiples of 2^(e - 52), 2^e the smallest power of two above the table's largest magnitude (exact for every
+//            table whose entries are multiples of that unit: dyadic tables are).  Columns: the table's distinct objects (<= N^2), numbered
+//            through an LDS hash table (which object gets which number never enters a decision), plus one private idle column per slot.
+//            Costs: pairs (idle, -q) ordered lexicographically and added componentwise -- an ordered group, so the shortest-augmenting-
+//            path solver (Jonker-Volgenant) runs on them unchanged and the count needs no large constant.  ONE wavefront inserts the
+//            slots in ascending order; the search is Dijkstra's over the SLOTS (a slot's <= N + 1 finite entries are relaxed one lane each;
+//            a matched column leads to exactly one slot, so the relaxations of one scan never collide), with the duals u (a register per
+//            slot), v (LDS, per column) keeping every reduced cost >= 0.
+//   ties   : slots are inserted in ascending h S + s; the unscanned slot of least distance is scanned next, the lowest slot among
+//            equals; a free column replaces the best one found so far only if strictly nearer, within one scan the entry of lowest
+//            rank in the slot's list, its idle column last; a slot's distance and predecessor change only for a strictly smaller
+//            distance; the search stops as soon as no unscanned slot is strictly nearer than the best free column.
+// ws per env: [ticket | pad to 64 bytes | nb chunks x N slots x N entries of 16 bytes]; one call at a time per workspace.
+// LDS: q 32 768 + objects 16 384 + column numbers 8 192 + the hash table, later the columns' duals 49 152 + the columns' slots 4 096
+//      + one scan's relaxations 1 280 + the result 256 + scan totals 64 + the largest magnitude, the flag 16 = 112 208 bytes.
+constexpr int PLN_T = 1024, PLN_W = PLN_T / 64, PLN_CH = 512, PLN_G = PLN_CH / 64, PLN_N = SSA_MAX_PLAN_SLOTS, PLN_PF = 8;
+constexpr int PLN_HASH = 2 * PLN_N * PLN_N, PLN_NONE = 0x7fffffff, PLN_IDLE = PLN_N, PLN_INF = 1 << 20;
+static_assert(PLN_N == 64 && PLN_HASH == 8 * PLN_T, "a slot's list is one entry per lane; eight hash slots per thread");
+struct alignas(16) PlnEnt { unsigned long long key; int j; int pad; };
+struct PlnLds {
+    long long q[PLN_N][PLN_N];                  // slot i's k-th entry: first its key, then its quantised score
+    int obj[PLN_N][PLN_N];                      // ... its object (-1: none)
+    unsigned short col[PLN_N][PLN_N];           // ... its column: first its hash slot, then its number
+    unsigned long long pool[3 * PLN_HASH / 4];  // the hash keys (int [PLN_HASH]) and numbers (short [PLN_HASH]); then vq (int64 [N^2]), vc (int [N^2])
+    signed char rowof[PLN_N * PLN_N];           // the slot a column is matched to (-1: free)
+    long long rlq[PLN_N];                       // one scan's relaxation of slot i: the distance (rlc, rlq) through entry rlk, valid if rls == the scan's stamp
+    int rlc[PLN_N], rlk[PLN_N], rls[PLN_N];
+    int res[PLN_N];                             // slot i's object
+    int wtot[PLN_W];
+    unsigned long long amax;                    // the bits of the table's largest magnitude
+    int won, pad;
+};
+static_assert(sizeof(PlnLds) == 112208, "the LDS sum of the comment above");
+SSA_DEV unsigned long long pln_key(double v)    // finite v: unsigned order of the keys = value order, -0.0 = +0.0; never 0
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v + 0.0);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+SSA_DEV double pln_val(unsigned long long k)
+{
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+SSA_DEV bool pln_before(unsigned long long k, int j, unsigned long long k2, int j2) { return k > k2 || (k == k2 && j < j2); }
+// one exchange stage: lanes l and l ^ d compare; the lane with keep_first keeps the entry that comes first
+// lane l ^ d's value, d a power of two below 64, all 64 lanes active: DPP inside a row of 16 (quad permutes for 1 and 2, half-row mirror
+// then quad reversal for 4 -- l ^ 7 ^ 3 --, a rotation by 8 for 8) and gfx950's row and half swaps for 16 and 32: no LDS-crossbar traffic,
+// which sixteen wavefronts sorting at once would otherwise queue for
+SSA_DEV int pln_x32(int v, int d, int lane)
+{
+    typedef unsigned pair_t __attribute__((ext_vector_type(2)));
+    switch (d) {
+        case 1: return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
+        case 2: return __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);
+        case 4: return __builtin_amdgcn_update_dpp(0, __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true), 0x1B, 0xF, 0xF, true);
+        case 8: return __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, true);
+        case 16: {
+            const pair_t r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+            return (int)((lane & 16) ? r[0] : r[1]);
+        }
+        default: {
+            const pair_t r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+            return (int)((lane & 32) ? r[0] : r[1]);
+        }
+    }
+}
+SSA_DEV unsigned long long pln_x64(unsigned long long v, int d, int lane)
+{
+    const unsigned lo = (unsigned)pln_x32((int)(unsigned)v, d, lane), hi = (unsigned)pln_x32((int)(unsigned)(v >> 32), d, lane);
+    return ((unsigned long long)hi << 32) | lo;
+}
+SSA_DEV void pln_cx(unsigned long long& k, int& j, int d, bool keep_first, int lane)
+{
+    const unsigned long long k2 = pln_x64(k, d, lane);
+    const int j2 = pln_x32(j, d, lane);
+    if (pln_before(k, j, k2, j2) != keep_first) { k = k2; j = j2; }
+}
+SSA_DEV void pln_sort(unsigned long long& k, int& j, int lane)       // 64 entries, the first in lane 0
+{
+#pragma unroll
+    for (int size = 2; size <= 64; size <<= 1)
+#pragma unroll
+        for (int d = size >> 1; d > 0; d >>= 1) pln_cx(k, j, d, ((lane & d) == 0) == ((lane & size) == 0), lane);
+}
+SSA_DEV void pln_merge(unsigned long long& lk, int& lj, unsigned long long ck, int cj, int lane)      // both sorted; the first 64 of the union
+{
+    const unsigned long long rk = __shfl(ck, 63 - lane, 64);
+    const int rj = __shfl(cj, 63 - lane, 64);
+    if (pln_before(rk, rj, lk, lj)) { lk = rk; lj = rj; }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) pln_cx(lk, lj, d, (lane & d) == 0, lane);
+}
+SSA_DEV bool pln_less(int c, long long q, int c2, long long q2) { return c < c2 || (c == c2 && q < q2); }
+SSA_DEV void pln_wave_min(int& c, long long& q, int& id, int lane)      // the least (c, q, id) of the wavefront, in every lane (distinct id: the merge commutes)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int c2 = pln_x32(c, off, lane), id2 = pln_x32(id, off, lane);
+        const long long q2 = (long long)pln_x64((unsigned long long)q, off, lane);
+        if (pln_less(c2, q2, c, q) || (c2 == c && q2 == q && id2 < id)) { c = c2; q = q2; id = id2; }
+    }
+}
+SSA_DEV void pln_wave_sync()        // LDS written by one lane, read by another lane of the SAME wavefront
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+// the deciding part: ONE wavefront over the table in LDS; lane i is slot i (its dual, its matched entry) and, within a scan, entry k = lane
+SSA_DEV void pln_decide(PlnLds& L, int N, int lane)
+{
+    long long* vq = reinterpret_cast<long long*>(L.pool);
+    int* vc = reinterpret_cast<int*>(L.pool + PLN_N * PLN_N);
+    int uc = 0, mk = -1, vidc = 0;              // slot `lane`: its dual, its matched entry (PLN_IDLE: its idle column), its idle column's dual
+    long long uq = 0, vidq = 0;
+    int stamp = 1;
+    for (int i0 = 0; i0 < N; ++i0) {
+        {   // u[i0] = its least cost less the column's dual: every reduced cost of the new slot >= 0 (its idle column's dual is still 0)
+            const int cn = (lane < N) ? (int)L.col[i0][lane] : 0xffff;
+            int c = PLN_INF, id = lane;
+            long long q = 0;
+            if (cn != 0xffff) { c = -vc[cn]; q = -L.q[i0][lane] - vq[cn]; }
+            pln_wave_min(c, q, id, lane);
+            if (!pln_less(c, q, 1, 0)) { c = 1; q = 0; }
+            if (lane == i0) { uc = c; uq = q; }
+        }
+        int Dc = (lane == i0) ? 0 : PLN_INF, pred = -1, predk = -1;
+        long long Dq = 0;
+        bool vis = false;
+        int bc = PLN_INF, brow = -1, bk = -1;
+        long long bq = 0;
+        for (int scan = 0; scan < N; ++scan) {      // (every scan takes a new slot: N at most)
+            int mc = vis ? PLN_INF : Dc, mi = lane;
+            long long mq = vis ? 0 : Dq;
+            pln_wave_min(mc, mq, mi, lane);
+            if (mc >= PLN_INF || !pln_less(mc, mq, bc, bq)) break;
+            if (lane == mi) vis = true;
+            const int uic = __shfl(uc, mi, 64), mkm = __shfl(mk, mi, 64), vic = __shfl(vidc, mi, 64);
+            const long long uiq = __shfl(uq, mi, 64), viq = __shfl(vidq, mi, 64);
+            const int cn = (lane < N) ? (int)L.col[mi][lane] : 0xffff;
+            int sc = PLN_INF, sk = lane;
+            long long sq = 0;
+            if (cn != 0xffff) {
+                const int nc = mc - uic - vc[cn];
+                const long long nq = mq - L.q[mi][lane] - uiq - vq[cn];
+                const int owner = L.rowof[cn];
+                if (owner < 0) { sc = nc; sq = nq; }
+                else if (owner != mi) { L.rlc[owner] = nc; L.rlq[owner] = nq; L.rlk[owner] = lane; L.rls[owner] = stamp; }
+            }
+            pln_wave_sync();
+            if (!vis && L.rls[lane] == stamp && pln_less(L.rlc[lane], L.rlq[lane], Dc, Dq)) {
+                Dc = L.rlc[lane]; Dq = L.rlq[lane]; pred = mi; predk = L.rlk[lane];
+            }
+            pln_wave_min(sc, sq, sk, lane);
+            if (mkm != PLN_IDLE) {      // its idle column is free: the last of the scan's candidates
+                const int ic = mc + 1 - uic - vic;
+                const long long iq = mq - uiq - viq;
+                if (pln_less(ic, iq, sc, sq)) { sc = ic; sq = iq; sk = PLN_IDLE; }
+            }
+            if (pln_less(sc, sq, bc, bq)) { bc = sc; bq = sq; brow = mi; bk = sk; }
+            ++stamp;
+        }
+        // the duals: every scanned slot rises by what it was nearer than the free column, its matched column falls by as much
+        if (vis) {
+            const int dc = bc - Dc;
+            const long long dq = bq - Dq;
+            uc += dc; uq += dq;
+            if (mk == PLN_IDLE) { vidc -= dc; vidq -= dq; }
+            else if (mk >= 0) { const int cn = L.col[lane][mk]; vc[cn] -= dc; vq[cn] -= dq; }
+        }
+        // the augmenting path, back from the free column to the new slot
+        for (int r = brow, k = bk, hop = 0; hop < N; ++hop) {      // (a path visits a slot once: N hops at most)
+            const int pr = __shfl(pred, r, 64), pk = __shfl(predk, r, 64);
+            if (lane == r) {
+                mk = k;
+                if (k != PLN_IDLE) L.rowof[L.col[r][k]] = (signed char)r;
+            }
+            if (r == i0) break;
+            r = pr; k = pk;
+        }
+        pln_wave_sync();
+    }
+    L.res[lane] = (lane < N && mk >= 0 && mk != PLN_IDLE) ? L.obj[lane][mk] : -1;
+    pln_wave_sync();
+}
+__global__ void __launch_bounds__(PLN_T) plan_sensors_kernel(const double* __restrict__ score, int64_t m, int S, int H, int col,
+                                                             int32_t* __restrict__ plan_out, int64_t* __restrict__ pick_out,
+                                                             unsigned long long* ws_all, int64_t ws_words)
+{
+    __shared__ PlnLds L;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, N = H * S;
+    const int64_t e = blockIdx.y, E = gridDim.y;
+    unsigned long long* ws = ws_all + e * ws_words;
+    PlnEnt* parts = reinterpret_cast<PlnEnt*>(ws + 8);
+    const int64_t j0 = (int64_t)blockIdx.x * PLN_CH;
+    for (int i = wave; i < N; i += PLN_W) {
+        const int h = i / S, s = i - h * S;
+        const double* base = score + (((int64_t)h * E + e) * S + s) * m * SSA_LOOK_NSCORE + col;
+        double v[PLN_G];
+#pragma unroll
+        for (int g = 0; g < PLN_G; ++g) {
+            const int64_t jj = j0 + g * 64 + lane;
+            v[g] = (jj < m) ? base[jj * SSA_LOOK_NSCORE] : __builtin_nan("");
+        }
+        unsigned long long lk = 0;
+        int lj = PLN_NONE;
+#pragma unroll
+        for (int g = 0; g < PLN_G; ++g) {
+            const bool ok = fabs(v[g]) <= 0x1p1020;       // (NaN, +-inf, out of range: false)
+            unsigned long long ck = ok ? pln_key(v[g]) : 0ull;
+            int cj = ok ? (int)(j0 + g * 64 + lane) : PLN_NONE;
+            const unsigned long long wk = __shfl(lk, N - 1, 64);
+            const int wj = __shfl(lj, N - 1, 64);
+            if (!__any(ok && pln_before(ck, cj, wk, wj))) continue;
+            pln_sort(ck, cj, lane);
+            pln_merge(lk, lj, ck, cj, lane);
+        }
+        if (lane < N) {
+            PlnEnt c;
+            c.key = lk; c.j = lj; c.pad = 0;
+            parts[((int64_t)blockIdx.x * N + i) * N + lane] = c;
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const bool won = atomicInc(reinterpret_cast<unsigned int*>(ws), gridDim.x - 1) == gridDim.x - 1;
+        if (won) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        L.won = won;
+        L.amax = 0;
+    }
+    __syncthreads();
+    if (!L.won) return;
+    const int nb = (int)gridDim.x;
+    for (int i = wave; i < N; i += PLN_W) {
+        unsigned long long lk = 0;
+        int lj = PLN_NONE;
+        for (int b0 = 0; b0 < nb; b0 += PLN_PF) {
+            PlnEnt c[PLN_PF];
+#pragma unroll
+            for (int p = 0; p < PLN_PF; ++p) {
+                c[p].key = 0; c[p].j = PLN_NONE;
+                if (lane < N && b0 + p < nb) c[p] = parts[((int64_t)(b0 + p) * N + i) * N + lane];
+            }
+#pragma unroll
+            for (int p = 0; p < PLN_PF; ++p) {
+                const unsigned long long fk = __shfl(c[p].key, 0, 64), wk = __shfl(lk, N - 1, 64);
+                const int fj = __shfl(c[p].j, 0, 64), wj = __shfl(lj, N - 1, 64);
+                if (!pln_before(fk, fj, wk, wj)) continue;
+                pln_merge(lk, lj, c[p].key, c[p].j, lane);
+            }
+        }
+        const bool has = lane < N && lj != PLN_NONE;
+        L.q[i][lane] = (long long)lk;
+        L.obj[i][lane] = has ? lj : -1;
+        unsigned long long a = has ? (unsigned long long)__double_as_longlong(fabs(pln_val(lk))) : 0ull;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long a2 = __shfl_xor(a, off, 64);
+            a = a2 > a ? a2 : a;
+        }
+        if (lane == 0) atomicMax(&L.amax, a);
+    }
+    int* hkey = reinterpret_cast<int*>(L.pool);
+    unsigned short* hid = reinterpret_cast<unsigned short*>(L.pool + PLN_HASH / 2);
+#pragma unroll
+    for (int p = 0; p < PLN_HASH / PLN_T; ++p) hkey[t + PLN_T * p] = -1;
+    __syncthreads();
+    int ex;
+    (void)frexp(__longlong_as_double((long long)L.amax), &ex);      // amax < 2^ex, the smallest such power of two
+    for (int idx = t; idx < N * PLN_N; idx += PLN_T) {
+        const int i = idx >> 6, k = idx & 63, o = L.obj[i][k];
+        if (o < 0) { L.col[i][k] = 0xffff; continue; }
+        L.q[i][k] = (long long)rint(ldexp(pln_val((unsigned long long)L.q[i][k]), 52 - ex));      // |q| <= 2^52
+        unsigned slot = ((unsigned)o * 2654435761u) >> 19;
+        for (;;) {
+            const int old = atomicCAS(&hkey[slot], -1, o);
+            if (old == -1 || old == o) break;
+            slot = (slot + 1) & (PLN_HASH - 1);
+        }
+        L.col[i][k] = (unsigned short)slot;
+    }
+    __syncthreads();
+    {   // number the occupied hash slots 0, 1, ...: eight slots per thread, a scan over the workgroup
+        int cnt = 0;
+#pragma unroll
+        for (int p = 0; p < 8; ++p) cnt += hkey[8 * t + p] != -1;
+        int inc = cnt;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int up = __shfl_up(inc, off, 64);
+            if (lane >= off) inc += up;
+        }
+        if (lane == 63) L.wtot[wave] = inc;
+        __syncthreads();
+        int at = inc - cnt;
+        for (int w = 0; w < wave; ++w) at += L.wtot[w];
+#pragma unroll
+        for (int p = 0; p < 8; ++p)
+            if (hkey[8 * t + p] != -1) hid[8 * t + p] = (unsigned short)at++;
+    }
+    __syncthreads();
+    for (int idx = t; idx < N * PLN_N; idx += PLN_T) {
+        const int i = idx >> 6, k = idx & 63;
+        if (L.col[i][k] != 0xffff) L.col[i][k] = hid[L.col[i][k]];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < 3 * PLN_HASH / 4 / PLN_T; ++p) L.pool[t + PLN_T * p] = 0;      // the columns' duals
+    reinterpret_cast<int*>(L.rowof)[t] = -1;
+    if (t < PLN_N) L.rls[t] = 0;
+    __syncthreads();
+    if (t >= 64) return;
+    pln_decide(L, N, lane);
+    // the rows of this env: [H][E][SSA_MAX_SENSORS], -1 beyond S and in unfilled slots; the picks' scores are read where they were read first
+    for (int idx = lane; idx < H * SSA_MAX_SENSORS; idx += 64) {
+        const int h = idx >> 3, s = idx & 7;
+        const int o = (s < S) ? L.res[h * S + s] : -1;
+        const int64_t row = ((int64_t)h * E + e) * SSA_MAX_SENSORS + s;
+        plan_out[row] = o;
+        if (pick_out) {
+            pick_out[2 * row] = o;
+            pick_out[2 * row + 1] = (o >= 0) ? __double_as_longlong(score[((((int64_t)h * E + e) * S + s) * m + o) * SSA_LOOK_NSCORE + col]) : 0;
+        }
+    }
+}
+
 // ---- diagnostic reductions of SURVEY 8f-4 (ssa_tasker_simple_2.py:436-446, 750-775): NEES = d^T inv(P) d with
 // d = x_true - x_filter, NIS = y^T inv(S) y.  One lane per (step, object): Gaussian elimination with partial pivoting on
 // the augmented system [P | d] (the arithmetic class of numpy.linalg.inv's LU), then the dot product.
@@ -5180,6 +5522,30 @@ int ssa_match_sensors_envs_f64(const double* score, int64_t n_obj, int32_t n_sen
     if (need < 0 || !assign_envs_fit(n_obj, n_sensor, n_env)) return SSA_E_INVALID;
     hipLaunchKernelGGL(match_sensors_envs_kernel, dim3(nblk(n_obj, ASG_CH), (unsigned)n_env), dim3(ASG_T), 0, (hipStream_t)stream, score,
                        n_obj, (int)n_sensor, (int)column, fallback, action_out, pick_out, (unsigned long long*)workspace, need / n_env / 8);
+    return launch_status();
+}
+
+// ---- the horizon-wide optimal plan (plan_sensors_kernel): the argument rules in the header's order; the workspace size, or SSA_E_INVALID
+static int64_t plan_sensors_need(int64_t n_obj, int32_t n_sensor, int32_t n_step, int32_t n_env, int32_t column)
+{
+    if (n_sensor < 1 || n_sensor > SSA_MAX_SENSORS || n_step < 1 || (int64_t)n_step * n_sensor > SSA_MAX_PLAN_SLOTS) return SSA_E_INVALID;
+    if (n_env < 1 || n_env > 65535 || column < 0 || column >= SSA_LOOK_NSCORE || n_obj < 1) return SSA_E_INVALID;
+    const int64_t N = (int64_t)n_step * n_sensor;
+    if (n_obj > 0x7fffffffll / (N * n_env)) return SSA_E_INVALID;       // (n_step n_env n_sensor n_obj >= 2^31)
+    return n_env * (64 + (int64_t)nblk(n_obj, PLN_CH) * N * N * (int64_t)sizeof(PlnEnt));
+}
+int64_t ssa_plan_sensors_workspace_bytes(int64_t n_obj, int32_t n_sensor, int32_t n_step, int32_t n_env)
+{
+    return plan_sensors_need(n_obj, n_sensor, n_step, n_env, 0);
+}
+int ssa_plan_sensors_f64(const double* score, int64_t n_obj, int32_t n_sensor, int32_t n_step, int32_t n_env, int32_t column,
+                         int32_t* plan_out, int64_t* pick_out, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    if (!score || !row_aligned(plan_out)) return SSA_E_INVALID;
+    const int64_t need = plan_sensors_need(n_obj, n_sensor, n_step, n_env, column);
+    if (need < 0 || !workspace || ((uintptr_t)workspace & 63) || workspace_bytes < need) return SSA_E_INVALID;
+    hipLaunchKernelGGL(plan_sensors_kernel, dim3(nblk(n_obj, PLN_CH), (unsigned)n_env), dim3(PLN_T), 0, (hipStream_t)stream, score, n_obj,
+                       (int)n_sensor, (int)n_step, (int)column, plan_out, pick_out, (unsigned long long*)workspace, need / n_env / 8);
     return launch_status();
 }
 

@@ -385,6 +385,52 @@ def assign_sensors_envs(score, column, fallback=None, out=None, picks=None, work
     return out
 
 
+def check_plan_slots(n_step, n_sensor):
+    """a plan has at most MAX_PLAN_SLOTS (step, sensor) slots: a ValueError that names the cap, before any launch"""
+    if int(n_step) * int(n_sensor) > _lib.MAX_PLAN_SLOTS:
+        raise ValueError("a horizon-wide plan has at most %d (step, sensor) slots (SSA_MAX_PLAN_SLOTS), got %d steps x %d sensors = %d"
+                         % (_lib.MAX_PLAN_SLOTS, n_step, n_sensor, int(n_step) * int(n_sensor)))
+
+
+def plan_sensors_workspace(n_obj, n_sensor, n_step, n_env, device):
+    """zeroed workspace of ssa_plan_sensors_f64 for n_env envs of n_step x n_sensor slots over n_obj objects each (one call at a time:
+    keep it with the stream that uses it; the kernel leaves it ready for the next call)"""
+    check_plan_slots(n_step, n_sensor)
+    nbytes = int(_lib.load().ssa_plan_sensors_workspace_bytes(int(n_obj), int(n_sensor), int(n_step), int(n_env)))
+    if nbytes < 0:
+        raise _lib.SsaHipError("ssa_plan_sensors_workspace_bytes(%d, %d, %d, %d) failed with code %d" % (n_obj, n_sensor, n_step, n_env, nbytes))
+    return torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
+
+
+def plan_sensors(score, column, out=None, picks=None, workspace=None):
+    """the horizon-wide optimal tasking plan of a sensor network on the device (ssa_plan_sensors_f64): ONE assignment problem over all
+    H' * S (step, sensor) slots of column `column` (_lib.LOOK_*) of a forecast's scores -- [H', S, m, 3] (one env: what
+    launch_forecast_sensors leaves) or [H', E, S, m, 3] (what launch_forecast_sensors_envs leaves) -- in ONE launch: the most slots
+    filled, then the largest sum of scores, no object twice in an env's plan; finite scores of magnitude <= 2^1020 only.  Returns the
+    int32 CUDA table [H', MAX_SENSORS] or [H', E, MAX_SENSORS] (`out`: a 32-byte aligned table to write; -1 beyond S and in unfilled
+    slots): the schedule launch_rollout_sensors / launch_rollout_sensors_envs takes.  picks: int64 [H', (E,) MAX_SENSORS, 2] to receive
+    the objects and their scores' bit patterns.  workspace: plan_sensors_workspace (default: a fresh one).  H' * S > MAX_PLAN_SLOTS is a
+    ValueError.  No host sync."""
+    if not (isinstance(score, torch.Tensor) and score.is_cuda and score.dtype == f64 and score.is_contiguous() and score.dim() in (4, 5)
+            and score.shape[-1] == _lib.LOOK_NSCORE):
+        raise _lib.SsaHipError("score must be a contiguous CUDA float64 tensor [H', S, m, %d] or [H', E, S, m, %d]" % ((_lib.LOOK_NSCORE,) * 2))
+    Hp, S, m = int(score.shape[0]), int(score.shape[-3]), int(score.shape[-2])
+    E = int(score.shape[1]) if score.dim() == 5 else 1
+    check_plan_slots(Hp, S)
+    lib = _lib.load()
+    W = _lib.MAX_SENSORS
+    out = torch.empty(tuple(score.shape[:-3]) + (W,), dtype=torch.int32, device=score.device) if out is None else out
+    ws = plan_sensors_workspace(m, S, Hp, E, score.device) if workspace is None else workspace
+    ptr = {}
+    for t, name, dtype, n in ((out, "out", torch.int32, Hp * E * W), (picks, "picks", torch.int64, 2 * Hp * E * W)):
+        ptr[name] = None if t is None else _chk(t, name, dtype)
+        if t is not None and t.numel() != n:
+            raise _lib.SsaHipError("%s must hold %d %s words" % (name, n, dtype))
+    _lib.check(lib.ssa_plan_sensors_f64(score.data_ptr(), m, S, Hp, E, int(column), ptr["out"], ptr["picks"],
+                                        _chk(ws, "workspace", torch.int64), ws.numel() * 8, _stream()), "ssa_plan_sensors_f64")
+    return out
+
+
 def env_step(consts, params):
     """E1: the fused step.  `params` is a filled _lib.ssa_step_params."""
     lib = _lib.load()

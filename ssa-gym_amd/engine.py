@@ -115,6 +115,7 @@ class HotPathEngine:
         self._fore = None                               # ... and of launch_forecast_sensors
         self._assign_ws = None                          # (S, workspace) of launch_assign_sensors
         self._assign_row = None                         # assign_row()'s
+        self._plan = None                               # (shape, table, workspace) of launch_plan_sensors
         self._sensor_envs = None                        # launch_step_sensors_envs: its block, the [E][8] action table and its staging
         self._look_se = None                            # output buffers of launch_lookahead_sensors_envs
         self._assign_envs_ws = None                     # (S, workspace) of launch_assign_sensors_envs
@@ -687,6 +688,38 @@ class HotPathEngine:
                                        action_row.data_ptr(), picks.data_ptr() if picks is not None else 0, ws.data_ptr(), ws.numel() * 8, s)
         if rc:
             raise _lib.SsaHipError("%s failed with code %d" % (entry, rc))
+
+    def launch_plan_sensors(self, forecast, column, picks=None, stream=None):
+        """enqueue the horizon-wide optimal tasking plan (include/ssa_hip.h: ssa_plan_sensors_f64) on `forecast`, the dict
+        launch_forecast_sensors or launch_forecast_sensors_envs returned: ONE assignment problem over all H' * S (step, sensor) slots of
+        score column `column` (_lib.LOOK_*) -- the most slots filled, then the largest sum of scores, no object twice in an env's plan --
+        in ONE launch.  Returns this engine's own int32 CUDA table, [H', MAX_SENSORS] for scores [H', S, m, 3] and [H', E, MAX_SENSORS]
+        for scores [H', E, S, m, 3] (-1 beyond S and in unfilled slots): the schedule launch_rollout_sensors / launch_rollout_sensors_envs
+        takes as it is.  picks: int64 CUDA [H', (E,) MAX_SENSORS, 2] or None.  The table and the workspace are cached as the forecast's
+        buffers are (allocated on first use, again when H' or S changes).  H' * S > MAX_PLAN_SLOTS is a ValueError.  Asynchronous, no
+        host sync."""
+        score = forecast["score"]
+        ok = isinstance(score, torch.Tensor) and score.is_cuda and score.dtype == torch.float64 and score.is_contiguous()
+        if not (ok and score.dim() in (4, 5) and score.shape[-1] == _lib.LOOK_NSCORE and score.shape[-2] == self.m
+                and (score.dim() == 4 or score.shape[1] == self.E) and (score.dim() == 5 or self.E == 1)):
+            raise _lib.SsaHipError("plan: the contiguous CUDA float64 [H', S, %d, %d] (or [H', %d, S, %d, %d]) scores of a forecast are "
+                                   "needed" % (self.m, _lib.LOOK_NSCORE, self.E, self.m, _lib.LOOK_NSCORE))
+        Hp, S = int(score.shape[0]), int(score.shape[-3])
+        device.check_plan_slots(Hp, S)
+        lead = tuple(score.shape[:-3])
+        if picks is not None and not (isinstance(picks, torch.Tensor) and picks.is_cuda and picks.dtype == torch.int64 and picks.is_contiguous()
+                                      and picks.numel() == 2 * Hp * self.E * _lib.MAX_SENSORS):
+            raise _lib.SsaHipError("plan: picks must be a contiguous CUDA int64 tensor of %d elements" % (2 * Hp * self.E * _lib.MAX_SENSORS))
+        if self._plan is None or self._plan[0] != (lead, S):
+            self._plan = ((lead, S), torch.full(lead + (_lib.MAX_SENSORS,), -1, dtype=torch.int32, device=self.dev),
+                          device.plan_sensors_workspace(self.m, S, Hp, self.E, self.dev))
+        table, ws = self._plan[1], self._plan[2]
+        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        rc = self._lib.ssa_plan_sensors_f64(score.data_ptr(), self.m, S, Hp, self.E, int(column), table.data_ptr(),
+                                            picks.data_ptr() if picks is not None else 0, ws.data_ptr(), ws.numel() * 8, s)
+        if rc:
+            raise _lib.SsaHipError("ssa_plan_sensors_f64 failed with code %d" % rc)
+        return table
 
     def assign_row(self):
         """this engine's own int32 [MAX_SENSORS] action row, for a caller of launch_assign_sensors that reads one assignment back
