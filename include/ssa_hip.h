@@ -706,6 +706,60 @@ int ssa_forecast_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_
 int ssa_forecast_sensors_envs_f64(const ssa_consts *c, const ssa_step_params *p, const ssa_sensor_params *sites,
                                   const ssa_forecast_params *f, void *stream);
 
+/* ---------------------------------------------------------------- the dry run of B candidate schedules, one launch
+ * What a K-step tasking schedule would be worth if it were run: ssa_env_rollout_sensors_envs_f64 with every innovation equal to zero
+ * and nothing written but the records below.  The covariance update does not depend on the measurement drawn (P+ = P- - K S K^T) and
+ * under the filter's own model the expected posterior mean is the prior mean, so per pseudo-env e (a block of n_obj rows -- one
+ * candidate schedule) and step k = 0 .. K-1:
+ *   predict: every row exactly as an idle step predicts it, time index env_time[e] + time_offset + k;
+ *   actions: row (k, e) of `actions`, read as ssa_env_rollout_sensors_envs_f64 reads it -- entries s >= n_sensor are ignored; < 0 or
+ *            >= n_obj_caller: idle; two sensors on one object: the lowest-numbered one updates it; update_interval is honoured;
+ *   update : a row whose caller's index (obj_ids, else its index in the env) is sensor s's action runs the sensor step's update from
+ *            site s (visibility of the true state, S, its inverse, K), commits P+ = P- - K S K^T to the resident tile and leaves x as
+ *            the predict left it.  P+ is the step's and the lookahead's, bit for bit.  The measurement noise is never read;
+ *   status : the step's -- SSA_ST_UPDATE_LINALG (singular S) fails the filter from then on, the failure sentinels in the tile; a
+ *            later slot on that object is not attempted.  SSA_ST_UPDATE_NAN cannot arise.  Without a ring a failed row follows the
+ *            forecast: failed at entry -- it passes through from the input block; failed inside the horizon -- the sentinels.
+ * Output: one record of SSA_DRY_STRIDE doubles per slot, out[((k*E + e)*S + s)*SSA_DRY_STRIDE + ...]:
+ *   SSA_DRY_ACTION : the caller's index of the object if the update was attempted, else -1 (as SSA_UPD_ACTION)
+ *   SSA_DRY_VISIBLE, SSA_DRY_TAKEN : 1 / 0
+ *   SSA_DRY_STATUS : the SSA_ST_* the object carries after the step; 0 for a slot that updates nobody
+ *   SSA_DRY_SCORE + SSA_LOOK_TRACE_GAIN / POS_TRACE_GAIN / INFO_GAIN: from this step's P- and P+ exactly as ssa_lookahead_sensors_f64
+ *                    computes them; NaN unless taken
+ *   SSA_DRY_SPARE  : 0
+ * A slot that updates nobody -- idle, out of range, a lower sensor's object, a step the interval skips -- gets the cleared record
+ * (ACTION -1, zeros, NaN scores), written by the env's first row; a tasked filter that has failed gets ACTION -1, zeros, its status
+ * and NaN scores from its own row.  A valid action that no row of its env holds (obj_ids) leaves its record unwritten.  Nothing else
+ * is written: no ring slot, status word, failure record, statistics word, observation row or update record; the tile is not stored.
+ * Of ssa_step_params it reads the INPUT fields ssa_forecast_sensors_envs_f64 reads; obj_ids is per env, and an id of -1 marks a padding
+ * row that matches no action and writes nothing; launch_mask is not honoured (the time words come from env_time).  Of `sites`:
+ * n_sensor, enu, obs_itrs, obs_limit and R.  One launch.
+ * Refused before any launch: every refusal of ssa_forecast_sensors_envs_f64 that applies (with d->out as its output), a NULL `d`,
+ * n_steps < 1, NULL or misaligned `actions`, NULL `out`, n_obj_caller < 1, n_env * n_sensor * n_steps >= 2^31 (SSA_E_INVALID);
+ * several envs with n_obj % 4 != 0 (SSA_E_UNSUPPORTED: whole tiles per env).  n_env == 1 is accepted for any n_obj: the full-catalogue
+ * form on a ring slot. */
+#define SSA_DRY_STRIDE 8
+#define SSA_DRY_ACTION 0
+#define SSA_DRY_VISIBLE 1
+#define SSA_DRY_TAKEN 2
+#define SSA_DRY_STATUS 3
+#define SSA_DRY_SCORE 4
+#define SSA_DRY_SPARE 7
+typedef struct ssa_dryrun_sensors_params {
+    int32_t n_steps;          /* K >= 1 */
+    int32_t n_obj_caller;     /* actions >= this are idle: the catalogue's size, which a gathered block's n_obj is not */
+    const int32_t *actions;   /* [K][E][SSA_MAX_SENSORS] device words, 32-byte aligned, read-only */
+    double *out;              /* [K][E][S][SSA_DRY_STRIDE], required */
+} ssa_dryrun_sensors_params;
+int ssa_dryrun_sensors_envs_f64(const ssa_consts *c, const ssa_step_params *p, const ssa_sensor_params *sites,
+                                const ssa_dryrun_sensors_params *d, void *stream);
+/* ... and the totals of its records: total[e*SSA_LOOK_NSCORE + c] = the sum of SSA_DRY_SCORE + c over env e's slots with SSA_DRY_TAKEN
+ * set, added in slot order (k outer, s inner) in fp64 -- one defined sum per candidate and column; 0 for a candidate that takes nothing.
+ * records: [K][E][S][SSA_DRY_STRIDE] as ssa_dryrun_sensors_envs_f64 leaves them; total: [E][SSA_LOOK_NSCORE].  One launch.
+ * Refused before any launch (SSA_E_INVALID): NULL records or total, a count < 1, n_sensor > SSA_MAX_SENSORS,
+ * n_env * n_sensor * n_steps >= 2^31. */
+int ssa_dryrun_totals_f64(const double *records, int32_t n_env, int32_t n_steps, int32_t n_sensor, double *total, void *stream);
+
 /* ---------------------------------------------------------------- the tasking assignment of a sensor network, on the device
  * One object per sensor from one column of the scores ssa_lookahead_sensors_f64 leaves, in ONE launch and written where the next launch
  * reads it: the global greedy assignment of agents._assign_lookahead_sensors (S ssa_masked_argmax_f64 launches, S read-backs and the

@@ -89,6 +89,10 @@ class ssa_forecast_params(C.Structure):
     _fields_ = [("n_steps", C.c_int32), ("reserved", C.c_int32), ("out", ssa_lookahead_out)]
 
 
+class ssa_dryrun_sensors_params(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("n_obj_caller", C.c_int32), ("actions", c_dp), ("out", c_dp)]
+
+
 class ssa_screen_params(C.Structure):
     _fields_ = [
         ("n", C.c_int64), ("n_time", C.c_int32), ("n_site", C.c_int32), ("step", C.c_double), ("min_alt", C.c_double),
@@ -123,6 +127,7 @@ AGENT_NAIVE_GREEDY, AGENT_VISIBLE_GREEDY, AGENT_SHANNON, AGENT_POS_ERROR, AGENT_
 MAX_SENSORS = 8
 MAX_PLAN_SLOTS = 64
 LOOK_NSCORE, LOOK_TRACE_GAIN, LOOK_POS_TRACE_GAIN, LOOK_INFO_GAIN = 3, 0, 1, 2
+DRY_STRIDE, DRY_ACTION, DRY_VISIBLE, DRY_TAKEN, DRY_STATUS, DRY_SCORE, DRY_SPARE = 8, 0, 1, 2, 3, 4, 7
 STAT_STRIDE, STAT_MAX_DPOS, STAT_CNT_LT_1E4, STAT_CNT_LT_1E7, STAT_ARGMAX_SPOS, STAT_N_FAILED, STAT_MAX_SPOS = 8, 0, 1, 2, 3, 4, 5
 
 # every symbol the header declares, with its ctypes signature
@@ -152,6 +157,9 @@ SIGNATURES = {
                                            C.POINTER(ssa_forecast_params), c_dp]),
     "ssa_forecast_sensors_envs_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
                                                 C.POINTER(ssa_forecast_params), c_dp]),
+    "ssa_dryrun_sensors_envs_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
+                                              C.POINTER(ssa_dryrun_sensors_params), c_dp]),
+    "ssa_dryrun_totals_f64": (C.c_int, [c_dp, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp]),
     "ssa_env_rollout_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_rollout_params),
                                               C.POINTER(ssa_sensor_params), C.POINTER(ssa_rollout_sensors_params), c_dp]),
     "ssa_env_rollout_sensors_envs_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_rollout_params),

@@ -339,3 +339,58 @@ def plan_info_gain_sensors_horizon(env, horizon):              # a schedule [H',
 
 def plan_trace_gain_sensors_horizon(env, horizon):             # ... of tr P- - tr P+
     return _plan_horizon(env, horizon, _lib.LOOK_TRACE_GAIN)
+
+
+# ---- search on top of the dry run: env.evaluate_schedules() values whole schedules -- revisits included, which
+# no forecast can value -- so a planner can compare candidates from one state.  The smallest such planner: local search around a plan.
+REFINE_KINDS = {'info': _lib.LOOK_INFO_GAIN, 'trace': _lib.LOOK_TRACE_GAIN, 'pos_trace': _lib.LOOK_POS_TRACE_GAIN}
+
+
+def refine_plan_sensors(env, plan, kind='info', rounds=4, candidates=64, seed=0):
+    """a schedule [K', S] for env.rollout_sensors(), no worse than `plan` under the dry run: `rounds` rounds of `candidates` schedules,
+    each scored by ONE env.evaluate_schedules() launch.  Candidate 0 is the incumbent; every other one is the incumbent with one slot
+    (k, s) redrawn from the objects the forecast shows visible to s at step k with status OK and not already in row k -- an object
+    planned at another step is allowed: the revisit the forecast planners cannot express.  The incumbent becomes the first candidate
+    with the largest total in column `kind` ('info', 'trace', 'pos_trace').  ONE forecast launch for the masks.  The draws come from
+    RandomState(seed): env.np_random and the action space's generator are not touched.  Returns (plan, total [3] float64 of it)."""
+    if kind not in REFINE_KINDS:
+        raise ValueError("refine_plan_sensors: kind must be one of %s, got %r" % (sorted(REFINE_KINDS), kind))
+    if int(rounds) < 0 or int(candidates) < 1:
+        raise ValueError("refine_plan_sensors: rounds >= 0 and candidates >= 1, got %r and %r" % (rounds, candidates))
+    if hasattr(env, "num_envs"):
+        raise _lib.SsaHipError("refine_plan_sensors covers a single env (the vector env has no dry run yet)")
+    if env._engine is None:
+        raise _lib.SsaHipError("no device state: a plan is refined by dry runs, which run on the GPU only (no CPU fallback)")
+    col = REFINE_KINDS[kind]
+    plan = np.array(plan, dtype=np.int64)
+    if plan.ndim != 2 or plan.shape[1] != env.n_sensor:
+        raise ValueError("refine_plan_sensors: a plan [K, %d], got shape %s" % (env.n_sensor, plan.shape))
+    K = min(plan.shape[0], int(env.n - 1 - env.i))
+    if K < 1:
+        raise ValueError("refine_plan_sensors: at least one step inside the episode")
+    plan = plan[:K]
+    S = plan.shape[1]
+    rng = np.random.RandomState(seed)
+    ok = None
+    if int(candidates) > 1 and int(rounds) > 0:
+        f = env.forecast_sensors(K)
+        ok = (f["visible"].cpu().numpy() != 0) & (f["status"].cpu().numpy() == _lib.ST_OK)       # [K', S, m]
+    total = None
+    for _ in range(int(rounds) if int(candidates) > 1 else 0):
+        cand = np.repeat(plan[None], int(candidates), axis=0)
+        for c in range(1, int(candidates)):
+            k, s = divmod(int(rng.randint(K * S)), S)
+            free = ok[k, s].copy()
+            row = plan[k]
+            free[row[(row >= 0) & (row < free.shape[0])]] = False
+            pool = np.flatnonzero(free)
+            if len(pool):
+                cand[c, k, s] = pool[rng.randint(len(pool))]
+        totals = env.evaluate_schedules(cand)["total"].cpu().numpy()
+        # (the first of equal maxima: the incumbent stays unless something is strictly better.  A NaN total -- a taken update of a
+        # covariance that has no log-determinant left, late in an episode -- never wins)
+        best = int(np.argmax(np.where(np.isnan(totals[:, col]), -np.inf, totals[:, col])))
+        plan, total = cand[best], totals[best]
+    if total is None:
+        total = env.evaluate_schedules(plan)["total"].cpu().numpy()[0]
+    return plan, np.asarray(total, dtype=np.float64)

@@ -1021,6 +1021,7 @@ struct ActBase {
     static constexpr bool envs = false;           // `sensors` in each of several envs: a row of actions per env (ActSensorEnvs)
     static constexpr bool look_envs = false;      // `look_sensors` in each of several envs (ActLookSensorEnvs)
     static constexpr bool plain = false;          // the plain one-env launch form, decided by the launcher (ActPlain)
+    static constexpr bool dryrun = false;         // `sensors` + `envs` as a dry run: P+ committed to the tile, x kept, records only (ActDryRunEnvs)
     SSA_DEV int get() { return -1; }
     SSA_DEV void before_wait(Tiles&, int, int) {}
     SSA_DEV void mid_step(Tiles&, int) {}
@@ -1211,6 +1212,43 @@ struct ActScheduleEnvs : ActBase {
     SSA_DEV int action(const ssa_sensor_params*, int k) const { return row[k]; }
     SSA_DEV double* records(const ssa_sensor_params*) const { return upd; }
 };
+// ActDryRunEnvs (dryrun_sensors_kernel, ssa_dryrun_sensors_envs_f64): ActScheduleEnvs as a dry run -- step kk of a candidate schedule on
+// a resident tile whose (pseudo-)env is a scalar, read-only like the forecast's.  The `sensors` / `envs` paths of process_wave hold for it
+// (the row's sensor, its site, visibility, S, the inverse, K); behind `dryrun` the update commits P+ = P- - K S K^T alone (the `all`
+// path's arithmetic, through the row's consumed staging matrix, so that P- is still there for the scores), x stays the predict's, the
+// noise is not fetched, a failed row follows the forecast's rule (no ring to re-read), and the one output is the slot's record.
+// records() is null: nothing of the sensor step's update record is written.  An action >= n_obj_caller is idle whatever n_obj is (a
+// gathered block's n_obj is not the catalogue's size): the row's words are filtered as they are read.
+struct ActDryRunEnvs : ActBase {
+    static constexpr bool sensors = true, envs = true, dryrun = true;
+    const ssa_sensor_params* s;
+    const ssa_dryrun_sensors_params* v;   // (in the kernel's argument block, as `s`)
+    int kk;                            // the step
+    int env;                           // the tile's env
+    ConstPtr<int32_t> row;             // ... its action words at step kk
+    double* out;                       // ... its records of step kk
+    int lim;                           // n_obj_caller
+    SSA_DEV const ssa_sensor_params* sites() const { return s; }
+    SSA_DEV void enter(uint32_t, int n_env, int64_t n_obj, int64_t base)
+    {
+        env = (n_env > 1) ? __builtin_amdgcn_readfirstlane((int)((uint32_t)base / (uint32_t)n_obj)) : 0;
+        const int64_t ke = (int64_t)kk * n_env + env;
+        row = (ConstPtr<int32_t>)v->actions + ke * SSA_MAX_SENSORS;
+        out = v->out + ke * s->n_sensor * SSA_DRY_STRIDE;
+        lim = v->n_obj_caller;
+    }
+    typedef int row_t __attribute__((ext_vector_type(SSA_MAX_SENSORS)));
+    SSA_DEV row_t actions(const ssa_sensor_params*) const
+    {
+        row_t r = *(ConstPtr<row_t>)__builtin_assume_aligned(row, sizeof(row_t));
+#pragma unroll
+        for (int k = 0; k < SSA_MAX_SENSORS; ++k) r[k] = r[k] < lim ? r[k] : -1;
+        return r;
+    }
+    SSA_DEV int action(const ssa_sensor_params*, int k) const { return row[k] < lim ? row[k] : -1; }
+    SSA_DEV double* records(const ssa_sensor_params*) const { return nullptr; }
+    SSA_DEV double* record(int sid) const { return out + (int64_t)sid * SSA_DRY_STRIDE; }
+};
 // the sensor that updates the object the caller calls `jid`: the lowest-numbered one whose action it is, -1 for none
 template <class ACT>
 SSA_DEV int sensor_index(const ACT& a, const ssa_sensor_params* s, int64_t jid)
@@ -1385,6 +1423,48 @@ SSA_DEV void lookahead_store(const Tiles& t, const ssa_lookahead_out& o, int g, 
     }
 }
 
+// the dry run's record of a tasked row g (lane l of it): the slot's action, visibility, outcome and status, and the lookahead's three
+// scores from P- (the tile) and P+ (the first 36 slots of the row's staging matrix, pp_at<0>) -- lookahead_store's arithmetic, line by line
+SSA_DEV void dryrun_store(const Tiles& t, double* rec, int g, int l, double action, int st, bool vis, bool taken)
+{
+    const double* Pm = &t.P[g * 36];
+    const double* Pp = &t.UA[g * 117];
+    double ld = 0.0;
+    if (taken && l < 2) {
+        const double* src = (l == 0) ? Pm : Pp;
+        double A[21];
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = r; c < 6; ++c) A[tri(r, c)] = src[r * 6 + c];
+        ld = logdet_chol(A);
+    }
+    const double ld_post = __shfl_down(ld, 1, 64);
+    if (l == 0) {
+        const double nan = __builtin_nan("");
+        double sc[SSA_LOOK_NSCORE] = {nan, nan, nan};
+        if (taken) {
+            double trm = 0.0, trp = 0.0, pos_m = 0.0, pos_p = 0.0;
+#pragma unroll
+            for (int r = 0; r < 6; ++r) {
+                trm += Pm[7 * r];
+                trp += Pp[7 * r];
+                if (r == 2) { pos_m = trm; pos_p = trp; }
+            }
+            sc[SSA_LOOK_TRACE_GAIN] = trm - trp;
+            sc[SSA_LOOK_POS_TRACE_GAIN] = pos_m - pos_p;
+            sc[SSA_LOOK_INFO_GAIN] = 0.5 * (ld - ld_post);
+        }
+        rec[SSA_DRY_ACTION] = action;
+        rec[SSA_DRY_VISIBLE] = vis ? 1.0 : 0.0;
+        rec[SSA_DRY_TAKEN] = taken ? 1.0 : 0.0;
+        rec[SSA_DRY_STATUS] = (double)st;
+#pragma unroll
+        for (int k = 0; k < SSA_LOOK_NSCORE; ++k) rec[SSA_DRY_SCORE + k] = sc[k];
+        rec[SSA_DRY_SPARE] = 0.0;
+    }
+}
+
 template <int PROP, int TILE, class ACT>
 SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& p, int lane, int64_t obj_in, bool valid,
                           int64_t base, int cnt, TileRegs& pf, int64_t next_base, int next_cnt, int tile, ACT& asrc)
@@ -1408,6 +1488,8 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     constexpr bool ENVS = ACT::envs;           // SENS in each of several envs, whole tiles per env (ActSensorEnvs)
     constexpr bool LENVS = ACT::look_envs;     // LSENS in each of several envs, whole tiles per env (ActLookSensorEnvs)
     constexpr bool PLAIN = ACT::plain;         // the launcher's plain form (ActPlain): the decisions below marked PLAIN are constants
+    constexpr bool DRY = ACT::dryrun;          // SENS + ENVS as a dry run on a resident tile: P+ alone committed, records only (ActDryRunEnvs)
+    static_assert(!DRY || (SENS && ENVS && TILE == 2), "ActDryRunEnvs: a resident tile's sensor step in several envs");
     static_assert(!PLAIN || (!ACT::late && !ALL && !SENS && !LSENS), "ActPlain: a step kernel's form");   // (and launched as the one-tile instance only)
 #define SSA_NENV (PLAIN ? 1 : p.n_env)   /* (at the place of use: every other instance reads the word where it did) */
     // (ActLookSensors, multi-tile instance: the next tile's loads leave once, behind the last pass -- except with SSA_PROP_ELEMENTS, whose
@@ -1532,7 +1614,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     if (!ACT::late && !ALL && __any(my_update)) __builtin_amdgcn_s_setprio(3);
     int tmod = 0;                                           // row of `trans` / `z_noise` (episodes wrap)
     double upd_in = 0.0;
-    if (may_update && l < (ALL ? 9 : 12)) {   // (ActAll: the matrix only -- the noise slots stay zero, z_noise is never read)
+    if (may_update && l < ((ALL || DRY) ? 9 : 12)) {   // (ActAll, a dry run: the matrix only -- the noise slots stay zero, z_noise is never read)
         tmod = time_row(tix, p.n_time);
         const int64_t aobj = ACT::late ? jid : (int64_t)act;   // (the measurement noise is indexed as the caller numbers the objects)
         const double* src = (l < 9) ? p.trans + (int64_t)tmod * 9 + l
@@ -1930,7 +2012,8 @@ look_pass:
                     W[36 + lane] = W[9 + a * 3] * SI[b] + W[9 + a * 3 + 1] * SI[3 + b] + W[9 + a * 3 + 2] * SI[6 + b];
                 }
                 wave_lds_sync();
-                if constexpr (ALL) {   // P+ = P- - K S K^T into the row's consumed staging matrix; x and the tile's P stay as they are
+                if constexpr (ALL || DRY) {   // P+ = P- - K S K^T into the row's consumed staging matrix; x and the tile's P stay as they are
+                                              // (a dry run commits P+ to the tile behind its record, below)
                     if (lane < 36) {
                         const int a = lane / 6, b = lane - 6 * a;
                         double corr = 0.0;
@@ -1988,6 +2071,15 @@ look_pass:
         look_vis = visible;
         look_taken = taken;
     }
+    if constexpr (DRY) {   // the slot's record from P- (the tile) and P+ (the staging matrix); then P+ is the tile's
+        if (my_update)
+            dryrun_store(t, asrc.record(sid), g, l, attempted ? (double)(p.obj_ids ? (int64_t)t.Oid[g] : obj - (int64_t)asrc.env * p.n_obj) : -1.0,
+                         st_new, visible, taken);
+        wave_lds_sync();
+        if (taken) {
+            for (int idx = l; idx < 36; idx += 16) t.P[g * 36 + idx] = t.UA[g * 117 + idx];
+        }
+    }
     // The update is the register-pressure peak behind the propagator and only ONE wavefront of a launch runs it: whatever is
     // live across it would be spilled by EVERY wavefront.  So the values that are cheap to get again are got again behind
     // it: the lane coordinates, the object / env, and the next tile's loads (issued a second time).
@@ -2010,7 +2102,27 @@ look_pass:
         rec[SSA_UPD_ACTION] = -1.0;
       }
     }
-    if constexpr (ENVS) {   // (ActSensorEnvs: the block below once per env -- by the first row of the tile's env, into that env's records.  Written
+    if constexpr (DRY) {    // (ActDryRunEnvs: the slots that update nobody, once per env by its first row -- the cleared record)
+        if (valid && obj == (int64_t)asrc.env * p.n_obj && l == 0) {
+            for (int k = 0; k < SP->n_sensor; ++k) {
+                const int a = asrc.action(SP, k);   // (>= n_obj_caller: read as -1)
+                bool owns = a >= 0 && interval_ok;
+                for (int q = 0; q < k; ++q)
+                    if (asrc.action(SP, q) == a) owns = false;
+                if (!owns) {
+                    double* rec = asrc.record(k);
+                    const double nan = __builtin_nan("");
+                    rec[SSA_DRY_ACTION] = -1.0;
+                    rec[SSA_DRY_VISIBLE] = 0.0;
+                    rec[SSA_DRY_TAKEN] = 0.0;
+                    rec[SSA_DRY_STATUS] = 0.0;
+#pragma unroll
+                    for (int q = 0; q < SSA_LOOK_NSCORE; ++q) rec[SSA_DRY_SCORE + q] = nan;
+                    rec[SSA_DRY_SPARE] = 0.0;
+                }
+            }
+        }
+    } else if constexpr (ENVS) {   // (ActSensorEnvs: the block below once per env -- by the first row of the tile's env, into that env's records.  Written
                             // out a second time: the one-env kernels' instructions do not survive any rewording of their own block)
         if (asrc.records(SP) && valid && obj == (int64_t)asrc.env * p.n_obj && l == 0) {
             for (int k = 0; k < SP->n_sensor; ++k) {
@@ -2051,7 +2163,7 @@ look_pass:
             t.P[g * 36 + idx] = (a == b) ? (a < 3 ? X_FAILED_POS : X_FAILED_VEL) : 0.0;
         }
         if (l < 6) t.X[g * 6 + l] = (l < 3) ? X_FAILED_POS : X_FAILED_VEL;
-        if (!ALL && p.fail_log && l == 0) {
+        if (!ALL && !DRY && p.fail_log && l == 0) {
             // filter_error()'s record (:369-382): who, why, when, and error_failed() of the state the filter failed FROM (:376-378) -- the
             // step's inputs, still in HBM (a rare, row-divergent branch: three loads per failing filter)
             if (ACT::late) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the closed loop stores the previous step's tile inside this one)
@@ -2074,8 +2186,8 @@ look_pass:
             }
         }
     }
-    if constexpr (FCAST) {
-        // a forecast has no ring: a row that had failed when the launch started passes through from the input slot, as below; one that
+    if constexpr (FCAST || DRY) {
+        // a forecast (a dry run) has no ring: a row that had failed when the launch started passes through from the input slot, as below; one that
         // failed at an earlier step of the horizon carries the sentinels F1 gave it then (its input slot holds the healthy state)
         if (valid && st_in != SSA_ST_OK) {
             const bool at_entry = p.status[obj] != SSA_ST_OK;   // (the caller's word: never written by this launch)
@@ -2085,7 +2197,7 @@ look_pass:
             }
             if (l < 6) t.X[g * 6 + l] = at_entry ? p.x_in[obj * 6 + l] : ((l < 3) ? X_FAILED_POS : X_FAILED_VEL);
         }
-        if (l == 0) t.St[g] = st_pred;   // (the predict's outcome alone travels to the next step)
+        if (l == 0) t.St[g] = DRY ? st_new : st_pred;   // (a forecast: the predict's outcome alone travels to the next step; a dry run: the step's)
     } else {
     if (valid && st_in != SSA_ST_OK) {  // already failed: the filter state passes through unchanged (:272)
         if (ACT::late) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (its previous state left for HBM earlier in THIS step)
@@ -2118,6 +2230,8 @@ look_pass:
     } else if constexpr (ALL) {   // the lookahead's outputs; nothing of the step's epilogue (observation, metrics, statistics, tile store)
         if (valid) lookahead_store(t, *asrc.o, g, l, (int64_t)e * p.n_obj + (p.obj_ids ? (int64_t)t.Oid[g] : obj - (int64_t)e * p.n_obj),
                                    st_new, look_vis, look_taken);
+        return;
+    } else if constexpr (DRY) {   // the records are out; nothing of the step's epilogue, and the tile stays where it is
         return;
     }
     observe_rows(t, g, l, cnt != OBJ_PER_WAVE);
@@ -2684,7 +2798,41 @@ SSA_DEV ActScheduleEnvs ring_act(const VecRollSensK& a, ssa_step_params& pk, int
     return ActScheduleEnvs{{}, &a.s, &a.v, kk, 0, nullptr, nullptr};   // (process_wave enters the tile's env)
 }
 SSA_RESIDENT_KERNEL(rollout_sensor_envs_kernel, VecRollSensK)
+// The dry run of B candidate schedules (ssa_dryrun_sensors_envs_f64): the sixth resident-tile kernel -- the forecast's read-only plan
+// and source (the caller's block; step k's differs from it in the time alone) with the schedule's action source as a dry run
+// (ActDryRunEnvs).  The tiles walk all E * n_obj rows, whole tiles per pseudo-env with several of them (the launcher).
+struct DryRunK {
+    StepK k;
+    ssa_sensor_params s;
+    ssa_dryrun_sensors_params d;
+};
+SSA_DEV const StepK& step_of(const DryRunK& a) { return a.k; }
+SSA_DEV ForePlan roll_plan(const DryRunK& a) { return ForePlan{a.d.n_steps, (int64_t)a.k.p.n_env * a.k.p.n_obj}; }
+SSA_DEV ssa_step_params roll_source(const DryRunK& a, ForePlan) { return a.k.p; }
+SSA_DEV ActDryRunEnvs roll_act(ForePlan, const DryRunK& ka, ssa_step_params& pk, int kk, int)
+{
+    pk = ka.k.p;
+    pk.time_offset = ka.k.p.time_offset + kk;
+    return ActDryRunEnvs{{}, &ka.s, &ka.d, kk, 0, nullptr, nullptr, 0};   // (process_wave enters the tile's env)
+}
+SSA_RESIDENT_KERNEL(dryrun_sensors_kernel, DryRunK)
 #undef SSA_RESIDENT_KERNEL
+// The totals of a dry run's records (ssa_dryrun_totals_f64): one thread per (candidate, score column) adds the taken slots' scores in
+// slot order, k outer and s inner -- one defined fp64 sum, whatever the launch's shape.
+__global__ void __launch_bounds__(64) dryrun_totals_kernel(const double* __restrict__ rec, int n_env, int n_steps, int n_sensor,
+                                                           double* __restrict__ total)
+{
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= (int64_t)n_env * SSA_LOOK_NSCORE) return;
+    const int b = (int)(i / SSA_LOOK_NSCORE), c = (int)(i - (int64_t)b * SSA_LOOK_NSCORE);
+    double t = 0.0;
+    for (int k = 0; k < n_steps; ++k)
+        for (int s = 0; s < n_sensor; ++s) {
+            const double* r = rec + (((int64_t)k * n_env + b) * n_sensor + s) * SSA_DRY_STRIDE;
+            if (r[SSA_DRY_TAKEN] != 0.0) t += r[SSA_DRY_SCORE + c];
+        }
+    total[i] = t;
+}
 // grid (n_steps, n_env): folds step k's shard set into the statistics slot of step k -- when that slot still
 // belongs to step k at the end of the rollout (the last `history` steps) -- and clears it
 __global__ void __launch_bounds__(64) rollout_fold_kernel(unsigned long long* __restrict__ shards, double* __restrict__ stats_ring,
@@ -5031,6 +5179,34 @@ int ssa_forecast_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p,
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     hipStream_t s = (hipStream_t)stream;
     with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(forecast_sensor_envs_kernel<P>, dim3(g.nwork), dim3(64), 0, s, k, (int)g.ntiles, g.nwork); });
+    return launch_status();
+}
+int ssa_dryrun_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_dryrun_sensors_params* d,
+                                void* stream)
+{
+    if (!d) return SSA_E_INVALID;
+    // (the forecast's rules with d->out as every required output)
+    const ssa_lookahead_out o = {d->out, (int32_t*)d->out, (uint8_t*)d->out, nullptr, nullptr, nullptr};
+    LookK lk;
+    DryRunK k;
+    const int rc = lookahead_sensors_args(c, p, sp, &o, true, lk, k.s);
+    if (rc != SSA_OK) return rc;
+    if (d->n_steps < 1 || d->n_obj_caller < 1 || !row_aligned(d->actions)) return SSA_E_INVALID;
+    if (!rows_fit(p->n_env, sp->n_sensor, d->n_steps)) return SSA_E_INVALID;
+    k.k = lk.k;
+    k.k.p.launch_mask = 0;   // (the time words are read from env_time: a resident tile's steps do not see SSA_LAUNCH_INLINE_ENVS)
+    k.d = *d;
+    const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
+    hipStream_t s = (hipStream_t)stream;
+    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(dryrun_sensors_kernel<P>, dim3(g.nwork), dim3(64), 0, s, k, (int)g.ntiles, g.nwork); });
+    return launch_status();
+}
+int ssa_dryrun_totals_f64(const double* records, int32_t n_env, int32_t n_steps, int32_t n_sensor, double* total, void* stream)
+{
+    if (!records || !total || n_env < 1 || n_steps < 1 || n_sensor < 1 || n_sensor > SSA_MAX_SENSORS) return SSA_E_INVALID;
+    if (!rows_fit(n_env, n_sensor, n_steps)) return SSA_E_INVALID;
+    hipLaunchKernelGGL(dryrun_totals_kernel, dim3((unsigned)nblk((int64_t)n_env * SSA_LOOK_NSCORE, 64)), dim3(64), 0, (hipStream_t)stream, records,
+                       (int)n_env, (int)n_steps, (int)n_sensor, total);
     return launch_status();
 }
 // the checks and the argument block shared by ssa_env_rollout_f64 and ssa_env_rollout_sensors_f64 (sens: r->actions is not read); SSA_OK or

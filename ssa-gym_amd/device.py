@@ -431,6 +431,68 @@ def plan_sensors(score, column, out=None, picks=None, workspace=None):
     return out
 
 
+def dryrun_rows(actions, n_obj, n_sensor=None):
+    """the host side of a gathered dry run (engine.launch_dryrun_sensors): for candidates `actions` [B, K, S] over a catalogue of n_obj
+    objects, (ids [B, W] int32, words [K, B, MAX_SENSORS] int32).  ids[b] = the distinct valid objects (0 <= a < n_obj) candidate b names,
+    ascending, padded with -1 to W = 4 * ceil(max_b distinct / 4) (at least one tile: an all-idle batch still has its first row, which
+    clears the records); words = the action rows as ssa_dryrun_sensors_params.actions takes them, -1 beyond S."""
+    import numpy as np
+    a = np.asarray(actions)
+    if a.ndim != 3 or a.shape[1] < 1 or a.shape[0] < 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("dry run: actions must be an integer array [B, K, S], got %s %s" % (a.dtype, a.shape))
+    B, K, S = a.shape
+    if not 1 <= S <= _lib.MAX_SENSORS or (n_sensor is not None and S != int(n_sensor)):
+        raise ValueError("dry run: actions [B, K, S] must have S = %s sensors, got %d" % (n_sensor or "1 .. %d" % _lib.MAX_SENSORS, S))
+    a = a.astype(np.int64)
+    # per candidate: its entries sorted with the idle ones last, the first of every run of equal objects kept (no loop over B)
+    idle = np.iinfo(np.int64).max
+    v = np.sort(np.where((a >= 0) & (a < int(n_obj)), a, idle).reshape(B, K * S), axis=1)
+    keep = v < idle
+    keep[:, 1:] &= v[:, 1:] != v[:, :-1]
+    W = 4 * max(1, -(-int(keep.sum(axis=1).max()) // 4))
+    ids = np.full((B, W), -1, dtype=np.int32)
+    ids[np.nonzero(keep)[0], (np.cumsum(keep, axis=1) - 1)[keep]] = v[keep]
+    words = np.full((K, B, _lib.MAX_SENSORS), -1, dtype=np.int32)
+    words[:, :, :S] = np.clip(a, -1, np.iinfo(np.int32).max).transpose(1, 0, 2)
+    return ids, words
+
+
+def dryrun_sensors(consts, params, sensors, actions, n_steps, n_obj_caller, out=None):
+    """the dry run of candidate schedules on the device (ssa_dryrun_sensors_envs_f64), stateless: `params` a filled _lib.ssa_step_params
+    (its INPUT fields: n_env pseudo-envs of n_obj rows each, obj_ids per env), `sensors` host.make_sensor_params(), `actions` a contiguous
+    32-byte aligned CUDA int32 tensor [K, n_env, MAX_SENSORS].  Returns the records [K, n_env, S, DRY_STRIDE] (CUDA float64; `out`: the
+    tensor to write).  Nothing else is written.  No host sync."""
+    K, E, S = int(n_steps), int(params.n_env), int(sensors.n_sensor)
+    if not (isinstance(actions, torch.Tensor) and actions.is_cuda and actions.dtype == torch.int32 and actions.is_contiguous()
+            and tuple(actions.shape) == (K, E, _lib.MAX_SENSORS)):
+        raise _lib.SsaHipError("dry run: actions must be a contiguous CUDA int32 tensor [%d, %d, %d]" % (K, E, _lib.MAX_SENSORS))
+    if out is None:
+        out = torch.empty((K, E, S, _lib.DRY_STRIDE), dtype=f64, device=actions.device)
+    elif _chk(out, "out") and out.numel() != K * E * S * _lib.DRY_STRIDE:
+        raise _lib.SsaHipError("out must hold %d doubles" % (K * E * S * _lib.DRY_STRIDE))
+    d = _lib.ssa_dryrun_sensors_params()
+    d.n_steps, d.n_obj_caller, d.actions, d.out = K, int(n_obj_caller), actions.data_ptr(), out.data_ptr()
+    _lib.check(_lib.load().ssa_dryrun_sensors_envs_f64(C.byref(consts), C.byref(params), C.byref(sensors), C.byref(d), _stream()),
+               "ssa_dryrun_sensors_envs_f64")
+    return out
+
+
+def dryrun_totals(records, out=None):
+    """the totals of a dry run's records [K, E, S, DRY_STRIDE] (contiguous CUDA float64, as dryrun_sensors leaves them) on the device
+    (ssa_dryrun_totals_f64): [E, LOOK_NSCORE], per candidate and score column the sum of the taken slots' scores in slot order (k outer,
+    s inner) -- one defined fp64 sum; 0 for none.  No host sync."""
+    _chk(records, "records")
+    if records.dim() != 4 or records.shape[3] != _lib.DRY_STRIDE:
+        raise _lib.SsaHipError("records must be [K, E, S, %d]" % _lib.DRY_STRIDE)
+    K, E, S = (int(v) for v in records.shape[:3])
+    if out is None:
+        out = torch.empty((E, _lib.LOOK_NSCORE), dtype=f64, device=records.device)
+    elif _chk(out, "out") and out.numel() != E * _lib.LOOK_NSCORE:
+        raise _lib.SsaHipError("out must hold %d doubles" % (E * _lib.LOOK_NSCORE))
+    _lib.check(_lib.load().ssa_dryrun_totals_f64(records.data_ptr(), E, K, S, out.data_ptr(), _stream()), "ssa_dryrun_totals_f64")
+    return out
+
+
 def env_step(consts, params):
     """E1: the fused step.  `params` is a filled _lib.ssa_step_params."""
     lib = _lib.load()

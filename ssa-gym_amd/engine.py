@@ -120,6 +120,7 @@ class HotPathEngine:
         self._look_se = None                            # output buffers of launch_lookahead_sensors_envs
         self._assign_envs_ws = None                     # (S, workspace) of launch_assign_sensors_envs
         self._fore_e = None                             # output buffers of launch_forecast_sensors_envs
+        self._dry = {}                                  # launch_dryrun_sensors: per (B, K, S, W) its upload, time words, gathered block and records
         self._pcache = {}
         self._cref = C.byref(self.consts)
         self._pref = C.byref(self._p)
@@ -660,6 +661,55 @@ class HotPathEngine:
         if rc:
             raise _lib.SsaHipError("ssa_forecast_sensors_envs_f64 failed with code %d" % rc)
         return res
+
+    def launch_dryrun_sensors(self, slot_in, time_offset, sensors, actions, stream=None, gather=True):
+        """enqueue the dry run of B candidate tasking schedules from history slot `slot_in` (include/ssa_hip.h: ssa_dryrun_sensors_envs_f64;
+        one env): what each schedule `actions[b]` ([B, K, S] integers, the caller's object numbering; < 0 or >= n_obj: idle; two sensors
+        on one object in a row: the lower one updates it) would do to the covariances if it were run from this state with every
+        innovation zero -- step k has time index time_offset + k --, in ONE launch.  Only the objects a candidate names can change its
+        value, so the launch runs on a gathered block: the distinct objects of each candidate (device.dryrun_rows), padded to W rows, B
+        pseudo-envs of W rows gathered from the slot with torch index ops (through the layout's inverse table when one is set).
+        gather=False (B == 1): the full-catalogue form on the slot itself -- every object predicted K times, the cost of a rollout; the
+        tests' yardstick.  Nothing of the engine's state is written.  Returns this engine's record tensor [B, K, S, DRY_STRIDE] (a view
+        of a buffer cached per (B, K, S, W), rewritten by the next call).  Asynchronous, no host sync."""
+        if self.E != 1:
+            raise _lib.SsaHipError("the dry run of a sensor network's schedules covers one env (n_env == 1)")
+        S = int(sensors.n_sensor)
+        if isinstance(actions, torch.Tensor):
+            actions = actions.detach().cpu().numpy()
+        ids, words = device.dryrun_rows(actions, self.m, S)
+        B, K = int(ids.shape[0]), int(words.shape[0])
+        if not gather and B != 1:
+            raise _lib.SsaHipError("launch_dryrun_sensors(gather=False) takes one candidate, got %d" % B)
+        W = int(ids.shape[1]) if gather else 0
+        key = (B, K, S, W)
+        buf = self._dry.get(key)
+        if buf is None:
+            # one upload per call: the ids and the action words side by side (the words 32-byte aligned: they come first)
+            buf = self._dry[key] = {"dev": torch.empty(K * B * _lib.MAX_SENSORS + B * W, dtype=torch.int32, device=self.dev),
+                                    "out": torch.empty((K, B, S, _lib.DRY_STRIDE), dtype=f64, device=self.dev),
+                                    "time": torch.empty(max(B, 1), dtype=torch.int32, device=self.dev)}
+        nw = K * B * _lib.MAX_SENSORS
+        up = np.concatenate((words.reshape(-1), ids.reshape(-1))) if gather else words.reshape(-1)
+        st = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
+        with torch.cuda.stream(st):
+            buf["dev"].copy_(torch.from_numpy(up))
+            p = self._lookahead_params(slot_in, time_offset)
+            if gather:
+                dev_ids = buf["dev"][nw:].view(B, W)
+                # a padding row takes the state of the candidate's first object (object 0 for an all-idle candidate): a healthy row to predict
+                rows = torch.where(dev_ids >= 0, dev_ids, dev_ids[:, :1].clamp(min=0).expand(B, W)).reshape(-1).to(torch.int64)
+                if self._order is not None:
+                    rows = self._slot_of.index_select(0, rows)
+                sl = int(slot_in) % self.H
+                g = buf["state"] = (self.x_true[sl].index_select(0, rows), self.x_filter[sl].index_select(0, rows),
+                                    self.P_filter[sl].index_select(0, rows), self.status.index_select(0, rows))
+                buf["time"].copy_(self.env_time0[:1].expand(B))
+                p.n_obj, p.n_env = W, B
+                p.x_true_in, p.x_in, p.P_in, p.status = (t.data_ptr() for t in g)
+                p.env_time, p.obj_ids = buf["time"].data_ptr(), dev_ids.data_ptr()
+            device.dryrun_sensors(self.consts, p, sensors, buf["dev"][:nw].view(K, B, _lib.MAX_SENSORS), K, self.m, out=buf["out"])
+        return buf["out"].permute(1, 0, 2, 3)
 
     def launch_assign_sensors(self, look, column, action_row, fallback_row=None, picks=None, stream=None, rule='greedy'):
         """enqueue the tasking assignment of a sensor network (include/ssa_hip.h: ssa_assign_sensors_f64) on `look`, the dict

@@ -843,6 +843,42 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
             raise ValueError("forecast_sensors: a horizon of at least one step, got %r" % (horizon,))
         return dict(e.launch_forecast_sensors(self.i % e.H, self.i + 1, self._sites(), H, out=want, stream=self._stream.cuda_stream))
 
+    def evaluate_schedules(self, actions, gather=True):
+        """The dry run of B candidate tasking schedules (no reference counterpart; include/ssa_hip.h: ssa_dryrun_sensors_envs_f64;
+        DESIGN.md section 8p): what each schedule would be worth if rollout_sensors() ran it from the state at step i, in ONE launch and
+        without spending the env.  The covariance update does not depend on the measurement drawn and the expected innovation is zero,
+        so a schedule is run with P+ = P- - K S K^T committed and x+ = x-: deterministic, read-only, and -- unlike forecast_sensors() --
+        a revisit is valued from the covariance the earlier visit left.  `actions`: integers [K, S] or [B, K, S] (S = n_sensor; 1 without
+        config['observers']: the env's own observer as a one-site network), K clipped to steps - 1 - i; an entry < 0 or >= m is an idle
+        sensor; two sensors on one object in a row are NOT refused -- the lower one takes it and the record shows who did.  A dict of
+        CUDA tensors, B = 1 for [K, S]:
+            score   [B, K', S, 3] float64: columns _lib.LOOK_* from the step's P- and P+; NaN unless taken
+            taken, visible [B, K', S] bool;  status [B, K', S] int32 (the SSA_ST_* the object carries after the step; 0: nobody updated)
+            action  [B, K', S] int64: the object whose update was attempted, else -1
+            total   [B, 3] float64: the sum of the taken slots' scores per column, in slot order (k outer, s inner); 0 for none
+        Nothing of the env changes: no engine tensor, not i, the histories or np_random.  Only the objects a candidate names are run
+        (gather=False, B == 1: the whole catalogue on the slot itself -- the cost of a rollout; the tests' yardstick)."""
+        import torch
+        from .. import device
+        if self._engine is None:
+            raise _lib.SsaHipError("no device state: the dry run of a schedule runs on the GPU only (no CPU fallback)")
+        a = actions.detach().cpu().numpy() if isinstance(actions, torch.Tensor) else np.asarray(actions)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[2] != self.n_sensor or a.dtype.kind not in "iu":
+            raise ValueError("evaluate_schedules: integer schedules [K, %d] or [B, K, %d], got %s %s" % (self.n_sensor, self.n_sensor, a.dtype, a.shape))
+        K = min(int(a.shape[1]), self.n - 1 - self.i)
+        if K < 1:
+            raise ValueError("evaluate_schedules: at least one step inside the episode (i = %d, steps = %d, K = %d)" % (self.i, self.n, a.shape[1]))
+        e = self._engine
+        rec = e.launch_dryrun_sensors(self.i % e.H, self.i + 1, self._sites(), a[:, :K], stream=self._stream, gather=gather)
+        with torch.cuda.stream(self._stream):
+            score = rec[..., _lib.DRY_SCORE:_lib.DRY_SCORE + _lib.LOOK_NSCORE]
+            taken = rec[..., _lib.DRY_TAKEN] != 0
+            total = device.dryrun_totals(rec.permute(1, 0, 2, 3))     # (the engine's [K, B, S, 8] block; slot order: one defined fp64 sum)
+            return {"score": score, "taken": taken, "visible": rec[..., _lib.DRY_VISIBLE] != 0,
+                    "status": rec[..., _lib.DRY_STATUS].to(torch.int32), "action": rec[..., _lib.DRY_ACTION].to(torch.int64), "total": total}
+
     def aer_obs(self, obs):
         """:834-840 -- [az, el, range, trace(P)] per object, NaN/inf -> 0.001."""
         from .. import device
