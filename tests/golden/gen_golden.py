@@ -14,6 +14,11 @@ callbacks -> files whose name starts with "ukf_" / "episode_" are COMPOSITE
 goldens (reference callbacks + restated filterpy), all others are pure
 reference outputs.  The *.npz / *.npy files written here are committed; the
 reference itself never leaves this container.
+
+Two further generators use the same loader, each for one fixture:
+    gen_conics_golden.py               kepler_conics_golden.npz: fx on every non-elliptic conic branch (pure reference)
+    gen_episode_failures_reference.py  episode_failures_reference.json: failure statistics of five 2 000-object, 479-step
+                                       episodes (COMPOSITE: reference callbacks + oracle/ukf_numpy.py; ~5 min per seed on 8 cores)
 """
 import os
 import sys

@@ -14,8 +14,8 @@ import numpy as np
 import pytest
 
 from conftest import golden
-from support.devmath import (_conic_states, build_devmath, check_conic_branches_lean_form_vs_restatements_and_oracle,
-                             check_elements_strong_elliptic_chain_vs_reference_golden, check_fast_atan2, check_fast_exp,
+from support.devmath import (CONIC_FORMS, _conic_states, build_devmath, check_conic_branches_lean_form_vs_restatements_and_oracle,
+                             check_device_math_vs_reference_conics_golden, check_elements_strong_elliptic_chain_vs_reference_golden, check_fast_atan2, check_fast_exp,
                              check_fast_sincos_and_reciprocals, check_fg_hyperbolic_and_near_parabolic_states,
                              check_fg_universal_solvers_vs_reference_golden, check_near_parabolic_bands_fast_vs_libm)
 from support.gpu import namespace
@@ -121,6 +121,11 @@ def test_device_math_fg_hyperbolic_and_near_parabolic_states(dm, oracle_ld):
 
 def test_device_math_conic_branches_lean_form_vs_restatements_and_oracle(dm, oracle_ld):
     check_conic_branches_lean_form_vs_restatements_and_oracle(dm, oracle_ld)
+
+
+@pytest.mark.parametrize("form", CONIC_FORMS)
+def test_device_math_conic_branches_vs_reference_conics_golden(dm, oracle_ld, form):
+    check_device_math_vs_reference_conics_golden(dm, form, oracle_ld)
 
 
 def test_device_math_near_parabolic_bands_fast_vs_libm(dm):

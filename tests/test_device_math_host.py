@@ -15,8 +15,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from support.devmath import (build_devmath, check_conic_branches_lean_form_vs_restatements_and_oracle,
-                             check_elements_strong_elliptic_chain_vs_reference_golden, check_fast_atan2, check_fast_exp,
+from support.devmath import (CONIC_FORMS, build_devmath, check_conic_branches_lean_form_vs_restatements_and_oracle,
+                             check_device_math_vs_reference_conics_golden, check_elements_strong_elliptic_chain_vs_reference_golden, check_fast_atan2, check_fast_exp,
                              check_fast_sincos_and_reciprocals, check_fg_hyperbolic_and_near_parabolic_states,
                              check_fg_universal_solvers_vs_reference_golden, check_near_parabolic_bands_fast_vs_libm)
 
@@ -120,6 +120,11 @@ def test_fg_hyperbolic_and_near_parabolic_states(hm, oracle_ld):
 
 def test_conic_branches_lean_form_vs_restatements_and_oracle(hm, oracle_ld):
     check_conic_branches_lean_form_vs_restatements_and_oracle(hm, oracle_ld)
+
+
+@pytest.mark.parametrize("form", CONIC_FORMS)
+def test_conic_branches_vs_reference_conics_golden(hm, oracle_ld, form):
+    check_device_math_vs_reference_conics_golden(hm, form, oracle_ld)
 
 
 def test_near_parabolic_bands_fast_vs_libm(hm):

@@ -19,6 +19,13 @@ three-sigma band of +-6 %), the status-code mix, the 'jones' step, the overlap o
 oracle's own yardstick, the POPULATION the failures come from (filters the oracle sees diverged by step 300: 13 % of the objects, 57 %
 of the oracle's late failures) and the distribution of first-failure steps.  A variant that reproduced the count with the wrong filters
 (random ones: 13 % from that population, overlap 0.01) fails it.
+
+The oracle is our own restatement, so the gate (tests/support/episode_gate.py::hold_to, stated once) is also applied against the REFERENCE
+COMPOSITE -- tests/golden/episode_failures_reference.json: the same five episodes run by the reference's own fx_xyz_farnocchia,
+robust_cholesky, hx_aer_erfa, mean_z_uvw and residual_z_aer driving oracle/ukf_numpy.py (gen_episode_failures_reference.py): the oracle
+is held to it on the CPU, fixture against fixture, and the HIP variants on the GPU from the same runs.  Measured: composite 264 failures
+pooled (248 LinAlgError, 13 AssertionError, 3 NaN), oracle 273, hybrid 277, elements 263; overlaps with the composite 0.086 / 0.111 /
+0.095 against the yardstick's 0.092; first-failure medians 370 / 365 / 374 / 375, KS <= 0.076.
 """
 import json
 import os
@@ -28,32 +35,22 @@ import pytest
 
 import episode_workload as ew
 from conftest import GOLDEN
+from support.episode_gate import band, hold_to, ks_distance, late_in_population, yardstick
 
 FIXTURE = os.path.join(GOLDEN, "episode_failures_oracle.json")
-
-
-def band(a, b):
-    """two failure counts are 'the same statistics' when they differ by no more than three standard deviations of a
-    Poisson count of their size (+3): the oracle's own two summation orders differ by 52 vs 64 at step 479"""
-    return abs(a - b) <= 3.0 * np.sqrt(max(a, b)) + 3.0
-
-
-def ks_distance(a, b):
-    """two-sample Kolmogorov-Smirnov statistic of two samples of first-failure steps"""
-    a, b = np.sort(np.asarray(a, dtype=float)), np.sort(np.asarray(b, dtype=float))
-    grid = np.concatenate([a, b])
-    return float(np.max(np.abs(np.searchsorted(a, grid, side="right") / len(a) - np.searchsorted(b, grid, side="right") / len(b))))
-
-
-def late_in_population(run, population, after=ew.DIVERGED_STEP):
-    """(failures after step `after` that lie in `population`, failures after step `after`)"""
-    late = [j for j, s in zip(run["failed_ids"], run["failed_first_step"]) if s > after]
-    return len(set(late) & set(population)), len(late)
+REFERENCE_FIXTURE = os.path.join(GOLDEN, "episode_failures_reference.json")
 
 
 @pytest.fixture(scope="module")
 def fixture():
     return json.load(open(FIXTURE))
+
+
+@pytest.fixture(scope="module")
+def reference_fixture():
+    """the same five episodes run by the reference's own callbacks (tests/golden/gen_episode_failures_reference.py)"""
+    f = json.load(open(REFERENCE_FIXTURE))
+    return {seed: f["seed%d" % seed]["reference_composite"] for seed in ew.SEEDS}
 
 
 @pytest.fixture(scope="module")
@@ -104,8 +101,19 @@ def test_the_oracles_own_yardstick(fixture):
     assert pop_in >= 0.4 * pop_n and div_n <= 0.2 * 2000 * len(ew.SEEDS)
 
 
+def test_oracle_episode_statistics_match_the_reference_composite(fixture, reference_fixture):
+    """fixture against fixture (no GPU, no oracle run): the oracle's reference-order episodes are held to the REFERENCE COMPOSITE -- the
+    reference's own fx_xyz_farnocchia, robust_cholesky, hx_aer_erfa, mean_z_uvw and residual_z_aer driving oracle/ukf_numpy.py over the
+    same inputs -- with the gate the HIP variants face against the oracle (support.episode_gate.hold_to), and no looser one.  Without
+    this the gate below is circular: our kernels against our own restatement."""
+    ref = {seed: fixture["seed%d" % seed]["reference_order"] for seed in ew.SEEDS}
+    exc = sum((reference_fixture[s]["failed_exception"] for s in ew.SEEDS), [])
+    print("[reference composite] first-failure exceptions: %s" % {e: exc.count(e) for e in sorted(set(exc))})
+    hold_to("oracle, reference order", ref, reference_fixture, yardstick(fixture), "the reference composite")
+
+
 @pytest.mark.gpu
-def test_faithful_variants_reproduce_the_reference_failures_fg_does_not(fixture):
+def test_faithful_variants_reproduce_the_reference_failures_fg_does_not(fixture, reference_fixture):
     import torch
     import ssa_gym_amd
     from ssa_gym_amd import _lib, device, host, engine
@@ -127,51 +135,22 @@ def test_faithful_variants_reproduce_the_reference_failures_fg_does_not(fixture)
                      "fg + reference covariance": ew.run_hip(hip, w, "fg", covariance="reference")}
     ref = {seed: fixture["seed%d" % seed]["reference_order"] for seed in ew.SEEDS}
     cen = {seed: fixture["seed%d" % seed]["centred_means"] for seed in ew.SEEDS}
-    yard = [ew.jaccard(ref[s]["failed_ids"], cen[s]["failed_ids"]) for s in ew.SEEDS]
+    yard = yardstick(fixture)
     ref_first = sum((ref[s]["failed_first_step"] for s in ew.SEEDS), [])
     cen_first = sum((cen[s]["failed_first_step"] for s in ew.SEEDS), [])
     print("[oracle] pooled failed @479: %d (reference order) / %d (centred means); overlap of the two per seed %s; first-failure step median %d / %d, "
           "KS distance between them %.3f" % (sum(ref[s]["failed_at"]["479"] for s in ew.SEEDS), sum(cen[s]["failed_at"]["479"] for s in ew.SEEDS),
                                           np.round(yard, 3).tolist(), np.median(ref_first), np.median(cen_first), ks_distance(ref_first, cen_first)))
-    # ---- the behaviour-faithful variants
+    # ---- the behaviour-faithful variants: against the oracle, and against the reference's own code (the same gate, the same runs)
     for name in ("hybrid", "elements"):
-        r = runs[name]
-        # (1) pooled counts per window
-        for wdw in ew.WINDOWS:
-            a, b = sum(r[s]["failed_at"][wdw] for s in ew.SEEDS), sum(ref[s]["failed_at"][str(wdw)] for s in ew.SEEDS)
-            assert band(a, b), (name, wdw, a, b)
-        tot = sum(r[s]["failed_at"][479] for s in ew.SEEDS)
-        assert tot >= 150
-        # (2) the ladder, not Kepler; nothing from the update
-        mix = np.sum([r[s]["status_mix"] for s in ew.SEEDS], axis=0)
-        assert mix[_lib.ST_PREDICT_LINALG] >= 0.8 * tot and mix[_lib.ST_UPDATE_NAN] == 0 and mix[_lib.ST_UPDATE_LINALG] == 0
-        # (3) a 'jones' episode ends where the reference's does
-        for s in ew.SEEDS:
-            assert abs(r[s]["jones_done_step"] - ref[s]["jones_done_step"]) <= 1, (name, s)
-        # (4) WHICH filters: overlap with the oracle's failed sets at the level of the oracle's own yardstick (its two summation orders)
-        J = [ew.jaccard(r[s]["failed_ids"], ref[s]["failed_ids"]) for s in ew.SEEDS]
-        Jc = [ew.jaccard(r[s]["failed_ids"], cen[s]["failed_ids"]) for s in ew.SEEDS]
-        # (5) the population they come from: filters the ORACLE sees diverged by step 300
-        k = n = 0
-        for s in ew.SEEDS:
-            kk, nn = late_in_population(r[s], ref[s]["diverged_at_%d" % ew.DIVERGED_STEP])
-            k, n = k + kk, n + nn
-        # (6) WHEN: the distribution of first-failure steps
-        first = sum((r[s]["failed_first_step"] for s in ew.SEEDS), [])
-        ks = ks_distance(first, ref_first)
-        print("[%s] pooled failed @479: %d; per seed %s; overlap with the oracle per seed %s (mean %.3f; with its centred-means run %.3f; the oracle's "
-              "own yardstick %.3f); late failures inside the oracle's diverged population: %d of %d; first-failure step median %d (oracle %d), KS %.3f"
-              % (name, tot, [r[s]["failed_at"][479] for s in ew.SEEDS], np.round(J, 3).tolist(), np.mean(J), np.mean(Jc), np.mean(yard), k, n,
-                 np.median(first), np.median(ref_first), ks))
-        assert np.mean(J) >= 0.5 * np.mean(yard) and np.mean(J) >= 0.03, (name, J, yard)       # (chance: 0.014)
-        assert k >= 0.4 * n, (name, k, n)                                                         # (a random 13 % would give 0.13)
-        assert abs(np.median(first) - np.median(ref_first)) <= 25 and ks <= 0.25, (name, np.median(first), np.median(ref_first), ks)
-        assert all(150 <= r[s]["first_failure_step"] <= 400 for s in ew.SEEDS)
+        hold_to(name, runs[name], ref, yard, "the oracle", also=("its centred-means run", cen))
+        hold_to(name, runs[name], reference_fixture, yard, "the reference composite")
     # ---- fg: NOT the reference's failure behaviour (more accurate on diverged states; nothing fails), stated as such
     for s in ew.SEEDS:
         fg = runs["fg"][s]
         assert all(v == 0 for v in fg["failed_at"].values()), (s, fg["failed_at"])
         assert abs(fg["jones_done_step"] - ref[s]["jones_done_step"]) <= 1        # a 'jones' episode still ends at the same step
+        assert abs(fg["jones_done_step"] - reference_fixture[s]["jones_done_step"]) <= 1      # ... as the reference's own code ends it
     # what each ingredient contributes: the reference's covariance arithmetic alone (with the accurate propagator) fails nothing,
     # its propagator alone (with the cancellation-free covariance) a tenth of the reference's count
     assert all(v == 0 for v in extra["fg + reference covariance"]["failed_at"].values())
