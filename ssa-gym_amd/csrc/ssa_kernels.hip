@@ -214,12 +214,13 @@ SSA_DEV int64_t env_row0(const ssa_step_params& p, int64_t base)
 {
     return p.n_env > 1 ? (int64_t)((uint32_t)base / (uint32_t)p.n_obj) * p.n_obj : 0;
 }
-// PLAIN (step_plain_kernel, see ActPlain): one env and no obs_mirror, known when the kernel was compiled
+// PLAIN (step_plain_kernel, see ActPlain): one env and no obs_mirror, known when the kernel was compiled -- and the ragged last tile only:
+// the plain form's whole tile has a store stage of its own (plain_tile_out)
 template <bool NT, bool PLAIN = false>
 SSA_DEV void store_tile(const Tiles& t, const ssa_step_params& p, int lane, int64_t base, int cnt)
 {
 #define SSA_SKIP(b) 0   // (no store is skipped; without the ragged tile's `skip` below the multi-tile step kernel allocates its registers differently)
-    if (cnt == OBJ_PER_WAVE) {
+    if (!PLAIN && cnt == OBJ_PER_WAVE) {
         // A whole tile (wave-uniform; every tile of a launch but a ragged last one).  Every group of lanes stores from
         // (uniform pointer) + lane x 16 bytes on both sides -- the global address in scalar-base + lane-offset form, the LDS address
         // one shared register plus an immediate -- instead of selecting 64-bit destination and source pointers per lane range
@@ -246,7 +247,7 @@ SSA_DEV void store_tile(const Tiles& t, const ssa_step_params& p, int lane, int6
             }
             if (NT) __builtin_nontemporal_store(pair, reinterpret_cast<v2d*>(dst));
             else *reinterpret_cast<v2d*>(dst) = pair;
-            if (!PLAIN && p.obs_mirror) {   // (e.g. host-mapped memory; with obj_ids: row by row at the caller's index of the object)
+            if (p.obs_mirror) {   // (e.g. host-mapped memory; with obj_ids: row by row at the caller's index of the object)
                 // (in observation entries; several envs: the table holds indices within the env, whose rows start at env_row0)
                 const int64_t at = p.obj_ids ? (env_row0(p, base) + t.Oid[jj]) * 12 + r : base * 12 - 64 + 2 * lane;
                 if (p.launch_mask & SSA_LAUNCH_MIRROR_F32)      // the host-facing copy in single precision: half the bytes over PCIe
@@ -258,7 +259,7 @@ SSA_DEV void store_tile(const Tiles& t, const ssa_step_params& p, int lane, int6
         if (!SSA_SKIP(8) && lane < 16) {   // metrics [E][4][m]: four 32-byte runs per tile
             const int kk = lane >> 2, jj = lane & 3;
             const int64_t obj = base + jj;
-            if (PLAIN || p.n_env == 1) {   // (scalar row stride, one 64-bit multiply-add per lane)
+            if (p.n_env == 1) {   // (scalar row stride, one 64-bit multiply-add per lane)
                 p.metrics[(int64_t)kk * p.n_obj + obj] = t.Met[jj * 4 + kk];
             } else {
                 const int64_t e = (int64_t)((uint32_t)obj / (uint32_t)p.n_obj), j = obj - e * p.n_obj;
@@ -305,23 +306,28 @@ SSA_DEV void store_tile(const Tiles& t, const ssa_step_params& p, int lane, int6
 }
 
 // O1/O2 for the row's object from the tiles (results.py:61, :37)
+// metric l (< 4) of row g's object: |x - x_true| over the position / the velocity block, then sigma_pos, sigma_vel.  Written once:
+// observe_rows stages it in t.Met, the plain whole-tile store stage (plain_tile_out) stores it from the register -- the same
+// expressions in the same order (under -ffp-contract=fast a reworded sum may contract differently)
+SSA_DEV double metric_value(const Tiles& t, int g, int l)
+{
+    const int off = (l & 1) * 3;  // 0: position block, 1: velocity block
+    double v;
+    if (l < 2) {
+        double a0 = t.X[g * 6 + off] - t.T[g * 6 + off];
+        double a1 = t.X[g * 6 + off + 1] - t.T[g * 6 + off + 1];
+        double a2 = t.X[g * 6 + off + 2] - t.T[g * 6 + off + 2];
+        v = sqrt_fast(a0 * a0 + a1 * a1 + a2 * a2);
+    } else {   // (a negative sum -- indefinite covariance -- gives NaN, as numpy's sqrt)
+        v = sqrt_fast(t.P[g * 36 + 7 * off] + t.P[g * 36 + 7 * (off + 1)] + t.P[g * 36 + 7 * (off + 2)]);
+    }
+    return v;
+}
 SSA_DEV void observe_rows(Tiles& t, int g, int l, bool stage_obs)
 {
     // (a whole tile's observation rows leave straight from the state / covariance tiles: store_tile)
     if (stage_obs && l < 12) t.Obs[g * 12 + l] = (l < 6) ? t.X[g * 6 + l] : t.P[g * 36 + 7 * (l - 6)];
-    if (l < 4) {
-        const int off = (l & 1) * 3;  // 0: position block, 1: velocity block
-        double v;
-        if (l < 2) {
-            double a0 = t.X[g * 6 + off] - t.T[g * 6 + off];
-            double a1 = t.X[g * 6 + off + 1] - t.T[g * 6 + off + 1];
-            double a2 = t.X[g * 6 + off + 2] - t.T[g * 6 + off + 2];
-            v = sqrt_fast(a0 * a0 + a1 * a1 + a2 * a2);
-        } else {   // (a negative sum -- indefinite covariance -- gives NaN, as numpy's sqrt)
-            v = sqrt_fast(t.P[g * 36 + 7 * off] + t.P[g * 36 + 7 * (off + 1)] + t.P[g * 36 + 7 * (off + 2)]);
-        }
-        t.Met[g * 4 + l] = v;
-    }
+    if (l < 4) t.Met[g * 4 + l] = metric_value(t, g, l);
 }
 
 // U3 on the matrix unit.  With D^(g) the 12 x 8 matrix of object g's rows [d_i, 1, 0], the transform needs
@@ -1465,6 +1471,91 @@ SSA_DEV void dryrun_store(const Tiles& t, double* rec, int g, int l, double acti
     }
 }
 
+// ---- The store stage of a WHOLE tile in the plain form (step_plain_kernel, ActPlain): what store_tile's whole-tile block writes, word for
+// word, scheduled for a wavefront whose life is bound by dependent round trips.
+//   plain_dst_fetch: what the compiler does not keep from the head -- the destinations status, obs, metrics and the metrics' row stride
+//     n_obj -- in ONE batch of scalar loads from the argument segment, issued in front of the metrics' arithmetic and waited for once,
+//     behind it.  As asm statements: a plain load of an argument word is sunk to its use, which puts a scalar round trip in front of each
+//     store group.  The pointers are typed as global ones -- through an asm statement an untyped pointer is generic and its stores go
+//     through the FLAT segment.  The caller issues the batch on the path that waits for it ONLY: the compiler takes an asm statement's
+//     results for written when it has run, and would hand their registers out again while the loads are still in flight.
+//   plain_tile_out: the metrics and the status word leave from the lanes that computed them (no t.Met / t.St round trip).  Then every lane
+//     issues ALL its LDS reads -- P main (16 B), one 16-byte piece by lane range (the tail of P | x | x_true), the observation pair --
+//     before the first store, and the stores follow behind counted waits (the DS unit returns a wavefront's reads in issue order).
+//     Every store is (scalar base) + (unsigned 32-bit lane offset): one shared offset register, lane x 16, for P / x / x_true, whose bases
+//     are moved back by the group's first lane on the scalar unit.  The observation rows [x, diag P] of object g leave from lanes 8..13
+//     of row g (no division: the row IS the object), entries [2 k, 2 k + 2) from lane 8 + k.  n_obj: one tile per wavefront bounds it by
+//     80 x the CU count (tile_grid), far below 2^24, so lane x n_obj is a 24-bit multiply and every byte offset fits 32 bits.
+typedef __attribute__((address_space(1))) char* GlobalBytes;
+struct PlainDst {
+    __attribute__((address_space(1))) int32_t* status;
+    __attribute__((address_space(1))) double *obs, *metrics;
+    uint32_t n_obj;   // (the low word: see above)
+};
+SSA_DEV void plain_dst_fetch(PlainDst& d)
+{
+    const ConstPtr<ssa_step_params> kp = tile_kernel_params();
+    asm volatile("s_load_dwordx2 %0, %4, %5\n\ts_load_dwordx2 %1, %4, %6\n\ts_load_dwordx2 %2, %4, %7\n\ts_load_dword %3, %4, %8"
+                 : "=&s"(d.status), "=&s"(d.obs), "=&s"(d.metrics), "=&s"(d.n_obj)
+                 : "s"(kp), "i"(offsetof(ssa_step_params, status)), "i"(offsetof(ssa_step_params, obs)), "i"(offsetof(ssa_step_params, metrics)),
+                   "i"(offsetof(ssa_step_params, n_obj)));
+}
+// a store base the compiler cannot see into: it would peel the constant part off again and add it behind a per-lane 64-bit sum
+SSA_DEV GlobalBytes opaque_base(GlobalBytes b)
+{
+    asm volatile("" : "+s"(b));
+    return b;
+}
+template <bool NT>
+SSA_DEV void store16_at(GlobalBytes sbase, uint32_t off, v2d v)
+{
+    // (the offset is made the masked region's own value: shared between regions its zero-extension is hoisted out of them, and the
+    // store, which then sees a 64-bit register pair, adds the base per lane)
+    asm volatile("" : "+v"(off));
+    __attribute__((address_space(1))) v2d* dst = (__attribute__((address_space(1))) v2d*)(sbase + (uint64_t)off);
+    if (NT) __builtin_nontemporal_store(v, dst);
+    else *dst = v;
+}
+template <bool NT>
+SSA_DEV void plain_tile_out(Tiles& t, const ssa_step_params& p, PlainDst d, int lane, int64_t base, double met, int st_new)
+{
+    const uint32_t g = (uint32_t)lane >> 4, l = (uint32_t)lane & 15u;
+    // the destinations have arrived (the one wait for the scalar batch, in front of the stage's first LDS read)
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(d.status), "+s"(d.obs), "+s"(d.metrics), "+s"(d.n_obj)::"memory");
+    if (l < 4u) *(__attribute__((address_space(1))) double*)((GlobalBytes)(d.metrics + base) + (uint64_t)((__umul24(l, d.n_obj) + g) << 3)) = met;
+    if (l == 0u) *(__attribute__((address_space(1))) int32_t*)((GlobalBytes)(d.status + base) + (uint64_t)(g << 2)) = st_new;
+    // the batch: four reads per lane, every address inside the tiles whatever the lane (a lane outside a group reads words it does not store)
+    const uint32_t t0 = (uint32_t)(uintptr_t)(LdsVoidPtr)&t;
+    const uint32_t off16 = (uint32_t)lane << 4;
+    const uint32_t a_main = t0 + (uint32_t)offsetof(Tiles, P) + off16;
+    const uint32_t a_aux = a_main + (lane < 8 ? 1024u : lane < 20 ? (uint32_t)offsetof(Tiles, X) - 8u * 16u : (uint32_t)offsetof(Tiles, T) - 20u * 16u);
+    // lanes 8..13 of a row, k = l - 8: its object's observation entries [2 k, 2 k + 2) -- x[2 k], x[2 k + 1] (k < 3) | P[2 k - 6][2 k - 6] and the
+    // next diagonal entry: g x (row bytes) + l x (step) + (origin - 8 steps), the three constants selected by the half (24-bit multiply-adds)
+    const uint32_t k = l - 8u;
+    const bool ox = l < 11u;
+    const uint32_t a_o0 = t0 + __umul24(g, ox ? 48u : 288u) + __umul24(l, ox ? 16u : 112u) +
+                          (ox ? (uint32_t)offsetof(Tiles, X) - 8u * 16u : (uint32_t)offsetof(Tiles, P) - 11u * 112u);
+    const uint32_t a_o1 = a_o0 + (ox ? 8u : 56u);
+    v2d m, a;
+    double o0, o1;
+    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b64 %2, %6\n\tds_read_b64 %3, %7"
+                 : "=&v"(m), "=&v"(a), "=&v"(o0), "=&v"(o1)
+                 : "v"(a_main), "v"(a_aux), "v"(a_o0), "v"(a_o1)
+                 : "memory");
+    const GlobalBytes Pb = (GlobalBytes)((__attribute__((address_space(1))) double*)p.P_out + base * 36);
+    const GlobalBytes Pt = opaque_base(Pb + 1024);
+    const GlobalBytes xb = opaque_base((GlobalBytes)((__attribute__((address_space(1))) double*)p.x_out + base * 6) - 8 * 16);
+    const GlobalBytes tb = opaque_base((GlobalBytes)((__attribute__((address_space(1))) double*)p.x_true_out + base * 6) - 20 * 16);
+    asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(m)::"memory");
+    store16_at<NT>(Pb, off16, m);
+    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(a)::"memory");
+    if (lane < 8) store16_at<NT>(Pt, off16, a);
+    if ((unsigned)(lane - 8) < 12u) store16_at<NT>(xb, off16, a);
+    if ((unsigned)(lane - 20) < 12u) store16_at<NT>(tb, off16, a);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(o0), "+v"(o1)::"memory");
+    if (k < 6u) store16_at<NT>((GlobalBytes)(d.obs + base * 12), __umul24(g, 96u) + (k << 4), v2d{o0, o1});
+}
+
 template <int PROP, int TILE, class ACT>
 SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& p, int lane, int64_t obj_in, bool valid,
                           int64_t base, int cnt, TileRegs& pf, int64_t next_base, int next_cnt, int tile, ACT& asrc)
@@ -2204,7 +2295,7 @@ look_pass:
         for (int idx = l; idx < 36; idx += 16) t.P[g * 36 + idx] = p.P_in[obj * 36 + idx];
         if (l < 6) t.X[g * 6 + l] = p.x_in[obj * 6 + l];
     }
-    if (l == 0) t.St[g] = st_new;
+    if (!(PLAIN && cnt == OBJ_PER_WAVE) && l == 0) t.St[g] = st_new;   // (the plain form's whole tile stores the register: plain_tile_out)
     }
     wave_lds_sync();
     if constexpr (LSENS) {   // sensor look_s's outputs (one env), then the next sensor's pass
@@ -2234,7 +2325,18 @@ look_pass:
     } else if constexpr (DRY) {   // the records are out; nothing of the step's epilogue, and the tile stays where it is
         return;
     }
-    observe_rows(t, g, l, cnt != OBJ_PER_WAVE);
+    // (the plain form's whole tile -- wave-uniform --: the metrics from registers and a store stage of its own, see plain_tile_out)
+    const bool plain_whole = PLAIN && cnt == OBJ_PER_WAVE;
+    if constexpr (PLAIN) {
+        if (plain_whole) {
+            PlainDst dst;
+            plain_dst_fetch(dst);
+            double met = 0.0;
+            if (l < 4) met = metric_value(t, g, l);
+            plain_tile_out<TILE != 1>(t, p, dst, lane, base, met, st_new);
+        }
+    }
+    if (!plain_whole) observe_rows(t, g, l, cnt != OBJ_PER_WAVE);
     // O4 in the epilogue (atomics-statistics path): the (az, el, range, trace P) block of the NEW state -- the 'aer'
     // observation mode and the multi-GPU all-gather payload -- from the tiles, so that no second pass over x / P (the
     // former post kernel: 6.7 MB re-read per 20 000 objects plus a launch) is needed
@@ -2250,7 +2352,7 @@ look_pass:
             __hip_atomic_store(slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (agent scope: SSA_LAUNCH_FOLD_INSIDE reads them in this launch)
             __hip_atomic_store(slot + 1, idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        store_tile<TILE != 1, PLAIN>(t, p, lane, base, cnt);
+        if (!plain_whole) store_tile<TILE != 1, PLAIN>(t, p, lane, base, cnt);
         // O3 by sharded atomics: max delta_pos (as ordered bits: non-negative doubles and NaN order like unsigned
         // integers, so NaN wins exactly as in np.max), trinary counts (packed in one word), failures
         const bool one_env = SSA_NENV == 1 || ((uint32_t)base / (uint32_t)p.n_obj == (uint32_t)(base + cnt - 1) / (uint32_t)p.n_obj);
