@@ -16,21 +16,26 @@ def planted(m):
     return (1, 2) if m < 8 else (m - 3, 2)
 
 
-def make_engine(hip, m, propagator, layout, generic):
+def make_engine(hip, m, propagator, layout, generic, z_noise=None, R=None, plant=True):
+    """z_noise ([1][N_TIME][m][3]) / R: another noise table / measurement covariance than the module's own; plant=False: the batch as
+    make_batch gives it, nothing planted (callers that make filters fail INSIDE a step bring their own trouble)"""
     g = make_batch(8, seed=1)[3]
-    consts = hip.host.make_consts(g["Q"], g["R"], 1e-4, 2.0, -3, 20.0, np.radians(20.0), g["obs_lla"], obs_type='aer', propagator=propagator)
+    consts = hip.host.make_consts(g["Q"], g["R"] if R is None else R, 1e-4, 2.0, -3, 20.0, np.radians(20.0), g["obs_lla"], obs_type='aer',
+                                  propagator=propagator)
     xt, x, P, _ = make_batch(m, seed=1200 + m)
     nan_obj, failed_obj = planted(m)
-    x[nan_obj, 1] = np.nan
+    if plant:
+        x[nan_obj, 1] = np.nan
     trans = c2t()[:N_TIME]
-    zn = np.random.RandomState(3).normal(size=(1, N_TIME, m, 3)) * np.array([4.8e-6, 4.8e-6, 1e3])
+    zn = np.random.RandomState(3).normal(size=(1, N_TIME, m, 3)) * np.array([4.8e-6, 4.8e-6, 1e3]) if z_noise is None else z_noise
     eng = hip.engine.HotPathEngine(consts, m, 1, trans, zn, history=H)
     eng.force_generic = generic
     if layout:
         eng.set_layout(np.random.RandomState(m).permutation(m))
     eng.load_state(0, xt, x, P)
-    pos = int(eng._slot_of[failed_obj]) if layout else failed_obj
-    eng.status[pos] = hip.lib.ST_UPDATE_LINALG      # failed before the first step: its state passes through
+    if plant:
+        pos = int(eng._slot_of[failed_obj]) if layout else failed_obj
+        eng.status[pos] = hip.lib.ST_UPDATE_LINALG      # failed before the first step: its state passes through
     return eng, consts
 
 
@@ -51,14 +56,14 @@ def schedule(m):
     return [0, nan_obj, failed_obj, m - 1, 0, 1 % m]
 
 
-def run(hip, m, propagator, layout, generic):
+def run(hip, m, propagator, layout, generic, z_noise=None, R=None, actions=None, plant=True):
     """N_STEPS deferred-fold steps through HipLocalStepper on the two-slot ring: the slot each step wrote, each step's statistics row
-    (cloned once the next launch -- or flush() -- has folded it), the failure log, and the instance every launch took"""
+    (cloned once the next launch -- or flush() -- has folded it), the failure log, and the instance every launch took.  z_noise / R / plant: make_engine's; actions: another schedule of N_STEPS actions than schedule(m)"""
     from ssa_gym_amd import parallel
-    eng, consts = make_engine(hip, m, propagator, layout, generic)
+    eng, consts = make_engine(hip, m, propagator, layout, generic, z_noise=z_noise, R=R, plant=plant)
     assert eng.stats_from_metrics
     local = parallel.HipLocalStepper(eng, consts, fast_stats=True, defer_fold=True)
-    local.load_schedule(schedule(m))
+    local.load_schedule(schedule(m) if actions is None else list(actions))
     steps, rows = [], {}
     for _ in range(N_STEPS):
         local.step(-1)
