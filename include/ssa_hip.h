@@ -759,6 +759,31 @@ int ssa_dryrun_sensors_envs_f64(const ssa_consts *c, const ssa_step_params *p, c
  * Refused before any launch (SSA_E_INVALID): NULL records or total, a count < 1, n_sensor > SSA_MAX_SENSORS,
  * n_env * n_sensor * n_steps >= 2^31. */
 int ssa_dryrun_totals_f64(const double *records, int32_t n_env, int32_t n_steps, int32_t n_sensor, double *total, void *stream);
+/* ... and the gathered block in front of it, for B candidates in each of E envs: the E * B pseudo-envs of W rows that
+ * ssa_dryrun_sensors_envs_f64 then takes (n_env = E * B, n_obj = W, obj_ids = ids, env_time = time_out), copied out of the envs' state
+ * in ONE launch.  Output row q = (e * B + b) * W + w:
+ *   j = ids[q]; an id < 0 or >= n_obj (padding, or anything else) is replaced by the candidate's first id, ids[(e * B + b) * W], taken
+ *   as 0 when negative and as n_obj - 1 when >= n_obj -- a padding row carries the state of the candidate's first object, and of object 0
+ *   in an all-idle candidate: a healthy row to predict;
+ *   r = e * n_obj + j, the caller's global row; with a slot_of table r = slot_of[r], the storage row (an entry outside 0 .. E * n_obj - 1
+ *   is brought to the nearest end: the launch reads inside the source blocks whatever ids and slot_of hold);
+ *   rows r of x_true_in, x_in, P_in (6, 6 and 36 doubles) and word r of status_in are copied to row q of the outputs, bit for bit;
+ *   time_out[e * B + b] = env_time[e].
+ * Nothing else is written.  The outputs must not overlap the inputs or one another.
+ * Refused before any launch (SSA_E_INVALID): a NULL block, any NULL pointer but slot_of, a count < 1, n_rows % 4 != 0, reserved != 0,
+ * E * B * W >= 2^31 or E * n_obj >= 2^31, one of the six double pointers not 16-byte aligned (the rows move as 16-byte pieces). */
+typedef struct ssa_dryrun_gather_params {
+    int64_t n_obj;             /* m: rows per env in the source block */
+    int32_t n_env, n_cand;     /* E >= 1, B >= 1 */
+    int32_t n_rows, reserved;  /* W >= 4, W % 4 == 0;  reserved == 0 */
+    const int32_t *ids;        /* [E*B][W]: the caller's object index, -1 = padding */
+    const int32_t *slot_of;    /* [E*m] caller's global row -> storage row, or NULL */
+    const int32_t *env_time;   /* [E] */
+    const double *x_true_in, *x_in, *P_in;  const int32_t *status_in;   /* [E*m] rows of 6 / 6 / 36 doubles, 1 word */
+    double *x_true_out, *x_out, *P_out;  int32_t *status_out;           /* [E*B*W] rows */
+    int32_t *time_out;         /* [E*B] */
+} ssa_dryrun_gather_params;
+int ssa_dryrun_gather_f64(const ssa_dryrun_gather_params *g, void *stream);
 
 /* ---------------------------------------------------------------- the tasking assignment of a sensor network, on the device
  * One object per sensor from one column of the scores ssa_lookahead_sensors_f64 leaves, in ONE launch and written where the next launch

@@ -93,6 +93,12 @@ class ssa_dryrun_sensors_params(C.Structure):
     _fields_ = [("n_steps", C.c_int32), ("n_obj_caller", C.c_int32), ("actions", c_dp), ("out", c_dp)]
 
 
+class ssa_dryrun_gather_params(C.Structure):
+    _fields_ = [("n_obj", C.c_int64), ("n_env", C.c_int32), ("n_cand", C.c_int32), ("n_rows", C.c_int32), ("reserved", C.c_int32),
+                ("ids", c_dp), ("slot_of", c_dp), ("env_time", c_dp), ("x_true_in", c_dp), ("x_in", c_dp), ("P_in", c_dp),
+                ("status_in", c_dp), ("x_true_out", c_dp), ("x_out", c_dp), ("P_out", c_dp), ("status_out", c_dp), ("time_out", c_dp)]
+
+
 class ssa_screen_params(C.Structure):
     _fields_ = [
         ("n", C.c_int64), ("n_time", C.c_int32), ("n_site", C.c_int32), ("step", C.c_double), ("min_alt", C.c_double),
@@ -160,6 +166,7 @@ SIGNATURES = {
     "ssa_dryrun_sensors_envs_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
                                               C.POINTER(ssa_dryrun_sensors_params), c_dp]),
     "ssa_dryrun_totals_f64": (C.c_int, [c_dp, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp]),
+    "ssa_dryrun_gather_f64": (C.c_int, [C.POINTER(ssa_dryrun_gather_params), c_dp]),
     "ssa_env_rollout_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_rollout_params),
                                               C.POINTER(ssa_sensor_params), C.POINTER(ssa_rollout_sensors_params), c_dp]),
     "ssa_env_rollout_sensors_envs_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_rollout_params),

@@ -352,13 +352,16 @@ def refine_plan_sensors(env, plan, kind='info', rounds=4, candidates=64, seed=0)
     (k, s) redrawn from the objects the forecast shows visible to s at step k with status OK and not already in row k -- an object
     planned at another step is allowed: the revisit the forecast planners cannot express.  The incumbent becomes the first candidate
     with the largest total in column `kind` ('info', 'trace', 'pos_trace').  ONE forecast launch for the masks.  The draws come from
-    RandomState(seed): env.np_random and the action space's generator are not touched.  Returns (plan, total [3] float64 of it)."""
+    RandomState(seed): env.np_random and the action space's generator are not touched.  Returns (plan, total [3] float64 of it).
+    A vector env (SSA_Tasker_VecEnv; section 8q): `plan` [E, K, S]; env e searches with RandomState(seed + e) exactly as a single env
+    in its state would with that seed, one forecast and one evaluate_schedules() launch per round serve all envs; returns
+    (plan [E, K', S], total [E, 3])."""
     if kind not in REFINE_KINDS:
         raise ValueError("refine_plan_sensors: kind must be one of %s, got %r" % (sorted(REFINE_KINDS), kind))
     if int(rounds) < 0 or int(candidates) < 1:
         raise ValueError("refine_plan_sensors: rounds >= 0 and candidates >= 1, got %r and %r" % (rounds, candidates))
     if hasattr(env, "num_envs"):
-        raise _lib.SsaHipError("refine_plan_sensors covers a single env (the vector env has no dry run yet)")
+        return _refine_plan_sensors_envs(env, plan, REFINE_KINDS[kind], int(rounds), int(candidates), seed)
     if env._engine is None:
         raise _lib.SsaHipError("no device state: a plan is refined by dry runs, which run on the GPU only (no CPU fallback)")
     col = REFINE_KINDS[kind]
@@ -393,4 +396,45 @@ def refine_plan_sensors(env, plan, kind='info', rounds=4, candidates=64, seed=0)
         plan, total = cand[best], totals[best]
     if total is None:
         total = env.evaluate_schedules(plan)["total"].cpu().numpy()[0]
+    return plan, np.asarray(total, dtype=np.float64)
+
+
+def _refine_plan_sensors_envs(vec, plan, col, rounds, candidates, seed):
+    """refine_plan_sensors for a vector env: `plan` [E, K, S]; every env runs the single env's local search on
+    its own incumbent with its own RandomState(seed + e), drawn from in the single env's order, and ONE vec.evaluate_schedules()
+    launch per round values the candidates of all envs ([E, candidates, K', S]); ONE vec.forecast_sensors() for the masks.  One horizon
+    for all envs, K' = min(K, min_e(steps - 1 - i_e)).  Returns (plan [E, K', S] int64 as vec.rollout_sensors() takes it, total [E, 3])."""
+    if vec._eng is None:
+        raise _lib.SsaHipError("no device state: a plan is refined by dry runs, which run on the GPU only (no CPU fallback)")
+    E, S = int(vec.num_envs), int(vec.n_sensor)
+    plan = np.array(plan, dtype=np.int64)
+    if plan.ndim != 3 or plan.shape[0] != E or plan.shape[2] != S:
+        raise ValueError("refine_plan_sensors: a plan [%d, K, %d], got shape %s" % (E, S, plan.shape))
+    K = min(plan.shape[1], int(vec.n - 1 - np.max(vec.i)))
+    if K < 1:
+        raise ValueError("refine_plan_sensors: at least one step inside every env's episode")
+    plan = plan[:, :K]
+    rngs = [np.random.RandomState(seed + e) for e in range(E)]
+    ok = None
+    if candidates > 1 and rounds > 0:
+        f = vec.forecast_sensors(K)
+        ok = (f["visible"].cpu().numpy() != 0) & (f["status"].cpu().numpy() == _lib.ST_OK)       # [E, K', S, m]
+    total = None
+    for _ in range(rounds if candidates > 1 else 0):
+        cand = np.repeat(plan[:, None], candidates, axis=1)
+        for e in range(E):
+            for c in range(1, candidates):
+                k, s = divmod(int(rngs[e].randint(K * S)), S)
+                free = ok[e, k, s].copy()
+                row = plan[e, k]
+                free[row[(row >= 0) & (row < free.shape[0])]] = False
+                pool = np.flatnonzero(free)
+                if len(pool):
+                    cand[e, c, k, s] = pool[rngs[e].randint(len(pool))]
+        totals = vec.evaluate_schedules(cand)["total"].cpu().numpy()                              # [E, candidates, 3]
+        # (per env the first of equal maxima; a NaN total never wins: the single env's rule)
+        best = np.argmax(np.where(np.isnan(totals[:, :, col]), -np.inf, totals[:, :, col]), axis=1)
+        plan, total = cand[np.arange(E), best], totals[np.arange(E), best]
+    if total is None:
+        total = vec.evaluate_schedules(plan)["total"].cpu().numpy()[:, 0]
     return plan, np.asarray(total, dtype=np.float64)

@@ -2935,6 +2935,54 @@ __global__ void __launch_bounds__(64) dryrun_totals_kernel(const double* __restr
         }
     total[i] = t;
 }
+// The gathered block of a vector dry run (ssa_dryrun_gather_f64): output row q of the E * B * W takes the 48 doubles and the status
+// word of one source row.  A row is 24 pieces of 16 bytes (3 of x_true, 3 of x, 18 of P: the row strides of 48 and 288 bytes keep
+// every piece aligned) and one word: half a wavefront per row, one lane per piece -- lanes 0 .. 23 a piece each, lane 24 the status
+// word, lane 25 of a candidate's first row its time word, the rest idle -- so a wavefront holds two whole rows and a block eight.
+// Every lane of a row forms the same source row from the same two or three words (the id, the candidate's first id, the table's
+// entry): broadcast loads.  The indices are brought into range before they address anything.
+#define SSA_GATHER_ROWS 8     // rows per block of 256 lanes
+__global__ void __launch_bounds__(32 * SSA_GATHER_ROWS) dryrun_gather_kernel(const ssa_dryrun_gather_params g)
+{
+    const int lane = threadIdx.x & 31;
+    const int64_t q = (int64_t)blockIdx.x * SSA_GATHER_ROWS + (threadIdx.x >> 5);
+    const int64_t W = g.n_rows, m = g.n_obj;
+    if (q >= (int64_t)g.n_env * g.n_cand * W || lane > 25) return;
+    // (the launcher keeps every row count below 2^31: 32-bit divisions)
+    const int64_t cand = (uint32_t)q / (uint32_t)g.n_rows;
+    const int64_t e = (uint32_t)cand / (uint32_t)g.n_cand;
+    if (lane == 25) {
+        if (q == cand * W) g.time_out[cand] = g.env_time[e];
+        return;
+    }
+    int64_t j = g.ids[q];
+    if (j < 0 || j >= m) {      // padding: the candidate's first object, object 0 for an all-idle candidate
+        j = g.ids[cand * W];
+        j = j < 0 ? 0 : j >= m ? m - 1 : j;
+    }
+    int64_t r = e * m + j;
+    if (g.slot_of) {
+        r = g.slot_of[r];
+        r = r < 0 ? 0 : r >= g.n_env * m ? g.n_env * m - 1 : r;
+    }
+    if (lane == 24) {
+        g.status_out[q] = g.status_in[r];
+        return;
+    }
+    const double* src;
+    double* dst;
+    if (lane < 3) {
+        src = g.x_true_in + r * 6 + 2 * lane;
+        dst = g.x_true_out + q * 6 + 2 * lane;
+    } else if (lane < 6) {
+        src = g.x_in + r * 6 + 2 * (lane - 3);
+        dst = g.x_out + q * 6 + 2 * (lane - 3);
+    } else {
+        src = g.P_in + r * 36 + 2 * (lane - 6);
+        dst = g.P_out + q * 36 + 2 * (lane - 6);
+    }
+    *reinterpret_cast<double2*>(dst) = *reinterpret_cast<const double2*>(src);
+}
 // grid (n_steps, n_env): folds step k's shard set into the statistics slot of step k -- when that slot still
 // belongs to step k at the end of the rollout (the last `history` steps) -- and clears it
 __global__ void __launch_bounds__(64) rollout_fold_kernel(unsigned long long* __restrict__ shards, double* __restrict__ stats_ring,
@@ -5309,6 +5357,22 @@ int ssa_dryrun_totals_f64(const double* records, int32_t n_env, int32_t n_steps,
     if (!rows_fit(n_env, n_sensor, n_steps)) return SSA_E_INVALID;
     hipLaunchKernelGGL(dryrun_totals_kernel, dim3((unsigned)nblk((int64_t)n_env * SSA_LOOK_NSCORE, 64)), dim3(64), 0, (hipStream_t)stream, records,
                        (int)n_env, (int)n_steps, (int)n_sensor, total);
+    return launch_status();
+}
+int ssa_dryrun_gather_f64(const ssa_dryrun_gather_params* g, void* stream)
+{
+    if (!g || g->n_obj < 1 || g->n_env < 1 || g->n_cand < 1 || g->n_rows < 1 || g->n_rows % 4 || g->reserved) return SSA_E_INVALID;
+    if (!g->ids || !g->env_time || !g->x_true_in || !g->x_in || !g->P_in || !g->status_in || !g->x_true_out || !g->x_out || !g->P_out ||
+        !g->status_out || !g->time_out)
+        return SSA_E_INVALID;
+    // (n_obj and E * B first: every product below stays inside 64 bits)
+    if (g->n_obj >= ((int64_t)1 << 31) || !rows_fit(g->n_env, g->n_obj) || !rows_fit(g->n_env, g->n_cand) ||
+        !rows_fit((int64_t)g->n_env * g->n_cand, g->n_rows))
+        return SSA_E_INVALID;
+    for (const double* ptr : {g->x_true_in, g->x_in, g->P_in, (const double*)g->x_true_out, (const double*)g->x_out, (const double*)g->P_out})
+        if ((uintptr_t)ptr % 16) return SSA_E_INVALID;
+    const int64_t rows = (int64_t)g->n_env * g->n_cand * g->n_rows;
+    hipLaunchKernelGGL(dryrun_gather_kernel, dim3(nblk(rows, SSA_GATHER_ROWS)), dim3(32 * SSA_GATHER_ROWS), 0, (hipStream_t)stream, *g);
     return launch_status();
 }
 // the checks and the argument block shared by ssa_env_rollout_f64 and ssa_env_rollout_sensors_f64 (sens: r->actions is not read); SSA_OK or

@@ -493,6 +493,62 @@ def dryrun_totals(records, out=None):
     return out
 
 
+def dryrun_gather_rows(ids, n_env, n_cand, n_obj, slot_of=None):
+    """the rule of ssa_dryrun_gather_f64 in numpy: for `ids` (integers, E * B * W of them: per env and candidate the W object indices
+    dryrun_rows leaves, -1 = padding) the source row of every output row, int64 [E * B * W].  Row (e, b, w): j = ids[e, b, w]; an id
+    < 0 or >= n_obj is replaced by the candidate's first id, taken as 0 when negative and as n_obj - 1 beyond the end (a padding row
+    carries the state of the candidate's first object; object 0 in an all-idle candidate); the row is e * n_obj + j, and with
+    `slot_of` (the storage row of every caller's global row, [E * n_obj]) slot_of[e * n_obj + j].  Needs no device."""
+    import numpy as np
+    E, B, m = int(n_env), int(n_cand), int(n_obj)
+    a = np.asarray(ids)
+    if E < 1 or B < 1 or m < 1 or a.size < E * B or a.size % (E * B) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("dry-run gather: integer ids [%d * %d, W] with W >= 1 and n_obj >= 1, got %s of %d" % (E, B, a.dtype, a.size))
+    j = a.astype(np.int64).reshape(E, B, -1)
+    first = np.clip(j[:, :, :1], 0, m - 1)
+    rows = np.where((j >= 0) & (j < m), j, first) + (np.arange(E, dtype=np.int64) * m)[:, None, None]
+    if slot_of is not None:
+        t = np.asarray(slot_of).astype(np.int64).reshape(-1)
+        if t.size != E * m:
+            raise ValueError("dry-run gather: slot_of must hold %d rows, got %d" % (E * m, t.size))
+        rows = np.clip(t[rows], 0, E * m - 1)
+    return rows.reshape(-1)
+
+
+def dryrun_gather(ids, env_time, x_true, x_filter, P_filter, status, n_env, n_cand, n_obj, slot_of=None, out=None):
+    """the gathered block of a vector dry run on the device (ssa_dryrun_gather_f64; the rule: dryrun_gather_rows), stateless: `ids`
+    contiguous CUDA int32 [E * B, W] (W % 4 == 0), `env_time` int32 [E], the source block x_true / x_filter [E * n_obj, 6], P_filter
+    [E * n_obj, 6, 6] float64 and status int32 [E * n_obj], slot_of int32 [E * n_obj] or None.  Returns (x_true, x_filter, P_filter,
+    status, time) of the E * B pseudo-envs of W rows -- [E * B * W, 6], [.., 6], [.., 6, 6] float64, [E * B * W] and [E * B] int32; `out`:
+    the five tensors to write, none of them a part of the inputs.  One launch, no host sync."""
+    E, B, m = int(n_env), int(n_cand), int(n_obj)
+    i32 = torch.int32
+    _chk(ids, "ids", i32)
+    if ids.dim() != 2 or ids.shape[0] != E * B:
+        raise _lib.SsaHipError("ids must be [%d, W]" % (E * B))
+    W = int(ids.shape[1])
+    R = E * B * W
+    g = _lib.ssa_dryrun_gather_params()
+    g.n_obj, g.n_env, g.n_cand, g.n_rows, g.reserved = m, E, B, W, 0
+    g.ids, g.env_time = ids.data_ptr(), _chk(env_time, "env_time", i32)
+    g.slot_of = _chk(slot_of, "slot_of", i32) if slot_of is not None else 0
+    g.x_true_in, g.x_in, g.P_in, g.status_in = _chk(x_true, "x_true"), _chk(x_filter, "x_filter"), _chk(P_filter, "P_filter"), _chk(status, "status", i32)
+    for t, n, nm in ((env_time, E, "env_time"), (x_true, 6 * E * m, "x_true"), (x_filter, 6 * E * m, "x_filter"), (P_filter, 36 * E * m, "P_filter"),
+                     (status, E * m, "status")) + (((slot_of, E * m, "slot_of"),) if slot_of is not None else ()):
+        if t.numel() != n:
+            raise _lib.SsaHipError("%s must hold %d elements, got %d" % (nm, n, t.numel()))
+    if out is None:
+        dev = ids.device
+        out = (torch.empty((R, 6), dtype=f64, device=dev), torch.empty((R, 6), dtype=f64, device=dev), torch.empty((R, 6, 6), dtype=f64, device=dev),
+               torch.empty(R, dtype=i32, device=dev), torch.empty(E * B, dtype=i32, device=dev))
+    for t, n, dt, nm in zip(out, (6 * R, 6 * R, 36 * R, R, E * B), (f64, f64, f64, i32, i32), ("x_true", "x_filter", "P_filter", "status", "time")):
+        if _chk(t, "out: " + nm, dt) and t.numel() != n:
+            raise _lib.SsaHipError("out: %s must hold %d elements, got %d" % (nm, n, t.numel()))
+    g.x_true_out, g.x_out, g.P_out, g.status_out, g.time_out = (t.data_ptr() for t in out)
+    _lib.check(_lib.load().ssa_dryrun_gather_f64(C.byref(g), _stream()), "ssa_dryrun_gather_f64")
+    return tuple(out)
+
+
 def env_step(consts, params):
     """E1: the fused step.  `params` is a filled _lib.ssa_step_params."""
     lib = _lib.load()

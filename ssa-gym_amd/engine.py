@@ -121,6 +121,7 @@ class HotPathEngine:
         self._assign_envs_ws = None                     # (S, workspace) of launch_assign_sensors_envs
         self._fore_e = None                             # output buffers of launch_forecast_sensors_envs
         self._dry = {}                                  # launch_dryrun_sensors: per (B, K, S, W) its upload, time words, gathered block and records
+        self._dry_envs = {}                             # launch_dryrun_sensors_envs: per (E * B, K, S, W) its upload, gathered block and records
         self._pcache = {}
         self._cref = C.byref(self.consts)
         self._pref = C.byref(self._p)
@@ -710,6 +711,57 @@ class HotPathEngine:
                 p.env_time, p.obj_ids = buf["time"].data_ptr(), dev_ids.data_ptr()
             device.dryrun_sensors(self.consts, p, sensors, buf["dev"][:nw].view(K, B, _lib.MAX_SENSORS), K, self.m, out=buf["out"])
         return buf["out"].permute(1, 0, 2, 3)
+
+    def launch_dryrun_sensors_envs(self, slot_in, time_offset, sensors, actions, stream=None, env_times=None):
+        """enqueue the dry run of B candidate tasking schedules in EVERY env of the engine (any n_env, 1 included):
+        `actions` integers [E, B, K, S], env e's candidates in e's own object numbering, each read as launch_dryrun_sensors reads one
+        -- step k of env e has the time index (e's time word) + time_offset + k.  The E * B candidates are E * B pseudo-envs of ONE
+        ssa_dryrun_sensors_envs_f64 launch on a gathered block of W rows each (device.dryrun_rows over all of them: W is the batch's),
+        and the block is gathered by ONE ssa_dryrun_gather_f64 launch in front of it -- through the layout's inverse table when one
+        is set -- which also hands every candidate its env's time word.  env_times: the envs' time words by value (any n_env: they
+        travel in the call's one upload, behind the action words and the ids); else the engine's env_time0 words.  The gathered block
+        has whole tiles whatever n_obj is.  Nothing of the engine's state is written.  Returns this engine's record tensor
+        [E, B, K, S, DRY_STRIDE] (a view of a buffer cached per (E * B, K, S, W), rewritten by the next call).  Asynchronous, no host
+        sync, no torch index op."""
+        S, E = int(sensors.n_sensor), self.E
+        if isinstance(actions, torch.Tensor):
+            actions = actions.detach().cpu().numpy()
+        actions = np.asarray(actions)
+        if actions.ndim != 4 or actions.shape[0] != E:
+            raise ValueError("dry run: actions must be an integer array [%d, B, K, S], got shape %s" % (E, actions.shape))
+        B = int(actions.shape[1])
+        ids, words = device.dryrun_rows(actions.reshape((E * B,) + actions.shape[2:]), self.m, S)
+        EB, K, W = E * B, int(words.shape[0]), int(ids.shape[1])
+        if env_times is not None and len(env_times) != E:
+            raise ValueError("dry run: env_times must hold %d time words, got %d" % (E, len(env_times)))
+        key = (EB, K, S, W)
+        buf = self._dry_envs.get(key)
+        if buf is None:
+            R = EB * W
+            d = self.dev
+            buf = self._dry_envs[key] = {
+                "dev": torch.empty(K * EB * _lib.MAX_SENSORS + R + E, dtype=torch.int32, device=d),    # (the words first: 32-byte aligned)
+                "state": (torch.empty((R, 6), dtype=f64, device=d), torch.empty((R, 6), dtype=f64, device=d),
+                          torch.empty((R, 6, 6), dtype=f64, device=d), torch.empty(R, dtype=torch.int32, device=d),
+                          torch.empty(EB, dtype=torch.int32, device=d)),
+                "out": torch.empty((K, EB, S, _lib.DRY_STRIDE), dtype=f64, device=d)}
+        nw, ni = K * EB * _lib.MAX_SENSORS, EB * W
+        times = np.zeros(E, dtype=np.int32) if env_times is None else np.asarray([int(v) for v in env_times], dtype=np.int32)
+        up = np.concatenate((words.reshape(-1), ids.reshape(-1), times))
+        st = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
+        sl = int(slot_in) % self.H
+        with torch.cuda.stream(st):
+            buf["dev"].copy_(torch.from_numpy(up))
+            dev_ids = buf["dev"][nw:nw + ni].view(EB, W)
+            g = device.dryrun_gather(dev_ids, buf["dev"][nw + ni:] if env_times is not None else self.env_time0,
+                                     self.x_true[sl], self.x_filter[sl], self.P_filter[sl], self.status, E, B, self.m,
+                                     slot_of=self._slot_of32 if self._order is not None else None, out=buf["state"])
+            p = self._lookahead_params(slot_in, time_offset)
+            p.n_obj, p.n_env = W, EB
+            p.x_true_in, p.x_in, p.P_in, p.status = (t.data_ptr() for t in g[:4])
+            p.env_time, p.obj_ids = g[4].data_ptr(), dev_ids.data_ptr()
+            device.dryrun_sensors(self.consts, p, sensors, buf["dev"][:nw].view(K, EB, _lib.MAX_SENSORS), K, self.m, out=buf["out"])
+        return buf["out"].view(K, E, B, S, _lib.DRY_STRIDE).permute(1, 2, 0, 3, 4)
 
     def launch_assign_sensors(self, look, column, action_row, fallback_row=None, picks=None, stream=None, rule='greedy'):
         """enqueue the tasking assignment of a sensor network (include/ssa_hip.h: ssa_assign_sensors_f64) on `look`, the dict

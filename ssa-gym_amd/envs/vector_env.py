@@ -550,6 +550,44 @@ class SSA_Tasker_VecEnv:
         r = self._launch_forecast_sensors(horizon, want)
         return {k: v.transpose(0, 1) for k, v in r.items()}
 
+    def evaluate_schedules(self, actions):
+        """SSA_Tasker_Env.evaluate_schedules() of every env from ONE dry-run launch (ssa_dryrun_gather_f64, then
+        ssa_dryrun_sensors_envs_f64 over E * B pseudo-envs): what each of B candidate schedules per env would be
+        worth if rollout_sensors() ran it from env e's state at its step i_e, without spending the envs.  `actions`: integers
+        [E, K, S] (B = 1) or [E, B, K, S], numpy or torch, env e's candidates in e's own object numbering (S = n_sensor; 1 without
+        config['observers']: the envs' own observer as a one-site network); an entry < 0 or >= m is an idle sensor, two sensors on one
+        object in a row are not refused -- the lower one takes it.  ONE horizon for all envs, K' = min(K, min_e(steps - 1 - i_e)), as
+        forecast_sensors().  ValueError: a wrong shape or dtype, K' < 1 (an env without a next step).  The single env's dict with a
+        leading [n_env] axis, CUDA tensors:
+            score   [E, B, K', S, 3] float64: columns _lib.LOOK_* from the step's P- and P+; NaN unless taken
+            taken, visible [E, B, K', S] bool;  status [E, B, K', S] int32;  action [E, B, K', S] int64 (-1: no update attempted)
+            total   [E, B, 3] float64: the sum of the taken slots' scores per column, in slot order (k outer, s inner); 0 for none
+        Nothing of the envs changes: no engine tensor, not i, tick, the bookkeeping or a generator; any rso_count (the gathered block
+        has whole tiles).  The next call with the same shapes overwrites the tensors."""
+        import torch
+        from .. import device
+        if self._eng is None:
+            raise _lib.SsaHipError("no device state: the dry run of a schedule runs on the GPU only (no CPU fallback)")
+        E, S = self.E, self.n_sensor
+        a = actions.detach().cpu().numpy() if isinstance(actions, torch.Tensor) else np.asarray(actions)
+        if a.ndim == 3:
+            a = a[:, None]
+        if a.ndim != 4 or a.shape[0] != E or a.shape[1] < 1 or a.shape[3] != S or a.dtype.kind not in "iu":
+            raise ValueError("evaluate_schedules: integer schedules [%d, K, %d] or [%d, B, K, %d], got %s %s" % (E, S, E, S, a.dtype, a.shape))
+        K = min(int(a.shape[2]), int(self.n - 1 - self.i.max()))
+        if K < 1:
+            raise ValueError("evaluate_schedules: at least one step inside every env's episode (i = %s, steps = %d, K = %d)"
+                             % (self.i.tolist(), self.n, a.shape[2]))
+        B = int(a.shape[1])
+        rec = self._eng.launch_dryrun_sensors_envs(self.tick % 2, 0, self._sites(), a[:, :, :K], stream=self._stream,
+                                                   env_times=[int(v) + 1 for v in self.i])
+        with torch.cuda.stream(self._stream):
+            # (the engine's [K', E * B, S, 8] block; slot order: one defined fp64 sum per candidate)
+            total = device.dryrun_totals(rec.permute(2, 0, 1, 3, 4).reshape(K, E * B, S, _lib.DRY_STRIDE)).view(E, B, _lib.LOOK_NSCORE)
+            return {"score": rec[..., _lib.DRY_SCORE:_lib.DRY_SCORE + _lib.LOOK_NSCORE], "taken": rec[..., _lib.DRY_TAKEN] != 0,
+                    "visible": rec[..., _lib.DRY_VISIBLE] != 0, "status": rec[..., _lib.DRY_STATUS].to(torch.int32),
+                    "action": rec[..., _lib.DRY_ACTION].to(torch.int64), "total": total}
+
     def assign_sensors(self, column, rule='greedy'):
         """the lookahead of every env and every env's assignment over score column `column` (_lib.LOOK_*) by `rule` ('greedy', or
         'optimal': most sensors tasked, then the largest sum): two launches and one read-back of E x 32 bytes.  int64 [E, S]; -1: the
