@@ -1,7 +1,8 @@
 """Thin torch front-end over the C ABI: PyTorch only owns device memory and streams here.
 
 Every function takes/returns CUDA (ROCm) float64 tensors laid out exactly like the
-reference's numpy arrays and launches on torch's current stream.  There is no CPU path:
+reference's numpy arrays and launches on torch's current stream (the sensor-network
+launchers: on the `stream` they are given, see _stream).  There is no CPU path:
 a CPU tensor or a missing library raises.
 """
 import ctypes as C
@@ -21,8 +22,21 @@ def _chk(t, name, dtype=f64):
     return t.data_ptr()
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+def _chk_n(t, name, dtype, n):
+    """_chk of an optional tensor that holds exactly n elements: its pointer, None for None"""
+    if t is None:
+        return None
+    ptr = _chk(t, name, dtype)
+    if t.numel() != n:
+        raise _lib.SsaHipError("%s must hold %d %s words" % (name, n, dtype))
+    return ptr
+
+
+def _stream(stream=None):
+    """the raw handle of `stream`: None (torch's current stream), a torch.cuda.Stream, or the handle itself"""
+    if stream is None:
+        return torch.cuda.current_stream().cuda_stream
+    return stream.cuda_stream if isinstance(stream, torch.cuda.Stream) else stream
 
 
 def as_dev(a, device="cuda", dtype=f64):
@@ -323,31 +337,42 @@ def assign_sensors_workspace(n_obj, n_sensor, device):
     return torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=device)
 
 
-def assign_sensors(score, column, fallback=None, out=None, picks=None, workspace=None, rule='greedy'):
+def assign_sensors(score, column, fallback=None, out=None, picks=None, workspace=None, rule='greedy', stream=None):
     """the tasking assignment of a sensor network on the device (ssa_assign_sensors_f64): the global greedy assignment of
     agents._assign_lookahead_sensors over column `column` (_lib.LOOK_*) of score [S, m, 3] -- the rows launch_lookahead_sensors leaves --
     in ONE launch.  fallback: int32 [MAX_SENSORS] draws for the sensors left without an object (taken in ascending s when in range and held
     by nobody; None: they stay idle, -1).  Returns the int32 CUDA row [MAX_SENSORS] (`out`: a 32-byte aligned row to write, e.g. one row
     of launch_rollout_sensors' schedule; entries s >= S are -1); picks: int64 [MAX_SENSORS, 2] to receive the assigned objects and their
     scores' bit patterns.  workspace: assign_sensors_workspace (default: a fresh one).  rule='optimal': the exact optimum instead
-    (ssa_match_sensors_f64: most sensors tasked, then the largest sum; finite scores only), same arguments, same workspace.  No host sync."""
+    (ssa_match_sensors_f64: most sensors tasked, then the largest sum; finite scores only), same arguments, same workspace.
+    stream: as every launcher's here (None: torch's current stream, a torch.cuda.Stream or a raw handle).  No host sync."""
     entry = assign_entry(rule)
-    lib = _lib.load()
     _chk(score, "score")
     if score.dim() != 3 or score.shape[2] != _lib.LOOK_NSCORE:
         raise _lib.SsaHipError("score must be [S, m, %d]" % _lib.LOOK_NSCORE)
     S, m = int(score.shape[0]), int(score.shape[1])
-    out = torch.empty(_lib.MAX_SENSORS, dtype=torch.int32, device=score.device) if out is None else out
+    W = _lib.MAX_SENSORS
+    out = torch.empty(W, dtype=torch.int32, device=score.device) if out is None else out
     ws = assign_sensors_workspace(m, S, score.device) if workspace is None else workspace
-    ptr = {}
-    for t, name, dtype, n in ((out, "out", torch.int32, _lib.MAX_SENSORS), (fallback, "fallback", torch.int32, _lib.MAX_SENSORS),
-                              (picks, "picks", torch.int64, 2 * _lib.MAX_SENSORS)):
-        ptr[name] = None if t is None else _chk(t, name, dtype)
-        if t is not None and t.numel() != n:
-            raise _lib.SsaHipError("%s must hold %d %s words" % (name, n, dtype))
-    _lib.check(getattr(lib, entry)(score.data_ptr(), m, S, int(column), ptr["fallback"], ptr["out"], ptr["picks"],
-                                   _chk(ws, "workspace", torch.int64), ws.numel() * 8, _stream()), entry)
+    _assign_check(W, fallback, out, picks, ws)
+    _assign_launch(entry, score, (m, S), column, fallback, out, picks, ws, stream)
     return out
+
+
+def _assign_check(n, fallback, out, picks, ws):
+    """the row arguments of assign_sensors (n = MAX_SENSORS words) and assign_sensors_envs (n = E * MAX_SENSORS)"""
+    _chk_n(out, "out", torch.int32, n)
+    _chk_n(fallback, "fallback", torch.int32, n)
+    _chk_n(picks, "picks", torch.int64, 2 * n)
+    _chk(ws, "workspace", torch.int64)
+
+
+def _assign_launch(entry, score, dims, column, fallback, out, picks, ws, stream=None):
+    """the launch half of assign_sensors and assign_sensors_envs, nothing checked: entry(score, *dims, column, fallback, out, picks,
+    workspace, stream) with dims = (m, S) or (m, S, E).  The engine's launches, which have checked the same arguments against their
+    own state, call it as it is: a second pass over them costs a quarter of the call's host time."""
+    _lib.check(getattr(_lib.load(), entry)(score.data_ptr(), *dims, int(column), None if fallback is None else fallback.data_ptr(), out.data_ptr(),
+                                           None if picks is None else picks.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(stream)), entry)
 
 
 def assign_sensors_envs_workspace(n_obj, n_sensor, n_env, device):
@@ -359,7 +384,7 @@ def assign_sensors_envs_workspace(n_obj, n_sensor, n_env, device):
     return torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
 
 
-def assign_sensors_envs(score, column, fallback=None, out=None, picks=None, workspace=None, rule='greedy'):
+def assign_sensors_envs(score, column, fallback=None, out=None, picks=None, workspace=None, rule='greedy', stream=None):
     """the tasking assignment of a sensor network in each of E envs (ssa_assign_sensors_envs_f64): assign_sensors for every env's slab of
     score [E, S, m, 3] -- the rows launch_lookahead_sensors_envs leaves -- in ONE launch.  fallback: int32 [E, MAX_SENSORS] draws per env
     (None: a sensor left without an object stays idle, -1).  Returns the int32 CUDA table [E, MAX_SENSORS] (`out`: a 32-byte aligned
@@ -367,7 +392,6 @@ def assign_sensors_envs(score, column, fallback=None, out=None, picks=None, work
     [E, MAX_SENSORS, 2] to receive the assigned objects and their scores' bit patterns.  workspace: assign_sensors_envs_workspace
     (default: a fresh one).  rule: as assign_sensors ('optimal': ssa_match_sensors_envs_f64).  No host sync."""
     entry = assign_entry(rule, envs=True)
-    lib = _lib.load()
     _chk(score, "score")
     if score.dim() != 4 or score.shape[3] != _lib.LOOK_NSCORE:
         raise _lib.SsaHipError("score must be [E, S, m, %d]" % _lib.LOOK_NSCORE)
@@ -375,13 +399,8 @@ def assign_sensors_envs(score, column, fallback=None, out=None, picks=None, work
     W = _lib.MAX_SENSORS
     out = torch.empty((E, W), dtype=torch.int32, device=score.device) if out is None else out
     ws = assign_sensors_envs_workspace(m, S, E, score.device) if workspace is None else workspace
-    ptr = {}
-    for t, name, dtype, n in ((out, "out", torch.int32, E * W), (fallback, "fallback", torch.int32, E * W), (picks, "picks", torch.int64, 2 * E * W)):
-        ptr[name] = None if t is None else _chk(t, name, dtype)
-        if t is not None and t.numel() != n:
-            raise _lib.SsaHipError("%s must hold %d %s words" % (name, n, dtype))
-    _lib.check(getattr(lib, entry)(score.data_ptr(), m, S, E, int(column), ptr["fallback"], ptr["out"], ptr["picks"],
-                                   _chk(ws, "workspace", torch.int64), ws.numel() * 8, _stream()), entry)
+    _assign_check(E * W, fallback, out, picks, ws)
+    _assign_launch(entry, score, (m, S, E), column, fallback, out, picks, ws, stream)
     return out
 
 
@@ -402,7 +421,7 @@ def plan_sensors_workspace(n_obj, n_sensor, n_step, n_env, device):
     return torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
 
 
-def plan_sensors(score, column, out=None, picks=None, workspace=None):
+def plan_sensors(score, column, out=None, picks=None, workspace=None, stream=None):
     """the horizon-wide optimal tasking plan of a sensor network on the device (ssa_plan_sensors_f64): ONE assignment problem over all
     H' * S (step, sensor) slots of column `column` (_lib.LOOK_*) of a forecast's scores -- [H', S, m, 3] (one env: what
     launch_forecast_sensors leaves) or [H', E, S, m, 3] (what launch_forecast_sensors_envs leaves) -- in ONE launch: the most slots
@@ -421,13 +440,9 @@ def plan_sensors(score, column, out=None, picks=None, workspace=None):
     W = _lib.MAX_SENSORS
     out = torch.empty(tuple(score.shape[:-3]) + (W,), dtype=torch.int32, device=score.device) if out is None else out
     ws = plan_sensors_workspace(m, S, Hp, E, score.device) if workspace is None else workspace
-    ptr = {}
-    for t, name, dtype, n in ((out, "out", torch.int32, Hp * E * W), (picks, "picks", torch.int64, 2 * Hp * E * W)):
-        ptr[name] = None if t is None else _chk(t, name, dtype)
-        if t is not None and t.numel() != n:
-            raise _lib.SsaHipError("%s must hold %d %s words" % (name, n, dtype))
-    _lib.check(lib.ssa_plan_sensors_f64(score.data_ptr(), m, S, Hp, E, int(column), ptr["out"], ptr["picks"],
-                                        _chk(ws, "workspace", torch.int64), ws.numel() * 8, _stream()), "ssa_plan_sensors_f64")
+    _lib.check(lib.ssa_plan_sensors_f64(score.data_ptr(), m, S, Hp, E, int(column), _chk_n(out, "out", torch.int32, Hp * E * W),
+                                        _chk_n(picks, "picks", torch.int64, 2 * Hp * E * W), _chk(ws, "workspace", torch.int64),
+                                        ws.numel() * 8, _stream(stream)), "ssa_plan_sensors_f64")
     return out
 
 
@@ -457,7 +472,7 @@ def dryrun_rows(actions, n_obj, n_sensor=None):
     return ids, words
 
 
-def dryrun_sensors(consts, params, sensors, actions, n_steps, n_obj_caller, out=None):
+def dryrun_sensors(consts, params, sensors, actions, n_steps, n_obj_caller, out=None, stream=None):
     """the dry run of candidate schedules on the device (ssa_dryrun_sensors_envs_f64), stateless: `params` a filled _lib.ssa_step_params
     (its INPUT fields: n_env pseudo-envs of n_obj rows each, obj_ids per env), `sensors` host.make_sensor_params(), `actions` a contiguous
     32-byte aligned CUDA int32 tensor [K, n_env, MAX_SENSORS].  Returns the records [K, n_env, S, DRY_STRIDE] (CUDA float64; `out`: the
@@ -472,7 +487,7 @@ def dryrun_sensors(consts, params, sensors, actions, n_steps, n_obj_caller, out=
         raise _lib.SsaHipError("out must hold %d doubles" % (K * E * S * _lib.DRY_STRIDE))
     d = _lib.ssa_dryrun_sensors_params()
     d.n_steps, d.n_obj_caller, d.actions, d.out = K, int(n_obj_caller), actions.data_ptr(), out.data_ptr()
-    _lib.check(_lib.load().ssa_dryrun_sensors_envs_f64(C.byref(consts), C.byref(params), C.byref(sensors), C.byref(d), _stream()),
+    _lib.check(_lib.load().ssa_dryrun_sensors_envs_f64(C.byref(consts), C.byref(params), C.byref(sensors), C.byref(d), _stream(stream)),
                "ssa_dryrun_sensors_envs_f64")
     return out
 
@@ -515,7 +530,7 @@ def dryrun_gather_rows(ids, n_env, n_cand, n_obj, slot_of=None):
     return rows.reshape(-1)
 
 
-def dryrun_gather(ids, env_time, x_true, x_filter, P_filter, status, n_env, n_cand, n_obj, slot_of=None, out=None):
+def dryrun_gather(ids, env_time, x_true, x_filter, P_filter, status, n_env, n_cand, n_obj, slot_of=None, out=None, stream=None):
     """the gathered block of a vector dry run on the device (ssa_dryrun_gather_f64; the rule: dryrun_gather_rows), stateless: `ids`
     contiguous CUDA int32 [E * B, W] (W % 4 == 0), `env_time` int32 [E], the source block x_true / x_filter [E * n_obj, 6], P_filter
     [E * n_obj, 6, 6] float64 and status int32 [E * n_obj], slot_of int32 [E * n_obj] or None.  Returns (x_true, x_filter, P_filter,
@@ -545,7 +560,7 @@ def dryrun_gather(ids, env_time, x_true, x_filter, P_filter, status, n_env, n_ca
         if _chk(t, "out: " + nm, dt) and t.numel() != n:
             raise _lib.SsaHipError("out: %s must hold %d elements, got %d" % (nm, n, t.numel()))
     g.x_true_out, g.x_out, g.P_out, g.status_out, g.time_out = (t.data_ptr() for t in out)
-    _lib.check(_lib.load().ssa_dryrun_gather_f64(C.byref(g), _stream()), "ssa_dryrun_gather_f64")
+    _lib.check(_lib.load().ssa_dryrun_gather_f64(C.byref(g), _stream(stream)), "ssa_dryrun_gather_f64")
     return tuple(out)
 
 

@@ -29,10 +29,40 @@ class _Snapshot(tuple):
     order = None
 
 
+def _dev_tensor(t, dtype, n=None, at_least=False):
+    """is `t` what device._chk takes -- a contiguous CUDA tensor of `dtype` -- with n elements (at_least: n or more; None: any number)?"""
+    try:
+        device._chk(t, "", dtype)
+    except _lib.SsaHipError:
+        return False
+    return n is None or (t.numel() >= n if at_least else t.numel() == n)
+
+
+def _tensor_args(what, args, at_least=False):
+    """the tensor arguments of launch `what`: every (tensor, dtype, n, name) of `args` that is not None must pass _dev_tensor"""
+    for t, dt, n, nm in args:
+        if t is not None and not _dev_tensor(t, dt, n, at_least):
+            raise _lib.SsaHipError("%s: %s must be a contiguous CUDA %s tensor of %s%d elements" % (what, nm, dt, ">= " if at_least else "", n))
+
+
+def _in_stream(stream):
+    """the context in which torch's own ops go to `stream` (as device._stream takes it; None: no change), for the launches that run some
+    next to the library's kernels: the dry runs' upload and gather"""
+    return torch.cuda.stream(stream if stream is None or isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream))
+
+
+def _dry_target(p, g, ids):
+    """a _lookahead_params block `p` re-targeted at the gathered block of a dry run: g = (x_true, x_filter, P_filter, status, time words)
+    of ids.shape[0] pseudo-envs of ids.shape[1] rows each, `ids` [n, W] the caller's object of every row (-1: padding)"""
+    p.n_env, p.n_obj = ids.shape
+    p.x_true_in, p.x_in, p.P_in, p.status, p.env_time = (t.data_ptr() for t in g)
+    p.obj_ids = ids.data_ptr()
+
+
 class HotPathEngine:
     def __init__(self, consts, n_obj, n_env, trans, z_noise, history, device_name="cuda",
                  zn_stride_env=None, zn_stride_time=None, zn_stride_obj=3):
-        _lib.load()
+        self._lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.SsaHipError("no GPU visible: the ssa-gym hot path runs on MI355X only (no CPU fallback)")
         self.consts = consts
@@ -79,7 +109,6 @@ class HotPathEngine:
         self._p.zn_stride_env, self._p.zn_stride_time = self.zn_stride_env, self.zn_stride_time
         self._p.zn_stride_obj = int(zn_stride_obj)
         self._p.n_time = self.n_time
-        self._lib = _lib.load()
         self._stats_ws = device.stats_workspace(self.E, d)
         self.work = torch.zeros(self._lib.ssa_env_step_work_bytes(self.m, self.E) // 4, dtype=torch.int32, device=d)
         self._p.work, self._p.stat_ws, self._p.launch_mask = self.work.data_ptr(), self._stats_ws.data_ptr(), 0
@@ -120,7 +149,7 @@ class HotPathEngine:
         self._look_se = None                            # output buffers of launch_lookahead_sensors_envs
         self._assign_envs_ws = None                     # (S, workspace) of launch_assign_sensors_envs
         self._fore_e = None                             # output buffers of launch_forecast_sensors_envs
-        self._dry = {}                                  # launch_dryrun_sensors: per (B, K, S, W) its upload, time words, gathered block and records
+        self._dry = {}                                  # launch_dryrun_sensors: per (B, K, S, W) its upload, gathered block and records
         self._dry_envs = {}                             # launch_dryrun_sensors_envs: per (E * B, K, S, W) its upload, gathered block and records
         self._pcache = {}
         self._cref = C.byref(self.consts)
@@ -152,8 +181,7 @@ class HotPathEngine:
             if order.shape != ((self.m,) if self.E == 1 else (self.E, self.m)) or \
                     not np.array_equal(np.sort(order.reshape(self.E, self.m), axis=1), np.broadcast_to(np.arange(self.m), (self.E, self.m))):
                 raise _lib.SsaHipError("set_layout: `order` must be a permutation of 0 .. n_obj - 1 (one per env)")
-            if self.E > 1 and self.m % 4:
-                raise _lib.SsaHipError("a storage layout with several envs needs n_obj % 4 == 0 (whole tiles per env)")
+            self._whole_tiles("a storage layout with")
         self._order = None
         self._p.obj_ids = 0
         self._pcache.clear()
@@ -397,6 +425,30 @@ class HotPathEngine:
             self._fold_pending = (self._shard_cur, stats_ptr, argmax, metrics_ptr if from_metrics else 0)
             self._shard_cur ^= 1
 
+    # ------------------------------------------------------------------ the refusals several launches share
+    def _one_env(self, what):
+        """`what` (a launch of the one-env entries) on an engine of several envs"""
+        if self.E != 1:
+            raise _lib.SsaHipError("%s covers one env (n_env == 1)" % what)
+
+    def _whole_tiles(self, what):
+        """`what` (... several envs) where an env's objects do not fill whole tiles of four: a tile would straddle two envs"""
+        if self.E > 1 and self.m % 4:
+            raise _lib.SsaHipError("%s several envs needs n_obj %% 4 == 0 (whole tiles per env)" % what)
+
+    def _schedule(self, actions, lead, S):
+        """an open-loop schedule as the rollout kernels read it: `actions` must be a contiguous CUDA int32 tensor [K, *lead, S] or
+        [K, *lead, MAX_SENSORS] with K >= 1; returned with its rows padded to MAX_SENSORS words (-1: idle), the ABI's row stride -- one
+        aligned 32-byte read per step.  S None (launch_rollout: a word per env, no sensor axis): [K, *lead], returned as it is."""
+        tails = [()] if S is None else [(S,), (_lib.MAX_SENSORS,)]
+        if not (_dev_tensor(actions, torch.int32) and actions.dim() >= 1 and actions.shape[0] >= 1
+                and tuple(actions.shape[1:]) in [lead + t for t in tails]):
+            raise _lib.SsaHipError("rollout: actions must be a contiguous CUDA int32 tensor %s"
+                                   % " or ".join("[K]" + "".join("[%d]" % v for v in lead + t) for t in tails))
+        if S is not None and actions.shape[-1] != _lib.MAX_SENSORS:
+            actions = torch.nn.functional.pad(actions, (0, _lib.MAX_SENSORS - S), value=-1)
+        return actions
+
     def _check_sensor_noise(self, sensors, envs=False):
         """the extent of z_noise that the sensors of `sensors` index: sensor s reads z_noise[s * sensors.zn_stride_sensor ...]; envs: in
         every env of the engine, env e's tables zn_stride_env behind env e - 1's"""
@@ -413,8 +465,7 @@ class HotPathEngine:
         z_noise[s * sensors.zn_stride_sensor ...]; the per-sensor update records go to `upd_out` (a pointer to [S][UPD_STRIDE] doubles, may
         be 0).  `sensors`: host.make_sensor_params(); its action words and record pointer are set here.  Every other keyword as
         launch_step (fast_stats, fold_inside, argmax_spos, obs_mirror, aer_out, stats_out, ...).  Asynchronous, no host sync."""
-        if self.E != 1:
-            raise _lib.SsaHipError("a sensor network's step covers one env (n_env == 1)")
+        self._one_env("a sensor network's step")
         S = int(sensors.n_sensor)
         if len(actions) != S:
             raise _lib.SsaHipError("launch_step_sensors: %d actions for %d sensors" % (len(actions), S))
@@ -458,8 +509,7 @@ class HotPathEngine:
             a = np.asarray(actions, dtype=np.int64)
             if a.shape != (self.E, S):
                 raise _lib.SsaHipError("launch_step_sensors_envs: actions must be [%d][%d] (envs x sensors), got %s" % (self.E, S, a.shape))
-        if self.E > 1 and self.m % 4:
-            raise _lib.SsaHipError("a sensor network in several envs needs n_obj % 4 == 0 (whole tiles per env)")
+        self._whole_tiles("a sensor network in")
         self._check_sensor_noise(sensors, envs=True)
         v, table, rows_np = self._sensor_envs_block()
         v.upd = int(upd_out)
@@ -521,6 +571,24 @@ class HotPathEngine:
         p.time_offset, p.launch_mask = int(time_offset), 0
         return p
 
+    def _launch_look(self, entry, attr, lead, prior_lead, out, slot_in, time_offset, stream, sensors=None, n_steps=None, env_times=None):
+        """the launch of the lookahead family: entry ssa_X_f64 of method launch_X, its output buffers `attr` (_lookahead_out: score lead
+        + [3], the prediction prior_lead + [6 ...]), the input block of history slot `slot_in`; env_times: the envs' time words by value
+        in that block (SSA_LAUNCH_INLINE_ENVS); sensors: the network's block; n_steps: a forecast -- the outputs travel in an
+        ssa_forecast_params block.  Returns the result dict."""
+        o, res = self._lookahead_out("launch_" + entry[4:-4], attr, lead, prior_lead, out)
+        p = self._lookahead_params(slot_in, time_offset)
+        if env_times is not None:
+            if self.E > _lib.INLINE_ENVS:
+                raise _lib.SsaHipError("env_times: at most %d envs travel in the parameter block" % _lib.INLINE_ENVS)
+            p.inline_time[:self.E] = [int(v) for v in env_times]
+            p.launch_mask = _lib.LAUNCH_INLINE_ENVS
+        if n_steps is not None:
+            o = _lib.ssa_forecast_params(n_steps=n_steps, out=o)
+        blocks = (p, o) if sensors is None else (p, sensors, o)
+        _lib.check(getattr(self._lib, entry)(self._cref, *(C.byref(b) for b in blocks), device._stream(stream)), entry)
+        return res
+
     def launch_lookahead(self, slot_in, time_offset, out=(), stream=None, env_times=None):
         """enqueue the one-step tasking lookahead (include/ssa_hip.h: ssa_lookahead_f64) from history slot `slot_in` for the step whose
         time index is env_time + time_offset (env_times: the envs' time words by value, n_env <= 8; else the engine's env_time0 words, as a
@@ -529,18 +597,7 @@ class HotPathEngine:
         status [E*m] int32, visible [E*m] uint8 and the parts asked for (x_prior [E*m, 6], P_prior / P_post [E*m, 6, 6]) -- the buffers
         are allocated on first use and reused by the next call.  Asynchronous, no host sync."""
         N = self.m * self.E
-        o, res = self._lookahead_out("launch_lookahead", "_look", (N,), (N,), out)
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        p = self._lookahead_params(slot_in, time_offset)
-        if env_times is not None:
-            if self.E > _lib.INLINE_ENVS:
-                raise _lib.SsaHipError("env_times: at most %d envs travel in the parameter block" % _lib.INLINE_ENVS)
-            p.inline_time[:self.E] = [int(v) for v in env_times]
-            p.launch_mask = _lib.LAUNCH_INLINE_ENVS
-        rc = self._lib.ssa_lookahead_f64(self._cref, C.byref(p), C.byref(o), s)
-        if rc:
-            raise _lib.SsaHipError("ssa_lookahead_f64 failed with code %d" % rc)
-        return res
+        return self._launch_look("ssa_lookahead_f64", "_look", (N,), (N,), out, slot_in, time_offset, stream, env_times=env_times)
 
     def launch_lookahead_sensors(self, slot_in, time_offset, sensors, out=(), stream=None):
         """enqueue the lookahead of a sensor network (include/ssa_hip.h: ssa_lookahead_sensors_f64; one env): launch_lookahead for every
@@ -550,15 +607,9 @@ class HotPathEngine:
         visible [S, m] uint8 and the parts of LOOKAHEAD_PARTS asked for in `out` (x_prior [m, 6], P_prior [m, 6, 6] -- the prediction, the
         same for every sensor -- and P_post [S, m, 6, 6]).  The buffers are allocated on first use (again when S changes) and reused by
         the next call.  Asynchronous, no host sync."""
-        if self.E != 1:
-            raise _lib.SsaHipError("the lookahead of a sensor network covers one env (n_env == 1)")
-        o, res = self._lookahead_out("launch_lookahead_sensors", "_look_s", (int(sensors.n_sensor), self.m), (self.m,), out)
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        p = self._lookahead_params(slot_in, time_offset)
-        rc = self._lib.ssa_lookahead_sensors_f64(self._cref, C.byref(p), C.byref(sensors), C.byref(o), s)
-        if rc:
-            raise _lib.SsaHipError("ssa_lookahead_sensors_f64 failed with code %d" % rc)
-        return res
+        self._one_env("the lookahead of a sensor network")
+        return self._launch_look("ssa_lookahead_sensors_f64", "_look_s", (int(sensors.n_sensor), self.m), (self.m,), out, slot_in, time_offset,
+                                 stream, sensors)
 
     def launch_lookahead_sensors_envs(self, slot_in, time_offset, sensors, out=(), stream=None, env_times=None):
         """enqueue the lookahead of a sensor network in EVERY env of the engine, one launch (include/ssa_hip.h:
@@ -568,18 +619,8 @@ class HotPathEngine:
         [E, S, m, 3], status [E, S, m] int32, visible [E, S, m] uint8 and the parts of LOOKAHEAD_PARTS asked for in `out` (x_prior
         [E, m, 6], P_prior [E, m, 6, 6], P_post [E, S, m, 6, 6]).  The buffers are its own, allocated on first use (again when S changes)
         and reused by the next call.  Several envs need n_obj % 4 == 0.  Asynchronous, no host sync."""
-        o, res = self._lookahead_out("launch_lookahead_sensors_envs", "_look_se", (self.E, int(sensors.n_sensor), self.m), (self.E, self.m), out)
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        p = self._lookahead_params(slot_in, time_offset)
-        if env_times is not None:
-            if self.E > _lib.INLINE_ENVS:
-                raise _lib.SsaHipError("env_times: at most %d envs travel in the parameter block" % _lib.INLINE_ENVS)
-            p.inline_time[:self.E] = [int(v) for v in env_times]
-            p.launch_mask = _lib.LAUNCH_INLINE_ENVS
-        rc = self._lib.ssa_lookahead_sensors_envs_f64(self._cref, C.byref(p), C.byref(sensors), C.byref(o), s)
-        if rc:
-            raise _lib.SsaHipError("ssa_lookahead_sensors_envs_f64 failed with code %d" % rc)
-        return res
+        return self._launch_look("ssa_lookahead_sensors_envs_f64", "_look_se", (self.E, int(sensors.n_sensor), self.m), (self.E, self.m), out,
+                                 slot_in, time_offset, stream, sensors, env_times=env_times)
 
     def launch_assign_sensors_envs(self, look, column, fallback=None, picks=None, stream=None, rule='greedy'):
         """enqueue every env's tasking assignment, one launch (include/ssa_hip.h: ssa_assign_sensors_envs_f64), on `look`, the dict
@@ -591,24 +632,17 @@ class HotPathEngine:
         Asynchronous, no host sync."""
         entry = device.assign_entry(rule, envs=True)
         score = look["score"]
-        S = int(score.shape[1]) if isinstance(score, torch.Tensor) and score.dim() == 4 else 0
         W = _lib.MAX_SENSORS
-        for t, dt, n, nm in ((fallback, torch.int32, self.E * W, "fallback"), (picks, torch.int64, 2 * self.E * W, "picks")):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == n):
-                raise _lib.SsaHipError("assign: %s must be a contiguous CUDA %s tensor of %d elements" % (nm, dt, n))
-        if not (isinstance(score, torch.Tensor) and score.is_cuda and score.dtype == torch.float64 and score.is_contiguous()
-                and tuple(score.shape) == (self.E, S, self.m, _lib.LOOK_NSCORE)):
+        _tensor_args("assign", ((fallback, torch.int32, self.E * W, "fallback"), (picks, torch.int64, 2 * self.E * W, "picks")))
+        if not (_dev_tensor(score, f64) and score.dim() == 4 and tuple(score.shape) == (self.E, score.shape[1], self.m, _lib.LOOK_NSCORE)):
             raise _lib.SsaHipError("assign: the contiguous CUDA float64 [%d, S, %d, %d] scores of launch_lookahead_sensors_envs are needed"
                                    % (self.E, self.m, _lib.LOOK_NSCORE))
+        S = int(score.shape[1])
         if self._assign_envs_ws is None or self._assign_envs_ws[0] != S:
             self._assign_envs_ws = (S, device.assign_sensors_envs_workspace(self.m, S, self.E, self.dev))
-        ws = self._assign_envs_ws[1]
         table = self.action_table()
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        rc = getattr(self._lib, entry)(score.data_ptr(), self.m, S, self.E, int(column), fallback.data_ptr() if fallback is not None else 0,
-                                       table.data_ptr(), picks.data_ptr() if picks is not None else 0, ws.data_ptr(), ws.numel() * 8, s)
-        if rc:
-            raise _lib.SsaHipError("%s failed with code %d" % (entry, rc))
+        # (the launch half of device.assign_sensors_envs: what that function checks has been checked above, against this engine's E and m)
+        device._assign_launch(entry, score, (self.m, S, self.E), column, fallback, table, picks, self._assign_envs_ws[1], stream)
         return table
 
     def launch_forecast_sensors(self, slot_in, time_offset, sensors, n_steps, out=(), stream=None):
@@ -619,20 +653,12 @@ class HotPathEngine:
         status [H, S, m] int32, visible [H, S, m] uint8 and the parts of LOOKAHEAD_PARTS asked for in `out` (x_prior [H, m, 6], P_prior
         [H, m, 6, 6], P_post [H, S, m, 6, 6]).  The buffers are allocated on first use (again when H or S changes) and reused by the next
         call; the scores alone are 24 * H * S * m bytes, P_post 288 * H * S * m.  Asynchronous, no host sync."""
-        if self.E != 1:
-            raise _lib.SsaHipError("the forecast of a sensor network covers one env (n_env == 1)")
+        self._one_env("the forecast of a sensor network")
         H = int(n_steps)
         if H < 1:
             raise _lib.SsaHipError("launch_forecast_sensors: n_steps must be >= 1, got %d" % H)
-        f = _lib.ssa_forecast_params()
-        f.n_steps = H
-        f.out, res = self._lookahead_out("launch_forecast_sensors", "_fore", (H, int(sensors.n_sensor), self.m), (H, self.m), out)
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        p = self._lookahead_params(slot_in, time_offset)
-        rc = self._lib.ssa_forecast_sensors_f64(self._cref, C.byref(p), C.byref(sensors), C.byref(f), s)
-        if rc:
-            raise _lib.SsaHipError("ssa_forecast_sensors_f64 failed with code %d" % rc)
-        return res
+        return self._launch_look("ssa_forecast_sensors_f64", "_fore", (H, int(sensors.n_sensor), self.m), (H, self.m), out, slot_in, time_offset,
+                                 stream, sensors, n_steps=H)
 
     def launch_forecast_sensors_envs(self, slot_in, time_offset, sensors, n_steps, out=(), stream=None, env_times=None):
         """enqueue the tasking forecast of a sensor network in EVERY env of the engine, one launch (include/ssa_hip.h:
@@ -647,21 +673,8 @@ class HotPathEngine:
         H = int(n_steps)
         if H < 1:
             raise _lib.SsaHipError("launch_forecast_sensors_envs: n_steps must be >= 1, got %d" % H)
-        f = _lib.ssa_forecast_params()
-        f.n_steps = H
-        f.out, res = self._lookahead_out("launch_forecast_sensors_envs", "_fore_e", (H, self.E, int(sensors.n_sensor), self.m),
-                                         (H, self.E, self.m), out)
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        p = self._lookahead_params(slot_in, time_offset)
-        if env_times is not None:
-            if self.E > _lib.INLINE_ENVS:
-                raise _lib.SsaHipError("env_times: at most %d envs travel in the parameter block" % _lib.INLINE_ENVS)
-            p.inline_time[:self.E] = [int(v) for v in env_times]
-            p.launch_mask = _lib.LAUNCH_INLINE_ENVS
-        rc = self._lib.ssa_forecast_sensors_envs_f64(self._cref, C.byref(p), C.byref(sensors), C.byref(f), s)
-        if rc:
-            raise _lib.SsaHipError("ssa_forecast_sensors_envs_f64 failed with code %d" % rc)
-        return res
+        return self._launch_look("ssa_forecast_sensors_envs_f64", "_fore_e", (H, self.E, int(sensors.n_sensor), self.m), (H, self.E, self.m), out,
+                                 slot_in, time_offset, stream, sensors, n_steps=H, env_times=env_times)
 
     def launch_dryrun_sensors(self, slot_in, time_offset, sensors, actions, stream=None, gather=True):
         """enqueue the dry run of B candidate tasking schedules from history slot `slot_in` (include/ssa_hip.h: ssa_dryrun_sensors_envs_f64;
@@ -673,8 +686,7 @@ class HotPathEngine:
         gather=False (B == 1): the full-catalogue form on the slot itself -- every object predicted K times, the cost of a rollout; the
         tests' yardstick.  Nothing of the engine's state is written.  Returns this engine's record tensor [B, K, S, DRY_STRIDE] (a view
         of a buffer cached per (B, K, S, W), rewritten by the next call).  Asynchronous, no host sync."""
-        if self.E != 1:
-            raise _lib.SsaHipError("the dry run of a sensor network's schedules covers one env (n_env == 1)")
+        self._one_env("the dry run of a sensor network's schedules")
         S = int(sensors.n_sensor)
         if isinstance(actions, torch.Tensor):
             actions = actions.detach().cpu().numpy()
@@ -683,34 +695,33 @@ class HotPathEngine:
         if not gather and B != 1:
             raise _lib.SsaHipError("launch_dryrun_sensors(gather=False) takes one candidate, got %d" % B)
         W = int(ids.shape[1]) if gather else 0
-        key = (B, K, S, W)
-        buf = self._dry.get(key)
-        if buf is None:
-            # one upload per call: the ids and the action words side by side (the words 32-byte aligned: they come first)
-            buf = self._dry[key] = {"dev": torch.empty(K * B * _lib.MAX_SENSORS + B * W, dtype=torch.int32, device=self.dev),
-                                    "out": torch.empty((K, B, S, _lib.DRY_STRIDE), dtype=f64, device=self.dev),
-                                    "time": torch.empty(max(B, 1), dtype=torch.int32, device=self.dev)}
-        nw = K * B * _lib.MAX_SENSORS
-        up = np.concatenate((words.reshape(-1), ids.reshape(-1))) if gather else words.reshape(-1)
-        st = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
-        with torch.cuda.stream(st):
-            buf["dev"].copy_(torch.from_numpy(up))
+        with _in_stream(stream):
+            buf, (dev_words, dev_ids) = self._dry_buffers(self._dry, B, K, S, W, (words, ids[:, :W]))
             p = self._lookahead_params(slot_in, time_offset)
             if gather:
-                dev_ids = buf["dev"][nw:].view(B, W)
+                dev_ids = dev_ids.view(B, W)
                 # a padding row takes the state of the candidate's first object (object 0 for an all-idle candidate): a healthy row to predict
                 rows = torch.where(dev_ids >= 0, dev_ids, dev_ids[:, :1].clamp(min=0).expand(B, W)).reshape(-1).to(torch.int64)
                 if self._order is not None:
                     rows = self._slot_of.index_select(0, rows)
                 sl = int(slot_in) % self.H
-                g = buf["state"] = (self.x_true[sl].index_select(0, rows), self.x_filter[sl].index_select(0, rows),
-                                    self.P_filter[sl].index_select(0, rows), self.status.index_select(0, rows))
-                buf["time"].copy_(self.env_time0[:1].expand(B))
-                p.n_obj, p.n_env = W, B
-                p.x_true_in, p.x_in, p.P_in, p.status = (t.data_ptr() for t in g)
-                p.env_time, p.obj_ids = buf["time"].data_ptr(), dev_ids.data_ptr()
-            device.dryrun_sensors(self.consts, p, sensors, buf["dev"][:nw].view(K, B, _lib.MAX_SENSORS), K, self.m, out=buf["out"])
+                buf["state"] = (self.x_true[sl].index_select(0, rows), self.x_filter[sl].index_select(0, rows),
+                                self.P_filter[sl].index_select(0, rows), self.status.index_select(0, rows), self.env_time0[:1].repeat(B))
+                _dry_target(p, buf["state"], dev_ids)
+            device.dryrun_sensors(self.consts, p, sensors, dev_words.view(K, B, _lib.MAX_SENSORS), K, self.m, out=buf["out"], stream=stream)
         return buf["out"].permute(1, 0, 2, 3)
+
+    def _dry_buffers(self, cache, n, K, S, W, parts):
+        """the buffers of a dry run of n pseudo-envs, cached in `cache` per (n, K, S, W) -- "dev": the call's ONE upload, "out": the records
+        [K, n, S, DRY_STRIDE] -- and the upload itself, in torch's current stream: the int32 arrays `parts` side by side (the action
+        words first: the kernel reads them 32 bytes at a time).  Returns (the cache entry, the device views of the parts)."""
+        up = np.concatenate([a.reshape(-1) for a in parts])
+        buf = cache.get((n, K, S, W))
+        if buf is None:
+            buf = cache[(n, K, S, W)] = {"dev": torch.empty(up.size, dtype=torch.int32, device=self.dev),
+                                         "out": torch.empty((K, n, S, _lib.DRY_STRIDE), dtype=f64, device=self.dev)}
+        buf["dev"].copy_(torch.from_numpy(up))
+        return buf, buf["dev"].split([a.size for a in parts])
 
     def launch_dryrun_sensors_envs(self, slot_in, time_offset, sensors, actions, stream=None, env_times=None):
         """enqueue the dry run of B candidate tasking schedules in EVERY env of the engine (any n_env, 1 included):
@@ -734,33 +745,18 @@ class HotPathEngine:
         EB, K, W = E * B, int(words.shape[0]), int(ids.shape[1])
         if env_times is not None and len(env_times) != E:
             raise ValueError("dry run: env_times must hold %d time words, got %d" % (E, len(env_times)))
-        key = (EB, K, S, W)
-        buf = self._dry_envs.get(key)
-        if buf is None:
-            R = EB * W
-            d = self.dev
-            buf = self._dry_envs[key] = {
-                "dev": torch.empty(K * EB * _lib.MAX_SENSORS + R + E, dtype=torch.int32, device=d),    # (the words first: 32-byte aligned)
-                "state": (torch.empty((R, 6), dtype=f64, device=d), torch.empty((R, 6), dtype=f64, device=d),
-                          torch.empty((R, 6, 6), dtype=f64, device=d), torch.empty(R, dtype=torch.int32, device=d),
-                          torch.empty(EB, dtype=torch.int32, device=d)),
-                "out": torch.empty((K, EB, S, _lib.DRY_STRIDE), dtype=f64, device=d)}
-        nw, ni = K * EB * _lib.MAX_SENSORS, EB * W
         times = np.zeros(E, dtype=np.int32) if env_times is None else np.asarray([int(v) for v in env_times], dtype=np.int32)
-        up = np.concatenate((words.reshape(-1), ids.reshape(-1), times))
-        st = torch.cuda.current_stream() if stream is None else stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
         sl = int(slot_in) % self.H
-        with torch.cuda.stream(st):
-            buf["dev"].copy_(torch.from_numpy(up))
-            dev_ids = buf["dev"][nw:nw + ni].view(EB, W)
-            g = device.dryrun_gather(dev_ids, buf["dev"][nw + ni:] if env_times is not None else self.env_time0,
-                                     self.x_true[sl], self.x_filter[sl], self.P_filter[sl], self.status, E, B, self.m,
-                                     slot_of=self._slot_of32 if self._order is not None else None, out=buf["state"])
+        with _in_stream(stream):
+            buf, (dev_words, dev_ids, dev_times) = self._dry_buffers(self._dry_envs, EB, K, S, W, (words, ids, times))
+            dev_ids = dev_ids.view(EB, W)
+            # (the gathered block is the entry's own: allocated by the first call's gather, written again by every later one)
+            buf["state"] = device.dryrun_gather(dev_ids, dev_times if env_times is not None else self.env_time0,
+                                                self.x_true[sl], self.x_filter[sl], self.P_filter[sl], self.status, E, B, self.m,
+                                                slot_of=self._slot_of32 if self._order is not None else None, out=buf.get("state"), stream=stream)
             p = self._lookahead_params(slot_in, time_offset)
-            p.n_obj, p.n_env = W, EB
-            p.x_true_in, p.x_in, p.P_in, p.status = (t.data_ptr() for t in g[:4])
-            p.env_time, p.obj_ids = g[4].data_ptr(), dev_ids.data_ptr()
-            device.dryrun_sensors(self.consts, p, sensors, buf["dev"][:nw].view(K, EB, _lib.MAX_SENSORS), K, self.m, out=buf["out"])
+            _dry_target(p, buf["state"], dev_ids)
+            device.dryrun_sensors(self.consts, p, sensors, dev_words.view(K, EB, _lib.MAX_SENSORS), K, self.m, out=buf["out"], stream=stream)
         return buf["out"].view(K, E, B, S, _lib.DRY_STRIDE).permute(1, 2, 0, 3, 4)
 
     def launch_assign_sensors(self, look, column, action_row, fallback_row=None, picks=None, stream=None, rule='greedy'):
@@ -773,23 +769,16 @@ class HotPathEngine:
         instead (ssa_match_sensors_f64: most sensors tasked, then the largest sum), same row, same workspace.  Asynchronous, no host sync."""
         entry = device.assign_entry(rule)
         score = look["score"]
-        S = int(score.shape[0]) if isinstance(score, torch.Tensor) and score.dim() == 3 else 0
-        for t, dt, n, nm in ((action_row, torch.int32, _lib.MAX_SENSORS, "action_row"), (fallback_row, torch.int32, _lib.MAX_SENSORS, "fallback_row"),
-                             (picks, torch.int64, 2 * _lib.MAX_SENSORS, "picks")):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == n):
-                raise _lib.SsaHipError("assign: %s must be a contiguous CUDA %s tensor of %d elements" % (nm, dt, n))
-        if action_row is None or not (isinstance(score, torch.Tensor) and score.is_cuda and score.dtype == torch.float64
-                                      and score.is_contiguous() and tuple(score.shape) == (S, self.m, _lib.LOOK_NSCORE)):
+        W = _lib.MAX_SENSORS
+        _tensor_args("assign", ((action_row, torch.int32, W, "action_row"), (fallback_row, torch.int32, W, "fallback_row"),
+                                (picks, torch.int64, 2 * W, "picks")))
+        if action_row is None or not (_dev_tensor(score, f64) and score.dim() == 3 and tuple(score.shape) == (score.shape[0], self.m, _lib.LOOK_NSCORE)):
             raise _lib.SsaHipError("assign: an action row and the contiguous CUDA float64 [S, %d, %d] scores of launch_lookahead_sensors "
                                    "are needed" % (self.m, _lib.LOOK_NSCORE))
+        S = int(score.shape[0])
         if self._assign_ws is None or self._assign_ws[0] != S:
             self._assign_ws = (S, device.assign_sensors_workspace(self.m, S, self.dev))
-        ws = self._assign_ws[1]
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        rc = getattr(self._lib, entry)(score.data_ptr(), self.m, S, int(column), fallback_row.data_ptr() if fallback_row is not None else 0,
-                                       action_row.data_ptr(), picks.data_ptr() if picks is not None else 0, ws.data_ptr(), ws.numel() * 8, s)
-        if rc:
-            raise _lib.SsaHipError("%s failed with code %d" % (entry, rc))
+        device._assign_launch(entry, score, (self.m, S), column, fallback_row, action_row, picks, self._assign_ws[1], stream)
 
     def launch_plan_sensors(self, forecast, column, picks=None, stream=None):
         """enqueue the horizon-wide optimal tasking plan (include/ssa_hip.h: ssa_plan_sensors_f64) on `forecast`, the dict
@@ -801,27 +790,18 @@ class HotPathEngine:
         buffers are (allocated on first use, again when H' or S changes).  H' * S > MAX_PLAN_SLOTS is a ValueError.  Asynchronous, no
         host sync."""
         score = forecast["score"]
-        ok = isinstance(score, torch.Tensor) and score.is_cuda and score.dtype == torch.float64 and score.is_contiguous()
-        if not (ok and score.dim() in (4, 5) and score.shape[-1] == _lib.LOOK_NSCORE and score.shape[-2] == self.m
+        if not (_dev_tensor(score, f64) and score.dim() in (4, 5) and score.shape[-1] == _lib.LOOK_NSCORE and score.shape[-2] == self.m
                 and (score.dim() == 4 or score.shape[1] == self.E) and (score.dim() == 5 or self.E == 1)):
             raise _lib.SsaHipError("plan: the contiguous CUDA float64 [H', S, %d, %d] (or [H', %d, S, %d, %d]) scores of a forecast are "
                                    "needed" % (self.m, _lib.LOOK_NSCORE, self.E, self.m, _lib.LOOK_NSCORE))
         Hp, S = int(score.shape[0]), int(score.shape[-3])
         device.check_plan_slots(Hp, S)
         lead = tuple(score.shape[:-3])
-        if picks is not None and not (isinstance(picks, torch.Tensor) and picks.is_cuda and picks.dtype == torch.int64 and picks.is_contiguous()
-                                      and picks.numel() == 2 * Hp * self.E * _lib.MAX_SENSORS):
-            raise _lib.SsaHipError("plan: picks must be a contiguous CUDA int64 tensor of %d elements" % (2 * Hp * self.E * _lib.MAX_SENSORS))
+        _tensor_args("plan", ((picks, torch.int64, 2 * Hp * self.E * _lib.MAX_SENSORS, "picks"),))
         if self._plan is None or self._plan[0] != (lead, S):
             self._plan = ((lead, S), torch.full(lead + (_lib.MAX_SENSORS,), -1, dtype=torch.int32, device=self.dev),
                           device.plan_sensors_workspace(self.m, S, Hp, self.E, self.dev))
-        table, ws = self._plan[1], self._plan[2]
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        rc = self._lib.ssa_plan_sensors_f64(score.data_ptr(), self.m, S, Hp, self.E, int(column), table.data_ptr(),
-                                            picks.data_ptr() if picks is not None else 0, ws.data_ptr(), ws.numel() * 8, s)
-        if rc:
-            raise _lib.SsaHipError("ssa_plan_sensors_f64 failed with code %d" % rc)
-        return table
+        return device.plan_sensors(score, column, out=self._plan[1], picks=picks, workspace=self._plan[2], stream=stream)
 
     def assign_row(self):
         """this engine's own int32 [MAX_SENSORS] action row, for a caller of launch_assign_sensors that reads one assignment back
@@ -834,15 +814,11 @@ class HotPathEngine:
         """K = actions.shape[0] consecutive steps in one launch (include/ssa_hip.h: ssa_env_rollout_f64): step k reads
         history slot (slot_in + k) % H, writes (slot_in + k + 1) % H and has time index time_offset + k.  `actions`
         is a device int32 tensor [K][E] (open-loop schedule).  Statistics: the last min(K, H) steps' slots."""
-        if not (isinstance(actions, torch.Tensor) and actions.is_cuda and actions.dtype == torch.int32 and actions.is_contiguous()
-                and actions.dim() == 2 and actions.shape[1] == self.E and actions.shape[0] >= 1):
-            raise _lib.SsaHipError("rollout: actions must be a contiguous CUDA int32 tensor [K][n_env]")
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        actions = self._schedule(actions, (self.E,), None)
+        s = device._stream(stream)
         r = self._rollout_params(slot_in, time_offset, int(actions.shape[0]), argmax_spos, s)
         r.upd_ring, r.actions = self._bu, actions.data_ptr()
-        rc = self._lib.ssa_env_rollout_f64(self._cref, self._pref, C.byref(r), s)
-        if rc:
-            raise _lib.SsaHipError("ssa_env_rollout_f64 failed with code %d" % rc)
+        _lib.check(self._lib.ssa_env_rollout_f64(self._cref, self._pref, C.byref(r), s), "ssa_env_rollout_f64")
 
     def _rollout_params(self, slot_in, time_offset, K, argmax_spos, s):
         """what launch_rollout, launch_rollout_sensors and launch_rollout_sensors_envs share: pending statistics folded, the ssa_rollout_params block of K steps from
@@ -880,26 +856,20 @@ class HotPathEngine:
         or [K, MAX_SENSORS] (row k = the sensors' objects at step k; < 0: idle; two sensors on one object: the lower one updates it).
         The per-sensor update records of the last min(K, H) steps are in self.upd_sensors [H, S, UPD_STRIDE] (allocated on first use,
         again when S changes), slot (slot_in + k + 1) % H for step k.  Asynchronous, no host sync."""
-        if self.E != 1:
-            raise _lib.SsaHipError("a sensor network's rollout covers one env (n_env == 1)")
+        self._one_env("a sensor network's rollout")
         S = int(sensors.n_sensor)
-        if not (isinstance(actions, torch.Tensor) and actions.is_cuda and actions.dtype == torch.int32 and actions.is_contiguous()
-                and actions.dim() == 2 and actions.shape[1] in (S, _lib.MAX_SENSORS) and actions.shape[0] >= 1):
-            raise _lib.SsaHipError("rollout: actions must be a contiguous CUDA int32 tensor [K][%d] or [K][%d]" % (S, _lib.MAX_SENSORS))
+        actions = self._schedule(actions, (), S)
         self._check_sensor_noise(sensors)
-        if actions.shape[1] != _lib.MAX_SENSORS:      # (the ABI's row stride: one aligned 32-byte read per step)
-            actions = torch.nn.functional.pad(actions, (0, _lib.MAX_SENSORS - S), value=-1)
         self._roll_sched = actions      # (kept until the next launch: the kernel reads it whatever stream it runs in)
         upd = self.upd_sensors
         if upd is None or upd.shape[1] != S:
             upd = self.upd_sensors = torch.zeros((self.H, S, _lib.UPD_STRIDE), dtype=f64, device=self.dev)
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        s = device._stream(stream)
         r = self._rollout_params(slot_in, time_offset, int(actions.shape[0]), argmax_spos, s)
         rs = _lib.ssa_rollout_sensors_params()
         rs.actions, rs.upd_ring = actions.data_ptr(), upd.data_ptr()
-        rc = self._lib.ssa_env_rollout_sensors_f64(self._cref, self._pref, C.byref(r), C.byref(sensors), C.byref(rs), s)
-        if rc:
-            raise _lib.SsaHipError("ssa_env_rollout_sensors_f64 failed with code %d" % rc)
+        _lib.check(self._lib.ssa_env_rollout_sensors_f64(self._cref, self._pref, C.byref(r), C.byref(sensors), C.byref(rs), s),
+                   "ssa_env_rollout_sensors_f64")
 
     def launch_rollout_sensors_envs(self, slot_in, time_offset, sensors, actions, stream=None, argmax_spos=False, records=False):
         """launch_rollout_sensors in EVERY env of the engine (include/ssa_hip.h: ssa_env_rollout_sensors_envs_f64): the K = actions.shape[0]
@@ -912,28 +882,21 @@ class HotPathEngine:
         update records whatever H is --, reused (and rewritten) by the next call.  Several envs need n_obj % 4 == 0.  Asynchronous, no
         host sync."""
         S = int(sensors.n_sensor)
-        if not (isinstance(actions, torch.Tensor) and actions.is_cuda and actions.dtype == torch.int32 and actions.is_contiguous()
-                and actions.dim() == 3 and actions.shape[1] == self.E and actions.shape[2] in (S, _lib.MAX_SENSORS) and actions.shape[0] >= 1):
-            raise _lib.SsaHipError("rollout: actions must be a contiguous CUDA int32 tensor [K][%d][%d] or [K][%d][%d]"
-                                   % (self.E, S, self.E, _lib.MAX_SENSORS))
-        if self.E > 1 and self.m % 4:
-            raise _lib.SsaHipError("a sensor network in several envs needs n_obj % 4 == 0 (whole tiles per env)")
+        actions = self._schedule(actions, (self.E,), S)
+        self._whole_tiles("a sensor network in")
         self._check_sensor_noise(sensors, envs=True)
-        if actions.shape[2] != _lib.MAX_SENSORS:      # (the ABI's row stride: one aligned 32-byte read per tile and step)
-            actions = torch.nn.functional.pad(actions, (0, _lib.MAX_SENSORS - S), value=-1)
         self._roll_sched = actions      # (kept until the next launch: the kernel reads it whatever stream it runs in)
         K = int(actions.shape[0])
         out = self._roll_envs_out
         if out is None or out[0].shape[0] < K or out[1].shape[2] != S or (records and out[1].shape[0] < K):
             out = self._roll_envs_out = (torch.zeros((K, self.E, _lib.STAT_STRIDE), dtype=f64, device=self.dev),
                                          torch.zeros((K if records else 0, self.E, S, _lib.UPD_STRIDE), dtype=f64, device=self.dev))
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        s = device._stream(stream)
         r = self._rollout_params(slot_in, time_offset, K, argmax_spos, s)
         re = _lib.ssa_rollout_sensors_envs_params()
         re.actions, re.stats_out, re.upd_out = actions.data_ptr(), out[0].data_ptr(), out[1].data_ptr() if records else 0
-        rc = self._lib.ssa_env_rollout_sensors_envs_f64(self._cref, self._pref, C.byref(r), C.byref(sensors), C.byref(re), s)
-        if rc:
-            raise _lib.SsaHipError("ssa_env_rollout_sensors_envs_f64 failed with code %d" % rc)
+        _lib.check(self._lib.ssa_env_rollout_sensors_envs_f64(self._cref, self._pref, C.byref(r), C.byref(sensors), C.byref(re), s),
+                   "ssa_env_rollout_sensors_envs_f64")
         return out[0][:K], (out[1][:K] if records else None)
 
     def launch_closed_loop(self, slot_in, time_offset, kind, actions, stats_out, upd_out=None, fallback=None, picks=None, stream=None,
@@ -953,13 +916,9 @@ class HotPathEngine:
         K = int(actions.numel()) - 1
         if K < 1:
             raise _lib.SsaHipError("closed loop: actions must hold K + 1 >= 2 words")
-        for t, dt, n, nm in ((actions, torch.int32, K + 1, "actions"), (stats_out, f64, K * _lib.STAT_STRIDE, "stats_out"),
-                             (upd_out, f64, K * _lib.UPD_STRIDE, "upd_out"), (fallback, torch.int32, K + 1, "fallback"),
-                             (picks, torch.int64, 2 * (K + 1), "picks")):
-            if t is None:
-                continue
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= n):
-                raise _lib.SsaHipError("closed loop: %s must be a contiguous CUDA %s tensor of >= %d elements" % (nm, dt, n))
+        _tensor_args("closed loop", ((actions, torch.int32, K + 1, "actions"), (stats_out, f64, K * _lib.STAT_STRIDE, "stats_out"),
+                                     (upd_out, f64, K * _lib.UPD_STRIDE, "upd_out"), (fallback, torch.int32, K + 1, "fallback"),
+                                     (picks, torch.int64, 2 * (K + 1), "picks")), at_least=True)
         if self._loop_ws is None:
             nb = int(self._lib.ssa_closed_loop_workspace_bytes(self.m, self.E))
             if nb <= 0:
@@ -967,7 +926,7 @@ class HotPathEngine:
             self._loop_ws = torch.zeros(nb // 8, dtype=torch.int64, device=self.dev)
             self._loop_err_host = torch.zeros(1, dtype=torch.int32).pin_memory()
             self.loop_error = self._loop_err_host.numpy()
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        s = device._stream(stream)
         self.flush_stats(s)
         self.loop_error[0] = 0      # (a launch that gave up must not poison the next one: nothing is in flight here, run_agent synchronises)
         r = _lib.ssa_closed_loop_params()
@@ -987,8 +946,7 @@ class HotPathEngine:
         rc = self._lib.ssa_env_closed_loop_f64(self._cref, self._pref, C.byref(r), s)
         if rc == _lib.E_UNSUPPORTED:
             return False
-        if rc:
-            raise _lib.SsaHipError("ssa_env_closed_loop_f64 failed with code %d" % rc)
+        _lib.check(rc, "ssa_env_closed_loop_f64")
         return True
 
     def launch_agent_select(self, slot_cur, time_offset, kind, action_ptr, fallback_ptr=0, pick_ptr=0, stream=None, have_prev=True):
@@ -998,7 +956,6 @@ class HotPathEngine:
         if self._agent_ws is None:
             nb = self._lib.ssa_agent_select_workspace_bytes(self.m, self.E)
             self._agent_ws = torch.empty(max(int(nb), 16), dtype=torch.uint8, device=self.dev)
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
         sc = int(slot_cur) % self.H
         sp = (sc + self.H - 1) % self.H
         # (with a storage layout the candidates are named as the caller numbers them: ssa_agent_select_ids_f64)
@@ -1006,16 +963,13 @@ class HotPathEngine:
                                                 self._bP + sc * self._sP, (self._bP + sp * self._sP) if have_prev else 0, self.trans.data_ptr(),
                                                 self.env_time0.data_ptr(), int(time_offset), self.n_time, fallback_ptr,
                                                 self._agent_ws.data_ptr(), action_ptr, pick_ptr, self.m, self.E,
-                                                self._obj_ids.data_ptr() if self._order is not None else 0, s)
-        if rc:
-            raise _lib.SsaHipError("ssa_agent_select_f64 failed with code %d" % rc)
+                                                self._obj_ids.data_ptr() if self._order is not None else 0, device._stream(stream))
+        _lib.check(rc, "ssa_agent_select_ids_f64")
 
     def profile_ms(self, slot):
         """duration [ms] of the dominant kernel of the step launched with profile_slot=slot (waits for it)."""
         ms = C.c_float(0.0)
-        rc = self._lib.ssa_env_step_profile_ms(int(slot), C.byref(ms))
-        if rc:
-            raise _lib.SsaHipError("ssa_env_step_profile_ms failed with code %d" % rc)
+        _lib.check(self._lib.ssa_env_step_profile_ms(int(slot), C.byref(ms)), "ssa_env_step_profile_ms")
         return float(ms.value)
 
     def flush_stats(self, stream=None):
@@ -1032,7 +986,8 @@ class HotPathEngine:
             rc = self._lib.ssa_stats_fold_f64(self._shard_sets[k].data_ptr(), dst, self.E, s)
         self._fold_pending = None
         if rc:
-            raise _lib.SsaHipError("ssa_stats_fold_f64 failed with code %d" % rc)
+            raise _lib.SsaHipError("%s failed with code %d" % ("ssa_stats_fold_metrics_f64" if metrics else "ssa_stats_fold_spos_f64" if argmax
+                                                               else "ssa_stats_fold_f64", rc))
 
     def set_actions(self, actions):
         a = torch.as_tensor(np.asarray(actions, dtype=np.int32).reshape(self.E))
