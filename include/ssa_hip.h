@@ -550,11 +550,25 @@ int ssa_lookahead_f64(const ssa_consts *c_host, const ssa_step_params *p_host, c
  *   SSA_UPD_ACTION = -1 (OBS_TAKEN = VISIBLE = 0 unless the update was attempted).
  *   Measurement noise of sensor s: z_noise + s*zn_stride_sensor + i*zn_stride_time + action[s]*zn_stride_obj (ssa_step_params strides).
  * n_env == 1 only (SSA_E_UNSUPPORTED otherwise; a network in each of several envs: ssa_env_step_sensors_envs_f64 below);
- * 1 <= n_sensor <= SSA_MAX_SENSORS. */
+ * 1 <= n_sensor <= SSA_MAX_SENSORS.
+ * Measurement kinds: bit s of `angles_only` set -- sensor s measures azimuth and elevation only (a telescope); clear -- azimuth,
+ * elevation and range (the default).  For an angles-only sensor the update is the UKF update with dim_z = 2: hx, the predicted
+ * measurement and the residual are the first two components of the az-el-range ones (the azimuth wrap unchanged), R is R[s][0..1][0..1],
+ * K = Pxz inv(S) with a 2 x 2 S.  Visibility, failure handling (a singular 2 x 2 S: SSA_ST_UPDATE_LINALG; a NaN in x+:
+ * SSA_ST_UPDATE_NAN), update_interval, SSA_FLAG_RESAMPLE, SSA_FLAG_REFERENCE_COV and every propagator hold unchanged.  For such a sensor
+ * every entry point that takes this block
+ *   reads R[s][0..1][0..1] only (the third row and column of R[s] may hold anything, NaN included), and
+ *   reads the first two words of each noise triple only (the tables keep three words per (sensor, step, object), so that changing a
+ *   sensor's kind changes no other sensor's draws).
+ * Its update record holds SSA_UPD_Y[2] = 0 and SSA_UPD_S in block form: the 2 x 2 innovation covariance in [0..1][0..1], exact zeros in
+ * the rest of row and column 2 and exactly 1.0 at [2][2] -- ssa_nis_f64 on the record then returns the 2-dof NIS as it stands.
+ * SSA_UPD_Z_TRUE[2] and the third column of SSA_UPD_SIGMAS_H keep the range the geometry gives: recorded, not used by the update.
+ * Refused before any launch (SSA_E_INVALID), behind every other refusal of an entry: a bit set at or above n_sensor; any bit set while
+ * ssa_consts.obs_type is not SSA_OBS_AER. */
 #define SSA_MAX_SENSORS 8
 typedef struct ssa_sensor_params {
     int32_t n_sensor;                      /* S */
-    int32_t reserved;
+    int32_t angles_only;                   /* bit s: sensor s measures az and el only (0: every sensor measures az, el and range) */
     int32_t action[SSA_MAX_SENSORS];       /* object sensor s observes, BY VALUE (< 0: idle) */
     double enu[SSA_MAX_SENSORS][9];        /* ecef2aer's trans_uvw_ecef matrix of site s (as ssa_consts.enu) */
     double obs_itrs[SSA_MAX_SENSORS][3];   /* lla2ecef(site s) */
@@ -566,7 +580,7 @@ typedef struct ssa_sensor_params {
 int ssa_env_step_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_sensor_params *s_host, void *stream);
 
 /* ---------------------------------------------------------------- a sensor network in each of E envs, one launch
- * ssa_env_step_sensors_f64 for every env of a vector launch: the sites (`sites`: n_sensor, enu, obs_itrs, obs_limit, R,
+ * ssa_env_step_sensors_f64 for every env of a vector launch: the sites (`sites`: n_sensor, angles_only, enu, obs_itrs, obs_limit, R,
  * zn_stride_sensor -- its `action` and `upd` are not read) are shared by all envs; each env tasks them on its own objects.  Per env the
  * semantics are exactly ssa_env_step_sensors_f64's: an action < 0 or >= n_obj is an idle sensor; two sensors of ONE env on one object --
  * the lowest-numbered one updates it; the same object index in two envs is two objects, both updated; a failed filter or a step the
@@ -597,8 +611,8 @@ int ssa_env_step_sensors_envs_f64(const ssa_consts *c, const ssa_step_params *p,
  * once; the hypothetical update runs once per sensor.  Output rows, with m = n_obj and the caller's object numbering:
  *   score [S*m][SSA_LOOK_NSCORE], status [S*m], visible [S*m], P_post [S*m][36] (or NULL): row s * m + j;
  *   x_prior [m][6], P_prior [m][36] (or NULL): row j -- the prediction does not depend on the site.
- * Reads the same ssa_step_params fields as ssa_lookahead_f64 and, of ssa_sensor_params, n_sensor, enu, obs_itrs, obs_limit and R
- * (its action, zn_stride_sensor and upd are not read).  Nothing is written but `out`.
+ * Reads the same ssa_step_params fields as ssa_lookahead_f64 and, of ssa_sensor_params, n_sensor, angles_only, enu, obs_itrs, obs_limit
+ * and R (its action, zn_stride_sensor and upd are not read).  Nothing is written but `out`.
  * Refused before any launch: NULL blocks or required outputs, n_sensor outside 1 .. SSA_MAX_SENSORS, a NaN elevation mask
  * (SSA_E_INVALID); n_env != 1 (SSA_E_UNSUPPORTED); and every refusal of ssa_lookahead_f64. */
 int ssa_lookahead_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_sensor_params *s_host,

@@ -67,7 +67,7 @@ class ssa_lookahead_out(C.Structure):
 
 class ssa_sensor_params(C.Structure):
     _fields_ = [
-        ("n_sensor", C.c_int32), ("reserved", C.c_int32), ("action", C.c_int32 * 8),
+        ("n_sensor", C.c_int32), ("angles_only", C.c_int32), ("action", C.c_int32 * 8),
         ("enu", (C.c_double * 9) * 8), ("obs_itrs", (C.c_double * 3) * 8), ("obs_limit", C.c_double * 8), ("R", (C.c_double * 9) * 8),
         ("zn_stride_sensor", C.c_int64), ("upd", c_dp),
     ]

@@ -2031,6 +2031,14 @@ look_pass:
                         for (int c = 0; c < 3; ++c) rz[c] = zin[c] - zp[c];
                     }
                 }
+                // an angles-only sensor (ssa_sensor_params.angles_only; the row's sensor, or the pass's): no range residual -- an
+                // assignment, so nothing of the range noise word survives.  With S in block form below, column 2 of Pxz and of K are
+                // exact zeros and x+ / P+ are the update of dim_z = 2
+                if constexpr (SENS) {
+                    if ((SP->angles_only >> sid) & 1) rz[2] = 0.0;
+                } else if constexpr (LSENS) {
+                    if ((SP->angles_only >> look_s) & 1) rz[2] = 0.0;
+                }
                 upd_go = true;
                 if (l <= 12) {
 #pragma unroll
@@ -2052,6 +2060,9 @@ look_pass:
             const double* Rm = C.R;   // (ActSensors: R of row gu's sensor, a wave-uniform index)
             if constexpr (SENS) Rm = SP->R[__builtin_amdgcn_readlane(sid, gu * 16)];
             if constexpr (LSENS) Rm = SP->R[look_s];
+            // (row gu's sensor measures az and el only: wave-uniform, the turn's own)
+            [[maybe_unused]] const bool ang = SENS    ? ((SP->angles_only >> __builtin_amdgcn_readlane(sid, gu * 16)) & 1) != 0
+                                              : LSENS ? ((SP->angles_only >> look_s) & 1) != 0 : false;
             if (g == gu && l == 13) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) W[54 + c] = y_row[c];
@@ -2084,6 +2095,10 @@ look_pass:
                     const int a = ri - 6;
                     W[a * 3 + ij] = acc + Rm[a * 3 + ij];
                     W[ij * 3 + a] = acc + Rm[ij * 3 + a];
+                    if constexpr (SENS || LSENS) {
+                        // (an angles-only sensor: R's 2 x 2 block alone; row and column 2 of S are exact 0 and 1, whatever R holds there)
+                        if (ang && ij == 2) W[a * 3 + 2] = W[6 + a] = (a == 2) ? 1.0 : 0.0;
+                    }
                 }
             }
             wave_lds_sync();
@@ -5033,6 +5048,13 @@ static bool noise_stride_ok(const ssa_sensor_params* sp)
 {
     return sp->zn_stride_sensor >= 0 && (sp->n_sensor <= 1 || sp->zn_stride_sensor != 0);
 }
+// ... and of the sensors' measurement kinds (ssa_sensor_params.angles_only): no bit at or above n_sensor, and none at all unless the
+// observation is az-el-range.  Every entry applies it behind all its other rules, so that no older refusal changes its rank
+static bool kinds_ok(const ssa_consts* c, const ssa_sensor_params* sp)
+{
+    const uint32_t bits = (uint32_t)sp->angles_only;
+    return bits == 0 || ((bits >> sp->n_sensor) == 0 && c->obs_type == SSA_OBS_AER);
+}
 // a network's sites as the kernels take them that read neither its action words nor its record destination
 static ssa_sensor_params idle_sites(const ssa_sensor_params* sp)
 {
@@ -5099,6 +5121,7 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     TileGrid g;
     const int rc = step_args(c, p, sens != nullptr, g);
     if (rc != SSA_OK) return rc;
+    if (sens && !kinds_ok(c, sens)) return SSA_E_INVALID;
     StepK k;
     k.c = *c;
     k.p = *p;
@@ -5276,6 +5299,7 @@ int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, con
     LookSensK k;
     const int rc = lookahead_sensors_args(c, p, sp, o, false, k.k, k.s);
     if (rc != SSA_OK) return rc;
+    if (!kinds_ok(c, sp)) return SSA_E_INVALID;
     const TileGrid g = tile_grid(p->n_obj);
     dim3 grid((unsigned)g.nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
@@ -5290,6 +5314,7 @@ int ssa_lookahead_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p
     VecLookSensK k;
     const int rc = lookahead_sensors_args(c, p, sp, o, true, k.k, k.s);
     if (rc != SSA_OK) return rc;
+    if (!kinds_ok(c, sp)) return SSA_E_INVALID;
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     dim3 grid((unsigned)g.nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
@@ -5306,7 +5331,7 @@ int ssa_forecast_sensors_f64(const ssa_consts* c, const ssa_step_params* p, cons
     ForeSensK k;
     const int rc = lookahead_sensors_args(c, p, sp, &f->out, false, lk, k.s);
     if (rc != SSA_OK) return rc;
-    if (f->n_steps < 1) return SSA_E_INVALID;
+    if (f->n_steps < 1 || !kinds_ok(c, sp)) return SSA_E_INVALID;
     k.k = lk.k;
     k.k.p.launch_mask = 0;   // (the time word is read from env_time: a resident tile's steps do not see SSA_LAUNCH_INLINE_ENVS)
     k.f = *f;
@@ -5323,7 +5348,7 @@ int ssa_forecast_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p,
     VecForeSensK k;
     const int rc = lookahead_sensors_args(c, p, sp, &f->out, true, lk, k.s);
     if (rc != SSA_OK) return rc;
-    if (f->n_steps < 1) return SSA_E_INVALID;
+    if (f->n_steps < 1 || !kinds_ok(c, sp)) return SSA_E_INVALID;
     k.k = lk.k;   // (launch_mask: SSA_LAUNCH_INLINE_ENVS alone survives lookahead_args, and the kernel reads inline_time by it)
     k.f = *f;
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
@@ -5342,7 +5367,7 @@ int ssa_dryrun_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p, c
     const int rc = lookahead_sensors_args(c, p, sp, &o, true, lk, k.s);
     if (rc != SSA_OK) return rc;
     if (d->n_steps < 1 || d->n_obj_caller < 1 || !row_aligned(d->actions)) return SSA_E_INVALID;
-    if (!rows_fit(p->n_env, sp->n_sensor, d->n_steps)) return SSA_E_INVALID;
+    if (!rows_fit(p->n_env, sp->n_sensor, d->n_steps) || !kinds_ok(c, sp)) return SSA_E_INVALID;
     k.k = lk.k;
     k.k.p.launch_mask = 0;   // (the time words are read from env_time: a resident tile's steps do not see SSA_LAUNCH_INLINE_ENVS)
     k.d = *d;
@@ -5441,6 +5466,7 @@ int ssa_env_rollout_sensors_f64(const ssa_consts* c, const ssa_step_params* p, c
     RollSensK rk;
     const int rc = rollout_sensors_args(c, p, r, sp, rs->actions, false, rk.k, rk.s);
     if (rc != SSA_OK) return rc;
+    if (!kinds_ok(c, sp)) return SSA_E_INVALID;
     rk.rs = *rs;
     const TileGrid g = tile_grid(p->n_obj);
     hipStream_t s = (hipStream_t)stream;
@@ -5454,7 +5480,7 @@ int ssa_env_rollout_sensors_envs_f64(const ssa_consts* c, const ssa_step_params*
     VecRollSensK rk;
     const int rc = rollout_sensors_args(c, p, r, sp, re->actions, true, rk.k, rk.s);
     if (rc != SSA_OK) return rc;
-    if (!re->stats_out) return SSA_E_INVALID;
+    if (!re->stats_out || !kinds_ok(c, sp)) return SSA_E_INVALID;
     rk.v = *re;
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     hipStream_t s = (hipStream_t)stream;

@@ -70,11 +70,18 @@ MAX_SENSORS = 8
 
 def resolve_sensors(config):
     """the sensor network of a config dict (EXTENSION, no reference counterpart), or None without config['observers']:
-    {'sites': [(lat, lon, h)] * S (degrees, degrees, metres), 'obs_limit': [S] degrees or None, 'z_sigma': [S] or None}.
+    {'sites': [(lat, lon, h)] * S (degrees, degrees, metres), 'obs_limit': [S] degrees or None, 'z_sigma': [S] or None,
+    'angles_only': [S] booleans}.
     config['observers'] lists 1 <= S <= 8 sites; the optional config['sensor_obs_limit'] / config['sensor_z_sigma'] give per-sensor
-    values (S of them; default: the scalar obs_limit / z_sigma / R).  Anything else raises ValueError."""
+    values (S of them; default: the scalar obs_limit / z_sigma / R).  The optional config['sensor_measurement'] gives each sensor's
+    measurement kind, S strings: 'aer' (azimuth, elevation, range: the default) or 'ae' (azimuth and elevation only, a telescope:
+    the update of dim_z = 2); it needs obs_type 'aer' and, for an 'ae' entry, more than one site (a one-site env runs the
+    one-observer kernels, which measure az, el and range).  Anything else raises ValueError."""
     sites = config.get('observers')
     lim, zs = config.get('sensor_obs_limit'), config.get('sensor_z_sigma')
+    kinds = config.get('sensor_measurement')
+    if sites is None and kinds is not None:
+        raise ValueError("config['sensor_measurement'] needs config['observers']")
     if sites is None:
         if lim is not None or zs is not None:
             raise ValueError("config['sensor_obs_limit'] / config['sensor_z_sigma'] need config['observers']")
@@ -97,7 +104,21 @@ def resolve_sensors(config):
         zs = [np.asarray(z, dtype=np.float64) for z in zs]
         if any(z.shape != (3,) or not np.all(np.isfinite(z)) or np.any(z < 0) for z in zs):
             raise ValueError("config['sensor_z_sigma']: every entry is a z_sigma of three non-negative values")
-    return {'sites': [tuple(float(v) for v in row) for row in arr], 'obs_limit': lim, 'z_sigma': zs}
+    if kinds is None:
+        kinds = ['aer'] * S
+    else:
+        if isinstance(kinds, str) or not hasattr(kinds, '__len__') or len(kinds) != S:
+            raise ValueError("config['sensor_measurement'] must give one measurement kind per sensor: %d" % S)
+        kinds = list(kinds)
+        if any(not isinstance(k, str) or k not in ('aer', 'ae') for k in kinds):
+            raise ValueError("config['sensor_measurement']: every entry is 'aer' or 'ae', got %r" % (kinds,))
+        if config.get('obs_type') != 'aer':
+            raise ValueError("config['sensor_measurement'] needs obs_type 'aer', got %r" % (config.get('obs_type'),))
+        if S == 1 and kinds[0] == 'ae':
+            raise ValueError("config['sensor_measurement']: a one-site network cannot be 'ae' -- with one site step(), rollout, "
+                             "run_agent, run_policy and lookahead() run the one-observer kernels, which measure az, el and range")
+    return {'sites': [tuple(float(v) for v in row) for row in arr], 'obs_limit': lim, 'z_sigma': zs,
+            'angles_only': [k == 'ae' for k in kinds]}
 
 
 def resolve_config(config):
@@ -134,7 +155,7 @@ def resolve_config(config):
             R = np.array([np.diag(z ** 2) for z in zs])
         else:
             zs, R = np.tile(c.z_sigma, (S, 1)), np.tile(c.R, (S, 1, 1))
-        c.net = SimpleNamespace(lla=lla, obs_limit=lim, z_sigma=zs, R=R)
+        c.net = SimpleNamespace(lla=lla, obs_limit=lim, z_sigma=zs, R=R, angles_only=np.array(net['angles_only'], dtype=bool))
         c.obs_lla, c.obs_limit = lla[0], lim[0]
         c.z_sigma, c.R = zs[0], np.copy(R[0])
     c.obs_itrs = host.lla2ecef(c.obs_lla)

@@ -6,6 +6,7 @@ Same constructor dict, env id, spaces, return shapes and inspectable attributes
 order, one launch per step, one small device->host copy for reward/done, lazy numpy views of
 the device-resident history.  Citations: ssa_tasker_simple_2.py:line in the reference.
 """
+import math
 import time
 from datetime import timedelta
 
@@ -53,6 +54,8 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         self.z_sigma, self.R = c.z_sigma, c.R
         self.obs_lla, self.obs_itrs, self.obs_limit = c.obs_lla, c.obs_itrs, c.obs_limit
         self.n_sensor = c.n_sensor
+        # (config['sensor_measurement']: True where a sensor measures az and el only, section 8r; without a network: the one az-el-range observer)
+        self.sensor_angles_only = np.zeros(c.n_sensor, dtype=bool) if c.net is None else c.net.angles_only
         if c.net is not None:
             self.sensor_lla, self.sensor_obs_limit = c.net.lla, c.net.obs_limit
             self.sensor_z_sigma, self.sensor_R = c.net.z_sigma, c.net.R
@@ -134,7 +137,8 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         # stream synchronisation and one observation copy instead of four blocking transfers
         self._stats_host = torch.zeros(_lib.STAT_STRIDE, dtype=torch.float64).pin_memory()
         if self.n_sensor > 1:     # the network's sites and one update record per sensor (host-mapped, as the single record)
-            self._sensors = host.make_sensor_params(self.sensor_lla, self.sensor_obs_limit, self.sensor_R, self.n * self.m * 3)
+            self._sensors = host.make_sensor_params(self.sensor_lla, self.sensor_obs_limit, self.sensor_R, self.n * self.m * 3,
+                                                    angles_only=self.sensor_angles_only)
             self._upd_s_host = torch.zeros((self.n_sensor, _lib.UPD_STRIDE), dtype=torch.float64).pin_memory()
             self._upd_s_np, self._upd_s_ptr = self._upd_s_host.numpy(), self._upd_s_host.data_ptr()
         self._upd_host = torch.zeros(_lib.UPD_STRIDE, dtype=torch.float64).pin_memory()
@@ -685,11 +689,13 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         return out
 
     # two-sided chi-square critical points stats.chi2.ppf([alpha / 2, 1 - alpha / 2], df) for the reference's alpha = 0.05
-    # (:756, :762); other alphas need scipy
+    # (:756, :762); other alphas need scipy -- but for df = 2 (the updates of angles-only sensors), where the quantile is closed-form
     _CHI2_95 = {3: (0.21579528262389788, 9.348403604496145), 6: (1.2373442457912032, 14.449375335447922)}
 
     @classmethod
     def _chi2_points(cls, alpha, df):
+        if df == 2:      # (chi2(2) is exponential with mean 2: ppf(q) = -2 ln(1 - q))
+            return -2.0 * math.log(1.0 - alpha / 2), -2.0 * math.log(alpha / 2)
         if abs(alpha - 0.05) < 1e-15 and df in cls._CHI2_95:
             return cls._CHI2_95[df]
         from scipy import stats
@@ -702,7 +708,8 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         interval, counted ON THE DEVICE (ssa_nis_f64 / ssa_nees_f64 + ssa_chi2_contained_f64) over the steps simulated so
         far that are still resident.  The reference's Test 4 covers the WHOLE episode (its history arrays hold every step): build the
         env with config['history'] = 'full' for that -- with a short ring (history = 2, what 'auto' picks for very large envs) the NEES
-        window is the last `history` steps only, and 'nees_steps' in the result says how many it was.
+        window is the last `history` steps only, and 'nees_steps' in the result says how many it was.  A sensor network: the updates
+        of 'ae' sensors (config['sensor_measurement']) are counted against the 2-dof interval, the others against the 3-dof one, pooled.
         Returns {'Test 2: NIS chi2': pct, 'Test 4: NEES chi2': pct, counts...}."""
         self._caller_order()
         import torch
@@ -710,12 +717,19 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         e = self._engine
         out = {}
         k = np.nonzero(self.obs_taken[:self.i + 1])      # (a sensor network: every (step, sensor) update, pooled)
-        lo, hi = self._chi2_points(alpha, 3)
+        inside, valid = 0, 0
         if len(k[0]):
             nis = device.nis(torch.as_tensor(self._y[k]).to("cuda"), torch.as_tensor(self._S_sel[k]).to("cuda"))
-            inside, valid = device.chi2_contained(nis, lo, hi)
-        else:
-            inside, valid = 0, 0
+            if self.sensor_angles_only.any():      # (k[1]: the update's sensor; each kind against the interval of its own dimension)
+                ang = torch.as_tensor(self.sensor_angles_only[k[1]]).to("cuda")
+                parts = ((nis[~ang], 3), (nis[ang], 2))
+            else:
+                parts = ((nis, 3),)
+            for v, df in parts:
+                if v.numel():
+                    lo, hi = self._chi2_points(alpha, df)
+                    a, b = device.chi2_contained(v.contiguous(), lo, hi)
+                    inside, valid = inside + a, valid + b
         out['Test 2: NIS chi2'] = round(100.0 * inside / valid, 2) if valid else float('nan')
         out['nis_inside'], out['nis_valid'] = inside, valid
         first = max(0, self.i - e.H + 1)

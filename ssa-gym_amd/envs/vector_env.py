@@ -157,7 +157,9 @@ class SSA_Tasker_VecEnv:
         if S > 1:      # (noise per (env, sensor, time step): [E, S, n, 1, 3], sensor s scaled by its own z_sigma)
             from .. import host
             self._zs = torch.as_tensor(c.net.z_sigma, dtype=torch.float64, device="cuda").view(S, 1, 1, 3)
-            self._sensors = host.make_sensor_params(c.net.lla, c.net.obs_limit, c.net.R, self.n * 3)
+            self._sensors = host.make_sensor_params(c.net.lla, c.net.obs_limit, c.net.R, self.n * 3, angles_only=c.net.angles_only)
+        # (config['sensor_measurement']: True where a sensor measures az and el only; without a network: the one az-el-range observer)
+        self.sensor_angles_only = np.zeros(S, dtype=bool) if c.net is None else c.net.angles_only
         self._site = (c.obs_lla, c.obs_limit, c.R)      # (the env's own observer: a one-site network for lookahead_sensors)
         self._look_sites = None
         self._rows_host = None                          # step_agent: pinned [E, MAX_SENSORS] read-back of the action table

@@ -109,15 +109,20 @@ def make_consts(Q, R, alpha, beta, kappa, dt, obs_limit_rad, obs_lla, obs_type='
     return c
 
 
-def make_sensor_params(sites_lla, obs_limits_rad, Rs, zn_stride_sensor):
+def make_sensor_params(sites_lla, obs_limits_rad, Rs, zn_stride_sensor, angles_only=None):
     """pack a sensor network (include/ssa_hip.h: ssa_sensor_params): site s at sites_lla[s] = (lat [rad], lon [rad], h [m]) with elevation
     mask obs_limits_rad[s] and measurement noise covariance Rs[s] (3 x 3); sensor s's noise table starts zn_stride_sensor doubles after
-    sensor s - 1's.  Every sensor idle (action -1) and no record destination: the caller sets `action` and `upd` per step."""
+    sensor s - 1's.  angles_only: S booleans, True where sensor s measures azimuth and elevation only (None: every sensor measures
+    az, el and range).  Every sensor idle (action -1) and no record destination: the caller sets `action` and `upd` per step."""
     S = len(sites_lla)
     if not 1 <= S <= _lib.MAX_SENSORS or len(obs_limits_rad) != S or len(Rs) != S:
         raise ValueError("a sensor network has 1 .. %d sites, each with one elevation mask and one R" % _lib.MAX_SENSORS)
     sp = _lib.ssa_sensor_params()
     sp.n_sensor = S
+    kinds = [False] * S if angles_only is None else [bool(k) for k in angles_only]
+    if len(kinds) != S:
+        raise ValueError("angles_only has %d entries for %d sensors" % (len(kinds), S))
+    sp.angles_only = sum(1 << k for k in range(S) if kinds[k])
     for k in range(_lib.MAX_SENSORS):
         sp.action[k] = -1
     for k in range(S):
