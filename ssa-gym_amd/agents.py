@@ -115,44 +115,74 @@ def agent_trace_gain(obs, env):                 # argmax tr P- - tr P+ over the 
 # launch for all envs (ssa_lookahead_sensors_envs_f64, ssa_assign_sensors_envs_f64) and one read-back of E x 32 bytes; a sensor left
 # without an object draws by the same rule from single_action_space, envs in ascending order (the envs' own generators are not touched).
 # vec.step_agent(agent) is the step that takes the rows without the host in between.
+#
+# Every rule below is written ONCE, over arrays with a leading env axis: a single env is the batch of one, the
+# axis added on the way in (_lift) and taken off on the way out (_strip).  Where the two kinds of env differ, both classes answer the same
+# methods -- assign_sensors, _tasking_stream, _forecast_scores, _slab_assigner, _plan_table -- so this module asks the env, never the
+# env's engine, and every launch stays the env's own: a single env's the one-env entries, a vector env's the *_envs ones.
+def _num_envs(env):
+    """E of a vector env (SSA_Tasker_VecEnv), None for a single env: the one place in this module that tells the two apart"""
+    return getattr(env, "num_envs", None)
+
+
+def _lift(env, x):
+    """x with the env axis in front: a vector env's own, a single env's as the batch of one (a view)"""
+    return x[None] if _num_envs(env) is None else x
+
+
+def _strip(env, x):
+    return x[0] if _num_envs(env) is None else x
+
+
+def _steps_left(env):
+    """the steps every env still has in its episode: one horizon for all envs"""
+    return int(env.n - 1 - np.max(env.i))
+
+
+def _need_device_state(env, why):
+    if (env._engine if _num_envs(env) is None else env._eng) is None:
+        raise _lib.SsaHipError("no device state: %s (no CPU fallback)" % why)
+
+
 def _draw_unassigned(env, taken):
     if len(taken) >= env.m:
         raise ValueError("%d sensors but %d objects: no object left to assign" % (len(taken) + 1, env.m))
-    space = env.single_action_space if hasattr(env, "single_action_space") else env.action_space
+    space = env.action_space if _num_envs(env) is None else env.single_action_space
     while True:
         for j in np.atleast_1d(space.sample()):
             if int(j) not in taken:
                 return int(j)
 
 
-def _assign_lookahead_sensors_envs(vec, k, rule='greedy'):
-    # int64 [E, S], -1 where the scores leave a sensor without an object
-    acts = vec.assign_sensors(k) if rule == 'greedy' else vec.assign_sensors(k, rule=rule)
-    for act in acts:                                        # (envs ascending, sensors ascending)
-        taken = set(act[act >= 0].tolist())
-        for s in np.flatnonzero(act < 0):
-            act[s] = _draw_unassigned(vec, taken)
-            taken.add(int(act[s]))
-    return acts
+def _plan_copy(env, plan):
+    """an int64 C-order copy of a plan: [H', S], one env's rows, or [E, H', S], every env's -- the rank decides, not the env's kind"""
+    plan = np.array(plan, dtype=np.int64, order='C')
+    E = _num_envs(env) or 1
+    if plan.ndim not in (2, 3) or (plan.ndim == 3 and plan.shape[0] != E):
+        raise ValueError("a plan is [H', S], one env's, or every env's, [%d, H', S]: got shape %s" % (E, plan.shape))
+    return plan
+
+
+def _fill_plan(env, plan):
+    """the -1 entries of a plan [H', S] filled row by row, sensors ascending: an object no sensor of that row holds, drawn from the
+    action space's generator (env.np_random and a vector env's _rng are not touched).  Such a sensor has no healthy visible object left
+    at that step, so its draw updates nothing the forecast counted on.  A plan [E, H', S] is filled env by env, envs ascending, from
+    the one generator (a vector env's single_action_space); the rows of one assignment, [S] per env, are a plan of one step."""
+    plan = _plan_copy(env, plan)
+    for row in plan.reshape(-1, plan.shape[-1]):            # (a view: envs ascending, rows ascending)
+        taken = set(row[row >= 0].tolist())
+        for s in np.flatnonzero(row < 0):
+            row[s] = _draw_unassigned(env, taken)
+            taken.add(int(row[s]))
+    return plan
 
 
 def _assign_lookahead_sensors(env, k, rule='greedy'):
-    if hasattr(env, "num_envs"):                           # (a vector env: every env's row)
-        return _assign_lookahead_sensors_envs(env, k, rule)
-    score = env.lookahead_sensors()["score"]               # [S, 3, m]: a view of the engine's [S][m][3] rows
-    S = score.shape[0]
-    row = env._engine.assign_row()
-    # the rounds above on the device (ssa_assign_sensors_f64; no fallback words: a sensor without an object comes back -1): one launch
-    # and one 32-byte read-back where S masked arg-max launches and S read-backs were
-    # (permuted back, the view IS the engine's contiguous [S][m][3] block: launch_assign_sensors refuses anything else)
-    env._engine.launch_assign_sensors({"score": score.permute(0, 2, 1)}, k, row, stream=env._stream.cuda_stream, rule=rule)
-    env._stream.synchronize()
-    act = row.cpu().numpy()[:S].astype(np.int64)
-    taken = set(act[act >= 0].tolist())
-    for s in np.flatnonzero(act < 0):
-        act[s] = _draw_unassigned(env, taken)
-        taken.add(int(act[s]))
-    return act if env.n_sensor > 1 else int(act[0])        # (one sensor: a Discrete action, as agent_info_gain's)
+    # the rounds above on the device (env.assign_sensors: no fallback words, int64 [S] or [E, S], -1 where the scores leave a sensor
+    # without an object), the -1 entries filled as a plan of one step per env: envs ascending, sensors ascending
+    acts = env.assign_sensors(k) if rule == 'greedy' else env.assign_sensors(k, rule=rule)
+    acts = _strip(env, _fill_plan(env, _lift(env, acts)))
+    return acts if env.n_sensor > 1 or _num_envs(env) is not None else int(acts[0])      # (one sensor: a Discrete action, as agent_info_gain's)
 
 
 def agent_info_gain_sensors(obs, env):          # one object per sensor, greedy over 1/2 ln(det P- / det P+) from every site
@@ -184,78 +214,37 @@ def agent_trace_gain_sensors_optimal(obs, env):  # one object per sensor, the la
 # takes at step h, and the whole plan is what vec.rollout_sensors() takes (section 8l): ONE forecast launch for all envs (ssa_forecast_sensors_envs_f64), then per step ONE assignment launch for all envs
 # on the contiguous slab h, each env's earlier picks removed from its own part of the slab; one read-back, the -1 entries filled per
 # env, envs ascending, from single_action_space.
-def _fill_plan(env, plan):
-    """the -1 entries of a plan [H', S] filled row by row, sensors ascending: an object no sensor of that row holds, drawn from the
-    action space's generator (env.np_random is not touched).  Such a sensor has no healthy visible object left at that step, so its
-    draw updates nothing the forecast counted on."""
-    plan = np.array(plan, dtype=np.int64)
-    for row in plan:
-        taken = set(row[row >= 0].tolist())
-        for s in np.flatnonzero(row < 0):
-            row[s] = _draw_unassigned(env, taken)
-            taken.add(int(row[s]))
-    return plan
+def _plan_rows(env, table):
+    """an int32 device table [H', E, MAX_SENSORS] of a planner as the plan it stands for: int64 [H', S] ([E, H', S] of a vector env)"""
+    return _strip(env, np.ascontiguousarray(table.cpu().numpy()[:, :, :env.n_sensor].astype(np.int64).transpose(1, 0, 2)))
 
 
 def _plan_assigned(env, horizon, k, rule='greedy'):
-    """the device's part of a plan: int64 [H', S], -1 where the scores leave a sensor without an object"""
+    """the device's part of a plan: int64 [H', S] ([E, H', S] of a vector env), -1 where the scores leave a sensor without an object.
+    ONE forecast launch for all envs, then per step ONE assignment launch for all envs on the contiguous slab score[h] = [E, S, m, 3],
+    into row h of a table of the planner's own (not the engine's action table); what an env planned at an earlier step is NaN in a copy
+    of its part of the slab."""
     import torch
-    with torch.cuda.stream(env._stream):
-        score = env.forecast_sensors(horizon)["score"]         # [H', S, m, 3]
-        Hp, S, m = score.shape[:3]
-        e = env._engine
-        rows = torch.full((Hp, _lib.MAX_SENSORS), -1, dtype=torch.int32, device=score.device)
-        planned = torch.zeros(m + 1, dtype=torch.bool, device=score.device)     # (slot m: where the -1 entries of a row land)
-        for h in range(Hp):
-            slab = score[h] if h == 0 else score[h].masked_fill(planned[:m].view(1, m, 1), float("nan"))
-            e.launch_assign_sensors({"score": slab}, k, rows[h], stream=env._stream.cuda_stream, rule=rule)
-            r = rows[h].long()
-            planned[torch.where(r >= 0, r, torch.full_like(r, m))] = True
-    env._stream.synchronize()
-    return rows.cpu().numpy()[:, :S].astype(np.int64)
-
-
-def _fill_plan_envs(vec, plan):
-    """a vector env's plan [E, H', S]: _fill_plan for every env, envs ascending, from single_action_space (the envs' _rng is not touched)"""
-    plan = np.asarray(plan, dtype=np.int64)
-    if plan.ndim != 3 or plan.shape[0] != vec.num_envs:
-        raise ValueError("a vector env's plan is [%d, H', S], got shape %s" % (vec.num_envs, plan.shape))
-    return np.stack([_fill_plan(vec, plan[e]) for e in range(plan.shape[0])])
-
-
-def _plan_assigned_envs(vec, horizon, k, rule='greedy'):
-    """the device's part of a vector env's plan: int64 [E, H', S], -1 where the scores leave a sensor without an object.  ONE forecast
-    launch for all envs, then per step ONE assignment launch for all envs (ssa_assign_sensors_envs_f64) on the contiguous slab
-    score[h] = [E, S, m, 3], into row h of a table of the planner's own (not the engine's action table), with ONE workspace; what an
-    env planned at an earlier step is NaN in a copy of its part of the slab."""
-    import torch
-    from . import device
-    cur = vec._stream if vec._inline else torch.cuda.current_stream()
+    cur = env._tasking_stream()
     with torch.cuda.stream(cur):
-        score = vec._launch_forecast_sensors(horizon)["score"]     # [H', E, S, m, 3]
+        score = env._forecast_scores(horizon)                      # [H', E, S, m, 3]
         Hp, E, S, m = score.shape[:4]
+        assign = env._slab_assigner(score)
         rows = torch.full((Hp, E, _lib.MAX_SENSORS), -1, dtype=torch.int32, device=score.device)
         planned = torch.zeros((E, m + 1), dtype=torch.bool, device=score.device)     # (slot m: where the -1 entries of a row land)
-        env_ix = torch.arange(E, device=score.device).view(E, 1)
-        ws = device.assign_sensors_envs_workspace(m, S, E, score.device)
         for h in range(Hp):
             slab = score[h] if h == 0 else score[h].masked_fill(planned[:, :m].view(E, 1, m, 1), float("nan"))
-            device.assign_sensors_envs(slab, k, out=rows[h], workspace=ws, rule=rule)
+            assign(slab, k, rows[h], rule)
             r = rows[h].long()
-            planned[env_ix, torch.where(r >= 0, r, torch.full_like(r, m))] = True
+            planned.scatter_(1, torch.where(r >= 0, r, torch.full_like(r, m)), True)      # (env e's picks into env e's row)
     cur.synchronize()
-    return np.ascontiguousarray(rows.cpu().numpy()[:, :, :S].astype(np.int64).transpose(1, 0, 2))
+    return _plan_rows(env, rows)
 
 
 def _plan_lookahead_sensors(env, horizon, k, rule='greedy'):
     from . import device
     device.assign_entry(rule)                              # (an unknown rule: refused before anything else)
-    if hasattr(env, "num_envs"):                           # (a vector env: every env's plan, [E, H', S])
-        if env._eng is None:
-            raise _lib.SsaHipError("no device state: a plan comes from the forecast, which runs on the GPU only (no CPU fallback)")
-        return _fill_plan_envs(env, _plan_assigned_envs(env, horizon, k, rule))
-    if env._engine is None:
-        raise _lib.SsaHipError("no device state: a plan comes from the forecast, which runs on the GPU only (no CPU fallback)")
+    _need_device_state(env, "a plan comes from the forecast, which runs on the GPU only")
     return _fill_plan(env, _plan_assigned(env, horizon, k, rule))
 
 
@@ -283,14 +272,15 @@ def _fill_plan_horizon(env, plan):
     object that appears NOWHERE in this env's plan (planned or filled, at any step).  Such an object cannot be a candidate of that slot
     -- the plan would have filled the slot with it --, so its draw updates nothing the plan counts on.  If every object appears in the
     plan already (fewer objects than slots can make it so), the row rule of _fill_plan is all that is left: an object no sensor of that
-    row holds."""
-    plan = np.array(plan, dtype=np.int64)
-    used = set(plan[plan >= 0].tolist())
-    for row in plan:
-        for s in np.flatnonzero(row < 0):
-            taken = used if len(used) < env.m else set(row[row >= 0].tolist())
-            row[s] = _draw_unassigned(env, taken)
-            used.add(int(row[s]))
+    row holds.  A plan [E, H', S] is filled env by env, envs ascending, each env with its own set of objects in use."""
+    plan = _plan_copy(env, plan)
+    for one in plan.reshape((-1,) + plan.shape[-2:]):       # (views: envs ascending)
+        used = set(one[one >= 0].tolist())
+        for row in one:
+            for s in np.flatnonzero(row < 0):
+                taken = used if len(used) < env.m else set(row[row >= 0].tolist())
+                row[s] = _draw_unassigned(env, taken)
+                used.add(int(row[s]))
     return plan
 
 
@@ -299,8 +289,7 @@ def _plan_horizon_steps(env, horizon):
     from . import device
     if int(horizon) < 1:
         raise ValueError("forecast_sensors: a horizon of at least one step, got %r" % (horizon,))
-    left = int(env.n - 1 - np.max(env.i))
-    Hp = min(int(horizon), left)
+    Hp = min(int(horizon), _steps_left(env))
     device.check_plan_slots(Hp, env.n_sensor)
     return Hp
 
@@ -308,26 +297,17 @@ def _plan_horizon_steps(env, horizon):
 def _plan_horizon_assigned(env, horizon, k):
     """the device's part of a horizon-wide plan: int64 [H', S] ([E, H', S] of a vector env), -1 in the slots the plan leaves idle"""
     import torch
-    S = env.n_sensor
-    if hasattr(env, "num_envs"):
-        cur = env._stream if env._inline else torch.cuda.current_stream()
-        with torch.cuda.stream(cur):
-            table = env._eng.launch_plan_sensors(env._launch_forecast_sensors(horizon), k, stream=cur.cuda_stream)
-        cur.synchronize()
-        return np.ascontiguousarray(table.cpu().numpy()[:, :, :S].astype(np.int64).transpose(1, 0, 2))
-    with torch.cuda.stream(env._stream):
-        table = env._engine.launch_plan_sensors(env.forecast_sensors(horizon), k, stream=env._stream.cuda_stream)
-    env._stream.synchronize()
-    return table.cpu().numpy()[:, :S].astype(np.int64)
+    cur = env._tasking_stream()
+    with torch.cuda.stream(cur):
+        table = env._plan_table(horizon, k)                 # [H', E, MAX_SENSORS]: the forecast's launch, then the plan's
+    cur.synchronize()
+    return _plan_rows(env, table)
 
 
 def _plan_horizon(env, horizon, k):
     _plan_horizon_steps(env, horizon)
-    vector = hasattr(env, "num_envs")
-    if (env._eng if vector else env._engine) is None:
-        raise _lib.SsaHipError("no device state: a plan comes from the forecast, which runs on the GPU only (no CPU fallback)")
-    plan = _plan_horizon_assigned(env, horizon, k)
-    return np.stack([_fill_plan_horizon(env, p) for p in plan]) if vector else _fill_plan_horizon(env, plan)
+    _need_device_state(env, "a plan comes from the forecast, which runs on the GPU only")
+    return _fill_plan_horizon(env, _plan_horizon_assigned(env, horizon, k))
 
 
 def plan_info_gain_sensors_horizon(env, horizon):              # a schedule [H', S] for env.rollout_sensors() ([E, H', S] of a vector
@@ -354,71 +334,33 @@ def refine_plan_sensors(env, plan, kind='info', rounds=4, candidates=64, seed=0)
     with the largest total in column `kind` ('info', 'trace', 'pos_trace').  ONE forecast launch for the masks.  The draws come from
     RandomState(seed): env.np_random and the action space's generator are not touched.  Returns (plan, total [3] float64 of it).
     A vector env (SSA_Tasker_VecEnv; section 8q): `plan` [E, K, S]; env e searches with RandomState(seed + e) exactly as a single env
-    in its state would with that seed, one forecast and one evaluate_schedules() launch per round serve all envs; returns
-    (plan [E, K', S], total [E, 3])."""
+    in its state would with that seed -- it is the same loop, a single env being the batch of one --, drawn from in the single env's
+    order; ONE forecast and ONE evaluate_schedules() launch per round ([E, candidates, K', S]) serve all envs, with one horizon for
+    all, K' = min(K, min_e(steps - 1 - i_e)); returns (plan [E, K', S] as vec.rollout_sensors() takes it, total [E, 3]).
+    Of an env this reads forecast_sensors(), evaluate_schedules(), i, n, m, n_sensor and num_envs, and for the device-state guard
+    _engine / _eng: nothing else."""
     if kind not in REFINE_KINDS:
         raise ValueError("refine_plan_sensors: kind must be one of %s, got %r" % (sorted(REFINE_KINDS), kind))
     if int(rounds) < 0 or int(candidates) < 1:
         raise ValueError("refine_plan_sensors: rounds >= 0 and candidates >= 1, got %r and %r" % (rounds, candidates))
-    if hasattr(env, "num_envs"):
-        return _refine_plan_sensors_envs(env, plan, REFINE_KINDS[kind], int(rounds), int(candidates), seed)
-    if env._engine is None:
-        raise _lib.SsaHipError("no device state: a plan is refined by dry runs, which run on the GPU only (no CPU fallback)")
-    col = REFINE_KINDS[kind]
+    _need_device_state(env, "a plan is refined by dry runs, which run on the GPU only")
+    col, rounds, candidates = REFINE_KINDS[kind], int(rounds), int(candidates)
+    E, S = _num_envs(env), int(env.n_sensor)
+    lead = () if E is None else (int(E),)
     plan = np.array(plan, dtype=np.int64)
-    if plan.ndim != 2 or plan.shape[1] != env.n_sensor:
-        raise ValueError("refine_plan_sensors: a plan [K, %d], got shape %s" % (env.n_sensor, plan.shape))
-    K = min(plan.shape[0], int(env.n - 1 - env.i))
+    if plan.ndim != len(lead) + 2 or plan.shape[:-2] != lead or plan.shape[-1] != S:
+        raise ValueError("refine_plan_sensors: a plan [%sK, %d], got shape %s" % ("".join("%d, " % v for v in lead), S, plan.shape))
+    plan = _lift(env, plan)                                                                       # [E, K, S]
+    E = plan.shape[0]
+    K = min(plan.shape[1], _steps_left(env))
     if K < 1:
-        raise ValueError("refine_plan_sensors: at least one step inside the episode")
-    plan = plan[:K]
-    S = plan.shape[1]
-    rng = np.random.RandomState(seed)
-    ok = None
-    if int(candidates) > 1 and int(rounds) > 0:
-        f = env.forecast_sensors(K)
-        ok = (f["visible"].cpu().numpy() != 0) & (f["status"].cpu().numpy() == _lib.ST_OK)       # [K', S, m]
-    total = None
-    for _ in range(int(rounds) if int(candidates) > 1 else 0):
-        cand = np.repeat(plan[None], int(candidates), axis=0)
-        for c in range(1, int(candidates)):
-            k, s = divmod(int(rng.randint(K * S)), S)
-            free = ok[k, s].copy()
-            row = plan[k]
-            free[row[(row >= 0) & (row < free.shape[0])]] = False
-            pool = np.flatnonzero(free)
-            if len(pool):
-                cand[c, k, s] = pool[rng.randint(len(pool))]
-        totals = env.evaluate_schedules(cand)["total"].cpu().numpy()
-        # (the first of equal maxima: the incumbent stays unless something is strictly better.  A NaN total -- a taken update of a
-        # covariance that has no log-determinant left, late in an episode -- never wins)
-        best = int(np.argmax(np.where(np.isnan(totals[:, col]), -np.inf, totals[:, col])))
-        plan, total = cand[best], totals[best]
-    if total is None:
-        total = env.evaluate_schedules(plan)["total"].cpu().numpy()[0]
-    return plan, np.asarray(total, dtype=np.float64)
-
-
-def _refine_plan_sensors_envs(vec, plan, col, rounds, candidates, seed):
-    """refine_plan_sensors for a vector env: `plan` [E, K, S]; every env runs the single env's local search on
-    its own incumbent with its own RandomState(seed + e), drawn from in the single env's order, and ONE vec.evaluate_schedules()
-    launch per round values the candidates of all envs ([E, candidates, K', S]); ONE vec.forecast_sensors() for the masks.  One horizon
-    for all envs, K' = min(K, min_e(steps - 1 - i_e)).  Returns (plan [E, K', S] int64 as vec.rollout_sensors() takes it, total [E, 3])."""
-    if vec._eng is None:
-        raise _lib.SsaHipError("no device state: a plan is refined by dry runs, which run on the GPU only (no CPU fallback)")
-    E, S = int(vec.num_envs), int(vec.n_sensor)
-    plan = np.array(plan, dtype=np.int64)
-    if plan.ndim != 3 or plan.shape[0] != E or plan.shape[2] != S:
-        raise ValueError("refine_plan_sensors: a plan [%d, K, %d], got shape %s" % (E, S, plan.shape))
-    K = min(plan.shape[1], int(vec.n - 1 - np.max(vec.i)))
-    if K < 1:
-        raise ValueError("refine_plan_sensors: at least one step inside every env's episode")
+        raise ValueError("refine_plan_sensors: at least one step inside %s episode" % ("every env's" if lead else "the"))
     plan = plan[:, :K]
-    rngs = [np.random.RandomState(seed + e) for e in range(E)]
+    rngs = [np.random.RandomState(seed + e if e else seed) for e in range(E)]
     ok = None
     if candidates > 1 and rounds > 0:
-        f = vec.forecast_sensors(K)
-        ok = (f["visible"].cpu().numpy() != 0) & (f["status"].cpu().numpy() == _lib.ST_OK)       # [E, K', S, m]
+        f = env.forecast_sensors(K)
+        ok = _lift(env, (f["visible"].cpu().numpy() != 0) & (f["status"].cpu().numpy() == _lib.ST_OK))      # [E, K', S, m]
     total = None
     for _ in range(rounds if candidates > 1 else 0):
         cand = np.repeat(plan[:, None], candidates, axis=1)
@@ -431,10 +373,11 @@ def _refine_plan_sensors_envs(vec, plan, col, rounds, candidates, seed):
                 pool = np.flatnonzero(free)
                 if len(pool):
                     cand[e, c, k, s] = pool[rngs[e].randint(len(pool))]
-        totals = vec.evaluate_schedules(cand)["total"].cpu().numpy()                              # [E, candidates, 3]
-        # (per env the first of equal maxima; a NaN total never wins: the single env's rule)
+        totals = _lift(env, env.evaluate_schedules(_strip(env, cand))["total"].cpu().numpy())    # [E, candidates, 3]
+        # (per env the first of equal maxima: the incumbent stays unless something is strictly better.  A NaN total -- a taken update
+        # of a covariance that has no log-determinant left, late in an episode -- never wins)
         best = np.argmax(np.where(np.isnan(totals[:, :, col]), -np.inf, totals[:, :, col]), axis=1)
         plan, total = cand[np.arange(E), best], totals[np.arange(E), best]
     if total is None:
-        total = vec.evaluate_schedules(plan)["total"].cpu().numpy()[:, 0]
-    return plan, np.asarray(total, dtype=np.float64)
+        total = _lift(env, env.evaluate_schedules(_strip(env, plan))["total"].cpu().numpy())[:, 0]
+    return _strip(env, plan), np.asarray(_strip(env, total), dtype=np.float64)

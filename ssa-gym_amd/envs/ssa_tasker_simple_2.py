@@ -16,6 +16,7 @@ from .. import _lib, host
 from ._config import draw_initial_state, resolve_config, reward_done
 from ._gymshim import Env, np_random, spaces
 from ._policy import _PolicyLoop
+from ._tasking import SENSOR_AGENT_COLUMNS, SENSOR_AGENT_RULES, check_schedules, lookahead_result, network_sites, schedules_result, sensor_agent_rule
 from ._views import _FailureMessages, _History, _Sparse
 
 
@@ -484,9 +485,7 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
 
     def _sites(self):
         """the sites of the env as a network: its own; without config['observers'] the env's one observer as a one-site block, built once"""
-        if self._look_sites is None:
-            self._look_sites = self._sensors if self.n_sensor > 1 else host.make_sensor_params([self.obs_lla], [self.obs_limit], [self.R], 0)
-        return self._look_sites
+        return network_sites(self, self.obs_lla, self.obs_limit, self.R)
 
     AGENT_KINDS = {'agent_naive_greedy': _lib.AGENT_NAIVE_GREEDY, 'agent_visible_greedy': _lib.AGENT_VISIBLE_GREEDY,
                    'agent_visible_greedy_aer': _lib.AGENT_VISIBLE_GREEDY, 'agent_shannon': _lib.AGENT_SHANNON,
@@ -571,11 +570,8 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
             pos += kk
         return self._obs_out(refresh_aer_dev=True), np.asarray(actions, dtype=int), np.asarray(rewards), np.asarray(dones, dtype=bool)
 
-    SENSOR_AGENT_COLUMNS = {'agent_info_gain_sensors': _lib.LOOK_INFO_GAIN, 'agent_trace_gain_sensors': _lib.LOOK_TRACE_GAIN}
-    # every agent run_agent_sensors takes: name -> (score column, assignment rule of device.ASSIGN_RULES)
-    SENSOR_AGENT_RULES = {'agent_info_gain_sensors': (_lib.LOOK_INFO_GAIN, 'greedy'), 'agent_trace_gain_sensors': (_lib.LOOK_TRACE_GAIN, 'greedy'),
-                          'agent_info_gain_sensors_optimal': (_lib.LOOK_INFO_GAIN, 'optimal'),
-                          'agent_trace_gain_sensors_optimal': (_lib.LOOK_TRACE_GAIN, 'optimal')}
+    # (every agent run_agent_sensors takes: the one table of envs/_tasking.py under the names it has here)
+    SENSOR_AGENT_COLUMNS, SENSOR_AGENT_RULES = SENSOR_AGENT_COLUMNS, SENSOR_AGENT_RULES
 
     def run_agent_sensors(self, agent, n_steps, fallback_actions=None):
         """run_agent() for a sensor network (no reference counterpart): the loop
@@ -593,12 +589,7 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         if self._engine is None:
             raise _lib.SsaHipError("no device state: a sensor network's closed loop runs on the GPU only (no CPU fallback)")
         import torch
-        name = agent if isinstance(agent, str) else getattr(agent, "__name__", None)
-        if name not in self.SENSOR_AGENT_RULES:
-            raise NotImplementedError("run_agent_sensors: %r has no device-side version (supported: %s; with the optimal assignment: %s)"
-                                      % (agent, sorted(self.SENSOR_AGENT_COLUMNS),
-                                         sorted(set(self.SENSOR_AGENT_RULES) - set(self.SENSOR_AGENT_COLUMNS))))
-        column, rule = self.SENSOR_AGENT_RULES[name]
+        column, rule = sensor_agent_rule(agent, 'run_agent_sensors')
         self._caller_order()
         shaped = self.reward_type == 'shaped'
         e, sites, S, W = self._engine, self._sites(), self.n_sensor, _lib.MAX_SENSORS
@@ -814,11 +805,7 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         of the next step after step(j)).  The tensors are the env's lookahead buffers: the next call overwrites them."""
         self._single_sensor('lookahead')
         e, want = self._engine, self._lookahead_parts('lookahead', covariances)
-        r = e.launch_lookahead(self.i % e.H, self.i + 1, out=want, stream=self._stream.cuda_stream)
-        res = {"score": r["score"].t(), "visible": r["visible"], "status": r["status"]}
-        for k in want:
-            res[k] = r[k]
-        return res
+        return lookahead_result(e.launch_lookahead(self.i % e.H, self.i + 1, out=want, stream=self._stream.cuda_stream), want)
 
     def lookahead_sensors(self, covariances=False):
         """The lookahead of every sensor of the network (no reference counterpart; include/ssa_hip.h: ssa_lookahead_sensors_f64; DESIGN.md
@@ -832,11 +819,7 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         and with covariances=True also x_prior [m, 6], P_prior [m, 6, 6] (the prediction, the same for every sensor) and P_post
         [S, m, 6, 6].  The tensors are the env's buffers: the next call overwrites them."""
         e, want = self._engine, self._lookahead_parts('lookahead_sensors', covariances)
-        r = e.launch_lookahead_sensors(self.i % e.H, self.i + 1, self._sites(), out=want, stream=self._stream.cuda_stream)
-        res = {"score": r["score"].permute(0, 2, 1), "visible": r["visible"], "status": r["status"]}
-        for k in want:
-            res[k] = r[k]
-        return res
+        return lookahead_result(e.launch_lookahead_sensors(self.i % e.H, self.i + 1, self._sites(), out=want, stream=self._stream.cuda_stream), want)
 
     def forecast_sensors(self, horizon, covariances=False):
         """The H-step tasking forecast of the network (no reference counterpart; include/ssa_hip.h: ssa_forecast_sensors_f64; DESIGN.md
@@ -872,26 +855,47 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
             total   [B, 3] float64: the sum of the taken slots' scores per column, in slot order (k outer, s inner); 0 for none
         Nothing of the env changes: no engine tensor, not i, the histories or np_random.  Only the objects a candidate names are run
         (gather=False, B == 1: the whole catalogue on the slot itself -- the cost of a rollout; the tests' yardstick)."""
-        import torch
-        from .. import device
         if self._engine is None:
             raise _lib.SsaHipError("no device state: the dry run of a schedule runs on the GPU only (no CPU fallback)")
-        a = actions.detach().cpu().numpy() if isinstance(actions, torch.Tensor) else np.asarray(actions)
-        if a.ndim == 2:
-            a = a[None]
-        if a.ndim != 3 or a.shape[2] != self.n_sensor or a.dtype.kind not in "iu":
-            raise ValueError("evaluate_schedules: integer schedules [K, %d] or [B, K, %d], got %s %s" % (self.n_sensor, self.n_sensor, a.dtype, a.shape))
+        a = check_schedules(actions, self.n_sensor)
         K = min(int(a.shape[1]), self.n - 1 - self.i)
         if K < 1:
             raise ValueError("evaluate_schedules: at least one step inside the episode (i = %d, steps = %d, K = %d)" % (self.i, self.n, a.shape[1]))
         e = self._engine
         rec = e.launch_dryrun_sensors(self.i % e.H, self.i + 1, self._sites(), a[:, :K], stream=self._stream, gather=gather)
-        with torch.cuda.stream(self._stream):
-            score = rec[..., _lib.DRY_SCORE:_lib.DRY_SCORE + _lib.LOOK_NSCORE]
-            taken = rec[..., _lib.DRY_TAKEN] != 0
-            total = device.dryrun_totals(rec.permute(1, 0, 2, 3))     # (the engine's [K, B, S, 8] block; slot order: one defined fp64 sum)
-            return {"score": score, "taken": taken, "visible": rec[..., _lib.DRY_VISIBLE] != 0,
-                    "status": rec[..., _lib.DRY_STATUS].to(torch.int32), "action": rec[..., _lib.DRY_ACTION].to(torch.int64), "total": total}
+        return schedules_result(rec, self._stream)
+
+    # ---- what agents.py asks of an env beside its public queries (DESIGN.md section 8s; SSA_Tasker_VecEnv answers the same for its E
+    # envs): the planners' arrays carry a leading env axis, this env being the batch of one
+    def assign_sensors(self, column, rule='greedy'):
+        """the network's lookahead and its assignment over score column `column` (_lib.LOOK_*) by `rule` ('greedy', or 'optimal': most
+        sensors tasked, then the largest sum): two launches and one 32-byte read-back (SSA_Tasker_VecEnv.assign_sensors for one env).
+        int64 [S]; -1: the scores left that sensor without an object.  Nothing of the env changes."""
+        score = self.lookahead_sensors()["score"]              # [S, 3, m]: a view of the engine's [S][m][3] rows
+        S = score.shape[0]
+        row = self._engine.assign_row()
+        # the rounds of the agents on the device (ssa_assign_sensors_f64; no fallback words: a sensor without an object comes back -1): one
+        # launch and one 32-byte read-back where S masked arg-max launches and S read-backs were
+        # (permuted back, the view IS the engine's contiguous [S][m][3] block: launch_assign_sensors refuses anything else)
+        self._engine.launch_assign_sensors({"score": score.permute(0, 2, 1)}, column, row, stream=self._stream.cuda_stream, rule=rule)
+        self._stream.synchronize()
+        return row.cpu().numpy()[:S].astype(np.int64)
+
+    def _tasking_stream(self):
+        return self._stream                 # (the torch stream the planners' launches go in)
+
+    def _forecast_scores(self, horizon):
+        """the forecast's scores as the engine leaves them, with the env axis: [H', 1, S, m, 3] (a view; slab h is score[h])"""
+        return self.forecast_sensors(horizon)["score"].unsqueeze(1)
+
+    def _slab_assigner(self, score):
+        """assign(slab [1, S, m, 3], column, row [1, MAX_SENSORS], rule): one launch in the env's stream, the engine's workspace"""
+        e, stream = self._engine, self._stream.cuda_stream
+        return lambda slab, column, row, rule: e.launch_assign_sensors({"score": slab[0]}, column, row[0], stream=stream, rule=rule)
+
+    def _plan_table(self, horizon, column):
+        """the forecast's launch and the horizon-wide plan's (ssa_plan_sensors_f64) on it: the engine's int32 table as [H', 1, MAX_SENSORS]"""
+        return self._engine.launch_plan_sensors(self.forecast_sensors(horizon), column, stream=self._stream.cuda_stream).unsqueeze(1)
 
     def aer_obs(self, obs):
         """:834-840 -- [az, el, range, trace(P)] per object, NaN/inf -> 0.001."""

@@ -32,6 +32,9 @@ import numpy as np
 from .. import _lib
 from ._config import draw_initial_state, resolve_config, reward_done
 from ._gymshim import np_random, spaces
+# (the agent table is one object: SENSOR_AGENTS is SSA_Tasker_Env.SENSOR_AGENT_COLUMNS, SENSOR_AGENT_RULES the env's of that name)
+from ._tasking import SENSOR_AGENT_COLUMNS as SENSOR_AGENTS, SENSOR_AGENT_RULES, sensor_agent_column, sensor_agent_rule  # noqa: F401
+from ._tasking import check_schedules, env_time_words, lookahead_result, network_sites, schedules_result
 
 
 def check_sensor_actions(actions, E, S, m):
@@ -46,29 +49,6 @@ def check_sensor_actions(actions, E, S, m):
         if len(np.unique(a[e])) != S:
             raise ValueError("step: two sensors tasked to the same object (%s) in env %d" % (a[e], e))
     return a
-
-
-SENSOR_AGENTS = {'agent_info_gain_sensors': _lib.LOOK_INFO_GAIN, 'agent_trace_gain_sensors': _lib.LOOK_TRACE_GAIN}
-# every agent of a sensor network that decides on the device: name -> (score column, assignment rule of device.ASSIGN_RULES)
-SENSOR_AGENT_RULES = {'agent_info_gain_sensors': (_lib.LOOK_INFO_GAIN, 'greedy'), 'agent_trace_gain_sensors': (_lib.LOOK_TRACE_GAIN, 'greedy'),
-                      'agent_info_gain_sensors_optimal': (_lib.LOOK_INFO_GAIN, 'optimal'),
-                      'agent_trace_gain_sensors_optimal': (_lib.LOOK_TRACE_GAIN, 'optimal')}
-
-
-def sensor_agent_rule(agent):
-    """(score column, assignment rule) of a lookahead agent of a sensor network, given as the function of agents.py or its name;
-    anything else has no device form in a vector env (NotImplementedError).  Needs no device state."""
-    name = agent if isinstance(agent, str) else getattr(agent, '__name__', None)
-    if name not in SENSOR_AGENT_RULES:
-        raise NotImplementedError("step_agent: %r is not implemented; the agents of a sensor network that decide on the device are %s, "
-                                  "and with the optimal assignment %s"
-                                  % (agent, " and ".join(sorted(SENSOR_AGENTS)), " and ".join(sorted(set(SENSOR_AGENT_RULES) - set(SENSOR_AGENTS)))))
-    return SENSOR_AGENT_RULES[name]
-
-
-def sensor_agent_column(agent):
-    """the score column of sensor_agent_rule(agent)"""
-    return sensor_agent_rule(agent)[0]
 
 
 def check_fallback_actions(fallback, E, S):
@@ -459,49 +439,23 @@ class SSA_Tasker_VecEnv:
         """SSA_Tasker_Env.lookahead() of every env from ONE launch: the same dict with a leading [n_env] axis -- score [E, 3, m],
         visible / status [E, m], and with covariances=True x_prior [E, m, 6], P_prior / P_post [E, m, 6, 6]; objects in each env's own
         order.  Nothing of the envs changes; the next call overwrites the tensors."""
-        import torch
         from .. import engine as _engine
         if self.n_sensor > 1:
             raise NotImplementedError("lookahead: not implemented for a sensor network in a vector env (config['observers'] with %d "
                                       "sensors); use lookahead_sensors" % self.n_sensor)
-        if np.any(self.i + 1 >= self.n):
-            raise ValueError("lookahead: an env has no next step")
-        e = self._eng
+        words = env_time_words(self, "lookahead")
         want = _engine.HotPathEngine.LOOKAHEAD_PARTS if covariances else ()
-        times = [int(v) + 1 for v in self.i]
-        if self._inline:
-            r = e.launch_lookahead(self.tick % 2, 0, out=want, stream=self._stream.cuda_stream, env_times=times)
-        else:     # (the time words in device memory, as a step reads them; a synchronous copy: the pinned staging is the step's)
-            e.env_time0.copy_(torch.as_tensor(times, dtype=torch.int32))
-            r = e.launch_lookahead(self.tick % 2, 0, out=want)
-        E, m = self.E, self.m
-        res = {"score": r["score"].view(E, m, _lib.LOOK_NSCORE).permute(0, 2, 1), "visible": r["visible"].view(E, m),
-               "status": r["status"].view(E, m)}
-        shapes = {"x_prior": (E, m, 6), "P_prior": (E, m, 6, 6), "P_post": (E, m, 6, 6)}
-        for k in want:
-            res[k] = r[k].view(shapes[k])
-        return res
+        return lookahead_result(self._eng.launch_lookahead(self.tick % 2, 0, out=want, **words), want, envs=self.E)
 
     def _sites(self):
         """the sites of the envs as a network: their own; without config['observers'] the envs' one observer as a one-site block"""
-        if self._look_sites is None:
-            from .. import host
-            lla, lim, R = self._site
-            self._look_sites = self._sensors if self.n_sensor > 1 else host.make_sensor_params([lla], [lim], [R], 0)
-        return self._look_sites
+        return network_sites(self, *self._site)
 
     def _launch_lookahead_sensors(self, want=()):
-        """the network's lookahead of every env enqueued for the step each env takes next (time words by value up to 8 envs, through
-        env_time0 beyond); the engine's result dict"""
-        import torch
-        if np.any(self.i + 1 >= self.n):
-            raise ValueError("lookahead_sensors: an env has no next step")
-        e = self._eng
-        times = [int(v) + 1 for v in self.i]
-        if self._inline:
-            return e.launch_lookahead_sensors_envs(self.tick % 2, 0, self._sites(), out=want, stream=self._stream.cuda_stream, env_times=times)
-        e.env_time0.copy_(torch.as_tensor(times, dtype=torch.int32))      # (a synchronous copy: the pinned staging is the step's)
-        return e.launch_lookahead_sensors_envs(self.tick % 2, 0, self._sites(), out=want)
+        """the network's lookahead of every env enqueued for the step each env takes next (_tasking.env_time_words); the engine's
+        result dict"""
+        words = env_time_words(self, "lookahead_sensors")
+        return self._eng.launch_lookahead_sensors_envs(self.tick % 2, 0, self._sites(), out=want, **words)
 
     def lookahead_sensors(self, covariances=False):
         """SSA_Tasker_Env.lookahead_sensors() of every env from ONE launch (ssa_lookahead_sensors_envs_f64): the
@@ -511,27 +465,38 @@ class SSA_Tasker_VecEnv:
         the scores are the greedy baselines' gains.  Nothing of the envs changes; the next call overwrites the tensors."""
         from .. import engine as _engine
         want = _engine.HotPathEngine.LOOKAHEAD_PARTS if covariances else ()
-        r = self._launch_lookahead_sensors(want)
-        res = {"score": r["score"].permute(0, 1, 3, 2), "visible": r["visible"], "status": r["status"]}
-        for k in want:
-            res[k] = r[k]
-        return res
+        return lookahead_result(self._launch_lookahead_sensors(want), want)
 
     def _launch_forecast_sensors(self, horizon, want=()):
         """the network's H'-step forecast of every env enqueued from the step each env takes next, H' = min(horizon, the fewest steps
-        an env has left) (time words by value up to 8 envs, through env_time0 beyond); the engine's result dict, [H', E, ...]"""
-        import torch
+        an env has left) (_tasking.env_time_words); the engine's result dict, [H', E, ...]"""
         if int(horizon) < 1:
             raise ValueError("forecast_sensors: a horizon of at least one step, got %r" % (horizon,))
-        if np.any(self.i + 1 >= self.n):
-            raise ValueError("forecast_sensors: an env has no next step")
+        words = env_time_words(self, "forecast_sensors")
         H = min(int(horizon), int(self.n - 1 - self.i.max()))
-        e = self._eng
-        times = [int(v) + 1 for v in self.i]
-        if self._inline:
-            return e.launch_forecast_sensors_envs(self.tick % 2, 0, self._sites(), H, out=want, stream=self._stream.cuda_stream, env_times=times)
-        e.env_time0.copy_(torch.as_tensor(times, dtype=torch.int32))      # (a synchronous copy: the pinned staging is the step's)
-        return e.launch_forecast_sensors_envs(self.tick % 2, 0, self._sites(), H, out=want)
+        return self._eng.launch_forecast_sensors_envs(self.tick % 2, 0, self._sites(), H, out=want, **words)
+
+    # ---- what agents.py asks of an env beside its public queries (DESIGN.md section 8s; SSA_Tasker_Env answers the same four)
+    def _tasking_stream(self):
+        """the torch stream the planners' launches go in: the query launches' own (_tasking.env_time_words)"""
+        import torch
+        return self._stream if self._inline else torch.cuda.current_stream()
+
+    def _forecast_scores(self, horizon):
+        """the forecast's scores as the engine leaves them, [H', E, S, m, 3] (contiguous; slab h of all envs is score[h])"""
+        return self._launch_forecast_sensors(horizon)["score"]
+
+    def _slab_assigner(self, score):
+        """assign(slab [E, S, m, 3], column, row [E, MAX_SENSORS], rule): every env's assignment of one slab into a row of the planner's
+        own, one launch in torch's current stream (device.assign_sensors_envs) with ONE workspace of the planner's own for all calls"""
+        from .. import device
+        E, S, m = (int(v) for v in score.shape[1:4])
+        ws = device.assign_sensors_envs_workspace(m, S, E, score.device)
+        return lambda slab, column, row, rule: device.assign_sensors_envs(slab, column, out=row, workspace=ws, rule=rule)
+
+    def _plan_table(self, horizon, column):
+        """the forecast's launch and the horizon-wide plan's (ssa_plan_sensors_f64) on it: the engine's int32 table [H', E, MAX_SENSORS]"""
+        return self._eng.launch_plan_sensors(self._launch_forecast_sensors(horizon), column, stream=self._tasking_stream().cuda_stream)
 
     def forecast_sensors(self, horizon, covariances=False):
         """SSA_Tasker_Env.forecast_sensors() of every env from ONE launch (ssa_forecast_sensors_envs_f64): from
@@ -566,41 +531,27 @@ class SSA_Tasker_VecEnv:
             total   [E, B, 3] float64: the sum of the taken slots' scores per column, in slot order (k outer, s inner); 0 for none
         Nothing of the envs changes: no engine tensor, not i, tick, the bookkeeping or a generator; any rso_count (the gathered block
         has whole tiles).  The next call with the same shapes overwrites the tensors."""
-        import torch
-        from .. import device
         if self._eng is None:
             raise _lib.SsaHipError("no device state: the dry run of a schedule runs on the GPU only (no CPU fallback)")
-        E, S = self.E, self.n_sensor
-        a = actions.detach().cpu().numpy() if isinstance(actions, torch.Tensor) else np.asarray(actions)
-        if a.ndim == 3:
-            a = a[:, None]
-        if a.ndim != 4 or a.shape[0] != E or a.shape[1] < 1 or a.shape[3] != S or a.dtype.kind not in "iu":
-            raise ValueError("evaluate_schedules: integer schedules [%d, K, %d] or [%d, B, K, %d], got %s %s" % (E, S, E, S, a.dtype, a.shape))
+        a = check_schedules(actions, self.n_sensor, envs=self.E)
         K = min(int(a.shape[2]), int(self.n - 1 - self.i.max()))
         if K < 1:
             raise ValueError("evaluate_schedules: at least one step inside every env's episode (i = %s, steps = %d, K = %d)"
                              % (self.i.tolist(), self.n, a.shape[2]))
-        B = int(a.shape[1])
         rec = self._eng.launch_dryrun_sensors_envs(self.tick % 2, 0, self._sites(), a[:, :, :K], stream=self._stream,
                                                    env_times=[int(v) + 1 for v in self.i])
-        with torch.cuda.stream(self._stream):
-            # (the engine's [K', E * B, S, 8] block; slot order: one defined fp64 sum per candidate)
-            total = device.dryrun_totals(rec.permute(2, 0, 1, 3, 4).reshape(K, E * B, S, _lib.DRY_STRIDE)).view(E, B, _lib.LOOK_NSCORE)
-            return {"score": rec[..., _lib.DRY_SCORE:_lib.DRY_SCORE + _lib.LOOK_NSCORE], "taken": rec[..., _lib.DRY_TAKEN] != 0,
-                    "visible": rec[..., _lib.DRY_VISIBLE] != 0, "status": rec[..., _lib.DRY_STATUS].to(torch.int32),
-                    "action": rec[..., _lib.DRY_ACTION].to(torch.int64), "total": total}
+        return schedules_result(rec, self._stream)
 
     def assign_sensors(self, column, rule='greedy'):
         """the lookahead of every env and every env's assignment over score column `column` (_lib.LOOK_*) by `rule` ('greedy', or
         'optimal': most sensors tasked, then the largest sum): two launches and one read-back of E x 32 bytes.  int64 [E, S]; -1: the
         scores left that sensor without an object.  Nothing of the envs changes."""
-        import torch
         from .. import device
         device.assign_entry(rule)                     # (an unknown rule: refused before anything is launched)
         if self._eng is None:
             raise _lib.SsaHipError("no device state: the assignment comes from the lookahead, which runs on the GPU only (no CPU fallback)")
         look = self._launch_lookahead_sensors()
-        cur = self._stream if self._inline else torch.cuda.current_stream()
+        cur = self._tasking_stream()
         table = self._eng.launch_assign_sensors_envs(look, column, stream=cur.cuda_stream, rule=rule)
         cur.synchronize()
         return table.cpu().numpy()[:, :self.n_sensor].astype(np.int64)

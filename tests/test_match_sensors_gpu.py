@@ -526,7 +526,7 @@ def test_plans_with_the_optimal_rule(envs, hip):
     E, S, m = 3, 3, 8
     vec = SSA_Tasker_VecEnv(cfg3(envs, m=m, steps=12, update_interval=1, sensor_obs_limit=[-89.0, -89.0, -89.0]), E, seed=10)
     vec.step(np.stack([rs.permutation(m)[:S] for _ in range(E)]))
-    raw = agents._plan_assigned_envs(vec, 4, col, "optimal")              # [E, H', S]
+    raw = agents._plan_assigned(vec, 4, col, "optimal")              # [E, H', S]
     score = vec._launch_forecast_sensors(4)["score"]
     torch.cuda.synchronize()
     score = score.cpu().numpy()                                           # [H', E, S, m, 3]

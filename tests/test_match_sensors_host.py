@@ -121,11 +121,11 @@ def test_new_agent_names_resolve_before_the_engine_is_touched():
     from ssa_gym_amd.envs import vector_env as V
     from ssa_gym_amd.envs.ssa_tasker_simple_2 import SSA_Tasker_Env
     old = {'agent_info_gain_sensors': _lib.LOOK_INFO_GAIN, 'agent_trace_gain_sensors': _lib.LOOK_TRACE_GAIN}
-    assert SSA_Tasker_Env.SENSOR_AGENT_COLUMNS == old and V.SENSOR_AGENTS == old
+    assert SSA_Tasker_Env.SENSOR_AGENT_COLUMNS == old and V.SENSOR_AGENTS is SSA_Tasker_Env.SENSOR_AGENT_COLUMNS      # (one table, two names)
     want = {'agent_info_gain_sensors': (_lib.LOOK_INFO_GAIN, 'greedy'), 'agent_trace_gain_sensors': (_lib.LOOK_TRACE_GAIN, 'greedy'),
             'agent_info_gain_sensors_optimal': (_lib.LOOK_INFO_GAIN, 'optimal'),
             'agent_trace_gain_sensors_optimal': (_lib.LOOK_TRACE_GAIN, 'optimal')}
-    assert SSA_Tasker_Env.SENSOR_AGENT_RULES == want and V.SENSOR_AGENT_RULES == want
+    assert SSA_Tasker_Env.SENSOR_AGENT_RULES == want and V.SENSOR_AGENT_RULES is SSA_Tasker_Env.SENSOR_AGENT_RULES
     for name, (col, rule) in want.items():
         fn = getattr(agents, name)
         assert V.sensor_agent_rule(fn) == V.sensor_agent_rule(name) == (col, rule)

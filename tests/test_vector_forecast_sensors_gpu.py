@@ -322,7 +322,7 @@ def test_vector_planners_follow_the_rule(envs, sky):
     fc = _np_env(vec.forecast_sensors(H))
     table = vec._eng.action_table().clone()
     for planner, col in ((agents.plan_info_gain_sensors, _lib.LOOK_INFO_GAIN), (agents.plan_trace_gain_sensors, _lib.LOOK_TRACE_GAIN)):
-        raw = agents._plan_assigned_envs(vec, H, col)
+        raw = agents._plan_assigned(vec, H, col)
         assert raw.shape == (E, H, S) and raw.dtype == np.int64
         want = plan_np(fc["score"][..., col])
         assert np.array_equal(raw, want), (sky, col, raw, want)
@@ -357,8 +357,8 @@ def test_forecast_against_execution(envs):
     for _ in range(2):
         vec.step(_actions(rs, E, S, m))
     fc = _np_env(vec.forecast_sensors(H, covariances=True))
-    raw = agents._plan_assigned_envs(vec, H, _lib.LOOK_INFO_GAIN)
-    plan = agents._fill_plan_envs(vec, raw)
+    raw = agents._plan_assigned(vec, H, _lib.LOOK_INFO_GAIN)
+    plan = agents._fill_plan(vec, raw)
     taken = 0
     for h in range(H):
         _, _, done, _ = vec.step(plan[:, h])

@@ -11,6 +11,7 @@ import pytest
 from support.codeobj import KERNEL_FAMILIES, _kernels, assert_family_budget, header
 from support.gpu import lib  # noqa: F401  (the module fixture)
 from support.refusals import LOOK_PTRS, OUT_PTRS, bad_rk4, nan_mask, refused, valid_blocks
+from support.vector_dryrun import StubVecEnv
 from support.vector_forecast import bare_vec
 
 
@@ -110,7 +111,7 @@ def test_planner_fills_unassigned_entries_per_env_on_the_host():
     vec = bare_vec(3, E=3, m=10, seed=1)
     vec._rng = [np.random.RandomState(7 + e) for e in range(3)]
     states = [r.get_state()[2] for r in vec._rng]
-    plan = agents._fill_plan_envs(vec, raw)
+    plan = agents._fill_plan(vec, raw)
     assert states == [r.get_state()[2] for r in vec._rng]
     assert plan.dtype == np.int64 and plan.shape == raw.shape
     assert np.array_equal(plan[raw >= 0], raw[raw >= 0]) and (raw[0, 1] == -1).all()      # (the caller's array is not written)
@@ -119,11 +120,13 @@ def test_planner_fills_unassigned_entries_per_env_on_the_host():
     twin = bare_vec(3, E=3, m=10, seed=1)
     want = np.stack([agents._fill_plan(twin, raw[e]) for e in range(3)])
     assert np.array_equal(plan, want)
-    for bad in (raw[0], raw[:2], raw.reshape(-1)):                                        # not [E, H', S]
+    for bad in (raw[:2], raw.reshape(-1), raw[None]):                                     # neither [E, H', S] nor one env's [H', S]
         with pytest.raises(ValueError):
-            agents._fill_plan_envs(vec, bad)
+            agents._fill_plan(vec, bad)
+    with pytest.raises(ValueError, match="a plan"):                                       # (one env's rows where every env's plan enters)
+        agents.refine_plan_sensors(StubVecEnv(E=3, m=10, S=3), raw[0])
     with pytest.raises(ValueError):                                                       # more sensors than objects
-        agents._fill_plan_envs(bare_vec(3, E=1, m=2), np.array([[[0, 1, -1]]]))
+        agents._fill_plan(bare_vec(3, E=1, m=2), np.array([[[0, 1, -1]]]))
 
 
 def test_new_kernels_keep_the_forecast_kernels_budget(tmp_path):
