@@ -541,6 +541,114 @@ SSA_DEV void covariance_reference(Tiles& t, const ssa_consts& C, int lane, const
     }
 }
 
+// U3 with SSA_FLAG_REFERENCE_COV in the plain family (step_plain_kernel): ONE tile feeds both matrix passes.  The two tiles above -- the rows
+// [sigma_i' - sigma_0', 1, 0] of t.D and the rows [sigma_i' - x, 0, 0] of Y -- are the same thirteen propagated points minus a vector every
+// lane can fetch, each written once (behind six row broadcasts, and Y behind a fence of its own) and read once.  Here lanes 0 .. 12 of a row
+// write their point as it left the propagator, rows of 8 doubles [sigma_i'[0..5], -, -] in the factor tile + D (contiguous and free by
+// then), and each pass subtracts in the matrix unit's operand layout: the same IEEE subtraction on the same operands as the row layout's,
+// so the same bits -- d_i = sigma_i' - sigma_0' with one rounding, y_i = sigma_i' - x with one rounding (forming y_i from d_i would take two,
+// and fail other filters than the reference does).  The two pad words of a row are never written and no lane reads one as a value that is
+// used: the lanes lo >= 2 read them as components "6, 7", which reach rows / columns >= 6 of the 8 x 8 result only -- a NaN there touches
+// nothing that is stored.
+SSA_DEV int sbase(int g) { return g * 104 + (g & 1) * 28 + (g >> 1) * 32; }   // 0, 132, 240, 372: bank slots as dbase() / ybase()
+static_assert(372 + 13 * 8 <= OBJ_PER_WAVE * 36 + 408, "the rows of sigma points fit the factor tile + D");
+SSA_DEV void sigma_rows_write(Tiles& t, int g, int l, const double (&o)[6])
+{
+    typedef double v2d_t __attribute__((ext_vector_type(2)));
+    if (l <= 12) {
+        v2d_t* dst = reinterpret_cast<v2d_t*>(&t.UA[sbase(g) + l * 8]);
+        dst[0] = v2d_t{o[0], o[1]};
+        dst[1] = v2d_t{o[2], o[3]};
+        dst[2] = v2d_t{o[4], o[5]};
+    }
+    if (l == 0 || l == 13) {   // sigma_0' (until the mean replaces it) | x_true[i]
+        v2d_t* dst = reinterpret_cast<v2d_t*>(l == 0 ? &t.X[g * 6] : &t.T[g * 6]);
+        dst[0] = v2d_t{o[0], o[1]};
+        dst[1] = v2d_t{o[2], o[3]};
+        dst[2] = v2d_t{o[4], o[5]};
+    }
+}
+// the first pass, moment_sums_mfma<true> from the rows above: t.M[mid][a] = sum_{i = 1 .. 12} (sigma_i'[a] - sigma_0'[a]).  The column of
+// ones is a register constant of the right operand (1.0 in the lanes lo == 2): the products d x 1.0 and the zeros added to them are exact,
+// and the sums leave column 2 of both blocks as they left column 6 of the 8 x 8 result.
+SSA_DEV void moment_sums_rows(Tiles& t, int lane)
+{
+    const int hi = lane >> 4, mid = (lane >> 2) & 3, lo = lane & 3;
+    const double* src = &t.UA[sbase(mid) + hi * 8 + lo];
+    const double* s0 = &t.UA[sbase(mid) + lo];       // sigma_0'
+    const double z0 = s0[0], z1 = s0[4];
+    double a0[3], a1[3];
+#pragma unroll
+    for (int kc = 0; kc < 3; ++kc) {                 // rows 4 kc + hi + 1
+        a0[kc] = src[8 + kc * 32];
+        a1[kc] = src[8 + kc * 32 + 4];
+    }
+    const double one = (lo == 2) ? 1.0 : 0.0;
+    double c01 = 0.0, c11 = 0.0;
+#pragma unroll
+    for (int kc = 0; kc < 3; ++kc) {
+        const double d0 = a0[kc] - z0, d1 = a1[kc] - z1;
+        c01 = __builtin_amdgcn_mfma_f64_4x4x4f64(d0, one, c01, 0, 0, 0);
+        c11 = __builtin_amdgcn_mfma_f64_4x4x4f64(d1, one, c11, 0, 0, 0);
+    }
+    if (lo == 2) {
+        t.M[mid * 12 + hi] = c01;
+        if (hi < 2) t.M[mid * 12 + 4 + hi] = c11;
+    }
+}
+// the second pass, covariance_reference from the same rows: behind the mean (t.X holds x), y = sigma_i' - x formed in the operand layout, rows
+// 4 kc + hi; the weights on the right operand, the three k-chunks and the three vector fmas of point 12 as they are above -- the accumulation
+// order i = 0 .. 12 is unchanged.  No row broadcasts, no second tile and no fence of its own: the rows are as old as the first pass, the mean sits behind the caller's.
+SSA_DEV void covariance_reference_rows(Tiles& t, const ssa_consts& C, int lane)
+{
+    const int hi = lane >> 4, mid = (lane >> 2) & 3, lo = lane & 3;
+    const double* src = &t.UA[sbase(mid) + hi * 8 + lo];
+    const double* r12 = &t.UA[sbase(mid) + 12 * 8];
+    const double* xb = &t.X[mid * 6];                // (components "6, 7" of the lanes lo / hi >= 2: the next object's words or pad1, unused)
+    // every read of the tile and of the mean, then one wait
+    double a0[3], a1[3];
+#pragma unroll
+    for (int kc = 0; kc < 3; ++kc) {
+        a0[kc] = src[kc * 32];
+        a1[kc] = src[kc * 32 + 4];
+    }
+    const double x_lo = xb[lo], x_lo4 = xb[4 + lo], x_hi = xb[hi], x_hi4 = xb[4 + hi];
+    const double s_lo = r12[lo], s_lo4 = r12[4 + lo], s_hi = r12[hi], s_hi4 = r12[4 + hi];
+    Moments mo = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int kc = 0; kc < 3; ++kc) {
+        const double y0 = a0[kc] - x_lo, y1 = a1[kc] - x_lo4;
+        const double w = (kc == 0 && hi == 0) ? C.Wc0 : C.Wi;
+        const double b0 = w * y0, b1 = w * y1;
+        mo.c00 = __builtin_amdgcn_mfma_f64_4x4x4f64(y0, b0, mo.c00, 0, 0, 0);
+        mo.c01 = __builtin_amdgcn_mfma_f64_4x4x4f64(y0, b1, mo.c01, 0, 0, 0);
+        mo.c11 = __builtin_amdgcn_mfma_f64_4x4x4f64(y1, b1, mo.c11, 0, 0, 0);
+    }
+    {   // point 12 (see covariance_reference)
+        const double ai = s_hi - x_hi, ai4 = s_hi4 - x_hi4, bj = C.Wi * (s_lo - x_lo), bj4 = C.Wi * (s_lo4 - x_lo4);
+        mo.c00 = fma(ai, bj, mo.c00);
+        mo.c01 = fma(ai, bj4, mo.c01);
+        mo.c11 = fma(ai4, bj4, mo.c11);
+    }
+    const int hi1 = hi & 1, lo1 = lo & 1;
+    double* P = &t.P[mid * 36];
+    const double p00 = mo.c00 + t.Q[hi * 6 + lo];
+    const double p01 = mo.c01 + t.Q[hi * 6 + 4 + lo1];
+    const double p11 = mo.c11 + t.Q[(4 + hi1) * 6 + 4 + lo1];
+    if (hi <= lo) {
+        P[hi * 6 + lo] = p00;
+        P[lo * 6 + hi] = p00;
+    }
+    if (lo < 2) {
+        P[hi * 6 + 4 + lo] = p01;
+        P[(4 + lo) * 6 + hi] = p01;
+        if (hi <= lo) {
+            P[(4 + hi) * 6 + 4 + lo] = p11;
+            P[(4 + lo) * 6 + 4 + hi] = p11;
+        }
+    }
+}
+
 // U2 (common case): upper Cholesky of scale*P for the row's object, lane-distributed: lane c owns column c of the factor in
 // registers; step j (LAPACK dpotf2('U') order) needs column j's finished entries U[i][j], i < j, and the pivot -- all held
 // by lane j -- in every lane, which is one v_mov_b64_dpp row_newbcast:j each (21 per factorisation, no LDS round trip, no
@@ -1833,7 +1941,11 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // ---- U3: unscented transform, centred form of x = dot(Wm, sigmas_f):
     //   x = sigma_0' + m',   m' = (sum(Wm) - 1) sigma_0' + Wi sum_{i>=1} (sigma_i' - sigma_0')
     // (the reference's sum evaluated without the 1e8-fold cancellation of Wm0 ~ -2e8)
-    {
+    // (the plain family with SSA_FLAG_REFERENCE_COV: one tile of the points themselves feeds both matrix passes, see sigma_rows_write)
+    const bool rows_form = PLAIN && (C.flags & SSA_FLAG_REFERENCE_COV);   // (wave-uniform; false at compile time outside the plain family)
+    if (rows_form) {
+        sigma_rows_write(t, g, l, o);
+    } else {
         typedef double v2d_t __attribute__((ext_vector_type(2)));
         double d[6];
 #pragma unroll
@@ -1853,7 +1965,8 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     }
     wave_lds_sync();
     Moments mo = {0.0, 0.0, 0.0};
-    if (C.flags & SSA_FLAG_REFERENCE_COV) mo = moment_sums_mfma<true>(t, lane);   // (wave-uniform branch: the sums alone, six matrix instructions)
+    if (rows_form) moment_sums_rows(t, lane);
+    else if (!PLAIN && (C.flags & SSA_FLAG_REFERENCE_COV)) mo = moment_sums_mfma<true>(t, lane);   // (wave-uniform branch: the sums alone, six matrix instructions)
     else mo = moment_sums_mfma(t, lane);
     wave_lds_sync();
     double xb_l = 0.0;   // lanes 0..5: component l of the prior mean
@@ -1868,7 +1981,8 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     }
     const bool nan_x = ((__ballot(l < 6 && xb_l != xb_l) >> (g * 16)) & 0xFFFFull) != 0;
     wave_lds_sync();
-    if (C.flags & SSA_FLAG_REFERENCE_COV) covariance_reference(t, C, lane, o, xb_l);   // (wave-uniform branch)
+    if (rows_form) covariance_reference_rows(t, C, lane);
+    else if (!PLAIN && (C.flags & SSA_FLAG_REFERENCE_COV)) covariance_reference(t, C, lane, o, xb_l);   // (wave-uniform branch)
     else covariance_finish(t, C, lane, mo);
     wave_lds_sync();
 
