@@ -671,6 +671,52 @@ SSA_DEV void chol_step(const double (&a)[6], double (&uc)[6], int lc, bool& ok)
     if (J == 5) ok = ok && (y > 0.0) && (y <= 1.79769313486231570e308);
     uc[J] = (lc >= J) ? v * y : 0.0;              // lane J: ajj / sqrt(ajj) = the diagonal entry
 }
+// ---- The factorisation in the plain family (step_plain_kernel; FUSED, set by process_wave<.., ActPlain> alone).  The same operations on the
+// same operands in the same order per entry -- the same bits -- with three things taken off the vector unit:
+//  * the row broadcast of U[i][J] and the fused multiply-add that consumes it are ONE instruction, v_fmac_f64_dpp with the negated DPP source
+//    (the compiler does not form it: the negation selects the three-address fma before its DPP combiner runs).  The loop runs RIGHT-looking
+//    for it: as soon as row I of the factor exists, A[J][c] -= U[I][J] U[I][c] for every J > I, each accumulator still taking its terms in
+//    the order I = 0 .. J - 1.  The six pivot broadcasts feed a v_mul_f64, which has no DPP form, and stay moves.
+//  * no select per step: the lanes lc < J keep what the arithmetic leaves there.  No later step reads it (row_bcast<J'>(uc[i]) reads lane
+//    J' > i, the last pivot's test reads lane 5); the factor tile's lower triangle is zeroed where the rows are stored (chol_store_rows_zeroed).
+//  * the verdicts are wavefront masks in scalar registers from the compares on (chol_row_regs_fused).
+// Wait states.  The hazard recogniser does not look inside an asm statement; a DPP instruction must not read a VGPR that a vector
+// instruction wrote less than 2 wait states before it, and the compiler applies the rule to every VGPR operand, the accumulator included.
+//  (a) uc[I], the DPP source, may be the instruction in front of the statement (v * y): the statement opens with s_nop 1, which is the
+//      2 wait states for it and for anything else the compiler placed there (the first statement's accumulators, scale * pv).
+//  (b) inside a statement every instruction has an accumulator of its own and none writes uc[I].
+//  (c) the accumulators a statement writes are next read by a DPP instruction in the NEXT statement, which needs y of the next pivot: the
+//      refined reciprocal square root of one of them, eight vector instructions at the least, lies in between by data dependence.
+#define SSA_FMAC_BCAST(J) "v_fmac_f64_dpp %[v" #J "], -%[u], %[u] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
+template <int I>
+SSA_DEV void chol_row_update(double u, double (&v)[6])   // v[J] = fma(-row_bcast<J>(u), u, v[J]), J = I + 1 .. 5; u = uc[I]
+{
+    static_assert(I >= 0 && I < 5, "rows 0 .. 4 of the factor");
+    if constexpr (I == 0)
+        asm volatile("s_nop 1\n\t" SSA_FMAC_BCAST(1) SSA_FMAC_BCAST(2) SSA_FMAC_BCAST(3) SSA_FMAC_BCAST(4) SSA_FMAC_BCAST(5)
+                     : [v1] "+v"(v[1]), [v2] "+v"(v[2]), [v3] "+v"(v[3]), [v4] "+v"(v[4]), [v5] "+v"(v[5]) : [u] "v"(u));
+    else if constexpr (I == 1)
+        asm volatile("s_nop 1\n\t" SSA_FMAC_BCAST(2) SSA_FMAC_BCAST(3) SSA_FMAC_BCAST(4) SSA_FMAC_BCAST(5)
+                     : [v2] "+v"(v[2]), [v3] "+v"(v[3]), [v4] "+v"(v[4]), [v5] "+v"(v[5]) : [u] "v"(u));
+    else if constexpr (I == 2)
+        asm volatile("s_nop 1\n\t" SSA_FMAC_BCAST(3) SSA_FMAC_BCAST(4) SSA_FMAC_BCAST(5)
+                     : [v3] "+v"(v[3]), [v4] "+v"(v[4]), [v5] "+v"(v[5]) : [u] "v"(u));
+    else if constexpr (I == 3)
+        asm volatile("s_nop 1\n\t" SSA_FMAC_BCAST(4) SSA_FMAC_BCAST(5) : [v4] "+v"(v[4]), [v5] "+v"(v[5]) : [u] "v"(u));
+    else
+        asm volatile("s_nop 1\n\t" SSA_FMAC_BCAST(5) : [v5] "+v"(v[5]) : [u] "v"(u));
+}
+#undef SSA_FMAC_BCAST
+// step J of the FUSED form: v[J] arrives finished (chol_row_update<0 .. J - 1>); row J of the factor, then its terms into the rows below
+template <int J>
+SSA_DEV void chol_step_fused(double (&v)[6], double (&uc)[6], unsigned long long& bad)
+{
+    const double y = row_bcast<J>(rsqrt_nr(v[J]));   // as chol_step: NaN / inf when the pivot is <= 0 or NaN, and it poisons what follows
+    if constexpr (J == 5)   // (y is row-uniform: so are the bits; one ballot per compare, see chol_row_regs_fused)
+        bad |= __builtin_amdgcn_ballot_w64(!(y > 0.0)) | __builtin_amdgcn_ballot_w64(!(y <= 1.79769313486231570e308));
+    uc[J] = v[J] * y;                                // (lanes lc < J: not an entry of the factor, see above)
+    if constexpr (J < 5) chol_row_update<J>(uc[J], v);
+}
 // One entry of the matrix a rung factorises, in the REFERENCE's two roundings: sigma_points() hands robust_cholesky the product
 // (n + lambda) P already rounded, and the ladder adds its jitter to that (dynamics.py:410: cholesky(a + e)).  Written out with an
 // optimisation barrier between the two: under -ffp-contract=fast the compiler fused scale * p + jit into one fma at some call sites and -- where it could
@@ -716,6 +762,59 @@ SSA_DEV void chol_store_rows(double* Ug, const double (&uc)[6], int l)
         for (int j = 0; j < 6; ++j) Ug[j * 6 + l] = uc[j];
     }
 }
+// the lanes of every row whose bit is set in `m16`, as a condition: the wavefront mask is a scalar constant, no lane compares its index
+SSA_DEV bool row_lanes(unsigned long long m16) { return __builtin_amdgcn_inverse_ballot_w64(m16 * 0x0001000100010001ull); }
+// chol_row_regs in the FUSED form (chol_step_fused).  Returns the wavefront's FAILED lanes, whole rows of them, as a scalar mask: what
+// __ballot(!ok) is of chol_row_regs' answer.  scipy's check_finite: lanes 0 .. 5 of a row see its 36 entries between them; their six bits
+// of the compares' ballot decide the row (lanes 6 .. 15 repeat lane 5).  Per 16-bit field: bit 15 of (bits + 0x7fff) is "some bit is set"
+// -- the sum stays inside the field -- and h | (h - (h >> 15)) fills the field from it.
+template <bool PLAIN>
+SSA_DEV unsigned long long chol_row_regs_fused(const double* Pg, double scale, double jit, int l, double (&uc)[6])
+{
+    const int lc = l < 6 ? l : 5;
+    double a[6];
+    unsigned long long nf = 0ull;   // (one ballot per compare, joined as scalars: the ballot of a joined condition goes through a select and a compare)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const double pv = Pg[j * 6 + lc];
+        nf |= __builtin_amdgcn_ballot_w64(!(fabs(pv) <= 1.79769313486231570e308));
+        a[j] = (PLAIN || lc != j) ? scale * pv : scaled_entry(scale, pv, jit);
+    }
+    nf &= 0x003F003F003F003Full;
+    const unsigned long long h = (nf + 0x7FFF7FFF7FFF7FFFull) & 0x8000800080008000ull;
+    unsigned long long bad = h | (h - (h >> 15));
+    chol_step_fused<0>(a, uc, bad);
+    chol_step_fused<1>(a, uc, bad);
+    chol_step_fused<2>(a, uc, bad);
+    chol_step_fused<3>(a, uc, bad);
+    chol_step_fused<4>(a, uc, bad);
+    chol_step_fused<5>(a, uc, bad);
+    return bad;
+}
+// chol_store_rows for the FUSED form, whose lanes l < j hold no zeros in uc[j]: the six rows as they are, then +0.0 over the fifteen
+// entries (j, c < j) of the strictly lower triangle, by lanes of the same address &Ug[l] through two more two-address writes -- entry
+// 6 j + c is l + 6 / l + 18 for l in {0, 6, 7, 12, 13, 14}, l + 26 / l + 33 for l in {0, 1}: all fifteen, each inside the block, none on
+// or above the diagonal.  A wavefront's LDS writes land in issue order, so the zeros replace what the first three writes left there.
+// (Every step: the transform and the update use the factor tile as scratch.)
+SSA_DEV void chol_store_rows_zeroed(double* Ug, const double (&uc)[6], int l)
+{
+    double* col = Ug + l;
+    if (row_lanes(0x003Full)) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) col[j * 6] = uc[j];
+    }
+    wave_lds_sync();   // (the order ACROSS lanes: to the compiler col[6] of one lane and col[12] of another are unrelated)
+    double z = 0.0;
+    SSA_OPAQUE(z);     // (one register pair for both writes)
+    if (row_lanes(0x70C1ull)) {
+        col[6] = z;
+        col[18] = z;
+    }
+    if (row_lanes(0x0003ull)) {
+        col[26] = z;
+        col[33] = z;
+    }
+}
 
 // robust_cholesky (dynamics.py:402-417) for the four objects of the wavefront: plain attempt, then a + 10^i I for
 // i = -6..9 (first success wins); returns the calling row's -1, 0..15, or 16 (LinAlgError).
@@ -751,16 +850,26 @@ SSA_DEV bool chol_lane_ok(const double* Pg, double scale, double jit)
     }
     return (y > 0.0) && (y <= 1.79769313486231570e308);
 }
+template <bool FUSED = false>   // FUSED: the plain family's factorisation (chol_step_fused), the first attempt and the winning rung's both
 SSA_DEV int robust_chol_row_lds(Tiles& t, double scale, int g, int l)
 {
     double uc[6];
     int rung = 16;
-    const bool ok = chol_row_regs<true>(&t.P[g * 36], scale, 0.0, g, l, uc);
-    if (ok) {
-        chol_store_rows(&t.UA[g * 36], uc, l);
-        rung = -1;
+    unsigned long long bad;
+    if constexpr (FUSED) {
+        bad = chol_row_regs_fused<true>(&t.P[g * 36], scale, 0.0, l, uc);
+        if (!__builtin_amdgcn_inverse_ballot_w64(bad)) {
+            chol_store_rows_zeroed(&t.UA[g * 36], uc, l);
+            rung = -1;
+        }
+    } else {
+        const bool ok = chol_row_regs<true>(&t.P[g * 36], scale, 0.0, g, l, uc);
+        if (ok) {
+            chol_store_rows(&t.UA[g * 36], uc, l);
+            rung = -1;
+        }
+        bad = __ballot(!ok);
     }
-    const unsigned long long bad = __ballot(!ok);
     wave_lds_sync();
     if (bad == 0ull) return rung;                  // the common case, wave-uniform
     __builtin_amdgcn_s_setprio(3);                 // a straggler in the making: issue priority for the rest of its life
@@ -787,8 +896,13 @@ SSA_DEV int robust_chol_row_lds(Tiles& t, double scale, int g, int l)
         if (won != 0u) {
             rung = __ffs((int)won) - 1;
             const double jw = __shfl(jit, g * 16 + rung, 64);            // the winning rung's jitter, from the lane that tried it
-            chol_row_regs<false>(Pg, scale, jw, g, l, uc);               // (succeeds: the same arithmetic said so)
-            chol_store_rows(&t.UA[g * 36], uc, l);
+            if constexpr (FUSED) {                                       // (succeeds: the same arithmetic said so)
+                chol_row_regs_fused<false>(Pg, scale, jw, l, uc);
+                chol_store_rows_zeroed(&t.UA[g * 36], uc, l);
+            } else {
+                chol_row_regs<false>(Pg, scale, jw, g, l, uc);
+                chol_store_rows(&t.UA[g * 36], uc, l);
+            }
         }
     }
     wave_lds_sync();
@@ -1836,7 +1950,7 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     const bool active = valid && st_in == SSA_ST_OK;
 
     // ---- U1/U2: sigma points
-    const int rung = robust_chol_row_lds(t, C.scale, g, l);
+    const int rung = robust_chol_row_lds<PLAIN>(t, C.scale, g, l);   // (PLAIN: the fused form, chol_step_fused)
     asrc.mid_step(t, lane);   // (closed loop: the PREVIOUS step's tile leaves for HBM now, its last reader of t.Obs)
     if (may_update && l < 12) t.Obs[g * 12 + l] = upd_in;
     wave_lds_sync();
