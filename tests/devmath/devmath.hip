@@ -56,6 +56,16 @@ __global__ void k_propagate(const double* x, int64_t n, double dt, double* out, 
     const bool h = PROP == 1 ? ssa::kepler_fg_fast<0>(s, dt, o) : ssa::kepler_elements_fast(s, dt, o);
     if (ok) { store6(out, i, o); okf[i] = h; }
 }
+// SSA_PROP_J2_RK4 (propagate_j2_rk4): nsub RK4 sub-steps under (j2, r_eq); ok = its return value
+__global__ void k_propagate_j2(const double* x, int64_t n, double dt, ssa::J2Params q, double* out, int32_t* okf)
+{
+    bool ok;
+    const int64_t i = item(n, ok);
+    double s[6], o[6];
+    load6(x, i, s);
+    const bool h = ssa::propagate_j2_rk4(s, dt, q, o);
+    if (ok) { store6(out, i, o); okf[i] = h; }
+}
 __global__ void k_uv_fast(const double* x, int64_t n, double dt, double* out, int32_t* handled)
 {
     bool ok;
@@ -168,6 +178,12 @@ int dm_propagate(const double* x, int64_t n, double dt, int32_t prop, double* ou
     if (prop == 1) DM_LAUNCH(k_propagate<1>, x, n, dt, out, ok);
     if (prop == 0) DM_LAUNCH(k_propagate<0>, x, n, dt, out, ok);
     return -1;
+}
+int dm_propagate_j2(const double* x, int64_t n, double dt, double j2, double r_eq, int32_t nsub, double* out, int32_t* ok, void* stream)
+{
+    if (nsub < 1) return -1;
+    const ssa::J2Params q = {j2, r_eq, nsub};
+    DM_LAUNCH(k_propagate_j2, x, n, dt, q, out, ok);
 }
 int dm_uv_fast(const double* x, int64_t n, double dt, double* out, int32_t* handled, void* stream) { DM_LAUNCH(k_uv_fast, x, n, dt, out, handled); }
 int dm_uv_general(const double* x, int64_t n, double dt, double* out, int32_t* ok, void* stream) { DM_LAUNCH(k_uv_general, x, n, dt, out, ok); }

@@ -16,6 +16,12 @@ void hm_propagate(const double* x, long n, double dt, int prop, double* out, int
     for (long i = 0; i < n; ++i)
         ok[i] = prop == 1 ? ssa::kepler_fg_fast<0>(x + 6 * i, dt, out + 6 * i) : ssa::kepler_elements_fast(x + 6 * i, dt, out + 6 * i);
 }
+// SSA_PROP_J2_RK4 (propagate_j2_rk4): nsub RK4 sub-steps under (j2, r_eq); ok[i] = its return value
+void hm_propagate_j2(const double* x, long n, double dt, double j2, double r_eq, int nsub, double* out, int* ok)
+{
+    const ssa::J2Params q = {j2, r_eq, nsub};
+    for (long i = 0; i < n; ++i) ok[i] = ssa::propagate_j2_rk4(x + 6 * i, dt, q, out + 6 * i);
+}
 void hm_uv_fast(const double* x, long n, double dt, double* out, int* handled)
 {
     for (long i = 0; i < n; ++i) { bool h; ssa::kepler_uv_fast(x + 6 * i, dt, out + 6 * i, h); handled[i] = h; }

@@ -1,6 +1,8 @@
 """The device-math probe's build and the test bodies that run on both backends: tests/test_device_math_host.py hands them HostMath
 (tests/hostmath, on the CPU), tests/test_device_math_gpu.py DeviceMath (tests/devmath, on the device) -- same bodies, same bounds."""
+import ctypes as C
 import os
+import subprocess
 
 import numpy as np
 
@@ -22,6 +24,92 @@ def build_devmath(force=False):
     if force or _build.stale(DEVMATH_LIB, deps):
         _build.hipcc_shared(DEVMATH_SRC, DEVMATH_LIB)
     return DEVMATH_LIB
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+class HostMath:
+    """numpy-level backend over tests/hostmath (ctypes).  States x[n, 6] -> (y[n, 6], flag[n] bool); scalars elementwise."""
+
+    def __init__(self, lib):
+        self.lib = lib
+
+    def _states(self, fn, x, dt, *pre):
+        x = _f64(x)
+        out = np.empty_like(x)
+        flag = np.zeros(len(x), dtype=np.int32)
+        fn(_p(x), C.c_long(len(x)), C.c_double(dt), *pre, _p(out), _p(flag))
+        return out, flag.astype(bool)
+
+    def propagate(self, x, dt, prop):
+        return self._states(self.lib.hm_propagate, x, dt, C.c_int(prop))
+
+    def propagate_j2(self, x, dt, nsub, j2, r_eq):
+        return self._states(self.lib.hm_propagate_j2, x, dt, C.c_double(j2), C.c_double(r_eq), C.c_int(nsub))
+
+    def uv_fast(self, x, dt):
+        return self._states(self.lib.hm_uv_fast, x, dt)
+
+    def uv_general(self, x, dt):
+        return self._states(self.lib.hm_uv_general, x, dt)
+
+    def general_libm(self, x, dt):
+        return self._states(self.lib.hm_general_libm, x, dt)
+
+    def general_fast(self, x, dt):
+        return self._states(self.lib.hm_general_fast, x, dt)
+
+    def conic_lean(self, x, dt):
+        return self._states(self.lib.hm_conic_lean, x, dt)
+
+    def band(self, nu, ecc, q, tof):
+        nu, ecc, q = _f64(nu), _f64(ecc), _f64(q)
+        fast, libm = np.empty_like(nu), np.empty_like(nu)
+        self.lib.hm_band(_p(nu), _p(ecc), _p(q), C.c_long(len(nu)), C.c_double(tof), _p(fast), _p(libm))
+        return fast, libm
+
+    def log_pos(self, x):
+        x = _f64(x)
+        r = np.empty_like(x)
+        self.lib.hm_log_pos(_p(x), C.c_long(len(x)), _p(r))
+        return r
+
+    def sincos(self, x):
+        x = _f64(x)
+        s, c = np.empty_like(x), np.empty_like(x)
+        self.lib.hm_sincos_fast(_p(x), C.c_long(len(x)), _p(s), _p(c))
+        return s, c
+
+    def atan2(self, y, x):
+        y, x = _f64(y), _f64(x)
+        r = np.empty_like(x)
+        self.lib.hm_atan2_fast(_p(y), _p(x), C.c_long(len(x)), _p(r))
+        return r
+
+    def exp(self, x):
+        x = _f64(x)
+        r = np.empty_like(x)
+        self.lib.hm_exp_fast(_p(x), C.c_long(len(x)), _p(r))
+        return r
+
+    def recip(self, x):
+        x = _f64(x)
+        r, q = np.empty_like(x), np.empty_like(x)
+        self.lib.hm_recip(_p(x), C.c_long(len(x)), _p(r), _p(q))
+        return r, q
+
+
+def build_hostmath(out_dir):
+    """tests/hostmath compiled with g++ into out_dir (contraction off, the shim's include path first) and loaded: a HostMath"""
+    so = os.path.join(out_dir, "libhostmath.so")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D_GNU_SOURCE", "-fPIC", "-shared", "-ffp-contract=off",
+                           "-I" + os.path.join(HERE, "hostmath"), "-o", so, os.path.join(HERE, "hostmath", "hostmath.cpp")])
+    return HostMath(C.CDLL(so))
 
 
 def check_fg_universal_solvers_vs_reference_golden(mm, idt):
@@ -324,3 +412,126 @@ def check_fast_exp(mm):
     r = mm.exp(x)
     ref = np.exp(x.astype(np.longdouble))
     assert (np.abs((r - ref) / ref).astype(np.float64)).max() < 4.5e-16
+
+
+# ---------------------------------------------------------------------------------------------------------------- SSA_PROP_J2_RK4
+# propagate_j2_rk4 against the 80-bit RK4 of the same scheme (oracle/j2_reference.py rk4_j2 in np.longdouble).  The two differ by
+# rounding alone, so the bound is the scheme's own float64 floor: the build's distance from the 80-bit value, per row norm-wise
+# relative on the position and the velocity block, is at most 3 x the numpy float64 restatement's distance on the same rows at the
+# same (dt, nsub) -- maximum and median -- plus 1e-15 (four ulps: rows the restatement hits by luck).  The 3 x and the form are
+# check_parity's (tests/test_hip_step.py).
+J2_CASES = ((20.0, 4), (20.0, 1), (-20.0, 4), (30.0, 6), (150.0, 30), (600.0, 120))
+J2_SLACK = 1e-15
+_J2 = {}
+
+
+def j2_pool():
+    """476 rows: the catalogue (448); 8 polar and 8 exactly equatorial (z = 0, v_z = 0) circular orbits at 6 600 km; 8 GEO rows (four
+    of them exactly equatorial); two rows on the z axis; one high-e row (10 km/s at 6 600 km); one hyperbolic row (11.5 km/s)"""
+    if "pool" not in _J2:
+        mu, R = 398600441800000.0, 6.6e6
+        vc = np.sqrt(mu / R)
+        rows = []
+        for k in range(8):      # polar: the orbit's plane holds the z axis
+            th, ph = 0.3 + 2 * np.pi * k / 8, 0.7 * k
+            rows.append([R * np.cos(th) * np.cos(ph), R * np.cos(th) * np.sin(ph), R * np.sin(th),
+                         -vc * np.sin(th) * np.cos(ph), -vc * np.sin(th) * np.sin(ph), vc * np.cos(th)])
+        for k in range(8):      # equatorial, exactly
+            th = 0.1 + 2 * np.pi * k / 8
+            rows.append([R * np.cos(th), R * np.sin(th), 0.0, -vc * np.sin(th), vc * np.cos(th), 0.0])
+        Rg = 4.2164e7
+        vg = np.sqrt(mu / Rg)
+        for k in range(8):      # GEO: inclinations 0 (four rows) .. 0.08 rad
+            th, inc = 0.5 + 2 * np.pi * k / 8, 0.02 * max(0, k - 3)
+            rows.append([Rg * np.cos(th), Rg * np.sin(th), 0.0, -vg * np.sin(th) * np.cos(inc), vg * np.cos(th) * np.cos(inc), vg * np.sin(inc)])
+        rows += [[0.0, 0.0, R, vc, 0.0, 0.0], [0.0, 0.0, -R, 0.0, -vc, 0.0]]
+        u, w = np.array([1.0, 1.0, 1.0]) / np.sqrt(3.0), np.array([1.0, -1.0, 0.0]) / np.sqrt(2.0)
+        rows += [np.concatenate([R * u, 1.0e4 * w]), np.concatenate([R * u, 1.15e4 * w])]
+        pool = np.concatenate([golden("catalogue_subset.npy"), np.array(rows)])
+        assert pool.shape == (476, 6)
+        pool.setflags(write=False)
+        _J2["pool"] = pool
+    return _J2["pool"]
+
+
+def j2_yardstick(dt, nsub, j2, r_eq):
+    """(80-bit value rounded to double, the float64 restatement) of the pool at (dt, nsub, j2, r_eq): computed once, shared, read-only"""
+    import j2_reference as J
+    key = (float(dt), int(nsub), float(j2), float(r_eq))
+    if key not in _J2:
+        x = j2_pool()
+        ld = J.rk4_j2(x, dt, nsub, j2, r_eq, np.longdouble)
+        f64 = J.rk4_j2(x, dt, nsub, j2, r_eq, np.float64)
+        pair = (ld, f64)
+        for a in pair:
+            a.setflags(write=False)
+        _J2[key] = pair
+    return _J2[key]
+
+
+def _relnorm_ld(a, b, sl):
+    """relnorm with the difference taken in 80 bits (b: the 80-bit value)"""
+    d = (np.asarray(a, dtype=np.longdouble) - b)[..., sl]
+    return (np.sqrt((d * d).sum(-1)) / np.sqrt((b[..., sl] * b[..., sl]).sum(-1))).astype(np.float64)
+
+
+def assert_j2_criterion(run, label, cases=J2_CASES, j2=None, r_eq=None, rows=None):
+    """run(x, dt, nsub) -> y [n, 6] on the pool's `rows` (all of them by default), held to the yardstick at (j2, r_eq) (the defaults
+    of oracle/j2_reference.py unless given) at every case.  Prints both sides; returns {(dt, nsub): ((build max pos, vel), (build
+    median pos, vel), (restatement max pos, vel), (restatement median pos, vel))}."""
+    import j2_reference as J
+    j2 = J.J2_EARTH if j2 is None else j2
+    r_eq = J.R_EQ_EARTH if r_eq is None else r_eq
+    rows = slice(None) if rows is None else rows
+    x = j2_pool()[rows]
+    out = {}
+    for dt, nsub in cases:
+        ld, f64 = j2_yardstick(dt, nsub, j2, r_eq)
+        y = run(x, dt, nsub)
+        assert y.shape == x.shape and np.isfinite(y).all(), (label, dt, nsub)
+        fig = []
+        for sl in (slice(0, 3), slice(3, 6)):
+            fig.append((_relnorm_ld(y, ld[rows], sl), _relnorm_ld(f64[rows], ld[rows], sl)))
+        out[(dt, nsub)] = (tuple(b.max() for b, _ in fig), tuple(np.median(b) for b, _ in fig),
+                           tuple(r.max() for _, r in fig), tuple(np.median(r) for _, r in fig))
+        print("[j2 rk4 vs 80-bit] %-18s dt %5.0f nsub %3d, %3d rows: build max pos/vel %.2e / %.2e median %.2e / %.2e; float64 restatement max "
+              "%.2e / %.2e median %.2e / %.2e" % ((label, dt, nsub, len(x)) + out[(dt, nsub)][0] + out[(dt, nsub)][1] + out[(dt, nsub)][2] + out[(dt, nsub)][3]))
+        for what, (b, r) in zip(("position", "velocity"), fig):
+            assert b.max() <= 3 * r.max() + J2_SLACK, (label, dt, nsub, what, "max", b.max(), r.max(), int(np.argmax(b)))
+            assert np.median(b) <= 3 * np.median(r) + J2_SLACK, (label, dt, nsub, what, "median", np.median(b), np.median(r))
+    return out
+
+
+def j2_nonfinite_rows():
+    """(x [9, 6], bad [9]): three rows that cannot be propagated -- one NaN velocity component, r = 0, an infinite coordinate -- each
+    between ordinary neighbours"""
+    x = j2_pool()[[3, 10, 450, 17, 460, 24, 470, 31, 38]].copy()
+    x[1, 4] = np.nan
+    x[3, :3] = 0.0
+    x[5, 0] = np.inf
+    bad = np.zeros(len(x), dtype=bool)
+    bad[[1, 3, 5]] = True
+    return x, bad
+
+
+def check_j2_rk4_vs_80bit(mm):
+    """mm.propagate_j2(x, dt, nsub, j2, r_eq) -> (y, ok) with the default constants: the criterion at every case on the whole pool; dt = 0
+    returns the input's bits; a row that cannot be propagated returns false and NaN in every component, and its neighbours their own bits"""
+    import j2_reference as J
+    def run(x, dt, nsub):
+        y, ok = mm.propagate_j2(x, dt, nsub, J.J2_EARTH, J.R_EQ_EARTH)
+        assert ok.all(), (dt, nsub)
+        return y
+    out = assert_j2_criterion(run, "propagate_j2_rk4")
+    x = j2_pool()
+    for nsub in (1, 4):
+        y, ok = mm.propagate_j2(x, 0.0, nsub, J.J2_EARTH, J.R_EQ_EARTH)
+        assert ok.all() and np.array_equal(y.view(np.uint64), x.view(np.uint64)), nsub
+    xb, bad = j2_nonfinite_rows()
+    for dt, nsub in ((20.0, 4), (20.0, 1), (-20.0, 4)):
+        y, ok = mm.propagate_j2(xb, dt, nsub, J.J2_EARTH, J.R_EQ_EARTH)
+        assert np.array_equal(ok, ~bad), (dt, nsub, ok)
+        assert np.isnan(y[bad]).all(), (dt, nsub, y[bad])
+        clean, _ = mm.propagate_j2(xb[~bad], dt, nsub, J.J2_EARTH, J.R_EQ_EARTH)
+        assert np.array_equal(y[~bad].view(np.uint64), clean.view(np.uint64)), (dt, nsub)
+    return out

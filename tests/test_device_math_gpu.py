@@ -17,7 +17,7 @@ from conftest import golden
 from support.devmath import (CONIC_FORMS, _conic_states, build_devmath, check_conic_branches_lean_form_vs_restatements_and_oracle,
                              check_device_math_vs_reference_conics_golden, check_elements_strong_elliptic_chain_vs_reference_golden, check_fast_atan2, check_fast_exp,
                              check_fast_sincos_and_reciprocals, check_fg_hyperbolic_and_near_parabolic_states,
-                             check_fg_universal_solvers_vs_reference_golden, check_near_parabolic_bands_fast_vs_libm)
+                             check_fg_universal_solvers_vs_reference_golden, check_j2_rk4_vs_80bit, check_near_parabolic_bands_fast_vs_libm)
 from support.gpu import namespace
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +32,7 @@ class DeviceMath:
         self.lib, self.torch = lib, torch
 
     def _up(self, a):
-        return self.torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
+        return self.torch.from_numpy(np.array(a, dtype=np.float64, order="C")).cuda()      # (a copy: the shared pools are read-only)
 
     def _call(self, name, *args):
         stream = C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
@@ -50,6 +50,9 @@ class DeviceMath:
 
     def propagate(self, x, dt, prop):
         return self._states("propagate", x, dt, C.c_int32(prop))
+
+    def propagate_j2(self, x, dt, nsub, j2, r_eq):
+        return self._states("propagate_j2", x, dt, C.c_double(j2), C.c_double(r_eq), C.c_int32(nsub))
 
     def uv_fast(self, x, dt):
         return self._states("uv_fast", x, dt)
@@ -97,7 +100,7 @@ def dm():
     import torch
     assert torch.cuda.is_available(), "GPU tests need a visible MI355X"
     lib = C.CDLL(build_devmath())
-    for f in ("propagate", "uv_fast", "uv_general", "general_libm", "general_fast", "conic_lean", "band", "log_pos", "sincos_fast",
+    for f in ("propagate", "propagate_j2", "uv_fast", "uv_general", "general_libm", "general_fast", "conic_lean", "band", "log_pos", "sincos_fast",
               "atan2_fast", "exp_fast", "recip"):
         getattr(lib, "dm_" + f).restype = C.c_int
     return DeviceMath(lib, torch)
@@ -135,6 +138,10 @@ def test_device_math_near_parabolic_bands_fast_vs_libm(dm):
 @pytest.mark.parametrize("idt", range(3))
 def test_device_math_elements_strong_elliptic_chain_vs_reference_golden(dm, idt):
     check_elements_strong_elliptic_chain_vs_reference_golden(dm, idt)
+
+
+def test_device_math_j2_rk4_vs_80bit(dm):
+    check_j2_rk4_vs_80bit(dm)
 
 
 def test_device_math_fast_sincos_and_reciprocals(dm):
@@ -368,15 +375,18 @@ DTS = (20.0, 150.0, 5400.0, 86400.0)
 
 
 @pytest.mark.parametrize("dt", DTS)
-@pytest.mark.parametrize("kernel", ["elements", "fg", "hybrid", "kepler_elements"])
+@pytest.mark.parametrize("kernel", ["elements", "fg", "hybrid", "kepler_elements", "j2"])
 def test_device_math_product_kernels_do_not_depend_on_wave_neighbours(hip, oracle_ld, kernel, dt):
-    """ssa_propagate_f64 (ELEMENTS / FG / HYBRID) and ssa_kepler_elements_f64: each item's bits, whatever shares its wavefront"""
+    """ssa_propagate_f64 (ELEMENTS / FG / HYBRID), ssa_kepler_elements_f64 and ssa_propagate_j2_f64 (5 s sub-steps, 64 at the most:
+    the NaN / inf rows of the pool among the others): each item's bits, whatever shares its wavefront"""
     device, torch = hip
     from ssa_gym_amd import _lib
     x, cls = _state_pool(dt, oracle_ld)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
     if kernel == "kepler_elements":
         run = lambda a: (device.kepler_elements(up(a), dt).cpu().numpy(),)
+    elif kernel == "j2":
+        run = lambda a: (device.propagate_j2(up(a), dt, 0.00108263, 6378136.6, min(64, int(np.ceil(dt / 5.0)))).cpu().numpy(),)
     else:
         prop = {"elements": _lib.PROP_ELEMENTS, "fg": _lib.PROP_FG, "hybrid": _lib.PROP_HYBRID}[kernel]
         run = lambda a: (device.propagate(up(a), dt, propagator=prop).cpu().numpy(),)

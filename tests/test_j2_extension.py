@@ -37,11 +37,16 @@ def test_two_body_limit_matches_farnocchia(hip):
     assert relnorm(y0, kep, slice(3, 6)).max() < 1e-10
 
 
-def test_ukf_step_with_j2_propagator(hip):
-    """the fused step with SSA_PROP_J2_RK4 against the restated UKF (oracle/ukf_numpy.py) driven by the DOP853 J2 fx."""
+def test_ukf_step_with_j2_propagator(hip, oracle):
+    """the fused step with SSA_PROP_J2_RK4 against the restated UKF (oracle/ukf_numpy.py) driven by the DOP853 J2 fx -- the check that
+    includes the truncation of RK4 and the integrator's own tolerance, both multiplied by the sigma-point weights (1.7e5 at alpha =
+    1e-3) -- and, for the rounding, against the 80-bit yardstick of the same scheme under the criterion of tests/test_j2_step_gpu.py:
+    position, velocity and sd-normalised covariance at most 3 x the float64 yardstick's own distance plus 1e-12 / 1e-12 / 1e-9, the
+    truth row at most 3 x the float64 restatement's plus 1e-15."""
     import j2_reference as J
     import ukf_numpy as U
     import oracle as orc
+    from support import j2 as sj
     g = golden("ukf_step_golden.npz")
     c2t = golden("c2t_2020-05-04_dt20_n480.npy")
     m, alpha = 12, 1e-3
@@ -62,8 +67,14 @@ def test_ukf_step_with_j2_propagator(hip):
         f.x, f.P, f.Q = x0[j].copy(), g["P0"].copy(), g["Q"].copy()
         f.predict()
         assert np.linalg.norm((xg[j] - f.x)[:3]) / np.linalg.norm(f.x[:3]) < 1e-6      # alpha = 1e-3: fp64 floor ~1e-9
+        assert np.linalg.norm((xg[j] - f.x)[3:]) / np.linalg.norm(f.x[3:]) < 1e-6
         sd = np.sqrt(np.diag(f.P))
         assert np.max(np.abs(Pg[j] - f.P) / np.outer(sd, sd)) < 1e-5
         ref_t = J.fx_xyz_cowell_j2(xt[j], 20.0)
         assert np.linalg.norm(xtg[j] - ref_t) / np.linalg.norm(ref_t) < 1e-10
     assert np.all(eng.status.cpu().numpy() == 0)
+    ld = [sj.predict_reference(oracle, x0[j], g["P0"], g["Q"], 20.0, alpha, 4, ld=True) for j in range(m)]
+    f64 = [sj.predict_reference(oracle, x0[j], g["P0"], g["Q"], 20.0, alpha, 4, ld=False) for j in range(m)]
+    sj.assert_filter_criterion([sj.distances({"x": xg[j], "P": Pg[j]}, ld[j]) for j in range(m)],
+                               [sj.distances(f64[j], ld[j]) for j in range(m)], "catalogue filters, predict only")
+    sj.assert_truth_criterion(xtg, xt, 20.0, 4, J.J2_EARTH, J.R_EQ_EARTH, "catalogue rows")
