@@ -368,6 +368,11 @@ int ssa_residual_z_aer_f64(const double *a, const double *b, double *c, int64_t 
 /* V1  object_visibility(): mask[n] = elevation(x_true) >= obs_limit; el[n] optional (:418-434). */
 int ssa_visible_mask_f64(const double *x_true, const double *M, const ssa_consts *c_host, uint8_t *mask,
                          double *el, int64_t n, void *stream);
+/* EXTENSION, no reference counterpart: the sunlit rule of ssa_sensor_params, for the n true states x_true[n][6] against ONE 32-byte row
+ * of a Sun table, sun_row = (sx, sy, sz, dark word; the word is not read): mask[n] = 1 where the object is outside the Earth's
+ * cylindrical shadow of radius shadow_radius -- (p >= 0) || (d2 >= R R) with p = r.s, d2 = r.r - p p -- else 0; a NaN in r or s: 0.
+ * The device function is the one the sensor kernels evaluate. */
+int ssa_sunlit_mask_f64(const double *x_true, const double *sun_row, double shadow_radius, uint8_t *mask, int64_t n, void *stream);
 /* O1/O2  observations() + error() for n objects of one env (results.py:61,37); metrics[4][n]. */
 int ssa_observe_f64(const double *x_true, const double *x, const double *P, double *obs, double *metrics,
                     int64_t n, void *stream);
@@ -564,7 +569,19 @@ int ssa_lookahead_f64(const ssa_consts *c_host, const ssa_step_params *p_host, c
  * the rest of row and column 2 and exactly 1.0 at [2][2] -- ssa_nis_f64 on the record then returns the 2-dof NIS as it stands.
  * SSA_UPD_Z_TRUE[2] and the third column of SSA_UPD_SIGMAS_H keep the range the geometry gives: recorded, not used by the update.
  * Refused before any launch (SSA_E_INVALID), behind every other refusal of an entry: a bit set at or above n_sensor; any bit set while
- * ssa_consts.obs_type is not SSA_OBS_AER. */
+ * ssa_consts.obs_type is not SSA_OBS_AER.
+ * Illumination: bit s of `sunlit_only` set -- sensor s (an optical one, or a laser ranger: the test does not depend on obs_type or on the
+ * sensor's kind) sees an object only while the object is sunlit and the sensor's own site is dark.  `sun` is a table of n_time rows,
+ * row t = time_row of the update, the row whose `trans` matrix the same update reads: the unit vector s from the geocentre to the Sun in
+ * the frame of x_true (taken as unit length, never normalised, never computed here) and the word of the sites' dark bits.  With r the
+ * object's TRUE position at the time of the update, p = r.s and d2 = r.r - p p, the object is sunlit iff (p >= 0) || (d2 >= R R), R =
+ * shadow_radius: the Earth's cylindrical shadow -- a NaN anywhere gives not sunlit.  For such a sensor
+ *   visible = elevation >= obs_limit[s]  &&  bit s of the row's dark word  &&  sunlit;
+ * an object that fails it is an invisible object in every respect (record, status, OBS_TAKEN, lookahead score NaN).  It holds in every
+ * entry point that takes this block: a forecast's step h, a dry run's slot, each env's own time word in the *_envs forms.
+ * With sunlit_only == 0 neither `sun` nor `shadow_radius` is read.
+ * Refused before any launch (SSA_E_INVALID), behind every other refusal of an entry: a sunlit_only bit at or above n_sensor; any bit set
+ * while `sun` is NULL or not 32-byte aligned; any bit set while !(shadow_radius >= 0). */
 #define SSA_MAX_SENSORS 8
 typedef struct ssa_sensor_params {
     int32_t n_sensor;                      /* S */
@@ -576,6 +593,12 @@ typedef struct ssa_sensor_params {
     double R[SSA_MAX_SENSORS][9];          /* measurement noise covariance of sensor s */
     int64_t zn_stride_sensor;              /* doubles between the noise tables of consecutive sensors */
     double *upd;                           /* [S][SSA_UPD_STRIDE] update record per sensor, or NULL */
+    /* illumination (appended under ABI 23; a zero tail: no sensor tests it) */
+    const double *sun;                     /* [n_time] rows of 32 bytes on the device, base 32-byte aligned: doubles sx, sy, sz, then ONE int64
+                                              word, bit s set = site s is dark at this row.  Not read unless sunlit_only != 0 */
+    double shadow_radius;                  /* R [m] of the Earth's cylindrical shadow.  Not read unless sunlit_only != 0 */
+    int32_t sunlit_only;                   /* bit s: sensor s sees only sunlit objects, and only while its site is dark */
+    int32_t reserved2;                     /* 0 */
 } ssa_sensor_params;
 int ssa_env_step_sensors_f64(const ssa_consts *c_host, const ssa_step_params *p_host, const ssa_sensor_params *s_host, void *stream);
 

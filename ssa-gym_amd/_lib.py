@@ -70,6 +70,7 @@ class ssa_sensor_params(C.Structure):
         ("n_sensor", C.c_int32), ("angles_only", C.c_int32), ("action", C.c_int32 * 8),
         ("enu", (C.c_double * 9) * 8), ("obs_itrs", (C.c_double * 3) * 8), ("obs_limit", C.c_double * 8), ("R", (C.c_double * 9) * 8),
         ("zn_stride_sensor", C.c_int64), ("upd", c_dp),
+        ("sun", c_dp), ("shadow_radius", C.c_double), ("sunlit_only", C.c_int32), ("reserved2", C.c_int32),
     ]
 
 
@@ -184,6 +185,7 @@ SIGNATURES = {
     "ssa_mean_z_uvw_f64": (C.c_int, [c_dp, C.POINTER(ssa_consts), c_dp, C.c_int64, c_dp]),
     "ssa_residual_z_aer_f64": (C.c_int, [c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_visible_mask_f64": (C.c_int, [c_dp, c_dp, C.POINTER(ssa_consts), c_dp, c_dp, C.c_int64, c_dp]),
+    "ssa_sunlit_mask_f64": (C.c_int, [c_dp, c_dp, C.c_double, c_dp, C.c_int64, c_dp]),
     "ssa_observe_f64": (C.c_int, [c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_agent_scores_f64": (C.c_int, [c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(ssa_consts), c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_visible_mask_at_f64": (C.c_int, [c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.POINTER(ssa_consts), c_dp, c_dp, C.c_int64, c_dp]),

@@ -104,7 +104,7 @@ struct alignas(16) Tiles {
     int St[OBJ_PER_WAVE];              // @1504
     int Oid[OBJ_PER_WAVE];             // @1520  the caller's index of each row's object (ssa_step_params.obj_ids; else unused)
     double X[OBJ_PER_WAVE * 6];        // @1536  x_in, then sigma_0', then x_out
-    double pad1[8];                    // @1728
+    double pad1[8];                    // @1728  [0..4): the update's row of the Sun table (ssa_sensor_params.sun), for the sensors that need it
     double T[OBJ_PER_WAVE * 6];        // @1792  x_true_in, later x_true_out
     double UA[OBJ_PER_WAVE * 36];      // Cholesky factor rows [4][36] (the transform's moment sums stay in registers)
     double D[408];                     // centred propagated sigma points (see above); scratch of the update
@@ -1937,6 +1937,18 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
         }
         upd_in = *src;
     }
+    // a sensor that sees sunlit objects only (ssa_sensor_params.sunlit_only; the row's sensor, or any of the lookahead's passes): the
+    // 32-byte row of the Sun table at the SAME time row travels with the update's inputs, one word in each of the row's idle lanes 12..15
+    // -- a network's tile belongs to one env, so the row is the wavefront's and every selected row brings the same four words
+    if constexpr (SENS || LSENS) {
+        const int32_t sun_bits = asrc.sites()->sunlit_only;
+        if (sun_bits != 0) {   // (wave-uniform: with no bit set nothing is loaded)
+            if (may_update && l >= 12 && (LSENS || ((sun_bits >> sid) & 1))) {
+                tmod = time_row(tix, p.n_time);
+                upd_in = asrc.sites()->sun[(int64_t)tmod * 4 + (l - 12)];   // (lane 15: the dark word's bits, moved as they are)
+            }
+        }
+    }
 
     if (TILE == 0 && pf.dma) tile_dma_wait(t, pf, lane);   // (the one-tile kernels: the tile came by LDS-DMA)
     else if (TILE != 2) tile_commit(t, pf, lane);        // TILE 1: requested one tile ago (or by the kernel prologue)
@@ -1953,6 +1965,10 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     const int rung = robust_chol_row_lds<PLAIN>(t, C.scale, g, l);   // (PLAIN: the fused form, chol_step_fused)
     asrc.mid_step(t, lane);   // (closed loop: the PREVIOUS step's tile leaves for HBM now, its last reader of t.Obs)
     if (may_update && l < 12) t.Obs[g * 12 + l] = upd_in;
+    if constexpr (SENS || LSENS) {   // (the Sun row, where it was fetched: into the gap behind t.X, which nothing else writes)
+        const int32_t sun_bits = asrc.sites()->sunlit_only;
+        if (sun_bits != 0 && may_update && l >= 12 && (LSENS || ((sun_bits >> sid) & 1))) t.pad1[l - 12] = upd_in;
+    }
     wave_lds_sync();
     const bool chol_fail = (rung == 16);
     const bool is_sigma = (l <= 12);
@@ -2214,8 +2230,18 @@ look_pass:
                 if (PLAIN || C.obs_type == SSA_OBS_AER) { z[0] = aer[0]; z[1] = aer[1]; z[2] = aer[2]; }
                 else { z[0] = sf[0]; z[1] = sf[1]; z[2] = sf[2]; }
             }
-            if constexpr (SENS || LSENS) visible = row_bcast<13>(el_mine) >= lim;   // (as seen from the row's sensor)
-            else visible = row_bcast<13>(el_mine) >= C.obs_limit;  // object_visible(): elevation of the TRUE state (:418-425)
+            if constexpr (SENS || LSENS) {
+                // a sensor that sees sunlit objects only, from a dark site: lane 13 holds the propagated truth in sf and tests it against
+                // the Sun row the head left in LDS; an object that fails has no elevation (a NaN is below every mask), so that it is an
+                // invisible object in every respect and the broadcast below stays the one there was
+                const int sun_s = SENS ? sid : look_s;
+                if ((SP->sunlit_only >> sun_s) & 1) {
+                    const double* sun = &t.pad1[0];
+                    const bool dark = (__double_as_longlong(sun[3]) >> sun_s) & 1;
+                    if (!(dark && sunlit_cylinder(sf, sun, SP->shadow_radius))) el_mine = __builtin_nan("");
+                }
+                visible = row_bcast<13>(el_mine) >= lim;   // (as seen from the row's sensor)
+            } else visible = row_bcast<13>(el_mine) >= C.obs_limit;  // object_visible(): elevation of the TRUE state (:418-425)
             if (rec && l == 13) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) rec[SSA_UPD_Z_TRUE + c] = z[c];
@@ -3604,6 +3630,15 @@ __global__ void visible_kernel(const double* __restrict__ x, const double* __res
     hx_aer(xx, Mm, g.enu, g.obs, zz);
     mask[i] = zz[1] >= g.obs_limit ? 1 : 0;
     if (el) el[i] = zz[1];
+}
+// the sunlit rule of the sensor kernels (sunlit_cylinder) for n true states against ONE row of a Sun table: a lane per object
+__global__ void sunlit_kernel(const double* __restrict__ x, const double* __restrict__ sun_row, double shadow_radius,
+                              uint8_t* __restrict__ mask, int64_t n)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double r[3] = {x[i * 6], x[i * 6 + 1], x[i * 6 + 2]}, s[3] = {sun_row[0], sun_row[1], sun_row[2]};
+    mask[i] = sunlit_cylinder(r, s, shadow_radius) ? 1 : 0;
 }
 __global__ void observe_kernel(const double* __restrict__ xt, const double* __restrict__ x, const double* __restrict__ P,
                                double* __restrict__ obs, double* __restrict__ met, int64_t n)
@@ -5283,6 +5318,14 @@ static bool kinds_ok(const ssa_consts* c, const ssa_sensor_params* sp)
     const uint32_t bits = (uint32_t)sp->angles_only;
     return bits == 0 || ((bits >> sp->n_sensor) == 0 && c->obs_type == SSA_OBS_AER);
 }
+// ... and of the sensors that see sunlit objects only (ssa_sensor_params.sunlit_only): no bit at or above n_sensor, and with any bit set
+// a Sun table (32-byte rows) and a shadow radius that is a number >= 0.  Whatever obs_type is.  Applied with kinds_ok, behind all else
+static bool illumination_ok(const ssa_sensor_params* sp)
+{
+    const uint32_t bits = (uint32_t)sp->sunlit_only;
+    return bits == 0 || ((bits >> sp->n_sensor) == 0 && sp->sun && ((uintptr_t)sp->sun & 31) == 0 && sp->shadow_radius >= 0.0);
+}
+static bool sensor_tail_ok(const ssa_consts* c, const ssa_sensor_params* sp) { return kinds_ok(c, sp) && illumination_ok(sp); }
 // a network's sites as the kernels take them that read neither its action words nor its record destination
 static ssa_sensor_params idle_sites(const ssa_sensor_params* sp)
 {
@@ -5349,7 +5392,7 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     TileGrid g;
     const int rc = step_args(c, p, sens != nullptr, g);
     if (rc != SSA_OK) return rc;
-    if (sens && !kinds_ok(c, sens)) return SSA_E_INVALID;
+    if (sens && !sensor_tail_ok(c, sens)) return SSA_E_INVALID;
     StepK k;
     k.c = *c;
     k.p = *p;
@@ -5527,7 +5570,7 @@ int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, con
     LookSensK k;
     const int rc = lookahead_sensors_args(c, p, sp, o, false, k.k, k.s);
     if (rc != SSA_OK) return rc;
-    if (!kinds_ok(c, sp)) return SSA_E_INVALID;
+    if (!sensor_tail_ok(c, sp)) return SSA_E_INVALID;
     const TileGrid g = tile_grid(p->n_obj);
     dim3 grid((unsigned)g.nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
@@ -5542,7 +5585,7 @@ int ssa_lookahead_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p
     VecLookSensK k;
     const int rc = lookahead_sensors_args(c, p, sp, o, true, k.k, k.s);
     if (rc != SSA_OK) return rc;
-    if (!kinds_ok(c, sp)) return SSA_E_INVALID;
+    if (!sensor_tail_ok(c, sp)) return SSA_E_INVALID;
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     dim3 grid((unsigned)g.nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
@@ -5559,7 +5602,7 @@ int ssa_forecast_sensors_f64(const ssa_consts* c, const ssa_step_params* p, cons
     ForeSensK k;
     const int rc = lookahead_sensors_args(c, p, sp, &f->out, false, lk, k.s);
     if (rc != SSA_OK) return rc;
-    if (f->n_steps < 1 || !kinds_ok(c, sp)) return SSA_E_INVALID;
+    if (f->n_steps < 1 || !sensor_tail_ok(c, sp)) return SSA_E_INVALID;
     k.k = lk.k;
     k.k.p.launch_mask = 0;   // (the time word is read from env_time: a resident tile's steps do not see SSA_LAUNCH_INLINE_ENVS)
     k.f = *f;
@@ -5576,7 +5619,7 @@ int ssa_forecast_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p,
     VecForeSensK k;
     const int rc = lookahead_sensors_args(c, p, sp, &f->out, true, lk, k.s);
     if (rc != SSA_OK) return rc;
-    if (f->n_steps < 1 || !kinds_ok(c, sp)) return SSA_E_INVALID;
+    if (f->n_steps < 1 || !sensor_tail_ok(c, sp)) return SSA_E_INVALID;
     k.k = lk.k;   // (launch_mask: SSA_LAUNCH_INLINE_ENVS alone survives lookahead_args, and the kernel reads inline_time by it)
     k.f = *f;
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
@@ -5595,7 +5638,7 @@ int ssa_dryrun_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p, c
     const int rc = lookahead_sensors_args(c, p, sp, &o, true, lk, k.s);
     if (rc != SSA_OK) return rc;
     if (d->n_steps < 1 || d->n_obj_caller < 1 || !row_aligned(d->actions)) return SSA_E_INVALID;
-    if (!rows_fit(p->n_env, sp->n_sensor, d->n_steps) || !kinds_ok(c, sp)) return SSA_E_INVALID;
+    if (!rows_fit(p->n_env, sp->n_sensor, d->n_steps) || !sensor_tail_ok(c, sp)) return SSA_E_INVALID;
     k.k = lk.k;
     k.k.p.launch_mask = 0;   // (the time words are read from env_time: a resident tile's steps do not see SSA_LAUNCH_INLINE_ENVS)
     k.d = *d;
@@ -5694,7 +5737,7 @@ int ssa_env_rollout_sensors_f64(const ssa_consts* c, const ssa_step_params* p, c
     RollSensK rk;
     const int rc = rollout_sensors_args(c, p, r, sp, rs->actions, false, rk.k, rk.s);
     if (rc != SSA_OK) return rc;
-    if (!kinds_ok(c, sp)) return SSA_E_INVALID;
+    if (!sensor_tail_ok(c, sp)) return SSA_E_INVALID;
     rk.rs = *rs;
     const TileGrid g = tile_grid(p->n_obj);
     hipStream_t s = (hipStream_t)stream;
@@ -5708,7 +5751,7 @@ int ssa_env_rollout_sensors_envs_f64(const ssa_consts* c, const ssa_step_params*
     VecRollSensK rk;
     const int rc = rollout_sensors_args(c, p, r, sp, re->actions, true, rk.k, rk.s);
     if (rc != SSA_OK) return rc;
-    if (!re->stats_out || !kinds_ok(c, sp)) return SSA_E_INVALID;
+    if (!re->stats_out || !sensor_tail_ok(c, sp)) return SSA_E_INVALID;
     rk.v = *re;
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     hipStream_t s = (hipStream_t)stream;
@@ -5897,6 +5940,14 @@ int ssa_residual_z_aer_f64(const double* a, const double* b, double* c, int64_t 
     if (!a || !b || !c || n < 0) return SSA_E_INVALID;
     if (n == 0) return SSA_OK;
     hipLaunchKernelGGL(residual_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, a, b, c, n);
+    return launch_status();
+}
+
+int ssa_sunlit_mask_f64(const double* x_true, const double* sun_row, double shadow_radius, uint8_t* mask, int64_t n, void* stream)
+{
+    if (!x_true || !sun_row || !mask || n < 0) return SSA_E_INVALID;
+    if (n == 0) return SSA_OK;
+    hipLaunchKernelGGL(sunlit_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, x_true, sun_row, shadow_radius, mask, n);
     return launch_status();
 }
 

@@ -29,6 +29,17 @@ constexpr double NEWTON_TOL = 1.48e-08;   // farnocchia.py:337
 
 SSA_DEV double dot3(const double* a, const double* b) { return fma(a[2], b[2], fma(a[1], b[1], a[0] * b[0])); }
 
+// Is the object at r (geocentric, the frame of x_true) outside the Earth's cylindrical shadow?  s: the unit vector from the geocentre to
+// the Sun in the same frame (taken as unit length: not normalised), R: the shadow's radius.  With p = r.s and d2 = r.r - p p the object is
+// sunlit iff it is on the Sun's side of the terminator plane or outside the cylinder -- both comparisons written so that a NaN anywhere
+// in r or s gives NOT sunlit.  No penumbra, no taper of the umbra, no flattening, no refraction (include/ssa_hip.h: ssa_sensor_params).
+SSA_DEV bool sunlit_cylinder(const double* r, const double* s, double R)
+{
+    const double p = dot3(r, s);
+    const double d2 = dot3(r, r) - p * p;
+    return (p >= 0.0) || (d2 >= R * R);
+}
+
 // 1/v and 1/sqrt(v) to double precision (<= ~1 ulp) from the hardware estimates (v_rcp_f64 / v_rsq_f64, relative
 // error e ~ 2^-26) plus ONE third-order correction -- 1/v = y (1 + e + e^2), 1/sqrt(v) = y (1 + e/2 + 3 e^2/8), residual
 // e^3 ~ 2^-78 -- 3 / 5 VALU instructions instead of the 10-15 of the IEEE division / square-root sequences (and 1 / 3

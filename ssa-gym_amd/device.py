@@ -152,6 +152,18 @@ def visible_mask(x_true, M, consts, want_el=False):
     return (mask, el) if want_el else mask
 
 
+def sunlit_mask(x_true, sun_row, shadow_radius):
+    """the sensor kernels' sunlit rule (ssa_sunlit_mask_f64) for every row of x_true[n,6] against one row of a Sun table, sun_row[>=3] =
+    (sx, sy, sz, ...) on the device: uint8 mask[n], 1 where the object is outside the Earth's cylindrical shadow of that radius."""
+    lib = _lib.load()
+    n = x_true.shape[0]
+    mask = torch.empty(n, dtype=torch.uint8, device=x_true.device)
+    if sun_row.numel() < 3:
+        raise _lib.SsaHipError("sun_row must hold the three components of the Sun's direction")
+    _lib.check(lib.ssa_sunlit_mask_f64(_chk(x_true, "x_true"), _chk(sun_row, "sun_row"), float(shadow_radius),
+                                       _chk(mask, "mask", torch.uint8), n, _stream()), "ssa_sunlit_mask_f64")
+    return mask
+
 
 def catalogue_screen(elements, trans, sites, step, min_alt, first, max_gap, want_gap=False, want_flags=False):
     """catalogue._accepted for every candidate row of elements[n,6] (a, ecc, inc, raan, argp, nu), seen from a network of sites[S,13]

@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, device
+from . import _lib, device, host
 
 f64 = torch.float64
 
@@ -82,6 +82,7 @@ class HotPathEngine:
         self.status = torch.zeros(N, dtype=torch.int32, device=d)
         self.trans = device.as_dev(np.asarray(trans, dtype=np.float64).reshape(-1, 9), d)
         self.n_time = self.trans.shape[0]
+        self.sun = None      # set_sun_table: the [n_time, 4] rows (sx, sy, sz, the sites' dark word) of ssa_sensor_params.sun, next to `trans`
         self.z_noise = z_noise if isinstance(z_noise, torch.Tensor) else device.as_dev(z_noise, d)
         # default strides for z_noise[E][n_time][m][3]
         self.zn_stride_time = self.m * 3 if zn_stride_time is None else int(zn_stride_time)
@@ -448,6 +449,21 @@ class HotPathEngine:
         if S is not None and actions.shape[-1] != _lib.MAX_SENSORS:
             actions = torch.nn.functional.pad(actions, (0, _lib.MAX_SENSORS - S), value=-1)
         return actions
+
+    def set_sun_table(self, sun, dark, sensors=()):
+        """keep the Sun table of this engine's epoch on the device (include/ssa_hip.h: ssa_sensor_params.sun): sun [n_time, 3] unit vectors
+        from the geocentre to the Sun in the frame of x_true, dark [n_time] integers whose bit s says that site s is dark at that row (the
+        same rows as `trans`: one epoch, one table for all envs).  Every block of `sensors` (host.make_sensor_params) is pointed at it.
+        Returns the [n_time, 4] float64 device tensor (the fourth column holds the words' bits)."""
+        rows = host.pack_sun_rows(sun, dark)
+        if rows.shape[0] != self.n_time:
+            raise _lib.SsaHipError("the Sun table has %d rows, trans has %d" % (rows.shape[0], self.n_time))
+        self.sun = device.as_dev(rows, self.dev)
+        if self.sun.data_ptr() % 32:
+            raise _lib.SsaHipError("the Sun table's device rows are not 32-byte aligned")
+        for sp in sensors:
+            sp.sun = self.sun.data_ptr()
+        return self.sun
 
     def _check_sensor_noise(self, sensors, envs=False):
         """the extent of z_noise that the sensors of `sensors` index: sensor s reads z_noise[s * sensors.zn_stride_sensor ...]; envs: in

@@ -7,7 +7,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from .. import _lib, host
-from . import dynamics, transformations
+from . import dynamics, sun, transformations
 from ._gymshim import spaces
 
 _MODELS = {(("hx", "aer"), ("mean_z", "uvw"), ("residual_z", "aer")): 'aer',
@@ -71,13 +71,19 @@ MAX_SENSORS = 8
 def resolve_sensors(config):
     """the sensor network of a config dict (EXTENSION, no reference counterpart), or None without config['observers']:
     {'sites': [(lat, lon, h)] * S (degrees, degrees, metres), 'obs_limit': [S] degrees or None, 'z_sigma': [S] or None,
-    'angles_only': [S] booleans}.
+    'angles_only': [S] booleans, 'illumination': [S] of None or a limit in degrees}.
     config['observers'] lists 1 <= S <= 8 sites; the optional config['sensor_obs_limit'] / config['sensor_z_sigma'] give per-sensor
     values (S of them; default: the scalar obs_limit / z_sigma / R).  The optional config['sensor_measurement'] gives each sensor's
     measurement kind, S strings: 'aer' (azimuth, elevation, range: the default) or 'ae' (azimuth and elevation only, a telescope:
     the update of dim_z = 2); it needs obs_type 'aer' and, for an 'ae' entry, more than one site (a one-site env runs the
-    one-observer kernels, which measure az, el and range).  Anything else raises ValueError."""
+    one-observer kernels, which measure az, el and range).  The optional config['sensor_illumination'] gives each sensor None (no
+    illumination test: a radar, the default) or a number: the sensor sees only sunlit objects, and only while the Sun is below that
+    elevation (degrees, -90 .. 90; -12 is nautical twilight) at its site.  It is independent of the measurement kind and of obs_type
+    (a laser ranger needs sunlight too) and needs at least two sites, for the reason 'ae' does.  Anything else raises ValueError."""
     sites = config.get('observers')
+    illum = config.get('sensor_illumination')
+    if sites is None and illum is not None:
+        raise ValueError("config['sensor_illumination'] needs config['observers']")
     lim, zs = config.get('sensor_obs_limit'), config.get('sensor_z_sigma')
     kinds = config.get('sensor_measurement')
     if sites is None and kinds is not None:
@@ -117,8 +123,24 @@ def resolve_sensors(config):
         if S == 1 and kinds[0] == 'ae':
             raise ValueError("config['sensor_measurement']: a one-site network cannot be 'ae' -- with one site step(), rollout, "
                              "run_agent, run_policy and lookahead() run the one-observer kernels, which measure az, el and range")
+    if illum is None:
+        illum = [None] * S
+    else:
+        if isinstance(illum, str) or not hasattr(illum, '__len__') or len(illum) != S:
+            raise ValueError("config['sensor_illumination'] must give one entry per sensor (None or a Sun elevation limit in degrees): %d" % S)
+        illum = list(illum)
+        for v in illum:
+            if v is None:
+                continue
+            if isinstance(v, (bool, str)) or not np.isscalar(v) or not np.isreal(v) or not -90.0 <= float(v) <= 90.0:
+                raise ValueError("config['sensor_illumination']: every entry is None or a Sun elevation limit in [-90, 90] degrees, "
+                                 "got %r" % (illum,))
+        illum = [None if v is None else float(v) for v in illum]
+        if S == 1 and illum[0] is not None:
+            raise ValueError("config['sensor_illumination'] needs at least two sites -- with one site step(), rollout, run_agent, "
+                             "run_policy and lookahead() run the one-observer kernels, whose visibility is the elevation mask alone")
     return {'sites': [tuple(float(v) for v in row) for row in arr], 'obs_limit': lim, 'z_sigma': zs,
-            'angles_only': [k == 'ae' for k in kinds]}
+            'angles_only': [k == 'ae' for k in kinds], 'illumination': illum}
 
 
 def resolve_config(config):
@@ -155,7 +177,9 @@ def resolve_config(config):
             R = np.array([np.diag(z ** 2) for z in zs])
         else:
             zs, R = np.tile(c.z_sigma, (S, 1)), np.tile(c.R, (S, 1, 1))
-        c.net = SimpleNamespace(lla=lla, obs_limit=lim, z_sigma=zs, R=R, angles_only=np.array(net['angles_only'], dtype=bool))
+        c.net = SimpleNamespace(lla=lla, obs_limit=lim, z_sigma=zs, R=R, angles_only=np.array(net['angles_only'], dtype=bool),
+                                sunlit_only=np.array([v is not None for v in net['illumination']], dtype=bool),
+                                sun_limit=np.radians([0.0 if v is None else v for v in net['illumination']]))
         c.obs_lla, c.obs_limit = lla[0], lim[0]
         c.z_sigma, c.R = zs[0], np.copy(R[0])
     c.obs_itrs = host.lla2ecef(c.obs_lla)
@@ -184,6 +208,22 @@ def resolve_config(config):
         c.trans = np.asarray(config['trans_matrix'], dtype=np.float64).reshape(-1, 3, 3)
     else:
         c.trans = transformations.trans_matrix_table(config['t_0'], c.dt, c.n)
+    # the Sun of the illumination test (config['sensor_illumination']): config['sun_table'], [n, 3] unit vectors in the frame
+    # of x_true, overrides the ephemeris as config['trans_matrix'] overrides the rotation; the sites' dark words always come from the
+    # `trans` and the vectors in force.  Without a sensor that asks for it nothing is computed
+    c.sun = c.sun_dark = None
+    c.shadow_radius = float(config.get('shadow_radius', host.R_EQ_EARTH))
+    if c.net is not None and c.net.sunlit_only.any():
+        if not c.shadow_radius >= 0.0:
+            raise ValueError("config['shadow_radius'] must be a number >= 0, got %r" % (config.get('shadow_radius'),))
+        if config.get('sun_table') is not None:
+            c.sun = np.array(config['sun_table'], dtype=np.float64)
+            if c.sun.shape != (c.trans.shape[0], 3):
+                raise ValueError("config['sun_table'] must be %s unit vectors, one per row of the trans table, got %s"
+                                 % ((c.trans.shape[0], 3), c.sun.shape))
+        else:
+            c.sun = sun.sun_table(config['t_0'], c.dt, c.trans.shape[0])
+        c.sun_dark = sun.dark_sites(c.trans, c.sun, c.net.lla, c.net.sun_limit)      # (a bit of a sensor without the test: not read)
     return c
 
 

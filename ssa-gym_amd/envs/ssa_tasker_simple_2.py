@@ -57,6 +57,10 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         self.n_sensor = c.n_sensor
         # (config['sensor_measurement']: True where a sensor measures az and el only, section 8r; without a network: the one az-el-range observer)
         self.sensor_angles_only = np.zeros(c.n_sensor, dtype=bool) if c.net is None else c.net.angles_only
+        # (config['sensor_illumination']: True where a sensor sees only sunlit objects, and only from a dark site, section 8t; sun_table: the
+        # Sun's direction per row of trans_matrix, None unless a sensor asks for it; sun_dark: per row the word of the sites' dark bits)
+        self.sensor_sunlit_only = np.zeros(c.n_sensor, dtype=bool) if c.net is None else c.net.sunlit_only
+        self.sun_table, self.sun_dark, self.shadow_radius = c.sun, c.sun_dark, c.shadow_radius
         if c.net is not None:
             self.sensor_lla, self.sensor_obs_limit = c.net.lla, c.net.obs_limit
             self.sensor_z_sigma, self.sensor_R = c.net.z_sigma, c.net.R
@@ -139,7 +143,10 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         self._stats_host = torch.zeros(_lib.STAT_STRIDE, dtype=torch.float64).pin_memory()
         if self.n_sensor > 1:     # the network's sites and one update record per sensor (host-mapped, as the single record)
             self._sensors = host.make_sensor_params(self.sensor_lla, self.sensor_obs_limit, self.sensor_R, self.n * self.m * 3,
-                                                    angles_only=self.sensor_angles_only)
+                                                    angles_only=self.sensor_angles_only, sunlit_only=self.sensor_sunlit_only,
+                                                    shadow_radius=self.shadow_radius)
+            if self.sun_table is not None:      # (the packed table lives on the device next to trans; the block points at it)
+                e.set_sun_table(self.sun_table, self.sun_dark, [self._sensors])
             self._upd_s_host = torch.zeros((self.n_sensor, _lib.UPD_STRIDE), dtype=torch.float64).pin_memory()
             self._upd_s_np, self._upd_s_ptr = self._upd_s_host.numpy(), self._upd_s_host.data_ptr()
         self._upd_host = torch.zeros(_lib.UPD_STRIDE, dtype=torch.float64).pin_memory()
@@ -752,8 +759,15 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
             raise ValueError("sensor %r: the env has %d sensor(s)" % (sensor, self.n_sensor))
         self._caller_order()
         e = self._engine
-        M = e.trans[self.i % e.n_time].reshape(3, 3)
-        return device.visible_mask(e.x_true[self.i % e.H], M, self._sensor_consts[int(sensor)]).cpu().numpy().astype(bool)
+        row = self.i % e.n_time
+        M = e.trans[row].reshape(3, 3)
+        mask = device.visible_mask(e.x_true[self.i % e.H], M, self._sensor_consts[int(sensor)])
+        if self.sensor_sunlit_only[int(sensor)]:      # (the sensor kernels' rule at this time row, so that the helpers agree with step())
+            if (int(self.sun_dark[row]) >> int(sensor)) & 1:
+                mask = mask & device.sunlit_mask(e.x_true[self.i % e.H], e.sun[row], self.shadow_radius)
+            else:
+                mask = mask & 0
+        return mask.cpu().numpy().astype(bool)
 
     # (sensor=: a sensor network's site s; default the primary sensor, the only one without config['observers'])
     def visible_objects(self, sensor=0):

@@ -137,9 +137,14 @@ class SSA_Tasker_VecEnv:
         if S > 1:      # (noise per (env, sensor, time step): [E, S, n, 1, 3], sensor s scaled by its own z_sigma)
             from .. import host
             self._zs = torch.as_tensor(c.net.z_sigma, dtype=torch.float64, device="cuda").view(S, 1, 1, 3)
-            self._sensors = host.make_sensor_params(c.net.lla, c.net.obs_limit, c.net.R, self.n * 3, angles_only=c.net.angles_only)
+            self._sensors = host.make_sensor_params(c.net.lla, c.net.obs_limit, c.net.R, self.n * 3, angles_only=c.net.angles_only,
+                                                    sunlit_only=c.net.sunlit_only, shadow_radius=c.shadow_radius)
         # (config['sensor_measurement']: True where a sensor measures az and el only; without a network: the one az-el-range observer)
         self.sensor_angles_only = np.zeros(S, dtype=bool) if c.net is None else c.net.angles_only
+        # (config['sensor_illumination']: True where a sensor sees only sunlit objects, and only from a dark site; sun_table: the Sun's
+        # direction per row of the trans table -- one epoch, one table for all envs --, None unless a sensor asks for it)
+        self.sensor_sunlit_only = np.zeros(S, dtype=bool) if c.net is None else c.net.sunlit_only
+        self.sun_table, self.sun_dark, self.shadow_radius = c.sun, c.sun_dark, c.shadow_radius
         self._site = (c.obs_lla, c.obs_limit, c.R)      # (the env's own observer: a one-site network for lookahead_sensors)
         self._look_sites = None
         self._rows_host = None                          # step_agent: pinned [E, MAX_SENSORS] read-back of the action table
@@ -147,6 +152,8 @@ class SSA_Tasker_VecEnv:
         z = torch.randn((self.E,) + self._z_shape, dtype=torch.float64, device="cuda", generator=self._gen) * self._zs
         self._eng = engine.HotPathEngine(self._consts, self.m, self.E, c.trans, z, history=2,
                                          zn_stride_env=S * self.n * 3, zn_stride_time=3, zn_stride_obj=0)
+        if self.sun_table is not None:
+            self._eng.set_sun_table(self.sun_table, self.sun_dark, [self._sensors])
         self._rng = [np_random(seed + e)[0] for e in range(self.E)]
         self.single_action_space = spaces.MultiDiscrete([self.m] * S) if S > 1 else spaces.Discrete(self.m)
         self.single_observation_space = c.obs_space

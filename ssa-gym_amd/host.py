@@ -109,11 +109,27 @@ def make_consts(Q, R, alpha, beta, kappa, dt, obs_limit_rad, obs_lla, obs_type='
     return c
 
 
-def make_sensor_params(sites_lla, obs_limits_rad, Rs, zn_stride_sensor, angles_only=None):
+def pack_sun_rows(sun, dark):
+    """the rows of ssa_sensor_params.sun as one float64 array [n, 4]: sun [n, 3] unit vectors from the geocentre to the Sun (the frame
+    of x_true), dark [n] integers whose bit s says that site s is dark at that row (envs/sun.py: dark_sites) -- the word's BITS travel in
+    the fourth column"""
+    sun = np.asarray(sun, dtype=np.float64)
+    dark = np.asarray(dark, dtype=np.int64)
+    if sun.ndim != 2 or sun.shape[1] != 3 or dark.shape != (sun.shape[0],):
+        raise ValueError("a Sun table is [n, 3] vectors and [n] dark words, got %s and %s" % (sun.shape, dark.shape))
+    rows = np.empty((sun.shape[0], 4), dtype=np.float64)
+    rows[:, :3] = sun
+    rows[:, 3] = dark.view(np.float64)
+    return rows
+
+
+def make_sensor_params(sites_lla, obs_limits_rad, Rs, zn_stride_sensor, angles_only=None, sunlit_only=None, shadow_radius=R_EQ_EARTH):
     """pack a sensor network (include/ssa_hip.h: ssa_sensor_params): site s at sites_lla[s] = (lat [rad], lon [rad], h [m]) with elevation
     mask obs_limits_rad[s] and measurement noise covariance Rs[s] (3 x 3); sensor s's noise table starts zn_stride_sensor doubles after
     sensor s - 1's.  angles_only: S booleans, True where sensor s measures azimuth and elevation only (None: every sensor measures
-    az, el and range).  Every sensor idle (action -1) and no record destination: the caller sets `action` and `upd` per step."""
+    az, el and range).  sunlit_only: S booleans, True where sensor s sees only sunlit objects, and only while its site is dark (None: no
+    sensor tests the illumination); shadow_radius: the radius [m] of the Earth's cylindrical shadow.  The Sun table itself lives on the
+    device: engine.set_sun_table points the block at it (`sun` stays NULL here).  Every sensor idle (action -1) and no record destination: the caller sets `action` and `upd` per step."""
     S = len(sites_lla)
     if not 1 <= S <= _lib.MAX_SENSORS or len(obs_limits_rad) != S or len(Rs) != S:
         raise ValueError("a sensor network has 1 .. %d sites, each with one elevation mask and one R" % _lib.MAX_SENSORS)
@@ -133,5 +149,11 @@ def make_sensor_params(sites_lla, obs_limits_rad, Rs, zn_stride_sensor, angles_o
         sp.R[k][:] = np.asarray(Rs[k], dtype=np.float64).reshape(9)
     sp.zn_stride_sensor = int(zn_stride_sensor)
     sp.upd = 0
+    lit = [False] * S if sunlit_only is None else [bool(k) for k in sunlit_only]
+    if len(lit) != S:
+        raise ValueError("sunlit_only has %d entries for %d sensors" % (len(lit), S))
+    sp.sunlit_only = sum(1 << k for k in range(S) if lit[k])
+    sp.shadow_radius = float(shadow_radius) if any(lit) else 0.0
+    sp.sun, sp.reserved2 = 0, 0
     return sp
 
