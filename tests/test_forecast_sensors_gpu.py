@@ -10,12 +10,12 @@ import pytest
 
 from support.batches import c2t, make_batch
 from support.gpu import envs, hip  # noqa: F401  (the module fixtures)
-from support.sensors import BAD, N_TIME, _assert_same_env, _distinct, cfg8, sites_rad
+from support.sensors import BAD as BAD_AT, N_TIME, _assert_same_env, _distinct, cfg8, sites_rad
 
 pytestmark = pytest.mark.gpu
 
 MASKS_DEG = [15.0, 0.0, 30.0, 5.0, 20.0, -10.0, 10.0, 25.0]
-FAILED = 21           # the object whose filter had failed before the launch (BAD's state is NaN: it fails in the first predict)
+FAILED_AT = 21        # the object whose filter had failed before the launch (BAD's state is NaN: it fails in the first predict)
 KEYS = ("score", "status", "visible", "x_prior", "P_prior", "P_post")
 
 
@@ -41,6 +41,7 @@ def _engine_case(hip, m, H, S, propagator="hybrid", obs_type="aer", interval=1, 
     returns the yardstick's slabs"""
     torch, L, host = hip.torch, hip.lib, hip.host
     xt, x, P, g = make_batch(m, seed=123)
+    BAD, FAILED = BAD_AT % m, FAILED_AT % m     # (folded into a batch smaller than that)
     x[BAD, 1] = np.nan
     lla, lim = sites_rad()[:S], np.radians(MASKS_DEG[:S])
     if obs_type == "aer":
@@ -97,6 +98,8 @@ def _engine_case(hip, m, H, S, propagator="hybrid", obs_type="aer", interval=1, 
     sent = np.array([1e20] * 3 + [1e12] * 3)
     assert all(np.array_equal(xp[h, BAD], sent) and np.array_equal(Pp[h, BAD], np.diag(sent)) for h in range(H))
     healthy = (st == L.ST_OK).all(axis=(0, 1))
+    if m <= FAILED_AT:     # (a handful of objects: a tile's shape is the case, the sky's situations are the larger batches')
+        return fc
     # an object hidden from one site and visible from another, at a step that updates
     cross = [(h, s0, s1) for h in np.flatnonzero(upd) for s0 in range(S) for s1 in range(S)
              if (~vis[h, s0] & vis[h, s1] & healthy).any()]
@@ -114,9 +117,9 @@ def _engine_case(hip, m, H, S, propagator="hybrid", obs_type="aer", interval=1, 
     return fc
 
 
-@pytest.mark.parametrize("m,H,S", [(403, 9, 3), (2003, 5, 8), (30001, 3, 2)])
+@pytest.mark.parametrize("m,H,S", [(403, 9, 3), (2003, 5, 8), (30001, 3, 2), (7, 4, 3)])
 def test_forecast_equals_its_definition_hybrid(hip, m, H, S):
-    """a partial last tile; eight sites; more than 20 480 objects (several tiles per wavefront)"""
+    """a partial last tile; eight sites; more than 20 480 objects (several tiles per wavefront); one whole tile and a partial one"""
     _engine_case(hip, m, H, S)
 
 

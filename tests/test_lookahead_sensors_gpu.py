@@ -155,6 +155,16 @@ def test_multi_tile_instance_above_20480_objects(envs):
     check_against_step(env, net, rs, n=12)
 
 
+@pytest.mark.parametrize("m", [5, 7, 2003])
+def test_slices_with_a_ragged_last_tile(envs, m):
+    """object counts that are no multiple of a tile's four -- one whole tile and a partial one of one row, of three rows; a partial tile
+    behind 500 whole ones -- at step 0 and after two steps: every slice against the single-sensor lookahead"""
+    env = envs.make('ssa_tasker_simple-v2', config=cfg8(envs, m=m))
+    check_slices(env)
+    _advance(env, np.random.RandomState(m), 2)
+    check_slices(env)
+
+
 def test_one_sensor_equals_the_existing_lookahead(envs):
     """S = 1 -- an env without observers and a one-site network -- is env.lookahead() bit for bit"""
     base = cfg8(envs, sensors=0)
