@@ -228,6 +228,29 @@ typedef struct ssa_step_params {
                                   status / obs / metrics stay in storage order.  An object's arithmetic does not depend on its position. */
     const double *metrics_prev;/* with SSA_LAUNCH_STATS_FROM_METRICS and stat_shards_prev: the `metrics` block [4][m] the PREVIOUS step wrote (it must
                                   still hold that step's rows: the service wavefronts of this launch reduce its delta_pos row) */
+    /* ---- moving (space-based) sensors of a network, appended under ABI version 23: a zero tail is the behaviour before.
+     * A sensor s >= 1 of an ssa_sensor_params network with bit s of `site_moving` set is not a point on the Earth's surface: wherever a
+     * kernel would read ssa_sensor_params.enu[s] / obs_itrs[s] it reads row (t, s) of `site_rows` instead, t being the time row whose
+     * `trans` matrix the same update reads (step, every pass of a lookahead, step h of a forecast, a rollout's or dry run's step, each
+     * env's own time word in the *_envs entries).  The measurement arithmetic is unchanged: d = M x - obs, then the enu product.
+     * Visibility of such a sensor: ssa_sensor_params.obs_limit[s] is NOT read.  With o = the row's obs_itrs, d = M r - o for the object's
+     * true position r at the update, p = -(o.d), dd = d.d, oo = o.o:
+     *     clear   = (p <= 0) || (p >= dd) || (oo dd - p p >= R_b R_b dd)      the segment sensor -> object stays outside the sphere R_b
+     *     visible = clear && (no sunlit_only bit || object sunlit)            the Sun row's dark bit is NOT read for a moving sensor
+     * A NaN anywhere gives not visible; an object that fails is an invisible object in every respect (record, status, OBS_TAKEN, a
+     * lookahead score of NaN).  Measurement kinds, R, noise tables, failure handling, flags and propagators are untouched.
+     * With site_moving == 0 neither `site_rows` nor `limb_radius` is read.
+     * Refused before any launch, behind every other refusal of an entry -- SSA_E_INVALID by the entries that take an
+     * ssa_sensor_params: a site_moving bit at or above n_sensor, or bit 0 (sensor 0 is the primary observer of ssa_consts); any bit set
+     * while `site_rows` is NULL or not 128-byte aligned; any bit set while !(limb_radius >= 0); any bit set while obs_type is not
+     * SSA_OBS_AER -- SSA_E_UNSUPPORTED by the entries that take no ssa_sensor_params -- ssa_env_step_f64 and its profiled
+     * form, ssa_env_step_instance, ssa_env_rollout_f64, ssa_env_closed_loop_f64, ssa_lookahead_f64 --: any bit set. */
+    const double *site_rows;   /* [n_time][n_sensor][16] doubles on the device, base 128-byte aligned.  Row (t, s): enu[9] in the layout of
+                                  ssa_sensor_params.enu[s], obs_itrs[3], then 4 words that are 0.  Row t is the row whose `trans` the
+                                  same update reads.  Entries of sensors without a bit in site_moving are never read. */
+    double   limb_radius;      /* R_b [m]: the radius a moving sensor's line of sight must clear */
+    int32_t  site_moving;      /* bit s: sensor s takes enu / obs_itrs from site_rows and is screened by line of sight */
+    int32_t  reserved3;        /* 0 */
 } ssa_step_params;
 #define SSA_FAIL_STRIDE 8
 #define SSA_FAIL_ENV 0
@@ -373,6 +396,13 @@ int ssa_visible_mask_f64(const double *x_true, const double *M, const ssa_consts
  * cylindrical shadow of radius shadow_radius -- (p >= 0) || (d2 >= R R) with p = r.s, d2 = r.r - p p -- else 0; a NaN in r or s: 0.
  * The device function is the one the sensor kernels evaluate. */
 int ssa_sunlit_mask_f64(const double *x_true, const double *sun_row, double shadow_radius, uint8_t *mask, int64_t n, void *stream);
+/* EXTENSION, no reference counterpart: the line-of-sight rule of a moving sensor (ssa_step_params.site_moving), for the n true states
+ * x_true[n][6] against ONE `trans` row (9 doubles) and ONE 128-byte site row (enu[9], obs_itrs[3], 4 words that are not read), all on the
+ * device: mask[n] = 1 where the segment from the sensor to the object stays outside the sphere of radius limb_radius --
+ * (p <= 0) || (p >= dd) || (oo dd - p p >= R_b R_b dd) with d = M r - o, p = -(o.d), dd = d.d, oo = o.o -- else 0; a NaN anywhere: 0.
+ * The device function is the one the sensor kernels evaluate.  Refused (SSA_E_INVALID): a NULL pointer, n < 0. */
+int ssa_los_mask_f64(const double *x_true, const double *trans_row, const double *site_row, double limb_radius, uint8_t *mask, int64_t n,
+                     void *stream);
 /* O1/O2  observations() + error() for n objects of one env (results.py:61,37); metrics[4][n]. */
 int ssa_observe_f64(const double *x_true, const double *x, const double *P, double *obs, double *metrics,
                     int64_t n, void *stream);

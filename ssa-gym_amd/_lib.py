@@ -38,6 +38,7 @@ class ssa_step_params(C.Structure):
         ("spos_tiles", c_dp), ("spos_tiles_prev", c_dp),
         ("fail_log", c_dp), ("fail_count", c_dp), ("fail_cap", C.c_int32), ("reserved1", C.c_int32),
         ("obj_ids", c_dp), ("metrics_prev", c_dp),
+        ("site_rows", c_dp), ("limb_radius", C.c_double), ("site_moving", C.c_int32), ("reserved3", C.c_int32),
     ]
 
 
@@ -186,6 +187,7 @@ SIGNATURES = {
     "ssa_residual_z_aer_f64": (C.c_int, [c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_visible_mask_f64": (C.c_int, [c_dp, c_dp, C.POINTER(ssa_consts), c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_sunlit_mask_f64": (C.c_int, [c_dp, c_dp, C.c_double, c_dp, C.c_int64, c_dp]),
+    "ssa_los_mask_f64": (C.c_int, [c_dp, c_dp, c_dp, C.c_double, c_dp, C.c_int64, c_dp]),
     "ssa_observe_f64": (C.c_int, [c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_agent_scores_f64": (C.c_int, [c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(ssa_consts), c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_visible_mask_at_f64": (C.c_int, [c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.POINTER(ssa_consts), c_dp, c_dp, C.c_int64, c_dp]),

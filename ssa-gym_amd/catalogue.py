@@ -212,12 +212,16 @@ def visible_catalogue(n, seed=0, *, sites=(DEFAULT_SITE,), el_min_deg=15.0, t_0=
 def catalogue_for_config(config, n=20000, seed=0, **kw):
     """visible_catalogue for the sensors of an env_config dict: the sites of config['observers'] (else config['observer']), the masks of
     config['sensor_obs_limit'] (else el_min_deg, default 15 deg -- not the env's obs_limit, -90 by default, which accepts everything)
-    and config['t_0'].  Keyword arguments override these and pass through to visible_catalogue."""
+    and config['t_0'].  Keyword arguments override these and pass through to visible_catalogue.
+    The screen is on the GROUND sites only: a space-based sensor of config['observers'] ({'orbit': ...}) and its
+    sensor_obs_limit entry (None) are left out -- nothing is screened from orbit, so an object only such a sensor could see is dropped."""
     args = {}
     if config.get('observers') is not None:
-        args['sites'] = [tuple(s) for s in config['observers']]
+        orbiting = [isinstance(s, dict) for s in config['observers']]
+        args['sites'] = [tuple(s) for s, o in zip(config['observers'], orbiting) if not o]
         if config.get('sensor_obs_limit') is not None:
-            args['el_min_deg'] = list(config['sensor_obs_limit'])
+            lim = list(config['sensor_obs_limit'])
+            args['el_min_deg'] = [v for v, o in zip(lim, orbiting) if not o] if any(orbiting) and len(lim) == len(orbiting) else lim
     elif config.get('observer') is not None:
         args['sites'] = [tuple(config['observer'])]
     if config.get('t_0') is not None:

@@ -973,6 +973,34 @@ SSA_DEV int time_row(int tix, int n_time)
     if (n_time <= 0) return 0;
     return ((unsigned)tix < (unsigned)n_time) ? tix : tix % n_time;
 }
+// hx of a MOVING sensor s of a network (ssa_step_params.site_moving): hx_aer_enu with the sensor's 12 site words taken from row
+// (time row, s) of ssa_step_params.site_rows instead of the sites' block.  A network's tile belongs to one env, so the time row is the
+// wavefront's (the first active lane's), the row's address is formed from scalars and its 128 bytes come by scalar loads from the constant
+// address space -- nothing of the launch writes the table -- into scalar registers, where the block's site words live on the other path.
+// Issued here, behind the predict, whose lanes never wait for it.  lim: the mask every real elevation clears (a moving sensor has no
+// horizon).  Returns whether the sphere of limb_radius blocks the line of sight from the sensor to the lane's state x.
+SSA_DEV bool hx_moving_site(const ssa_step_params& p, int n_sensor, int s, int tix, const double* x, const double* M, double* z, double* R,
+                            double& lim)
+{
+    const int row = __builtin_amdgcn_readfirstlane(time_row(tix, p.n_time));
+    const ConstPtr<double> src = (ConstPtr<double>)__builtin_assume_aligned(p.site_rows, 128) + ((int64_t)row * n_sensor + s) * 16;
+    double site[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) site[i] = src[i];
+    hx_aer_enu(x, M, site, site + 9, z, R);
+    // the vector hx_aer_enu has just formed, behind a barrier: the rule's own products (d.d among them) must not be merged with those of
+    // hx_aer_enu's range -- under -ffp-contract=fast a shared d0 * d0 changes which product of the sum is fused, and the range then differs
+    // in its last bit from the one the ground path computes from the same words (tests/test_orbiting_gpu.py pins the equality).
+    // Every lane of the row evaluates the rule on its own state; only the truth lane's verdict (lane 13) reaches the broadcast that
+    // decides visibility -- the sigma lanes' is formed and dropped, which is cheaper than a lane test around a dozen instructions
+    double d[3];
+    observer_to_object(x, M, site + 9, d);
+    SSA_OPAQUE(d[0]);
+    SSA_OPAQUE(d[1]);
+    SSA_OPAQUE(d[2]);
+    lim = -__builtin_inf();
+    return !los_clear(d, site + 9, p.limb_radius);
+}
 
 // O4 for one object (ssa_tasker_simple_2.py:834-840): [hx(x_filter[:3]), trace(P)], NaN/inf -> 0.001
 SSA_DEV void aer_obs_row(const double* x, const double* P, const ssa_step_params& p, const ssa_consts& C, int e, int64_t obj)
@@ -1940,6 +1968,13 @@ SSA_DEV void process_wave(Tiles& t, const ssa_consts& C, const ssa_step_params& 
     // a sensor that sees sunlit objects only (ssa_sensor_params.sunlit_only; the row's sensor, or any of the lookahead's passes): the
     // 32-byte row of the Sun table at the SAME time row travels with the update's inputs, one word in each of the row's idle lanes 12..15
     // -- a network's tile belongs to one env, so the row is the wavefront's and every selected row brings the same four words
+    // ... and the word of the moving sensors (ssa_step_params.site_moving), fetched here once and held in a scalar register, so that no
+    // pass of a lookahead waits for it behind the predict
+    [[maybe_unused]] int32_t moving_bits = 0;
+    if constexpr (SENS || LSENS) {
+        moving_bits = p.site_moving;
+        asm volatile("" : "+s"(moving_bits));
+    }
     if constexpr (SENS || LSENS) {
         const int32_t sun_bits = asrc.sites()->sunlit_only;
         if (sun_bits != 0) {   // (wave-uniform: with no bit set nothing is loaded)
@@ -2208,6 +2243,7 @@ look_pass:
             double enu_vec[3];
             double el_mine;
             double lim = 0.0;   // (ActSensors: the elevation mask of the row's sensor)
+            bool blocked = false;   // (a moving sensor: the Earth stands between it and the lane's state)
             {
                 double Mm[9], aer[3];
 #pragma unroll
@@ -2217,14 +2253,20 @@ look_pass:
                     for (;;) {
                         const int su = __builtin_amdgcn_readfirstlane(sid);
                         if (sid == su) {
-                            hx_aer_enu(sf, Mm, SP->enu[su], SP->obs_itrs[su], aer, enu_vec);
-                            lim = SP->obs_limit[su];
+                            if ((moving_bits >> su) & 1) blocked = hx_moving_site(p, SP->n_sensor, su, tix, sf, Mm, aer, enu_vec, lim);
+                            else {
+                                hx_aer_enu(sf, Mm, SP->enu[su], SP->obs_itrs[su], aer, enu_vec);
+                                lim = SP->obs_limit[su];
+                            }
                             break;
                         }
                     }
                 } else if constexpr (LSENS) {   // (the pass's sensor: one site for the whole wavefront)
-                    hx_aer_enu(sf, Mm, SP->enu[look_s], SP->obs_itrs[look_s], aer, enu_vec);
-                    lim = SP->obs_limit[look_s];
+                    if ((moving_bits >> look_s) & 1) blocked = hx_moving_site(p, SP->n_sensor, look_s, tix, sf, Mm, aer, enu_vec, lim);
+                    else {
+                        hx_aer_enu(sf, Mm, SP->enu[look_s], SP->obs_itrs[look_s], aer, enu_vec);
+                        lim = SP->obs_limit[look_s];
+                    }
                 } else hx_aer_enu(sf, Mm, C.enu, C.obs_itrs, aer, enu_vec);
                 el_mine = aer[1];
                 if (PLAIN || C.obs_type == SSA_OBS_AER) { z[0] = aer[0]; z[1] = aer[1]; z[2] = aer[2]; }
@@ -2234,12 +2276,15 @@ look_pass:
                 // a sensor that sees sunlit objects only, from a dark site: lane 13 holds the propagated truth in sf and tests it against
                 // the Sun row the head left in LDS; an object that fails has no elevation (a NaN is below every mask), so that it is an
                 // invisible object in every respect and the broadcast below stays the one there was
+                // (a moving sensor has no night: the row's dark bit is not read for it, the object's own illumination still is -- and an
+                // object behind the Earth's limb has no elevation either, against the mask of -infinity hx_moving_site left in lim)
                 const int sun_s = SENS ? sid : look_s;
                 if ((SP->sunlit_only >> sun_s) & 1) {
                     const double* sun = &t.pad1[0];
-                    const bool dark = (__double_as_longlong(sun[3]) >> sun_s) & 1;
+                    const bool dark = (((__double_as_longlong(sun[3]) >> sun_s) | (long long)(moving_bits >> sun_s)) & 1) != 0;
                     if (!(dark && sunlit_cylinder(sf, sun, SP->shadow_radius))) el_mine = __builtin_nan("");
                 }
+                if (blocked) el_mine = __builtin_nan("");
                 visible = row_bcast<13>(el_mine) >= lim;   // (as seen from the row's sensor)
             } else visible = row_bcast<13>(el_mine) >= C.obs_limit;  // object_visible(): elevation of the TRUE state (:418-425)
             if (rec && l == 13) {
@@ -3639,6 +3684,22 @@ __global__ void sunlit_kernel(const double* __restrict__ x, const double* __rest
     if (i >= n) return;
     const double r[3] = {x[i * 6], x[i * 6 + 1], x[i * 6 + 2]}, s[3] = {sun_row[0], sun_row[1], sun_row[2]};
     mask[i] = sunlit_cylinder(r, s, shadow_radius) ? 1 : 0;
+}
+// the line-of-sight rule of a moving sensor (los_clear, on the vector hx_aer_enu forms) for n true states against ONE trans row and ONE
+// site row: a lane per object
+__global__ void los_kernel(const double* __restrict__ x, const double* __restrict__ trans_row, const double* __restrict__ site_row,
+                           double limb_radius, uint8_t* __restrict__ mask, int64_t n)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double M[9], o[3], d[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) M[k] = trans_row[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[k] = site_row[9 + k];
+    const double r[3] = {x[i * 6], x[i * 6 + 1], x[i * 6 + 2]};
+    observer_to_object(r, M, o, d);
+    mask[i] = los_clear(d, o, limb_radius) ? 1 : 0;
 }
 __global__ void observe_kernel(const double* __restrict__ xt, const double* __restrict__ x, const double* __restrict__ P,
                                double* __restrict__ obs, double* __restrict__ met, int64_t n)
@@ -5325,7 +5386,20 @@ static bool illumination_ok(const ssa_sensor_params* sp)
     const uint32_t bits = (uint32_t)sp->sunlit_only;
     return bits == 0 || ((bits >> sp->n_sensor) == 0 && sp->sun && ((uintptr_t)sp->sun & 31) == 0 && sp->shadow_radius >= 0.0);
 }
-static bool sensor_tail_ok(const ssa_consts* c, const ssa_sensor_params* sp) { return kinds_ok(c, sp) && illumination_ok(sp); }
+// ... and of the moving sensors (ssa_step_params.site_moving): no bit at or above n_sensor, not bit 0 (sensor 0 is the primary observer
+// of ssa_consts), and with any bit set a table of 128-byte rows, a limb radius that is a number >= 0 and the az-el-range observation
+static bool moving_ok(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp)
+{
+    const uint32_t bits = (uint32_t)p->site_moving;
+    return bits == 0 || ((bits >> sp->n_sensor) == 0 && !(bits & 1u) && p->site_rows && ((uintptr_t)p->site_rows & 127) == 0 &&
+                         p->limb_radius >= 0.0 && c->obs_type == SSA_OBS_AER);
+}
+// ... which an entry without a network cannot honour: its kernels read the one observer of ssa_consts.  Behind all its other rules
+static int no_moving_sites(const ssa_step_params* p) { return p->site_moving != 0 ? SSA_E_UNSUPPORTED : SSA_OK; }
+static bool sensor_tail_ok(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp)
+{
+    return kinds_ok(c, sp) && illumination_ok(sp) && moving_ok(c, p, sp);
+}
 // a network's sites as the kernels take them that read neither its action words nor its record destination
 static ssa_sensor_params idle_sites(const ssa_sensor_params* sp)
 {
@@ -5392,7 +5466,8 @@ static int step_launch(const ssa_consts* c, const ssa_step_params* p, void* stre
     TileGrid g;
     const int rc = step_args(c, p, sens != nullptr, g);
     if (rc != SSA_OK) return rc;
-    if (sens && !sensor_tail_ok(c, sens)) return SSA_E_INVALID;
+    if (sens && !sensor_tail_ok(c, p, sens)) return SSA_E_INVALID;
+    if (!sens && no_moving_sites(p) != SSA_OK) return no_moving_sites(p);
     StepK k;
     k.c = *c;
     k.p = *p;
@@ -5473,7 +5548,9 @@ int ssa_env_step_instance(const ssa_consts* c, const ssa_step_params* p)
 {
     TileGrid g;
     const int rc = step_args(c, p, false, g);
-    return rc != SSA_OK ? rc : (step_plain_form(c, p, false, g) ? 1 : 0);
+    if (rc != SSA_OK) return rc;
+    if (no_moving_sites(p) != SSA_OK) return no_moving_sites(p);
+    return step_plain_form(c, p, false, g) ? 1 : 0;
 }
 int ssa_env_step_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, void* stream)
 {
@@ -5541,6 +5618,7 @@ int ssa_lookahead_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_l
     LookK k;
     const int rc = lookahead_args(c, p, o, k);
     if (rc != SSA_OK) return rc;
+    if (no_moving_sites(p) != SSA_OK) return no_moving_sites(p);
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     dim3 grid((unsigned)g.nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
@@ -5570,7 +5648,7 @@ int ssa_lookahead_sensors_f64(const ssa_consts* c, const ssa_step_params* p, con
     LookSensK k;
     const int rc = lookahead_sensors_args(c, p, sp, o, false, k.k, k.s);
     if (rc != SSA_OK) return rc;
-    if (!sensor_tail_ok(c, sp)) return SSA_E_INVALID;
+    if (!sensor_tail_ok(c, p, sp)) return SSA_E_INVALID;
     const TileGrid g = tile_grid(p->n_obj);
     dim3 grid((unsigned)g.nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
@@ -5585,7 +5663,7 @@ int ssa_lookahead_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p
     VecLookSensK k;
     const int rc = lookahead_sensors_args(c, p, sp, o, true, k.k, k.s);
     if (rc != SSA_OK) return rc;
-    if (!sensor_tail_ok(c, sp)) return SSA_E_INVALID;
+    if (!sensor_tail_ok(c, p, sp)) return SSA_E_INVALID;
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     dim3 grid((unsigned)g.nwork), block(64);
     hipStream_t s = (hipStream_t)stream;
@@ -5602,7 +5680,7 @@ int ssa_forecast_sensors_f64(const ssa_consts* c, const ssa_step_params* p, cons
     ForeSensK k;
     const int rc = lookahead_sensors_args(c, p, sp, &f->out, false, lk, k.s);
     if (rc != SSA_OK) return rc;
-    if (f->n_steps < 1 || !sensor_tail_ok(c, sp)) return SSA_E_INVALID;
+    if (f->n_steps < 1 || !sensor_tail_ok(c, p, sp)) return SSA_E_INVALID;
     k.k = lk.k;
     k.k.p.launch_mask = 0;   // (the time word is read from env_time: a resident tile's steps do not see SSA_LAUNCH_INLINE_ENVS)
     k.f = *f;
@@ -5619,7 +5697,7 @@ int ssa_forecast_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p,
     VecForeSensK k;
     const int rc = lookahead_sensors_args(c, p, sp, &f->out, true, lk, k.s);
     if (rc != SSA_OK) return rc;
-    if (f->n_steps < 1 || !sensor_tail_ok(c, sp)) return SSA_E_INVALID;
+    if (f->n_steps < 1 || !sensor_tail_ok(c, p, sp)) return SSA_E_INVALID;
     k.k = lk.k;   // (launch_mask: SSA_LAUNCH_INLINE_ENVS alone survives lookahead_args, and the kernel reads inline_time by it)
     k.f = *f;
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
@@ -5638,7 +5716,7 @@ int ssa_dryrun_sensors_envs_f64(const ssa_consts* c, const ssa_step_params* p, c
     const int rc = lookahead_sensors_args(c, p, sp, &o, true, lk, k.s);
     if (rc != SSA_OK) return rc;
     if (d->n_steps < 1 || d->n_obj_caller < 1 || !row_aligned(d->actions)) return SSA_E_INVALID;
-    if (!rows_fit(p->n_env, sp->n_sensor, d->n_steps) || !sensor_tail_ok(c, sp)) return SSA_E_INVALID;
+    if (!rows_fit(p->n_env, sp->n_sensor, d->n_steps) || !sensor_tail_ok(c, p, sp)) return SSA_E_INVALID;
     k.k = lk.k;
     k.k.p.launch_mask = 0;   // (the time words are read from env_time: a resident tile's steps do not see SSA_LAUNCH_INLINE_ENVS)
     k.d = *d;
@@ -5706,6 +5784,7 @@ int ssa_env_rollout_f64(const ssa_consts* c, const ssa_step_params* p, const ssa
     RollK rk;
     const int rc = rollout_args(c, p, r, false, rk);
     if (rc != SSA_OK) return rc;
+    if (no_moving_sites(p) != SSA_OK) return no_moving_sites(p);
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     hipStream_t s = (hipStream_t)stream;
     with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(rollout_kernel<P>, dim3(g.nwork), dim3(64), 0, s, rk, (int)g.ntiles, g.nwork); });
@@ -5737,7 +5816,7 @@ int ssa_env_rollout_sensors_f64(const ssa_consts* c, const ssa_step_params* p, c
     RollSensK rk;
     const int rc = rollout_sensors_args(c, p, r, sp, rs->actions, false, rk.k, rk.s);
     if (rc != SSA_OK) return rc;
-    if (!sensor_tail_ok(c, sp)) return SSA_E_INVALID;
+    if (!sensor_tail_ok(c, p, sp)) return SSA_E_INVALID;
     rk.rs = *rs;
     const TileGrid g = tile_grid(p->n_obj);
     hipStream_t s = (hipStream_t)stream;
@@ -5751,7 +5830,7 @@ int ssa_env_rollout_sensors_envs_f64(const ssa_consts* c, const ssa_step_params*
     VecRollSensK rk;
     const int rc = rollout_sensors_args(c, p, r, sp, re->actions, true, rk.k, rk.s);
     if (rc != SSA_OK) return rc;
-    if (!re->stats_out || !sensor_tail_ok(c, sp)) return SSA_E_INVALID;
+    if (!re->stats_out || !sensor_tail_ok(c, p, sp)) return SSA_E_INVALID;
     rk.v = *re;
     const TileGrid g = tile_grid((int64_t)p->n_env * p->n_obj);
     hipStream_t s = (hipStream_t)stream;
@@ -5797,6 +5876,7 @@ int ssa_env_closed_loop_f64(const ssa_consts* c, const ssa_step_params* p, const
     if (ntiles + L.ng + 1 > cap) return SSA_E_UNSUPPORTED;   // every wavefront (compute + service) must be resident: the decision is a grid-wide exchange
     if (r->workspace_bytes < L.total * 8) return SSA_E_INVALID;
     if (r->wait_ticks < 0 || (r->flags & ~(SSA_LOOP_ARGMAX_SPOS | SSA_LOOP_DEBUG_WITHHOLD))) return SSA_E_INVALID;
+    if (no_moving_sites(p) != SSA_OK) return no_moving_sites(p);
     LoopK lk;
     lk.k.c = *c;
     lk.k.p = *p;
@@ -5948,6 +6028,15 @@ int ssa_sunlit_mask_f64(const double* x_true, const double* sun_row, double shad
     if (!x_true || !sun_row || !mask || n < 0) return SSA_E_INVALID;
     if (n == 0) return SSA_OK;
     hipLaunchKernelGGL(sunlit_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, x_true, sun_row, shadow_radius, mask, n);
+    return launch_status();
+}
+
+int ssa_los_mask_f64(const double* x_true, const double* trans_row, const double* site_row, double limb_radius, uint8_t* mask, int64_t n,
+                     void* stream)
+{
+    if (!x_true || !trans_row || !site_row || !mask || n < 0) return SSA_E_INVALID;
+    if (n == 0) return SSA_OK;
+    hipLaunchKernelGGL(los_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, x_true, trans_row, site_row, limb_radius, mask, n);
     return launch_status();
 }
 

@@ -788,13 +788,31 @@ SSA_DEV int robust_chol6(const double* A, double* U)
 // Also hands back R, the observer-local cartesian vector az / el / range are formed from: aer2uvw(z) (transformations.py
 // :284-297: r cos el cos az, r cos el sin az, r sin el) IS that vector, so the update's mean_z_uvw takes it from here
 // instead of going through two more sincos per sigma point.
-SSA_DEV void hx_aer_enu(const double* x, const double* M, const double* enu, const double* obs, double* z, double* R)
+// d = M x[:3] - obs: the vector from the observer to the object in the observer's frame (the first line of hx_aer_enu, stated once so
+// that the line-of-sight rule of a moving sensor -- los_clear -- judges the very vector the measurement is formed from)
+SSA_DEV void observer_to_object(const double* x, const double* M, const double* obs, double* d)
 {
-    double xi[3], d[3];
+    double xi[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) xi[i] = M[i * 3] * x[0] + M[i * 3 + 1] * x[1] + M[i * 3 + 2] * x[2];
 #pragma unroll
     for (int i = 0; i < 3; ++i) d[i] = xi[i] - obs[i];
+}
+// Does the segment from a sensor at o (geocentric) to the object at o + d stay outside the sphere of radius R about the geocentre?  With
+// p = -(o.d), dd = d.d, oo = o.o the closest point of the LINE lies at the fraction p / dd of the segment, and its squared distance is
+// oo - p p / dd: clear iff that point lies before the sensor (p <= 0) or beyond the object (p >= dd) -- both ends are outside the sphere,
+// which the callers guarantee for the sensor -- or outside the sphere, written without the division.  Every comparison is false for a
+// NaN, so that a NaN anywhere in o or d gives NOT clear.  A sphere: no flattening, no refraction (include/ssa_hip.h: ssa_step_params).
+SSA_DEV bool los_clear(const double* d, const double* o, double R)
+{
+    const double p = -dot3(o, d);
+    const double dd = dot3(d, d), oo = dot3(o, o);
+    return (p <= 0.0) || (p >= dd) || (oo * dd - p * p >= R * R * dd);
+}
+SSA_DEV void hx_aer_enu(const double* x, const double* M, const double* enu, const double* obs, double* z, double* R)
+{
+    double d[3];
+    observer_to_object(x, M, obs, d);
 #pragma unroll
     for (int j = 0; j < 3; ++j) R[j] = enu[j] * d[0] + enu[3 + j] * d[1] + enu[6 + j] * d[2];
     // elevation as atan2(u, hypot(e, n)) == asin(u / range) (better conditioned towards the zenith than the reference's asin)

@@ -165,6 +165,20 @@ def sunlit_mask(x_true, sun_row, shadow_radius):
     return mask
 
 
+def los_mask(x_true, trans_row, site_row, limb_radius):
+    """the sensor kernels' line-of-sight rule of a moving sensor (ssa_los_mask_f64) for every row of x_true[n,6] against one row of the
+    trans table, trans_row[9], and one row of a site table, site_row[16] = (enu[9], obs_itrs[3], 4 unread words), all on the device:
+    uint8 mask[n], 1 where the segment from the sensor to the object stays outside the sphere of radius limb_radius."""
+    lib = _lib.load()
+    n = x_true.shape[0]
+    mask = torch.empty(n, dtype=torch.uint8, device=x_true.device)
+    if trans_row.numel() < 9 or site_row.numel() < 12:
+        raise _lib.SsaHipError("trans_row must hold 9 words and site_row the 12 site words")
+    _lib.check(lib.ssa_los_mask_f64(_chk(x_true, "x_true"), _chk(trans_row, "trans_row"), _chk(site_row, "site_row"), float(limb_radius),
+                                    _chk(mask, "mask", torch.uint8), n, _stream()), "ssa_los_mask_f64")
+    return mask
+
+
 def catalogue_screen(elements, trans, sites, step, min_alt, first, max_gap, want_gap=False, want_flags=False):
     """catalogue._accepted for every candidate row of elements[n,6] (a, ecc, inc, raan, argp, nu), seen from a network of sites[S,13]
     (enu 9 as host.enu_matrix, obs_itrs 3, el_min [rad]) through trans[T,3,3]: accept[n] uint8, plus worst_gap[n] int32 and flags[n]

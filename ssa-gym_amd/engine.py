@@ -60,6 +60,8 @@ def _dry_target(p, g, ids):
 
 
 class HotPathEngine:
+    site_rows, _site_moving, limb_radius = None, 0, 0.0      # (until set_site_table: no sensor moves)
+
     def __init__(self, consts, n_obj, n_env, trans, z_noise, history, device_name="cuda",
                  zn_stride_env=None, zn_stride_time=None, zn_stride_obj=3):
         self._lib = _lib.load()
@@ -383,6 +385,8 @@ class HotPathEngine:
         p, pref, stats_ptr, metrics_ptr = self._step_params(slot_in, slot_out, aer_out, stats_out, upd_out, self._shard_cur if fast_stats else -1,
                                                shards_out, shards_clear, aer_cols, obs_mirror, argmax)
         p.time_offset = int(time_offset)
+        if sensors is not None or self._site_moving:      # (an engine without a site table -- every plain env -- pays one attribute read)
+            self._set_sites(p, sensors)
         p.actions = self._actions_ptr if actions_ptr is None else actions_ptr
         inline = _lib.LAUNCH_MIRROR_F32 if mirror_f32 else 0      # (obs_mirror / aer_out are float arrays: the host-facing copy in single precision)
         if env_words is not None:
@@ -464,6 +468,45 @@ class HotPathEngine:
         for sp in sensors:
             sp.sun = self.sun.data_ptr()
         return self.sun
+
+    def set_site_table(self, rows, moving, limb_radius):
+        """keep the site rows of this engine's moving (space-based) sensors on the device (include/ssa_hip.h: ssa_step_params.site_rows):
+        rows [n_time, S, 16] as host.pack_site_rows packs them (the same time rows as `trans`: one epoch, one table for all envs), moving S
+        booleans -- True where sensor s takes its site from the table and is screened by line of sight instead of an elevation mask
+        (never sensor 0) --, limb_radius [m] the sphere its line of sight must clear.  From now on every ssa_step_params block this engine
+        builds for a launch that takes a sensor network of S sensors carries the table; the launches without a network never do.
+        moving all False (or rows None) takes the table off.  Returns the device tensor."""
+        flags = [bool(k) for k in moving] if moving is not None else []
+        self._pcache.clear()      # (the cached step blocks may carry the table that was)
+        if rows is None or not any(flags):
+            self.site_rows, self._site_moving, self.limb_radius = None, 0, 0.0
+            self._set_sites(self._p, None)
+            return None
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        if rows.ndim != 3 or rows.shape[0] != self.n_time or rows.shape[1] != len(flags) or rows.shape[2] != host.SITE_ROW:
+            raise _lib.SsaHipError("the site table must be [%d, %d, %d] (trans rows x sensors x %d), got %s"
+                                   % (self.n_time, len(flags), host.SITE_ROW, host.SITE_ROW, rows.shape))
+        if flags[0] or len(flags) > _lib.MAX_SENSORS:
+            raise _lib.SsaHipError("sensor 0 is the primary observer and cannot move; a network has at most %d sensors" % _lib.MAX_SENSORS)
+        if not float(limb_radius) >= 0.0:
+            raise _lib.SsaHipError("limb_radius must be a number >= 0, got %r" % (limb_radius,))
+        dev = device.as_dev(rows, self.dev)
+        if dev.data_ptr() % 128:      # (the allocator's blocks are 512-byte aligned; a view would not be)
+            raise _lib.SsaHipError("the site table's device rows are not 128-byte aligned")
+        self.site_rows, self.limb_radius = dev, float(limb_radius)
+        self._site_moving = sum(1 << k for k, f in enumerate(flags) if f)
+        return dev
+
+    def _set_sites(self, p, sensors):
+        """the moving sensors' fields of the block `p` of a launch: the engine's table for a launch that takes the network `sensors`,
+        zeros for one that takes none (its entry would refuse them)"""
+        if sensors is None or not self._site_moving:
+            p.site_rows, p.limb_radius, p.site_moving = 0, 0.0, 0
+            return
+        if int(sensors.n_sensor) != self.site_rows.shape[1]:
+            raise _lib.SsaHipError("the engine's site table is that of %d sensors, the launch's network has %d"
+                                   % (self.site_rows.shape[1], int(sensors.n_sensor)))
+        p.site_rows, p.limb_radius, p.site_moving = self.site_rows.data_ptr(), self.limb_radius, self._site_moving
 
     def _check_sensor_noise(self, sensors, envs=False):
         """the extent of z_noise that the sensors of `sensors` index: sensor s reads z_noise[s * sensors.zn_stride_sensor ...]; envs: in
@@ -594,6 +637,7 @@ class HotPathEngine:
         ssa_forecast_params block.  Returns the result dict."""
         o, res = self._lookahead_out("launch_" + entry[4:-4], attr, lead, prior_lead, out)
         p = self._lookahead_params(slot_in, time_offset)
+        self._set_sites(p, sensors)
         if env_times is not None:
             if self.E > _lib.INLINE_ENVS:
                 raise _lib.SsaHipError("env_times: at most %d envs travel in the parameter block" % _lib.INLINE_ENVS)
@@ -714,6 +758,7 @@ class HotPathEngine:
         with _in_stream(stream):
             buf, (dev_words, dev_ids) = self._dry_buffers(self._dry, B, K, S, W, (words, ids[:, :W]))
             p = self._lookahead_params(slot_in, time_offset)
+            self._set_sites(p, sensors)
             if gather:
                 dev_ids = dev_ids.view(B, W)
                 # a padding row takes the state of the candidate's first object (object 0 for an all-idle candidate): a healthy row to predict
@@ -771,6 +816,7 @@ class HotPathEngine:
                                                 self.x_true[sl], self.x_filter[sl], self.P_filter[sl], self.status, E, B, self.m,
                                                 slot_of=self._slot_of32 if self._order is not None else None, out=buf.get("state"), stream=stream)
             p = self._lookahead_params(slot_in, time_offset)
+            self._set_sites(p, sensors)
             _dry_target(p, buf["state"], dev_ids)
             device.dryrun_sensors(self.consts, p, sensors, dev_words.view(K, EB, _lib.MAX_SENSORS), K, self.m, out=buf["out"], stream=stream)
         return buf["out"].view(K, E, B, S, _lib.DRY_STRIDE).permute(1, 2, 0, 3, 4)
@@ -836,7 +882,7 @@ class HotPathEngine:
         r.upd_ring, r.actions = self._bu, actions.data_ptr()
         _lib.check(self._lib.ssa_env_rollout_f64(self._cref, self._pref, C.byref(r), s), "ssa_env_rollout_f64")
 
-    def _rollout_params(self, slot_in, time_offset, K, argmax_spos, s):
+    def _rollout_params(self, slot_in, time_offset, K, argmax_spos, s, sensors=None):
         """what launch_rollout, launch_rollout_sensors and launch_rollout_sensors_envs share: pending statistics folded, the ssa_rollout_params block of K steps from
         history slot `slot_in` (rings, per-step shard sets and -- argmax_spos -- arg-max slots; actions and record ring left to the
         caller) and self._p made the parameter block of the first step"""
@@ -855,13 +901,14 @@ class HotPathEngine:
             if self._roll_spos is None or self._roll_spos.shape[0] < K:
                 self._roll_spos = torch.zeros((K, self.ntiles, 2), dtype=torch.int64, device=self.dev)
             r.spos_tiles = self._roll_spos.data_ptr()
-        self._first_step_block(time_offset)
+        self._first_step_block(time_offset, sensors)
         return r
 
-    def _first_step_block(self, time_offset):
-        """self._p made the parameter block of the first step of a multi-step launch (rollout, closed loop)"""
+    def _first_step_block(self, time_offset, sensors=None):
+        """self._p made the parameter block of the first step of a multi-step launch (rollout, closed loop; sensors: a network's)"""
         p = self._p
         p.time_offset = int(time_offset)
+        self._set_sites(p, sensors)
         p.launch_mask, p.stat_shards_prev, p.stats_prev, p.aer_out, p.metrics_prev = 0, 0, 0, 0, 0
         p.spos_tiles, p.spos_tiles_prev = 0, 0
 
@@ -881,7 +928,7 @@ class HotPathEngine:
         if upd is None or upd.shape[1] != S:
             upd = self.upd_sensors = torch.zeros((self.H, S, _lib.UPD_STRIDE), dtype=f64, device=self.dev)
         s = device._stream(stream)
-        r = self._rollout_params(slot_in, time_offset, int(actions.shape[0]), argmax_spos, s)
+        r = self._rollout_params(slot_in, time_offset, int(actions.shape[0]), argmax_spos, s, sensors)
         rs = _lib.ssa_rollout_sensors_params()
         rs.actions, rs.upd_ring = actions.data_ptr(), upd.data_ptr()
         _lib.check(self._lib.ssa_env_rollout_sensors_f64(self._cref, self._pref, C.byref(r), C.byref(sensors), C.byref(rs), s),
@@ -908,7 +955,7 @@ class HotPathEngine:
             out = self._roll_envs_out = (torch.zeros((K, self.E, _lib.STAT_STRIDE), dtype=f64, device=self.dev),
                                          torch.zeros((K if records else 0, self.E, S, _lib.UPD_STRIDE), dtype=f64, device=self.dev))
         s = device._stream(stream)
-        r = self._rollout_params(slot_in, time_offset, K, argmax_spos, s)
+        r = self._rollout_params(slot_in, time_offset, K, argmax_spos, s, sensors)
         re = _lib.ssa_rollout_sensors_envs_params()
         re.actions, re.stats_out, re.upd_out = actions.data_ptr(), out[0].data_ptr(), out[1].data_ptr() if records else 0
         _lib.check(self._lib.ssa_env_rollout_sensors_envs_f64(self._cref, self._pref, C.byref(r), C.byref(sensors), C.byref(re), s),

@@ -71,7 +71,7 @@ MAX_SENSORS = 8
 def resolve_sensors(config):
     """the sensor network of a config dict (EXTENSION, no reference counterpart), or None without config['observers']:
     {'sites': [(lat, lon, h)] * S (degrees, degrees, metres), 'obs_limit': [S] degrees or None, 'z_sigma': [S] or None,
-    'angles_only': [S] booleans, 'illumination': [S] of None or a limit in degrees}.
+    'angles_only': [S] booleans, 'illumination': [S] of None or a limit in degrees, 'orbit': [S] of None or a state of six}.
     config['observers'] lists 1 <= S <= 8 sites; the optional config['sensor_obs_limit'] / config['sensor_z_sigma'] give per-sensor
     values (S of them; default: the scalar obs_limit / z_sigma / R).  The optional config['sensor_measurement'] gives each sensor's
     measurement kind, S strings: 'aer' (azimuth, elevation, range: the default) or 'ae' (azimuth and elevation only, a telescope:
@@ -79,8 +79,40 @@ def resolve_sensors(config):
     one-observer kernels, which measure az, el and range).  The optional config['sensor_illumination'] gives each sensor None (no
     illumination test: a radar, the default) or a number: the sensor sees only sunlit objects, and only while the Sun is below that
     elevation (degrees, -90 .. 90; -12 is nautical twilight) at its site.  It is independent of the measurement kind and of obs_type
-    (a laser ranger needs sunlight too) and needs at least two sites, for the reason 'ae' does.  Anything else raises ValueError."""
+    (a laser ranger needs sunlight too) and needs at least two sites, for the reason 'ae' does.
+    A space-based sensor: an entry of config['observers'] may be {'orbit': [x, y, z, vx, vy, vz]} instead of a site -- the
+    sensor's state at t_0 in the frame of x_true, metres and m/s; the env propagates it to every row of the trans table on the device
+    (orbit_site_table).  Never entry 0: the primary sensor is a ground site.  Such a sensor has no elevation mask -- its line of sight
+    must clear the sphere of config['limb_radius'] instead --, so its config['sensor_obs_limit'] entry is None (the one place a None
+    may stand in that list), and no night: its config['sensor_illumination'] entry is None or the string 'sunlit' (the object outside
+    the Earth's shadow, no test of a site), never a number.  It needs obs_type 'aer'.  Its 'sites' entry is (0, 0, 0), a placeholder
+    no kernel reads.  Anything else raises ValueError."""
     sites = config.get('observers')
+    orbits = None
+    if sites is not None and not isinstance(sites, (str, dict)) and hasattr(sites, '__len__'):
+        orbits = [None] * len(sites)
+        ground = []
+        for k, ent in enumerate(sites):
+            if isinstance(ent, dict):
+                if set(ent) != {'orbit'}:
+                    raise ValueError("config['observers'][%d]: a space-based sensor is {'orbit': [x, y, z, vx, vy, vz]}, got %r" % (k, ent))
+                try:
+                    st = np.asarray(ent['orbit'], dtype=np.float64)
+                except (TypeError, ValueError):
+                    st = np.empty(0)
+                if st.shape != (6,) or not np.all(np.isfinite(st)):
+                    raise ValueError("config['observers'][%d]['orbit'] must be six finite values (x, y, z [m], vx, vy, vz [m/s]), got %r"
+                                     % (k, ent['orbit']))
+                if k == 0:
+                    raise ValueError("config['observers'][0] must be a ground site: the primary sensor (the env's own observer) cannot orbit")
+                if config.get('obs_type') != 'aer':
+                    raise ValueError("a space-based sensor needs obs_type 'aer', got %r" % (config.get('obs_type'),))
+                orbits[k] = st
+                ground.append((0.0, 0.0, 0.0))
+            else:
+                ground.append(ent)
+        if any(o is not None for o in orbits):
+            sites = ground
     illum = config.get('sensor_illumination')
     if sites is None and illum is not None:
         raise ValueError("config['sensor_illumination'] needs config['observers']")
@@ -99,6 +131,20 @@ def resolve_sensors(config):
     if arr.ndim != 2 or arr.shape[1] != 3 or not 1 <= arr.shape[0] <= MAX_SENSORS or not np.all(np.isfinite(arr)):
         raise ValueError("config['observers'] must list 1 .. %d sites (lat, lon, h), got %r" % (MAX_SENSORS, sites))
     S = arr.shape[0]
+    orbits = [None] * S if orbits is None else orbits
+    moving = [o is not None for o in orbits]
+    if lim is not None and any(moving):
+        # (an orbiting sensor's entry is None -- there is no elevation mask to give it -- and stands for the placeholder 0 below)
+        if isinstance(lim, str) or not hasattr(lim, '__len__') or len(lim) != S:
+            raise ValueError("config['sensor_obs_limit'] must give one elevation mask (degrees) per sensor: %d" % S)
+        lim = list(lim)
+        for k in range(S):
+            if moving[k] and lim[k] is not None:
+                raise ValueError("config['sensor_obs_limit'][%d] must be None: a space-based sensor has no elevation mask (its line of "
+                                 "sight clears config['limb_radius'] instead)" % k)
+            if not moving[k] and lim[k] is None:
+                raise ValueError("config['sensor_obs_limit'][%d]: a ground site needs an elevation mask (degrees)" % k)
+        lim = [0.0 if moving[k] else lim[k] for k in range(S)]
     if lim is not None:
         lim = np.asarray(lim, dtype=np.float64)
         if lim.shape != (S,) or not np.all(np.isfinite(lim)):
@@ -129,18 +175,23 @@ def resolve_sensors(config):
         if isinstance(illum, str) or not hasattr(illum, '__len__') or len(illum) != S:
             raise ValueError("config['sensor_illumination'] must give one entry per sensor (None or a Sun elevation limit in degrees): %d" % S)
         illum = list(illum)
-        for v in illum:
+        for k, v in enumerate(illum):
             if v is None:
+                continue
+            if moving[k]:      # (no site, no night: the object's own illumination or nothing)
+                if not (isinstance(v, str) and v == 'sunlit'):
+                    raise ValueError("config['sensor_illumination'][%d]: a space-based sensor takes None or 'sunlit' (the object outside "
+                                     "the Earth's shadow; there is no site whose Sun elevation a number could limit), got %r" % (k, v))
                 continue
             if isinstance(v, (bool, str)) or not np.isscalar(v) or not np.isreal(v) or not -90.0 <= float(v) <= 90.0:
                 raise ValueError("config['sensor_illumination']: every entry is None or a Sun elevation limit in [-90, 90] degrees, "
                                  "got %r" % (illum,))
-        illum = [None if v is None else float(v) for v in illum]
+        illum = [None if v is None else 0.0 if moving[k] else float(v) for k, v in enumerate(illum)]
         if S == 1 and illum[0] is not None:
             raise ValueError("config['sensor_illumination'] needs at least two sites -- with one site step(), rollout, run_agent, "
                              "run_policy and lookahead() run the one-observer kernels, whose visibility is the elevation mask alone")
     return {'sites': [tuple(float(v) for v in row) for row in arr], 'obs_limit': lim, 'z_sigma': zs,
-            'angles_only': [k == 'ae' for k in kinds], 'illumination': illum}
+            'angles_only': [k == 'ae' for k in kinds], 'illumination': illum, 'orbit': orbits}
 
 
 def resolve_config(config):
@@ -179,7 +230,9 @@ def resolve_config(config):
             zs, R = np.tile(c.z_sigma, (S, 1)), np.tile(c.R, (S, 1, 1))
         c.net = SimpleNamespace(lla=lla, obs_limit=lim, z_sigma=zs, R=R, angles_only=np.array(net['angles_only'], dtype=bool),
                                 sunlit_only=np.array([v is not None for v in net['illumination']], dtype=bool),
-                                sun_limit=np.radians([0.0 if v is None else v for v in net['illumination']]))
+                                sun_limit=np.radians([0.0 if v is None else v for v in net['illumination']]),
+                                moving=np.array([o is not None for o in net['orbit']], dtype=bool),
+                                orbit=[None if o is None else np.copy(o) for o in net['orbit']])
         c.obs_lla, c.obs_limit = lla[0], lim[0]
         c.z_sigma, c.R = zs[0], np.copy(R[0])
     c.obs_itrs = host.lla2ecef(c.obs_lla)
@@ -224,7 +277,55 @@ def resolve_config(config):
         else:
             c.sun = sun.sun_table(config['t_0'], c.dt, c.trans.shape[0])
         c.sun_dark = sun.dark_sites(c.trans, c.sun, c.net.lla, c.net.sun_limit)      # (a bit of a sensor without the test: not read)
+    # the space-based sensors (config['observers'] entries {'orbit': ...}): the sphere their line of sight must clear.  What
+    # needs no GPU is refused here -- the radius, a sensor that starts inside the sphere --, the rest by orbit_site_table at construction
+    c.limb_radius = float(config.get('limb_radius', host.R_EQ_EARTH + 100e3))
+    if c.net is not None and c.net.moving.any():
+        if not c.limb_radius >= 0.0:
+            raise ValueError("config['limb_radius'] must be a number >= 0, got %r" % (config.get('limb_radius'),))
+        for k in np.nonzero(c.net.moving)[0]:
+            if not np.linalg.norm(c.net.orbit[k][:3]) >= c.limb_radius:
+                raise ValueError("config['observers'][%d]: the orbit starts %.0f m from the geocentre, inside config['limb_radius'] = %.0f m"
+                                 % (k, np.linalg.norm(c.net.orbit[k][:3]), c.limb_radius))
     return c
+
+
+def orbit_site_table(c, config):
+    """the site rows of the space-based sensors of a resolved config `c` (resolve_config; `config` the dict it came from), float64
+    [n_time, S, 16] as host.pack_site_rows packs them, or None without one.  Needs the GPU: every orbit is propagated from its state at
+    t_0 to the epoch of every row of the trans table ON THE DEVICE, by the propagator the env's truth uses -- device.propagate (the
+    two-body solver of the kernel variant), or device.propagate_j2 for a J2 env --, one step of time_step after another exactly as the
+    truth of the objects it watches advances: a sensor is an object.  Row t of sensor s: host.orbit_site_rows of trans[t] and the
+    position at row t.  Raises ValueError for an orbit whose propagation fails (a NaN position) or that dips below config['limb_radius']
+    at any row."""
+    if c.net is None or not c.net.moving.any():
+        return None
+    import torch
+    from .. import device
+    idx = [int(k) for k in np.nonzero(c.net.moving)[0]]
+    n_time = c.trans.shape[0]
+    x = device.as_dev(np.stack([c.net.orbit[k] for k in idx]))
+    pos = torch.empty((n_time, len(idx), 3), dtype=torch.float64, device=x.device)
+    pos[0] = x[:, :3]
+    for t in range(1, n_time):
+        if c.consts.propagator == _lib.PROP_J2_RK4:
+            x = device.propagate_j2(x, c.dt, c.consts.j2, c.consts.r_eq, c.consts.rk4_substeps)
+        else:
+            x = device.propagate(x, c.dt, c.consts.propagator)
+        pos[t] = x[:, :3]
+    pos = pos.cpu().numpy()
+    S = c.n_sensor
+    enu, obs = np.zeros((n_time, S, 9)), np.zeros((n_time, S, 3))
+    for q, k in enumerate(idx):
+        r = np.linalg.norm(pos[:, q], axis=1)
+        if not np.all(np.isfinite(pos[:, q])):
+            raise ValueError("config['observers'][%d]: the orbit's propagation fails at time row %d"
+                             % (k, int(np.argmax(~np.isfinite(pos[:, q]).all(axis=1)))))
+        if not np.all(r >= c.limb_radius):
+            raise ValueError("config['observers'][%d]: the orbit dips to %.0f m from the geocentre at time row %d, below "
+                             "config['limb_radius'] = %.0f m" % (k, r.min(), int(np.argmin(r)), c.limb_radius))
+        enu[:, k], obs[:, k] = host.orbit_site_rows(c.trans.reshape(-1, 9), pos[:, q])
+    return host.pack_site_rows(enu, obs)
 
 
 def reward_done(reward_type, st, hit, paid, last, m, n):

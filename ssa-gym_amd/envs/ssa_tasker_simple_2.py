@@ -13,7 +13,7 @@ from datetime import timedelta
 import numpy as np
 
 from .. import _lib, host
-from ._config import draw_initial_state, resolve_config, reward_done
+from ._config import draw_initial_state, orbit_site_table, resolve_config, reward_done
 from ._gymshim import Env, np_random, spaces
 from ._policy import _PolicyLoop
 from ._tasking import SENSOR_AGENT_COLUMNS, SENSOR_AGENT_RULES, check_schedules, lookahead_result, network_sites, schedules_result, sensor_agent_rule
@@ -61,6 +61,12 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         # Sun's direction per row of trans_matrix, None unless a sensor asks for it; sun_dark: per row the word of the sites' dark bits)
         self.sensor_sunlit_only = np.zeros(c.n_sensor, dtype=bool) if c.net is None else c.net.sunlit_only
         self.sun_table, self.sun_dark, self.shadow_radius = c.sun, c.sun_dark, c.shadow_radius
+        # (config['observers'] entries {'orbit': ...}: True where a sensor is space-based, section 8v; site_table: its [n, S, 16] site rows
+        # per row of trans_matrix -- the orbit propagated on the device, here and now --, None without one; limb_radius: the sphere its
+        # line of sight must clear)
+        self.sensor_moving = np.zeros(c.n_sensor, dtype=bool) if c.net is None else c.net.moving
+        self.limb_radius = c.limb_radius
+        self.site_table = orbit_site_table(c, config)
         if c.net is not None:
             self.sensor_lla, self.sensor_obs_limit = c.net.lla, c.net.obs_limit
             self.sensor_z_sigma, self.sensor_R = c.net.z_sigma, c.net.R
@@ -147,6 +153,8 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
                                                     shadow_radius=self.shadow_radius)
             if self.sun_table is not None:      # (the packed table lives on the device next to trans; the block points at it)
                 e.set_sun_table(self.sun_table, self.sun_dark, [self._sensors])
+            if self.site_table is not None:     # (... and the moving sensors' site rows: every sensor launch of the engine carries them)
+                e.set_site_table(self.site_table, self.sensor_moving, self.limb_radius)
             self._upd_s_host = torch.zeros((self.n_sensor, _lib.UPD_STRIDE), dtype=torch.float64).pin_memory()
             self._upd_s_np, self._upd_s_ptr = self._upd_s_host.numpy(), self._upd_s_host.data_ptr()
         self._upd_host = torch.zeros(_lib.UPD_STRIDE, dtype=torch.float64).pin_memory()
@@ -761,9 +769,12 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         e = self._engine
         row = self.i % e.n_time
         M = e.trans[row].reshape(3, 3)
-        mask = device.visible_mask(e.x_true[self.i % e.H], M, self._sensor_consts[int(sensor)])
+        if self.sensor_moving[int(sensor)]:           # (a space-based sensor: line of sight instead of an elevation mask, and no night)
+            mask = device.los_mask(e.x_true[self.i % e.H], e.trans[row], e.site_rows[row, int(sensor)], self.limb_radius)
+        else:
+            mask = device.visible_mask(e.x_true[self.i % e.H], M, self._sensor_consts[int(sensor)])
         if self.sensor_sunlit_only[int(sensor)]:      # (the sensor kernels' rule at this time row, so that the helpers agree with step())
-            if (int(self.sun_dark[row]) >> int(sensor)) & 1:
+            if self.sensor_moving[int(sensor)] or (int(self.sun_dark[row]) >> int(sensor)) & 1:
                 mask = mask & device.sunlit_mask(e.x_true[self.i % e.H], e.sun[row], self.shadow_radius)
             else:
                 mask = mask & 0

@@ -30,7 +30,7 @@ is the same without a network.
 import numpy as np
 
 from .. import _lib
-from ._config import draw_initial_state, resolve_config, reward_done
+from ._config import draw_initial_state, orbit_site_table, resolve_config, reward_done
 from ._gymshim import np_random, spaces
 # (the agent table is one object: SENSOR_AGENTS is SSA_Tasker_Env.SENSOR_AGENT_COLUMNS, SENSOR_AGENT_RULES the env's of that name)
 from ._tasking import SENSOR_AGENT_COLUMNS as SENSOR_AGENTS, SENSOR_AGENT_RULES, sensor_agent_column, sensor_agent_rule  # noqa: F401
@@ -145,6 +145,11 @@ class SSA_Tasker_VecEnv:
         # direction per row of the trans table -- one epoch, one table for all envs --, None unless a sensor asks for it)
         self.sensor_sunlit_only = np.zeros(S, dtype=bool) if c.net is None else c.net.sunlit_only
         self.sun_table, self.sun_dark, self.shadow_radius = c.sun, c.sun_dark, c.shadow_radius
+        # (config['observers'] entries {'orbit': ...}: True where a sensor is space-based; site_table: its site rows per row of the trans
+        # table -- the orbit propagated on the device, one table for all envs --, None without one)
+        self.sensor_moving = np.zeros(S, dtype=bool) if c.net is None else c.net.moving
+        self.limb_radius = c.limb_radius
+        self.site_table = orbit_site_table(c, config)
         self._site = (c.obs_lla, c.obs_limit, c.R)      # (the env's own observer: a one-site network for lookahead_sensors)
         self._look_sites = None
         self._rows_host = None                          # step_agent: pinned [E, MAX_SENSORS] read-back of the action table
@@ -154,6 +159,8 @@ class SSA_Tasker_VecEnv:
                                          zn_stride_env=S * self.n * 3, zn_stride_time=3, zn_stride_obj=0)
         if self.sun_table is not None:
             self._eng.set_sun_table(self.sun_table, self.sun_dark, [self._sensors])
+        if self.site_table is not None:
+            self._eng.set_site_table(self.site_table, self.sensor_moving, self.limb_radius)
         self._rng = [np_random(seed + e)[0] for e in range(self.E)]
         self.single_action_space = spaces.MultiDiscrete([self.m] * S) if S > 1 else spaces.Discrete(self.m)
         self.single_observation_space = c.obs_space

@@ -123,6 +123,45 @@ def pack_sun_rows(sun, dark):
     return rows
 
 
+SITE_ROW = 16      # doubles per (time row, sensor) of ssa_step_params.site_rows: enu[9], obs_itrs[3], 4 zeros -- 128 bytes
+
+
+def pack_site_rows(enu, obs):
+    """the rows of ssa_step_params.site_rows as one float64 array [n_time, S, 16]: enu [n_time, S, 9] (or [n_time, S, 3, 3]) in the
+    element layout of enu_matrix / ssa_sensor_params.enu[s], obs [n_time, S, 3] the sensor's position in the frame `trans` maps into;
+    the last 4 words of every row are 0.  Rows of the sensors that do not move are never read: leave them 0."""
+    enu = np.asarray(enu, dtype=np.float64)
+    obs = np.asarray(obs, dtype=np.float64)
+    if enu.ndim == 4 and enu.shape[2:] == (3, 3):
+        enu = enu.reshape(enu.shape[0], enu.shape[1], 9)
+    if enu.ndim != 3 or enu.shape[2] != 9 or obs.shape != enu.shape[:2] + (3,):
+        raise ValueError("site rows are enu [n_time, S, 9] and obs [n_time, S, 3], got %s and %s" % (enu.shape, obs.shape))
+    if not 1 <= enu.shape[1] <= _lib.MAX_SENSORS or enu.shape[0] < 1:
+        raise ValueError("site rows need n_time >= 1 and 1 .. %d sensors, got %s" % (_lib.MAX_SENSORS, enu.shape[:2]))
+    rows = np.zeros(enu.shape[:2] + (SITE_ROW,), dtype=np.float64)
+    rows[:, :, :9] = enu
+    rows[:, :, 9:12] = obs
+    return rows
+
+
+def orbit_site_rows(trans, r_inertial):
+    """the site words of ONE orbiting sensor, (enu [n_time, 9], obs [n_time, 3]) for pack_site_rows: trans [n_time, 9] (or [n_time, 3, 3])
+    the matrices of ssa_step_params.trans, r_inertial [n_time, 3] the sensor's position at the same epochs in the frame of x_true.
+        obs_t = trans_t . r_t
+        enu_t = trans_t        (enu_matrix's element layout; the kernel applies it transposed: uvw[j] = sum_i enu[i][j] d[i])
+    so that the kernel's local vector uvw = enu_t^T (trans_t x - obs_t) is x - r_t itself, in INERTIAL axes: with hx_aer_enu's own
+    reading of it -- uvw = (north, east, up), az = atan2(east, north) -- east is y, north is x, up is z, the azimuth is the topocentric
+    right ascension, the elevation the topocentric declination and the range the slant range."""
+    trans = np.asarray(trans, dtype=np.float64)
+    r = np.asarray(r_inertial, dtype=np.float64)
+    if trans.ndim == 3 and trans.shape[1:] == (3, 3):
+        trans = trans.reshape(-1, 9)
+    if trans.ndim != 2 or trans.shape[1] != 9 or r.shape != (trans.shape[0], 3):
+        raise ValueError("an orbit's site rows need trans [n_time, 9] and r_inertial [n_time, 3], got %s and %s" % (trans.shape, r.shape))
+    obs = np.einsum('tij,tj->ti', trans.reshape(-1, 3, 3), r)
+    return trans.copy(), obs
+
+
 def make_sensor_params(sites_lla, obs_limits_rad, Rs, zn_stride_sensor, angles_only=None, sunlit_only=None, shadow_radius=R_EQ_EARTH):
     """pack a sensor network (include/ssa_hip.h: ssa_sensor_params): site s at sites_lla[s] = (lat [rad], lon [rad], h [m]) with elevation
     mask obs_limits_rad[s] and measurement noise covariance Rs[s] (3 x 3); sensor s's noise table starts zn_stride_sensor doubles after
