@@ -985,6 +985,41 @@ typedef struct ssa_screen_params {
 } ssa_screen_params;
 int ssa_catalogue_screen_f64(const ssa_screen_params *p, void *stream);
 
+/* EXTENSION (ABI 23, additive): the screen by a network's OWN visibility rule -- ssa_catalogue_screen_f64 with every sensor judged as
+ * the fused kernels judge it (ssa_step_params.site_rows / site_moving, ssa_sensor_params.sun / sunlit_only).  Candidates, samples, the
+ * altitude test and the fold of accept / worst_gap / flags from the per-sample verdicts are those of `base`, unchanged.  With r the
+ * candidate's inertial position at sample i (before the rotation) and x = trans[i] r, sensor s sees sample i if
+ *   no site_moving bit s:  asin(up_s / |x - obs_itrs_s|) >= el_min_s on base.sites[s]                (the ground mask, as above)
+ *   site_moving bit s:     los_clear(x - o, o, limb_radius), o = the obs_itrs words of site_rows row (i, s): the segment from the sensor
+ *                          to the object stays outside the sphere of radius limb_radius.  base.sites[s] is NOT read, nor the row's enu words
+ *   sunlit_only bit s:     additionally the object outside the Earth's cylindrical shadow -- (p >= 0) || (d2 >= R R), p = r.sun_i,
+ *                          d2 = r.r - p p, R = shadow_radius -- and, for a GROUND sensor, bit s of row i's dark word.  A moving sensor's
+ *                          dark bit is NOT read
+ * and a NaN anywhere gives "not visible".  A sample is visible if any sensor sees it.  seen_by[c] (optional): bit s set iff sensor s
+ * sees candidate c at one sample or more.  Row i of site_rows and of sun belongs to sample i, the sample trans[i] belongs to.
+ * Bit 0 of site_moving is ALLOWED here: the screen has no primary observer and no ssa_consts, so sensor 0 may be in orbit (a network
+ * of one space-based sensor).  The step entries keep refusing it.
+ * With site_moving == 0 neither site_rows nor limb_radius is read; with sunlit_only == 0 neither sun nor shadow_radius; with both 0
+ * the three outputs are those of ssa_catalogue_screen_f64 on `base`.
+ * Refused before any launch (SSA_E_INVALID), in this order: a NULL block; every refusal of ssa_catalogue_screen_f64 on `base`, in its
+ * order; reserved != 0; a site_moving bit at or above n_site; any such bit with site_rows NULL or not 128-byte aligned; any such bit
+ * with !(limb_radius >= 0); a sunlit_only bit at or above n_site; any such bit with sun NULL or not 32-byte aligned; any such bit with
+ * !(shadow_radius >= 0).  n == 0 launches nothing. */
+typedef struct ssa_screen_network_params {
+    ssa_screen_params base;     /* every field with its present meaning */
+    const double *site_rows;    /* [base.n_time][base.n_site][16]; layout and 128-byte base alignment of ssa_step_params.site_rows;
+                                   row (i, s) belongs to sample i, the sample trans[i] belongs to; read only for sensors with a bit
+                                   in site_moving */
+    const double *sun;          /* [base.n_time] rows of 32 bytes; layout and 32-byte base alignment of ssa_sensor_params.sun
+                                   (sx, sy, sz in the frame of the candidate's inertial position, then the int64 word of dark bits);
+                                   read only if sunlit_only != 0 */
+    double limb_radius, shadow_radius;
+    int32_t site_moving, sunlit_only;   /* bit s, as in ssa_step_params / ssa_sensor_params */
+    uint8_t *seen_by;           /* [n] or NULL: bit s set iff sensor s sees the candidate at one sample or more */
+    int64_t reserved;           /* 0 */
+} ssa_screen_network_params;
+int ssa_catalogue_screen_network_f64(const ssa_screen_network_params *p, void *stream);
+
 /* ------------------------------------------------ all-gather by direct peer stores (SURVEY 8e "Collective")
  * The reference runs one env per process and has no exchange step; the sharded env of this library (one env's objects spread over the
  * GPUs of a node) reassembles every step's observation block + statistics words on every rank.  These two entry points do that without a

@@ -109,6 +109,13 @@ class ssa_screen_params(C.Structure):
     ]
 
 
+class ssa_screen_network_params(C.Structure):
+    _fields_ = [
+        ("base", ssa_screen_params), ("site_rows", c_dp), ("sun", c_dp), ("limb_radius", C.c_double), ("shadow_radius", C.c_double),
+        ("site_moving", C.c_int32), ("sunlit_only", C.c_int32), ("seen_by", c_dp), ("reserved", C.c_int64),
+    ]
+
+
 # constants of include/ssa_hip.h
 E_INVALID, E_LAUNCH, E_UNSUPPORTED = -1, -2, -3
 ABI_VERSION = 23
@@ -215,6 +222,7 @@ SIGNATURES = {
     "ssa_nis_f64": (C.c_int, [c_dp, c_dp, c_dp, C.c_int64, c_dp]),
     "ssa_chi2_contained_f64": (C.c_int, [c_dp, C.c_int64, C.c_double, C.c_double, c_dp, c_dp]),
     "ssa_catalogue_screen_f64": (C.c_int, [C.POINTER(ssa_screen_params), c_dp]),
+    "ssa_catalogue_screen_network_f64": (C.c_int, [C.POINTER(ssa_screen_network_params), c_dp]),
 }
 
 _lib = None

@@ -214,7 +214,8 @@ def catalogue_for_config(config, n=20000, seed=0, **kw):
     config['sensor_obs_limit'] (else el_min_deg, default 15 deg -- not the env's obs_limit, -90 by default, which accepts everything)
     and config['t_0'].  Keyword arguments override these and pass through to visible_catalogue.
     The screen is on the GROUND sites only: a space-based sensor of config['observers'] ({'orbit': ...}) and its
-    sensor_obs_limit entry (None) are left out -- nothing is screened from orbit, so an object only such a sensor could see is dropped."""
+    sensor_obs_limit entry (None) are left out -- nothing is screened from orbit, so an object only such a sensor could see is dropped.
+    catalogue_for_network screens by the network's own rule instead: from orbit, and with a telescope's night and the Earth's shadow."""
     args = {}
     if config.get('observers') is not None:
         orbiting = [isinstance(s, dict) for s in config['observers']]
@@ -228,6 +229,194 @@ def catalogue_for_config(config, n=20000, seed=0, **kw):
         args['t_0'] = config['t_0']
     args.update(kw)
     return visible_catalogue(n, seed, **args)
+
+
+def _network_sensors(sensors, el_min_deg, illumination):
+    """the sensors of visible_catalogue_network, checked (no GPU): (sites [S] of (lat, lon, h) with (0, 0, 0) in an orbit's place, masks
+    [S] in degrees with 0 in an orbit's place, orbits [S] of a state [6] or None, sun limits [S] in degrees or None, sunlit_only word).
+    Anything else raises ValueError."""
+    if isinstance(sensors, (str, dict)) or not hasattr(sensors, '__len__') or not 1 <= len(sensors) <= MAX_SITES:
+        raise ValueError("sensors must list 1 .. %d entries, (lat, lon, h) or {'orbit': [x, y, z, vx, vy, vz]}, got %r" % (MAX_SITES, sensors))
+    S = len(sensors)
+    sites, orbits = [], []
+    for k, ent in enumerate(sensors):
+        if isinstance(ent, dict):
+            if set(ent) != {'orbit'}:
+                raise ValueError("sensors[%d]: a space-based sensor is {'orbit': [x, y, z, vx, vy, vz]}, got %r" % (k, ent))
+            try:
+                st = np.asarray(ent['orbit'], dtype=np.float64)
+            except (TypeError, ValueError):
+                st = np.empty(0)
+            if st.shape != (6,) or not np.all(np.isfinite(st)):
+                raise ValueError("sensors[%d]['orbit'] must be six finite values (x, y, z [m], vx, vy, vz [m/s]), got %r" % (k, ent['orbit']))
+            orbits.append(st)
+            sites.append((0.0, 0.0, 0.0))
+        else:
+            orbits.append(None)
+            sites.append(ent)
+    moving = [o is not None for o in orbits]
+    if np.ndim(el_min_deg) == 0 and el_min_deg is not None:
+        masks = [0.0 if m else el_min_deg for m in moving]
+    else:
+        if isinstance(el_min_deg, str) or not hasattr(el_min_deg, '__len__') or len(el_min_deg) != S:
+            raise ValueError("el_min_deg must be one elevation mask (degrees) or one entry per sensor (None for an orbit): %d" % S)
+        for k, v in enumerate(el_min_deg):
+            if moving[k] != (v is None):
+                raise ValueError("el_min_deg[%d]: a space-based sensor takes None (its line of sight clears limb_radius instead), a ground "
+                                 "site an elevation mask in degrees, got %r" % (k, v))
+        masks = [0.0 if m else v for m, v in zip(moving, el_min_deg)]
+    _site_table(sites, masks)      # (the sites and masks themselves: finite numbers, three per site)
+    if illumination is None:
+        illumination = [None] * S
+    if isinstance(illumination, str) or not hasattr(illumination, '__len__') or len(illumination) != S:
+        raise ValueError("illumination must be None or one entry per sensor: %d" % S)
+    limits, word = [], 0
+    for k, v in enumerate(illumination):
+        if v is None:
+            limits.append(None)
+            continue
+        if moving[k]:
+            if not (isinstance(v, str) and v == 'sunlit'):
+                raise ValueError("illumination[%d]: a space-based sensor takes None or 'sunlit', got %r" % (k, v))
+            limits.append(0.0)      # (no site, no night: the dark bit of a moving sensor is never read)
+        else:
+            if isinstance(v, (bool, str)) or not np.isscalar(v) or not np.isreal(v) or not -90.0 <= float(v) <= 90.0:
+                raise ValueError("illumination[%d]: a ground site takes None or a Sun elevation limit in [-90, 90] degrees, got %r" % (k, v))
+            limits.append(float(v))
+        word |= 1 << k
+    return sites, masks, orbits, limits, word
+
+
+def _orbit_positions(orbits, step, T, limb_radius):
+    """[T, S, 3]: every orbiting sensor's inertial position at the samples i * step, by repeated two-body steps of `step` on the device
+    (device.propagate, as _config.orbit_site_table); zeros for a ground site.  ValueError for an orbit that fails or dips below limb_radius."""
+    import torch
+    from . import device
+    idx = [k for k, o in enumerate(orbits) if o is not None]
+    x = device.as_dev(np.stack([orbits[k] for k in idx]))
+    dev_pos = torch.empty((T, len(idx), 3), dtype=torch.float64, device=x.device)
+    dev_pos[0] = x[:, :3]
+    for t in range(1, T):
+        x = device.propagate(x, step)
+        dev_pos[t] = x[:, :3]
+    dev_pos = dev_pos.cpu().numpy()
+    pos = np.zeros((T, len(orbits), 3))
+    for q, k in enumerate(idx):
+        if not np.all(np.isfinite(dev_pos[:, q])):
+            raise ValueError("sensors[%d]: the orbit's propagation fails at sample %d" % (k, int(np.argmax(~np.isfinite(dev_pos[:, q]).all(axis=1)))))
+        r = np.linalg.norm(dev_pos[:, q], axis=1)
+        if not np.all(r >= limb_radius):
+            raise ValueError("sensors[%d]: the orbit dips to %.0f m from the geocentre at sample %d, below limb_radius = %.0f m"
+                             % (k, r.min(), int(np.argmin(r)), limb_radius))
+        pos[:, k] = dev_pos[:, q]
+    return pos
+
+
+def visible_catalogue_network(n, seed=0, *, sensors, el_min_deg=15.0, illumination=None, t_0=datetime(2020, 5, 4), step=150.0,
+                              duration=4 * 3600.0, first_window=45 * 60.0, max_gap=1.5 * 3600.0, min_altitude=300e3,
+                              limb_radius=RE_EQ + 100e3, shadow_radius=RE_EQ, sun_table=None):
+    """visible_catalogue by the network's OWN visibility rule (ssa_catalogue_screen_network_f64): the same draw loop
+    (_draw: same RandomState(seed), regimes, batches and element draws), the same altitude floor, first window and gap rule, but
+    sensor s sees a sample as the env's kernels would let it.
+      sensors: 1 .. 8 entries, each a ground site (lat, lon, h; deg, deg, m) or a space-based sensor {'orbit': [x, y, z, vx, vy, vz]},
+        its state at t_0 in the frame of x_true -- at any position of the list, position 0 included (the screen has no primary observer).
+      el_min_deg: one elevation mask for every ground site, or one entry per sensor with None for an orbit, whose line of sight must
+        clear the sphere of limb_radius (host.R_EQ_EARTH + 100 km) instead.
+      illumination: None, or one entry per sensor as config['sensor_illumination']: for a ground site None or the Sun elevation limit in
+        degrees below which the site is dark; for an orbit None or 'sunlit'.  A sensor with an entry sees only candidates outside the
+        Earth's cylindrical shadow of shadow_radius (host.R_EQ_EARTH), a ground site only while it is dark.
+    The tables stand at the screen's own samples t_0 + i * step: trans_matrix_table, the Sun (envs.sun.sun_table, or sun_table [T, 3]
+    unit vectors in the frame of x_true), the sites' dark words (envs.sun.dark_sites) and every orbit's positions.  An orbit is
+    propagated on the device by repeated steps of `step` (device.propagate): TWO-BODY, whatever propagator an env will use later -- the
+    screen's candidates are two-body too.  An orbit that fails or dips below limb_radius at any sample raises ValueError, as every bad
+    shape does.  With ground sites only and no illumination the rows are visible_catalogue's exactly.  Always draws; needs the
+    library and a GPU."""
+    n, step, duration = int(n), float(step), float(duration)
+    if n < 0:
+        raise ValueError("n must be >= 0, got %d" % n)
+    if not np.isfinite(step) or step <= 0:
+        raise ValueError("step must be a positive number of seconds, got %r" % step)
+    if not np.isfinite(duration) or duration < step:
+        raise ValueError("duration must be at least one step (%r s), got %r" % (step, duration))
+    for name, v in (("first_window", first_window), ("max_gap", max_gap), ("min_altitude", min_altitude)):
+        if not np.isfinite(float(v)) or (name != "min_altitude" and float(v) < 0):
+            raise ValueError("%s must be a finite%s number, got %r" % (name, "" if name == "min_altitude" else " non-negative", v))
+    sites, masks, orbits, limits, sunlit_only = _network_sensors(sensors, el_min_deg, illumination)
+    S = len(sites)
+    site_moving = sum(1 << k for k, o in enumerate(orbits) if o is not None)
+    T = int(np.ceil(duration / step))
+    first, gap = int(first_window / step), int(max_gap / step)
+    if site_moving:
+        if not float(limb_radius) >= 0.0:
+            raise ValueError("limb_radius must be a number >= 0, got %r" % (limb_radius,))
+        for k, o in enumerate(orbits):
+            if o is not None and not np.linalg.norm(o[:3]) >= limb_radius:
+                raise ValueError("sensors[%d]: the orbit starts %.0f m from the geocentre, inside limb_radius = %.0f m"
+                                 % (k, np.linalg.norm(o[:3]), limb_radius))
+    sun_vec = None
+    if sunlit_only:
+        if not float(shadow_radius) >= 0.0:
+            raise ValueError("shadow_radius must be a number >= 0, got %r" % (shadow_radius,))
+        if sun_table is not None:
+            sun_vec = np.array(sun_table, dtype=np.float64)
+            if sun_vec.shape != (T, 3):
+                raise ValueError("sun_table must be %s unit vectors, one per sample t_0 + i * step, got %s" % ((T, 3), sun_vec.shape))
+    from .envs.transformations import trans_matrix_table
+    from .envs import sun as sun_mod
+    from . import _lib, device, host
+    import torch
+    tab = _site_table(sites, masks)
+    M_t = trans_matrix_table(t_0, step, T)
+    sun_rows = None
+    if sunlit_only:
+        if sun_vec is None:
+            sun_vec = sun_mod.sun_table(t_0, step, T)
+        lla = np.array(sites, dtype=np.float64) * [host.deg2rad, host.deg2rad, 1]
+        dark = sun_mod.dark_sites(M_t, sun_vec, lla, np.radians([0.0 if v is None else v for v in limits]))
+        sun_rows = host.pack_sun_rows(sun_vec, dark)
+    _lib.load()
+    if not torch.cuda.is_available():
+        raise _lib.SsaHipError("visible_catalogue_network screens on the GPU (there is no CPU fallback): no device")
+    rows = None
+    if site_moving:
+        pos = _orbit_positions(orbits, step, T, float(limb_radius))
+        enu, obs = np.zeros((T, S, 9)), np.zeros((T, S, 3))
+        for k, o in enumerate(orbits):
+            if o is not None:
+                enu[:, k], obs[:, k] = host.orbit_site_rows(M_t.reshape(-1, 9), pos[:, k])
+        rows = device.as_dev(host.pack_site_rows(enu, obs))
+    trans, site_tab = device.as_dev(M_t), device.as_dev(tab)
+    sun_dev = None if sun_rows is None else device.as_dev(sun_rows)
+
+    def screen(cand):
+        acc = device.catalogue_screen_network(device.as_dev(np.stack(cand, axis=1)), trans, site_tab, step, min_altitude, first, gap,
+                                              site_rows=rows, site_moving=site_moving, limb_radius=limb_radius, sun=sun_dev,
+                                              sunlit_only=sunlit_only, shadow_radius=shadow_radius)
+        return acc.cpu().numpy().astype(bool)
+    return _draw(n, seed, screen)
+
+
+def catalogue_for_network(config, n=20000, seed=0, **kw):
+    """visible_catalogue_network for the sensors of an env_config dict: config['observers'] (else config['observer']) with the
+    space-based ones kept, config['sensor_obs_limit'], config['sensor_illumination'], config['limb_radius'], config['shadow_radius'] and
+    config['t_0'].  Keyword arguments override these and pass through.  A config['sun_table'] stands on the ENV's time rows (t_0 + i *
+    time_step), not on the screen's samples: a config that has one raises ValueError unless the caller passes sun_table= for the
+    screen's own samples."""
+    args = {}
+    if config.get('observers') is not None:
+        args['sensors'] = [dict(s) if isinstance(s, dict) else tuple(s) for s in config['observers']]
+    elif config.get('observer') is not None:
+        args['sensors'] = [tuple(config['observer'])]
+    if config.get('observers') is not None and config.get('sensor_obs_limit') is not None:
+        args['el_min_deg'] = list(config['sensor_obs_limit'])
+    for key, name in (('sensor_illumination', 'illumination'), ('limb_radius', 'limb_radius'), ('shadow_radius', 'shadow_radius'),
+                      ('t_0', 't_0')):
+        if config.get(key) is not None:
+            args[name] = list(config[key]) if key == 'sensor_illumination' else config[key]
+    if config.get('sun_table') is not None and kw.get('sun_table') is None:
+        raise ValueError("config['sun_table'] is on the env's time rows, not the screen's samples: pass sun_table= [T, 3] for t_0 + i * step")
+    args.update(kw)
+    return visible_catalogue_network(n, seed, **args)
 
 
 def regime_order(x, tile=4, n_xcd=8, one_tile_limit=20480):

@@ -6059,12 +6059,39 @@ int ssa_visible_mask_at_f64(const double* x_true, const double* trans, const int
     return launch_status();
 }
 
-int ssa_catalogue_screen_f64(const ssa_screen_params* p, void* stream)
+// the refusals of the ground-mask screen, stated once for both screen entries (the pointers matter only where something would launch)
+static int screen_refused(const ssa_screen_params* p)
 {
     if (!p || p->n < 0 || p->n_time < 1 || p->n_site < 1 || p->n_site > SSA_MAX_SENSORS || p->first < 0) return SSA_E_INVALID;
+    if (p->n > 0 && (!p->elements || !p->trans || !p->sites || !p->accept)) return SSA_E_INVALID;
+    return SSA_OK;
+}
+
+int ssa_catalogue_screen_f64(const ssa_screen_params* p, void* stream)
+{
+    if (screen_refused(p) != SSA_OK) return SSA_E_INVALID;
     if (p->n == 0) return SSA_OK;
-    if (!p->elements || !p->trans || !p->sites || !p->accept) return SSA_E_INVALID;
     hipLaunchKernelGGL(catalogue_screen_kernel, dim3(nblk(p->n, SSA_SCREEN_WAVES)), dim3(64 * SSA_SCREEN_WAVES), 0, (hipStream_t)stream, *p);
+    return launch_status();
+}
+
+int ssa_catalogue_screen_network_f64(const ssa_screen_network_params* q, void* stream)
+{
+    if (!q || screen_refused(&q->base) != SSA_OK || q->reserved != 0) return SSA_E_INVALID;
+    const uint32_t beyond = ~0u << q->base.n_site;      // (n_site is 1 .. 8 here)
+    if (q->site_moving != 0) {
+        if ((uint32_t)q->site_moving & beyond) return SSA_E_INVALID;
+        if (!q->site_rows || ((uintptr_t)q->site_rows & 127) != 0) return SSA_E_INVALID;
+        if (!(q->limb_radius >= 0.0)) return SSA_E_INVALID;
+    }
+    if (q->sunlit_only != 0) {
+        if ((uint32_t)q->sunlit_only & beyond) return SSA_E_INVALID;
+        if (!q->sun || ((uintptr_t)q->sun & 31) != 0) return SSA_E_INVALID;
+        if (!(q->shadow_radius >= 0.0)) return SSA_E_INVALID;
+    }
+    if (q->base.n == 0) return SSA_OK;
+    hipLaunchKernelGGL(catalogue_screen_network_kernel, dim3(nblk(q->base.n, SSA_SCREEN_WAVES)), dim3(64 * SSA_SCREEN_WAVES), 0,
+                       (hipStream_t)stream, *q);
     return launch_status();
 }
 

@@ -198,6 +198,37 @@ def catalogue_screen(elements, trans, sites, step, min_alt, first, max_gap, want
         return accept
     return (accept,) + ((gap,) if want_gap else ()) + ((flags,) if want_flags else ())
 
+
+def catalogue_screen_network(elements, trans, sites, step, min_alt, first, max_gap, *, site_rows=None, site_moving=0, limb_radius=0.0,
+                             sun=None, sunlit_only=0, shadow_radius=0.0, want_gap=False, want_flags=False, want_seen_by=False):
+    """catalogue_screen by the network's own visibility rule (ssa_catalogue_screen_network_f64): sensor s with bit s of site_moving is
+    screened by line of sight from its rows of site_rows[T,S,16] (host.pack_site_rows) past the sphere of limb_radius -- sites[s] is
+    not read --, sensor s with bit s of sunlit_only additionally needs the candidate outside the Earth's cylindrical shadow of
+    shadow_radius and, on the ground, bit s of the dark word of sun[T,4] (host.pack_sun_rows).  Returns accept[n] uint8, plus
+    worst_gap[n] int32, flags[n] uint8 and seen_by[n] uint8 (bit s: sensor s sees the candidate at some sample) on request, in that
+    order.  With both words 0 the outputs are catalogue_screen's."""
+    lib = _lib.load()
+    n, dev = elements.shape[0], elements.device
+    T, S = trans.shape[0], sites.shape[0]
+    accept = torch.empty(n, dtype=torch.uint8, device=dev)
+    gap = torch.empty(n, dtype=torch.int32, device=dev) if want_gap else None
+    flags = torch.empty(n, dtype=torch.uint8, device=dev) if want_flags else None
+    seen = torch.empty(n, dtype=torch.uint8, device=dev) if want_seen_by else None
+    p = _lib.ssa_screen_network_params(
+        site_rows=_chk_n(site_rows, "site_rows", f64, T * S * 16), sun=_chk_n(sun, "sun", f64, T * 4),
+        limb_radius=float(limb_radius), shadow_radius=float(shadow_radius), site_moving=int(site_moving), sunlit_only=int(sunlit_only),
+        seen_by=_chk(seen, "seen_by", torch.uint8) if want_seen_by else None, reserved=0)
+    p.base = _lib.ssa_screen_params(n=n, n_time=T, n_site=S, step=float(step), min_alt=float(min_alt),
+                                    first=int(first), max_gap=int(max_gap), elements=_chk(elements, "elements"), trans=_chk(trans, "trans"),
+                                    sites=_chk(sites, "sites"), accept=_chk(accept, "accept", torch.uint8),
+                                    worst_gap=_chk(gap, "worst_gap", torch.int32) if want_gap else None,
+                                    flags=_chk(flags, "flags", torch.uint8) if want_flags else None)
+    _lib.check(lib.ssa_catalogue_screen_network_f64(C.byref(p), _stream()), "ssa_catalogue_screen_network_f64")
+    if not (want_gap or want_flags or want_seen_by):
+        return accept
+    return (accept,) + ((gap,) if want_gap else ()) + ((flags,) if want_flags else ()) + ((seen,) if want_seen_by else ())
+
+
 def observe(x_true, x, P, obs=None, metrics=None):
     """O1/O2: observations() + error() -> obs[n,12], metrics[4,n]."""
     lib = _lib.load()
