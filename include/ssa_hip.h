@@ -1020,6 +1020,63 @@ typedef struct ssa_screen_network_params {
 } ssa_screen_network_params;
 int ssa_catalogue_screen_network_f64(const ssa_screen_network_params *p, void *stream);
 
+/* ---------------------------------------------------------------- the pass table of a sensor network: a whole episode in one launch
+ * EXTENSION (ABI 23, additive; no reference counterpart).  The visibility test of every fused kernel is judged on the TRUE state, and
+ * the truth chain x_true[i + 1] = propagate(x_true[i], dt) depends on no action, no noise draw and no filter: which sensor can see
+ * which object at which step of the rest of an episode is known when the episode starts.  This entry produces all of it, under the
+ * network's own rule, in one launch.
+ * Inputs: of ssa_step_params the fields a lookahead reads -- x_true_in, trans, env_time, time_offset, n_time, n_obj, n_env, obj_ids,
+ * site_rows, limb_radius, site_moving and, the only launch_mask bit honoured, SSA_LAUNCH_INLINE_ENVS with inline_time (as
+ * ssa_lookahead_f64); of ssa_sensor_params n_sensor, enu, obs_itrs, obs_limit, sun, shadow_radius, sunlit_only; of ssa_consts dt,
+ * propagator, j2, r_eq, rk4_substeps; T = n_steps.  For h = 0 .. T-1, env e, sensor s and object j:
+ *   x_{h+1}  the truth after h + 1 CHAINED propagations by dt with the env's propagator -- the chain the step kernels run, not one
+ *            propagation by (h + 1) dt.  Every SSA_PROP_* value, through the device functions of the stand-alone operators
+ *            (ssa_propagate_f64 / ssa_propagate_j2_f64), which are the ones the step kernels run on a healthy state;
+ *   row      time_row(env_time[e] + time_offset + h, n_time) (inline_time[e] with SSA_LAUNCH_INLINE_ENVS): the row of `trans`, of the
+ *            Sun table and of site_rows alike;
+ *   access(h, e, s, j), the fused kernels' verdict for sensor s on x_{h+1}:
+ *            a ground sensor      elevation (hx_aer_erfa from enu[s] / obs_itrs[s]) >= obs_limit[s];
+ *            a site_moving sensor the line of sight from row (row, s) of site_rows clear of the sphere limb_radius (obs_limit not read);
+ *            a sunlit_only bit    additionally the object outside the Earth's cylindrical shadow, and for a ground sensor bit s of
+ *                                 the row's dark word;
+ *            a NaN anywhere       0.
+ * The filter's status and ssa_consts.update_interval do NOT enter: a forecast's visible[h] == access[h] AND (the update would be
+ * attempted -- the filter has not failed, the step is not one the update_interval skips).
+ * Outputs, in the caller's object numbering (obj_ids honoured per env: a storage layout never shows), E = n_env, S = n_sensor,
+ * m = n_obj, W = ceil(T / 64):
+ *   bits   uint64 [E][S][m][W], required, 8-byte aligned: bit (h mod 64) of word (h div 64) of row (e, s, j) is access(h, e, s, j);
+ *          bits at h >= T are 0.  Packed along TIME, per object: the mask of step k is (bits[..., k / 64] >> (k % 64)) & 1.
+ *   pass   int32 [E][S][m][4] or NULL, over the steps counted: first (smallest h with the bit set, -1: none), length (consecutive set
+ *          bits from `first`), count (set bits), passes (maximal runs of set bits).
+ *   n_left const int32 [E] device words or NULL: env e counts only h < min(T, n_left[e]) (a value < 0 counts as 0); later bits are
+ *          0.  NULL: T for every env.
+ *   env_sel / n_sel: const int32 [n_sel] device words, or NULL with n_sel == 0 (= every env).  Only the named envs are computed and
+ *          only their slabs of bits / pass are written; every other byte is left as it is (a vector env refreshes the envs that
+ *          have just auto-reset).  A word outside 0 .. n_env - 1 names no env: nothing is computed or written for it.
+ * Nothing else is written: no ring slot, status word, record, statistic or observation; z_noise, x_in, P_in and status are not read,
+ * nor of ssa_sensor_params angles_only, R, action, zn_stride_sensor, upd.  Any n_env >= 1 and any n_obj (every env starts on a wavefront
+ * boundary; no whole-tile rule).  One launch.
+ * Refused before any launch, SSA_E_INVALID, in this order: a NULL block; n_obj < 1 or n_env < 1; NULL x_true_in, trans or env_time;
+ * SSA_LAUNCH_INLINE_ENVS with n_env > SSA_INLINE_ENVS; an unknown propagator (SSA_PROP_J2_RK4: rk4_substeps outside 1 .. 4096);
+ * n_sensor outside 1 .. SSA_MAX_SENSORS; a NaN elevation mask; n_steps < 1; NULL or misaligned bits; n_sel < 0; n_sel > 0 with a NULL
+ * env_sel; n_sel > n_env; n_env * n_sensor * n_obj * W >= 2^31; and, behind all of these, the rules of the sensor tail for sunlit_only
+ * (ssa_sensor_params) and site_moving (ssa_step_params) as every sensor entry applies them.  ssa_consts.obs_type is read by the
+ * site_moving rule alone (a moving sensor needs SSA_OBS_AER, as everywhere) and is not judged otherwise. */
+typedef struct ssa_access_params {
+    int32_t n_steps;          /* T >= 1 */
+    int32_t n_sel;            /* 0: every env; else the number of words of env_sel */
+    uint64_t *bits;           /* [E][S][m][W] */
+    int32_t *pass;            /* [E][S][m][4] (first, length, count, passes) or NULL */
+    const int32_t *n_left;    /* [E] or NULL */
+    const int32_t *env_sel;   /* [n_sel] or NULL */
+} ssa_access_params;
+#define SSA_PASS_FIRST 0
+#define SSA_PASS_LENGTH 1
+#define SSA_PASS_COUNT 2
+#define SSA_PASS_PASSES 3
+int ssa_access_sensors_f64(const ssa_consts *c, const ssa_step_params *p, const ssa_sensor_params *sites,
+                           const ssa_access_params *a, void *stream);
+
 /* ------------------------------------------------ all-gather by direct peer stores (SURVEY 8e "Collective")
  * The reference runs one env per process and has no exchange step; the sharded env of this library (one env's objects spread over the
  * GPUs of a node) reassembles every step's observation block + statistics words on every rank.  These two entry points do that without a

@@ -10,6 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "ssa_kernels.hip")
 DEPS = [SRC, os.path.join(HERE, "csrc", "ssa_math.hpp"), os.path.join(HERE, "csrc", "ssa_conics.hpp"),
         os.path.join(HERE, "csrc", "ssa_screen.hpp"), os.path.join(HERE, "csrc", "ssa_screen_body.hpp"),
+        os.path.join(HERE, "csrc", "ssa_access.hpp"),
         os.path.join(os.path.dirname(HERE), "include", "ssa_hip.h")]
 LIB = os.path.join(HERE, "libssa_hip.so")
 ARCH = "gfx950"

@@ -116,6 +116,11 @@ class ssa_screen_network_params(C.Structure):
     ]
 
 
+class ssa_access_params(C.Structure):
+    # (`pass_`: the header's field `pass`, a keyword here)
+    _fields_ = [("n_steps", C.c_int32), ("n_sel", C.c_int32), ("bits", c_dp), ("pass_", c_dp), ("n_left", c_dp), ("env_sel", c_dp)]
+
+
 # constants of include/ssa_hip.h
 E_INVALID, E_LAUNCH, E_UNSUPPORTED = -1, -2, -3
 ABI_VERSION = 23
@@ -143,6 +148,7 @@ MAX_SENSORS = 8
 MAX_PLAN_SLOTS = 64
 LOOK_NSCORE, LOOK_TRACE_GAIN, LOOK_POS_TRACE_GAIN, LOOK_INFO_GAIN = 3, 0, 1, 2
 DRY_STRIDE, DRY_ACTION, DRY_VISIBLE, DRY_TAKEN, DRY_STATUS, DRY_SCORE, DRY_SPARE = 8, 0, 1, 2, 3, 4, 7
+PASS_FIRST, PASS_LENGTH, PASS_COUNT, PASS_PASSES = range(4)
 STAT_STRIDE, STAT_MAX_DPOS, STAT_CNT_LT_1E4, STAT_CNT_LT_1E7, STAT_ARGMAX_SPOS, STAT_N_FAILED, STAT_MAX_SPOS = 8, 0, 1, 2, 3, 4, 5
 
 # every symbol the header declares, with its ctypes signature
@@ -223,6 +229,8 @@ SIGNATURES = {
     "ssa_chi2_contained_f64": (C.c_int, [c_dp, C.c_int64, C.c_double, C.c_double, c_dp, c_dp]),
     "ssa_catalogue_screen_f64": (C.c_int, [C.POINTER(ssa_screen_params), c_dp]),
     "ssa_catalogue_screen_network_f64": (C.c_int, [C.POINTER(ssa_screen_network_params), c_dp]),
+    "ssa_access_sensors_f64": (C.c_int, [C.POINTER(ssa_consts), C.POINTER(ssa_step_params), C.POINTER(ssa_sensor_params),
+                                         C.POINTER(ssa_access_params), c_dp]),
 }
 
 _lib = None

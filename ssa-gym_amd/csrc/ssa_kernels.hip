@@ -5278,6 +5278,8 @@ __global__ void __launch_bounds__(64) peer_wait_kernel(const unsigned long long*
 
 }  // namespace ssa
 
+#include "ssa_access.hpp"   // the pass table of a sensor network (needs time_row, env_time_of and the propagators above)
+
 // ============================================================================= C ABI
 using namespace ssa;
 
@@ -5322,11 +5324,16 @@ static int post_parts(int64_t n_obj, int32_t n_env)
     return (int)want;
 }
 // the checks of ssa_consts every fused launch shares: observation model, propagator, RK4 substeps
+// (the propagator's half alone: what an entry that forms no measurement judges -- ssa_access_sensors_f64)
+static bool propagator_ok(const ssa_consts* c)
+{
+    if (c->propagator != SSA_PROP_FG && c->propagator != SSA_PROP_ELEMENTS && c->propagator != SSA_PROP_J2_RK4 && c->propagator != SSA_PROP_HYBRID) return false;
+    return c->propagator != SSA_PROP_J2_RK4 || (c->rk4_substeps >= 1 && c->rk4_substeps <= 4096);
+}
 static bool consts_ok(const ssa_consts* c)
 {
     if (c->obs_type != SSA_OBS_AER && c->obs_type != SSA_OBS_XYZ) return false;
-    if (c->propagator != SSA_PROP_FG && c->propagator != SSA_PROP_ELEMENTS && c->propagator != SSA_PROP_J2_RK4 && c->propagator != SSA_PROP_HYBRID) return false;
-    return c->propagator != SSA_PROP_J2_RK4 || (c->rk4_substeps >= 1 && c->rk4_substeps <= 4096);
+    return propagator_ok(c);
 }
 // the tile kernels' grid: tiles per wavefront T = ceil(tiles / resident wavefront slots); G = ceil(tiles / T) wavefronts.  T = 1:
 // the one-tile instance, else the grid-stride walk.
@@ -6092,6 +6099,37 @@ int ssa_catalogue_screen_network_f64(const ssa_screen_network_params* q, void* s
     if (q->base.n == 0) return SSA_OK;
     hipLaunchKernelGGL(catalogue_screen_network_kernel, dim3(nblk(q->base.n, SSA_SCREEN_WAVES)), dim3(64 * SSA_SCREEN_WAVES), 0,
                        (hipStream_t)stream, *q);
+    return launch_status();
+}
+
+// the pass table of a sensor network (ssa_access.hpp).  The rules in the header's order; the shared ones through the functions every
+// sensor entry calls -- the sensor tail on a copy whose measurement kinds are cleared: this entry forms no measurement and does not judge them
+int ssa_access_sensors_f64(const ssa_consts* c, const ssa_step_params* p, const ssa_sensor_params* sp, const ssa_access_params* a, void* stream)
+{
+    if (!c || !p || !sp || !a) return SSA_E_INVALID;
+    if (p->n_obj <= 0 || p->n_env <= 0) return SSA_E_INVALID;
+    if (!p->x_true_in || !p->trans || !p->env_time) return SSA_E_INVALID;
+    if (!inline_envs_fit(p) || !propagator_ok(c)) return SSA_E_INVALID;
+    if (sites_ok(sp) != SSA_OK) return SSA_E_INVALID;
+    if (a->n_steps < 1 || !a->bits || ((uintptr_t)a->bits & 7) != 0) return SSA_E_INVALID;
+    if (a->n_sel < 0 || (a->n_sel > 0 && !a->env_sel) || a->n_sel > p->n_env) return SSA_E_INVALID;
+    const int64_t W = ((int64_t)a->n_steps + 63) / 64;
+    const int64_t rows = (int64_t)p->n_env * sp->n_sensor;      // (every product below is taken only once its factors are below 2^31)
+    if (p->n_obj >= ((int64_t)1 << 31) || !rows_fit(rows, 1) || !rows_fit(rows, p->n_obj) || !rows_fit(rows * p->n_obj, W)) return SSA_E_INVALID;
+    ssa_sensor_params tail = *sp;
+    tail.angles_only = 0;
+    if (!sensor_tail_ok(c, p, &tail)) return SSA_E_INVALID;
+    AccessK k;
+    k.p = *p;
+    k.p.launch_mask = p->launch_mask & SSA_LAUNCH_INLINE_ENVS;
+    k.s = idle_sites(sp);
+    k.a = *a;
+    k.dt = c->dt;
+    k.j2 = J2Params{c->j2, c->r_eq, c->rk4_substeps};
+    k.waves_per_env = (int32_t)((p->n_obj + 63) / 64);
+    const int64_t nsel = a->n_sel > 0 ? a->n_sel : p->n_env;      // (nsel <= n_env: the grid is below n_env * n_obj < 2^31 wavefronts)
+    hipStream_t s = (hipStream_t)stream;
+    with_prop(c->propagator, [&](auto P) { hipLaunchKernelGGL(access_sensors_kernel<P>, dim3((unsigned)(nsel * k.waves_per_env)), dim3(64), 0, s, k); });
     return launch_status();
 }
 

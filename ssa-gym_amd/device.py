@@ -549,6 +549,68 @@ def dryrun_sensors(consts, params, sensors, actions, n_steps, n_obj_caller, out=
     return out
 
 
+def access_words(n_steps):
+    """W: the 64-bit words per row of a pass table over n_steps steps"""
+    return (int(n_steps) + 63) // 64
+
+
+def access_sensors(consts, params, sensors, n_steps, bits=None, summary=None, n_left=None, env_sel=None, stream=None):
+    """the pass table of a sensor network on the device (ssa_access_sensors_f64), stateless: `params` a filled _lib.ssa_step_params (its
+    INPUT fields: x_true_in, trans, env_time, time_offset, n_time, n_obj, n_env, obj_ids and the moving sensors' tail), `sensors`
+    host.make_sensor_params().  bits: a contiguous CUDA int64 tensor of n_env * S * n_obj * W words to write (None: a new [n_env, S,
+    n_obj, W] one), W = access_words(n_steps); summary: a contiguous CUDA int32 tensor of n_env * S * n_obj * 4 words for (first, length,
+    count, passes), True for a new one, None / False for none; n_left: CUDA int32 [n_env] or None; env_sel: CUDA int32 words, the envs to
+    compute (every other env's slab of bits / summary is left as it is), or None for all.  Returns (bits, summary).  Nothing else is
+    written; no host sync."""
+    T, E, S, m = int(n_steps), int(params.n_env), int(sensors.n_sensor), int(params.n_obj)
+    W = access_words(T)
+    dev = torch.device("cuda")
+    if bits is None:
+        bits = torch.empty((E, S, m, W), dtype=torch.int64, device=dev)
+    if summary is True:
+        summary = torch.empty((E, S, m, 4), dtype=torch.int32, device=dev)
+    elif summary is False:
+        summary = None
+    a = _lib.ssa_access_params()
+    a.n_steps = T
+    a.bits = _chk_n(bits, "bits", torch.int64, E * S * m * W)
+    a.pass_ = _chk_n(summary, "summary", torch.int32, E * S * m * 4) or 0
+    a.n_left = _chk_n(n_left, "n_left", torch.int32, E) or 0
+    if env_sel is not None:
+        a.env_sel, a.n_sel = _chk(env_sel, "env_sel", torch.int32), int(env_sel.numel())
+    _lib.check(_lib.load().ssa_access_sensors_f64(C.byref(consts), C.byref(params), C.byref(sensors), C.byref(a), _stream(stream)),
+               "ssa_access_sensors_f64")
+    return bits, summary
+
+
+def access_mask(bits, k):
+    """the bool mask [..., S, m] of step k of a pass table `bits` [..., S, m, W] (int64 words, bit h mod 64 of word h div 64 = step h):
+    one shift-and-mask, no kernel of the library.  k: one step for the whole table, or one per entry of its LEADING axis (the envs of a
+    vector table [E, S, m, W], each at its own step: the words are gathered first)"""
+    import numpy as np
+    ks = np.asarray(k, dtype=np.int64)
+    if ks.size == 0 or ks.min() < 0 or ks.max() >= 64 * bits.shape[-1]:
+        raise _lib.SsaHipError("access_mask: step %r outside the table's %d words" % (k, bits.shape[-1]))
+    if ks.ndim == 0:
+        return ((bits[..., int(ks) >> 6] >> (int(ks) & 63)) & 1).to(torch.bool)
+    if ks.shape != (bits.shape[0],) or bits.dim() < 2:
+        raise _lib.SsaHipError("access_mask: one step per entry of the table's leading axis (%d), got %r" % (bits.shape[0], ks.shape))
+    lead = (-1,) + (1,) * (bits.dim() - 1)
+    at = torch.as_tensor(ks, device=bits.device)
+    words = bits.gather(-1, (at >> 6).view(lead).expand(bits.shape[:-1] + (1,))).squeeze(-1)
+    return ((words >> (at & 63).view(lead[:-1])) & 1).to(torch.bool)
+
+
+def access_unpack(bits, n_steps):
+    """a pass table `bits` [..., S, m, W] as the bool array [..., S, m, n_steps] (for small cases: one byte per cell)"""
+    T = int(n_steps)
+    if T < 0 or T > 64 * bits.shape[-1]:
+        raise _lib.SsaHipError("access_unpack: %d steps in %d words" % (T, bits.shape[-1]))
+    sh = torch.arange(64, dtype=torch.int64, device=bits.device)
+    cells = (bits.unsqueeze(-1) >> sh) & 1      # [..., W, 64]; an arithmetic shift: bit 63 comes out as -1 & 1 = 1
+    return cells.reshape(bits.shape[:-1] + (64 * bits.shape[-1],))[..., :T].to(torch.bool)
+
+
 def dryrun_totals(records, out=None):
     """the totals of a dry run's records [K, E, S, DRY_STRIDE] (contiguous CUDA float64, as dryrun_sensors leaves them) on the device
     (ssa_dryrun_totals_f64): [E, LOOK_NSCORE], per candidate and score column the sum of the taken slots' scores in slot order (k outer,

@@ -152,6 +152,7 @@ class HotPathEngine:
         self._look_se = None                            # output buffers of launch_lookahead_sensors_envs
         self._assign_envs_ws = None                     # (S, workspace) of launch_assign_sensors_envs
         self._fore_e = None                             # output buffers of launch_forecast_sensors_envs
+        self._access = None                             # ... and of launch_access_sensors: the pass table and its summary
         self._dry = {}                                  # launch_dryrun_sensors: per (B, K, S, W) its upload, gathered block and records
         self._dry_envs = {}                             # launch_dryrun_sensors_envs: per (E * B, K, S, W) its upload, gathered block and records
         self._pcache = {}
@@ -630,6 +631,15 @@ class HotPathEngine:
         p.time_offset, p.launch_mask = int(time_offset), 0
         return p
 
+    def _set_env_times(self, p, env_times):
+        """the envs' time words by value in the input block `p` of a query launch (SSA_LAUNCH_INLINE_ENVS); None: the engine's env_time0 words"""
+        if env_times is None:
+            return
+        if self.E > _lib.INLINE_ENVS:
+            raise _lib.SsaHipError("env_times: at most %d envs travel in the parameter block" % _lib.INLINE_ENVS)
+        p.inline_time[:self.E] = [int(v) for v in env_times]
+        p.launch_mask = _lib.LAUNCH_INLINE_ENVS
+
     def _launch_look(self, entry, attr, lead, prior_lead, out, slot_in, time_offset, stream, sensors=None, n_steps=None, env_times=None):
         """the launch of the lookahead family: entry ssa_X_f64 of method launch_X, its output buffers `attr` (_lookahead_out: score lead
         + [3], the prediction prior_lead + [6 ...]), the input block of history slot `slot_in`; env_times: the envs' time words by value
@@ -638,11 +648,7 @@ class HotPathEngine:
         o, res = self._lookahead_out("launch_" + entry[4:-4], attr, lead, prior_lead, out)
         p = self._lookahead_params(slot_in, time_offset)
         self._set_sites(p, sensors)
-        if env_times is not None:
-            if self.E > _lib.INLINE_ENVS:
-                raise _lib.SsaHipError("env_times: at most %d envs travel in the parameter block" % _lib.INLINE_ENVS)
-            p.inline_time[:self.E] = [int(v) for v in env_times]
-            p.launch_mask = _lib.LAUNCH_INLINE_ENVS
+        self._set_env_times(p, env_times)
         if n_steps is not None:
             o = _lib.ssa_forecast_params(n_steps=n_steps, out=o)
         blocks = (p, o) if sensors is None else (p, sensors, o)
@@ -735,6 +741,34 @@ class HotPathEngine:
             raise _lib.SsaHipError("launch_forecast_sensors_envs: n_steps must be >= 1, got %d" % H)
         return self._launch_look("ssa_forecast_sensors_envs_f64", "_fore_e", (H, self.E, int(sensors.n_sensor), self.m), (H, self.E, self.m), out,
                                  slot_in, time_offset, stream, sensors, n_steps=H, env_times=env_times)
+
+    def launch_access_sensors(self, slot_in, time_offset, sensors, n_steps, envs=None, n_left=None, summary=True, stream=None, env_times=None):
+        """enqueue the pass table of a sensor network (include/ssa_hip.h: ssa_access_sensors_f64): from the truth of history slot
+        `slot_in`, for each of T = n_steps chained steps -- time indices (env's time word) + time_offset .. + T - 1 -- which sensor of
+        `sensors` sees which object, by the fused kernels' own visibility rule (elevation mask, dark site, Earth shadow, line of sight
+        from orbit) and for every env of the engine, in ONE launch.  The filters do not enter: a failed filter's object is not masked out.
+        envs: the envs to compute (a sequence, or an int32 CUDA tensor: no host-to-device copy here) -- every other env's slab of the
+        tables is left as it is; None: all.  n_left: an int32 CUDA tensor [E], env e counts only its first min(T, n_left[e]) steps; None:
+        T.  env_times: as launch_lookahead's.  Nothing of the engine's state is read but x_true and nothing is written but the result:
+        {'bits': int64 [E, S, m, W] (W = ceil(T / 64); bit h mod 64 of word h div 64 = step h: device.access_mask /
+        device.access_unpack), 'pass': int32 [E, S, m, 4] (first, length, count, passes: _lib.PASS_*; None with summary=False)}, objects
+        at each env's own caller indices.  The tensors are this engine's, allocated on first use (again when S or W changes) and reused
+        by the next call.  Asynchronous, no host sync."""
+        T, S = int(n_steps), int(sensors.n_sensor)
+        if T < 1:
+            raise _lib.SsaHipError("launch_access_sensors: n_steps must be >= 1, got %d" % T)
+        shape = (self.E, S, self.m, device.access_words(T))
+        if self._access is None or tuple(self._access["bits"].shape) != shape:
+            self._access = {"bits": torch.zeros(shape, dtype=torch.int64, device=self.dev),
+                            "pass": torch.zeros(shape[:3] + (4,), dtype=torch.int32, device=self.dev)}
+        if envs is not None and not isinstance(envs, torch.Tensor):
+            envs = torch.as_tensor(np.asarray(envs, dtype=np.int32).reshape(-1)).to(self.dev)
+        p = self._lookahead_params(slot_in, time_offset)
+        self._set_sites(p, sensors)
+        self._set_env_times(p, env_times)
+        device.access_sensors(self.consts, p, sensors, T, bits=self._access["bits"], summary=self._access["pass"] if summary else None,
+                              n_left=n_left, env_sel=envs, stream=stream)
+        return {"bits": self._access["bits"], "pass": self._access["pass"] if summary else None}
 
     def launch_dryrun_sensors(self, slot_in, time_offset, sensors, actions, stream=None, gather=True):
         """enqueue the dry run of B candidate tasking schedules from history slot `slot_in` (include/ssa_hip.h: ssa_dryrun_sensors_envs_f64;

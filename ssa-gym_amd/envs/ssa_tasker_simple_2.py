@@ -246,6 +246,7 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         self._engine.fail_log[:] = 0.0             # (time index 0 = "not written": steps count from 1)
         self._ring_head = None
         self._argmax_sigma_prev = None
+        self._access_anchor = None      # (a new truth: action_masks() makes its table again)
         self.i = 0
         self._fetch_small(0)
         self.runtime['reset'] += time.time() - s
@@ -864,6 +865,51 @@ class SSA_Tasker_Env(_PolicyLoop, Env):
         if H < 1:
             raise ValueError("forecast_sensors: a horizon of at least one step, got %r" % (horizon,))
         return dict(e.launch_forecast_sensors(self.i % e.H, self.i + 1, self._sites(), H, out=want, stream=self._stream.cuda_stream))
+
+    _access_anchor = None      # (step index at which the pass table the engine holds was made, its steps; None: none since the last reset())
+
+    def access_sensors(self, horizon=None):
+        """The pass table of the network (no reference counterpart; include/ssa_hip.h: ssa_access_sensors_f64):
+        for each of the steps i+1 .. i+T -- T = min(horizon, steps - 1 - i), the whole rest of the episode by default -- which sensor
+        sees which object, by the visibility rule step() applies (elevation mask, dark site, Earth shadow, line of sight from orbit).
+        The truth does not depend on actions, noise or filters, so this is what step() WILL find, whatever is done until then; ONE
+        launch, no filter arithmetic, and nothing of the env changes.  A dict, objects in the env's own order, S = n_sensor (1 without
+        config['observers']: the env's own observer as a one-site network):
+            bits    [S, m, W] int64 CUDA, W = ceil(T / 64): bit h mod 64 of word h div 64 = step i + 1 + h (device.access_mask(bits, h),
+                    device.access_unpack(bits, T))
+            first, length, count, passes  [S, m] int32 CUDA: the first step seen (h; -1: never), the length of that first pass, the
+                    steps seen, the passes
+            n_steps T
+        A failed filter is NOT masked out (the table knows no filter): AND with the status where that is wanted --
+        lookahead_sensors()['visible'] == the mask AND (the update would be attempted).  The tensors are the engine's: the next call
+        overwrites them, and action_masks() reads them from now on."""
+        if self._engine is None:
+            raise _lib.SsaHipError("no device state: the pass table is made on the GPU only (no CPU fallback)")
+        T = self.n - 1 - self.i if horizon is None else min(int(horizon), self.n - 1 - self.i)
+        if T < 1:
+            raise ValueError("access_sensors: at least one step inside the episode (i = %d, steps = %d, horizon = %r)" % (self.i, self.n, horizon))
+        e = self._engine
+        r = e.launch_access_sensors(self.i % e.H, self.i + 1, self._sites(), T, stream=self._stream.cuda_stream)
+        self._access_anchor = (self.i, T)
+        p = r["pass"][0]
+        return {"bits": r["bits"][0], "first": p[..., _lib.PASS_FIRST], "length": p[..., _lib.PASS_LENGTH], "count": p[..., _lib.PASS_COUNT],
+                "passes": p[..., _lib.PASS_PASSES], "n_steps": T}
+
+    def action_masks(self):
+        """The action mask of the NEXT step: bool [S, m] on the device, True where sensor s will see object j at step i + 1 -- what
+        lookahead_sensors()['visible'] reports for every filter that has not failed, without the lookahead's UKF updates.  The pass
+        table is made by the first call after a reset() (access_sensors(): one launch over the rest of the episode); every later call
+        is one shift-and-mask of it (device.access_mask) and launches no kernel of the library.  It stays valid across step(),
+        rollout*(), run_agent*() and run_policy(): the truth does not depend on them.  A failed filter is not masked out: AND with the
+        status where wanted."""
+        from .. import device
+        if self.i + 1 >= self.n:
+            raise ValueError("action_masks: the episode has no next step (i = %d, steps = %d)" % (self.i, self.n))
+        a = self._access_anchor
+        if a is None or not (0 <= self.i - a[0] < a[1]):
+            self.access_sensors()
+            a = self._access_anchor
+        return device.access_mask(self._engine._access["bits"][0], self.i - a[0])
 
     def evaluate_schedules(self, actions, gather=True):
         """The dry run of B candidate tasking schedules (no reference counterpart; include/ssa_hip.h: ssa_dryrun_sensors_envs_f64;

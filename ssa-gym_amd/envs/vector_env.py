@@ -220,6 +220,8 @@ class SSA_Tasker_VecEnv:
         self._eng.z_noise[e].copy_(torch.randn(self._z_shape, dtype=torch.float64, device="cuda", generator=self._gen) * self._zs)
         self.i[e] = 0
         self.rewards_sum[e] = 0.0
+        if self._access_T is not None:      # (a new truth: action_masks() makes this env's slab of the pass table again)
+            self._access_stale = set(self._access_stale) | {e}
 
     def reset(self):
         slot = self.tick % 2
@@ -530,6 +532,58 @@ class SSA_Tasker_VecEnv:
         want = _engine.HotPathEngine.LOOKAHEAD_PARTS if covariances else ()
         r = self._launch_forecast_sensors(horizon, want)
         return {k: v.transpose(0, 1) for k, v in r.items()}
+
+    # the pass table of all envs: its steps, per env the step index it was made at and the steps it counts there,
+    # and the envs that have been reset since (their slabs are made again before a mask is formed); None: no table
+    _access_T, _access_anchor, _access_left, _access_stale = None, None, None, ()
+
+    def access_sensors(self, horizon=None, envs=None):
+        """SSA_Tasker_Env.access_sensors() of every env from ONE launch (ssa_access_sensors_f64): one table
+        [E, S, m, W] over T = min(horizon, steps - 1) steps (the whole episode by default), env e anchored at ITS step i_e and counting
+        min(T, steps - 1 - i_e) steps from there; later bits are 0.  envs: only these envs are made again (one launch, the others'
+        slabs and anchors stay); a table of another T is made for all.  The single env's dict with a leading [n_env] axis -- bits
+        [E, S, m, W] int64, first / length / count / passes [E, S, m] int32, CUDA, objects in each env's own order -- and n_steps, the
+        int64 [E] steps each env counts.  Nothing of the envs changes; the tensors are the engine's, and action_masks() reads them."""
+        import torch
+        if self._eng is None:
+            raise _lib.SsaHipError("no device state: the pass table is made on the GPU only (no CPU fallback)")
+        T = self.n - 1 if horizon is None else min(int(horizon), self.n - 1)
+        if T < 1:
+            raise ValueError("access_sensors: a horizon of at least one step inside the episode, got %r (steps = %d)" % (horizon, self.n))
+        if envs is None or self._access_T != T:
+            sel = np.arange(self.E)
+            self._access_T, self._access_anchor, self._access_left = T, np.zeros(self.E, dtype=np.int64), np.zeros(self.E, dtype=np.int64)
+        else:
+            sel = np.unique(np.asarray(envs, dtype=np.int64).reshape(-1))
+            if len(sel) == 0 or sel[0] < 0 or sel[-1] >= self.E:
+                raise ValueError("access_sensors: envs must name envs in 0 .. %d, got %r" % (self.E - 1, envs))
+        self._access_anchor[sel] = self.i[sel]
+        self._access_left[sel] = np.minimum(T, self.n - 1 - self.i[sel])
+        words = env_time_words(self, "access_sensors")
+        with torch.cuda.stream(self._tasking_stream()):
+            left = torch.as_tensor(self._access_left.astype(np.int32)).to("cuda")
+            r = self._eng.launch_access_sensors(self.tick % 2, 0, self._sites(), T, envs=None if len(sel) == self.E else sel, n_left=left, **words)
+        self._access_stale = set(self._access_stale) - set(int(v) for v in sel)
+        p = r["pass"]
+        return {"bits": r["bits"], "first": p[..., _lib.PASS_FIRST], "length": p[..., _lib.PASS_LENGTH], "count": p[..., _lib.PASS_COUNT],
+                "passes": p[..., _lib.PASS_PASSES], "n_steps": self._access_left.copy()}
+
+    def action_masks(self):
+        """The action masks of the NEXT step of every env: bool [E, S, m] on the device (SSA_Tasker_Env.action_masks() per env).  The
+        table is made by the first call (access_sensors(): one launch over whole episodes); afterwards a call is one gather and one
+        shift-and-mask of it, and launches a kernel of the library only when envs have auto-reset since the last call -- those envs'
+        slabs are then made again, all in ONE launch.  A failed filter is not masked out."""
+        from .. import device
+        if np.any(self.i + 1 >= self.n):
+            raise ValueError("action_masks: an env has no next step")
+        if self._access_T is None:
+            self.access_sensors()
+        else:
+            k = self.i - self._access_anchor
+            stale = sorted(set(self._access_stale) | set(np.where((k < 0) | (k >= self._access_left))[0].tolist()))
+            if stale:
+                self.access_sensors(self._access_T, envs=stale)
+        return device.access_mask(self._eng._access["bits"], self.i - self._access_anchor)
 
     def evaluate_schedules(self, actions):
         """SSA_Tasker_Env.evaluate_schedules() of every env from ONE dry-run launch (ssa_dryrun_gather_f64, then
